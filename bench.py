@@ -2,7 +2,7 @@
 """Headline benchmark: atom-steps/s of the MTP force call on a 64k-atom BCC W crystal with
 the level-16 potential (BASELINE.json configs[1]) on N MI355X of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one force call on positions already resident in HBM: zero the force array,
@@ -12,10 +12,16 @@ spatial domain decomposition (strong scaling, as BASELINE.json's metric asks); t
 the library's own (mtp_halo_*: device pack / unpack + one grouped RCCL send/recv per
 direction on its own stream) and the owned atoms run as interior | boundary | interior row
 ranges so both exchanges overlap force work -- no torch collective in the timed loop.
-Rank 0 prints one JSON line; `roofline` prices the dominant kernel against the bound that governs
-it (fp64 vector issue: the reference algorithm's flop count F_alg of SURVEY.md section 8d over the
-kernel time measured here), with the HBM side (algorithmic bytes, counter traffic) in its `hbm`
-sub-block, and `cpu_baseline` times the CPU oracle on this box's host cores in the same run.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline (`value`, `ms_per_step`, ...).  `--dump-outputs DIR` (one GPU) writes what the last timed
+step computed -- forces, the {energy, virial} tallies of that step, and with `--workload grades` the
+grades -- as DIR/<name>.npy in float64; the inputs are seeded, so equal arguments give equal inputs.
+`--full` adds the measurements that take runs of their own: `roofline` prices the dominant kernel
+against the bound that governs it (fp64 vector issue: the reference algorithm's flop count F_alg of
+SURVEY.md section 8d over the kernel time measured here), with the HBM side (algorithmic bytes,
+counter traffic) in its `hbm` sub-block; `cpu_baseline` times the CPU oracle on the host's cores in
+the same run; `whole_step` times the device-resident MD loop; `config.device_list_build_ms` times
+the device neighbour-list build.
 N > 1 with a failing library halo exits non-zero (no silent second path; MTP_BENCH_HALO=torch
 runs the torch twin on purpose).
 """
@@ -32,6 +38,21 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6   # vendor vector fp64 peak
+DUMP_BYTES_MAX = 63_000_000    # array bytes --dump-outputs writes at most (under 64 MB with the .npy headers)
+
+
+def dump_outputs(folder, arrays):
+    """Writes each array as <folder>/<name>.npy in float64.  When they hold more than DUMP_BYTES_MAX in all, every per-atom
+    array (more than 1024 rows) keeps a fixed, seeded sample of its rows, so runs with the same arguments still compare."""
+    os.makedirs(folder, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    big = sum(a.nbytes for a in arrays.values() if len(a) > 1024)
+    small = sum(a.nbytes for a in arrays.values()) - big
+    for name, a in arrays.items():
+        if small + big > DUMP_BYTES_MAX and len(a) > 1024:
+            keep = len(a) * (DUMP_BYTES_MAX - small) // big
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(folder, name + ".npy"), a)
 
 
 def algorithmic_bytes(nlist_entries, nall, nlocal):
@@ -93,7 +114,13 @@ def main():
                          "-- for launch-bound sizes (a caller like LAMMPS can do the same around mtp_compute_device)")
     ap.add_argument("--no-whole-step", action="store_true", help="skip the device-resident MD loop (whole-step time)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's forces, energy/virial (and grades) as DIR/<name>.npy (one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline pass, the CPU baseline, the device list build and the whole MD step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -123,6 +150,8 @@ def main():
         if world == 1 and args.gpus > 1:
             raise SystemExit("launch N>1 with: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N")
         args.gpus = world
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs writes one GPU's outputs: run it with --gpus 1")
     assert torch.cuda.is_available(), "bench.py needs MI355X GPUs (no CPU fallback)"
     backend = os.environ.get("MTP_BENCH_BACKEND", "nccl")   # "gloo": rehearsal of N > 1 on a single GPU
     devidx = local_rank % torch.cuda.device_count()
@@ -268,13 +297,23 @@ def main():
             run_step()
         ctx.synchronize(stream)
     ev.zero_()
+    # ev accumulates over the steps: with --dump-outputs a copy taken before the last step gives that step's tallies
+    ev_prev = torch.zeros_like(ev) if args.dump_outputs else None
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         run_step()
+    if ev_prev is not None:
+        ev_prev.copy_(ev)
+    run_step()
     t_issue = time.perf_counter() - t0      # the host's share: when this approaches dt the GPU waits for launches
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        out = {"forces": f, "energy_virial": (ev - ev_prev)[:7]}
+        if grade:
+            out.update(grades=grades_t, max_grade=maxg_t)
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()})
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -287,60 +326,61 @@ def main():
     ctx.synchronize(stream)
     energy_per_atom = float(ev[0].item()) / args.steps / natoms
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream, separate pass -----------
-    ctx.set_timing(True)
-    kms = []
-    for _ in range(min(args.steps, 50)):
-        f.zero_()
-        ctx.compute_device(x, ty, f, eflag=EFLAG, vflag=VFLAG, ev_t=ev, stream=stream, grade=grade,
-                           grades_t=grades_t, maxg_t=maxg_t)
-        kms.append(ctx.last_kernel_ms())
-    ctx.set_timing(False)
-    kernel_ms = float(np.mean(kms))
+    if args.full:
+        # ---- roofline of the dominant kernel: HIP events on the launch stream, separate pass -----------
+        ctx.set_timing(True)
+        kms = []
+        for _ in range(min(args.steps, 50)):
+            f.zero_()
+            ctx.compute_device(x, ty, f, eflag=EFLAG, vflag=VFLAG, ev_t=ev, stream=stream, grade=grade,
+                               grades_t=grades_t, maxg_t=maxg_t)
+            kms.append(ctx.last_kernel_ms())
+        ctx.set_timing(False)
+        kernel_ms = float(np.mean(kms))
 
-    # in-cutoff pair count of this rank (for the reference flop model), on the device
-    with torch.no_grad():
-        cnt = torch.diff(fi.long())
-        row = torch.repeat_interleave(il.long(), cnt)
-        d = x[ne.long()] - x[row]
-        jc_total = int(((d * d).sum(1) <= pot.info.max_cutoff ** 2).sum().item())
-    bytes_alg = algorithmic_bytes(int(plan.first[-1]), plan.nall, plan.nlocal)
-    flops_ref = algorithmic_flops_reference(sizes, jc_total, plan.nlocal)
-    achieved_gbs = bytes_alg / (kernel_ms * 1e-3) / 1e9
-    # rocprofv3 PMC counters of the dominant kernel (scripts/gpu_pmc.sh -> profiles/r02_pmc_counters.json): only quoted when
-    # they were collected from THIS build of the kernels (source hash) on this workload; per launch, like `achieved`
-    traffic, pmc_block = None, None
-    suffix = "" if args.workload == "w16" else "_" + args.workload
-    cpath = next((c for c in (os.path.join(ROOT, "profiles", "r%02d_pmc_counters%s.json" % (r, suffix)) for r in (3, 2))
-                  if os.path.exists(c)), "")
-    if cpath and world == 1:
-        try:
-            pc = json.load(open(cpath))
-            if pc.get("source_hash") == capi.kernel_source_hash() and pc.get("workload") == args.workload \
-                    and pc.get("cells", 32) == args.cells:
-                cn = pc["counters"]
-                traffic = pc.get("hbm_bytes_per_launch")
-                # kernel duration in shader cycles from the same counters: the wavefronts of the persistent grid live for the
-                # whole launch, SQ_WAVE_CYCLES counts quad-cycles (MI355X_MICROARCH.md)
-                ncu = 256
-                cyc = cn["SQ_WAVE_CYCLES"] * 4.0 / cn["SQ_WAVES"]
-                pmc_block = {
-                    "replayed": True,   # NOT measured in this run: read from the committed rocprofv3 collection below
-                    "source": "profiles/%s (same kernel sources: %s)" % (os.path.basename(cpath), pc["source_hash"][:12]),
-                    "lds_busy": cn["SQ_LDS_IDX_ACTIVE"] / ncu / cyc,                       # LDS pipe cycles / kernel cycles, per CU
-                    "lds_bank_conflict_share": cn["SQ_LDS_BANK_CONFLICT"] / max(cn["SQ_LDS_IDX_ACTIVE"], 1.0),
-                    "valu_busy": cn["SQ_ACTIVE_INST_VALU"] * 4.0 / (4 * ncu) / cyc,         # quad-cycles of VALU issue per SIMD
-                    "kernel_cycles": cyc, "clock_ghz_under_profiler": cyc / (kernel_ms * 1e-3) / 1e9,
-                    "lds_wave_instructions": cn["SQ_INSTS_LDS"], "valu_wave_instructions": cn["SQ_INSTS_VALU"],
-                    "waves_per_cu": cn["SQ_WAVES"] / ncu,
-                }
-        except Exception:
-            traffic, pmc_block = None, None
+        # in-cutoff pair count of this rank (for the reference flop model), on the device
+        with torch.no_grad():
+            cnt = torch.diff(fi.long())
+            row = torch.repeat_interleave(il.long(), cnt)
+            d = x[ne.long()] - x[row]
+            jc_total = int(((d * d).sum(1) <= pot.info.max_cutoff ** 2).sum().item())
+        bytes_alg = algorithmic_bytes(int(plan.first[-1]), plan.nall, plan.nlocal)
+        flops_ref = algorithmic_flops_reference(sizes, jc_total, plan.nlocal)
+        achieved_gbs = bytes_alg / (kernel_ms * 1e-3) / 1e9
+        # rocprofv3 PMC counters of the dominant kernel (scripts/gpu_pmc.sh -> profiles/r02_pmc_counters.json): only quoted when
+        # they were collected from THIS build of the kernels (source hash) on this workload; per launch, like `achieved`
+        traffic, pmc_block = None, None
+        suffix = "" if args.workload == "w16" else "_" + args.workload
+        cpath = next((c for c in (os.path.join(ROOT, "profiles", "r%02d_pmc_counters%s.json" % (r, suffix)) for r in (3, 2))
+                      if os.path.exists(c)), "")
+        if cpath and world == 1:
+            try:
+                pc = json.load(open(cpath))
+                if pc.get("source_hash") == capi.kernel_source_hash() and pc.get("workload") == args.workload \
+                        and pc.get("cells", 32) == args.cells:
+                    cn = pc["counters"]
+                    traffic = pc.get("hbm_bytes_per_launch")
+                    # kernel duration in shader cycles from the same counters: the wavefronts of the persistent grid live for the
+                    # whole launch, SQ_WAVE_CYCLES counts quad-cycles (MI355X_MICROARCH.md)
+                    ncu = 256
+                    cyc = cn["SQ_WAVE_CYCLES"] * 4.0 / cn["SQ_WAVES"]
+                    pmc_block = {
+                        "replayed": True,   # NOT measured in this run: read from the committed rocprofv3 collection below
+                        "source": "profiles/%s (same kernel sources: %s)" % (os.path.basename(cpath), pc["source_hash"][:12]),
+                        "lds_busy": cn["SQ_LDS_IDX_ACTIVE"] / ncu / cyc,                       # LDS pipe cycles / kernel cycles, per CU
+                        "lds_bank_conflict_share": cn["SQ_LDS_BANK_CONFLICT"] / max(cn["SQ_LDS_IDX_ACTIVE"], 1.0),
+                        "valu_busy": cn["SQ_ACTIVE_INST_VALU"] * 4.0 / (4 * ncu) / cyc,         # quad-cycles of VALU issue per SIMD
+                        "kernel_cycles": cyc, "clock_ghz_under_profiler": cyc / (kernel_ms * 1e-3) / 1e9,
+                        "lds_wave_instructions": cn["SQ_INSTS_LDS"], "valu_wave_instructions": cn["SQ_INSTS_VALU"],
+                        "waves_per_cu": cn["SQ_WAVES"] / ncu,
+                    }
+            except Exception:
+                traffic, pmc_block = None, None
 
     # ---- CPU baseline: the oracle (a port of the reference CPU path), rank 0, N = 1 -----------------
     # leg (i) one thread; leg (ii) every host core: threads over atoms adding into one force array (oracle/mtp_oracle_mt.c)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.pyoracle import Oracle
         o = Oracle(args.potential, selection=grade)
         xs = plan.x0
@@ -382,7 +422,7 @@ def main():
 
     # device-resident neighbour-list build, informational: same atoms, same cutoff, own context
     list_build_ms = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         cnb = capi.Context(pot, devidx)
         xh = plan.x0
         lo, hi = xh.min(0) - 1e-9, xh.max(0) + 1e-9
@@ -400,7 +440,7 @@ def main():
     # kick + drift, ghost refresh, force call (same flags as above), ghost-force fold, kick; every 10th step the
     # ghost images and the neighbour list are rebuilt on the device (lammps_mtp_kokkos_amd/md.py)
     whole = None
-    if rank == 0 and world == 1 and not grade and not args.no_whole_step:
+    if rank == 0 and world == 1 and args.full and not grade and not args.no_whole_step:
         from lammps_mtp_kokkos_amd.md import DeviceNVE, MVV2E
         ctx_md = capi.Context(pot, devidx)
         ctx_md.set_variant(dict(auto=0, large=1, small=2)[args.variant])
@@ -452,30 +492,33 @@ def main():
                             ", one stream: pack, forward exchange, all rows in one launch, reverse exchange, unpack")))
                        if decomposed else ("single GPU, step replayed from a HIP graph" if run_step is not step else "single GPU"),
                        "atoms_rank0": plan.nlocal, "ghosts_rank0": plan.nghost, "list_entries_rank0": int(plan.first[-1]),
-                       "in_cutoff_pairs_rank0": jc_total, "launch": info, "halo_schedule_probe": schedule_probe,
-                       "device_list_build_ms": list_build_ms,
+                       "launch": info, "halo_schedule_probe": schedule_probe,
                        # host time to ENQUEUE a step (python -> ctypes -> HIP launches), rank 0: the GPU waits for the
                        # host when this approaches ms_per_step
                        "host_issue_ms_per_step": t_issue / args.steps * 1e3},
-            # The governing bound of the fused kernel is fp64 vector issue, so that is what `achieved` /
-            # `peak` / `frac` price: the REFERENCE algorithm's flop count F_alg per launch over the kernel time measured
-            # here with HIP events.  The HBM side (the contract's default bound) is the `hbm` sub-block: algorithmic bytes
-            # over the same time, and the counter traffic beside it.
-            "roofline": {"bound": "fp64_valu", "achieved": flops_ref / (kernel_ms * 1e-3) / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": flops_ref / (kernel_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
-                         "traffic": traffic,
-                         "kernel": "mtp_wave_kernel", "kernel_ms": kernel_ms, "reference_flops_per_launch": flops_ref,
-                         "note": "achieved = SURVEY.md 8d F_alg (flops of the reference algorithm, not instructions executed: the "
-                                 "native kernel never forms the per-pair Jacobian) / kernel time by HIP events in this run; "
-                                 "traffic = HBM bytes per launch from rocprofv3 counters (replayed from profiles/, see pmc)",
-                         "hbm": {"achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS,
-                                 "algorithmic_bytes": bytes_alg, "traffic": traffic,
-                                 "traffic_ratio": (traffic / bytes_alg) if traffic else None},
-                         "pmc": pmc_block},
-            "cpu_baseline": cpu,
-            "whole_step": whole,
             "energy_per_atom_eV": energy_per_atom,
         }
+        if args.full:
+            line["config"].update(in_cutoff_pairs_rank0=jc_total, device_list_build_ms=list_build_ms)
+            line.update({
+                # The governing bound of the fused kernel is fp64 vector issue, so that is what `achieved` /
+                # `peak` / `frac` price: the REFERENCE algorithm's flop count F_alg per launch over the kernel time measured
+                # here with HIP events.  The HBM side (the contract's default bound) is the `hbm` sub-block: algorithmic bytes
+                # over the same time, and the counter traffic beside it.
+                "roofline": {"bound": "fp64_valu", "achieved": flops_ref / (kernel_ms * 1e-3) / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
+                             "unit": "TFLOP/s", "frac": flops_ref / (kernel_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
+                             "traffic": traffic,
+                             "kernel": "mtp_wave_kernel", "kernel_ms": kernel_ms, "reference_flops_per_launch": flops_ref,
+                             "note": "achieved = SURVEY.md 8d F_alg (flops of the reference algorithm, not instructions executed: the "
+                                     "native kernel never forms the per-pair Jacobian) / kernel time by HIP events in this run; "
+                                     "traffic = HBM bytes per launch from rocprofv3 counters (replayed from profiles/, see pmc)",
+                             "hbm": {"achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS,
+                                     "algorithmic_bytes": bytes_alg, "traffic": traffic,
+                                     "traffic_ratio": (traffic / bytes_alg) if traffic else None},
+                             "pmc": pmc_block},
+                "cpu_baseline": cpu,
+                "whole_step": whole,
+            })
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     halo = None          # the RCCL communicator goes before the process group and the HIP runtime do
     if world > 1:

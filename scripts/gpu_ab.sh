@@ -15,7 +15,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for cfg in "$@"; do
     i=$((i+1))
     envs=""; [ "$cfg" != "-" ] && envs="$cfg"
-    env $envs timeout -k 10 200 python bench.py --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline $BENCH_ARGS > $OUT/b${i}_$r.json 2> $OUT/b${i}_$r.err
+    env $envs timeout -k 10 200 python bench.py --full --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline $BENCH_ARGS > $OUT/b${i}_$r.json 2> $OUT/b${i}_$r.err
     python - <<PY
 import json
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC counter passes for the dominant kernel (separate rocprofv3 runs, --kernel-trace only, as the guide prescribes)
 # plus a --stats pass; writes $OUT/pmc_counters.json (per-launch means, tagged with the kernel source hash) and
-# $OUT/kernel_stats.csv -- copy both into profiles/ to have bench.py quote them.
+# $OUT/kernel_stats.csv -- copy both into profiles/ to have bench.py --full quote them.
 #   bash scripts/gpu_pmc.sh TAG [bench.py args, e.g. --workload wre20]
 OUT=gpurun_out/${1:-pmc}; shift
 ARGS="$@"
@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { tail -20 $OUT/build.log; exit 1; }
 run() {
   name=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline $ARGS > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline $ARGS > $OUT/$name.json 2> $OUT/$name.err
   echo "$name rc=$?"
 }
 run sq1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
@@ -20,7 +20,7 @@ run tcc1 FETCH_SIZE
 run tcc2 WRITE_SIZE
 run tcc3 TCC_HIT_sum TCC_MISS_sum TCC_EA0_ATOMIC_sum
 run mfma SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline $ARGS > $OUT/stats.json 2> $OUT/stats.err; echo "stats rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $ARGS > $OUT/stats.json 2> $OUT/stats.err; echo "stats rc=$?"
 find $OUT/stats -name "*kernel_stats.csv" | head -1 | xargs -r -I{} cp {} $OUT/kernel_stats.csv
 head -8 $OUT/kernel_stats.csv
 python - <<PY

@@ -10,7 +10,7 @@ i=0
 for cfg in "${CFGS[@]}"; do
   i=$((i+1))
   [ "$cfg" != "-" ] && export $cfg
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT/c$i -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-whole-step "$@" > $OUT/c$i.json 2> $OUT/c$i.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT/c$i -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-whole-step "$@" > $OUT/c$i.json 2> $OUT/c$i.err
   echo "[$cfg] rc=$?"
   [ "$cfg" != "-" ] && unset ${cfg%%=*}
   python - <<PY

@@ -8,7 +8,7 @@ python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { ta
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"
 tail -8 $OUT/pytest_gpu.log
 shift
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 try:

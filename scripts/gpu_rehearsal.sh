@@ -12,7 +12,7 @@ for c in 16 20 25 32; do
   for mode in plain self self_overlap; do
     envs="A=1"; [ $mode = self ] && envs="MTP_BENCH_SELF_HALO=1"; [ $mode = self_overlap ] && envs="MTP_BENCH_SELF_HALO=1 MTP_BENCH_HALO_OVERLAP=1"
     for rep in 1 2; do
-      env $envs timeout -k 10 200 python bench.py --cells $c --steps 300 --warmup 20 --no-cpu-baseline --no-whole-step > $OUT/sh$rep.json 2> $OUT/sh.err
+      env $envs timeout -k 10 200 python bench.py --full --cells $c --steps 300 --warmup 20 --no-cpu-baseline --no-whole-step > $OUT/sh$rep.json 2> $OUT/sh.err
     done
     [ $first = 1 ] || echo ',' >> $OUT/${TAG}_self_halo_rehearsal.json
     first=0

@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { tail -20 $OUT/build.log; exit 1; }
 envs=""; while [ "$1" != "--" ] && [ -n "$1" ]; do envs="$envs $1"; shift; done; shift
-env $envs timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-whole-step "$@" > $OUT/bench.json 2> $OUT/bench.err
+env $envs timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-whole-step "$@" > $OUT/bench.json 2> $OUT/bench.err
 echo rc=$?
 python - <<PY
 import csv, glob
