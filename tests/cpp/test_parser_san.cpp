@@ -4,8 +4,9 @@
 // -fsanitize=address,undefined by `make -C lammps_mtp_kokkos_amd/host san`; tests/test_sanitizers_cpu.py feeds it
 // every committed potential plus truncated and corrupted variants.  No GPU, no HIP runtime.
 //
-//   test_parser_san <file> <want_selection 0|1>      prints "OK B T S A C levels" or "ERR <code> <message>"
+//   test_parser_san <file> <want_selection 0|1>      prints "OK B T S A C levels sum err digest" or "ERR <code> <message>"
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -138,7 +139,48 @@ int main(int argc, char **argv)
   const double x[9] = {0, 0.5, 1, 1.5, 2, 2.5, 3, 3.5, 4}, g[3] = {0.1, 0.2, 0.3};
   mtp_mi355x::cfg_atom_lines(lines, 3, type, x, g, 5);
   sum += (long long) lines.size() + (long long) mtp_mi355x::log_extrapolation_mode(true, false, 2.0, 1e-5).size();
-  std::printf("OK %d %d %d %d %d %d %lld %.3e\n", pot.alpha_index_basic_count, pot.alpha_index_times_count, pot.alpha_scalar_count,
-              pot.alpha_moment_count, pot.coeff_count, pot.normal_levels, sum, prog_err);
+  // 64-bit FNV-1a digest of every field finalize writes (each vector: its length, then its bytes): two builds of the
+  // schedule builder that print the same digest for a potential hand the kernels byte-identical tables
+  uint64_t digest = 14695981039346656037ull;
+  auto hash_bytes = [&](const void *p, size_t n) {
+    for (size_t i = 0; i < n; i++) digest = (digest ^ ((const unsigned char *) p)[i]) * 1099511628211ull;
+  };
+  auto hash_vec = [&](const auto &v) {
+    const uint64_t n = v.size();
+    hash_bytes(&n, sizeof n);
+    hash_bytes(v.data(), v.size() * sizeof(v[0]));
+  };
+  hash_vec(pot.rows_by_level);
+  hash_vec(pot.level_offset);
+  hash_vec(pot.moment_perm);
+  hash_vec(pot.mapping_lds);
+  hash_vec(pot.basic_pack_lds);
+  hash_vec(pot.slot_of);
+  hash_bytes(&pot.slot_count, sizeof pot.slot_count);
+  hash_vec(pot.slot_coef_off);
+  hash_vec(pot.slot_mu);
+  hash_bytes(pot.deg_first, sizeof pot.deg_first);
+  hash_bytes(pot.deg_coef, sizeof pot.deg_coef);
+  hash_bytes(&pot.coef_total, sizeof pot.coef_total);
+  hash_vec(pot.basic_tgt);
+  hash_bytes(&pot.coef_dense, sizeof pot.coef_dense);
+  hash_vec(pot.fwd_blocks);
+  hash_bytes(&pot.fwd_block_count, sizeof pot.fwd_block_count);
+  hash_vec(pot.basic_pack);
+  hash_vec(pot.seed_idx);
+  hash_vec(pot.seed_val);
+  hash_vec(pot.prog_fwd);
+  hash_vec(pot.prog_bwd);
+  hash_vec(pot.seg_fwd);
+  hash_vec(pot.seg_bwd);
+  hash_bytes(&pot.stored_moment_count, sizeof pot.stored_moment_count);
+  hash_bytes(&pot.normal_levels, sizeof pot.normal_levels);
+  hash_vec(pot.leaf_cf);
+  hash_vec(pot.leaf_cb);
+  hash_vec(pot.e_map);
+  hash_vec(pot.e_lin);
+  std::printf("OK %d %d %d %d %d %d %lld %.3e %016llx\n", pot.alpha_index_basic_count, pot.alpha_index_times_count,
+              pot.alpha_scalar_count, pot.alpha_moment_count, pot.coeff_count, pot.normal_levels, sum, prog_err,
+              (unsigned long long) digest);
   return 0;
 }
