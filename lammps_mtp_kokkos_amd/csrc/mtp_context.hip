@@ -194,6 +194,9 @@ void mtp_context::plan()
     rebn.fp_row = (grows + p.coef_total + MTP_PITCH - 1) / MTP_PITCH;
     rebn.off_nb = std::max(std::max(grows + 3 * P * MTP_PITCH, (rebn.fp_row + Mu_) * MTP_PITCH), d_doubles + m_reb);
     const bool rebn_ok = nodg_ok && grows >= p.alpha_index_basic_count;
+    // (the force phase reads its coefficient blocks 16 at a time, up to 15 doubles past the last block: every layout keeps
+    // off_coef + coef_total <= off_nb, and the neighbour arrays behind off_nb are longer than that, so those reads stay
+    // inside the wave's image without slack)
     auto bytes_of = [&](const Layout &y) { return ((size_t) y.off_nb * 8 + tail + 15) / 16 * 16; };
     // registers: 8 wavefronts per CU (2 per SIMD at <= 256 VGPRs) in workgroups of up to 8, or -- for the table
     // shapes that have the 168-VGPR build -- 12 (3 per SIMD).  Measured on MI355X: a workgroup is only admitted when

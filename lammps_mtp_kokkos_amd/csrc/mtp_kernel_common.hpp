@@ -103,6 +103,71 @@ template <int CTRL> static __device__ __forceinline__ double dpp_f64(double v)
   hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
   return __longlong_as_double((long long) (((unsigned long long) (unsigned) hi << 32) | (unsigned) lo));
 }
+// acc += (c of lane N of this lane's row of 16) * m[i] for i < NT, the c lane of term i being N = i: one
+// v_fmac_f64_dpp row_newbcast per term (the DPP64 control gfx950 has), the same FMA as a v_fmac_f64 on a value
+// broadcast from LDS -- one per-lane ds_read_b64 of 16 coefficients instead of 16 broadcast reads.
+// Preconditions:
+//   - full EXEC: a masked-off source lane still feeds its whole row;
+//   - c is a VGPR pair that no VALU instruction wrote in the two instructions ahead of the statement (VALU write ->
+//     DPP read: 2 wait states, which hipcc does not insert ahead of an asm statement).  The callers pass a value fresh
+//     from an LDS load, which needs none; anything else needs an s_nop 1 in front (tests/test_isa_cpu.py checks the ISA);
+//   - m[i] are VGPR pairs.
+// All NT terms go into ONE statement: hipcc pads every instruction that reads the output of an asm statement with one
+// wait state (s_nop 0), so one statement per term would cost an s_nop per FMA; this way it is one per chunk.
+#define MTP_FMAC_DPP(i, op) "v_fmac_f64_dpp %0, %1, %" #op " row_newbcast:" #i " row_mask:0xf bank_mask:0xf\n\t"
+#define MTP_FD1 MTP_FMAC_DPP(0, 2)
+#define MTP_FD2 MTP_FD1 MTP_FMAC_DPP(1, 3)
+#define MTP_FD3 MTP_FD2 MTP_FMAC_DPP(2, 4)
+#define MTP_FD4 MTP_FD3 MTP_FMAC_DPP(3, 5)
+#define MTP_FD5 MTP_FD4 MTP_FMAC_DPP(4, 6)
+#define MTP_FD6 MTP_FD5 MTP_FMAC_DPP(5, 7)
+#define MTP_FD7 MTP_FD6 MTP_FMAC_DPP(6, 8)
+#define MTP_FD8 MTP_FD7 MTP_FMAC_DPP(7, 9)
+#define MTP_FD9 MTP_FD8 MTP_FMAC_DPP(8, 10)
+#define MTP_FD10 MTP_FD9 MTP_FMAC_DPP(9, 11)
+#define MTP_FD11 MTP_FD10 MTP_FMAC_DPP(10, 12)
+#define MTP_FD12 MTP_FD11 MTP_FMAC_DPP(11, 13)
+#define MTP_FD13 MTP_FD12 MTP_FMAC_DPP(12, 14)
+#define MTP_FD14 MTP_FD13 MTP_FMAC_DPP(13, 15)
+#define MTP_FD15 MTP_FD14 MTP_FMAC_DPP(14, 16)
+#define MTP_FD16 MTP_FD15 MTP_FMAC_DPP(15, 17)
+#define MTP_FO1 "v"(m[0])
+#define MTP_FO2 MTP_FO1, "v"(m[1])
+#define MTP_FO3 MTP_FO2, "v"(m[2])
+#define MTP_FO4 MTP_FO3, "v"(m[3])
+#define MTP_FO5 MTP_FO4, "v"(m[4])
+#define MTP_FO6 MTP_FO5, "v"(m[5])
+#define MTP_FO7 MTP_FO6, "v"(m[6])
+#define MTP_FO8 MTP_FO7, "v"(m[7])
+#define MTP_FO9 MTP_FO8, "v"(m[8])
+#define MTP_FO10 MTP_FO9, "v"(m[9])
+#define MTP_FO11 MTP_FO10, "v"(m[10])
+#define MTP_FO12 MTP_FO11, "v"(m[11])
+#define MTP_FO13 MTP_FO12, "v"(m[12])
+#define MTP_FO14 MTP_FO13, "v"(m[13])
+#define MTP_FO15 MTP_FO14, "v"(m[14])
+#define MTP_FO16 MTP_FO15, "v"(m[15])
+template <int NT> static __device__ __forceinline__ void fmac_row_bcast(double &acc, double c, const double *m)
+{
+  static_assert(NT >= 1 && NT <= 16, "one row of 16 lanes");
+#define MTP_FD_CASE(n) \
+  if constexpr (NT == n) asm("" MTP_FD##n : "+v"(acc) : "v"(c), MTP_FO##n);
+  MTP_FD_CASE(1) MTP_FD_CASE(2) MTP_FD_CASE(3) MTP_FD_CASE(4) MTP_FD_CASE(5) MTP_FD_CASE(6) MTP_FD_CASE(7) MTP_FD_CASE(8)
+  MTP_FD_CASE(9) MTP_FD_CASE(10) MTP_FD_CASE(11) MTP_FD_CASE(12) MTP_FD_CASE(13) MTP_FD_CASE(14) MTP_FD_CASE(15) MTP_FD_CASE(16)
+#undef MTP_FD_CASE
+}
+// one term: acc += row_bcast<N>(c) * m (same preconditions)
+template <int N> static __device__ __forceinline__ void fmac_row_bcast1(double &acc, double c, double m)
+{
+  static_assert(N >= 0 && N < 16, "lane of a row of 16");
+  asm(MTP_FMAC_DPP(%c2, 3) : "+v"(acc) : "v"(c), "i"(N), "v"(m));
+}
+// c of lane N of this lane's row of 16 (v_mov_b32_dpp row_newbcast on both halves)
+template <int N> static __device__ __forceinline__ double row_bcast(double c)
+{
+  return dpp_f64<0x150 + N>(c);
+}
+
 // value of the lane that differs in bit log2(H) (and possibly lower bits).  H = 16 / 32 use gfx950's row / half
 // swaps (lane maps measured with scripts/probes/permlane_probe.hip): with both operands equal to v,
 // v_permlane16_swap leaves rows {0,0,2,2} of v in the first register and rows {1,1,3,3} in the second.

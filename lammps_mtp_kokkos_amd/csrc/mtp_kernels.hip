@@ -26,12 +26,14 @@
 //                   F_ij = sum_s [ dg_s P_s r/|r| + g_s grad P_s ]  (pair_mtp.cpp:174-191, 236-246 summed
 //                   over k), with P_s = (r . grad P_s) / nu (Euler).  Lanes = (neighbour, half): every
 //                   lane raises the monomials of its neighbour degree by degree in registers and
-//                   evaluates the derivative polynomials with coefficients broadcast from LDS (half 0:
-//                   d/dx, half 1: d/dz, d/dy split between the halves by slot); 64 lanes then scatter
+//                   evaluates the derivative polynomials with coefficients broadcast by DPP from one per-lane LDS
+//                   read per 16 of them (half 0: d/dx, half 1: d/dz, d/dy split between the halves by slot); 64 lanes then scatter
 //                   f_j -= F_ij with fp64 HBM atomics and tally the virial (pair_mtp.cpp:248-277)
 //
 // Everything is fp64 (the reference's F_FLOAT); indices are int32.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "mtp_device.hpp"
 
@@ -569,6 +571,40 @@ template <int C> __device__ __forceinline__ double poly_eval(unsigned coef, cons
   return r;
 }
 
+// The same sum with the coefficients broadcast by DPP instead of by LDS: the lanes of a row of 16 belong to one half
+// (rows 0-1: half 0, rows 2-3: half 1), so coef_l = the block of this lane's half + 8 (lane & 15) bytes reads 16
+// coefficients per ds_read_b64 (one LDS cycle per half-wavefront, 32 consecutive banks: conflict-free), and
+// v_fmac_f64_dpp row_newbcast:i hands coefficient i to its row.  Same FMAs in the same order as poly_eval (bitwise the
+// same G); lanes whose coefficient lies past the block read whatever follows it in the image and are never broadcast.
+#ifndef MTP_COEF_DPP
+#define MTP_COEF_DPP 1   // 0: every coefficient is a broadcast ds_read_b64 (poly_eval), for A/B runs
+#endif
+template <int C, int K0> __device__ __forceinline__ void dpp_chunks(double &a, const double *c, const double *m)
+{
+  if constexpr (K0 < C) {
+    fmac_row_bcast<(C - K0 < 16 ? C - K0 : 16)>(a, c[K0 / 16], m + K0);
+    dpp_chunks<C, K0 + 16>(a, c, m);
+  }
+}
+template <int C> __device__ __forceinline__ double poly_eval_dpp(unsigned coef_l, const double *m)
+{
+  constexpr int K = (C + 15) / 16;   // 16-coefficient chunks: all reads first, one accumulation chain
+  double c[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) c[k] = lds_ld(coef_l, 16 * k);
+  double a = 0.0;
+  dpp_chunks<C, 0>(a, c, m);
+  return a;
+}
+// DPP for C >= 2 only: a single coefficient is one read either way, and the DPP form adds the zeroing of the sum.
+// coef: the block's address, + 8 (lane & 15) bytes where coef_dpp<C>.
+template <int C> constexpr bool coef_dpp = MTP_COEF_DPP && C >= 2;
+template <int C> __device__ __forceinline__ double poly_sum(unsigned coef, const double *m)
+{
+  if constexpr (coef_dpp<C>) return poly_eval_dpp<C>(coef, m);
+  else return poly_eval<C>(coef, m);
+}
+
 // Slots of tensor rank NU: m[] holds the monomials of degree NU-1 of this lane's neighbour, ordered
 // (a descending, then b descending): idx(a, b, c) = j (j + 1) / 2 + c with j = b + c.  A slot's coefficient
 // block is [d/dx | d/dy | d/dz], each over those monomials.  UA/VA collect sum_s g_s dP_s/dx (half 0) or
@@ -579,12 +615,13 @@ template <int C> __device__ __forceinline__ double poly_eval(unsigned coef, cons
 // GRADE (fused candidate vectors): W[mu] collects this lane's share of W_mu(n) = sum_{s in mu} P_s(r_n) / r_n^nu
 // (pair_mtp_extrapolation.cpp:193-198), again through P_s = (r . grad P_s) / nu.
 template <int NU, int DEG, int PITCH, bool GRADE, bool NODG>
-__device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoef, int part, double x,
+__device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoef, unsigned pcoef_l, int part, double x,
                                              double y, double z, double *m, double &UA, double &VA, double &UB,
                                              double &VB, const int *smu, double inv, double rw, double *W)
 {
   if constexpr (NU <= DEG) {
     constexpr int C = NU * (NU + 1) / 2;   // monomials of degree NU-1
+    const unsigned pc = coef_dpp<C> ? pcoef_l : pcoef;   // pcoef_l = pcoef + 8 (lane & 15): DPP chunks (poly_sum)
     if (NU < kp->P) {
       const int s0 = kp->deg_first[NU], cnt = kp->deg_first[NU + 1] - s0;
       const double inv_nu = 1.0 / NU;
@@ -593,14 +630,14 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
       const double rwn = rw * inv_nu;
       const double wa = GRADE ? (part ? z : x) * rwn : 0.0, wb = GRADE ? y * rwn : 0.0;
       {
-        unsigned ca = pcoef + 8u * (unsigned) (kp->deg_coef[NU] + part * 2 * C);
+        unsigned ca = pc + 8u * (unsigned) (kp->deg_coef[NU] + part * 2 * C);
         unsigned cg = pcol + 8u * (unsigned) (s0 * PITCH);
         for (int it = 0; it < cnt; it++) {
           // the slot, hence mu, is wave-uniform in this pass
           const int mu = (NODG || GRADE) ? __builtin_amdgcn_readfirstlane(smu[s0 + it]) : 0;
           const double g = lds_ld(cg, 0);
           const double dg = NODG ? lds_ld(pfp + 8u * (unsigned) (mu * PITCH), 0) : lds_ld(cg + dgo, 0);   // NODG: f'_mu (mu: SGPR)
-          const double G = poly_eval<C>(ca, m);
+          const double G = poly_sum<C>(ca, m);
           UA = fma(g, G, UA);
           VA = fma(dg * (NODG ? rwn : inv_nu), G, VA);
           if (GRADE) {
@@ -619,13 +656,13 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
         const bool ok = si < cnt;
         const int sc = ok ? si : 0;
         // (per-lane sc: 24-bit multiplies are full rate, 32-bit ones a quarter of it)
-        const unsigned cb = pcoef + 8u * (unsigned) (kp->deg_coef[NU] + C) + (unsigned) mul24(sc, 8 * 3 * C);
+        const unsigned cb = pc + 8u * (unsigned) (kp->deg_coef[NU] + C) + (unsigned) mul24(sc, 8 * 3 * C);
         const unsigned cg = pcol + (unsigned) mul24(s0 + sc, 8 * PITCH);
         // (the halves hold different slots, hence different mu: a per-lane value here)
         const int mu_raw = (NODG || GRADE) ? smu[s0 + sc] : 0;
         const double g_raw = lds_ld(cg, 0);
         const double dg_raw = NODG ? lds_ld(pfp + (unsigned) mul24(mu_raw, 8 * PITCH), 0) : lds_ld(cg + dgo, 0);
-        const double G = poly_eval<C>(cb, m);
+        const double G = poly_sum<C>(cb, m);
         const double g = ok ? g_raw : 0.0, dg = ok ? dg_raw : 0.0;
         UB = fma(g, G, UB);
         VB = fma(dg * (NODG ? rwn : inv_nu), G, VB);
@@ -644,7 +681,7 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
         m[C + NU] = z * m[T0 + NU - 1];
 #pragma unroll
         for (int i = 0; i < C; i++) m[i] *= x;
-        force_degree<NU + 1, DEG, PITCH, GRADE, NODG>(kp, pcol, pcoef, part, x, y, z, m, UA, VA, UB, VB, smu, inv, rw * inv, W);
+        force_degree<NU + 1, DEG, PITCH, GRADE, NODG>(kp, pcol, pcoef, pcoef_l, part, x, y, z, m, UA, VA, UB, VB, smu, inv, rw * inv, W);
       }
     }
   }
@@ -1071,9 +1108,34 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
         double UA = 0.0, VA = 0.0, UB = 0.0, VB = 0.0, S0 = 0.0;
         double Wm[4] = {0.0, 0.0, 0.0, 0.0};
         const bool fused = GRADE && kp->grade_fused;
+        const unsigned pcoef = w.addr(w.coef), pcoef_l = pcoef + 8u * (unsigned) (lane & 15);
         {   // rank 0: P_s = D_k, no gradient; dg_s = f'_mu (nodg: its row fp_row + mu; else the slot's dg row)
           const unsigned cg0 = pcol + 8u * (unsigned) (nodg ? kp->fp_row * PITCH : kp->dg_off);
-          for (int sidx = 0; sidx < kp->deg_first[1]; sidx++) {
+          const int n0 = kp->deg_first[1];
+#if MTP_COEF_DPP
+          // four slots per per-lane read: lane i of each row holds D_{s4 + i} (poly_eval_dpp)
+          for (int s4 = 0; s4 < n0; s4 += 4) {
+            const double c = lds_ld(pcoef_l + 8u * (unsigned) (kp->deg_coef[0] + s4), 0);
+            auto term = [&](auto I) {
+              constexpr int i = decltype(I)::value;
+              const int sidx = s4 + i;
+              if (i == 0 || sidx < n0) {   // (uniform)
+                const int mu = (nodg || GRADE) ? __builtin_amdgcn_readfirstlane(bt.smu[sidx]) : 0;
+                fmac_row_bcast1<i>(S0, c, lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0));
+                if (GRADE) {
+                  const double dk = row_bcast<i>(c);
+#pragma unroll
+                  for (int v = 0; v < 4; v++) Wm[v] += (mu == v && part == 0) ? dk : 0.0;
+                }
+              }
+            };
+            term(std::integral_constant<int, 0>());
+            term(std::integral_constant<int, 1>());
+            term(std::integral_constant<int, 2>());
+            term(std::integral_constant<int, 3>());
+          }
+#else
+          for (int sidx = 0; sidx < n0; sidx++) {
             const double dk = w.coef[kp->deg_coef[0] + sidx];
             const int mu = (nodg || GRADE) ? __builtin_amdgcn_readfirstlane(bt.smu[sidx]) : 0;
             S0 = fma(lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0), dk, S0);
@@ -1082,16 +1144,17 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
               for (int v = 0; v < 4; v++) Wm[v] += (mu == v && part == 0) ? dk : 0.0;
             }
           }
+#endif
         }
         double mono[DEG * (DEG + 1) / 2];
         mono[0] = 1.0;
         if (nodg) {
-          force_degree<1, DEG, PITCH, GRADE, true>(kp, pcol, w.addr(w.coef), part, x, y, z, mono, UA, VA, UB, VB, bt.smu, inv, inv, Wm);
+          force_degree<1, DEG, PITCH, GRADE, true>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, bt.smu, inv, inv, Wm);
           // dg_s / nu = f'_mu r^-nu / nu - g_s / r: the second term of every slot at once
           VA = fma(-inv, UA, VA);
           VB = fma(-inv, UB, VB);
         } else if constexpr (!NODG_CT) {
-          force_degree<1, DEG, PITCH, GRADE, false>(kp, pcol, w.addr(w.coef), part, x, y, z, mono, UA, VA, UB, VB, bt.smu, inv, inv, Wm);
+          force_degree<1, DEG, PITCH, GRADE, false>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, bt.smu, inv, inv, Wm);
         }
         if (fused) {
           // c[jt][mu][ri] += sum_n [type_n = jt] Q_ri(r_n) W_mu(n)  (pair_mtp_extrapolation.cpp:193-198, 323-329):
@@ -1735,6 +1798,9 @@ const char *mtp_kernel_build_flags()
 #endif
 #if MTP_POLY_ACC != 1
       "MTP_POLY_ACC=" MTP_STR(MTP_POLY_ACC) " "
+#endif
+#if MTP_COEF_DPP != 1
+      "MTP_COEF_DPP=" MTP_STR(MTP_COEF_DPP) " "
 #endif
 
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
