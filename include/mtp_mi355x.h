@@ -95,6 +95,11 @@ int mtp_potential_get_tables(const mtp_potential *pot, int32_t *alpha_index_basi
                              int32_t *alpha_index_times /*[T][4]*/, int32_t *alpha_moment_mapping /*[S]*/,
                              double *radial_coeffs /*[Sp*Sp*Mu*R]*/, double *species_coeffs /*[Sp]*/,
                              double *moment_coeffs /*[S]*/, double *inverse_active_set /*[C*C]*/);
+/* the force kernel instantiation a context of this potential launches (host only): head x tail blocks of the
+ * basic-moment pass, its lane grid (block lanes x blocks per lane) and the highest tensor rank of the unrolled force
+ * phase.  MTP_ERR_LIMIT (fwd_blocks still written) when no instantiation fits; any pointer may be NULL */
+int mtp_potential_kernel_shape(const mtp_potential *pot, int32_t *fwd_blocks, int32_t *block_lanes,
+                               int32_t *blocks_per_lane, int32_t *max_degree);
 
 /* The device copies made in PairMTPKokkos::settings (KOKKOS/pair_mtp_kokkos.cpp:108-174).
  * Fails with MTP_ERR_DEVICE when no gfx950 device is usable: there is no CPU fallback. */
@@ -224,6 +229,9 @@ int mtp_context_set_deterministic(mtp_context *ctx, int enable);
 /* register build the planner chose (2 or 3 wavefronts per SIMD) and whether the per-atom LDS image uses the
  * "rebuild" layout (radial tables built twice, moments overlaying them) */
 int mtp_context_plan_info(const mtp_context *ctx, int32_t *waves_per_simd, int32_t *rebuild_tables);
+/* per-atom LDS layout of the force calls' plan (after a set_neighbors call): 0 keep, 1 lean (no dg rows),
+ * 2 rebuild, 3 rebuild without dg rows (MTP_LAYOUT = keep | lean | rebuild | rebuild-nodg forces one) */
+int mtp_context_layout_mode(const mtp_context *ctx, int32_t *mode);
 /* last kernel time of the dominant kernel in ms, measured with HIP events on the launch
  * stream (enable with mtp_context_set_timing(ctx, 1); costs one event pair per call) */
 int mtp_context_set_timing(mtp_context *ctx, int enable);

@@ -33,7 +33,7 @@ EXPORTS = [
     "mtp_resident_totals", "mtp_resident_peratom_device", "mtp_resident_peratom_host", "mtp_copy_to_host",
     "mtp_ghosts_create", "mtp_ghosts_destroy", "mtp_ghosts_last_error", "mtp_ghosts_build", "mtp_ghosts_forward",
     "mtp_ghosts_reverse", "mtp_ghosts_reverse_finish", "mtp_ghosts_types", "mtp_nve_initial", "mtp_nve_final", "mtp_nve_monitor",
-    "mtp_context_set_deterministic", "mtp_zero_async",
+    "mtp_context_set_deterministic", "mtp_zero_async", "mtp_potential_kernel_shape", "mtp_context_layout_mode",
 ]
 HALO_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX = 0, 1
@@ -178,6 +178,14 @@ class Potential:
             out["inverse_active_set"] = inv
         return out
 
+    def kernel_shape(self):
+        """the force kernel instantiation a context of this potential launches (mtp_potential_kernel_shape)"""
+        a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        rc = lib().mtp_potential_kernel_shape(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+        if rc:
+            raise MtpError(rc, "%d head x tail blocks: no force kernel instantiation fits" % a.value)
+        return dict(fwd_blocks=a.value, block_lanes=b.value, blocks_per_lane=c.value, max_degree=d.value)
+
     def cfg_grade(self, coeff_ders):
         g = C.c_double(0)
         c = np.ascontiguousarray(coeff_ders, dtype=np.float64)
@@ -313,6 +321,12 @@ class Context:
         a, b = C.c_int32(), C.c_int32()
         self._check(lib().mtp_context_plan_info(self.h, C.byref(a), C.byref(b)))
         return dict(waves_per_simd=a.value, rebuild_tables=b.value)
+
+    def layout_mode(self):
+        """per-atom LDS layout of the force plan: 0 keep, 1 lean, 2 rebuild, 3 rebuild-nodg"""
+        m = C.c_int32()
+        self._check(lib().mtp_context_layout_mode(self.h, C.byref(m)))
+        return m.value
 
     def launch_info(self):
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()

@@ -399,6 +399,19 @@ int mtp_potential_get_info(const mtp_potential *p, mtp_potential_info *info)
   return MTP_OK;
 }
 
+int mtp_potential_kernel_shape(const mtp_potential *p, int32_t *fwd_blocks, int32_t *block_lanes,
+                               int32_t *blocks_per_lane, int32_t *max_degree)
+{
+  if (!p) return MTP_ERR_ARG;
+  if (fwd_blocks) *fwd_blocks = p->fwd_block_count;
+  int KL = 0, NB = 0;
+  if (mtp_pick_fwd_shape(p->fwd_block_count, &KL, &NB) != 0) return MTP_ERR_LIMIT;
+  if (block_lanes) *block_lanes = KL;
+  if (blocks_per_lane) *blocks_per_lane = NB;
+  if (max_degree) *max_degree = mtp_wave_kernel_deg(KL, p->max_alpha_index_basic);
+  return MTP_OK;
+}
+
 int mtp_potential_get_tables(const mtp_potential *p, int32_t *aib, int32_t *ait, int32_t *map, double *rc,
                              double *sc, double *mc, double *inv)
 {
@@ -1317,6 +1330,13 @@ int mtp_context_plan_info(const mtp_context *c, int32_t *waves_per_simd, int32_t
   if (!c || !c->have_list) return MTP_ERR_STATE;
   if (waves_per_simd) *waves_per_simd = c->lp[0].wps;
   if (rebuild_tables) *rebuild_tables = c->lp[0].rebuild ? 1 : 0;
+  return MTP_OK;
+}
+
+int mtp_context_layout_mode(const mtp_context *c, int32_t *mode)
+{
+  if (!c || !c->have_list) return MTP_ERR_STATE;
+  if (mode) *mode = c->lp[0].layout.mode;
   return MTP_OK;
 }
 

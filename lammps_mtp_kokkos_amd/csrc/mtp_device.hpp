@@ -113,6 +113,11 @@ struct MtpDevParams {
 int mtp_pick_shape(int B, int *KL, int *KB);
 // lane-grid shape of the force kernel's basic-moment pass: KL lanes x NB 3x3 blocks per lane; -1 beyond 256 blocks
 int mtp_pick_fwd_shape(int nblk, int *KL, int *NB);
+// highest tensor rank DEG the force kernel's unrolled force phase covers on a KL-lane grid: the low build (6 on the
+// narrow grids, 8 on the wide one) when the table's ranks P - 1 fit it, else the general build (11, the loader's cap).
+// The single rule for launch_pitch, mtp_wave_kernel_has_wps3 and mtp_potential_kernel_shape.
+constexpr int mtp_wave_kernel_dlow(int KL) { return KL <= 32 ? 6 : 8; }
+constexpr int mtp_wave_kernel_deg(int KL, int P) { return P - 1 <= mtp_wave_kernel_dlow(KL) ? mtp_wave_kernel_dlow(KL) : 11; }
 hipError_t mtp_launch_wave_kernel(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st);
 bool mtp_wave_kernel_has_wps3(int nfb, int P);
 hipError_t mtp_launch_ev_finish(double *ev_slots, double *ev, hipStream_t st);

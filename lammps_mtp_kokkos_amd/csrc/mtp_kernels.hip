@@ -1651,8 +1651,8 @@ hipError_t launch_grade(const MtpDevParams &p, int grid, int wpb, size_t lds, hi
 // share a CU (mtp_wave_kernel_has_wps3() tells the planner).
 template <int KL, int NB> hipError_t launch_pitch(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st)
 {
-  constexpr int DLOW = KL <= 32 ? 6 : 8;
-  if (p.P - 1 <= DLOW) {
+  constexpr int DLOW = mtp_wave_kernel_dlow(KL);
+  if (mtp_wave_kernel_deg(KL, p.P) == DLOW) {
     if constexpr (KL <= 32 && NB == 1)
       if (p.wps == 3) return launch_grade<KL, NB, DLOW, 3>(p, grid, wpb, lds, st);
     return launch_grade<KL, NB, DLOW, 2>(p, grid, wpb, lds, st);
@@ -1705,7 +1705,7 @@ int mtp_pick_fwd_shape(int nblk, int *KL, int *NB)
 bool mtp_wave_kernel_has_wps3(int nfb, int P)
 {
   int KL = 0, NB = 0;
-  return mtp_pick_fwd_shape(nfb, &KL, &NB) == 0 && KL <= 32 && NB == 1 && P - 1 <= 6;
+  return mtp_pick_fwd_shape(nfb, &KL, &NB) == 0 && KL <= 32 && NB == 1 && mtp_wave_kernel_deg(KL, P) == mtp_wave_kernel_dlow(KL);
 }
 
 hipError_t mtp_launch_wave_kernel(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st)
