@@ -354,25 +354,37 @@ __device__ __forceinline__ void products_backward(const MtpRow8 *rows, const int
 // cb = seed(a3) x mult -- no D[a3] read.  Row per lane as above; the constants are lane-contiguous like the rows.
 // FAR: rows and constants come from HBM / L2 (wide lane grids, whose rows do not fit in LDS): batches of U rows are
 // requested MTP_LD batches ahead of their use, as in the gather passes; otherwise both sit in the LDS blob.
+// REV (MTP_LEAF_SWEEP): the factors are final once the stored levels are done and cb is a constant, so the reverse terms
+// issue in the same sweep from the factors already in registers (D must hold the seeds by then).  Every D slot still
+// receives its seed, then the leaf terms in the same row and lane order, then the level terms: bitwise the same.
 #ifndef MTP_LD
 #define MTP_LD 1   // (2: equal, 4: 2 % slower at level 20)
 #endif
-template <int U, bool STORE, bool FAR>
-__device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double *cf, int beg, int nit, double *M, int lane)
+#ifndef MTP_LEAF_SWEEP
+#define MTP_LEAF_SWEEP 1   // 0: a second pass over the leaf rows for the reverse terms (leaf_backward), for A/B runs
+#endif
+#ifndef MTP_E_HOIST
+#define MTP_E_HOIST 1   // 0: the energy table of the stored scalars is read after the product passes, for A/B runs
+#endif
+template <int U, bool STORE, bool FAR, bool REV = false>
+__device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double *cf, int beg, int nit, double *M, int lane,
+                                               const double *cb = nullptr, double *D_ = nullptr)
 {
   constexpr int D = FAR ? MTP_LD : 1;
+  constexpr int NC = REV ? 2 : 1;   // constants per row: cf (and cb)
   double e = 0.0;
   const MtpRow8 *rp = rows + beg + lane;
-  const double *cp = cf + lane;
+  const double *cp = cf + lane, *bp = REV ? cb + lane : cp;
   const int nb = (nit + U - 1) / U;
   MtpRow8 q[D][U];
-  double qc[D][U];
-  auto fetch = [&](int b, MtpRow8 (&r)[U], double (&c)[U]) {
+  double qc[D][NC][U];
+  auto fetch = [&](int b, MtpRow8 (&r)[U], double (&c)[NC][U]) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int o = 64 * min(b * U + u, nit - 1);   // uniform clamp: the tail re-reads the last block
       r[u] = rp[o];
-      c[u] = cp[o];
+      c[0][u] = cp[o];
+      if constexpr (REV) c[NC - 1][u] = bp[o];
     }
   };
   if (FAR) {
@@ -386,29 +398,38 @@ __device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double
       const int b = b0 + d;
       if (b < nb) {   // uniform
         MtpRow8 rw[U];
-        double c[U], v[U];
+        double c[NC][U], m0[U], m1[U];
         if (FAR) {
 #pragma unroll
           for (int u = 0; u < U; u++) {
             rw[u] = q[d][u];
-            c[u] = qc[d][u];
+#pragma unroll
+            for (int k = 0; k < NC; k++) c[k][u] = qc[d][k][u];
           }
           if (b + D < nb) fetch(b + D, q[d], qc[d]);   // uniform
         } else {
           fetch(b, rw, c);
         }
 #pragma unroll
-        for (int u = 0; u < U; u++) v[u] = at8(M, rw[u].lo & 0xffffu) * at8(M, rw[u].lo >> 16);
+        for (int u = 0; u < U; u++) {
+          m0[u] = at8(M, rw[u].lo & 0xffffu);
+          m1[u] = at8(M, rw[u].lo >> 16);
+        }
 #pragma unroll
         for (int u = 0; u < U; u++)
           if (b * U + u < nit) {   // uniform branch
-            e = fma(c[u], v[u], e);
-            if (STORE) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v[u]);
+            const double v = m0[u] * m1[u];
+            e = fma(c[0][u], v, e);
+            if (STORE) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v);
+            if constexpr (REV) {
+              lds_add(&at8(D_, rw[u].lo >> 16), c[NC - 1][u] * m0[u]);
+              lds_add(&at8(D_, rw[u].lo & 0xffffu), c[NC - 1][u] * m1[u]);
+            }
           }
       }
     }
   }
-  if (STORE) wave_fence();
+  if (STORE || REV) wave_fence();
   return e;
 }
 
@@ -812,8 +833,9 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
   // across the wavefront's atoms and cross the lanes once, after the atom loop.  Per-atom outputs (vatom: vflag & 4,
   // eatom: eflag & 2) keep the per-atom reductions.
   double vacc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, eacc = 0.0;
-  // (Only in the 2-per-SIMD build: at 168 VGPRs the seven extra accumulators spill and cost more than the per-atom
-  // reductions -- measured 0.514 against 0.500 ms.)
+  // (Only in the 2-per-SIMD build: at 168 VGPRs the six virial accumulators spill 10 dwords, and deferring the energy
+  // alone was measured equal -- 0.4044 against 0.4044 ms; when that build still spilled, all seven cost more than the
+  // per-atom reductions: 0.514 against 0.500 ms.)
   const bool v_per_atom = WPS == 3 ? kp->vflag != 0 : (kp->vflag & 4) != 0;
   const bool e_per_atom = WPS == 3 ? true : (kp->eflag & 2) != 0;
 #ifdef MTP_STAMPS
@@ -821,6 +843,13 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
   unsigned long long st_prev = __builtin_amdgcn_s_memtime();
   const unsigned long long st_prologue = st_prev - st_entry;   // argument block, table copy, barrier, first list head
 #endif
+
+  auto store_seeds = [&]() {   // D[seed_idx[k]] = seed_val[k]: the adjoints of the stored scalars
+    if (kp->scalars_in_lds)
+      for (int k = lane; k < kp->nseed; k += 64) w.D[bt.seed_idx[k]] = bt.seed_val[k];
+    else
+      for (int k = lane; k < kp->nseed; k += 64) w.D[kp->g_seed_idx[k]] = kp->g_seed_val[k];
+  };
 
   int nx_i = __builtin_amdgcn_readfirstlane(hd_i), nx_b = __builtin_amdgcn_readfirstlane(hd_b);
   int nx_n = __builtin_amdgcn_readfirstlane(hd_e) - nx_b;
@@ -991,6 +1020,24 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
       }
     for (int m = kp->B + lane; m < kp->Am; m += 64) w.M[m] = 0.0;
     for (int m = lane; m < kp->Ad; m += 64) w.D[m] = 0.0;
+#if MTP_LEAF_SWEEP
+    // adjoint seeds (atom-invariant) behind the zeros, in the same program order: the leaf sweep adds onto them
+    store_seeds();
+#endif
+#if MTP_E_HOIST
+    // the first 64 energy-table entries, requested ahead of the product passes: the energy then costs one LDS round trip
+    int emap0 = 0;
+    double elin0 = 0.0;
+    if (lane < kp->Se) {
+      if (kp->scalars_in_lds) {
+        emap0 = bt.map[lane];
+        elin0 = bt.lin[lane];
+      } else {
+        emap0 = kp->g_map[lane];
+        elin0 = kp->g_lin[lane];
+      }
+    }
+#endif
     if (q == 0) {
 #pragma unroll
       for (int t = 0; t < NB; t++)
@@ -1018,8 +1065,8 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
     // (two code paths per table home, LDS blob or HBM/L2: no pointer selects between address spaces, see below)
     const int leaf_beg = __builtin_amdgcn_readfirstlane(bt.level[kp->nlevels]);
     const int leaf_nit = (__builtin_amdgcn_readfirstlane(bt.level[kp->nlevels + 1]) - leaf_beg) >> 6;
-    if (rows_lds) e = leaf_forward<MTP_PU, GRADE, false>(bt.rows, bt.leaf_cf, leaf_beg, leaf_nit, w.M, lane);
-    else e = leaf_forward<MTP_PU, GRADE, true>(kp->rows, kp->leaf_cf, leaf_beg, leaf_nit, w.M, lane);
+    if (rows_lds) e = leaf_forward<MTP_PU, GRADE, false, MTP_LEAF_SWEEP>(bt.rows, bt.leaf_cf, leaf_beg, leaf_nit, w.M, lane, bt.leaf_cb, w.D);
+    else e = leaf_forward<MTP_PU, GRADE, true, MTP_LEAF_SWEEP>(kp->rows, kp->leaf_cf, leaf_beg, leaf_nit, w.M, lane, kp->leaf_cb, w.D);
     STAMP(4);   // products forward
     // ---- candidate vector, species and linear blocks (pair_mtp_extrapolation.cpp:235-252) ----
     if (GRADE) {
@@ -1027,10 +1074,16 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
       for (int k = lane; k < kp->Sp; k += 64) crow[k] = k == itype ? 1.0 : 0.0;
       for (int k = lane; k < kp->S; k += 64) crow[kp->Sp + k] = w.M[kp->g_map_all[k]];
     }
+#if MTP_E_HOIST
+    if (lane < kp->Se) e += elin0 * w.M[emap0];
+    const int k_e = lane + 64;
+#else
+    const int k_e = lane;
+#endif
     if (kp->scalars_in_lds)
-      for (int k = lane; k < kp->Se; k += 64) e += bt.lin[k] * w.M[bt.map[k]];
+      for (int k = k_e; k < kp->Se; k += 64) e += bt.lin[k] * w.M[bt.map[k]];
     else
-      for (int k = lane; k < kp->Se; k += 64) e += kp->g_lin[k] * w.M[kp->g_map[k]];
+      for (int k = k_e; k < kp->Se; k += 64) e += kp->g_lin[k] * w.M[kp->g_map[k]];
     if (e_per_atom) {
       e = wave_sum(e) + kp->species_coeffs[itype];
       if (lane == 9) {   // (lane 9 carries the energy tally; nothing of e stays live into the force phase)
@@ -1041,14 +1094,15 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
       eacc += e + (lane == 0 ? kp->species_coeffs[itype] : 0.0);
     }
     // ---- 4b. adjoints (pair_mtp.cpp:217-233) ----------------------------------------------
-    if (kp->scalars_in_lds)
-      for (int k = lane; k < kp->nseed; k += 64) w.D[bt.seed_idx[k]] = bt.seed_val[k];
-    else
-      for (int k = lane; k < kp->nseed; k += 64) w.D[kp->g_seed_idx[k]] = kp->g_seed_val[k];
+#if !MTP_LEAF_SWEEP
+    store_seeds();
     wave_fence();
     STAMP(5);   // energy + seeds
     if (rows_lds) leaf_backward<MTP_PU, false>(bt.rows, bt.leaf_cb, leaf_beg, leaf_nit, w.M, w.D, lane);
     else leaf_backward<MTP_PU, true>(kp->rows, kp->leaf_cb, leaf_beg, leaf_nit, w.M, w.D, lane);
+#else
+    STAMP(5);   // energy
+#endif
     if constexpr (GATHER) {
       gather_pass(kp->prog_bwd, bt.seg_bwd, kp->nlevels, w.D, w.M, w.D, lane);
     } else {
@@ -1801,6 +1855,12 @@ const char *mtp_kernel_build_flags()
 #endif
 #if MTP_COEF_DPP != 1
       "MTP_COEF_DPP=" MTP_STR(MTP_COEF_DPP) " "
+#endif
+#if MTP_LEAF_SWEEP != 1
+      "MTP_LEAF_SWEEP=" MTP_STR(MTP_LEAF_SWEEP) " "
+#endif
+#if MTP_E_HOIST != 1
+      "MTP_E_HOIST=" MTP_STR(MTP_E_HOIST) " "
 #endif
 
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
