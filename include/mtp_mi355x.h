@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 3
+#define MTP_MI355X_ABI_VERSION 4
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -324,7 +324,8 @@ int mtp_halo_allreduce(mtp_halo *halo, void *stream, double *d_buf, int count, i
  * For drivers that keep the whole step in HBM (bench.py's whole-step number, lammps_mtp_kokkos_amd/md.py): the
  * periodic ghost images of ONE GPU's own atoms (Comm::borders / forward_comm / reverse_comm of a single rank; the
  * pair style needs them because it writes forces onto ghosts, pair_mtp.cpp:252-254, 315) and the two halves of a
- * velocity-Verlet step (fix nve).  Orthogonal box [0, box), every edge >= rghost.
+ * velocity-Verlet step (fix nve).  mtp_ghosts_build: orthogonal box [0, box), every edge >= rghost (the fast path the
+ * whole-step benchmark runs); mtp_ghosts_build_cell: any periodic cell, smaller than rghost included.
  */
 typedef struct mtp_ghosts mtp_ghosts;
 int mtp_ghosts_create(int device_id, mtp_ghosts **out);
@@ -336,6 +337,24 @@ const char *mtp_ghosts_last_error(const mtp_ghosts *g);
  * Synchronises the stream once (the ghost count sizes the caller's arrays and the neighbour list). */
 int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x /*[capacity][3]*/, int nlocal, int capacity,
                      const double box[3], double rghost, int *nall_out);
+/* The same for any periodic cell.  cell[9]: rows are the lattice vectors a, b, c (any right-handed, non-degenerate
+ * cell; LAMMPS' restricted triclinic is the lower-triangular case, an orthogonal box the diagonal one); origin at 0.
+ * With fractional coordinates s = x . cell^-1, the owned atoms are wrapped to s in [0, 1)^3 and written back as
+ * s . cell.  With plane spacings d_a = V / |cell_b x cell_c| (cyclic) and margins m_a = rghost / d_a, the image of
+ * atom i under the integer shift n != 0 is a ghost iff -m_a <= s_a + n_a < 1 + m_a for a = 0, 1, 2 (the slab
+ * criterion of LAMMPS' triclinic ghost cutoffs: a superset of "within rghost of the cell", separable per direction).
+ * Any number of images per direction, no lower limit on the cell size.  Ghost order, capacity protocol, the single
+ * stream synchronisation and the NULL-stream rule as for mtp_ghosts_build; shift[k] = n . cell.  MTP_ERR_ARG for a
+ * cell with det <= 0 or non-finite entries (nothing is launched); MTP_ERR_LIMIT, *nall_out = INT_MAX, when owned +
+ * ghost atoms do not fit an int (never wrapped).  mtp_ghosts_forward / reverse / reverse_finish / types then work
+ * on the handle unchanged. */
+int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x /*[capacity][3]*/, int nlocal, int capacity,
+                          const double cell[9], double rghost, int *nall_out);
+/* Host arithmetic only: bounds of every position mtp_ghosts_build_cell can write for this cell and rghost (the lo / hi
+ * that mtp_build_neighbors_device wants), the cell volume, and the images taken per direction and sign (ceil(m_a)).
+ * Any output may be NULL. */
+int mtp_ghosts_cell_bounds(const double cell[9], double rghost, double lo[3], double hi[3], double *volume,
+                           int nimage[3]);
 int mtp_ghosts_forward(mtp_ghosts *g, void *stream, double *d_x);   /* ghost rows <- owner + shift            */
 int mtp_ghosts_reverse(mtp_ghosts *g, void *stream, double *d_f);   /* owner rows += ghost rows (fp64 atomics) */
 /* The same together with the energy / virial fold of a force call made through mtp_compute_device_rows(...,

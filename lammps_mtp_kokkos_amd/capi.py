@@ -34,6 +34,7 @@ EXPORTS = [
     "mtp_ghosts_create", "mtp_ghosts_destroy", "mtp_ghosts_last_error", "mtp_ghosts_build", "mtp_ghosts_forward",
     "mtp_ghosts_reverse", "mtp_ghosts_reverse_finish", "mtp_ghosts_types", "mtp_nve_initial", "mtp_nve_final", "mtp_nve_monitor",
     "mtp_context_set_deterministic", "mtp_zero_async", "mtp_potential_kernel_shape", "mtp_context_layout_mode",
+    "mtp_ghosts_build_cell", "mtp_ghosts_cell_bounds",
 ]
 HALO_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX = 0, 1
@@ -497,6 +498,17 @@ class Ghosts:
         self._check(rc)
         return nall.value
 
+    def build_cell(self, x_t, nlocal, cell, rghost, stream=None):
+        """The same for any periodic cell (rows of the 3x3 `cell` are the lattice vectors; smaller than rghost is fine):
+        mtp_ghosts_build_cell.  Same capacity protocol as build()."""
+        c9 = (C.c_double * 9)(*[float(v) for v in np.asarray(cell, dtype=np.float64).reshape(9)])
+        nall = C.c_int(0)
+        rc = lib().mtp_ghosts_build_cell(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t), int(nlocal),
+                                         int(x_t.shape[0]), c9, C.c_double(rghost), C.byref(nall))
+        self.nall = nall.value
+        self._check(rc)
+        return nall.value
+
     def forward(self, x_t, stream=None):
         self._check(lib().mtp_ghosts_forward(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t)))
 
@@ -510,6 +522,17 @@ class Ghosts:
 
     def types(self, type_t, stream=None):
         self._check(lib().mtp_ghosts_types(self.h, C.c_void_p(stream) if stream else None, _ptr(type_t)))
+
+
+def ghosts_cell_bounds(cell, rghost):
+    """Host arithmetic (no device): dict(lo, hi, volume, nimage) -- the bounds of every position Ghosts.build_cell can
+    write for this cell (what build_neighbors_device wants), the cell volume, the images per direction and sign."""
+    c9 = (C.c_double * 9)(*[float(v) for v in np.asarray(cell, dtype=np.float64).reshape(9)])
+    lo, hi, vol, nim = (C.c_double * 3)(), (C.c_double * 3)(), C.c_double(0), (C.c_int * 3)()
+    rc = lib().mtp_ghosts_cell_bounds(c9, C.c_double(rghost), lo, hi, C.byref(vol), nim)
+    if rc:
+        raise MtpError(rc, "mtp_ghosts_cell_bounds: the cell must be finite with det > 0, rghost > 0")
+    return dict(lo=np.array(lo[:]), hi=np.array(hi[:]), volume=vol.value, nimage=np.array(nim[:], dtype=np.int64))
 
 
 def nve_initial(nlocal, x_t, v_t, f_t, type_t, inv_mass_t, dtf, dt, stream=None):

@@ -9,6 +9,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <new>
@@ -79,6 +80,95 @@ __global__ void __launch_bounds__(256) ghosts_fill_kernel(Box3 b, const double *
         }
         k++;
       }
+}
+
+// ---- any periodic cell (mtp_ghosts_build_cell): rows of h are the lattice vectors, hinv its inverse, s = x . hinv the
+// fractional coordinates, m[a] = rghost / (spacing of the lattice planes normal to direction a).  The image of an atom
+// under the integer shift n is a ghost iff -m[a] <= s[a] + n[a] < 1 + m[a] in all three directions (the slab criterion of
+// LAMMPS' triclinic ghost cutoffs): separable, so the allowed n[a] form the closed range below and nothing is looped over.
+struct Cell9 {
+  double h[9], hinv[9], m[3];
+};
+
+// per-atom shift ranges as the count pass found them; the fill pass reads them back instead of deriving them again from
+// the wrapped Cartesian position ((s . h) . hinv may land one ulp on the other side of a bound, and the fill would then
+// write past its atom's slots)
+struct alignas(16) ShiftRange {
+  int lo[3], cnt[3], pad[2];   // n[a] in [lo[a], lo[a] + cnt[a]); 32 bytes, two 16-byte stores / loads
+};
+
+// wraps the owned atoms into s in [0, 1)^3 and counts their images.  SUM64 (only when the host cannot rule out a total
+// beyond int from the margins alone): count[i] saturates at INT_MAX and the exact total goes to *total64, one atomic per
+// block, so that such a total is seen on the host rather than wrapped by the scan
+template <bool SUM64>
+__global__ void __launch_bounds__(256) ghosts_cell_count_kernel(Cell9 c, double *__restrict__ x, int n, int *__restrict__ count,
+                                                               ShiftRange *__restrict__ range,
+                                                               unsigned long long *__restrict__ total64)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long mine = 0;
+  if (i < n) {
+    const double p[3] = {x[3 * (size_t) i], x[3 * (size_t) i + 1], x[3 * (size_t) i + 2]};
+    double s[3];
+    ShiftRange r;
+    unsigned long long prod = 1;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      // (products and sums rounded one by one, in this order: the numpy twin in driver.make_ghosts_cell does the same)
+      double v = __dadd_rn(__dadd_rn(__dmul_rn(p[0], c.hinv[a]), __dmul_rn(p[1], c.hinv[3 + a])), __dmul_rn(p[2], c.hinv[6 + a]));
+      v -= floor(v);
+      if (!(v < 1.0)) v = 0.0;   // floor() rounding at the upper edge (and a non-finite coordinate: counted from 0)
+      s[a] = v;
+      const double lo = ceil(-c.m[a] - v), hi = ceil(1.0 + c.m[a] - v) - 1.0;   // lo <= 0 <= hi
+      r.lo[a] = (int) fmax(lo, -1073741824.0);
+      r.cnt[a] = (int) fmin(hi - lo + 1.0, 1073741824.0);
+      prod = prod > 0xffffffffull ? prod : prod * (unsigned long long) r.cnt[a];   // stays below 2^63
+    }
+    r.pad[0] = r.pad[1] = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+      x[3 * (size_t) i + a] = __dadd_rn(__dadd_rn(__dmul_rn(s[0], c.h[a]), __dmul_rn(s[1], c.h[3 + a])), __dmul_rn(s[2], c.h[6 + a]));
+    mine = prod - 1 > 0xffffffffull ? 0xffffffffull : prod - 1;   // 2^31 atoms of these still sum below 2^64
+    count[i] = mine > 0x7fffffffull ? 0x7fffffff : (int) mine;
+    range[i] = r;
+  }
+  if (SUM64) {
+    typedef hipcub::BlockReduce<unsigned long long, 256> Red;
+    __shared__ typename Red::TempStorage tmp;
+    const unsigned long long bsum = Red(tmp).Sum(mine);
+    if (threadIdx.x == 0 && bsum) atomicAdd(total64, bsum);
+  }
+}
+
+// one lane per GHOST (a 1-atom cell has hundreds of images of its one atom): the owner is the last atom whose scanned
+// offset is <= k, the shift triple comes from the position of k in that atom's box of shifts (lexicographic, the zero
+// shift left out) -> owner[k], shift[k] = n . h
+__global__ void __launch_bounds__(256) ghosts_cell_fill_kernel(Cell9 c, int n, int total, const int *__restrict__ first,
+                                                              const ShiftRange *__restrict__ range, int *__restrict__ owner,
+                                                              double *__restrict__ shift, int capacity)
+{
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= total || k >= capacity) return;
+  // bisection for the last atom with first[i] <= k (first[0] = 0 <= k, first[n] = total > k).  (A 16-ary search, 15
+  // independent probes a round, measured slower on MI355X: 17 us against 7.5 us for 31 773 ghosts of 65 536 atoms.)
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (first[mid] <= k) lo = mid;
+    else hi = mid - 1;
+  }
+  const ShiftRange r = range[lo];
+  int e = k - first[lo];
+  const int zero = (-r.lo[0] * r.cnt[1] - r.lo[1]) * r.cnt[2] - r.lo[2];   // where the atom itself would stand
+  if (e >= zero) e++;
+  const int q = e / r.cnt[2];
+  const double n2 = r.lo[2] + (e - q * r.cnt[2]);
+  const int q1 = q / r.cnt[1];
+  const double n1 = r.lo[1] + (q - q1 * r.cnt[1]), n0 = r.lo[0] + q1;
+  owner[k] = lo;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    shift[3 * (size_t) k + a] = __dadd_rn(__dadd_rn(__dmul_rn(n0, c.h[a]), __dmul_rn(n1, c.h[3 + a])), __dmul_rn(n2, c.h[6 + a]));
 }
 
 // x[nlocal + k] = x[owner[k]] + shift[k]   (one lane per coordinate)
@@ -164,13 +254,15 @@ struct mtp_ghosts {
   int cap_local = 0, cap_ghost = 0;
   int *d_count = nullptr, *d_first = nullptr, *d_owner = nullptr;
   double *d_shift = nullptr;
+  ShiftRange *d_range = nullptr;             // mtp_ghosts_build_cell only: [cap_range] + one 64-bit total behind them
+  int cap_range = 0;
   void *d_tmp = nullptr;
   size_t tmp_bytes = 0;
   std::string last_error;
   ~mtp_ghosts()
   {
     (void) hipSetDevice(device);
-    for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, d_tmp})
+    for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, (void *) d_range, d_tmp})
       if (p) (void) hipFree(p);
   }
 };
@@ -188,6 +280,68 @@ static int ghosts_null_stream(mtp_ghosts *g, const char *fn)
 {
   g->last_error = std::string(fn) + ": a NULL stream is not accepted (no context to take a stream from)";
   return MTP_ERR_ARG;
+}
+
+// allocation growth shared by the two builds: per-atom counts / offsets (+ the scan's workspace), per-ghost maps
+static hipError_t ghosts_reserve_local(mtp_ghosts *g, int nlocal, hipStream_t st)
+{
+  if (nlocal + 1 <= g->cap_local) return hipSuccess;
+  hipError_t e;
+  if (g->d_count) (void) hipFree(g->d_count);
+  if (g->d_first) (void) hipFree(g->d_first);
+  g->d_count = g->d_first = nullptr;
+  g->cap_local = 0;
+  const size_t n = (size_t) nlocal + 1 + nlocal / 8;
+  if ((e = hipMalloc((void **) &g->d_count, n * sizeof(int))) != hipSuccess) return e;
+  if ((e = hipMalloc((void **) &g->d_first, n * sizeof(int))) != hipSuccess) return e;
+  g->cap_local = (int) n;
+  size_t need = 0;
+  (void) hipcub::DeviceScan::ExclusiveSum(nullptr, need, g->d_count, g->d_first, (int) n, st);
+  if (need > g->tmp_bytes) {
+    if (g->d_tmp) (void) hipFree(g->d_tmp);
+    g->d_tmp = nullptr;
+    g->tmp_bytes = 0;
+    if ((e = hipMalloc(&g->d_tmp, need)) != hipSuccess) return e;
+    g->tmp_bytes = need;
+  }
+  return hipSuccess;
+}
+
+static hipError_t ghosts_reserve_ghosts(mtp_ghosts *g, int total)
+{
+  if (total <= g->cap_ghost) return hipSuccess;
+  hipError_t e;
+  if (g->d_owner) (void) hipFree(g->d_owner);
+  if (g->d_shift) (void) hipFree(g->d_shift);
+  g->d_owner = nullptr;
+  g->d_shift = nullptr;
+  g->cap_ghost = 0;
+  const size_t n = std::min((size_t) total + total / 8 + 64, (size_t) 0x7fffffff);
+  if ((e = hipMalloc((void **) &g->d_owner, n * sizeof(int))) != hipSuccess) return e;
+  if ((e = hipMalloc((void **) &g->d_shift, 3 * n * sizeof(double))) != hipSuccess) return e;
+  g->cap_ghost = (int) n;
+  return hipSuccess;
+}
+
+// h^-1 (cofactors over the determinant), the margins m[a] = rghost / d_a with d_a = V / |h_b x h_c| the spacing of the
+// lattice planes normal to direction a; returns the determinant (<= 0 or non-finite: not a cell this library takes)
+static double cell_setup(const double h[9], double rghost, double hinv[9], double m[3])
+{
+  for (int k = 0; k < 9; k++)
+    if (!std::isfinite(h[k])) return 0.0;
+  const double *a = h, *b = h + 3, *c = h + 6;
+  const double bc[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
+  const double ca[3] = {c[1] * a[2] - c[2] * a[1], c[2] * a[0] - c[0] * a[2], c[0] * a[1] - c[1] * a[0]};
+  const double ab[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+  const double det = a[0] * bc[0] + a[1] * bc[1] + a[2] * bc[2];
+  if (!std::isfinite(det) || !(det > 0.0)) return 0.0;
+  const double *cross[3] = {bc, ca, ab};
+  for (int k = 0; k < 3; k++) {
+    for (int r = 0; r < 3; r++) hinv[3 * r + k] = cross[k][r] / det;   // column k of h^-1 = (h_{k+1} x h_{k+2}) / det
+    m[k] = rghost * std::sqrt(cross[k][0] * cross[k][0] + cross[k][1] * cross[k][1] + cross[k][2] * cross[k][2]) / det;
+    if (!std::isfinite(m[k])) return 0.0;
+  }
+  return det;
 }
 
 extern "C" {
@@ -221,23 +375,7 @@ int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x, int nlocal, int c
     }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   MD_HIP(hipSetDevice(g->device));
-  if (nlocal + 1 > g->cap_local) {
-    if (g->d_count) (void) hipFree(g->d_count);
-    if (g->d_first) (void) hipFree(g->d_first);
-    g->d_count = g->d_first = nullptr;
-    const size_t n = (size_t) nlocal + 1 + nlocal / 8;
-    MD_HIP(hipMalloc((void **) &g->d_count, n * sizeof(int)));
-    MD_HIP(hipMalloc((void **) &g->d_first, n * sizeof(int)));
-    g->cap_local = (int) n;
-    size_t need = 0;
-    (void) hipcub::DeviceScan::ExclusiveSum(nullptr, need, g->d_count, g->d_first, (int) n, st);
-    if (need > g->tmp_bytes) {
-      if (g->d_tmp) (void) hipFree(g->d_tmp);
-      g->d_tmp = nullptr;
-      MD_HIP(hipMalloc(&g->d_tmp, need));
-      g->tmp_bytes = need;
-    }
-  }
+  MD_HIP(ghosts_reserve_local(g, nlocal, st));
   Box3 b{{box[0], box[1], box[2]}, rghost};
   const int nb = (nlocal + 255) / 256;
   MD_HIP(hipMemsetAsync(g->d_count, 0, ((size_t) nlocal + 1) * sizeof(int), st));
@@ -247,16 +385,7 @@ int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x, int nlocal, int c
   int total = 0;
   MD_HIP(hipMemcpyAsync(&total, g->d_first + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
   MD_HIP(hipStreamSynchronize(st));
-  if (total > g->cap_ghost) {
-    if (g->d_owner) (void) hipFree(g->d_owner);
-    if (g->d_shift) (void) hipFree(g->d_shift);
-    g->d_owner = nullptr;
-    g->d_shift = nullptr;
-    const size_t n = (size_t) total + total / 8 + 64;
-    MD_HIP(hipMalloc((void **) &g->d_owner, n * sizeof(int)));
-    MD_HIP(hipMalloc((void **) &g->d_shift, 3 * n * sizeof(double)));
-    g->cap_ghost = (int) n;
-  }
+  MD_HIP(ghosts_reserve_ghosts(g, total));
   g->nlocal = nlocal;
   g->nghost = total;
   *nall_out = nlocal + total;
@@ -267,6 +396,103 @@ int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x, int nlocal, int c
   if (nlocal > 0 && total > 0) {
     hipLaunchKernelGGL(ghosts_fill_kernel, dim3(nb), dim3(256), 0, st, b, d_x, nlocal, g->d_first, g->d_owner, g->d_shift,
                        g->cap_ghost);
+    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
+                       g->d_shift, 3 * total);
+  }
+  MD_HIP(hipGetLastError());
+  return MTP_OK;
+}
+
+int mtp_ghosts_cell_bounds(const double cell[9], double rghost, double lo[3], double hi[3], double *volume, int nimage[3])
+{
+  if (!cell || !(rghost > 0.0) || !std::isfinite(rghost)) return MTP_ERR_ARG;
+  double hinv[9], m[3];
+  const double det = cell_setup(cell, rghost, hinv, m);
+  if (!(det > 0.0)) return MTP_ERR_ARG;
+  if (volume) *volume = det;
+  for (int a = 0; a < 3; a++) {
+    if (nimage) nimage[a] = (int) std::fmin(std::ceil(m[a]), 2147483647.0);
+    // every position written has fractional coordinates in [-m, 1 + m]^3: the box of that parallelepiped's corners,
+    // widened by the rounding of s . cell + n . cell
+    double l = 0.0, u = 0.0;
+    for (int k = 0; k < 3; k++) {
+      const double t0 = -m[k] * cell[3 * k + a], t1 = (1.0 + m[k]) * cell[3 * k + a];
+      l += std::fmin(t0, t1);
+      u += std::fmax(t0, t1);
+    }
+    const double pad = 1e-9 * (u - l) + 1e-12;
+    if (lo) lo[a] = l - pad;
+    if (hi) hi[a] = u + pad;
+  }
+  return MTP_OK;
+}
+
+int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x, int nlocal, int capacity, const double cell[9],
+                          double rghost, int *nall_out)
+{
+  if (!g || !d_x || nlocal < 0 || capacity < nlocal || !cell || !(rghost > 0.0) || !std::isfinite(rghost) || !nall_out)
+    return MTP_ERR_ARG;
+  if (!stream) return ghosts_null_stream(g, "mtp_ghosts_build_cell");
+  Cell9 c;
+  for (int k = 0; k < 9; k++) c.h[k] = cell[k];
+  if (!(cell_setup(cell, rghost, c.hinv, c.m) > 0.0)) {
+    g->last_error = "mtp_ghosts_build_cell: the cell must be finite, right-handed and non-degenerate (det > 0)";
+    return MTP_ERR_ARG;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  MD_HIP(hipSetDevice(g->device));
+  MD_HIP(ghosts_reserve_local(g, nlocal, st));
+  if (nlocal + 1 > g->cap_range) {
+    if (g->d_range) (void) hipFree(g->d_range);
+    g->d_range = nullptr;
+    g->cap_range = 0;
+    MD_HIP(hipMalloc((void **) &g->d_range, ((size_t) g->cap_local + 1) * sizeof(ShiftRange)));
+    g->cap_range = g->cap_local;
+  }
+  // an atom has at most floor(1 + 2 m_a) + 1 shifts per direction: when that bound times nlocal fits an int (every cell
+  // a simulation meets), the scanned int total is exact and the 64-bit sum is not taken
+  double bound = (double) nlocal;
+  for (int a = 0; a < 3; a++) bound *= std::floor(1.0 + 2.0 * c.m[a]) + 1.0;
+  const bool sum64 = !(bound + (double) nlocal < 2147483647.0);
+  unsigned long long *d_total64 = reinterpret_cast<unsigned long long *>(g->d_range + g->cap_range);
+  const int nb = (nlocal + 255) / 256;
+  MD_HIP(hipMemsetAsync(g->d_count, 0, ((size_t) nlocal + 1) * sizeof(int), st));
+  if (sum64) MD_HIP(hipMemsetAsync(d_total64, 0, sizeof(unsigned long long), st));
+  if (nlocal > 0) {
+    if (sum64)
+      hipLaunchKernelGGL(ghosts_cell_count_kernel<true>, dim3(nb), dim3(256), 0, st, c, d_x, nlocal, g->d_count, g->d_range, d_total64);
+    else
+      hipLaunchKernelGGL(ghosts_cell_count_kernel<false>, dim3(nb), dim3(256), 0, st, c, d_x, nlocal, g->d_count, g->d_range, d_total64);
+  }
+  size_t tb = g->tmp_bytes;
+  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp, tb, g->d_count, g->d_first, nlocal + 1, st));
+  int total = 0;
+  unsigned long long total64 = 0;
+  if (sum64) MD_HIP(hipMemcpyAsync(&total64, d_total64, sizeof(total64), hipMemcpyDeviceToHost, st));
+  else MD_HIP(hipMemcpyAsync(&total, g->d_first + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
+  MD_HIP(hipStreamSynchronize(st));
+  if (sum64) {
+    if (total64 > 0x7fffffffull - (unsigned long long) nlocal) {   // never wrapped: the scanned offsets are not used
+      g->nlocal = nlocal;
+      g->nghost = 0;
+      *nall_out = 0x7fffffff;
+      g->last_error = "mtp_ghosts_build_cell: owned + ghost atoms do not fit a 32-bit count (cell far smaller than rghost?)";
+      return MTP_ERR_LIMIT;
+    }
+    total = (int) total64;   // == d_first[nlocal]: no per-atom count saturated
+  }
+  g->nlocal = nlocal;
+  g->nghost = 0;
+  *nall_out = nlocal + total;
+  if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written or kept
+    g->last_error = "mtp_ghosts_build_cell: capacity of the position array is smaller than owned + ghost atoms";
+    return MTP_ERR_LIMIT;
+  }
+  MD_HIP(ghosts_reserve_ghosts(g, total));
+  g->nghost = total;
+  if (total > 0) {
+    hipLaunchKernelGGL(ghosts_cell_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c, nlocal, total, g->d_first,
+                       g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
     hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
                        g->d_shift, 3 * total);
   }

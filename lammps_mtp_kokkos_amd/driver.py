@@ -58,6 +58,57 @@ def make_ghosts(pos, box, rghost, lo=None):
     return np.concatenate(xs), np.concatenate(owners)
 
 
+def cell_margins(cell, rghost):
+    """(cell^-1, margins m_a = rghost / d_a, volume) of a right-handed cell whose rows are the lattice vectors;
+    d_a = V / |cell_b x cell_c| is the spacing of the lattice planes normal to direction a.  Same arithmetic, in
+    the same order, as the library's mtp_ghosts_build_cell."""
+    h = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    cross = np.array([np.cross(h[1], h[2]), np.cross(h[2], h[0]), np.cross(h[0], h[1])])
+    det = h[0, 0] * cross[0, 0] + h[0, 1] * cross[0, 1] + h[0, 2] * cross[0, 2]
+    if not (np.isfinite(h).all() and det > 0.0):
+        raise ValueError("cell must be finite, right-handed and non-degenerate (det > 0)")
+    hinv = (cross / det).T                                   # column k of cell^-1 = (h_{k+1} x h_{k+2}) / det
+    m = rghost * np.sqrt(cross[:, 0] * cross[:, 0] + cross[:, 1] * cross[:, 1] + cross[:, 2] * cross[:, 2]) / det
+    return hinv, m, float(det)
+
+
+def make_ghosts_cell(pos, cell, rghost):
+    """Periodic images for any cell (triclinic, smaller than rghost): the numpy twin of mtp_ghosts_build_cell.
+    With fractional coordinates s = x . cell^-1 the owned atoms are wrapped to s in [0, 1)^3 (and returned as
+    s . cell); the image of atom i under the integer shift n != 0 is a ghost iff -m_a <= s_a + n_a < 1 + m_a in
+    all three directions.  Returns (x [nall, 3], owner [nall], shifts [nall, 3] integer), owned atoms first, ghosts
+    in atom order, then lexicographic shift order."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    h = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    hinv, m, _ = cell_margins(h, rghost)
+    n = pos.shape[0]
+    s = (pos[:, 0:1] * hinv[0] + pos[:, 1:2] * hinv[1]) + pos[:, 2:3] * hinv[2]
+    s = s - np.floor(s)
+    s[~(s < 1.0)] = 0.0                                      # floor() rounding at the upper edge
+    lo = np.ceil(-m - s).astype(np.int64)                    # allowed shifts: lo <= n_a <= hi, lo <= 0 <= hi
+    hi = np.ceil(1.0 + m - s).astype(np.int64) - 1
+    wrapped = (s[:, 0:1] * h[0] + s[:, 1:2] * h[1]) + s[:, 2:3] * h[2]
+    owners, shifts = [np.arange(n)], [np.zeros((n, 3), dtype=np.int64)]
+    if n:
+        for sx in range(int(lo[:, 0].min()), int(hi[:, 0].max()) + 1):
+            for sy in range(int(lo[:, 1].min()), int(hi[:, 1].max()) + 1):
+                for sz in range(int(lo[:, 2].min()), int(hi[:, 2].max()) + 1):
+                    if sx == sy == sz == 0:
+                        continue
+                    sh = np.array([sx, sy, sz])
+                    idx = np.nonzero(np.all((lo <= sh) & (sh <= hi), axis=1))[0]
+                    if len(idx):
+                        owners.append(idx)
+                        shifts.append(np.tile(sh, (len(idx), 1)))
+    owner = np.concatenate(owners)
+    shift = np.concatenate(shifts)
+    order = np.concatenate([np.arange(n), n + np.argsort(owner[n:], kind="stable")])   # atom order, then shift order
+    owner, shift = owner[order], shift[order]
+    sf = shift.astype(np.float64)
+    x = wrapped[owner] + ((sf[:, 0:1] * h[0] + sf[:, 1:2] * h[1]) + sf[:, 2:3] * h[2])
+    return x, owner, shift
+
+
 def full_neighbor_list(x, nlocal, cutoff, chunk=65536):
     """CSR full list over the first nlocal atoms: every j != i with |x_j - x_i| <= cutoff.  Rows are queried in
     chunks, so the Python lists of a 500k-atom system never exist all at once."""
@@ -94,4 +145,18 @@ def periodic_system(pos, box, types=None, list_cutoff=7.0):
     first, neigh = full_neighbor_list(x, n, list_cutoff)
     return System(x=x, types=np.asarray(types, dtype=np.int32)[owner], nlocal=n, owner=owner,
                   box=np.asarray(box, dtype=np.float64), ilist=np.arange(n, dtype=np.int32),
+                  first=first, neigh=neigh, cutoff=float(list_cutoff))
+
+
+def periodic_system_cell(pos, cell, types=None, list_cutoff=7.0):
+    """periodic_system for any cell (make_ghosts_cell): `box` of the result holds the cell's diagonal only; the
+    owned rows of `x` are the positions wrapped into the cell."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    n = pos.shape[0]
+    if types is None:
+        types = np.ones(n, dtype=np.int32)
+    x, owner, _ = make_ghosts_cell(pos, cell, list_cutoff)
+    first, neigh = full_neighbor_list(x, n, list_cutoff)
+    return System(x=x, types=np.asarray(types, dtype=np.int32)[owner], nlocal=n, owner=owner,
+                  box=np.diag(np.asarray(cell, dtype=np.float64).reshape(3, 3)).copy(), ilist=np.arange(n, dtype=np.int32),
                   first=first, neigh=neigh, cutoff=float(list_cutoff))
