@@ -236,7 +236,8 @@ void mtp_context::plan()
       else if (v == "rebuild" && rebn_ok) cands = {&rebn};
     }
     // the 3-per-SIMD build pays when there are atoms enough to fill twelve wavefronts per CU
-    bool has3 = mtp_wave_kernel_has_wps3(p.fwd_block_count, P);
+    // (slots: the 3-per-SIMD build keeps mu of every slot in one SGPR pair, two bits each; Mu <= 4 and ranks <= 6 give 28)
+    bool has3 = mtp_wave_kernel_has_wps3(p.fwd_block_count, P) && p.slot_count <= 32;
     if (const char *e = std::getenv("MTP_WPS")) has3 = has3 && std::atoi(e) == 3;   // tuning override: 2 = never, 3 = whenever it fits
     else has3 = has3 && !fine;
     // (the grade instantiation spilled 52 dwords at 168 VGPRs and was 2.6 % slower there until the force totals were

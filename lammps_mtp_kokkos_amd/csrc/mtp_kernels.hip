@@ -635,10 +635,34 @@ template <int C> __device__ __forceinline__ double poly_sum(unsigned coef, const
 // dg_s = f'_mu r^-nu - nu g_s / r.
 // GRADE (fused candidate vectors): W[mu] collects this lane's share of W_mu(n) = sum_{s in mu} P_s(r_n) / r_n^nu
 // (pair_mtp_extrapolation.cpp:193-198), again through P_s = (r . grad P_s) / nu.
-template <int NU, int DEG, int PITCH, bool GRADE, bool NODG>
+// The radial function mu of a slot, for the force phase.  The table smu[] in the LDS blob is atom-invariant, and in the
+// nodg layouts the row address of f'_mu depends on it: read where it is needed, every slot of every tile costs two
+// dependent LDS round trips (mu, then f'_mu) instead of one.  The 3-per-SIMD build has Mu <= 4 and ranks <= 6, hence at
+// most 28 slots (the planner checks 32, mtp_context.hip): there the whole table is two bits per slot in one SGPR pair,
+// formed once per wavefront, and a lookup is a shift and a mask (scalar for a uniform slot, v_lshrrev_b64 per lane).
+// The 2-per-SIMD builds keep the reads (PACKED = false): two more SGPRs across the atom loop cost them spills.
+#ifndef MTP_MU_BITS
+#define MTP_MU_BITS 1   // 0: mu is read from smu[] at the point of use in every build, for A/B runs
+#endif
+template <bool PACKED> struct SlotMu {
+  const int *smu;
+  unsigned long long bits;   // PACKED: mu(s) = bits >> 2 s & 3
+  template <bool NODG, bool GRADE> __device__ __forceinline__ int uniform(int s) const   // s wave-uniform
+  {
+    if constexpr (PACKED) return (int) (bits >> (2 * s)) & 3;
+    else return (NODG || GRADE) ? __builtin_amdgcn_readfirstlane(smu[s]) : 0;
+  }
+  template <bool NODG, bool GRADE> __device__ __forceinline__ int per_lane(int s) const
+  {
+    if constexpr (PACKED) return (int) (bits >> (2 * s)) & 3;
+    else return (NODG || GRADE) ? smu[s] : 0;
+  }
+};
+
+template <int NU, int DEG, int PITCH, bool GRADE, bool NODG, class SMU>
 __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoef, unsigned pcoef_l, int part, double x,
                                              double y, double z, double *m, double &UA, double &VA, double &UB,
-                                             double &VB, const int *smu, double inv, double rw, double *W)
+                                             double &VB, const SMU &smu, double inv, double rw, double *W)
 {
   if constexpr (NU <= DEG) {
     constexpr int C = NU * (NU + 1) / 2;   // monomials of degree NU-1
@@ -655,7 +679,7 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
         unsigned cg = pcol + 8u * (unsigned) (s0 * PITCH);
         for (int it = 0; it < cnt; it++) {
           // the slot, hence mu, is wave-uniform in this pass
-          const int mu = (NODG || GRADE) ? __builtin_amdgcn_readfirstlane(smu[s0 + it]) : 0;
+          const int mu = smu.template uniform<NODG, GRADE>(s0 + it);
           const double g = lds_ld(cg, 0);
           const double dg = NODG ? lds_ld(pfp + 8u * (unsigned) (mu * PITCH), 0) : lds_ld(cg + dgo, 0);   // NODG: f'_mu (mu: SGPR)
           const double G = poly_sum<C>(ca, m);
@@ -680,7 +704,7 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
         const unsigned cb = pc + 8u * (unsigned) (kp->deg_coef[NU] + C) + (unsigned) mul24(sc, 8 * 3 * C);
         const unsigned cg = pcol + (unsigned) mul24(s0 + sc, 8 * PITCH);
         // (the halves hold different slots, hence different mu: a per-lane value here)
-        const int mu_raw = (NODG || GRADE) ? smu[s0 + sc] : 0;
+        const int mu_raw = smu.template per_lane<NODG, GRADE>(s0 + sc);
         const double g_raw = lds_ld(cg, 0);
         const double dg_raw = NODG ? lds_ld(pfp + (unsigned) mul24(mu_raw, 8 * PITCH), 0) : lds_ld(cg + dgo, 0);
         const double G = poly_sum<C>(cb, m);
@@ -791,6 +815,21 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
   bt.leaf_cf = reinterpret_cast<const double *>(sh + kp->off_leaf_cf);   // (behind the rows: valid when rows_in_lds)
   bt.leaf_cb = reinterpret_cast<const double *>(sh + kp->off_leaf_cb);
   const bool rows_lds = kp->rows_in_lds != 0;
+  // (not in the KL = 16 grade build: there the SGPR pair costs a twelfth spilled VGPR dword)
+  constexpr bool MU_PACKED = MTP_MU_BITS && WPS == 3 && !(GRADE && KL == 16);
+  SlotMu<MU_PACKED> smu{bt.smu, 0ull};
+  if constexpr (MU_PACKED) {   // lane s holds mu(s): bit 0 of every slot by one ballot, bit 1 by another, interleaved
+    const int mu_l = lane < min(kp->nslot, 32) ? bt.smu[lane] : 0;
+    const unsigned long long b0 = __ballot((mu_l & 1) != 0), b1 = __ballot((mu_l & 2) != 0);
+    auto spread = [](unsigned long long x) {   // bit k -> bit 2 k (k < 32)
+      x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+      x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+      x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+      x = (x | (x << 2)) & 0x3333333333333333ull;
+      return (x | (x << 1)) & 0x5555555555555555ull;
+    };
+    smu.bits = spread(b0) | (spread(b1) << 1);
+  }
 
   const int kl = lane & (KL - 1), q = lane / KL;
   const unsigned wave_off = (kp->blob_bytes >> 3) + wave * kp->wave_doubles;   // doubles
@@ -1174,7 +1213,7 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
               constexpr int i = decltype(I)::value;
               const int sidx = s4 + i;
               if (i == 0 || sidx < n0) {   // (uniform)
-                const int mu = (nodg || GRADE) ? __builtin_amdgcn_readfirstlane(bt.smu[sidx]) : 0;
+                const int mu = nodg ? smu.template uniform<true, GRADE>(sidx) : smu.template uniform<false, GRADE>(sidx);
                 fmac_row_bcast1<i>(S0, c, lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0));
                 if (GRADE) {
                   const double dk = row_bcast<i>(c);
@@ -1191,7 +1230,7 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
 #else
           for (int sidx = 0; sidx < n0; sidx++) {
             const double dk = w.coef[kp->deg_coef[0] + sidx];
-            const int mu = (nodg || GRADE) ? __builtin_amdgcn_readfirstlane(bt.smu[sidx]) : 0;
+            const int mu = nodg ? smu.template uniform<true, GRADE>(sidx) : smu.template uniform<false, GRADE>(sidx);
             S0 = fma(lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0), dk, S0);
             if (GRADE) {
 #pragma unroll
@@ -1203,12 +1242,12 @@ __global__ void __launch_bounds__(WPS == 3 ? 768 : 512, WPS) mtp_wave_kernel(con
         double mono[DEG * (DEG + 1) / 2];
         mono[0] = 1.0;
         if (nodg) {
-          force_degree<1, DEG, PITCH, GRADE, true>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, bt.smu, inv, inv, Wm);
+          force_degree<1, DEG, PITCH, GRADE, true>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, smu, inv, inv, Wm);
           // dg_s / nu = f'_mu r^-nu / nu - g_s / r: the second term of every slot at once
           VA = fma(-inv, UA, VA);
           VB = fma(-inv, UB, VB);
         } else if constexpr (!NODG_CT) {
-          force_degree<1, DEG, PITCH, GRADE, false>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, bt.smu, inv, inv, Wm);
+          force_degree<1, DEG, PITCH, GRADE, false>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, smu, inv, inv, Wm);
         }
         if (fused) {
           // c[jt][mu][ri] += sum_n [type_n = jt] Q_ri(r_n) W_mu(n)  (pair_mtp_extrapolation.cpp:193-198, 323-329):
@@ -1861,6 +1900,9 @@ const char *mtp_kernel_build_flags()
 #endif
 #if MTP_E_HOIST != 1
       "MTP_E_HOIST=" MTP_STR(MTP_E_HOIST) " "
+#endif
+#if MTP_MU_BITS != 1
+      "MTP_MU_BITS=" MTP_STR(MTP_MU_BITS) " "
 #endif
 
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
