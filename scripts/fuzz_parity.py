@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Open-ended randomised GPU-vs-oracle parity sweep (the fixed-seed cases of tests/test_gpu_fuzz.py run the same
 function under `pytest -m gpu`).
-  python scripts/fuzz_parity.py [cases] [seed]"""
+  python scripts/fuzz_parity.py [--stars] [cases] [seed]
+--stars: the cases on disjoint stars with exact neighbour counts (tests/_stars.py), judged per star."""
 import os
 import sys
 import tempfile
@@ -13,11 +14,22 @@ os.environ.setdefault("MTP_BANK_SCALE", "1")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests._fuzz import fuzz_case  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _fuzz import fuzz_case, fuzz_star_case  # noqa: E402
 
-ncase = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 2026)
+args = [a for a in sys.argv[1:] if a != "--stars"]
+ncase = int(args[0]) if len(args) > 0 else 12
+rng = np.random.default_rng(int(args[1]) if len(args) > 1 else 2026)
 tmp = tempfile.mkdtemp()
+if "--stars" in sys.argv[1:]:
+    worst = 0.0
+    for case in range(ncase):
+        desc, w = fuzz_star_case(rng, tmp, "s%d" % case)       # (asserts the per-star tolerance itself)
+        worst = max(worst, *w.values())
+        print("case %2d %s  error / per-star tolerance %s" % (case, desc, " ".join("%s %.1e" % kv for kv in w.items())),
+              flush=True)
+    print("fuzz_parity --stars: worst error / per-star tolerance %.2e" % worst)
+    sys.exit(0 if worst <= 1.0 else 1)
 worst = 0.0
 for case in range(ncase):
     desc, err = fuzz_case(rng, tmp, "p%d" % case)
