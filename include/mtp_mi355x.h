@@ -232,6 +232,20 @@ int mtp_context_plan_info(const mtp_context *ctx, int32_t *waves_per_simd, int32
 /* per-atom LDS layout of the force calls' plan (after a set_neighbors call): 0 keep, 1 lean (no dg rows),
  * 2 rebuild, 3 rebuild without dg rows (MTP_LAYOUT = keep | lean | rebuild | rebuild-nodg forces one) */
 int mtp_context_layout_mode(const mtp_context *ctx, int32_t *mode);
+/* The launch plan without a device (host only).  For a list of `inum` rows with at most `max_numneigh` entries each on a
+ * GPU of `num_cus` compute units, `variant` as in mtp_context_set_variant, `grade` = a call with grades:
+ * mtp_plan_fixed_fields writes, as "name=value" lines, the force kernel's template arguments (KL NB PITCH GRADE DEG WPS)
+ * and every field of the kernel's argument block that the potential's table structure and the plan decide -- the
+ * fields a fixed-shape instantiation of the kernel may hold as compile-time constants (csrc/mtp_shape_fields.hpp);
+ * mtp_plan_fixed_shape writes the name of the compiled fixed-shape kernel such a launch runs, or "" when it runs a
+ * generic one.  A launch runs a fixed-shape kernel only when every field that shape fixes equals the launch's value. */
+int mtp_plan_fixed_fields(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade,
+                          char *buf, int buflen);
+int mtp_plan_fixed_shape(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade,
+                         char *name, int namelen);
+/* name of the fixed-shape kernel the context's last force launch ran, "" for a generic kernel (MTP_FIXED_SHAPE=0 in
+ * the environment, read at every launch, keeps all launches on the generic kernels: tests and A/B runs) */
+int mtp_context_last_shape(const mtp_context *ctx, char *name, int namelen);
 /* last kernel time of the dominant kernel in ms, measured with HIP events on the launch
  * stream (enable with mtp_context_set_timing(ctx, 1); costs one event pair per call) */
 int mtp_context_set_timing(mtp_context *ctx, int enable);

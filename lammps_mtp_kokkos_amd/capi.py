@@ -35,6 +35,7 @@ EXPORTS = [
     "mtp_ghosts_reverse", "mtp_ghosts_reverse_finish", "mtp_ghosts_types", "mtp_nve_initial", "mtp_nve_final", "mtp_nve_monitor",
     "mtp_context_set_deterministic", "mtp_zero_async", "mtp_potential_kernel_shape", "mtp_context_layout_mode",
     "mtp_ghosts_build_cell", "mtp_ghosts_cell_bounds",
+    "mtp_plan_fixed_fields", "mtp_plan_fixed_shape", "mtp_context_last_shape",
 ]
 HALO_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX = 0, 1
@@ -187,6 +188,29 @@ class Potential:
             raise MtpError(rc, "%d head x tail blocks: no force kernel instantiation fits" % a.value)
         return dict(fwd_blocks=a.value, block_lanes=b.value, blocks_per_lane=c.value, max_degree=d.value)
 
+    def plan_fixed_fields(self, num_cus, inum, max_numneigh, variant=VARIANT_AUTO, grade=False):
+        """the force kernel's template arguments and the fields of its argument block that the table structure and the
+        launch plan decide, without a device (mtp_plan_fixed_fields): {name: int, or list of ints}, in the library's order"""
+        buf = C.create_string_buffer(8192)
+        rc = lib().mtp_plan_fixed_fields(self.h, int(num_cus), int(inum), int(max_numneigh), int(variant), int(bool(grade)),
+                                         buf, 8192)
+        if rc:
+            raise MtpError(rc, "plan_fixed_fields")
+        out = {}
+        for line in buf.value.decode().splitlines():
+            k, v = line.split("=")
+            out[k] = [int(x) for x in v.split(",")] if "," in v else int(v)
+        return out
+
+    def plan_fixed_shape(self, num_cus, inum, max_numneigh, variant=VARIANT_AUTO, grade=False):
+        """name of the fixed-shape kernel such a launch would run, "" for a generic one (no device needed)"""
+        buf = C.create_string_buffer(128)
+        rc = lib().mtp_plan_fixed_shape(self.h, int(num_cus), int(inum), int(max_numneigh), int(variant), int(bool(grade)),
+                                        buf, 128)
+        if rc:
+            raise MtpError(rc, "plan_fixed_shape")
+        return buf.value.decode()
+
     def cfg_grade(self, coeff_ders):
         g = C.c_double(0)
         c = np.ascontiguousarray(coeff_ders, dtype=np.float64)
@@ -317,6 +341,12 @@ class Context:
 
     def synchronize(self, stream=None):
         self._check(lib().mtp_synchronize(self.h, C.c_void_p(stream) if stream else None))
+
+    def last_shape(self):
+        """name of the fixed-shape kernel the last force launch ran, "" for a generic kernel"""
+        buf = C.create_string_buffer(128)
+        self._check(lib().mtp_context_last_shape(self.h, buf, 128))
+        return buf.value.decode()
 
     def plan_info(self):
         a, b = C.c_int32(), C.c_int32()

@@ -11,6 +11,7 @@
 
 #include "../../include/mtp_mi355x.h"
 #include "mtp_device.hpp"
+#include "mtp_shape_fields.hpp"
 #include "mtp_potential.hpp"
 
 namespace {
@@ -118,16 +119,32 @@ struct mtp_context {
   bool timed = false;
 
   MtpDevParams base{};
+  const char *last_shape = "";   // name of the fixed-shape kernel the last force launch ran ("": a generic kernel)
 
   void plan();
 };
 
+namespace {
+
+// the four prefixes of the table blob a launch plan may copy into LDS (mtp_context: blob_bytes_*)
+struct BlobSizes {
+  int core = 0, tgt = 0, norows = 0, rows = 0;
+};
+
+}   // namespace
+
 // Choose the workgroup shape from the LDS budget (160 KiB / CU): every workgroup carries one copy
 // of the table blob plus one private region per wavefront.  Grade calls need extra table rows
 // (r^-nu, Q_ri) and scratch, so they get their own plan.
-void mtp_context::plan()
+//
+// Host only: the arithmetic needs the potential, the prefixes of its table blob, the CU count and the size of the list
+// (mtp_plan_fixed_fields asks it on machines without a device).
+static void plan_launch(const mtp_potential &p, const BlobSizes &bs, int num_cus, int inum, int max_numneigh, int variant,
+                        mtp_context::LaunchPlan (&lp)[3], MtpDevParams &base)
 {
-  const mtp_potential &p = *pot;
+  using Layout = mtp_context::Layout;
+  using LaunchPlan = mtp_context::LaunchPlan;
+  const int blob_bytes_core = bs.core, blob_bytes_tgt = bs.tgt, blob_bytes_norows = bs.norows, blob_bytes_rows = bs.rows;
   const int A = p.alpha_moment_count, P = p.max_alpha_index_basic;
   int KL = 16, KB = 1;
   (void) mtp_pick_shape(p.alpha_index_basic_count, &KL, &KB);
@@ -358,6 +375,124 @@ void mtp_context::plan()
   base.d_doubles = p.stored_moment_count;
 }
 
+void mtp_context::plan()
+{
+  BlobSizes bs;
+  bs.core = blob_bytes_core;
+  bs.tgt = blob_bytes_tgt;
+  bs.norows = blob_bytes_norows;
+  bs.rows = blob_bytes_rows;
+  plan_launch(*pot, bs, num_cus, inum, max_numneigh, variant, lp, base);
+}
+
+// the part of a launch's argument block that its plan decides
+static void apply_plan(MtpDevParams &p, const mtp_context::LaunchPlan &L, const mtp_potential &pot, bool grade)
+{
+  p.tab_rows = L.tab_rows;
+  p.m_doubles = L.m_doubles;
+  p.Am = grade ? pot.alpha_moment_count : pot.stored_moment_count;
+  p.ov_doubles = L.ov_doubles;
+  p.rebuild_tables = L.rebuild ? 1 : 0;
+  p.rows_in_lds = L.rows_lds ? 1 : 0;
+  p.blob_bytes = L.blob_bytes;
+  p.tgt_in_lds = L.tgt_lds ? 1 : 0;
+  p.dg_mode = L.layout.mode;
+  p.pow_row = L.layout.pow_row;
+  p.dg_off = L.layout.dg_off;
+  p.fp_row = L.layout.fp_row;
+  p.w_m = L.layout.off_m;
+  p.w_d = L.layout.off_d;
+  p.w_coef = L.layout.off_coef;
+  p.w_nb = L.layout.off_nb;
+  p.wps = L.wps;
+  p.wave_doubles = L.wave_doubles;
+  p.grade_flag = grade ? 1 : 0;
+}
+
+namespace {
+
+// The table blob every workgroup copies into LDS and its offsets in the argument block (host only; the pointers of the
+// HBM / L2 copies are the context's business).
+void build_blob(const mtp_potential &pot, const std::vector<MtpRow8> &rows8, MtpDevParams &bb, BlobSizes &bs,
+                std::vector<unsigned char> &blob)
+{
+  // The packed rows are the LAST piece of the blob: a launch plan copies them into LDS (blob_bytes_rows) or leaves
+  // them in HBM/L2 (blob_bytes_norows) -- measured at level 16: rows in LDS are 1.2 % faster when they fit beside
+  // the wavefronts' private regions anyway, and < 1 % slower otherwise (row reads do not depend on data).
+  auto put = [&](const void *src, size_t bytes) {
+    size_t off = (blob.size() + 15) / 16 * 16;
+    blob.resize(off + bytes, 0);
+    if (bytes) std::memcpy(blob.data() + off, src, bytes);
+    return (int) off;
+  };
+  bb.off_level = put(pot.level_offset.data(), pot.level_offset.size() * sizeof(int32_t));
+  bb.off_seg_fwd = put(pot.seg_fwd.data(), pot.seg_fwd.size() * sizeof(int32_t));
+  bb.off_seg_bwd = put(pot.seg_bwd.data(), pot.seg_bwd.size() * sizeof(int32_t));
+  std::vector<int32_t> slot_pad((size_t) pot.radial_func_count * MTP_PSTRIDE, -1);
+  for (int mu = 0; mu < pot.radial_func_count; mu++)
+    for (int nu = 0; nu < pot.max_alpha_index_basic; nu++)
+      slot_pad[(size_t) mu * MTP_PSTRIDE + nu] = pot.slot_of[(size_t) mu * pot.max_alpha_index_basic + nu];
+  bb.off_slot = put(slot_pad.data(), slot_pad.size() * sizeof(int32_t));
+  bb.off_radial = put(pot.radial_basis_coeffs.data(), pot.radial_basis_coeffs.size() * sizeof(double));
+  // scalar-side tables (24 B per basis function): LDS when they are small, HBM/L2 otherwise
+  bb.scalars_in_lds = (pot.e_map.size() + pot.seed_idx.size()) * 12 <= 4096;
+  if (const char *e = std::getenv("MTP_SCALARS_LDS")) bb.scalars_in_lds = std::atoi(e) != 0;   // tuning override
+  if (bb.scalars_in_lds) {
+    bb.off_seed_idx = put(pot.seed_idx.data(), pot.seed_idx.size() * sizeof(int32_t));
+    bb.off_seed_val = put(pot.seed_val.data(), pot.seed_val.size() * sizeof(double));
+    bb.off_map = put(pot.e_map.data(), pot.e_map.size() * sizeof(int32_t));
+    bb.off_lin = put(pot.e_lin.data(), pot.e_lin.size() * sizeof(double));
+  } else {
+    bb.off_seed_idx = bb.off_seed_val = bb.off_map = bb.off_lin = 0;
+  }
+  bb.off_smu = put(pot.slot_mu.data(), pot.slot_mu.size() * sizeof(int32_t));
+  bb.off_fwd = put(pot.fwd_blocks.data(), pot.fwd_blocks.size() * sizeof(int32_t));
+  bb.nfb = pot.fwd_block_count;
+  blob.resize((blob.size() + 15) / 16 * 16, 0);
+  bs.core = (int) blob.size();
+  bb.off_coef = put(pot.basic_tgt.data(), pot.basic_tgt.size() * sizeof(int32_t));
+  blob.resize((blob.size() + 15) / 16 * 16, 0);
+  bs.tgt = (int) blob.size();
+  bb.off_pack = put(pot.basic_pack_lds.data(), pot.basic_pack_lds.size() * sizeof(int32_t));
+  blob.resize((blob.size() + 15) / 16 * 16, 0);
+  bs.norows = (int) blob.size();
+  bb.off_rows = put(rows8.data(), rows8.size() * sizeof(MtpRow8));
+  bb.off_leaf_cf = put(pot.leaf_cf.data(), pot.leaf_cf.size() * sizeof(double));
+  bb.off_leaf_cb = pot.leaf_cb == pot.leaf_cf ? bb.off_leaf_cf : put(pot.leaf_cb.data(), pot.leaf_cb.size() * sizeof(double));
+  blob.resize((blob.size() + 15) / 16 * 16, 0);
+  bs.rows = (int) blob.size();
+  bb.blob_bytes = bs.norows;   // plan() decides per launch plan
+  bb.rows_in_lds = 0;
+}
+
+// the sizes and counts of the potential's tables in the argument block (host only)
+void fill_sizes(const mtp_potential &pot, MtpDevParams &b)
+{
+  b.Sp = pot.species_count;
+  b.R = pot.radial_basis_size;
+  b.Mu = pot.radial_func_count;
+  b.P = pot.max_alpha_index_basic;
+  b.A = pot.alpha_moment_count;
+  b.B = pot.alpha_index_basic_count;
+  b.T = pot.alpha_index_times_count;
+  b.S = pot.alpha_scalar_count;
+  b.C = pot.coeff_count;
+  b.nslot = pot.slot_count;
+  b.coef_total = pot.coef_total;
+  b.coef_dense = pot.coef_dense;
+  for (int d = 0; d <= MTP_PSTRIDE; d++) {
+    b.deg_first[d] = pot.deg_first[d];
+    b.deg_coef[d] = pot.deg_coef[d];
+  }
+  b.nlevels = pot.normal_levels;   // (the level table has one more entry: the leaf rows)
+  b.nseed = (int) pot.seed_idx.size();
+  b.Ad = pot.stored_moment_count;
+  b.Am = b.Ad;                      // per launch: the grade instantiation keeps the leaves' values too
+  b.Se = (int) pot.e_map.size();
+}
+
+}   // namespace
+
 extern "C" {
 
 int mtp_potential_load(const char *path, int want_selection, mtp_potential **out, char *err, int errlen)
@@ -511,36 +646,13 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
     pack_prog(pot->prog_bwd, c->d_prog_bwd);
     // table blob copied into LDS by every workgroup
     MtpDevParams &bb = c->base;
-    // The packed rows are the LAST piece of the blob: a launch plan copies them into LDS (blob_bytes_rows) or leaves
-    // them in HBM/L2 (blob_bytes_norows) -- measured at level 16: rows in LDS are 1.2 % faster when they fit beside
-    // the wavefronts' private regions anyway, and < 1 % slower otherwise (row reads do not depend on data).
     std::vector<unsigned char> blob;
-    auto put = [&](const void *src, size_t bytes) {
-      size_t off = (blob.size() + 15) / 16 * 16;
-      blob.resize(off + bytes, 0);
-      if (bytes) std::memcpy(blob.data() + off, src, bytes);
-      return (int) off;
-    };
-    bb.off_level = put(pot->level_offset.data(), pot->level_offset.size() * sizeof(int32_t));
-    bb.off_seg_fwd = put(pot->seg_fwd.data(), pot->seg_fwd.size() * sizeof(int32_t));
-    bb.off_seg_bwd = put(pot->seg_bwd.data(), pot->seg_bwd.size() * sizeof(int32_t));
-    std::vector<int32_t> slot_pad((size_t) pot->radial_func_count * MTP_PSTRIDE, -1);
-    for (int mu = 0; mu < pot->radial_func_count; mu++)
-      for (int nu = 0; nu < pot->max_alpha_index_basic; nu++)
-        slot_pad[(size_t) mu * MTP_PSTRIDE + nu] = pot->slot_of[(size_t) mu * pot->max_alpha_index_basic + nu];
-    bb.off_slot = put(slot_pad.data(), slot_pad.size() * sizeof(int32_t));
-    bb.off_radial = put(pot->radial_basis_coeffs.data(), pot->radial_basis_coeffs.size() * sizeof(double));
-    // scalar-side tables (24 B per basis function): LDS when they are small, HBM/L2 otherwise
-    bb.scalars_in_lds = (pot->e_map.size() + pot->seed_idx.size()) * 12 <= 4096;
-    if (const char *e = std::getenv("MTP_SCALARS_LDS")) bb.scalars_in_lds = std::atoi(e) != 0;   // tuning override
-    if (bb.scalars_in_lds) {
-      bb.off_seed_idx = put(pot->seed_idx.data(), pot->seed_idx.size() * sizeof(int32_t));
-      bb.off_seed_val = put(pot->seed_val.data(), pot->seed_val.size() * sizeof(double));
-      bb.off_map = put(pot->e_map.data(), pot->e_map.size() * sizeof(int32_t));
-      bb.off_lin = put(pot->e_lin.data(), pot->e_lin.size() * sizeof(double));
-    } else {
-      bb.off_seed_idx = bb.off_seed_val = bb.off_map = bb.off_lin = 0;
-    }
+    BlobSizes bs;
+    build_blob(*pot, rows8, bb, bs, blob);
+    c->blob_bytes_core = bs.core;
+    c->blob_bytes_tgt = bs.tgt;
+    c->blob_bytes_norows = bs.norows;
+    c->blob_bytes_rows = bs.rows;
     c->d_seed_idx.upload(pot->seed_idx, st);
     c->d_seed_val.upload(pot->seed_val, st);
     c->d_map.upload(pot->e_map, st);
@@ -555,26 +667,8 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
     bb.g_map_all = c->d_map_all.ptr;
     bb.leaf_cf = c->d_leaf_cf.ptr;
     bb.leaf_cb = c->d_leaf_cb.ptr;
-    bb.off_smu = put(pot->slot_mu.data(), pot->slot_mu.size() * sizeof(int32_t));
-    bb.off_fwd = put(pot->fwd_blocks.data(), pot->fwd_blocks.size() * sizeof(int32_t));
-    bb.nfb = pot->fwd_block_count;
-    blob.resize((blob.size() + 15) / 16 * 16, 0);
-    c->blob_bytes_core = (int) blob.size();
-    bb.off_coef = put(pot->basic_tgt.data(), pot->basic_tgt.size() * sizeof(int32_t));
     c->d_tgt.upload(pot->basic_tgt, st);
     bb.g_tgt = c->d_tgt.ptr;
-    blob.resize((blob.size() + 15) / 16 * 16, 0);
-    c->blob_bytes_tgt = (int) blob.size();
-    bb.off_pack = put(pot->basic_pack_lds.data(), pot->basic_pack_lds.size() * sizeof(int32_t));
-    blob.resize((blob.size() + 15) / 16 * 16, 0);
-    c->blob_bytes_norows = (int) blob.size();
-    bb.off_rows = put(rows8.data(), rows8.size() * sizeof(MtpRow8));
-    bb.off_leaf_cf = put(pot->leaf_cf.data(), pot->leaf_cf.size() * sizeof(double));
-    bb.off_leaf_cb = pot->leaf_cb == pot->leaf_cf ? bb.off_leaf_cf : put(pot->leaf_cb.data(), pot->leaf_cb.size() * sizeof(double));
-    blob.resize((blob.size() + 15) / 16 * 16, 0);
-    c->blob_bytes_rows = (int) blob.size();
-    bb.blob_bytes = c->blob_bytes_norows;   // plan() decides per launch plan
-    bb.rows_in_lds = 0;
     c->d_blob.upload(blob.data(), blob.size(), st);
     if (pot->has_selection) {   // inverse active set zero padded to a multiple of 16 for the MFMA grade kernel
       const int C = pot->coeff_count;
@@ -605,27 +699,7 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
     HIP_CHECK(hipStreamSynchronize(st));
 
     MtpDevParams &b = c->base;
-    b.Sp = pot->species_count;
-    b.R = pot->radial_basis_size;
-    b.Mu = pot->radial_func_count;
-    b.P = pot->max_alpha_index_basic;
-    b.A = pot->alpha_moment_count;
-    b.B = pot->alpha_index_basic_count;
-    b.T = pot->alpha_index_times_count;
-    b.S = pot->alpha_scalar_count;
-    b.C = pot->coeff_count;
-    b.nslot = pot->slot_count;
-    b.coef_total = pot->coef_total;
-    b.coef_dense = pot->coef_dense;
-    for (int d = 0; d <= MTP_PSTRIDE; d++) {
-      b.deg_first[d] = pot->deg_first[d];
-      b.deg_coef[d] = pot->deg_coef[d];
-    }
-    b.nlevels = pot->normal_levels;   // (the level table has one more entry: the leaf rows)
-    b.nseed = (int) pot->seed_idx.size();
-    b.Ad = pot->stored_moment_count;
-    b.Am = b.Ad;                      // per launch: the grade instantiation keeps the leaves' values too
-    b.Se = (int) pot->e_map.size();
+    fill_sizes(*pot, b);
     b.rmin = pot->min_cutoff;
     b.rmax = pot->max_cutoff;
     b.scaling = pot->scaling;
@@ -1140,24 +1214,7 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
     if (g >= 8) g = (g + 7) / 8 * 8;   // whole rounds of the 8 XCDs for the XCD-aware atom map
     return std::max(1, g);
   };
-  p.tab_rows = L.tab_rows;
-  p.m_doubles = L.m_doubles;
-  p.Am = grade_flag ? c->pot->alpha_moment_count : c->pot->stored_moment_count;
-  p.ov_doubles = L.ov_doubles;
-  p.rebuild_tables = L.rebuild ? 1 : 0;
-  p.rows_in_lds = L.rows_lds ? 1 : 0;
-  p.blob_bytes = L.blob_bytes;
-  p.tgt_in_lds = L.tgt_lds ? 1 : 0;
-  p.dg_mode = L.layout.mode;
-  p.pow_row = L.layout.pow_row;
-  p.dg_off = L.layout.dg_off;
-  p.fp_row = L.layout.fp_row;
-  p.w_m = L.layout.off_m;
-  p.w_d = L.layout.off_d;
-  p.w_coef = L.layout.off_coef;
-  p.w_nb = L.layout.off_nb;
-  p.wps = L.wps;
-  p.wave_doubles = L.wave_doubles;
+  apply_plan(p, L, *c->pot, grade_flag != 0);
   p.cvec = grade_flag ? c->d_cvec.ptr : nullptr;
   p.cpad = c->cpad;
   // the force kernel writes the radial block of the candidate vectors itself for the common table shape; other
@@ -1183,7 +1240,11 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
       }
       p.fq = c->d_fq.ptr;
     }
-    if (row_count > 0) HIP_CHECK(mtp_launch_wave_kernel(p, grid_for(L, wpb_launch), wpb_launch, lds_launch, st));
+    if (row_count > 0) {
+      const char *used = nullptr;
+      HIP_CHECK(mtp_launch_wave_kernel(p, grid_for(L, wpb_launch), wpb_launch, lds_launch, st, &used));
+      c->last_shape = used ? used : "";
+    }
     if (p.fq) HIP_CHECK(mtp_launch_fixed_to_force(p.fq, d_f, c->nall, st));
     if (c->timing) {
       HIP_CHECK(hipEventRecord(c->ev1, st));
@@ -1347,6 +1408,87 @@ int mtp_debug_read_stamps(mtp_context *c, unsigned long long *out16)
   if (!c || !out16) return MTP_ERR_ARG;
   if (hipMemcpy(out16, c->d_stamps.ptr, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return MTP_ERR_DEVICE;
   (void) hipMemset(c->d_stamps.ptr, 0, 16 * sizeof(unsigned long long));
+  return MTP_OK;
+}
+
+}   // extern "C"
+
+// ---- the plan without a device -------------------------------------------------------------------------------------
+// the argument block of a force (or grade) launch as far as the potential and the plan decide it; pointers stay null
+static int plan_params(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade, MtpDevParams &p)
+{
+  if (!pot || num_cus < 1 || inum < 0 || max_numneigh < 0 || variant < MTP_VARIANT_AUTO || variant > MTP_VARIANT_SMALL)
+    return MTP_ERR_ARG;
+  p = MtpDevParams{};
+  const std::vector<MtpRow8> rows8(pot->rows_by_level.size());   // (only their size matters here)
+  BlobSizes bs;
+  std::vector<unsigned char> blob;
+  build_blob(*pot, rows8, p, bs, blob);
+  fill_sizes(*pot, p);
+  int kl_ = 0, kb_ = 0;
+  if (mtp_pick_fwd_shape(pot->fwd_block_count, &kl_, &kb_) != 0) return MTP_ERR_LIMIT;
+  mtp_context::LaunchPlan lp[3];
+  try {
+    plan_launch(*pot, bs, num_cus, inum, max_numneigh, variant, lp, p);
+  } catch (const HipFail &) {
+    return MTP_ERR_LIMIT;
+  }
+  apply_plan(p, lp[grade ? 2 : 0], *pot, grade != 0);
+  return MTP_OK;
+}
+
+extern "C" {
+
+int mtp_plan_fixed_fields(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade,
+                          char *buf, int buflen)
+{
+  MtpDevParams p;
+  int rc = plan_params(pot, num_cus, inum, max_numneigh, variant, grade, p);
+  if (rc != MTP_OK) return rc;
+  if (!buf || buflen <= 0) return MTP_ERR_ARG;
+  int KL = 0, NB = 0;
+  (void) mtp_pick_fwd_shape(p.nfb, &KL, &NB);
+  const int dlow = mtp_wave_kernel_deg(KL, p.P) == mtp_wave_kernel_dlow(KL);
+  std::string s;
+  auto put = [&](const char *k, int v) { s += std::string(k) + "=" + std::to_string(v) + "\n"; };
+  put("KL", KL);
+  put("NB", NB);
+  put("PITCH", MTP_PITCH);
+  put("GRADE", grade ? 1 : 0);
+  put("DEG", mtp_wave_kernel_deg(KL, p.P));
+  put("WPS", dlow && p.wps == 3 ? 3 : 2);
+#define MTP_X(f) put(#f, p.f);
+  MTP_SHAPE_INT_FIELDS(MTP_X)
+#undef MTP_X
+#define MTP_X(f)                                                                          \
+  {                                                                                       \
+    s += #f "=";                                                                          \
+    for (int k = 0; k < MTP_SHAPE_ARR_LEN; k++) s += (k ? "," : "") + std::to_string(p.f[k]); \
+    s += "\n";                                                                            \
+  }
+  MTP_SHAPE_ARR_FIELDS(MTP_X)
+#undef MTP_X
+  if ((int) s.size() + 1 > buflen) return MTP_ERR_LIMIT;
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return MTP_OK;
+}
+
+int mtp_plan_fixed_shape(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade,
+                         char *name, int namelen)
+{
+  MtpDevParams p;
+  int rc = plan_params(pot, num_cus, inum, max_numneigh, variant, grade, p);
+  if (rc != MTP_OK) return rc;
+  if (!name || namelen <= 0) return MTP_ERR_ARG;
+  const char *m = mtp_fixed_shape_match(p);
+  std::snprintf(name, (size_t) namelen, "%s", m ? m : "");
+  return MTP_OK;
+}
+
+int mtp_context_last_shape(const mtp_context *c, char *name, int namelen)
+{
+  if (!c || !name || namelen <= 0) return MTP_ERR_ARG;
+  std::snprintf(name, (size_t) namelen, "%s", c->last_shape);
   return MTP_OK;
 }
 

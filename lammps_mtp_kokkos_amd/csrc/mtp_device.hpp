@@ -118,7 +118,10 @@ int mtp_pick_fwd_shape(int nblk, int *KL, int *NB);
 // The single rule for launch_pitch, mtp_wave_kernel_has_wps3 and mtp_potential_kernel_shape.
 constexpr int mtp_wave_kernel_dlow(int KL) { return KL <= 32 ? 6 : 8; }
 constexpr int mtp_wave_kernel_deg(int KL, int P) { return P - 1 <= mtp_wave_kernel_dlow(KL) ? mtp_wave_kernel_dlow(KL) : 11; }
-hipError_t mtp_launch_wave_kernel(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st);
+// launches the first compiled fixed-shape kernel (mtp_shape_fields.hpp) whose fixed fields all equal the launch's, else
+// (or with MTP_FIXED_SHAPE=0 in the environment, read per launch) the generic kernel; *used: that shape's name or nullptr
+hipError_t mtp_launch_wave_kernel(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st,
+                                  const char **used = nullptr);
 bool mtp_wave_kernel_has_wps3(int nfb, int P);
 hipError_t mtp_launch_ev_finish(double *ev_slots, double *ev, hipStream_t st);
 hipError_t mtp_launch_ev_finish_unpack(double *ev_slots, double *ev, int fold, double *f, const int *idx, const double *frecv,

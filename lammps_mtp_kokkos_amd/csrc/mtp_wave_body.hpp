@@ -1,0 +1,731 @@
+// Device helpers of the force kernel (included by mtp_kernels.hip and mtp_kernels_fixed.hip; internal).  The kernel's
+// statements are in mtp_wave_kernel_body.hpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "mtp_device.hpp"
+
+#include "mtp_kernel_common.hpp"
+#include "mtp_shape_fields.hpp"
+
+namespace {
+
+#ifndef MTP_PU
+#define MTP_PU 2   // times rows in flight per lane in the row-per-lane product passes (4 until the leaf moments and the
+                   // per-tile totals changed the balance: re-measured 1 / 2 / 3 / 4 / 5 / 6 rows: 0.473 / 0.473 / 0.477 / 0.482 /
+                   // 0.486 / 0.496 ms at level 16)
+#endif
+
+// The parameter block is read through the kernarg segment pointer (address space 4: scalar loads from the constant
+// cache that the compiler re-issues where a field is needed) instead of a by-value struct, which it kept in SGPRs
+// across the whole atom loop and spilled into VGPR lanes (a quarter of the static VALU instructions were
+// v_readlane / v_writelane, 255 VGPRs; now 229 and none).  Making the pointer opaque again at every phase boundary
+// was measured 1 % slower.
+typedef const __attribute__((address_space(4))) MtpDevParams *KP;
+
+// One accessor for every field of the argument block that a shape may fix: SHF(field) / SHA(array, index) yield the
+// shape's constant when SH fixes the field and kp->field otherwise (MTP_SHAPE_INT_FIELDS / MTP_SHAPE_ARR_FIELDS are
+// also what the launcher's field-wise match and the generator of mtp_fixed_shapes.hpp are made from).
+namespace shape_get {
+#define MTP_X(f)                                                                  \
+  template <class SH> __device__ __forceinline__ int f(KP kp)                     \
+  {                                                                               \
+    if constexpr (mtp_shape::has_##f<SH>::value) return SH::f;                    \
+    else return kp->f;                                                            \
+  }
+MTP_SHAPE_INT_FIELDS(MTP_X)
+#undef MTP_X
+#define MTP_X(f)                                                                  \
+  template <class SH> __device__ __forceinline__ int f(KP kp, int k)              \
+  {                                                                               \
+    if constexpr (mtp_shape::has_##f<SH>::value) return SH::f(k);                 \
+    else return kp->f[k];                                                         \
+  }
+MTP_SHAPE_ARR_FIELDS(MTP_X)
+#undef MTP_X
+}   // namespace shape_get
+#define SHF(f) (shape_get::f<SH>(kp))
+#define SHA(f, k) (shape_get::f<SH>(kp, (k)))
+
+// f[idx] += v.  Default: native fp64 HBM atomics (the sum depends on the arrival order in the last bits).
+// Deterministic mode (mtp_context_set_deterministic, tests / reproducible goldens): the contributions are added as
+// 64-bit fixed-point integers (2^-40 eV/A resolution, |f| < 2^23), which commute exactly, and converted once at the end.
+#define MTP_FIXED_SCALE 1099511627776.0   // 2^40
+static __device__ __forceinline__ void force_add(KP kp, size_t idx, double v)
+{
+  if (kp->fq) atomicAdd(reinterpret_cast<unsigned long long *>(kp->fq) + idx, (unsigned long long) __double2ll_rn(v * MTP_FIXED_SCALE));
+  else unsafeAtomicAdd(&kp->f[idx], v);
+}
+
+template <int PITCH> struct WaveLds {
+  static constexpr int NT = 32;   // neighbours per tile; the row pitch (33 doubles: odd, so the 32 lanes of a half-wavefront
+                                  // reading 32 different rows of one column hit 32 different 8-byte banks) is the template parameter
+  double *M, *D, *coef, *tab, *nbx, *nby, *nbz, *nbr, *nbi;
+  int *nbj, *nbjt, *cj;
+  unsigned m_addr;   // LDS byte address of M
+  __device__ __forceinline__ unsigned addr(const double *ptr) const { return m_addr + 8u * (unsigned) (ptr - M); }
+  template <class SH> __device__ __forceinline__ WaveLds(double *base, unsigned base_addr, KP kp, SH)
+  {
+    // Layouts of the per-atom image, chosen by the host planner (mtp_context.hip, plan()); all of them are
+    // [tables | overlay | neighbour arrays] with the regions placed through offsets in the parameter block
+    // (dg_mode: bit 0 = no dg rows, bit 1 = rebuild):
+    //   keep     [g rows | dg rows | overlay]: the coordinate-power rows live in the overlay from the tile build to the
+    //            end of the basic-moment pass, the moments / adjoints (later the derivative-polynomial coefficients)
+    //            from there on -- the two are never live together;
+    //   nodg     [g rows | overlay] (Mu <= 4): no dg rows.  d/dr (f_mu / r^nu) = f'_mu / r^nu - nu g / r, so
+    //            sum_s (dg_s / nu) G_s = sum_s f'_mu(s) (r^-nu / nu) G_s - (1/r) sum_s g_s G_s: the tile build parks the
+    //            radial derivatives f'_mu(r) of its neighbour in registers, Mu rows of them (instead of one dg row per
+    //            slot) are written behind the coefficient blocks ahead of the force phase, which multiplies them in
+    //            per slot and subtracts the g sums it forms anyway;
+    //   rebuild  everything overlays everything (potentials with many moments): the moments and adjoints sit on the
+    //            g rows, which are built a second time (with the dg rows unless nodg) ahead of the force phase (the
+    //            coefficient blocks sit behind the rows, the adjoints of the basics D[0, B) in front: the host checks
+    //            that they cannot meet).
+    tab = base;
+    M = tab + SHF(w_m);
+    D = tab + SHF(w_d);
+    coef = tab + SHF(w_coef);
+    nbx = tab + SHF(w_nb);
+    m_addr = base_addr + 8u * (unsigned) (M - tab);
+    nby = nbx + NT;
+    nbz = nby + NT;
+    nbr = nbz + NT;
+    nbi = nbr + NT;
+    nbj = reinterpret_cast<int *>(nbi + NT);
+    nbjt = nbj + NT;
+    cj = nbjt + NT;
+  }
+};
+
+// Phase 2: tables of one tile; columns [0, ntp) are written, ntp = nt rounded up to the
+// neighbour-group count with dummy neighbours sitting exactly on the cutoff (g = dg = 0).
+// with_dg: write the dg rows; do_park (nodg layouts): park[] receives f'_mu(r) of this lane's neighbour for its radial
+// functions mu = h, h + 2 (park[0..1]), from which fp_from_parked() writes the f' rows ahead of the force phase.
+#define MTP_PARK 2   // radial functions per half-wavefront that can be parked: Mu <= 4
+template <int PITCH, class SH>
+__device__ __forceinline__ void build_tile(KP kp, const BlockTables &bt, const WaveLds<PITCH> &w,
+                                           int t0, int cnt, int ntp, bool gather, bool powers, bool with_dg, bool do_park,
+                                           double (&park)[MTP_PARK],
+                                           double xi0, double xi1, double xi2, int i, int itype, int lane)
+{
+  if (gather) {
+    if (lane < ntp) {
+      const bool real = t0 + lane < cnt;
+      const int j = real ? w.cj[t0 + lane] : i;
+      double dx = 0, dy = 0, dz = 0, r = kp->rmax, inv = kp->inv_rmax;
+      if (real) {
+        const double *xj = row3(kp->x, j);
+        dx = xj[0] - xi0;
+        dy = xj[1] - xi1;
+        dz = xj[2] - xi2;
+        sqrt_and_inverse(dx * dx + dy * dy + dz * dz, r, inv);
+      }
+      w.nbx[lane] = dx;
+      w.nby[lane] = dy;
+      w.nbz[lane] = dz;
+      w.nbr[lane] = r;
+      w.nbi[lane] = inv;
+      w.nbj[lane] = j;
+      w.nbjt[lane] = real ? kp->type[j] - 1 : itype;
+    }
+    wave_fence();
+  }
+  // lanes = (neighbour n, half h): one pass over the tile.  The Chebyshev values q_k(r) and derivatives are
+  // shared by all radial functions of the neighbour; half h contracts them for mu = h, h+2, ... and writes
+  // the g / dg rows of those mu; the coordinate-power rows are split x,y | z between the halves.
+  const int Mu = SHF(Mu), P = SHF(P), R = SHF(R);
+  const double mult = 2.0 * kp->inv_span;
+  const int n = lane & 31, h = lane >> 5;
+  if (n < ntp) {
+    const double r = w.nbr[n], inv = w.nbi[n];
+    const int jt = w.nbjt[n];
+    const double d = r - kp->rmax;
+    const double ksi = (2.0 * r - (kp->rmin + kp->rmax)) * kp->inv_span;
+    double *col = w.tab + n;
+    // radial functions of this half: mu = h, h + 2, ...; the first MTP_PARK of them with static indices, so that the
+    // parked derivatives stay in registers (a loop-carried index would put the array into scratch memory)
+    auto each_mu = [&](auto &&body) {
+      double d0 = 0.0, d1 = 0.0;
+      if (h < Mu) d0 = body(h);
+      if (h + 2 < Mu) d1 = body(h + 2);
+      for (int mu = h + 2 * MTP_PARK; mu < Mu; mu += 2) (void) body(mu);
+      if (do_park) {
+        park[0] = d0;
+        park[1] = d1;
+      }
+    };
+    if (R == 8) {   // the MLIP default: basis in registers, coefficients in bursts of 16-byte reads
+      double qv[8], ev[8];
+      qv[0] = kp->scaling * (d * d);
+      qv[1] = kp->scaling * (ksi * d * d);
+      ev[0] = kp->scaling * 2.0 * d;
+      ev[1] = kp->scaling * (mult * d * d + 2.0 * ksi * d);
+#pragma unroll
+      for (int ri = 2; ri < 8; ri++) {   // mtp_rb_chevbyshev_basis.cpp:29-54
+        qv[ri] = 2.0 * ksi * qv[ri - 1] - qv[ri - 2];
+        ev[ri] = 2.0 * (mult * qv[ri - 1] + ksi * ev[ri - 1]) - ev[ri - 2];
+      }
+      each_mu([&](int mu) {
+        const int4 *sl4 = reinterpret_cast<const int4 *>(bt.slot + mu * MTP_PSTRIDE);
+        const int4 sa = sl4[0], sb = sl4[1], sc = sl4[2];
+        const int sv[MTP_PSTRIDE] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w, sc.x, sc.y, sc.z, sc.w};
+        const double2 *c2 = reinterpret_cast<const double2 *>(bt.radial + (mul24(itype * SHF(Sp) + jt, Mu) + mu) * 8);
+        const double2 c01 = c2[0], c23 = c2[1], c45 = c2[2], c67 = c2[3];
+        const double cc[8] = {c01.x, c01.y, c23.x, c23.y, c45.x, c45.y, c67.x, c67.y};
+        double val = cc[0] * qv[0], der = cc[0] * ev[0];
+#pragma unroll
+        for (int ri = 1; ri < 8; ri++) {
+          val = fma(cc[ri], qv[ri], val);
+          der = fma(cc[ri], ev[ri], der);
+        }
+        double rp = 1.0;
+#pragma unroll
+        for (int nu = 0; nu < MTP_PSTRIDE; nu++) {
+          if (nu < P) {
+            const int sidx = sv[nu];
+            const double g = val * rp;
+            if (sidx >= 0) {
+              double *gp = col + mul24(sidx, PITCH);
+              *gp = g;                                                       // f_mu / r^nu
+              if (with_dg) gp[SHF(dg_off)] = der * rp - nu * g * inv;         // d/dr (f_mu / r^nu)
+            }
+            rp *= inv;
+          }
+        }
+        return der;
+      });
+    } else {
+      each_mu([&](int mu) {
+        const int *sl = bt.slot + mu * MTP_PSTRIDE;
+        const double *c = bt.radial + mul24(mul24(itype * SHF(Sp) + jt, Mu) + mu, R);
+        double q0 = kp->scaling * (d * d), q1 = kp->scaling * (ksi * d * d);
+        double e0 = kp->scaling * 2.0 * d, e1 = kp->scaling * (mult * d * d + 2.0 * ksi * d);
+        double val = c[0] * q0, der = c[0] * e0;
+        if (R > 1) {
+          val += c[1] * q1;
+          der += c[1] * e1;
+        }
+        for (int ri = 2; ri < R; ri++) {
+          const double q2 = 2.0 * ksi * q1 - q0;
+          const double e2 = 2.0 * (mult * q1 + ksi * e1) - e0;
+          val += c[ri] * q2;
+          der += c[ri] * e2;
+          q0 = q1;
+          q1 = q2;
+          e0 = e1;
+          e1 = e2;
+        }
+        double rp = 1.0;
+        for (int nu = 0; nu < P; nu++) {
+          const int sidx = sl[nu];
+          const double g = val * rp;
+          if (sidx >= 0) {
+            double *gp = col + mul24(sidx, PITCH);
+            *gp = g;
+            if (with_dg) gp[SHF(dg_off)] = der * rp - nu * g * inv;
+          }
+          rp *= inv;
+        }
+        return der;
+      });
+    }
+    if (powers) {   // rows of one axis: [q] = u^q
+      const double u0 = h == 0 ? w.nbx[n] : w.nbz[n];
+      double *pc = col + mul24(SHF(pow_row) + (h == 0 ? 0 : 2 * P), PITCH);
+      double cur = 1.0;
+      pc[0] = 1.0;
+      for (int q = 1; q < P; q++) {
+        cur *= u0;
+        pc[q * PITCH] = cur;
+      }
+      if (h == 0) {
+        const double u1 = w.nby[n];
+        pc += mul24(P, PITCH);
+        cur = 1.0;
+        pc[0] = 1.0;
+        for (int q = 1; q < P; q++) {
+          cur *= u1;
+          pc[q * PITCH] = cur;
+        }
+      }
+    }
+  }
+  wave_fence();
+}
+
+// nodg layouts, ahead of the force phase: the Mu rows f'_mu(r_n) of the tile from the derivatives the tile build parked
+// in registers (row fp_row + mu; two stores per lane instead of one dg row per slot)
+template <int PITCH, class SH>
+__device__ __forceinline__ void fp_from_parked(KP kp, const WaveLds<PITCH> &w, int ntp, const double (&park)[MTP_PARK], int lane)
+{
+  const int n = lane & 31, h = lane >> 5, Mu = SHF(Mu);
+  if (n < ntp) {
+    double *col = w.tab + n + (size_t) SHF(fp_row) * PITCH;
+#pragma unroll
+    for (int mi = 0; mi < MTP_PARK; mi++) {
+      const int mu = 2 * mi + h;
+      if (mu < Mu) col[mul24(mu, PITCH)] = park[mi];
+    }
+  }
+  wave_fence();
+}
+
+// Packed rows carry BYTE offsets (8 x moment index) in their 16-bit fields, so that an LDS address is one
+// v_add_u32_sdwa (base + 16-bit word of the row) instead of a bit-field extract and a shift-add.
+static __device__ __forceinline__ double &at8(double *base, unsigned byte_off)
+{
+  return *reinterpret_cast<double *>(reinterpret_cast<char *>(base) + byte_off);
+}
+static __device__ __forceinline__ const double &at8(const double *base, unsigned byte_off)
+{
+  return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
+// Phase 4a: M[a3] += mult * M[a0] * M[a1], one dependency level at a time.  Rows of one level
+// never write an operand of the same level, so four rows per lane are in flight before their
+// ds_add_f64 issue.  (Two call sites, LDS-resident and HBM-resident rows: a select between the two
+// pointers would go through a generic pointer, which hipcc 7.2 miscompiles on gfx950.)
+template <int U>
+__device__ __forceinline__ void products_forward(const MtpRow8 *rows, const int *level, int nlevels, double *M,
+                                                 int lane)
+{
+  for (int l = 0; l < nlevels; l++) {
+    // levels are padded to whole 64-row blocks on the host (neutral rows): no bounds checks, no lane masks
+    const int beg = __builtin_amdgcn_readfirstlane(level[l]);
+    const int nit = (__builtin_amdgcn_readfirstlane(level[l + 1]) - beg) >> 6;
+    const MtpRow8 *rp = rows + beg + lane;
+    for (int it = 0; it < nit; it += U) {
+      MtpRow8 rw[U];
+      double v[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) rw[u] = rp[64 * min(it + u, nit - 1)];   // uniform clamp: the tail re-reads the last block
+#pragma unroll
+      for (int u = 0; u < U; u++) v[u] = at8(M, rw[u].lo & 0xffffu) * at8(M, rw[u].lo >> 16);
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (it + u < nit) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v[u]);   // uniform branch
+    }
+    wave_fence();
+  }
+}
+
+// Phase 4b: D[a1] += D[a3] mult M[a0]; D[a0] += D[a3] mult M[a1], levels in reverse.
+template <int U>
+__device__ __forceinline__ void products_backward(const MtpRow8 *rows, const int *level, int nlevels,
+                                                  const double *M, double *D, int lane)
+{
+  for (int l = nlevels - 1; l >= 0; l--) {
+    const int beg = __builtin_amdgcn_readfirstlane(level[l]);
+    const int nit = (__builtin_amdgcn_readfirstlane(level[l + 1]) - beg) >> 6;
+    const MtpRow8 *rp = rows + beg + lane;
+    for (int it = 0; it < nit; it += U) {
+      MtpRow8 rw[U];
+      double d3[U], m0[U], m1[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) rw[u] = rp[64 * min(it + u, nit - 1)];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        d3[u] = at8(D, rw[u].hi & 0xffffu) * (double) ((int) rw[u].hi >> 16);
+        m0[u] = at8(M, rw[u].lo & 0xffffu);
+        m1[u] = at8(M, rw[u].lo >> 16);
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++)
+        if (it + u < nit) {
+          lds_add(&at8(D, rw[u].lo >> 16), d3[u] * m0[u]);
+          lds_add(&at8(D, rw[u].lo & 0xffffu), d3[u] * m1[u]);
+        }
+    }
+    wave_fence();
+  }
+}
+
+// Leaf rows (mtp_potential.hpp: products that no row reads, i.e. scalars of the basis; pair_mtp.cpp:204-233).  Their
+// moments have no LDS slot in force calls.  Forward: the row's product goes straight into the site energy,
+// e += cf M[a0] M[a1] with cf = linear coefficient x mult (grade calls also keep M[a3] += mult M[a0] M[a1]: the
+// candidate vector lists the leaves' values).  Reverse: D[a0] += cb M[a1], D[a1] += cb M[a0] with the constant adjoint
+// cb = seed(a3) x mult -- no D[a3] read.  Row per lane as above; the constants are lane-contiguous like the rows.
+// FAR: rows and constants come from HBM / L2 (wide lane grids, whose rows do not fit in LDS): batches of U rows are
+// requested MTP_LD batches ahead of their use, as in the gather passes; otherwise both sit in the LDS blob.
+// REV (MTP_LEAF_SWEEP): the factors are final once the stored levels are done and cb is a constant, so the reverse terms
+// issue in the same sweep from the factors already in registers (D must hold the seeds by then).  Every D slot still
+// receives its seed, then the leaf terms in the same row and lane order, then the level terms: bitwise the same.
+#ifndef MTP_LD
+#define MTP_LD 1   // (2: equal, 4: 2 % slower at level 20)
+#endif
+#ifndef MTP_LEAF_SWEEP
+#define MTP_LEAF_SWEEP 1   // 0: a second pass over the leaf rows for the reverse terms (leaf_backward), for A/B runs
+#endif
+#ifndef MTP_E_HOIST
+#define MTP_E_HOIST 1   // 0: the energy table of the stored scalars is read after the product passes, for A/B runs
+#endif
+template <int U, bool STORE, bool FAR, bool REV = false>
+__device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double *cf, int beg, int nit, double *M, int lane,
+                                               const double *cb = nullptr, double *D_ = nullptr)
+{
+  constexpr int D = FAR ? MTP_LD : 1;
+  constexpr int NC = REV ? 2 : 1;   // constants per row: cf (and cb)
+  double e = 0.0;
+  const MtpRow8 *rp = rows + beg + lane;
+  const double *cp = cf + lane, *bp = REV ? cb + lane : cp;
+  const int nb = (nit + U - 1) / U;
+  MtpRow8 q[D][U];
+  double qc[D][NC][U];
+  auto fetch = [&](int b, MtpRow8 (&r)[U], double (&c)[NC][U]) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int o = 64 * min(b * U + u, nit - 1);   // uniform clamp: the tail re-reads the last block
+      r[u] = rp[o];
+      c[0][u] = cp[o];
+      if constexpr (REV) c[NC - 1][u] = bp[o];
+    }
+  };
+  if (FAR) {
+#pragma unroll
+    for (int d = 0; d < D; d++)
+      if (d < nb) fetch(d, q[d], qc[d]);   // uniform
+  }
+  for (int b0 = 0; b0 < nb; b0 += D) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      const int b = b0 + d;
+      if (b < nb) {   // uniform
+        MtpRow8 rw[U];
+        double c[NC][U], m0[U], m1[U];
+        if (FAR) {
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            rw[u] = q[d][u];
+#pragma unroll
+            for (int k = 0; k < NC; k++) c[k][u] = qc[d][k][u];
+          }
+          if (b + D < nb) fetch(b + D, q[d], qc[d]);   // uniform
+        } else {
+          fetch(b, rw, c);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          m0[u] = at8(M, rw[u].lo & 0xffffu);
+          m1[u] = at8(M, rw[u].lo >> 16);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+          if (b * U + u < nit) {   // uniform branch
+            const double v = m0[u] * m1[u];
+            e = fma(c[0][u], v, e);
+            if (STORE) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v);
+            if constexpr (REV) {
+              lds_add(&at8(D_, rw[u].lo >> 16), c[NC - 1][u] * m0[u]);
+              lds_add(&at8(D_, rw[u].lo & 0xffffu), c[NC - 1][u] * m1[u]);
+            }
+          }
+      }
+    }
+  }
+  if (STORE || REV) wave_fence();
+  return e;
+}
+
+template <int U, bool FAR>
+__device__ __forceinline__ void leaf_backward(const MtpRow8 *rows, const double *cb, int beg, int nit, const double *M,
+                                              double *D_, int lane)
+{
+  constexpr int D = FAR ? MTP_LD : 1;
+  const MtpRow8 *rp = rows + beg + lane;
+  const double *cp = cb + lane;
+  const int nb = (nit + U - 1) / U;
+  MtpRow8 q[D][U];
+  double qc[D][U];
+  auto fetch = [&](int b, MtpRow8 (&r)[U], double (&c)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int o = 64 * min(b * U + u, nit - 1);
+      r[u] = rp[o];
+      c[u] = cp[o];
+    }
+  };
+  if (FAR) {
+#pragma unroll
+    for (int d = 0; d < D; d++)
+      if (d < nb) fetch(d, q[d], qc[d]);
+  }
+  for (int b0 = 0; b0 < nb; b0 += D) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+      const int b = b0 + d;
+      if (b < nb) {
+        MtpRow8 rw[U];
+        double c[U], m0[U], m1[U];
+        if (FAR) {
+#pragma unroll
+          for (int u = 0; u < U; u++) {
+            rw[u] = q[d][u];
+            c[u] = qc[d][u];
+          }
+          if (b + D < nb) fetch(b + D, q[d], qc[d]);
+        } else {
+          fetch(b, rw, c);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          m0[u] = at8(M, rw[u].lo & 0xffffu);
+          m1[u] = at8(M, rw[u].lo >> 16);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+          if (b * U + u < nit) {
+            lds_add(&at8(D_, rw[u].lo >> 16), c[u] * m0[u]);
+            lds_add(&at8(D_, rw[u].lo & 0xffffu), c[u] * m1[u]);
+          }
+      }
+    }
+  }
+  wave_fence();
+}
+
+// Phase 4, gather form (round 2).  A level of a pass is a list of chunks; lane l of a group of 64 lanes runs one chunk:
+// acc = sum_u mult_u X[o0_u] Y[o1_u] over its CS operations, then ONE atomic add T[tgt] += acc.  Forward: X = Y = T =
+// moments (rows of one target); reverse: X = adjoints, Y = moments, T = adjoints (the terms of one destination), so a
+// reverse level issues one ds_add_f64 per CS terms instead of two per row.  Operations (8 bytes, lane-contiguous) come
+// from HBM / L2; those of the next trip are requested before the current trip's operands are read (a ring of 2, 4 or
+// 8 trips in flight was measured slower at level 20: 1.46 / 1.50 / 1.60 against 1.40 ms).
+template <int CS>
+__device__ __forceinline__ void gather_groups(const MtpRow8 *rp, int ngroups, const double *X, const double *Y, double *T)
+{
+  constexpr int U = CS >= 4 ? 4 : CS;        // operations of one chunk in flight
+  constexpr int G = CS >= 4 ? 1 : 4 / CS;    // chunks in flight
+  constexpr int PARTS = CS / U;              // trips per chunk (CS = 8: two)
+  const int ntrip = ((ngroups + G - 1) / G) * PARTS;
+  auto fetch = [&](int trip, MtpRow8 (&dst)[G][U]) {
+    const int g0 = (trip / PARTS) * G, part = trip % PARTS;
+#pragma unroll
+    for (int j = 0; j < G; j++)
+#pragma unroll
+      for (int u = 0; u < U; u++) dst[j][u] = rp[64 * (min(g0 + j, ngroups - 1) * CS + part * U + u)];
+  };
+  double acc[G];
+#pragma unroll
+  for (int j = 0; j < G; j++) acc[j] = 0.0;
+  MtpRow8 nxt[G][U];
+  fetch(0, nxt);
+  for (int trip = 0; trip < ntrip; trip++) {
+    MtpRow8 cur[G][U];
+#pragma unroll
+    for (int j = 0; j < G; j++)
+#pragma unroll
+      for (int u = 0; u < U; u++) cur[j][u] = nxt[j][u];
+    if (trip + 1 < ntrip) fetch(trip + 1, nxt);   // uniform
+    double xv[G][U], yv[G][U];
+#pragma unroll
+    for (int j = 0; j < G; j++)
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        xv[j][u] = at8(X, cur[j][u].lo & 0xffffu);
+        yv[j][u] = at8(Y, cur[j][u].lo >> 16);
+      }
+#pragma unroll
+    for (int j = 0; j < G; j++)
+#pragma unroll
+      for (int u = 0; u < U; u++) acc[j] = fma((double) ((int) cur[j][u].hi >> 16) * xv[j][u], yv[j][u], acc[j]);
+    if (trip % PARTS == PARTS - 1) {
+      const int g0 = (trip / PARTS) * G;
+#pragma unroll
+      for (int j = 0; j < G; j++) {
+        if (g0 + j < ngroups) lds_add(&at8(T, cur[j][0].hi & 0xffffu), acc[j]);   // uniform branch
+        acc[j] = 0.0;
+      }
+    }
+  }
+}
+
+// one pass: the levels in the order the segment table lists them (forward: ascending, reverse: descending)
+__device__ __forceinline__ void gather_pass(const MtpRow8 *prog, const int *seg, int nlevels, const double *X,
+                                            const double *Y, double *T, int lane)
+{
+  for (int l = 0; l < nlevels; l++) {
+    const int first = __builtin_amdgcn_readfirstlane(seg[4 * l]), ngroups = __builtin_amdgcn_readfirstlane(seg[4 * l + 1]);
+    const int cs = __builtin_amdgcn_readfirstlane(seg[4 * l + 2]);
+    const MtpRow8 *rp = prog + (size_t) first * 64 + lane;
+    if (cs == 4) gather_groups<4>(rp, ngroups, X, Y, T);
+    else if (cs == 8) gather_groups<8>(rp, ngroups, X, Y, T);
+    else if (cs == 2) gather_groups<2>(rp, ngroups, X, Y, T);
+    else gather_groups<1>(rp, ngroups, X, Y, T);
+    wave_fence();
+  }
+}
+
+// ---- phase 5 helpers ------------------------------------------------------------------------
+// sum_{i<C} coef[i] * m[i]; the coefficient address is the same in all lanes of a half (LDS broadcast)
+#ifndef MTP_POLY_ACC
+#define MTP_POLY_ACC 1   // independent accumulation chains of a derivative polynomial (1 | 2 | 4 measured at 65,536 atoms: 0.4367 | 0.4388 | 0.4406 ms; no difference at 2,048)
+#endif
+template <int C> __device__ __forceinline__ double poly_eval(unsigned coef, const double *m)
+{
+  constexpr int NA = MTP_POLY_ACC;
+  double a[NA];
+#pragma unroll
+  for (int k = 0; k < NA; k++) a[k] = 0.0;
+#ifndef MTP_POLY_CH
+#define MTP_POLY_CH 8
+#endif
+  constexpr int CH = MTP_POLY_CH;   // reads per burst
+#pragma unroll
+  for (int i0 = 0; i0 < C; i0 += CH) {
+    double c[CH];
+#pragma unroll
+    for (int u = 0; u < CH; u++)
+      if (i0 + u < C) c[u] = lds_ld(coef, i0 + u);
+#pragma unroll
+    for (int u = 0; u < CH; u++)
+      if (i0 + u < C) a[(i0 + u) % NA] = fma(c[u], m[i0 + u], a[(i0 + u) % NA]);
+  }
+  double r = a[0];
+#pragma unroll
+  for (int k = 1; k < NA; k++) r += a[k];
+  return r;
+}
+
+// The same sum with the coefficients broadcast by DPP instead of by LDS: the lanes of a row of 16 belong to one half
+// (rows 0-1: half 0, rows 2-3: half 1), so coef_l = the block of this lane's half + 8 (lane & 15) bytes reads 16
+// coefficients per ds_read_b64 (one LDS cycle per half-wavefront, 32 consecutive banks: conflict-free), and
+// v_fmac_f64_dpp row_newbcast:i hands coefficient i to its row.  Same FMAs in the same order as poly_eval (bitwise the
+// same G); lanes whose coefficient lies past the block read whatever follows it in the image and are never broadcast.
+#ifndef MTP_COEF_DPP
+#define MTP_COEF_DPP 1   // 0: every coefficient is a broadcast ds_read_b64 (poly_eval), for A/B runs
+#endif
+template <int C, int K0> __device__ __forceinline__ void dpp_chunks(double &a, const double *c, const double *m)
+{
+  if constexpr (K0 < C) {
+    fmac_row_bcast<(C - K0 < 16 ? C - K0 : 16)>(a, c[K0 / 16], m + K0);
+    dpp_chunks<C, K0 + 16>(a, c, m);
+  }
+}
+template <int C> __device__ __forceinline__ double poly_eval_dpp(unsigned coef_l, const double *m)
+{
+  constexpr int K = (C + 15) / 16;   // 16-coefficient chunks: all reads first, one accumulation chain
+  double c[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) c[k] = lds_ld(coef_l, 16 * k);
+  double a = 0.0;
+  dpp_chunks<C, 0>(a, c, m);
+  return a;
+}
+// DPP for C >= 2 only: a single coefficient is one read either way, and the DPP form adds the zeroing of the sum.
+// coef: the block's address, + 8 (lane & 15) bytes where coef_dpp<C>.
+template <int C> constexpr bool coef_dpp = MTP_COEF_DPP && C >= 2;
+template <int C> __device__ __forceinline__ double poly_sum(unsigned coef, const double *m)
+{
+  if constexpr (coef_dpp<C>) return poly_eval_dpp<C>(coef, m);
+  else return poly_eval<C>(coef, m);
+}
+
+// Slots of tensor rank NU: m[] holds the monomials of degree NU-1 of this lane's neighbour, ordered
+// (a descending, then b descending): idx(a, b, c) = j (j + 1) / 2 + c with j = b + c.  A slot's coefficient
+// block is [d/dx | d/dy | d/dz], each over those monomials.  UA/VA collect sum_s g_s dP_s/dx (half 0) or
+// dP_s/dz (half 1) and the same with dg_s / nu; UB/VB the d/dy terms of the slots this half owns.
+// NODG: no dg rows -- VA / VB collect sum_s f'_mu(s) (r^-nu / nu) G_s instead (f'_mu(r) of this lane's neighbour from
+// row fp_row + mu of the tile, rw = r^-NU on entry) and the caller subtracts (UA, UB) / r at the end:
+// dg_s = f'_mu r^-nu - nu g_s / r.
+// GRADE (fused candidate vectors): W[mu] collects this lane's share of W_mu(n) = sum_{s in mu} P_s(r_n) / r_n^nu
+// (pair_mtp_extrapolation.cpp:193-198), again through P_s = (r . grad P_s) / nu.
+// The radial function mu of a slot, for the force phase.  The table smu[] in the LDS blob is atom-invariant, and in the
+// nodg layouts the row address of f'_mu depends on it: read where it is needed, every slot of every tile costs two
+// dependent LDS round trips (mu, then f'_mu) instead of one.  The 3-per-SIMD build has Mu <= 4 and ranks <= 6, hence at
+// most 28 slots (the planner checks 32, mtp_context.hip): there the whole table is two bits per slot in one SGPR pair,
+// formed once per wavefront, and a lookup is a shift and a mask (scalar for a uniform slot, v_lshrrev_b64 per lane).
+// The 2-per-SIMD builds keep the reads (PACKED = false): two more SGPRs across the atom loop cost them spills.
+#ifndef MTP_MU_BITS
+#define MTP_MU_BITS 1   // 0: mu is read from smu[] at the point of use in every build, for A/B runs
+#endif
+template <bool PACKED> struct SlotMu {
+  const int *smu;
+  unsigned long long bits;   // PACKED: mu(s) = bits >> 2 s & 3
+  template <bool NODG, bool GRADE> __device__ __forceinline__ int uniform(int s) const   // s wave-uniform
+  {
+    if constexpr (PACKED) return (int) (bits >> (2 * s)) & 3;
+    else return (NODG || GRADE) ? __builtin_amdgcn_readfirstlane(smu[s]) : 0;
+  }
+  template <bool NODG, bool GRADE> __device__ __forceinline__ int per_lane(int s) const
+  {
+    if constexpr (PACKED) return (int) (bits >> (2 * s)) & 3;
+    else return (NODG || GRADE) ? smu[s] : 0;
+  }
+};
+
+template <int NU, int DEG, int PITCH, bool GRADE, bool NODG, class SH, class SMU>
+__device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoef, unsigned pcoef_l, int part, double x,
+                                             double y, double z, double *m, double &UA, double &VA, double &UB,
+                                             double &VB, const SMU &smu, double inv, double rw, double *W)
+{
+  if constexpr (NU <= DEG) {
+    constexpr int C = NU * (NU + 1) / 2;   // monomials of degree NU-1
+    const unsigned pc = coef_dpp<C> ? pcoef_l : pcoef;   // pcoef_l = pcoef + 8 (lane & 15): DPP chunks (poly_sum)
+    if (NU < SHF(P)) {
+      const int s0 = SHA(deg_first, NU), cnt = SHA(deg_first, NU + 1) - s0;
+      const double inv_nu = 1.0 / NU;
+      const unsigned dgo = 8u * (unsigned) SHF(dg_off);
+      const unsigned pfp = pcol + 8u * (unsigned) (SHF(fp_row) * PITCH);   // f' rows of this lane's column (NODG)
+      const double rwn = rw * inv_nu;
+      const double wa = GRADE ? (part ? z : x) * rwn : 0.0, wb = GRADE ? y * rwn : 0.0;
+      {
+        unsigned ca = pc + 8u * (unsigned) (SHA(deg_coef, NU) + part * 2 * C);
+        unsigned cg = pcol + 8u * (unsigned) (s0 * PITCH);
+        for (int it = 0; it < cnt; it++) {
+          // the slot, hence mu, is wave-uniform in this pass
+          const int mu = smu.template uniform<NODG, GRADE>(s0 + it);
+          const double g = lds_ld(cg, 0);
+          const double dg = NODG ? lds_ld(pfp + 8u * (unsigned) (mu * PITCH), 0) : lds_ld(cg + dgo, 0);   // NODG: f'_mu (mu: SGPR)
+          const double G = poly_sum<C>(ca, m);
+          UA = fma(g, G, UA);
+          VA = fma(dg * (NODG ? rwn : inv_nu), G, VA);
+          if (GRADE) {
+            const double val = G * wa;
+            if (mu == 0) W[0] += val;
+            else if (mu == 1) W[1] += val;
+            else if (mu == 2) W[2] += val;
+            else W[3] += val;
+          }
+          ca += 8u * 3 * C;
+          cg += 8u * PITCH;
+        }
+      }
+      for (int it = 0; 2 * it < cnt; it++) {
+        const int si = 2 * it + part;
+        const bool ok = si < cnt;
+        const int sc = ok ? si : 0;
+        // (per-lane sc: 24-bit multiplies are full rate, 32-bit ones a quarter of it)
+        const unsigned cb = pc + 8u * (unsigned) (SHA(deg_coef, NU) + C) + (unsigned) mul24(sc, 8 * 3 * C);
+        const unsigned cg = pcol + (unsigned) mul24(s0 + sc, 8 * PITCH);
+        // (the halves hold different slots, hence different mu: a per-lane value here)
+        const int mu_raw = smu.template per_lane<NODG, GRADE>(s0 + sc);
+        const double g_raw = lds_ld(cg, 0);
+        const double dg_raw = NODG ? lds_ld(pfp + (unsigned) mul24(mu_raw, 8 * PITCH), 0) : lds_ld(cg + dgo, 0);
+        const double G = poly_sum<C>(cb, m);
+        const double g = ok ? g_raw : 0.0, dg = ok ? dg_raw : 0.0;
+        UB = fma(g, G, UB);
+        VB = fma(dg * (NODG ? rwn : inv_nu), G, VB);
+        const int mu = ok ? mu_raw : -1;
+        if (GRADE) {
+          const double val = G * wb;
+#pragma unroll
+          for (int v = 0; v < 4; v++) W[v] += mu == v ? val : 0.0;
+        }
+      }
+      if constexpr (NU < DEG) {
+        // raise the monomials to degree NU: the new a = 0 tail from the old one, then the head times x
+        constexpr int T0 = (NU - 1) * NU / 2;
+#pragma unroll
+        for (int c = 0; c < NU; c++) m[C + c] = y * m[T0 + c];
+        m[C + NU] = z * m[T0 + NU - 1];
+#pragma unroll
+        for (int i = 0; i < C; i++) m[i] *= x;
+        force_degree<NU + 1, DEG, PITCH, GRADE, NODG, SH>(kp, pcol, pcoef, pcoef_l, part, x, y, z, m, UA, VA, UB, VB, smu, inv, rw * inv, W);
+      }
+    }
+  }
+}
+
+}   // namespace
