@@ -11,9 +11,11 @@
  *
  * Streams.  Device work is ordered on the `stream` (a hipStream_t) given to an entry point.  ONE rule for NULL:
  *   - entry points that take a context (mtp_compute_device[_rows], mtp_build_neighbors_device,
- *     mtp_set_neighbors_device_2d, mtp_synchronize, mtp_halo_force_step, mtp_ghosts_reverse_finish): NULL means the
+ *     mtp_set_neighbors_device_2d, mtp_synchronize, mtp_halo_force_step, mtp_ghosts_reverse_finish,
+ *     mtp_batch_cfg_grades): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
- *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async): NULL is
+ *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
+ *     mtp_batch_reduce): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
  * whose other GPU work runs on the default stream (PyTorch's default) must pass a real stream handle that its own
@@ -383,6 +385,59 @@ int mtp_nve_final(void *stream, int nlocal, double *d_v, const double *d_f, cons
 /* d_out2[0] = max_i |x_i - x_ref_i|^2 (the half-skin re-neighbouring test), d_out2[1] = sum_i m_i v_i^2 */
 int mtp_nve_monitor(void *stream, int nlocal, const double *d_x, const double *d_x_ref, const double *d_v,
                     const int *d_type, const double *d_mass, double *d_out2);
+
+/* ---- batched configurations: many small periodic cells in one device pass ------------------------------------------
+ *
+ * Training and candidate configurations (1 to 200 atoms, each with its own lattice, thousands at a time) are what the
+ * reference evaluates one `run 0` at a time: one PairMTP::compute (pair_mtp.cpp:72-280) or
+ * PairMTPExtrapolation::compute (pair_mtp_extrapolation.cpp:68-382) per configuration, each with its own Comm::borders
+ * and Neighbor build.  Here one pass serves the whole batch: every configuration gets a slot of its own in one large
+ * box (mtp_batch_layout), one ghost build takes a different cell per atom (mtp_ghosts_build_batch), the stock
+ * mtp_build_neighbors_device and ONE force call with MTP_ENERGY_ATOM | MTP_VIRIAL_ATOM run over all rows, and the
+ * per-atom outputs are reduced per configuration (mtp_batch_reduce, mtp_batch_cfg_grades).  Owned atoms of
+ * configuration k are rows [cfg_first[k], cfg_first[k + 1]) of every per-atom array; cfg_first[0] = 0, non-decreasing,
+ * empty configurations allowed.
+ */
+/* Host arithmetic only.  cells[ncfg][9] (rows = lattice vectors, as for mtp_ghosts_build_cell).  The ghost
+ * parallelepiped of configuration k (what mtp_ghosts_cell_bounds reports for its cell and rghost) is translated by
+ * origins[k] into slot k of a 3-D grid of uniform slots, sized by the largest extents in the batch and centred on the
+ * origin; two slots are at least `gap` apart along some axis, so with gap >= the list cutoff (required: gap >= rghost) no
+ * atom or image of one configuration lies within the list cutoff of another and the stock neighbour build keeps them
+ * apart.  lo / hi bound every position of the batch (what mtp_build_neighbors_device wants), *ncells is the number of
+ * list cells (edge rghost) that box implies.  MTP_ERR_ARG for a cell with det <= 0 or non-finite entries: err names the
+ * configuration.  MTP_ERR_LIMIT when the batch would need more than 2^26 list cells (the builder's limit) or a
+ * coordinate beyond 2048 A in magnitude (translation costs bits of the interatomic distances): err names
+ * the first configuration that does not fit and *nfit is the number of leading configurations that do -- the caller
+ * splits the batch there.  On success *nfit = ncfg.  ncells and nfit may be NULL. */
+int mtp_batch_layout(int ncfg, const double *cells /*[ncfg][9]*/, double rghost, double gap, double *origins /*[ncfg][3]*/,
+                     double lo[3], double hi[3], long long *ncells, int *nfit, char *err, int errlen);
+/* mtp_ghosts_build_cell with the cell looked up per atom (Comm::borders of every configuration at once).  cfg_first
+ * [ncfg + 1], cells [ncfg][9] and origins [ncfg][3] are HOST arrays (copied to the device by the call).  Atom i of
+ * configuration k is wrapped into cell k exactly as mtp_ghosts_build_cell wraps it, then translated by origins[k]; its
+ * images are found by the same slab criterion with cell k's margins.  Ghost order as ever: all owned atoms first, then
+ * the ghosts in atom order, then in lexicographic shift order, shift[k] = n . cell of the owner's configuration -- so
+ * mtp_ghosts_forward / reverse / reverse_finish / types work on the handle unchanged.  Capacity protocol, 64-bit total,
+ * the single stream synchronisation and the NULL-stream rule as for mtp_ghosts_build_cell.  MTP_ERR_ARG, nothing
+ * launched, for a cfg_first that does not start at 0 or decreases and for a bad cell (the error names the
+ * configuration). */
+int mtp_ghosts_build_batch(mtp_ghosts *g, void *stream, double *d_x /*[capacity][3]*/, int ncfg, const int *cfg_first,
+                           const double *cells, const double *origins, int capacity, double rghost, int *nall_out);
+/* Per-configuration totals of a force call made with MTP_ENERGY_ATOM | MTP_VIRIAL_ATOM: d_energy[k] = sum of d_eatom,
+ * d_virial[k][6] = sum of d_vatom over the owned rows of configuration k (the reference tallies vatom on the central
+ * atom, pair_mtp.cpp:268-276: ghost rows carry none), same sign and component order as d_ev; d_cfg_grade[k] = max of
+ * d_grades over those rows (neighbourhood mode: pair_mtp_extrapolation.cpp:333-335 per configuration).  Each output
+ * with its input may be NULL.  One wavefront per configuration (its workgroup for segments longer than 256 rows), rows
+ * read coalesced and combined in a fixed order without atomics: a configuration's result does not depend on the rest of
+ * the batch.  An empty configuration gets zeros.  d_cfg_first [ncfg + 1] is a device array.  No context: NULL stream is
+ * rejected. */
+int mtp_batch_reduce(void *stream, int ncfg, const int *d_cfg_first, const double *d_eatom, const double *d_vatom,
+                     const double *d_grades, double *d_energy, double *d_virial, double *d_cfg_grade);
+/* Configuration-mode grades per configuration, after a grade call (grade_flag != 0) over the nrows = cfg_first[ncfg] rows
+ * of the installed list: the context's candidate vectors are summed per configuration (the MPI_Allreduce of
+ * pair_mtp_extrapolation.cpp:369 with one "world" per configuration), graded by the same MFMA kernel as the
+ * neighbourhood grades (calculate_extrapolation_grade, :347-358) and divided by the configuration's atom count, 0 for an
+ * empty one (:373-376).  NULL stream = the context's. */
+int mtp_batch_cfg_grades(mtp_context *ctx, void *stream, int ncfg, const int *d_cfg_first, int nrows, double *d_cfg_grade);
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,12 @@ EXPORTS = [
     "mtp_context_set_deterministic", "mtp_zero_async", "mtp_potential_kernel_shape", "mtp_context_layout_mode",
     "mtp_ghosts_build_cell", "mtp_ghosts_cell_bounds",
     "mtp_plan_fixed_fields", "mtp_plan_fixed_shape", "mtp_context_last_shape",
+    "mtp_batch_layout", "mtp_ghosts_build_batch", "mtp_batch_reduce", "mtp_batch_cfg_grades",
 ]
+# mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
+# workgroup of BATCH_BLOCK threads; the grade kernel behind mtp_batch_cfg_grades takes GRADE_ROWS_PER_BLOCK rows a workgroup
+BATCH_WAVE_LANES, BATCH_WAVE_ROWS, BATCH_BLOCK, GRADE_ROWS_PER_BLOCK = 64, 256, 256, 128
+BATCH_MAX_COORD, BATCH_MAX_CELLS = 2048.0, 2 ** 26
 HALO_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX = 0, 1
 
@@ -342,6 +347,12 @@ class Context:
     def synchronize(self, stream=None):
         self._check(lib().mtp_synchronize(self.h, C.c_void_p(stream) if stream else None))
 
+    def batch_cfg_grades(self, cfg_first_t, nrows, cfg_grade_t, stream=None):
+        """configuration-mode grade of every configuration (rows [cfg_first[k], cfg_first[k + 1]) of the grade call just
+        made over `nrows` rows) into cfg_grade_t [ncfg]: mtp_batch_cfg_grades"""
+        self._check(lib().mtp_batch_cfg_grades(self.h, C.c_void_p(stream) if stream else None, int(cfg_first_t.numel()) - 1,
+                                               _ptr(cfg_first_t), int(nrows), _ptr(cfg_grade_t)))
+
     def last_shape(self):
         """name of the fixed-shape kernel the last force launch ran, "" for a generic kernel"""
         buf = C.create_string_buffer(128)
@@ -539,6 +550,22 @@ class Ghosts:
         self._check(rc)
         return nall.value
 
+    def build_batch(self, x_t, cfg_first, cells, origins, rghost, stream=None):
+        """The same for many cells at once (mtp_ghosts_build_batch): owned atoms of configuration k are rows
+        [cfg_first[k], cfg_first[k + 1]) of x_t, wrapped into cells[k] and translated by origins[k] (host arrays; the origins
+        come from batch_layout).  Same capacity protocol as build()."""
+        cf = np.ascontiguousarray(cfg_first, dtype=np.int32)
+        ncfg = len(cf) - 1
+        c9 = np.ascontiguousarray(cells, dtype=np.float64).reshape(ncfg, 9)
+        o3 = np.ascontiguousarray(origins, dtype=np.float64).reshape(ncfg, 3)
+        nall = C.c_int(0)
+        rc = lib().mtp_ghosts_build_batch(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t), ncfg, _np(cf, C.c_int),
+                                          _np(c9, C.c_double), _np(o3, C.c_double), int(x_t.shape[0]), C.c_double(rghost),
+                                          C.byref(nall))
+        self.nall = nall.value
+        self._check(rc)
+        return nall.value
+
     def forward(self, x_t, stream=None):
         self._check(lib().mtp_ghosts_forward(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t)))
 
@@ -563,6 +590,34 @@ def ghosts_cell_bounds(cell, rghost):
     if rc:
         raise MtpError(rc, "mtp_ghosts_cell_bounds: the cell must be finite with det > 0, rghost > 0")
     return dict(lo=np.array(lo[:]), hi=np.array(hi[:]), volume=vol.value, nimage=np.array(nim[:], dtype=np.int64))
+
+
+def batch_layout(cells, rghost, gap=None):
+    """Host arithmetic (no device): one slot per configuration in one box, any two at least `gap` (default rghost, the list
+    cutoff) apart -- mtp_batch_layout.  cells [ncfg, 3, 3].  Returns dict(origins [ncfg, 3], lo, hi, ncells); raises
+    MtpError with .nfit = the number of leading configurations that do fit when the batch is beyond the layout's limits."""
+    c9 = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1, 9)
+    ncfg = len(c9)
+    org = np.zeros((ncfg, 3))
+    lo, hi, nc, nfit = (C.c_double * 3)(), (C.c_double * 3)(), C.c_longlong(0), C.c_int(0)
+    err = C.create_string_buffer(512)
+    rc = lib().mtp_batch_layout(ncfg, _np(c9, C.c_double), C.c_double(rghost), C.c_double(rghost if gap is None else gap),
+                                _np(org, C.c_double), lo, hi, C.byref(nc), C.byref(nfit), err, 512)
+    if rc:
+        e = MtpError(rc, err.value.decode())
+        e.nfit = nfit.value
+        raise e
+    return dict(origins=org, lo=np.array(lo[:]), hi=np.array(hi[:]), ncells=nc.value)
+
+
+def batch_reduce(cfg_first_t, eatom_t=None, vatom_t=None, grades_t=None, energy_t=None, virial_t=None, cfg_grade_t=None,
+                 stream=None):
+    """per-configuration sums of eatom / vatom and maxima of grades over rows [cfg_first[k], cfg_first[k + 1]), all device
+    tensors (mtp_batch_reduce)"""
+    rc = lib().mtp_batch_reduce(C.c_void_p(stream) if stream else None, int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t),
+                                _ptr(eatom_t), _ptr(vatom_t), _ptr(grades_t), _ptr(energy_t), _ptr(virial_t), _ptr(cfg_grade_t))
+    if rc:
+        raise MtpError(rc, "mtp_batch_reduce: needs a stream, and an input for every output")
 
 
 def nve_initial(nlocal, x_t, v_t, f_t, type_t, inv_mass_t, dtf, dt, stream=None):

@@ -108,6 +108,8 @@ struct mtp_context {
   } lp[3];   // [0] force calls (wavefront per atom), [1] candidate-vector kernel of grade calls, [2] the fused kernel's
              // grade instantiation (its image also holds the leaf moments' values)
   DevBuf<double> d_cvec, d_ainv_pad, d_ainv_tiled, d_dbasic;
+  DevBuf<double> d_csum;   // mtp_batch_cfg_grades: [ncfg][cpad] candidate vectors summed per configuration
+  DevBuf<int> d_ident;     // and the identity ilist its grade launch reads them by
   int cpad = 0, dpad = 0;
   // device-resident outputs of mtp_compute_resident (the /kk styles' DualViews): which of them the last call filled
   bool res_valid = false;
@@ -1283,6 +1285,53 @@ int mtp_compute_device(mtp_context *c, void *stream, const double *d_x, const in
   if (!c) return MTP_ERR_ARG;
   return mtp_compute_device_rows(c, stream, 0, c->inum, 1, d_x, d_type, eflag, vflag, grade_flag, d_f, d_eatom, d_vatom,
                                  d_ev, d_grades, d_max_grade, d_coeff_ders);
+}
+
+// ---- batched configurations (include/mtp_mi355x.h) ----------------------------------------------------------------
+int mtp_batch_reduce(void *stream, int ncfg, const int *d_cfg_first, const double *d_eatom, const double *d_vatom,
+                     const double *d_grades, double *d_energy, double *d_virial, double *d_cfg_grade)
+{
+  if (ncfg < 0 || (ncfg > 0 && !d_cfg_first) || (d_energy && !d_eatom) || (d_virial && !d_vatom) || (d_cfg_grade && !d_grades))
+    return MTP_ERR_ARG;
+  if (!stream) return MTP_ERR_ARG;   // no context here: NULL is not mapped to anything (include/mtp_mi355x.h, "Streams")
+  if (ncfg == 0) return MTP_OK;
+  return mtp_launch_batch_reduce(ncfg, d_cfg_first, d_energy ? d_eatom : nullptr, d_virial ? d_vatom : nullptr,
+                                 d_cfg_grade ? d_grades : nullptr, d_energy, d_virial, d_cfg_grade,
+                                 reinterpret_cast<hipStream_t>(stream)) == hipSuccess
+      ? MTP_OK
+      : MTP_ERR_DEVICE;
+}
+
+int mtp_batch_cfg_grades(mtp_context *c, void *stream, int ncfg, const int *d_cfg_first, int nrows, double *d_cfg_grade)
+{
+  if (!c) return MTP_ERR_ARG;
+  if (ncfg < 0 || nrows < 0 || (ncfg > 0 && (!d_cfg_first || !d_cfg_grade))) return MTP_ERR_ARG;
+  if (!c->pot->has_selection || !c->pot->configuration_mode) {
+    c->last_error = "mtp_batch_cfg_grades: the potential carries no configuration-mode selection state";
+    return MTP_ERR_STATE;
+  }
+  if (!c->have_list || nrows > c->inum || (size_t) nrows * c->cpad > c->d_cvec.cap) {
+    c->last_error = "mtp_batch_cfg_grades: no candidate vectors for these rows (call after a grade call on the installed list)";
+    return MTP_ERR_STATE;
+  }
+  if (ncfg == 0) return MTP_OK;
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  try {
+    c->d_csum.reserve((size_t) ncfg * c->cpad);
+    c->d_ident.reserve((size_t) ncfg);
+    HIP_CHECK(mtp_launch_batch_colsum(c->d_cvec.ptr, c->cpad, ncfg, d_cfg_first, c->d_csum.ptr, c->d_ident.ptr, st));
+    HIP_CHECK(mtp_launch_grade_kernel(c->d_csum.ptr, c->d_ainv_pad.ptr, c->d_ainv_tiled.ptr, c->cpad, c->pot->coeff_count, ncfg,
+                                      c->d_ident.ptr, d_cfg_grade, nullptr, st));
+    HIP_CHECK(mtp_launch_batch_grade_scale(ncfg, d_cfg_first, d_cfg_grade, st));
+  } catch (const HipFail &f) {
+    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
+    return MTP_ERR_DEVICE;
+  }
+  return MTP_OK;
 }
 
 int mtp_synchronize(mtp_context *c, void *stream)

@@ -145,6 +145,18 @@ hipError_t mtp_launch_grade_kernel(const double *cvec, const double *ainv_pad, c
                                    int C, int inum, const int *ilist, double *grades, double *max_grade, hipStream_t st);
 // coeff_ders[c] += sum_ii cvec[ii][c]
 hipError_t mtp_launch_colsum_kernel(const double *cvec, int cpad, int C, int inum, double *coeff_ders, hipStream_t st);
+// batched configurations (include/mtp_mi355x.h): segmented forms of the tallies over the rows [cfg_first[k], cfg_first[k + 1])
+// of each configuration.  mtp_batch_reduce_kernel gives a wavefront to every segment of up to MTP_BATCH_WAVE_ROWS rows and
+// its workgroup of MTP_BATCH_BLOCK threads to a longer one
+#define MTP_BATCH_BLOCK 256
+#define MTP_BATCH_WAVE_ROWS 256
+hipError_t mtp_launch_batch_reduce(int ncfg, const int *cfg_first, const double *eatom, const double *vatom, const double *grades,
+                                   double *energy, double *virial, double *cfg_grade, hipStream_t st);
+// csum[k][0, cpad) = sum of the rows of configuration k of cvec, ident[k] = k
+hipError_t mtp_launch_batch_colsum(const double *cvec, int cpad, int ncfg, const int *cfg_first, double *csum, int *ident,
+                                   hipStream_t st);
+// cfg_grade[k] /= rows of configuration k (0 for none)
+hipError_t mtp_launch_batch_grade_scale(int ncfg, const int *cfg_first, double *cfg_grade, hipStream_t st);
 // device neighbour-list build (mtp_neighbor_kernels.hip): stage 1 (neigh == nullptr) bins, counts and scans and
 // leaves {entries, longest row} in d_info[2]; stage 2 fills neigh[]
 hipError_t mtp_launch_neighbor_build(const double *x, int inum, int nall, double cutoff, const double lo[3],

@@ -386,6 +386,138 @@ __global__ void __launch_bounds__(256) mtp_colsum_kernel(const double *__restric
   unsafeAtomicAdd(&coeff_ders[c], s);
 }
 
+// ---- batched configurations: per-configuration (segmented) forms of the tallies above.  Configuration k owns rows
+// [cfg_first[k], cfg_first[k + 1]) of the per-atom outputs of ONE force call over many cells (mtp_ghosts_build_batch).
+// No atomics, and the order of every sum depends on the segment's length alone: a configuration's result does not
+// depend on what else is in the batch.
+
+// what thread t of NT co-operating threads adds up of rows [r0, r1): v[0] = sum eatom, v[1..6] = sum vatom (the
+// reference tallies vatom on the central atom, pair_mtp.cpp:268-276: ghosts carry none), v[7] = max grades.  All reads
+// are coalesced: vatom is walked as the flat array it is, 3 NT elements a round -- 3 NT is a multiple of 6 and NT = 4
+// (mod 6) for NT = 64 and 256, so element t + NT j of every round is component (t + 4 j) % 6.
+template <int NT>
+__device__ __forceinline__ void segment_partials(int t, int r0, int r1, const double *__restrict__ eatom,
+                                                 const double *__restrict__ vatom, const double *__restrict__ grades, double v[8])
+{
+  static_assert(NT % 6 == 4, "component map of the flat vatom walk");
+  double e = 0.0, g = 0.0, acc[3] = {0.0, 0.0, 0.0};
+  for (int r = r0 + t; r < r1; r += NT) {
+    if (eatom) e += eatom[r];
+    if (grades) g = fmax(g, grades[r]);
+  }
+  if (vatom) {
+    const double *__restrict__ base = vatom + 6 * (size_t) r0;
+    const int n6 = 6 * (r1 - r0);
+    for (int e0 = 0; e0 < n6; e0 += 3 * NT) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const int q = e0 + t + NT * j;
+        if (q < n6) acc[j] += base[q];
+      }
+    }
+  }
+  v[0] = e;
+  v[7] = g;
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; j++) s += (t + 4 * j) % 6 == c ? acc[j] : 0.0;
+    v[1 + c] = s;
+  }
+}
+
+static __device__ __forceinline__ void segment_wave_fold(double v[8])   // sums and the maximum over the wavefront
+{
+#pragma unroll
+  for (int q = 0; q < 7; q++) v[q] = wave_sum(v[q]);
+#pragma unroll
+  for (int sft = 1; sft < 64; sft <<= 1) v[7] = fmax(v[7], shfl_xor_f64(v[7], sft));
+}
+
+// A workgroup of four wavefronts owns four consecutive configurations: one wavefront each for segments of up to
+// MTP_BATCH_WAVE_ROWS rows (the sizes this path is for: 1 to 200 atoms), the whole workgroup, one after another, for the
+// longer ones.  energy[k] and virial[k][6] carry the sign and component order of d_ev; cfg_grade[k] = max of the
+// segment's grades (neighbourhood mode); an empty segment writes zeros.  Any output (with its input) may be null.
+__global__ void __launch_bounds__(MTP_BATCH_BLOCK) mtp_batch_reduce_kernel(int ncfg, const int *__restrict__ cfg_first,
+                                                                          const double *__restrict__ eatom,
+                                                                          const double *__restrict__ vatom,
+                                                                          const double *__restrict__ grades,
+                                                                          double *__restrict__ energy, double *__restrict__ virial,
+                                                                          double *__restrict__ cfg_grade)
+{
+  __shared__ double part[MTP_BATCH_BLOCK / 64][8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k0 = blockIdx.x * (MTP_BATCH_BLOCK / 64);
+  auto write = [&](int k, const double *v) {
+    if (energy) energy[k] = v[0];
+    if (virial) {
+#pragma unroll
+      for (int c = 0; c < 6; c++) virial[6 * (size_t) k + c] = v[1 + c];
+    }
+    if (cfg_grade) cfg_grade[k] = v[7];
+  };
+  double v[8];
+  if (k0 + wave < ncfg) {   // (the whole wavefront)
+    const int k = k0 + wave, r0 = cfg_first[k], r1 = cfg_first[k + 1];
+    if (r1 - r0 <= MTP_BATCH_WAVE_ROWS) {
+      segment_partials<64>(lane, r0, r1, eatom, vatom, grades, v);
+      segment_wave_fold(v);
+      if (lane == 0) write(k, v);
+    }
+  }
+  for (int w = 0; w < MTP_BATCH_BLOCK / 64 && k0 + w < ncfg; w++) {   // (the whole workgroup)
+    const int k = k0 + w, r0 = cfg_first[k], r1 = cfg_first[k + 1];
+    if (r1 - r0 <= MTP_BATCH_WAVE_ROWS) continue;
+    segment_partials<MTP_BATCH_BLOCK>(threadIdx.x, r0, r1, eatom, vatom, grades, v);
+    segment_wave_fold(v);
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < 8; q++) part[wave][q] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) {
+        t[q] = part[0][q];
+#pragma unroll
+        for (int u = 1; u < MTP_BATCH_BLOCK / 64; u++) t[q] = q < 7 ? t[q] + part[u][q] : fmax(t[q], part[u][q]);
+      }
+      write(k, t);
+    }
+    __syncthreads();
+  }
+}
+
+// configuration mode: csum[k][c] = sum over the rows of configuration k of cvec[row][c] -- mtp_colsum_kernel per
+// configuration (pair_mtp_extrapolation.cpp:97-98, 240-252, 327, with one "rank" per configuration).  Columns over lanes
+// (every row is read coalesced), configurations over workgroups, rows in order: no atomics.  cvec is zero padded to cpad,
+// so csum is; ident[k] = k is the ilist the grade kernel then takes the rows of csum by.
+__global__ void __launch_bounds__(256) mtp_batch_colsum_kernel(const double *__restrict__ cvec, int cpad, int ncfg,
+                                                              const int *__restrict__ cfg_first, double *__restrict__ csum,
+                                                              int *__restrict__ ident)
+{
+  const int k = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (k >= ncfg) return;
+  if (c == 0) ident[k] = k;
+  if (c >= cpad) return;
+  const int r0 = cfg_first[k], r1 = cfg_first[k + 1];
+  double s = 0.0;
+  for (int r = r0; r < r1; r++) s += cvec[(size_t) r * cpad + c];
+  csum[(size_t) k * cpad + c] = s;
+}
+
+// max_grade /= natoms, 0 for no atoms (pair_mtp_extrapolation.cpp:373-376), per configuration
+__global__ void __launch_bounds__(256) mtp_batch_grade_scale_kernel(int ncfg, const int *__restrict__ cfg_first,
+                                                                   double *__restrict__ cfg_grade)
+{
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= ncfg) return;
+  const int n = cfg_first[k + 1] - cfg_first[k];
+  cfg_grade[k] = n > 0 ? cfg_grade[k] / (double) n : 0.0;
+}
+
 template <int KL, int NB, int PITCH, bool GRADE, int DEG, int WPS>
 hipError_t launch_one(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st)
 {
@@ -539,6 +671,29 @@ hipError_t mtp_launch_colsum_kernel(const double *cvec, int cpad, int C, int inu
 {
   hipLaunchKernelGGL(mtp_colsum_kernel, dim3((C + 255) / 256, (inum + 255) / 256), dim3(256), 0, st, cvec, cpad, C, inum,
                      coeff_ders);
+  return hipGetLastError();
+}
+
+hipError_t mtp_launch_batch_reduce(int ncfg, const int *cfg_first, const double *eatom, const double *vatom, const double *grades,
+                                   double *energy, double *virial, double *cfg_grade, hipStream_t st)
+{
+  constexpr int per_block = MTP_BATCH_BLOCK / 64;
+  hipLaunchKernelGGL(mtp_batch_reduce_kernel, dim3((ncfg + per_block - 1) / per_block), dim3(MTP_BATCH_BLOCK), 0, st, ncfg,
+                     cfg_first, eatom, vatom, grades, energy, virial, cfg_grade);
+  return hipGetLastError();
+}
+
+hipError_t mtp_launch_batch_colsum(const double *cvec, int cpad, int ncfg, const int *cfg_first, double *csum, int *ident,
+                                   hipStream_t st)
+{
+  hipLaunchKernelGGL(mtp_batch_colsum_kernel, dim3(ncfg, (cpad + 255) / 256), dim3(256), 0, st, cvec, cpad, ncfg, cfg_first, csum,
+                     ident);
+  return hipGetLastError();
+}
+
+hipError_t mtp_launch_batch_grade_scale(int ncfg, const int *cfg_first, double *cfg_grade, hipStream_t st)
+{
+  hipLaunchKernelGGL(mtp_batch_grade_scale_kernel, dim3((ncfg + 255) / 256), dim3(256), 0, st, ncfg, cfg_first, cfg_grade);
   return hipGetLastError();
 }
 

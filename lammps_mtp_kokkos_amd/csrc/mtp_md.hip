@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/mtp_mi355x.h"
 #include "mtp_device.hpp"
@@ -171,6 +172,102 @@ __global__ void __launch_bounds__(256) ghosts_cell_fill_kernel(Cell9 c, int n, i
     shift[3 * (size_t) k + a] = __dadd_rn(__dadd_rn(__dmul_rn(n0, c.h[a]), __dmul_rn(n1, c.h[3 + a])), __dmul_rn(n2, c.h[6 + a]));
 }
 
+// ---- many cells in one pass (mtp_ghosts_build_batch): the two kernels above with the cell looked up per atom.  Owned
+// atoms of configuration k are rows [cfg_first[k], cfg_first[k + 1]); slot[k] holds its cell and the origin its images
+// are translated by (mtp_batch_layout keeps the slots of two configurations at least the list cutoff apart).
+struct CellSlot {
+  Cell9 c;
+  double org[3];
+};
+
+// the configuration of owned row i: the last k < ncfg with cfg_first[k] <= i (empty configurations share their start
+// with the next one, which this skips)
+__device__ __forceinline__ int cfg_of_row(const int *__restrict__ cfg_first, int ncfg, int i)
+{
+  int lo = 0, hi = ncfg - 1;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (cfg_first[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// ghosts_cell_count_kernel per configuration: wraps atom i into ITS cell (same products, rounded one by one in the same
+// order), adds the slot origin, records the shift ranges and the configuration (range.pad[0]) for the fill pass
+template <bool SUM64>
+__global__ void __launch_bounds__(256) ghosts_batch_count_kernel(const CellSlot *__restrict__ slot, const int *__restrict__ cfg_first,
+                                                                int ncfg, double *__restrict__ x, int n, int *__restrict__ count,
+                                                                ShiftRange *__restrict__ range,
+                                                                unsigned long long *__restrict__ total64)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long mine = 0;
+  if (i < n) {
+    const int cfg = cfg_of_row(cfg_first, ncfg, i);
+    const double *__restrict__ h = slot[cfg].c.h, *__restrict__ hinv = slot[cfg].c.hinv, *__restrict__ m = slot[cfg].c.m;
+    const double p[3] = {x[3 * (size_t) i], x[3 * (size_t) i + 1], x[3 * (size_t) i + 2]};
+    double s[3];
+    ShiftRange r;
+    unsigned long long prod = 1;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      double v = __dadd_rn(__dadd_rn(__dmul_rn(p[0], hinv[a]), __dmul_rn(p[1], hinv[3 + a])), __dmul_rn(p[2], hinv[6 + a]));
+      v -= floor(v);
+      if (!(v < 1.0)) v = 0.0;   // floor() rounding at the upper edge (and a non-finite coordinate: counted from 0)
+      s[a] = v;
+      const double lo = ceil(-m[a] - v), hi = ceil(1.0 + m[a] - v) - 1.0;   // lo <= 0 <= hi
+      r.lo[a] = (int) fmax(lo, -1073741824.0);
+      r.cnt[a] = (int) fmin(hi - lo + 1.0, 1073741824.0);
+      prod = prod > 0xffffffffull ? prod : prod * (unsigned long long) r.cnt[a];   // stays below 2^63
+    }
+    r.pad[0] = cfg;
+    r.pad[1] = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const double w = __dadd_rn(__dadd_rn(__dmul_rn(s[0], h[a]), __dmul_rn(s[1], h[3 + a])), __dmul_rn(s[2], h[6 + a]));
+      x[3 * (size_t) i + a] = __dadd_rn(w, slot[cfg].org[a]);   // (the ghosts follow through owner + shift)
+    }
+    mine = prod - 1 > 0xffffffffull ? 0xffffffffull : prod - 1;
+    count[i] = mine > 0x7fffffffull ? 0x7fffffff : (int) mine;
+    range[i] = r;
+  }
+  if (SUM64) {
+    typedef hipcub::BlockReduce<unsigned long long, 256> Red;
+    __shared__ typename Red::TempStorage tmp;
+    const unsigned long long bsum = Red(tmp).Sum(mine);
+    if (threadIdx.x == 0 && bsum) atomicAdd(total64, bsum);
+  }
+}
+
+// ghosts_cell_fill_kernel with h taken from the owner's configuration
+__global__ void __launch_bounds__(256) ghosts_batch_fill_kernel(const CellSlot *__restrict__ slot, int n, int total,
+                                                               const int *__restrict__ first, const ShiftRange *__restrict__ range,
+                                                               int *__restrict__ owner, double *__restrict__ shift, int capacity)
+{
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= total || k >= capacity) return;
+  int lo = 0, hi = n - 1;   // the last atom with first[i] <= k
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (first[mid] <= k) lo = mid;
+    else hi = mid - 1;
+  }
+  const ShiftRange r = range[lo];
+  const double *__restrict__ h = slot[r.pad[0]].c.h;
+  int e = k - first[lo];
+  const int zero = (-r.lo[0] * r.cnt[1] - r.lo[1]) * r.cnt[2] - r.lo[2];   // where the atom itself would stand
+  if (e >= zero) e++;
+  const int q = e / r.cnt[2];
+  const double n2 = r.lo[2] + (e - q * r.cnt[2]);
+  const int q1 = q / r.cnt[1];
+  const double n1 = r.lo[1] + (q - q1 * r.cnt[1]), n0 = r.lo[0] + q1;
+  owner[k] = lo;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    shift[3 * (size_t) k + a] = __dadd_rn(__dadd_rn(__dmul_rn(n0, h[a]), __dmul_rn(n1, h[3 + a])), __dmul_rn(n2, h[6 + a]));
+}
+
 // x[nlocal + k] = x[owner[k]] + shift[k]   (one lane per coordinate)
 __global__ void __launch_bounds__(256) ghosts_forward_kernel(double *__restrict__ x, int nlocal,
                                                             const int *__restrict__ owner,
@@ -256,13 +353,18 @@ struct mtp_ghosts {
   double *d_shift = nullptr;
   ShiftRange *d_range = nullptr;             // mtp_ghosts_build_cell only: [cap_range] + one 64-bit total behind them
   int cap_range = 0;
+  CellSlot *d_slot = nullptr;                // mtp_ghosts_build_batch only: [cap_slot] cells + origins, and the
+  int *d_cfg_first = nullptr;                // [cap_slot + 1] first owned rows of the configurations
+  int cap_slot = 0;
+  std::vector<CellSlot> h_slot;              // host staging of d_slot
   void *d_tmp = nullptr;
   size_t tmp_bytes = 0;
   std::string last_error;
   ~mtp_ghosts()
   {
     (void) hipSetDevice(device);
-    for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, (void *) d_range, d_tmp})
+    for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, (void *) d_range, (void *) d_slot,
+                    (void *) d_cfg_first, d_tmp})
       if (p) (void) hipFree(p);
   }
 };
@@ -492,6 +594,210 @@ int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x, int nlocal, 
   g->nghost = total;
   if (total > 0) {
     hipLaunchKernelGGL(ghosts_cell_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c, nlocal, total, g->d_first,
+                       g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
+    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
+                       g->d_shift, 3 * total);
+  }
+  MD_HIP(hipGetLastError());
+  return MTP_OK;
+}
+
+// ---- batched configurations ------------------------------------------------------------------------------------------
+
+int mtp_batch_layout(int ncfg, const double *cells, double rghost, double gap, double *origins, double lo[3], double hi[3],
+                     long long *ncells_out, int *nfit_out, char *err, int errlen)
+{
+  auto fail = [&](int code, const std::string &msg) {
+    if (err && errlen > 0) std::snprintf(err, (size_t) errlen, "%s", msg.c_str());
+    return code;
+  };
+  if (nfit_out) *nfit_out = 0;
+  if (ncfg < 0 || (ncfg > 0 && (!cells || !origins)) || !lo || !hi || !(rghost > 0.0) || !std::isfinite(rghost) ||
+      !std::isfinite(gap) || !(gap >= rghost))
+    return fail(MTP_ERR_ARG, "mtp_batch_layout: needs cells, origins, lo, hi, rghost > 0 and gap >= rghost");
+  // bounding boxes of the ghost parallelepipeds, and the largest extents of every prefix of the batch (the slots of a
+  // prefix are uniform, sized by them)
+  std::vector<double> blo((size_t) 3 * ncfg), pmax((size_t) 3 * ncfg);
+  for (int k = 0; k < ncfg; k++) {
+    double l[3], u[3];
+    if (mtp_ghosts_cell_bounds(cells + 9 * (size_t) k, rghost, l, u, nullptr, nullptr) != MTP_OK)
+      return fail(MTP_ERR_ARG, "mtp_batch_layout: configuration " + std::to_string(k) +
+                                   ": the cell must be finite, right-handed and non-degenerate (det > 0)");
+    for (int a = 0; a < 3; a++) {
+      blo[3 * (size_t) k + a] = l[a];
+      pmax[3 * (size_t) k + a] = std::max(u[a] - l[a], k > 0 ? pmax[3 * (size_t) (k - 1) + a] : 0.0);
+    }
+  }
+  struct Grid {
+    int g[3];
+    double pitch[3], base[3], lo[3], hi[3];
+    long long ncells;
+    int why;   // 0 fits, 1 coordinate cap, 2 cell limit
+  };
+  // the first n configurations on a 3-D grid of uniform slots, grown along the axis that keeps the box smallest, centred
+  // on the origin (coordinates stay small: their magnitude costs bits of the interatomic distances)
+  auto place = [&](int n) {
+    Grid G{};
+    double S[3] = {0.0, 0.0, 0.0};
+    for (int a = 0; a < 3 && n > 0; a++) S[a] = pmax[3 * (size_t) (n - 1) + a];
+    for (int a = 0; a < 3; a++) {
+      G.g[a] = 1;
+      G.pitch[a] = S[a] + gap;
+    }
+    while ((long long) G.g[0] * G.g[1] * G.g[2] < n) {
+      int best = 0;
+      for (int a = 1; a < 3; a++)
+        if ((G.g[a] + 1) * G.pitch[a] < (G.g[best] + 1) * G.pitch[best]) best = a;
+      G.g[best]++;
+    }
+    double ncells = 1.0;
+    for (int a = 0; a < 3; a++) {
+      const double total = (G.g[a] - 1) * G.pitch[a] + S[a];
+      G.base[a] = -0.5 * total;
+      G.lo[a] = G.base[a] - 1e-9;
+      G.hi[a] = G.base[a] + total + 1e-9;
+      if (std::fmax(std::fabs(G.lo[a]), std::fabs(G.hi[a])) > 2048.0) G.why = 1;
+      // (the count mtp_build_neighbors_device derives from lo / hi)
+      ncells *= std::fmax(1.0, std::ceil((G.hi[a] - G.lo[a]) / rghost));
+    }
+    G.ncells = ncells < 4e18 ? (long long) ncells : (1ll << 62);
+    if (!G.why && G.ncells > (1ll << 26)) G.why = 2;
+    return G;
+  };
+  Grid G = place(ncfg);
+  if (G.why) {
+    int fit = 0, top = ncfg - 1;   // the longest prefix that fits (the empty one does)
+    while (fit < top) {
+      const int mid = fit + (top - fit + 1) / 2;
+      if (place(mid).why == 0) fit = mid;
+      else top = mid - 1;
+    }
+    if (nfit_out) *nfit_out = fit;
+    return fail(MTP_ERR_LIMIT, "mtp_batch_layout: configuration " + std::to_string(fit) + " is the first that does not fit: " +
+                                   (G.why == 1 ? "a coordinate of the batch would exceed 2048 A in magnitude"
+                                               : "the batch would need more than 2^26 list cells") +
+                                   " (split the batch)");
+  }
+  for (int k = 0; k < ncfg; k++) {
+    const int idx[3] = {k / (G.g[1] * G.g[2]), (k / G.g[2]) % G.g[1], k % G.g[2]};
+    for (int a = 0; a < 3; a++) origins[3 * (size_t) k + a] = (G.base[a] + idx[a] * G.pitch[a]) - blo[3 * (size_t) k + a];
+  }
+  for (int a = 0; a < 3; a++) {
+    lo[a] = G.lo[a];
+    hi[a] = G.hi[a];
+  }
+  if (ncells_out) *ncells_out = G.ncells;
+  if (nfit_out) *nfit_out = ncfg;
+  return MTP_OK;
+}
+
+int mtp_ghosts_build_batch(mtp_ghosts *g, void *stream, double *d_x, int ncfg, const int *cfg_first, const double *cells,
+                           const double *origins, int capacity, double rghost, int *nall_out)
+{
+  if (!g || !d_x || ncfg < 0 || !cfg_first || (ncfg > 0 && (!cells || !origins)) || !(rghost > 0.0) || !std::isfinite(rghost) ||
+      !nall_out)
+    return MTP_ERR_ARG;
+  if (!stream) return ghosts_null_stream(g, "mtp_ghosts_build_batch");
+  if (cfg_first[0] != 0) {
+    g->last_error = "mtp_ghosts_build_batch: cfg_first[0] must be 0";
+    return MTP_ERR_ARG;
+  }
+  for (int k = 0; k < ncfg; k++)
+    if (cfg_first[k + 1] < cfg_first[k]) {
+      g->last_error = "mtp_ghosts_build_batch: cfg_first decreases at configuration " + std::to_string(k);
+      return MTP_ERR_ARG;
+    }
+  const int nlocal = cfg_first[ncfg];
+  if (capacity < nlocal) {
+    g->last_error = "mtp_ghosts_build_batch: capacity is smaller than the owned atoms";
+    return MTP_ERR_ARG;
+  }
+  // an atom of configuration k has at most floor(1 + 2 m_a) + 1 shifts per direction: when that bound, summed over the
+  // batch, fits an int, the scanned int total is exact and the 64-bit sum is not taken
+  g->h_slot.resize((size_t) ncfg);
+  double bound = (double) nlocal;
+  for (int k = 0; k < ncfg; k++) {
+    CellSlot &s = g->h_slot[(size_t) k];
+    for (int q = 0; q < 9; q++) s.c.h[q] = cells[9 * (size_t) k + q];
+    if (!(cell_setup(s.c.h, rghost, s.c.hinv, s.c.m) > 0.0)) {
+      g->last_error = "mtp_ghosts_build_batch: configuration " + std::to_string(k) +
+          ": the cell must be finite, right-handed and non-degenerate (det > 0)";
+      return MTP_ERR_ARG;
+    }
+    double per_atom = 1.0;
+    for (int a = 0; a < 3; a++) {
+      s.org[a] = origins[3 * (size_t) k + a];
+      if (!std::isfinite(s.org[a])) {
+        g->last_error = "mtp_ghosts_build_batch: configuration " + std::to_string(k) + ": non-finite origin";
+        return MTP_ERR_ARG;
+      }
+      per_atom *= std::floor(1.0 + 2.0 * s.c.m[a]) + 1.0;
+    }
+    bound += per_atom * (double) (cfg_first[k + 1] - cfg_first[k]);
+  }
+  g->nlocal = nlocal;
+  g->nghost = 0;
+  *nall_out = nlocal;
+  if (nlocal == 0) return MTP_OK;   // nothing to wrap, no images
+  const bool sum64 = !(bound < 2147483647.0);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  MD_HIP(hipSetDevice(g->device));
+  MD_HIP(ghosts_reserve_local(g, nlocal, st));
+  if (nlocal + 1 > g->cap_range) {
+    if (g->d_range) (void) hipFree(g->d_range);
+    g->d_range = nullptr;
+    g->cap_range = 0;
+    MD_HIP(hipMalloc((void **) &g->d_range, ((size_t) g->cap_local + 1) * sizeof(ShiftRange)));
+    g->cap_range = g->cap_local;
+  }
+  if (ncfg > g->cap_slot) {
+    if (g->d_slot) (void) hipFree(g->d_slot);
+    if (g->d_cfg_first) (void) hipFree(g->d_cfg_first);
+    g->d_slot = nullptr;
+    g->d_cfg_first = nullptr;
+    g->cap_slot = 0;
+    const size_t n = (size_t) ncfg + ncfg / 8;
+    MD_HIP(hipMalloc((void **) &g->d_slot, n * sizeof(CellSlot)));
+    MD_HIP(hipMalloc((void **) &g->d_cfg_first, (n + 1) * sizeof(int)));
+    g->cap_slot = (int) n;
+  }
+  // (the stream is synchronised below, before this call returns: the host arrays outlive both copies)
+  MD_HIP(hipMemcpyAsync(g->d_slot, g->h_slot.data(), (size_t) ncfg * sizeof(CellSlot), hipMemcpyHostToDevice, st));
+  MD_HIP(hipMemcpyAsync(g->d_cfg_first, cfg_first, ((size_t) ncfg + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  unsigned long long *d_total64 = reinterpret_cast<unsigned long long *>(g->d_range + g->cap_range);
+  MD_HIP(hipMemsetAsync(g->d_count, 0, ((size_t) nlocal + 1) * sizeof(int), st));
+  if (sum64) MD_HIP(hipMemsetAsync(d_total64, 0, sizeof(unsigned long long), st));
+  const int nb = (nlocal + 255) / 256;
+  if (sum64)
+    hipLaunchKernelGGL(ghosts_batch_count_kernel<true>, dim3(nb), dim3(256), 0, st, g->d_slot, g->d_cfg_first, ncfg, d_x, nlocal,
+                       g->d_count, g->d_range, d_total64);
+  else
+    hipLaunchKernelGGL(ghosts_batch_count_kernel<false>, dim3(nb), dim3(256), 0, st, g->d_slot, g->d_cfg_first, ncfg, d_x, nlocal,
+                       g->d_count, g->d_range, d_total64);
+  size_t tb = g->tmp_bytes;
+  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp, tb, g->d_count, g->d_first, nlocal + 1, st));
+  int total = 0;
+  unsigned long long total64 = 0;
+  if (sum64) MD_HIP(hipMemcpyAsync(&total64, d_total64, sizeof(total64), hipMemcpyDeviceToHost, st));
+  else MD_HIP(hipMemcpyAsync(&total, g->d_first + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
+  MD_HIP(hipStreamSynchronize(st));
+  if (sum64) {
+    if (total64 > 0x7fffffffull - (unsigned long long) nlocal) {   // never wrapped: the scanned offsets are not used
+      *nall_out = 0x7fffffff;
+      g->last_error = "mtp_ghosts_build_batch: owned + ghost atoms do not fit a 32-bit count (split the batch)";
+      return MTP_ERR_LIMIT;
+    }
+    total = (int) total64;   // == d_first[nlocal]: no per-atom count saturated
+  }
+  *nall_out = nlocal + total;
+  if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written or kept
+    g->last_error = "mtp_ghosts_build_batch: capacity of the position array is smaller than owned + ghost atoms";
+    return MTP_ERR_LIMIT;
+  }
+  MD_HIP(ghosts_reserve_ghosts(g, total));
+  g->nghost = total;
+  if (total > 0) {
+    hipLaunchKernelGGL(ghosts_batch_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, g->d_slot, nlocal, total, g->d_first,
                        g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
     hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
                        g->d_shift, 3 * total);

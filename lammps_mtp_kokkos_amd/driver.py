@@ -109,6 +109,36 @@ def make_ghosts_cell(pos, cell, rghost):
     return x, owner, shift
 
 
+def make_ghosts_batch(configs, origins, rghost):
+    """Many cells in one system: the numpy twin of mtp_ghosts_build_batch.  configs: sequence of (pos, cell); origins
+    [ncfg, 3] (capi.batch_layout).  make_ghosts_cell per configuration, translated by its origin and re-ordered to the
+    device's order: all owned atoms first (configuration after configuration), then the ghosts in atom order, then
+    lexicographic shift order.  The origin is added to the wrapped owned positions and the ghosts are owner + shift,
+    rounded in that order, as on the device.  Returns (x [nall, 3], owner [nall] rows of x, shift [nall, 3] integer,
+    cfg [nall] the configuration of every row, cfg_first [ncfg + 1])."""
+    origins = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    counts = [len(np.asarray(p).reshape(-1, 3)) for p, _ in configs]
+    cfg_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    own_x, gh_x, gh_owner, gh_shift, gh_cfg = [], [], [], [], []
+    for k, (pos, cell) in enumerate(configs):
+        n = counts[k]
+        h = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+        x, owner, shift = make_ghosts_cell(np.asarray(pos, dtype=np.float64).reshape(-1, 3), h, rghost)
+        xo = x[:n] + origins[k]
+        sf = shift[n:].astype(np.float64)
+        own_x.append(xo)
+        gh_x.append(xo[owner[n:]] + ((sf[:, 0:1] * h[0] + sf[:, 1:2] * h[1]) + sf[:, 2:3] * h[2]))
+        gh_owner.append(owner[n:] + cfg_first[k])
+        gh_shift.append(shift[n:])
+        gh_cfg.append(np.full(len(owner) - n, k, dtype=np.int64))
+    ntot = int(cfg_first[-1])
+    x = np.concatenate(own_x + gh_x).reshape(-1, 3) if configs else np.zeros((0, 3))
+    owner = np.concatenate([np.arange(ntot)] + gh_owner).astype(np.int64)
+    shift = np.concatenate([np.zeros((ntot, 3), dtype=np.int64)] + gh_shift).reshape(-1, 3)
+    cfg = np.concatenate([np.repeat(np.arange(len(configs)), counts)] + gh_cfg).astype(np.int64)
+    return x, owner, shift, cfg, cfg_first
+
+
 def full_neighbor_list(x, nlocal, cutoff, chunk=65536):
     """CSR full list over the first nlocal atoms: every j != i with |x_j - x_i| <= cutoff.  Rows are queried in
     chunks, so the Python lists of a 500k-atom system never exist all at once."""

@@ -12,7 +12,8 @@ the library's HIP kernels (include/mtp_mi355x.h, "standalone MD support"):
 `box` is a 3-vector (orthogonal box with every edge >= the list cutoff: mtp_ghosts_build, the path the whole-step
 benchmark times) or a 3x3 cell whose rows are the lattice vectors (any periodic cell, triclinic or smaller than the
 cutoff: mtp_ghosts_build_cell, list bounds from mtp_ghosts_cell_bounds).  evaluate_cell is one such evaluation
-without the integrator.
+without the integrator; evaluate_cells does many of them -- training or candidate configurations, each with its own
+cell -- in one device pass (include/mtp_mi355x.h, "batched configurations").
 
 torch only allocates the arrays and provides the stream; the host sees the ghost count and the list size at a
 re-neighbouring (they size arrays) and nothing else.
@@ -193,3 +194,194 @@ def evaluate_cell(ctx, pos, cell, types=None, list_cutoff=7.0, vflag=1, grades=F
     if grades:
         out.update(grades=g_t[:n].cpu().numpy(), max_grade=float(mg_t.item()))
     return out
+
+
+class _BatchBuffers:
+    """device (and pinned host) arrays of evaluate_cells, grown as needed and reused across its passes"""
+
+    def __init__(self, torch, dev):
+        self.torch, self.dev = torch, dev
+        self.cap = self.cap_cfg = self.cap_work = self.cap_out = 0
+
+    def reserve(self, cap, ncfg, work, out):
+        torch, dev = self.torch, self.dev
+        if cap > self.cap:
+            self.cap = int(cap * 1.1) + 1024
+            self.xall = torch.empty((self.cap, 3), dtype=torch.float64, device=dev)
+            self.tall = torch.empty(self.cap, dtype=torch.int32, device=dev)
+            self.grades = torch.empty(self.cap, dtype=torch.float64, device=dev)
+        if ncfg > self.cap_cfg:
+            self.cap_cfg = int(ncfg * 1.1) + 16
+            self.res = torch.empty(8 * self.cap_cfg, dtype=torch.float64, device=dev)
+        if work > self.cap_work:
+            self.cap_work = int(work * 1.1) + 1024
+            self.work = torch.empty(self.cap_work, dtype=torch.float64, device=dev)
+        if out > self.cap_out:
+            self.cap_out = int(out * 1.1) + 1024
+            self.out_host = torch.empty(self.cap_out, dtype=torch.float64, pin_memory=True)
+
+
+def plan_cell_passes(cells, natoms, list_cutoff, max_atoms_per_pass=None):
+    """Host arithmetic only: the passes evaluate_cells makes over a batch.  cells [ncfg, 3, 3], natoms [ncfg].  A pass is
+    a run of consecutive configurations; a new one starts where the owned atoms would exceed `max_atoms_per_pass` (a
+    configuration is never split), where owned + ghost atoms could approach 2^31, and where mtp_batch_layout says the
+    batch no longer fits its limits (2^26 list cells, coordinates within 2048 A).  Returns ([(first, end, layout)], the
+    cell volumes, the most rows -- owned + ghost atoms -- every configuration can need)."""
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    natoms = np.asarray(natoms, dtype=np.int64)
+    cut = float(list_cutoff)
+    # volumes and margins m_a = rghost / d_a of all cells at once (driver.cell_margins); every atom has at most
+    # floor(1 + 2 m_a) + 1 shifts per direction, which bounds the rows a configuration can need
+    with np.errstate(all="ignore"):
+        cross = np.stack([np.cross(cells[:, 1], cells[:, 2]), np.cross(cells[:, 2], cells[:, 0]),
+                          np.cross(cells[:, 0], cells[:, 1])], axis=1)
+        volume = (cells[:, 0] * cross[:, 0]).sum(1)
+        margins = cut * np.sqrt((cross * cross).sum(2)) / volume[:, None]
+        bad = ~(np.isfinite(cells).all((1, 2)) & (volume > 0.0) & np.isfinite(margins).all(1))
+    if bad.any():
+        raise capi.MtpError(-20, "configuration %d: the cell must be finite, right-handed and non-degenerate (det > 0)"
+                            % int(np.nonzero(bad)[0][0]))
+    max_rows = natoms * np.prod(np.floor(1.0 + 2.0 * margins) + 1.0, axis=1)
+    queue, begin, atoms, rows = [], 0, 0, 0.0
+    for k in range(len(cells)):
+        n = int(natoms[k])
+        if k > begin and ((max_atoms_per_pass is not None and atoms + n > max_atoms_per_pass)
+                          or rows + max_rows[k] > 2.0 ** 31 - 2.0 ** 20):
+            queue.append((begin, k))
+            begin, atoms, rows = k, 0, 0.0
+        atoms, rows = atoms + n, rows + max_rows[k]
+    if begin < len(cells):
+        queue.append((begin, len(cells)))
+    queue.reverse()
+    passes = []
+    while queue:
+        k0, k1 = queue.pop()
+        try:
+            passes.append((k0, k1, capi.batch_layout(cells[k0:k1], cut, cut)))
+        except capi.MtpError as e:
+            if e.code != -24 or not 0 < e.nfit < k1 - k0:      # a configuration that does not fit on its own
+                raise
+            queue.append((k0 + e.nfit, k1))
+            queue.append((k0, k0 + e.nfit))
+    return passes, volume, max_rows
+
+
+def evaluate_cells(ctx, configs, list_cutoff=7.0, vflag=1, grades=False, max_atoms_per_pass=None, device=None):
+    """evaluate_cell for many small periodic cells in one device pass.  `configs` is a sequence of (pos, cell, types)
+    (types may be None; a configuration may be empty).  Every configuration gets a slot of its own in one large box
+    (mtp_batch_layout: no atom or image of one lies within the list cutoff of another), and one pass is one ghost build
+    with the cell looked up per atom (mtp_ghosts_build_batch), one list build, one force launch over all rows, the ghost
+    fold, the per-configuration reductions (mtp_batch_reduce, mtp_batch_cfg_grades) and one copy back, with one wait
+    each for the ghost count and the list size and one at the end.  The batch is split into passes by
+    `max_atoms_per_pass` (owned atoms; a configuration is never split), by the layout's limits (2^26 list cells,
+    coordinates within 2048 A) and where owned + ghost atoms would approach 2^31.
+
+    Returns a list of dicts in input order, each with the keys of evaluate_cell: energy, f [n, 3] in the order of `pos`,
+    virial [6], volume, x [n, 3] (wrapped into the cell, without the slot origin); with grades=True also grades [n] and
+    max_grade (neighbourhood mode) or cfg_grade (configuration mode: the grade of the configuration as a whole,
+    pair_mtp_extrapolation.cpp:369-376).  An atom type outside the potential is reported at the final synchronise of
+    its pass; the message names the pass."""
+    import torch
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    cut = float(list_cutoff)
+    cfg_mode = bool(grades) and bool(ctx.pot.info.configuration_mode)
+    C = int(ctx.pot.info.coeff_count)
+    items = []
+    for k, c in enumerate(configs):
+        pos = np.ascontiguousarray(c[0], dtype=np.float64).reshape(-1, 3)
+        types = c[2] if len(c) > 2 else None
+        types = np.ones(len(pos), dtype=np.int32) if types is None else np.ascontiguousarray(types, dtype=np.int32).reshape(-1)
+        if len(types) != len(pos):
+            raise ValueError("configuration %d: %d types for %d atoms" % (k, len(types), len(pos)))
+        items.append((pos, types))
+    all_cells = np.array([np.asarray(c[1], dtype=np.float64).reshape(3, 3) for c in configs], dtype=np.float64).reshape(-1, 3, 3)
+    natoms = np.array([len(it[0]) for it in items], dtype=np.int64)
+    passes, volume, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
+    ghosts = capi.Ghosts(dev.index or 0)
+    buf = _BatchBuffers(torch, dev)
+    results = [None] * len(items)
+    npass = 0
+    for k0, k1, lay in passes:
+        cells = all_cells[k0:k1]
+        npass += 1
+        part = items[k0:k1]
+        ncfg = k1 - k0
+        counts = natoms[k0:k1]
+        cf = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        n = int(cf[-1])
+        if n == 0:
+            for k in range(k0, k1):
+                results[k] = _empty_result(float(volume[k]), grades, cfg_mode)
+            continue
+        cap = n + int(max_rows[k0:k1].sum())
+        na = lambda nall: nall + (nall & 1)
+        buf.reserve(cap, ncfg, 10 * na(cap) + 10 + C + (C & 1), 7 * n + 8 * ncfg)
+        buf.xall[:n] = torch.from_numpy(np.concatenate([it[0] for it in part])).to(dev)
+        buf.tall[:n] = torch.from_numpy(np.concatenate([it[1] for it in part])).to(dev)
+        cf_t = torch.from_numpy(cf).to(dev)
+        try:
+            nall = ghosts.build_batch(buf.xall, cf, cells, lay["origins"], cut, stream=st)
+        except capi.MtpError as e:                            # (the capacity protocol; `cap` is an upper bound)
+            if e.code != -24 or ghosts.nall <= buf.cap or ghosts.nall >= 2 ** 31 - 1:
+                raise
+            keep = buf.xall[:n].clone()
+            buf.reserve(ghosts.nall, ncfg, 10 * na(ghosts.nall) + 10 + C + (C & 1), 0)
+            buf.xall[:n] = keep
+            buf.tall[:n] = torch.from_numpy(np.concatenate([it[1] for it in part])).to(dev)
+            nall = ghosts.build_batch(buf.xall, cf, cells, lay["origins"], cut, stream=st)
+        ghosts.types(buf.tall, stream=st)
+        ctx.build_neighbors_device(buf.xall, n, nall, cut, lay["lo"], lay["hi"], stream=st)
+        # f | ev | eatom | vatom | max grade | coeff_ders: one allocation, zeroed by one launch
+        m = na(nall)
+        work = buf.work[: 10 * m + 10 + C + (C & 1)]
+        fall, ev = work[: 3 * nall].view(nall, 3), work[3 * m: 3 * m + 8]
+        eatom, vatom = work[3 * m + 8: 4 * m + 8], work[4 * m + 8: 10 * m + 8]
+        maxg, coeff = work[10 * m + 8: 10 * m + 9], work[10 * m + 10: 10 * m + 10 + C]
+        capi.zero_async(work, stream=st)
+        vf = 4 if vflag else 0
+        ctx.compute_device_rows(0, n, False, buf.xall, buf.tall, fall, eflag=3, vflag=vf, grade=bool(grades), eatom_t=eatom,
+                                vatom_t=vatom if vf else None, ev_t=ev, grades_t=buf.grades if grades and not cfg_mode else None,
+                                maxg_t=maxg if grades else None, coeff_t=coeff if cfg_mode else None, stream=st)
+        ghosts.reverse_finish(ctx, fall, ev, eflag=3, vflag=vf, stream=st)
+        res = buf.res[: 8 * ncfg]
+        e_t, v_t, g_t = res[:ncfg], res[ncfg: 7 * ncfg], res[7 * ncfg:]
+        if not vf or not grades:
+            res.zero_()
+        capi.batch_reduce(cf_t, eatom_t=eatom, vatom_t=vatom if vf else None, grades_t=buf.grades if grades and not cfg_mode else None,
+                          energy_t=e_t, virial_t=v_t if vf else None, cfg_grade_t=g_t if grades and not cfg_mode else None, stream=st)
+        if cfg_mode:
+            ctx.batch_cfg_grades(cf_t, n, g_t, stream=st)
+        pieces = [buf.xall[:n].reshape(-1), fall[:n].reshape(-1), res] + ([buf.grades[:n]] if grades and not cfg_mode else [])
+        nout = sum(int(p.numel()) for p in pieces)
+        out = buf.out_host[:nout]
+        out.copy_(torch.cat(pieces), non_blocking=True)       # the one copy back, waited for below
+        try:
+            ctx.synchronize(stream=st)                        # an atom type outside the potential is reported here
+        except capi.MtpError as e:
+            raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
+        h = out.numpy()
+        xh = h[: 3 * n].reshape(n, 3) - np.repeat(lay["origins"], counts, axis=0)
+        fh = h[3 * n: 6 * n].reshape(n, 3).copy()
+        eh, vh = h[6 * n: 6 * n + ncfg].copy(), h[6 * n + ncfg: 6 * n + 7 * ncfg].reshape(ncfg, 6).copy()
+        ch, gh = h[6 * n + 7 * ncfg: 6 * n + 8 * ncfg].copy(), h[6 * n + 8 * ncfg:].copy()
+        for j in range(ncfg):
+            a, b = int(cf[j]), int(cf[j + 1])
+            r = dict(energy=float(eh[j]), f=fh[a:b], virial=vh[j], volume=float(volume[k0 + j]), x=xh[a:b])
+            if grades and cfg_mode:
+                r["cfg_grade"] = float(ch[j])
+            elif grades:
+                r["grades"], r["max_grade"] = gh[a:b], float(ch[j])
+            results[k0 + j] = r
+    return results
+
+
+def _empty_result(volume, grades, cfg_mode):
+    r = dict(energy=0.0, f=np.zeros((0, 3)), virial=np.zeros(6), volume=volume, x=np.zeros((0, 3)))
+    if grades and cfg_mode:
+        r.update(cfg_grade=0.0)
+    elif grades:
+        r.update(grades=np.zeros(0), max_grade=0.0)
+    return r
