@@ -1,10 +1,10 @@
-/* TEST INFRASTRUCTURE ONLY (see mtp_oracle.h).  PARITY UNPINNED against a running
- * reference; pinned by tests/test_oracle.py's independent checks.
+/* TEST INFRASTRUCTURE ONLY (see mtp_oracle.h).  Pinned bit for bit to the compiled reference
+ * (tests/test_reference_cpu.py) and by tests/test_oracle.py's independent checks.
  *
  * CPU restatement of /root/reference/LAMMPS/ML-MTP/{pair_mtp,pair_mtp_extrapolation,
  * mtp_radial_basis,mtp_rb_chevbyshev_basis}.cpp written fresh in C.  The arithmetic keeps
  * the reference's operation order (sums run in the same index order, the same three
- * divides per basic moment) so that a future run of the real reference can be compared
+ * divides per basic moment) so that a run of the real reference can be compared
  * to the last bits.
  */
 #define _POSIX_C_SOURCE 200809L

@@ -3,11 +3,10 @@
  * and bench.py's cpu_baseline leg may call this; the product (libmtp_mi355x.so) never
  * links or loads it.
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or potential files
- *  and its sources need LAMMPS headers (pair.h, memory.h,
- * text_file_reader.h, ...) that are absent from this image, so it cannot be compiled
- * here without writing stand-in headers, which this build's rules forbid.  The
- * restatement is therefore checked against (a) the closed form of the Chebyshev basis,
+ * PINNED to the compiled reference: `make ref` builds the reference's four CPU sources unchanged against the
+ * stand-in LAMMPS headers of tests/cpp/lammps_mock (oracle/_ref/libmtp_ref.so, git-ignored), and
+ * tests/test_reference_cpu.py asserts bitwise equality of every output of this restatement with it (DESIGN.md
+ * section 2).  Independently of that it is checked against (a) the closed form of the Chebyshev basis,
  * (b) an independent tensor-contraction (einsum) evaluation of the level-8 basis
  * functions from their mathematical definition, (c) F = -dE/dx by central differences,
  * (d) sum F = 0, E = sum eatom, rotation/translation/permutation invariance and the

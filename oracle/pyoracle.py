@@ -110,9 +110,10 @@ class Oracle:
             raise RuntimeError("oracle compute_mt rc=%d" % rc)
         return dict(energy=e.value, eatom=eatom, f=f, virial=virial, vatom=vatom)
 
-    def compute(self, x, types, ilist, first, neigh, eflag=3, vflag=4, extrapolation=False, natoms=0):
+    def compute(self, x, types, ilist, first, neigh, eflag=3, vflag=4, extrapolation=False, natoms=0, prefill=0.0):
         """x [nall,3] f64, types [nall] i32 (1-based), CSR neighbour list over ilist.
-        Returns dict(energy, eatom, f, virial, vatom[, grades, max_grade, coeff_ders])."""
+        Returns dict(energy, eatom, f, virial, vatom[, grades, max_grade, coeff_ders]).  prefill: what energy, eatom,
+        virial and vatom hold when the oracle is called (it accumulates; LAMMPS zeroes what a call tallies)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         types = np.ascontiguousarray(types, dtype=np.int32)
         ilist = np.ascontiguousarray(ilist, dtype=np.int32)
@@ -120,10 +121,10 @@ class Oracle:
         neigh = np.ascontiguousarray(neigh, dtype=np.int32)
         nall = x.shape[0]
         f = np.zeros((nall, 3))
-        eatom = np.zeros(nall)
-        vatom = np.zeros((nall, 6))
-        virial = np.zeros(6)
-        e = C.c_double(0.0)
+        eatom = np.full(nall, float(prefill))
+        vatom = np.full((nall, 6), float(prefill))
+        virial = np.full(6, float(prefill))
+        e = C.c_double(float(prefill))
         out = {}
         if not extrapolation:
             rc = lib().mtp_oracle_compute(C.byref(self.m), len(ilist), _p(ilist, C.c_int), _p(first, C.c_int),

@@ -2,6 +2,12 @@
 // public LAMMPS developer documentation for ONE purpose: to compile the adapter and drive it through the call sequence
 // LAMMPS makes on a pair style (tests/cpp/test_plugin_mock.cpp).  It is test scaffolding of THIS repository, not
 // LAMMPS, not the reference, and proves nothing about binary compatibility with a real LAMMPS build.
+//
+// A second user since: the recipe oracle/Makefile `ref`, which compiles the reference's four CPU sources of ML-MTP
+// unchanged against these stand-ins (with -DLAMMPS_MOCK_FMT and a header-only {fmt} on the include path) into the
+// judge of tests/test_reference_cpu.py.  What that needs on top -- Memory for 1-D / 3-D arrays and grow, fmt-formatted
+// Error and utils::logmesg, TextFileReader / ValueTokenizer (lammps_mock_text.h), Pair::ev_setup, MPI_Bcast /
+// MPI_Reduce -- is added beside what the adapter uses; nothing the adapter's drivers see has changed.
 #pragma once
 
 #include <cstdint>
@@ -13,8 +19,14 @@
 
 #include "mpi.h"
 
+#ifdef LAMMPS_MOCK_FMT
+#include "fmt/format.h"   // pointers.h of LAMMPS brings {fmt} to every style
+#endif
+
 #define FLERR __FILE__, __LINE__
 #define LAMMPS_VERSION "mock"
+#define NEIGHMASK 0x1FFFFFFF          // lmptype.h, default (SMALLBIG) sizes
+#define MPI_LMP_BIGINT MPI_LONG_LONG  // bigint is int64_t
 
 namespace LAMMPS_NS {
 
@@ -43,10 +55,81 @@ class Memory {
     std::free(array);
     array = nullptr;
   }
+  // 1-D and 3-D arrays, and grow (contents kept; a null array is created), as memory.h documents them
+  template <class T> T *create(T *&array, int n, const char *)
+  {
+    array = (T *) std::calloc((size_t) (n > 0 ? n : 1), sizeof(T));
+    return array;
+  }
+  template <class T> T *grow(T *&array, int n, const char *name)
+  {
+    if (!array) return create(array, n, name);
+    array = (T *) std::realloc(array, sizeof(T) * (size_t) (n > 0 ? n : 1));
+    return array;
+  }
+  template <class T> void destroy(T *&array)
+  {
+    std::free(array);
+    array = nullptr;
+  }
+  template <class T> T **grow(T **&array, int n1, int n2, const char *name)
+  {
+    if (!array) return create(array, n1, n2, name);
+    T *data = (T *) std::realloc(array[0], sizeof(T) * (size_t) n1 * n2);
+    array = (T **) std::realloc(array, sizeof(T *) * (size_t) n1);
+    for (int i = 0; i < n1; i++) array[i] = data + (size_t) i * n2;
+    return array;
+  }
+  template <class T> T ***create(T ***&array, int n1, int n2, int n3, const char *)
+  {
+    T *data = (T *) std::calloc((size_t) n1 * n2 * n3 + 1, sizeof(T));
+    T **plane = (T **) std::malloc(sizeof(T *) * ((size_t) n1 * n2 + 1));
+    array = (T ***) std::malloc(sizeof(T **) * (size_t) (n1 > 0 ? n1 : 1));
+    plane[0] = data;   // (so that destroy finds the blocks of an array with n1 * n2 == 0 as well)
+    array[0] = plane;
+    for (int i = 0; i < n1; i++) {
+      array[i] = plane + (size_t) i * n2;
+      for (int j = 0; j < n2; j++) array[i][j] = data + ((size_t) i * n2 + j) * n3;
+    }
+    return array;
+  }
+  template <class T> T ***grow(T ***&array, int n1, int n2, int n3, const char *name)
+  {
+    if (!array) return create(array, n1, n2, n3, name);
+    T *data = (T *) std::realloc(array[0][0], sizeof(T) * ((size_t) n1 * n2 * n3 + 1));
+    T **plane = (T **) std::realloc(array[0], sizeof(T *) * ((size_t) n1 * n2 + 1));
+    array = (T ***) std::realloc(array, sizeof(T **) * (size_t) (n1 > 0 ? n1 : 1));
+    plane[0] = data;
+    array[0] = plane;
+    for (int i = 0; i < n1; i++) {
+      array[i] = plane + (size_t) i * n2;
+      for (int j = 0; j < n2; j++) array[i][j] = data + ((size_t) i * n2 + j) * n3;
+    }
+    return array;
+  }
+  template <class T> void destroy(T ***&array)
+  {
+    if (!array) return;
+    std::free(array[0][0]);
+    std::free(array[0]);
+    std::free(array);
+    array = nullptr;
+  }
 };
 
 class Error {
  public:
+#ifdef LAMMPS_MOCK_FMT
+  // fmt-style arguments are formatted, as error.h documents
+  template <class... A> [[noreturn]] void all(const std::string &, int, const std::string &msg, A &&...args)
+  {
+    throw MockAbort("ERROR: " + fmt::vformat(msg, fmt::make_format_args(args...)));
+  }
+  template <class... A> [[noreturn]] void one(const std::string &, int, const std::string &msg, A &&...args)
+  {
+    throw MockAbort("ERROR on proc 0: " + fmt::vformat(msg, fmt::make_format_args(args...)));
+  }
+#else
   // (fmt-style arguments are appended unformatted: enough for a test driver)
   template <class... A> [[noreturn]] void all(const std::string &, int, const std::string &msg, A &&...)
   {
@@ -56,6 +139,7 @@ class Error {
   {
     throw MockAbort("ERROR on proc 0: " + msg);
   }
+#endif
 };
 
 class Atom {
@@ -111,6 +195,7 @@ class LAMMPS {
   MPI_Comm world = 0;
   void *kokkos = nullptr;
   std::string log;
+  bool quiet = false;   // keep utils::logmesg off stdout (the text is in `log` either way)
 };
 
 class Pointers {
@@ -138,8 +223,14 @@ namespace utils {
 inline void logmesg(LAMMPS *lmp, const std::string &mesg)
 {
   lmp->log += mesg;
-  std::fputs(mesg.c_str(), stdout);
+  if (!lmp->quiet) std::fputs(mesg.c_str(), stdout);
 }
+#ifdef LAMMPS_MOCK_FMT
+template <class... A> void logmesg(LAMMPS *lmp, const std::string &format, A &&...args)
+{
+  logmesg(lmp, fmt::vformat(format, fmt::make_format_args(args...)));
+}
+#endif
 inline std::string get_potential_file_path(const std::string &path)
 {
   if (FILE *fp = std::fopen(path.c_str(), "r")) {
@@ -175,6 +266,7 @@ class Pair : protected Pointers {
   int single_enable = 1, restartinfo = 1, one_coeff = 0, manybody_flag = 0, no_virial_fdotr_compute = 0;
   int nextra = 0;
   double *pvector = nullptr;
+  int copymode = 0;
   int allocated = 0;
   int **setflag = nullptr;
   double **cutsq = nullptr;
@@ -230,9 +322,59 @@ class Pair : protected Pointers {
       for (int i = 0; i < nall; i++)
         for (int q = 0; q < 6; q++) vatom[i][q] = 0.0;
   }
+
+  // ev_setup as pair.h / the developer guide describe it: the flags of ev_init, eatom / vatom (re)allocated when the
+  // atom arrays outgrew them, and only the accumulators that this call will tally are zeroed -- eng_vdwl / eng_coul
+  // with ENERGY_GLOBAL, virial with VIRIAL_PAIR or VIRIAL_FDOTR, eatom with ENERGY_ATOM, vatom with VIRIAL_ATOM, over
+  // owned and (newton on) ghost atoms.  What a call does not tally keeps what it held.
+  void ev_setup(int eflag, int vflag, int = 1)
+  {
+    evflag = 1;
+    eflag_either = eflag;
+    eflag_global = eflag & 1;
+    eflag_atom = eflag & 2;
+    vflag_either = vflag;
+    vflag_global = vflag & 3;
+    if (vflag_global == 2 && no_virial_fdotr_compute == 1) vflag_global = 1;
+    vflag_fdotr = 0;
+    if (vflag_global == 2) {
+      vflag_fdotr = 1;
+      vflag_global = 0;
+    }
+    vflag_atom = vflag & 4;
+    const int nall = atom->nlocal + atom->nghost;
+    if (eflag_atom && nall > maxeatom) {
+      std::free(eatom);
+      eatom = (double *) std::calloc((size_t) nall, sizeof(double));
+      maxeatom = nall;
+    }
+    if (vflag_atom && nall > maxvatom) {
+      if (vatom) {
+        std::free(vatom[0]);
+        std::free(vatom);
+      }
+      double *d = (double *) std::calloc((size_t) nall * 6, sizeof(double));
+      vatom = (double **) std::malloc(sizeof(double *) * (size_t) nall);
+      for (int i = 0; i < nall; i++) vatom[i] = d + 6 * (size_t) i;
+      maxvatom = nall;
+    }
+    const int n = force->newton_pair ? nall : atom->nlocal;
+    if (eflag_global) eng_vdwl = eng_coul = 0.0;
+    if (vflag_global || vflag_fdotr)
+      for (double &v : virial) v = 0.0;
+    if (eflag_atom)
+      for (int i = 0; i < n; i++) eatom[i] = 0.0;
+    if (vflag_atom)
+      for (int i = 0; i < n; i++)
+        for (int q = 0; q < 6; q++) vatom[i][q] = 0.0;
+  }
 };
 
 }   // namespace LAMMPS_NS
+
+#ifdef LAMMPS_MOCK_FMT
+#include "lammps_mock_text.h"   // text_file_reader.h, tokenizer.h and the rest of utils.h
+#endif
 
 // lammpsplugin.h
 extern "C" {

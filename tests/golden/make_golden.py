@@ -1,7 +1,9 @@
 """Writes the committed golden vectors (inputs + expected outputs).  The expected values
-come from the CPU oracle (oracle/mtp_oracle.c) -- NOT from a run of the reference, which
-cannot be built in this image ("Oracle"); they pin the oracle against
-regressions and give the GPU tests fixed vectors that need no generator run.
+come from the CPU oracle (oracle/mtp_oracle.c); the compiled reference (oracle/Makefile `ref`)
+gives the same bits on these inputs (tests/test_reference_cpu.py::
+test_committed_goldens_are_reference_outputs), so they are reference outputs too.  They pin the
+oracle against regressions and give the GPU tests fixed vectors that need no generator run.
+Reference outputs on the geometry edges: tests/golden/make_reference_golden.py.
 
     python tests/golden/make_golden.py
 """

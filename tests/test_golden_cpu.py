@@ -1,5 +1,6 @@
 """The committed golden vectors must be reproduced bit-for-bit by the oracle (they were
-written by it: a regression pin, see tests/golden/make_golden.py)."""
+written by it: a regression pin, see tests/golden/make_golden.py; tests/test_reference_cpu.py
+shows that they are outputs of the compiled reference as well)."""
 import os
 
 import numpy as np
