@@ -487,6 +487,9 @@ void fill_sizes(const mtp_potential &pot, MtpDevParams &b)
     b.deg_coef[d] = pot.deg_coef[d];
   }
   b.nlevels = pot.normal_levels;   // (the level table has one more entry: the leaf rows)
+  // the same table in the argument block when it fits (mtp_device.hpp); all zero otherwise
+  const bool lv_fit = pot.level_offset.size() == (size_t) pot.normal_levels + 2 && pot.level_offset.size() <= MTP_SHAPE_ARR_LEN;
+  for (int k = 0; k < MTP_SHAPE_ARR_LEN; k++) b.level_rows[k] = lv_fit && k < (int) pot.level_offset.size() ? pot.level_offset[k] : 0;
   b.nseed = (int) pot.seed_idx.size();
   b.Ad = pot.stored_moment_count;
   b.Am = b.Ad;                      // per launch: the grade instantiation keeps the leaves' values too

@@ -33,6 +33,11 @@ struct MtpDevParams {
   // one block of derivative-polynomial coefficients per slot (1 double for rank 0, 3*d*(d+1)/2 for rank d:
   // x-, y-, z-derivative, each over the monomials of degree d-1), rank d's blocks starting at deg_coef[d]
   int deg_first[MTP_PSTRIDE + 2], deg_coef[MTP_PSTRIDE + 2];
+  // the level table of the blob (off_level) once more: padded row offsets of the levels and of the leaf block, entries
+  // [0, nlevels + 1].  A shape field: a fixed-shape kernel has the bounds and block counts of its product levels as
+  // constants, and the launcher matches them here.  A table with more than MTP_PSTRIDE + 2 entries leaves this zero (no
+  // shape can fix it then); the generic kernels read the blob's copy
+  int level_rows[MTP_PSTRIDE + 2];
   int coef_total;          // doubles of all coefficient blocks
   int coef_dense;          // every coefficient has a source basic (no zero fill)
   double rmin, rmax, scaling, cutsq, inv_span;   // inv_span = 1 / (rmax - rmin)

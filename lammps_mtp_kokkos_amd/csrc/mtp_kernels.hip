@@ -745,6 +745,9 @@ const char *mtp_kernel_build_flags()
 #if MTP_MU_BITS != 1
       "MTP_MU_BITS=" MTP_STR(MTP_MU_BITS) " "
 #endif
+#if MTP_LEVEL_ARGS != 1
+      "MTP_LEVEL_ARGS=" MTP_STR(MTP_LEVEL_ARGS) " "
+#endif
 
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
       "MTP_GRADE_TPB=" MTP_STR(MTP_GRADE_TPB) " "

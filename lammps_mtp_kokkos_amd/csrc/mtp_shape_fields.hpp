@@ -21,7 +21,7 @@
   X(off_seg_fwd) X(off_seg_bwd) X(rows_in_lds) X(tgt_in_lds) X(scalars_in_lds) X(dg_mode) X(fp_row) X(pow_row)        \
   X(dg_off) X(w_m) X(w_d) X(w_coef) X(w_nb) X(tab_rows) X(ov_doubles) X(m_doubles) X(d_doubles)
 // int[MTP_PSTRIDE + 2] fields (a shape gives them as static constexpr int f(int k))
-#define MTP_SHAPE_ARR_FIELDS(X) X(deg_first) X(deg_coef)
+#define MTP_SHAPE_ARR_FIELDS(X) X(deg_first) X(deg_coef) X(level_rows)
 #define MTP_SHAPE_ARR_LEN (MTP_PSTRIDE + 2)
 
 // the generic shape: nothing fixed

@@ -284,62 +284,113 @@ static __device__ __forceinline__ const double &at8(const double *base, unsigned
   return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + byte_off);
 }
 
+// Row bounds of the product levels.  The level table is atom-invariant and wave-uniform, yet read from the LDS blob
+// every level start waits for an LDS round trip (and a lane read) before its first row address exists: seven such
+// starts per atom at level 16 (three levels forward, the leaf block, three levels in reverse).  MtpDevParams::level_rows
+// is the same table in the argument block, a shape field like the others: a fixed shape that lists it (and nlevels)
+// has the bounds, and with them the block count of every level, as constants (level_ct).  The generic kernels keep the
+// LDS reads: a scalar load of the field per bound costs their headline function ten more s_load than the round-6 guard
+// allows (tests/test_isa_params_cpu.py; profiles/r08_ab_table_reads.txt has the timing).
+#ifndef MTP_LEVEL_ARGS
+#define MTP_LEVEL_ARGS 1   // 0: the fixed shapes read the bounds from the blob's level table too, for A/B runs
+#endif
+template <class SH>
+constexpr bool level_ct = MTP_LEVEL_ARGS && mtp_shape::has_nlevels<SH>::value && mtp_shape::has_level_rows<SH>::value;
+template <class SH> __device__ __forceinline__ int level_row(const int *level, int l)   // l wave-uniform
+{
+  if constexpr (level_ct<SH>) return SH::level_rows(l);
+  else return __builtin_amdgcn_readfirstlane(level[l]);
+}
+
 // Phase 4a: M[a3] += mult * M[a0] * M[a1], one dependency level at a time.  Rows of one level
 // never write an operand of the same level, so four rows per lane are in flight before their
 // ds_add_f64 issue.  (Two call sites, LDS-resident and HBM-resident rows: a select between the two
 // pointers would go through a generic pointer, which hipcc 7.2 miscompiles on gfx950.)
-template <int U>
-__device__ __forceinline__ void products_forward(const MtpRow8 *rows, const int *level, int nlevels, double *M,
-                                                 int lane)
+// one level of nit blocks in trips of U (nit a constant where the shape fixes the level table: the loop unrolls and the idle
+// slot of an odd count, whose clamped index re-reads the last block, folds into the slot before it)
+template <int U> __device__ __forceinline__ void forward_level(const MtpRow8 *rp, int nit, double *M)
 {
-  for (int l = 0; l < nlevels; l++) {
-    // levels are padded to whole 64-row blocks on the host (neutral rows): no bounds checks, no lane masks
-    const int beg = __builtin_amdgcn_readfirstlane(level[l]);
-    const int nit = (__builtin_amdgcn_readfirstlane(level[l + 1]) - beg) >> 6;
-    const MtpRow8 *rp = rows + beg + lane;
-    for (int it = 0; it < nit; it += U) {
-      MtpRow8 rw[U];
-      double v[U];
+  for (int it = 0; it < nit; it += U) {
+    MtpRow8 rw[U];
+    double v[U];
 #pragma unroll
-      for (int u = 0; u < U; u++) rw[u] = rp[64 * min(it + u, nit - 1)];   // uniform clamp: the tail re-reads the last block
+    for (int u = 0; u < U; u++) rw[u] = rp[64 * min(it + u, nit - 1)];   // uniform clamp: the tail re-reads the last block
 #pragma unroll
-      for (int u = 0; u < U; u++) v[u] = at8(M, rw[u].lo & 0xffffu) * at8(M, rw[u].lo >> 16);
+    for (int u = 0; u < U; u++) v[u] = at8(M, rw[u].lo & 0xffffu) * at8(M, rw[u].lo >> 16);
 #pragma unroll
-      for (int u = 0; u < U; u++)
-        if (it + u < nit) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v[u]);   // uniform branch
-    }
+    for (int u = 0; u < U; u++)
+      if (it + u < nit) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v[u]);   // uniform branch
+  }
+}
+template <int U, class SH, int L> __device__ __forceinline__ void forward_levels_ct(const MtpRow8 *rows, double *M, int lane)
+{
+  if constexpr (L < SH::nlevels) {
+    constexpr int beg = SH::level_rows(L), nit = (SH::level_rows(L + 1) - beg) >> 6;
+    forward_level<U>(rows + beg + lane, nit, M);
     wave_fence();
+    forward_levels_ct<U, SH, L + 1>(rows, M, lane);
+  }
+}
+template <int U, class SH>
+__device__ __forceinline__ void products_forward(KP kp, const MtpRow8 *rows, const int *level, double *M, int lane)
+{
+  if constexpr (level_ct<SH>) {
+    static_assert(SH::nlevels + 2 <= MTP_SHAPE_ARR_LEN, "level_rows holds the whole level table or zeros");
+    forward_levels_ct<U, SH, 0>(rows, M, lane);
+  } else {
+    for (int l = 0; l < SHF(nlevels); l++) {
+      // levels are padded to whole 64-row blocks on the host (neutral rows): no bounds checks, no lane masks
+      const int beg = level_row<SH>(level, l);
+      forward_level<U>(rows + beg + lane, (level_row<SH>(level, l + 1) - beg) >> 6, M);
+      wave_fence();
+    }
   }
 }
 
 // Phase 4b: D[a1] += D[a3] mult M[a0]; D[a0] += D[a3] mult M[a1], levels in reverse.
-template <int U>
-__device__ __forceinline__ void products_backward(const MtpRow8 *rows, const int *level, int nlevels,
-                                                  const double *M, double *D, int lane)
+template <int U> __device__ __forceinline__ void backward_level(const MtpRow8 *rp, int nit, const double *M, double *D)
 {
-  for (int l = nlevels - 1; l >= 0; l--) {
-    const int beg = __builtin_amdgcn_readfirstlane(level[l]);
-    const int nit = (__builtin_amdgcn_readfirstlane(level[l + 1]) - beg) >> 6;
-    const MtpRow8 *rp = rows + beg + lane;
-    for (int it = 0; it < nit; it += U) {
-      MtpRow8 rw[U];
-      double d3[U], m0[U], m1[U];
+  for (int it = 0; it < nit; it += U) {
+    MtpRow8 rw[U];
+    double d3[U], m0[U], m1[U];
 #pragma unroll
-      for (int u = 0; u < U; u++) rw[u] = rp[64 * min(it + u, nit - 1)];
+    for (int u = 0; u < U; u++) rw[u] = rp[64 * min(it + u, nit - 1)];
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        d3[u] = at8(D, rw[u].hi & 0xffffu) * (double) ((int) rw[u].hi >> 16);
-        m0[u] = at8(M, rw[u].lo & 0xffffu);
-        m1[u] = at8(M, rw[u].lo >> 16);
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (it + u < nit) {
-          lds_add(&at8(D, rw[u].lo >> 16), d3[u] * m0[u]);
-          lds_add(&at8(D, rw[u].lo & 0xffffu), d3[u] * m1[u]);
-        }
+    for (int u = 0; u < U; u++) {
+      d3[u] = at8(D, rw[u].hi & 0xffffu) * (double) ((int) rw[u].hi >> 16);
+      m0[u] = at8(M, rw[u].lo & 0xffffu);
+      m1[u] = at8(M, rw[u].lo >> 16);
     }
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if (it + u < nit) {
+        lds_add(&at8(D, rw[u].lo >> 16), d3[u] * m0[u]);
+        lds_add(&at8(D, rw[u].lo & 0xffffu), d3[u] * m1[u]);
+      }
+  }
+}
+template <int U, class SH, int L>
+__device__ __forceinline__ void backward_levels_ct(const MtpRow8 *rows, const double *M, double *D, int lane)
+{
+  if constexpr (L >= 0) {
+    constexpr int beg = SH::level_rows(L), nit = (SH::level_rows(L + 1) - beg) >> 6;
+    backward_level<U>(rows + beg + lane, nit, M, D);
     wave_fence();
+    backward_levels_ct<U, SH, L - 1>(rows, M, D, lane);
+  }
+}
+template <int U, class SH>
+__device__ __forceinline__ void products_backward(KP kp, const MtpRow8 *rows, const int *level, const double *M, double *D,
+                                                  int lane)
+{
+  if constexpr (level_ct<SH>) {
+    backward_levels_ct<U, SH, SH::nlevels - 1>(rows, M, D, lane);
+  } else {
+    for (int l = SHF(nlevels) - 1; l >= 0; l--) {
+      const int beg = level_row<SH>(level, l);
+      backward_level<U>(rows + beg + lane, (level_row<SH>(level, l + 1) - beg) >> 6, M, D);
+      wave_fence();
+    }
   }
 }
 

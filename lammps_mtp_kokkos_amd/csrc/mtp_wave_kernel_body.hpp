@@ -369,14 +369,15 @@
     if constexpr (GATHER) {
       gather_pass(kp->prog_fwd, bt.seg_fwd, SHF(nlevels), w.M, w.M, w.M, lane);
     } else {
-      if (rows_lds) products_forward<MTP_PU>(bt.rows, bt.level, SHF(nlevels), w.M, lane);
-      else products_forward<MTP_PU>(kp->rows, bt.level, SHF(nlevels), w.M, lane);
+      if (rows_lds) products_forward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, lane);
+      else products_forward<MTP_PU, SH>(kp, kp->rows, bt.level, w.M, lane);
     }
     // ---- site energy (pair_mtp.cpp:204-212): the leaf rows' share first ------------------------------------
     double e = 0.0;
     // (two code paths per table home, LDS blob or HBM/L2: no pointer selects between address spaces, see below)
-    const int leaf_beg = __builtin_amdgcn_readfirstlane(bt.level[SHF(nlevels)]);
-    const int leaf_nit = (__builtin_amdgcn_readfirstlane(bt.level[SHF(nlevels) + 1]) - leaf_beg) >> 6;
+    // (bounds from the blob's level table or the shape's constants: level_row, mtp_wave_body.hpp)
+    const int leaf_beg = level_row<SH>(bt.level, SHF(nlevels));
+    const int leaf_nit = (level_row<SH>(bt.level, SHF(nlevels) + 1) - leaf_beg) >> 6;
     if (rows_lds) e = leaf_forward<MTP_PU, GRADE, false, MTP_LEAF_SWEEP>(bt.rows, bt.leaf_cf, leaf_beg, leaf_nit, w.M, lane, bt.leaf_cb, w.D);
     else e = leaf_forward<MTP_PU, GRADE, true, MTP_LEAF_SWEEP>(kp->rows, kp->leaf_cf, leaf_beg, leaf_nit, w.M, lane, kp->leaf_cb, w.D);
     STAMP(4);   // products forward
@@ -418,8 +419,8 @@
     if constexpr (GATHER) {
       gather_pass(kp->prog_bwd, bt.seg_bwd, SHF(nlevels), w.D, w.M, w.D, lane);
     } else {
-      if (rows_lds) products_backward<MTP_PU>(bt.rows, bt.level, SHF(nlevels), w.M, w.D, lane);
-      else products_backward<MTP_PU>(kp->rows, bt.level, SHF(nlevels), w.M, w.D, lane);
+      if (rows_lds) products_backward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, w.D, lane);
+      else products_backward<MTP_PU, SH>(kp, kp->rows, bt.level, w.M, w.D, lane);
     }
 
     STAMP(6);   // products backward
