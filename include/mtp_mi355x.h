@@ -12,7 +12,7 @@
  * Streams.  Device work is ordered on the `stream` (a hipStream_t) given to an entry point.  ONE rule for NULL:
  *   - entry points that take a context (mtp_compute_device[_rows], mtp_build_neighbors_device,
  *     mtp_set_neighbors_device_2d, mtp_synchronize, mtp_halo_force_step, mtp_ghosts_reverse_finish,
- *     mtp_batch_cfg_grades): NULL means the
+ *     mtp_batch_cfg_grades, mtp_batch_cfg_candidates, mtp_maxvol_select): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
  *     mtp_batch_reduce): NULL is
@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 4
+#define MTP_MI355X_ABI_VERSION 5
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -438,6 +438,64 @@ int mtp_batch_reduce(void *stream, int ncfg, const int *d_cfg_first, const doubl
  * neighbourhood grades (calculate_extrapolation_grade, :347-358) and divided by the configuration's atom count, 0 for an
  * empty one (:373-376).  NULL stream = the context's. */
 int mtp_batch_cfg_grades(mtp_context *ctx, void *stream, int ncfg, const int *d_cfg_first, int nrows, double *d_cfg_grade);
+
+
+/* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------
+ *
+ * The step of the active-learning loop that consumes the grades (MLIP's select-add; the reference only grades,
+ * pair_mtp_extrapolation.cpp:347-358, and writes the pre-selected configurations, :401-479).
+ *
+ * Convention.  The reference grades a candidate vector c with gamma_i = sum_j W[i][j] c_j, W being the second raw block
+ * of the #MVS_v1.1 tail read row-major (:347-358, :608-611).  Call the first block S.  This library takes the COLUMNS of
+ * S to be the selected candidate vectors and W = S^-1: the only reading under which a member of the active set grades
+ * exactly e_j with the reference's formula, and one every potential file of this project satisfies.  Whether files
+ * written by MLIP-3 itself follow it depends on how MLIP orders the blocks in memory; nothing here
+ * depends on that.  A swap puts pool row i into slot j: S[:, j] <- v_i.  With G[n, :] = W v_n and the pivot p = G[i][j],
+ * every row r of the stacked matrix [W^T ; G] is updated as r <- r - r[j] u, u = (G[i, :] - e_j) / p, and |det S| grows
+ * by the factor |p|.
+ */
+/* copy of the first raw block S (mtp_potential_get_tables returns the second, W); MTP_ERR_STATE without a selection block */
+int mtp_potential_get_active_set(const mtp_potential *pot, double *active_set /*[C*C]*/);
+/* Writes a potential file that is src_path with the two raw blocks replaced: the bytes of src_path up to and including
+ * the '#' in front of the raw blocks (pair_mtp_extrapolation.cpp:607), then active_set and inverse_active_set, C * C
+ * doubles each.  Host only; written under a temporary name beside dst_path and renamed.  MTP_ERR_SELECTION for a source
+ * without an #MVS tail, MTP_ERR_ARG for a coeff_count that is not the file's, otherwise the parser's codes. */
+int mtp_potential_write_selection(const char *src_path, const char *dst_path, const double *active_set,
+                                  const double *inverse_active_set, int coeff_count, char *err, int errlen);
+/* The per-atom candidate vectors dE_i/dtheta of the grade calls on the installed list (what
+ * PairMTPExtrapolation::compute accumulates per atom, :97-98, 240-252): row ii belongs to list row ii, *ld doubles apart,
+ * the first C of them used.  *nrows counts the rows from 0 that the grade calls on this list have covered without a gap:
+ * a call over a row range that starts above them (mtp_compute_device_rows) does not extend it.  The storage is the
+ * context's own: valid until the next list is installed.  MTP_ERR_STATE before a grade call that covers row 0. */
+int mtp_context_candidates_device(const mtp_context *ctx, const double **d_rows, int *nrows, int *ld);
+/* Per-configuration candidate vectors after a grade call over nrows = cfg_first[ncfg] rows (arguments as for
+ * mtp_batch_cfg_grades): the sums of the rows of each configuration divided by its atom count, so that a row's grade is
+ * the configuration grade mtp_batch_cfg_grades reports (:369-376); an empty configuration is a zero row.  The storage is
+ * the context's own, shared with mtp_batch_cfg_grades: valid until the next call of either.  NULL stream = the context's. */
+int mtp_batch_cfg_candidates(mtp_context *ctx, void *stream, int ncfg, const int *d_cfg_first, int nrows,
+                             const double **d_rows, int *ld);
+/* MaxVol over a pool of nrows candidate vectors d_rows[nrows][ld] (device, the first C of each row used), starting from
+ * the potential's S and W: while some |G[i][j]| exceeds `threshold`, the largest one (ties to the smaller n * C + j) is
+ * swapped in.  Per swap one pivot kernel and one pass over the (C + nrows) x cpad stacked matrix run on `stream`; the host
+ * reads a 16-byte status once per 16 swaps.  Every `refresh` swaps, and always before the call ends, G is recomputed from
+ * the pool and the current W: *converged = 1 only when freshly computed grades hold no entry above the threshold, and
+ * *max_grade_after is their maximum -- what a later grade call with the written file reports.  The context's own inverse
+ * is NOT changed: selection is followed by a reload of the written file, as in the MLIP loop.
+ *   active_set, inverse_active_set [C*C]  S' and W' (host); every changed column of S' is a pool row bit for bit
+ *   slot_source [C]                      the pool row now in slot j, -1 where the original column was kept
+ *   swap_rows, swap_slots, swap_pivots   [max_swaps] the log: swap k put row i into slot j with pivot p
+ *   log_volume_gain                      sum log |p| = log |det S'| - log |det S|
+ * NULL stream = the context's.  MTP_ERR_STATE without a selection block; MTP_ERR_ARG for threshold < 1, ld < C,
+ * max_swaps < 0, refresh < 1 (nothing launched), and for a non-finite candidate: the outputs then describe the state
+ * before the offending pivot.  nrows == 0 is valid: zero swaps, outputs equal to the potential's blocks bit for bit.
+ * Reaching max_swaps is no error: *converged = 0 and the outputs are the state reached.  The device memory of a call
+ * ((C + nrows) x cpad doubles and a little more) is the context's and is kept for the next one; MTP_ERR_LIMIT when it
+ * cannot be had. */
+int mtp_maxvol_select(mtp_context *ctx, void *stream, const double *d_rows, long long nrows, int ld, double threshold,
+                      int max_swaps, int refresh, double *active_set /*[C*C] host*/,
+                      double *inverse_active_set /*[C*C] host*/, int *slot_source /*[C]*/, int *swap_rows, int *swap_slots,
+                      double *swap_pivots /*[max_swaps]*/, int *nswaps, int *converged, double *log_volume_gain,
+                      double *max_grade_after);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,8 @@ EXPORTS = [
     "mtp_ghosts_build_cell", "mtp_ghosts_cell_bounds",
     "mtp_plan_fixed_fields", "mtp_plan_fixed_shape", "mtp_context_last_shape",
     "mtp_batch_layout", "mtp_ghosts_build_batch", "mtp_batch_reduce", "mtp_batch_cfg_grades",
+    "mtp_potential_get_active_set", "mtp_potential_write_selection", "mtp_context_candidates_device",
+    "mtp_batch_cfg_candidates", "mtp_maxvol_select",
 ]
 # mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
 # workgroup of BATCH_BLOCK threads; the grade kernel behind mtp_batch_cfg_grades takes GRADE_ROWS_PER_BLOCK rows a workgroup
@@ -147,6 +149,7 @@ def _ptr(t):
 class Potential:
     def __init__(self, path, selection=False):
         self.h = C.c_void_p()
+        self.path = os.fspath(path)
         err = C.create_string_buffer(512)
         rc = lib().mtp_potential_load(os.fsencode(path), int(selection), C.byref(self.h), err, 512)
         if rc:
@@ -184,6 +187,16 @@ class Potential:
         if inv is not None:
             out["inverse_active_set"] = inv
         return out
+
+    def active_set(self):
+        """the first raw block S of the selection state, [C, C]: its columns are the selected candidate vectors and the
+        second block (tables()["inverse_active_set"]) is its inverse (mtp_potential_get_active_set)"""
+        C_ = self.info.coeff_count
+        S = np.zeros((C_, C_))
+        rc = lib().mtp_potential_get_active_set(self.h, _np(S, C.c_double))
+        if rc:
+            raise MtpError(rc, "get_active_set: the potential carries no selection state")
+        return S
 
     def kernel_shape(self):
         """the force kernel instantiation a context of this potential launches (mtp_potential_kernel_shape)"""
@@ -353,6 +366,58 @@ class Context:
         self._check(lib().mtp_batch_cfg_grades(self.h, C.c_void_p(stream) if stream else None, int(cfg_first_t.numel()) - 1,
                                                _ptr(cfg_first_t), int(nrows), _ptr(cfg_grade_t)))
 
+    def candidates(self):
+        """per-atom candidate vectors of the grade calls on the installed list as a torch view [list rows, ld] of the
+        context's own storage (the first C columns are used): mtp_context_candidates_device"""
+        d, n, ld = C.c_void_p(), C.c_int(), C.c_int()
+        rc = lib().mtp_context_candidates_device(self.h, C.byref(d), C.byref(n), C.byref(ld))
+        if rc:                                               # (a const context keeps no message of its own)
+            raise MtpError(rc, "no candidate vectors: call after a grade call on the installed list")
+        return _device_view(d.value, n.value, ld.value)
+
+    def batch_cfg_candidates(self, cfg_first_t, nrows, stream=None):
+        """per-configuration candidate vectors (sums over the configuration's rows / its atom count) of the grade call just
+        made over `nrows` rows, as a torch view [ncfg, ld] of the context's own storage: mtp_batch_cfg_candidates"""
+        d, ld = C.c_void_p(), C.c_int()
+        ncfg = int(cfg_first_t.numel()) - 1
+        self._check(lib().mtp_batch_cfg_candidates(self.h, C.c_void_p(stream) if stream else None, ncfg, _ptr(cfg_first_t),
+                                                   int(nrows), C.byref(d), C.byref(ld)))
+        return _device_view(d.value, ncfg, ld.value)
+
+    def maxvol_select(self, rows_t, threshold, max_swaps=None, refresh=64, stream=None):
+        """MaxVol over the pool rows_t [N, ld] (fp64 device tensor, rows ld >= C doubles apart, the first C used), starting
+        from the potential's active set: mtp_maxvol_select.  max_swaps defaults to 4 C.  Returns dict(active_set,
+        inverse_active_set [C, C], slot_source [C], swaps [(row, slot, pivot)], nswaps, converged, log_volume_gain,
+        max_grade_after).  A non-finite candidate raises MtpError(ARG) whose .result is that dict for the state before the
+        offending pivot."""
+        C_ = int(self.pot.info.coeff_count)
+        max_swaps = 4 * C_ if max_swaps is None else int(max_swaps)
+        n = int(rows_t.shape[0])
+        ld = int(rows_t.stride(0)) if n > 0 else max(C_, int(rows_t.shape[1]) if rows_t.dim() > 1 else C_)
+        if n > 0 and (rows_t.dim() != 2 or rows_t.stride(1) != 1 or str(rows_t.dtype) != "torch.float64"):
+            raise ValueError("maxvol_select: the pool must be an fp64 matrix with contiguous rows")
+        if n > 0 and rows_t.shape[1] < C_:
+            ld = -1                              # (refused by the library: rows shorter than C)
+        S, W = np.zeros((C_, C_)), np.zeros((C_, C_))
+        src = np.zeros(C_, np.int32)
+        m = max(max_swaps, 1)
+        si, sj, sp = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m)
+        ns, conv, gain, mg = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
+        rc = lib().mtp_maxvol_select(self.h, C.c_void_p(stream) if stream else None, _ptr(rows_t) if n > 0 else None,
+                                     C.c_longlong(n), int(ld), C.c_double(threshold), int(max_swaps), int(refresh),
+                                     _np(S, C.c_double), _np(W, C.c_double), _np(src, C.c_int), _np(si, C.c_int),
+                                     _np(sj, C.c_int), _np(sp, C.c_double), C.byref(ns), C.byref(conv), C.byref(gain),
+                                     C.byref(mg))
+        k = ns.value
+        out = dict(active_set=S, inverse_active_set=W, slot_source=src,
+                   swaps=[(int(si[q]), int(sj[q]), float(sp[q])) for q in range(k)], nswaps=k, converged=bool(conv.value),
+                   log_volume_gain=gain.value, max_grade_after=mg.value)
+        if rc:
+            e = MtpError(rc, lib().mtp_last_error(self.h).decode())
+            e.result = out
+            raise e
+        return out
+
     def last_shape(self):
         """name of the fixed-shape kernel the last force launch ran, "" for a generic kernel"""
         buf = C.create_string_buffer(128)
@@ -386,6 +451,34 @@ class Context:
         ms = C.c_float(0)
         self._check(lib().mtp_context_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
+
+
+def _device_view(ptr, nrows, ld):
+    """torch view [nrows, ld] (fp64) of device memory the library owns -- no copy; the caller keeps the owner alive"""
+    import torch
+
+    class _Span:
+        pass
+    span = _Span()
+    span.__cuda_array_interface__ = dict(shape=(int(nrows), int(ld)), typestr="<f8", data=(int(ptr), False), version=2,
+                                         strides=None)
+    if nrows == 0:
+        return torch.zeros((0, int(ld)), dtype=torch.float64, device="cuda")
+    return torch.as_tensor(span, device="cuda")
+
+
+def write_selection(src, dst, active_set, inverse_active_set):
+    """`src` with its two raw selection blocks replaced by active_set (S: columns = selected candidate vectors) and
+    inverse_active_set (W = S^-1), written to `dst` through a temporary file: mtp_potential_write_selection (host only)"""
+    S = np.ascontiguousarray(active_set, dtype=np.float64)
+    W = np.ascontiguousarray(inverse_active_set, dtype=np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1] or W.shape != S.shape:
+        raise ValueError("write_selection: active_set and inverse_active_set must be square matrices of one size")
+    err = C.create_string_buffer(512)
+    rc = lib().mtp_potential_write_selection(os.fsencode(src), os.fsencode(dst), _np(S, C.c_double), _np(W, C.c_double),
+                                             int(S.shape[0]), err, 512)
+    if rc:
+        raise MtpError(rc, err.value.decode())
 
 
 def zero_async(t, stream=None):

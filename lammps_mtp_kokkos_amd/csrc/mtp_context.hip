@@ -1,7 +1,11 @@
 // Context (one GPU) and the extern "C" entry points of libmtp_mi355x (include/mtp_mi355x.h).
 #include <hip/hip_runtime.h>
 
+#include <unistd.h>
+
 #include <algorithm>
+#include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -110,7 +114,9 @@ struct mtp_context {
   DevBuf<double> d_cvec, d_ainv_pad, d_ainv_tiled, d_dbasic;
   DevBuf<double> d_csum;   // mtp_batch_cfg_grades: [ncfg][cpad] candidate vectors summed per configuration
   DevBuf<int> d_ident;     // and the identity ilist its grade launch reads them by
+  DevBuf<double> d_maxvol;   // mtp_maxvol_select: the stacked matrix [W^T ; G] and the small state around it, kept between calls
   int cpad = 0, dpad = 0;
+  int cvec_rows = 0;       // rows [0, cvec_rows) of the installed list all hold candidate vectors of grade calls on it
   // device-resident outputs of mtp_compute_resident (the /kk styles' DualViews): which of them the last call filled
   bool res_valid = false;
   int res_eflag = 0, res_vflag = 0, res_grade = 0;
@@ -573,6 +579,70 @@ int mtp_potential_get_tables(const mtp_potential *p, int32_t *aib, int32_t *ait,
   return MTP_OK;
 }
 
+int mtp_potential_get_active_set(const mtp_potential *p, double *active_set)
+{
+  if (!p || !active_set) return MTP_ERR_ARG;
+  if (!p->has_selection) return MTP_ERR_STATE;
+  std::memcpy(active_set, p->active_set.data(), p->active_set.size() * sizeof(double));
+  return MTP_OK;
+}
+
+int mtp_potential_write_selection(const char *src_path, const char *dst_path, const double *active_set,
+                                  const double *inverse_active_set, int coeff_count, char *err, int errlen)
+{
+  if (!src_path || !dst_path || !active_set || !inverse_active_set) {
+    copy_err("mtp_potential_write_selection: null argument", err, errlen);
+    return MTP_ERR_ARG;
+  }
+  mtp_potential src;
+  std::string msg;
+  const int rc = mtp_parse_file(src_path, true, src, msg);
+  if (rc != MTP_OK) {
+    copy_err(msg, err, errlen);
+    return rc;
+  }
+  if (coeff_count != src.coeff_count) {
+    copy_err("mtp_potential_write_selection: coeff_count is " + std::to_string(coeff_count) + ", the file's is " +
+                 std::to_string(src.coeff_count),
+             err, errlen);
+    return MTP_ERR_ARG;
+  }
+  // the text of the source up to and including the '#' of the raw blocks, byte for byte, then the two blocks
+  std::vector<char> head((size_t) src.selection_offset);
+  FILE *in = std::fopen(src_path, "rb");
+  const bool got = in && std::fread(head.data(), 1, head.size(), in) == head.size();
+  if (in) std::fclose(in);
+  if (!got) {
+    copy_err(std::string("Cannot read potential file ") + src_path, err, errlen);
+    return MTP_ERR_IO;
+  }
+  const std::string tmp = std::string(dst_path) + ".tmp" + std::to_string((long) getpid());
+  FILE *out = std::fopen(tmp.c_str(), "wb");
+  if (!out) {
+    copy_err("Cannot open " + tmp + " for writing: " + std::strerror(errno), err, errlen);
+    return MTP_ERR_IO;
+  }
+  const size_t n = (size_t) coeff_count * coeff_count;
+  bool ok = std::fwrite(head.data(), 1, head.size(), out) == head.size() &&
+            std::fwrite(active_set, sizeof(double), n, out) == n &&
+            std::fwrite(inverse_active_set, sizeof(double), n, out) == n;
+  int why = ok ? 0 : errno;   // of the call that failed, not of one after it
+  if (std::fclose(out) != 0 && ok) {
+    ok = false;
+    why = errno;
+  }
+  if (ok && std::rename(tmp.c_str(), dst_path) != 0) {
+    ok = false;
+    why = errno;
+  }
+  if (!ok) {
+    copy_err(std::string("Cannot write potential file ") + dst_path + ": " + std::strerror(why), err, errlen);
+    std::remove(tmp.c_str());
+    return MTP_ERR_IO;
+  }
+  return MTP_OK;
+}
+
 int mtp_cfg_grade(const mtp_potential *p, const double *c, double *grade)
 {
   if (!p || !c || !grade) return MTP_ERR_ARG;
@@ -776,6 +846,7 @@ static int finish_list(mtp_context *c, int inum, int nall, int max_numneigh)
   c->nall = nall;
   c->max_numneigh = max_numneigh;
   c->have_list = true;
+  c->cvec_rows = 0;
   try {
     c->plan();
     if (c->pot->has_selection && inum > 0) {   // candidate vectors, zero padded rows of cpad doubles
@@ -1118,6 +1189,7 @@ const char *mtp_build_flags(void)
     f += "MTP_STAMPS ";
 #endif
     f += mtp_kernel_build_flags();
+    f += mtp_maxvol_build_flags();
     if (!f.empty() && f.back() == ' ') f.pop_back();
     return f;
   }();
@@ -1268,6 +1340,7 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
                                          c->lp[1].wpb, c->lp[1].lds_bytes, st));
       }
       const double *cv = c->d_cvec.ptr + (size_t) row_begin * c->cpad;
+      if (row_begin <= c->cvec_rows) c->cvec_rows = std::max(c->cvec_rows, row_begin + row_count);   // (no gap below)
       if (cfg)
         HIP_CHECK(mtp_launch_colsum_kernel(cv, c->cpad, c->pot->coeff_count, row_count, d_coeff_ders, st));
       else
@@ -1333,6 +1406,116 @@ int mtp_batch_cfg_grades(mtp_context *c, void *stream, int ncfg, const int *d_cf
   } catch (const HipFail &f) {
     c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
     return MTP_ERR_DEVICE;
+  }
+  return MTP_OK;
+}
+
+// ---- MaxVol selection (include/mtp_mi355x.h) -------------------------------------------------------------------------
+int mtp_context_candidates_device(const mtp_context *c, const double **d_rows, int *nrows, int *ld)
+{
+  if (!c || !d_rows || !nrows || !ld) return MTP_ERR_ARG;
+  if (!c->pot->has_selection || !c->have_list || c->cvec_rows <= 0 || (size_t) c->cvec_rows * c->cpad > c->d_cvec.cap)
+    return MTP_ERR_STATE;   // (const context: no message) no grade call on the installed list yet
+  *d_rows = c->d_cvec.ptr;
+  *nrows = c->cvec_rows;
+  *ld = c->cpad;
+  return MTP_OK;
+}
+
+int mtp_batch_cfg_candidates(mtp_context *c, void *stream, int ncfg, const int *d_cfg_first, int nrows, const double **d_rows,
+                             int *ld)
+{
+  if (!c) return MTP_ERR_ARG;
+  if (ncfg < 0 || nrows < 0 || !d_rows || !ld || (ncfg > 0 && !d_cfg_first)) return MTP_ERR_ARG;
+  if (!c->pot->has_selection) {
+    c->last_error = "mtp_batch_cfg_candidates: the potential carries no selection state";
+    return MTP_ERR_STATE;
+  }
+  if (!c->have_list || nrows > c->cvec_rows || (size_t) nrows * c->cpad > c->d_cvec.cap) {
+    c->last_error = "mtp_batch_cfg_candidates: no candidate vectors for these rows (call after a grade call on the installed list)";
+    return MTP_ERR_STATE;
+  }
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  try {
+    c->d_csum.reserve((size_t) std::max(ncfg, 1) * c->cpad);
+    c->d_ident.reserve((size_t) std::max(ncfg, 1));
+    if (ncfg > 0) {
+      HIP_CHECK(mtp_launch_batch_colsum(c->d_cvec.ptr, c->cpad, ncfg, d_cfg_first, c->d_csum.ptr, c->d_ident.ptr, st));
+      HIP_CHECK(mtp_launch_maxvol_scale_rows(c->d_csum.ptr, c->cpad, ncfg, d_cfg_first, st));
+    }
+  } catch (const HipFail &f) {
+    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
+    return MTP_ERR_DEVICE;
+  }
+  *d_rows = c->d_csum.ptr;
+  *ld = c->cpad;
+  return MTP_OK;
+}
+
+int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long long nrows, int ld, double threshold,
+                      int max_swaps, int refresh, double *active_set, double *inverse_active_set, int *slot_source,
+                      int *swap_rows, int *swap_slots, double *swap_pivots, int *nswaps, int *converged,
+                      double *log_volume_gain, double *max_grade_after)
+{
+  if (!c) return MTP_ERR_ARG;
+  const mtp_potential &p = *c->pot;
+  if (!p.has_selection) {
+    c->last_error = "mtp_maxvol_select: the potential carries no selection state";
+    return MTP_ERR_STATE;
+  }
+  const int C = p.coeff_count;
+  if (!(threshold >= 1.0) || !std::isfinite(threshold) || nrows < 0 || ld < C || max_swaps < 0 || refresh < 1 ||
+      (nrows > 0 && !d_rows) || !active_set || !inverse_active_set || !slot_source || !nswaps || !converged ||
+      (max_swaps > 0 && (!swap_rows || !swap_slots || !swap_pivots))) {
+    c->last_error = "mtp_maxvol_select: needs threshold >= 1, ld >= coeff_count, max_swaps >= 0, refresh >= 1 and its outputs";
+    return MTP_ERR_ARG;
+  }
+  if (nrows * (long long) C > (1ll << 62) / C) {
+    c->last_error = "mtp_maxvol_select: too many rows";
+    return MTP_ERR_LIMIT;
+  }
+  double mg = 0.0;
+  int bad = 0;
+  *nswaps = 0;
+  *converged = 1;
+  if (nrows == 0) {   // nothing to select from: the potential's own blocks, bit for bit
+    std::memcpy(active_set, p.active_set.data(), p.active_set.size() * sizeof(double));
+    std::memcpy(inverse_active_set, p.inverse_active_set.data(), p.inverse_active_set.size() * sizeof(double));
+    for (int j = 0; j < C; j++) slot_source[j] = -1;
+  } else {
+    if (hipSetDevice(c->device) != hipSuccess) {
+      c->last_error = "hipSetDevice failed";
+      return MTP_ERR_DEVICE;
+    }
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipError_t e = hipSuccess;
+    try {   // the arena is the context's and is kept: a selection loop allocates once
+      c->d_maxvol.reserve(mtp_maxvol_arena_doubles(c->num_cus, C, nrows, max_swaps));
+      e = mtp_maxvol_run(st, c->num_cus, c->d_maxvol.ptr, C, p.active_set.data(), p.inverse_active_set.data(), d_rows, nrows,
+                         ld, threshold, max_swaps, refresh, active_set, inverse_active_set, slot_source, swap_rows, swap_slots,
+                         swap_pivots, nswaps, converged, &mg, &bad);
+    } catch (const HipFail &f) {
+      e = f.e;
+    } catch (const std::bad_alloc &) {
+      c->last_error = "mtp_maxvol_select: out of host memory";
+      return MTP_ERR_LIMIT;
+    }
+    if (e != hipSuccess) {
+      c->last_error = std::string("mtp_maxvol_select: ") + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory ? MTP_ERR_LIMIT : MTP_ERR_DEVICE;
+    }
+  }
+  double gain = 0.0;
+  for (int k = 0; k < *nswaps; k++) gain += std::log(std::fabs(swap_pivots[k]));
+  if (log_volume_gain) *log_volume_gain = gain;
+  if (max_grade_after) *max_grade_after = mg;
+  if (bad) {
+    c->last_error = "mtp_maxvol_select: a candidate vector (or a grade computed from it) is not finite";
+    return MTP_ERR_ARG;
   }
   return MTP_OK;
 }

@@ -162,6 +162,20 @@ hipError_t mtp_launch_batch_colsum(const double *cvec, int cpad, int ncfg, const
                                    hipStream_t st);
 // cfg_grade[k] /= rows of configuration k (0 for none)
 hipError_t mtp_launch_batch_grade_scale(int ncfg, const int *cfg_first, double *cfg_grade, hipStream_t st);
+// MaxVol selection (mtp_maxvol.hip; include/mtp_mi355x.h, mtp_maxvol_select).  S, W: the potential's two raw blocks
+// [C][C] (host); d_rows [N][ld] the pool (device).  Host outputs as mtp_maxvol_select's; *nonfinite != 0 when the pivot
+// search met a non-finite grade (the outputs then describe the state before it).  `arena`: device memory of
+// mtp_maxvol_arena_doubles(...) doubles, the caller's ((C + N) x cpad of them hold the stacked matrix).  Waits on `st`
+// once per 16 swaps; may throw std::bad_alloc (host staging of the two blocks).
+const char *mtp_maxvol_build_flags();   // "" for the shipped defaults (mtp_build_flags)
+size_t mtp_maxvol_arena_doubles(int num_cus, int C, long long N, int max_swaps);
+hipError_t mtp_maxvol_run(hipStream_t st, int num_cus, double *arena, int C, const double *S, const double *W,
+                          const double *d_rows, long long N, int ld, double threshold, int max_swaps, int refresh, double *S_out,
+                          double *W_out,
+                          int *slot_source, int *swap_rows, int *swap_slots, double *swap_pivots, int *nswaps_out,
+                          int *converged, double *max_grade_after, int *nonfinite);
+// rows[k][0, cpad) /= rows of configuration k (a zero row for none): per-configuration candidate vectors
+hipError_t mtp_launch_maxvol_scale_rows(double *rows, int cpad, int ncfg, const int *cfg_first, hipStream_t st);
 // device neighbour-list build (mtp_neighbor_kernels.hip): stage 1 (neigh == nullptr) bins, counts and scans and
 // leaves {entries, longest row} in d_info[2]; stage 2 fills neigh[]
 hipError_t mtp_launch_neighbor_build(const double *x, int inum, int nall, double cutoff, const double lo[3],

@@ -285,6 +285,7 @@ void parse_text(FILE *fp, bool want_selection, mtp_potential &p)
   p.active_set.resize(n);
   p.inverse_active_set.resize(n);
   fgetc(fp);   // the '#' in front of the raw fp64 block (:607)
+  p.selection_offset = std::ftell(fp);
   if (fread(p.active_set.data(), sizeof(double), n, fp) != n ||
       fread(p.inverse_active_set.data(), sizeof(double), n, fp) != n)
     throw ParseError{MTP_ERR_IO, "Unexpected end of file while reading the active set"};

@@ -28,6 +28,7 @@ struct mtp_potential {
   bool has_selection = false, configuration_mode = false;
   int coeff_count = 0;
   std::vector<double> active_set, inverse_active_set;   // [C][C]
+  long selection_offset = 0;   // bytes of the file up to and including the '#' in front of the two raw blocks
 
   // --- native schedule (built by finalize) -------------------------------------------------
   // times rows stably sorted by dependency level; level_offset[l]..level_offset[l+1]

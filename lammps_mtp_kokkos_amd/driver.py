@@ -190,3 +190,32 @@ def periodic_system_cell(pos, cell, types=None, list_cutoff=7.0):
     return System(x=x, types=np.asarray(types, dtype=np.int32)[owner], nlocal=n, owner=owner,
                   box=np.diag(np.asarray(cell, dtype=np.float64).reshape(3, 3)).copy(), ilist=np.arange(n, dtype=np.int32),
                   first=first, neigh=neigh, cutoff=float(list_cutoff))
+
+
+def maxvol_select_numpy(V, S, W, threshold, max_swaps):
+    """numpy twin of the library's mtp_maxvol_select (include/mtp_mi355x.h, "MaxVol selection"): the columns of S are the
+    selected candidate vectors, W = S^-1, G = V W^T.  While some |G[i, j]| exceeds `threshold`, the largest one -- ties to
+    the smaller linear index i * C + j, which is what np.argmax over the flattened matrix returns -- is swapped in:
+    S[:, j] <- V[i] and, with p = G[i, j] and u = (G[i, :] - e_j) / p, every row r of W^T and of G becomes r - r[j] u.
+    At most max_swaps swaps.  Returns (S', W', swaps = [(i, j, p)], G): G is the rank-1-updated matrix, not a fresh
+    V W'^T -- their difference is the drift the tests bound."""
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    S = np.array(S, dtype=np.float64)
+    Wt = np.array(W, dtype=np.float64).T.copy()
+    C = S.shape[0]
+    G = V[:, :C] @ Wt
+    swaps = []
+    while len(swaps) < max_swaps and G.size:
+        k = int(np.argmax(np.abs(G)))
+        i, j = divmod(k, C)
+        p = float(G[i, j])
+        if not abs(p) > threshold:
+            break
+        u = G[i].copy()
+        u[j] -= 1.0
+        u /= p
+        Wt -= np.outer(Wt[:, j], u)
+        G -= np.outer(G[:, j], u)
+        S[:, j] = V[i, :C]
+        swaps.append((i, j, p))
+    return S, Wt.T.copy(), swaps, G

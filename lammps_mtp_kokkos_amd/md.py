@@ -281,6 +281,13 @@ def evaluate_cells(ctx, configs, list_cutoff=7.0, vflag=1, grades=False, max_ato
     max_grade (neighbourhood mode) or cfg_grade (configuration mode: the grade of the configuration as a whole,
     pair_mtp_extrapolation.cpp:369-376).  An atom type outside the potential is reported at the final synchronise of
     its pass; the message names the pass."""
+    return _cell_passes(ctx, configs, list_cutoff, vflag, grades, max_atoms_per_pass, device, None)
+
+
+def _cell_passes(ctx, configs, list_cutoff, vflag, grades, max_atoms_per_pass, device, on_pass):
+    """the passes of evaluate_cells, shared with select_cells: `on_pass(k0, k1, cf, cf_t, n, stream)` (or None) is called
+    once per non-empty pass, after its device work is queued and before the copy back, while the context still holds that
+    pass's candidate vectors"""
     import torch
     dev = device or torch.device("cuda:0")
     if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
@@ -354,6 +361,8 @@ def evaluate_cells(ctx, configs, list_cutoff=7.0, vflag=1, grades=False, max_ato
                           energy_t=e_t, virial_t=v_t if vf else None, cfg_grade_t=g_t if grades and not cfg_mode else None, stream=st)
         if cfg_mode:
             ctx.batch_cfg_grades(cf_t, n, g_t, stream=st)
+        if on_pass is not None:
+            on_pass(k0, k1, cf, cf_t, n, st)
         pieces = [buf.xall[:n].reshape(-1), fall[:n].reshape(-1), res] + ([buf.grades[:n]] if grades and not cfg_mode else [])
         nout = sum(int(p.numel()) for p in pieces)
         out = buf.out_host[:nout]
@@ -385,3 +394,58 @@ def _empty_result(volume, grades, cfg_mode):
     elif grades:
         r.update(grades=np.zeros(0), max_grade=0.0)
     return r
+
+
+def select_cells(ctx, configs, threshold=1.1, out_path=None, list_cutoff=7.0, max_swaps=None, max_pool_bytes=2 ** 31,
+                 max_atoms_per_pass=None, device=None):
+    """The selection step of the active-learning loop over a batch of candidate configurations: the passes of
+    evaluate_cells(grades=True), every pass's candidate vectors copied into one pool on the device (one row per atom in
+    neighbourhood mode, one per configuration -- the sum over its atoms divided by their number -- in configuration mode),
+    ONE MaxVol selection over that pool starting from the potential's active set (Context.maxvol_select), and, with
+    `out_path`, the potential file with the new active set and its inverse (capi.write_selection; the context itself keeps
+    its old set: reload the written file to grade with the new one).  The pool is selected as a whole, because later swaps
+    change earlier grades: ValueError when it would exceed `max_pool_bytes` (the selection needs as much again for its
+    grade matrix).
+
+    Returns dict(selected: indices of the configurations that own a row now in the active set, ascending; nswaps,
+    converged, log_volume_gain = log |det S'| - log |det S|; grade_before [ncfg]: every configuration's grade against the
+    old set; max_grade_after: the largest grade of the pool against the new set; active_set, inverse_active_set [C, C];
+    slot_source [C]: per slot the configuration whose vector it now holds -- (configuration, atom) in neighbourhood mode --
+    or None where the original column was kept; swaps: the log [(pool row, slot, pivot)])."""
+    import torch
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__: the pool is filled on this stream
+        capi.use_private_torch_stream(dev)
+    info = ctx.pot.info
+    if not info.has_selection:
+        raise capi.MtpError(-23, "select_cells: the potential was loaded without its selection state")
+    cfg_mode = bool(info.configuration_mode)
+    C = int(info.coeff_count)
+    cpad = (C + 15) // 16 * 16
+    natoms = np.array([len(np.asarray(c[0], dtype=np.float64).reshape(-1, 3)) for c in configs], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(natoms)])
+    nrows = len(natoms) if cfg_mode else int(first[-1])
+    if nrows * cpad * 8 > max_pool_bytes:
+        raise ValueError("select_cells: a pool of %d candidate vectors needs %d bytes, max_pool_bytes is %d; a pool has to be "
+                         "selected as a whole" % (nrows, nrows * cpad * 8, max_pool_bytes))
+    pool = torch.zeros((nrows, cpad), dtype=torch.float64, device=dev)
+
+    def on_pass(k0, k1, cf, cf_t, n, st):
+        if cfg_mode:
+            pool[k0:k1] = ctx.batch_cfg_candidates(cf_t, n, stream=st)
+        else:
+            pool[int(first[k0]): int(first[k0]) + n] = ctx.candidates()[:n]
+
+    res = _cell_passes(ctx, configs, list_cutoff, 0, True, max_atoms_per_pass, dev, on_pass)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    sel = ctx.maxvol_select(pool, threshold, max_swaps=max_swaps, stream=st)
+    if out_path is not None:
+        capi.write_selection(ctx.pot.path, out_path, sel["active_set"], sel["inverse_active_set"])
+    owner = [None if r < 0 else (int(r) if cfg_mode else int(np.searchsorted(first, r, side="right") - 1))
+             for r in sel["slot_source"]]
+    source = [None if k is None else (k if cfg_mode else (k, int(r - first[k]))) for k, r in zip(owner, sel["slot_source"])]
+    return dict(selected=sorted({k for k in owner if k is not None}), nswaps=sel["nswaps"], converged=sel["converged"],
+                log_volume_gain=sel["log_volume_gain"],
+                grade_before=np.array([r["cfg_grade"] if cfg_mode else r["max_grade"] for r in res]),
+                max_grade_after=sel["max_grade_after"], active_set=sel["active_set"],
+                inverse_active_set=sel["inverse_active_set"], slot_source=source, swaps=sel["swaps"])
