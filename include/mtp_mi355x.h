@@ -12,10 +12,10 @@
  * Streams.  Device work is ordered on the `stream` (a hipStream_t) given to an entry point.  ONE rule for NULL:
  *   - entry points that take a context (mtp_compute_device[_rows], mtp_build_neighbors_device,
  *     mtp_set_neighbors_device_2d, mtp_synchronize, mtp_halo_force_step, mtp_ghosts_reverse_finish,
- *     mtp_batch_cfg_grades, mtp_batch_cfg_candidates, mtp_maxvol_select): NULL means the
+ *     mtp_batch_cfg_grades, mtp_batch_cfg_candidates, mtp_maxvol_select, mtp_design_rows_device): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
- *     mtp_batch_reduce): NULL is
+ *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
  * whose other GPU work runs on the default stream (PyTorch's default) must pass a real stream handle that its own
@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 5
+#define MTP_MI355X_ABI_VERSION 6
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -496,6 +496,77 @@ int mtp_maxvol_select(mtp_context *ctx, void *stream, const double *d_rows, long
                       double *inverse_active_set /*[C*C] host*/, int *slot_source /*[C]*/, int *swap_rows, int *swap_slots,
                       double *swap_pivots /*[max_swaps]*/, int *nswaps, int *converged, double *log_volume_gain,
                       double *max_grade_after);
+
+/* ---- linear refit: design rows of energy, force and virial ---------------------------------------------------------
+ *
+ * The model is linear in the species coefficients and in moment_coeffs xi: E = sum_i (species[t_i] + sum_a xi_a B_a(i)),
+ * and so are the forces and the virial PairMTP::compute returns (pair_mtp.cpp:204-276).  A refit of these Sp + S numbers
+ * with the radial coefficients fixed -- MLIP's linear regression, the "retrain" step of the active-learning loop -- needs
+ * the design matrix: per configuration one energy row, 3 N force rows and six virial rows over the columns
+ * [species (Sp) | moments (S)], the order of the last Sp + S entries of a candidate vector.  The rows are produced in
+ * forward mode: per centre atom i and direction d = (neighbour n, component c), dM_k = d m_k(n) / d u_{n,c} for the basics
+ * (the expressions of pair_mtp.cpp:163-191), dM[a3] += mult (dM[a0] M[a1] + M[a0] dM[a1]) through the times rows, and
+ * G_a(i, n, c) = dM[alpha_moment_mapping[a]].  Nothing here depends on xi or on the species coefficients.
+ */
+/* Design rows over rows [row_begin, row_begin + row_count) of the INSTALLED list (rows = positions in ilist, as for
+ * mtp_compute_device_rows).  All arrays are device arrays of the caller, leading dimension ld >= Sp + S, even.
+ *   d_basis  [row_count][ld] or NULL   row ii - row_begin: one-hot on the centre's type, then B_a(i); columns up to ld
+ *                                     zero.  Assigned, once per row: the site-energy design rows.
+ *   d_force  [3 nowned][ld]            ACCUMULATED (the caller zeroes it, mtp_zero_async): F[3 owner(n) + c][Sp + a] -= G
+ *                                     and F[3 i + c][Sp + a] += G, the sign for which F . theta is the force the force
+ *                                     calls return after the ghost fold; the species columns are never touched (they
+ *                                     are zero).  The own-row term is summed over the centre's directions on chip first;
+ *                                     a neighbour that is an image of the centre itself contributes to neither (the two
+ *                                     terms cancel exactly).  fp64 atomic adds: sums depend on arrival order in the
+ *                                     last bits.
+ *   d_owner  [nall] or NULL            owner(j): the owned row a list entry j is an image of (mtp_ghosts_owner_device);
+ *                                     NULL = identity.  No array with ghost rows is ever written.
+ *   d_virial_atom [row_count][6][ld] or NULL   assigned: the rows for which V . theta is the per-atom virial vatom[i]
+ *                                     (xx, yy, zz, xy, xz, yz; sign and symmetrisation of pair_mtp.cpp:257-276); their
+ *                                     sum over a configuration is its virial row block (mtp_batch_design_reduce).
+ * A scalar whose moment a LATER scalar is mapped to as well has zero force and virial columns: the reference seeds the
+ * adjoint by assignment (pair_mtp.cpp:217-218).  One workgroup of four wavefronts per centre atom; the kernel's table is
+ * built and uploaded by the first call on a context.  MTP_ERR_STATE before a list is installed; MTP_ERR_ARG for ld < Sp + S,
+ * an odd ld, a row range outside the list, nowned < 0 or a NULL d_force with row_count > 0; MTP_ERR_LIMIT when the
+ * workgroup's LDS image does not fit (mtp_last_error names the quantity).  Reported by the next mtp_synchronize: an atom
+ * type outside the potential (MTP_ERR_SPECIES), a row with more in-cutoff neighbours than the list's max_numneigh
+ * (MTP_ERR_LIMIT), a centre or an owner outside [0, nowned) or a list entry outside [0, nall) (MTP_ERR_ARG; such terms
+ * are skipped, never written).  A centre that is refused this way is skipped as a whole: its d_basis and d_virial_atom
+ * rows are NOT assigned and keep what the caller's buffers held, and after any of these errors no output of the call may
+ * be used. */
+int mtp_design_rows_device(mtp_context *ctx, void *stream, const double *d_x, const int *d_type, int row_begin,
+                           int row_count, const int *d_owner, int ld, double *d_basis, double *d_force, int nowned,
+                           double *d_virial_atom);
+/* The owner map of the last build on a ghost handle, for all rows: identity on the owned rows, the owner behind them
+ * (*nall entries).  The handle keeps the owners of its ghosts only; the full map is completed by one small launch on
+ * `stream` into storage of the handle and is valid until the next build. */
+int mtp_ghosts_owner_device(mtp_ghosts *g, void *stream, const int **d_owner, int *nall);
+/* Per-configuration design rows from the per-atom ones: d_energy[k][0, ld) = sum of d_basis over rows [cfg_first[k],
+ * cfg_first[k + 1]), d_virial[k][6][ld] the same of d_virial_atom (either pair may be NULL).  One workgroup per
+ * configuration and row kind, columns over the lanes, rows added in order without atomics: a configuration's rows do not
+ * depend on the rest of the batch; an empty one gets zeros.  d_cfg_first [ncfg + 1] is a device array. */
+int mtp_batch_design_reduce(void *stream, int ncfg, const int *d_cfg_first, int ld, const double *d_basis,
+                            const double *d_virial_atom, double *d_energy, double *d_virial);
+/* The tangent kernel's table as the host builds it from the native schedule (host only, for inspection): counts[4] =
+ * {rows (padded), level blocks, A, B}; rows [counts[0]][4] = {a0, a1, mult, a3} in dependency-level order, the leaf
+ * block last, over an image with a slot for every moment; level_offset [counts[1] + 1]; scalar_map / force_map [S]
+ * (force_map: -1 where a later scalar is mapped to the same moment); basic_pack [B] = slot | a << 8 | b << 12 | c << 16 |
+ * mu << 20.  Any pointer may be NULL. */
+int mtp_potential_design_table(const mtp_potential *pot, int32_t *counts, int32_t *rows, int32_t *level_offset,
+                               int32_t *scalar_map, int32_t *force_map, int32_t *basic_pack);
+/* Writes src_path with new linear coefficients to dst_path (host only; temporary file beside dst_path, then rename): the
+ * species_coeffs line (kept when species_coeffs == NULL) and the moment_coeffs line are replaced, numbers with 17
+ * significant digits; every other byte in front of the selection tail is kept.  The radial block of a candidate vector
+ * depends on moment_coeffs, so an #MVS tail of the source no longer describes the new potential: the written file ENDS
+ * BEFORE THE TAIL and the call returns MTP_WROTE_WITHOUT_SELECTION (> 0) instead of MTP_OK.  The written file is read
+ * back before the rename: the reference sizes its reader's line buffer from the table (T * 32 + 20 characters), and where
+ * a coefficient line does not come back bit for bit the call fails with MTP_ERR_LIMIT and writes nothing.  MTP_ERR_ARG
+ * for counts that are not the file's (species_count is not looked at when species_coeffs == NULL) and for non-finite
+ * coefficients, otherwise the parser's codes. */
+#define MTP_WROTE_WITHOUT_SELECTION 1
+int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const double *species_coeffs /*[Sp] or NULL*/,
+                               const double *moment_coeffs /*[S]*/, int species_count, int scalar_count, char *err,
+                               int errlen);
 
 #ifdef __cplusplus
 }

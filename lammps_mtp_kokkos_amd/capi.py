@@ -39,7 +39,10 @@ EXPORTS = [
     "mtp_batch_layout", "mtp_ghosts_build_batch", "mtp_batch_reduce", "mtp_batch_cfg_grades",
     "mtp_potential_get_active_set", "mtp_potential_write_selection", "mtp_context_candidates_device",
     "mtp_batch_cfg_candidates", "mtp_maxvol_select",
+    "mtp_design_rows_device", "mtp_ghosts_owner_device", "mtp_batch_design_reduce", "mtp_potential_design_table",
+    "mtp_potential_write_coeffs",
 ]
+WROTE_WITHOUT_SELECTION = 1   # mtp_potential_write_coeffs: the source's #MVS tail was left out
 # mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
 # workgroup of BATCH_BLOCK threads; the grade kernel behind mtp_batch_cfg_grades takes GRADE_ROWS_PER_BLOCK rows a workgroup
 BATCH_WAVE_LANES, BATCH_WAVE_ROWS, BATCH_BLOCK, GRADE_ROWS_PER_BLOCK = 64, 256, 256, 128
@@ -170,6 +173,8 @@ class Potential:
                     P=i.max_alpha_index_basic, C=i.coeff_count, levels=i.product_levels)
 
     def tables(self):
+        """copies of the parsed tables (mtp_potential_get_tables) and, since the linear refit, three scalars of get_info
+        beside them -- scaling, min_cutoff, max_cutoff -- so that the dict is all driver.design_twin needs"""
         i = self.info
         out = dict(
             alpha_index_basic=np.zeros((i.alpha_index_basic_count, 4), np.int32),
@@ -186,6 +191,7 @@ class Potential:
             raise MtpError(rc, "get_tables")
         if inv is not None:
             out["inverse_active_set"] = inv
+        out.update(scaling=float(i.scaling), min_cutoff=float(i.min_cutoff), max_cutoff=float(i.max_cutoff))
         return out
 
     def active_set(self):
@@ -197,6 +203,25 @@ class Potential:
         if rc:
             raise MtpError(rc, "get_active_set: the potential carries no selection state")
         return S
+
+    def design_table(self):
+        """the tangent (design-row) kernel's own table as the host builds it (mtp_potential_design_table): dict(rows
+        [n, 4] = {a0, a1, mult, a3} in dependency-level order over an image with a slot for every moment, level_offset,
+        scalar_map, force_map [S], basic_pack [B], A, B)"""
+        cnt = np.zeros(4, np.int32)
+        rc = lib().mtp_potential_design_table(self.h, _np(cnt, C.c_int32), None, None, None, None, None)
+        if rc:
+            raise MtpError(rc, "design_table")
+        S = self.info.alpha_scalar_count
+        out = dict(rows=np.zeros((int(cnt[0]), 4), np.int32), level_offset=np.zeros(int(cnt[1]) + 1, np.int32),
+                   scalar_map=np.zeros(S, np.int32), force_map=np.zeros(S, np.int32), basic_pack=np.zeros(int(cnt[3]), np.int32))
+        rc = lib().mtp_potential_design_table(self.h, None, _np(out["rows"], C.c_int32), _np(out["level_offset"], C.c_int32),
+                                              _np(out["scalar_map"], C.c_int32), _np(out["force_map"], C.c_int32),
+                                              _np(out["basic_pack"], C.c_int32))
+        if rc:
+            raise MtpError(rc, "design_table")
+        out.update(A=int(cnt[2]), B=int(cnt[3]))
+        return out
 
     def kernel_shape(self):
         """the force kernel instantiation a context of this potential launches (mtp_potential_kernel_shape)"""
@@ -356,6 +381,15 @@ class Context:
                                                   _ptr(x_t), _ptr(type_t), int(eflag), int(vflag), int(bool(grade)),
                                                   _ptr(f_t), _ptr(eatom_t), _ptr(vatom_t), _ptr(ev_t),
                                                   _ptr(grades_t), _ptr(maxg_t), _ptr(coeff_t)))
+
+    def design_rows(self, row_begin, row_count, x_t, type_t, force_t, nowned, ld, basis_t=None, virial_t=None, owner=None,
+                    stream=None):
+        """Design rows of rows [row_begin, row_begin + row_count) of the installed list (mtp_design_rows_device): force_t
+        [3 nowned, ld] is accumulated into (zero it first), basis_t [row_count, ld] and virial_t [row_count, 6, ld] are
+        assigned; `owner` is the device pointer of the owner map (Ghosts.owner) or None for the identity."""
+        self._check(lib().mtp_design_rows_device(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t), _ptr(type_t),
+                                                 int(row_begin), int(row_count), C.c_void_p(owner) if owner else None, int(ld),
+                                                 _ptr(basis_t), _ptr(force_t), int(nowned), _ptr(virial_t)))
 
     def synchronize(self, stream=None):
         self._check(lib().mtp_synchronize(self.h, C.c_void_p(stream) if stream else None))
@@ -673,6 +707,13 @@ class Ghosts:
     def types(self, type_t, stream=None):
         self._check(lib().mtp_ghosts_types(self.h, C.c_void_p(stream) if stream else None, _ptr(type_t)))
 
+    def owner(self, stream=None):
+        """(device pointer, nall) of the owner map of the last build over ALL rows -- identity on the owned rows -- in
+        storage of the handle, valid until the next build (mtp_ghosts_owner_device)"""
+        d, n = C.c_void_p(), C.c_int(0)
+        self._check(lib().mtp_ghosts_owner_device(self.h, C.c_void_p(stream) if stream else None, C.byref(d), C.byref(n)))
+        return d.value, n.value
+
 
 def ghosts_cell_bounds(cell, rghost):
     """Host arithmetic (no device): dict(lo, hi, volume, nimage) -- the bounds of every position Ghosts.build_cell can
@@ -711,6 +752,30 @@ def batch_reduce(cfg_first_t, eatom_t=None, vatom_t=None, grades_t=None, energy_
                                 _ptr(eatom_t), _ptr(vatom_t), _ptr(grades_t), _ptr(energy_t), _ptr(virial_t), _ptr(cfg_grade_t))
     if rc:
         raise MtpError(rc, "mtp_batch_reduce: needs a stream, and an input for every output")
+
+
+def batch_design_reduce(cfg_first_t, ld, basis_t=None, virial_atom_t=None, energy_t=None, virial_t=None, stream=None):
+    """per-configuration design rows: sums of the per-atom basis rows [rows, ld] into energy_t [ncfg, ld] and of the
+    per-atom virial rows [rows, 6, ld] into virial_t [ncfg, 6, ld] over rows [cfg_first[k], cfg_first[k + 1]), all device
+    tensors (mtp_batch_design_reduce)"""
+    rc = lib().mtp_batch_design_reduce(C.c_void_p(stream) if stream else None, int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t),
+                                       int(ld), _ptr(basis_t), _ptr(virial_atom_t), _ptr(energy_t), _ptr(virial_t))
+    if rc:
+        raise MtpError(rc, "mtp_batch_design_reduce: needs a stream, and an input for every output")
+
+
+def write_coeffs(src, dst, moment_coeffs, species_coeffs=None):
+    """`src` with its moment_coeffs (and, unless None, species_coeffs) replaced, 17 significant digits, written to `dst`
+    through a temporary file: mtp_potential_write_coeffs (host only).  Returns 0, or WROTE_WITHOUT_SELECTION when `src`
+    carries an #MVS selection tail: the tail describes the old coefficients and is left out of `dst`."""
+    m = np.ascontiguousarray(moment_coeffs, dtype=np.float64).reshape(-1)
+    sp = None if species_coeffs is None else np.ascontiguousarray(species_coeffs, dtype=np.float64).reshape(-1)
+    err = C.create_string_buffer(512)
+    rc = lib().mtp_potential_write_coeffs(os.fsencode(src), os.fsencode(dst), _np(sp, C.c_double), _np(m, C.c_double),
+                                          -1 if sp is None else len(sp), len(m), err, 512)
+    if rc < 0:
+        raise MtpError(rc, err.value.decode())
+    return rc
 
 
 def nve_initial(nlocal, x_t, v_t, f_t, type_t, inv_mass_t, dtf, dt, stream=None):

@@ -126,6 +126,13 @@ struct mtp_context {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
 
+  // design rows (mtp_design_rows_device): the tangent kernel's own table, built and uploaded by the first design call
+  bool design_ready = false;
+  DevBuf<MtpRow8> d_design_rows;
+  DevBuf<int32_t> d_design_ints;     // level offsets | basic descriptors | scalar map | force map
+  DevBuf<double> d_design_radial;
+  MtpDesignParams design{};
+
   MtpDevParams base{};
   const char *last_shape = "";   // name of the fixed-shape kernel the last force launch ran ("": a generic kernel)
 
@@ -1410,6 +1417,138 @@ int mtp_batch_cfg_grades(mtp_context *c, void *stream, int ncfg, const int *d_cf
   return MTP_OK;
 }
 
+// ---- design rows of the linear refit (include/mtp_mi355x.h) ----------------------------------------------------------
+static int design_prepare(mtp_context *c, hipStream_t st)
+{
+  if (c->design_ready) return MTP_OK;
+  const mtp_potential &pot = *c->pot;
+  mtp_design_table t;
+  mtp_build_design_table(pot, t);
+  if (t.A > 8191) {
+    c->last_error = "design rows: alpha_moments_count above 8191 is not supported by the packed times rows";
+    return MTP_ERR_LIMIT;
+  }
+  std::vector<MtpRow8> rows8(t.rows.size());
+  for (size_t k = 0; k < rows8.size(); k++) {
+    const MtpRow &r = t.rows[k];
+    if (r.mult > 32767 || r.mult < -32768) {
+      c->last_error = "design rows: a multiplicity of alpha_index_times does not fit 16 bits";
+      return MTP_ERR_LIMIT;
+    }
+    rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
+    rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
+  }
+  std::vector<int32_t> ints(t.level_offset);
+  ints.insert(ints.end(), t.basic_pack.begin(), t.basic_pack.end());
+  ints.insert(ints.end(), t.scalar_map.begin(), t.scalar_map.end());
+  ints.insert(ints.end(), t.force_map.begin(), t.force_map.end());
+  c->d_design_rows.upload(rows8, st);
+  c->d_design_ints.upload(ints, st);
+  c->d_design_radial.upload(pot.radial_basis_coeffs, st);
+  HIP_CHECK(hipStreamSynchronize(st));   // (the staging vectors go out of scope)
+  MtpDesignParams &d = c->design;
+  d = MtpDesignParams{};
+  d.Sp = pot.species_count;
+  d.R = pot.radial_basis_size;
+  d.Mu = pot.radial_func_count;
+  d.P = pot.max_alpha_index_basic;
+  d.A = t.A;
+  d.B = t.B;
+  d.S = t.S;
+  d.nblocks = t.nblocks;
+  d.rmin = pot.min_cutoff;
+  d.rmax = pot.max_cutoff;
+  d.scaling = pot.scaling;
+  d.cutsq = pot.max_cutoff * pot.max_cutoff;
+  d.inv_span = 1.0 / (pot.max_cutoff - pot.min_cutoff);
+  d.rows = c->d_design_rows.ptr;
+  d.level = c->d_design_ints.ptr;
+  d.pack = d.level + t.level_offset.size();
+  d.map = d.pack + t.B;
+  d.fmap = d.map + t.S;
+  d.radial = c->d_design_radial.ptr;
+  d.err_flag = c->d_err.ptr;
+  c->design_ready = true;
+  return MTP_OK;
+}
+
+int mtp_design_rows_device(mtp_context *c, void *stream, const double *d_x, const int *d_type, int row_begin, int row_count,
+                           const int *d_owner, int ld, double *d_basis, double *d_force, int nowned, double *d_virial_atom)
+{
+  if (!c) return MTP_ERR_ARG;
+  if (!c->have_list) {
+    c->last_error = "mtp_design_rows_device before a neighbour list is installed";
+    return MTP_ERR_STATE;
+  }
+  const int cols = c->pot->species_count + c->pot->alpha_scalar_count;
+  if (ld < cols || (ld & 1)) {
+    c->last_error = "mtp_design_rows_device: ld = " + std::to_string(ld) + " must be even and at least Sp + S = " + std::to_string(cols);
+    return MTP_ERR_ARG;
+  }
+  if (row_begin < 0 || row_count < 0 || row_begin + row_count > c->inum || nowned < 0) {
+    c->last_error = "mtp_design_rows_device: row range outside the neighbour list, or nowned < 0";
+    return MTP_ERR_ARG;
+  }
+  if (row_count > 0 && (!d_x || !d_type || !d_force)) {
+    c->last_error = "mtp_design_rows_device: positions, types and the force rows are required";
+    return MTP_ERR_ARG;
+  }
+  if (row_count == 0) return MTP_OK;
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  try {
+    const int rc = design_prepare(c, st);
+    if (rc != MTP_OK) return rc;
+    MtpDesignParams p = c->design;
+    p.row0 = row_begin;
+    p.nrows = row_count;
+    p.nowned = nowned;
+    p.nall = c->nall;
+    p.ld = ld;
+    p.cj_cap = std::max(c->max_numneigh, 1);
+    p.ilist = c->ilist;
+    p.first = c->first;
+    p.neigh = c->neigh;
+    p.type = d_type;
+    p.owner = d_owner;
+    p.x = d_x;
+    p.basis = d_basis;
+    p.force = d_force;
+    p.virial = d_virial_atom;
+    const size_t lds = mtp_design_lds_layout(p);
+    if (lds > 160 * 1024) {
+      const size_t fixed = lds - (size_t) p.cj_cap * sizeof(int);
+      c->last_error = "mtp_design_rows_device: the workgroup's LDS image needs " + std::to_string(lds) + " of 163840 bytes: " +
+          (fixed > 160 * 1024 ? std::to_string(MTP_DESIGN_WAVES + 1) + " moment images of alpha_moments_count = " + std::to_string(p.A) +
+                   " doubles and nine rows of alpha_scalar_moments = " + std::to_string(p.S) + " are too large"
+                              : "the list's longest row, max_numneigh = " + std::to_string(c->max_numneigh) + ", is too large");
+      return MTP_ERR_LIMIT;
+    }
+    const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+    const int grid = std::max(1, std::min(row_count, c->num_cus * per_cu));
+    HIP_CHECK(mtp_launch_design_kernel(p, grid, lds, st));
+  } catch (const HipFail &f) {
+    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
+    return MTP_ERR_DEVICE;
+  }
+  return MTP_OK;
+}
+
+int mtp_batch_design_reduce(void *stream, int ncfg, const int *d_cfg_first, int ld, const double *d_basis,
+                            const double *d_virial_atom, double *d_energy, double *d_virial)
+{
+  if (ncfg < 0 || ld < 1 || (ncfg > 0 && !d_cfg_first) || (d_energy && !d_basis) || (d_virial && !d_virial_atom)) return MTP_ERR_ARG;
+  if (!stream) return MTP_ERR_ARG;   // no context here: NULL is not mapped to anything (include/mtp_mi355x.h, "Streams")
+  if (ncfg == 0 || (!d_energy && !d_virial)) return MTP_OK;
+  return mtp_launch_batch_design_reduce(ncfg, d_cfg_first, ld, d_basis, d_virial_atom, d_energy, d_virial,
+                                        reinterpret_cast<hipStream_t>(stream)) == hipSuccess
+      ? MTP_OK
+      : MTP_ERR_DEVICE;
+}
+
 // ---- MaxVol selection (include/mtp_mi355x.h) -------------------------------------------------------------------------
 int mtp_context_candidates_device(const mtp_context *c, const double **d_rows, int *nrows, int *ld)
 {
@@ -1537,6 +1676,10 @@ int mtp_synchronize(mtp_context *c, void *stream)
     if (flag == 2) {
       c->last_error = "a neighbour list row holds more in-cutoff neighbours than the declared max_numneigh";
       return MTP_ERR_LIMIT;
+    }
+    if (flag == 3) {
+      c->last_error = "design rows: a centre or an owner outside [0, nowned), or a list entry outside [0, nall)";
+      return MTP_ERR_ARG;
     }
     c->last_error = "Too few species count in the MTP potential!";   // pair_mtp.cpp:92-93
     return MTP_ERR_SPECIES;

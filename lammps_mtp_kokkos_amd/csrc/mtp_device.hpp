@@ -187,3 +187,31 @@ size_t mtp_neighbor_scan_bytes(int n, int nall);
 hipError_t mtp_launch_list_from_2d(int inum, const int *d_ilist, const int *d_numneigh, const int *d_neighbors,
                                    long long stride_i, long long stride_jj, int cap, int *counts, void *cub_tmp,
                                    size_t cub_bytes, int *first, int *neigh, int *d_info, hipStream_t st);
+
+// ---- design rows (mtp_design.hip; include/mtp_mi355x.h, "linear refit") ------------------------------------------------
+#define MTP_DESIGN_WAVES 4    // wavefronts per workgroup = per centre atom
+#define MTP_DESIGN_NT 32      // neighbours per LDS tile (table row pitch MTP_PITCH doubles)
+struct MtpDesignParams {
+  int Sp, R, Mu, P, A, B, S, nblocks;   // nblocks: level blocks of the row table, the leaf block included
+  double rmin, rmax, scaling, cutsq, inv_span;
+  // the kernel's own table (mtp_design_table, HBM / L2; the small integer tables are copied into LDS once per workgroup)
+  const MtpRow8 *rows;   // byte offsets into a moment image with a slot for every moment
+  const int *level;      // [nblocks + 1] padded row offsets
+  const int *pack;       // [B] slot | a << 8 | b << 12 | c << 16 | mu << 20
+  const int *map, *fmap; // [S] moment of every scalar; the same or -1 (no force column)
+  const double *radial;  // [Sp][Sp][Mu][R]
+  // system
+  int row0, nrows, nowned, nall, ld, cj_cap;
+  const int *ilist, *first, *neigh, *type, *owner;
+  const double *x;
+  double *basis, *force, *virial;
+  int *err_flag;
+  // workgroup LDS image, offsets in doubles: M[a_pad] | dM[MTP_DESIGN_WAVES][a_pad] | acc[9][S] | tab[tab_rows][MTP_PITCH] |
+  // nbx, nby, nbz, 1/r [MTP_DESIGN_NT each] | ints
+  int a_pad, off_dm, off_acc, off_tab, off_nb, off_int, tab_rows;
+};
+// bytes of that image for a list whose rows hold at most cj_cap entries; fills the offsets of p (host only)
+size_t mtp_design_lds_layout(MtpDesignParams &p);
+hipError_t mtp_launch_design_kernel(const MtpDesignParams &p, int grid, size_t lds, hipStream_t st);
+hipError_t mtp_launch_batch_design_reduce(int ncfg, const int *cfg_first, int ld, const double *basis, const double *virial_atom,
+                                          double *energy, double *virial, hipStream_t st);

@@ -289,6 +289,14 @@ __global__ void __launch_bounds__(256) ghosts_reverse_kernel(double *__restrict_
   unsafeAtomicAdd(&f[3 * (size_t) owner[k] + c], f[3 * (size_t) nlocal + e]);
 }
 
+// owner_all[r] = r for the owned rows, owner[r - nlocal] behind them
+__global__ void __launch_bounds__(256) ghosts_owner_all_kernel(int *__restrict__ owner_all, int nlocal, const int *__restrict__ owner,
+                                                               int nall)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < nall) owner_all[r] = r < nlocal ? r : owner[r - nlocal];
+}
+
 __global__ void __launch_bounds__(256) ghosts_types_kernel(int *__restrict__ type, int nlocal, const int *__restrict__ owner,
                                                           int nghost)
 {
@@ -350,6 +358,8 @@ struct mtp_ghosts {
   int device = 0, nlocal = 0, nghost = 0;
   int cap_local = 0, cap_ghost = 0;
   int *d_count = nullptr, *d_first = nullptr, *d_owner = nullptr;
+  int *d_owner_all = nullptr;                // mtp_ghosts_owner_device only: [cap_owner_all] identity | d_owner
+  int cap_owner_all = 0;
   double *d_shift = nullptr;
   ShiftRange *d_range = nullptr;             // mtp_ghosts_build_cell only: [cap_range] + one 64-bit total behind them
   int cap_range = 0;
@@ -364,7 +374,7 @@ struct mtp_ghosts {
   {
     (void) hipSetDevice(device);
     for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, (void *) d_range, (void *) d_slot,
-                    (void *) d_cfg_first, d_tmp})
+                    (void *) d_cfg_first, (void *) d_owner_all, d_tmp})
       if (p) (void) hipFree(p);
   }
 };
@@ -844,6 +854,29 @@ int mtp_ghosts_types(mtp_ghosts *g, void *stream, int *d_type)
     hipLaunchKernelGGL(ghosts_types_kernel, dim3((g->nghost + 255) / 256), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), d_type, g->nlocal, g->d_owner, g->nghost);
   MD_HIP(hipGetLastError());
+  return MTP_OK;
+}
+
+int mtp_ghosts_owner_device(mtp_ghosts *g, void *stream, const int **d_owner, int *nall)
+{
+  if (!g || !d_owner || !nall) return MTP_ERR_ARG;
+  if (!stream) return ghosts_null_stream(g, "mtp_ghosts_owner_device");
+  const int n = g->nlocal + g->nghost;
+  MD_HIP(hipSetDevice(g->device));
+  if (n > g->cap_owner_all || !g->d_owner_all) {
+    if (g->d_owner_all) (void) hipFree(g->d_owner_all);
+    g->d_owner_all = nullptr;
+    g->cap_owner_all = 0;
+    const size_t cap = (size_t) n + n / 8 + 64;
+    MD_HIP(hipMalloc((void **) &g->d_owner_all, cap * sizeof(int)));
+    g->cap_owner_all = (int) std::min(cap, (size_t) 0x7fffffff);
+  }
+  if (n > 0)
+    hipLaunchKernelGGL(ghosts_owner_all_kernel, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       g->d_owner_all, g->nlocal, g->d_owner, n);
+  MD_HIP(hipGetLastError());
+  *d_owner = g->d_owner_all;
+  *nall = n;
   return MTP_OK;
 }
 

@@ -11,10 +11,13 @@
 #include <algorithm>
 #include <cassert>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+
+#include <unistd.h>
 
 namespace {
 
@@ -296,6 +299,12 @@ void parse_text(FILE *fp, bool want_selection, mtp_potential &p)
 
 int mtp_parse_file(const char *path, bool want_selection, mtp_potential &pot, std::string &err)
 {
+  const int rc = mtp_parse_text_file(path, want_selection, pot, err);
+  return rc == MTP_OK ? pot.finalize(err) : rc;
+}
+
+int mtp_parse_text_file(const char *path, bool want_selection, mtp_potential &pot, std::string &err)
+{
   FILE *fp = std::fopen(path, "rb");
   if (!fp) {
     err = std::string("Cannot open potential file ") + path + ": " + std::strerror(errno);
@@ -312,7 +321,6 @@ int mtp_parse_file(const char *path, bool want_selection, mtp_potential &pot, st
     rc = MTP_ERR_PARSE;
   }
   std::fclose(fp);
-  if (rc == MTP_OK) rc = pot.finalize(err);
   return rc;
 }
 
@@ -1283,3 +1291,217 @@ int mtp_potential::finalize(std::string &err)
   build_program(*this, true, refine, prog_bwd, seg_bwd);
   return MTP_OK;
 }
+
+// ---- the tangent kernel's table and the coefficient writer (host only; include/mtp_mi355x.h, "linear refit") ---------
+void mtp_build_design_table(const mtp_potential &pot, mtp_design_table &out)
+{
+  out.A = pot.alpha_moment_count;
+  out.B = pot.alpha_index_basic_count;
+  out.S = pot.alpha_scalar_count;
+  out.nblocks = (int) pot.level_offset.size() - 1;   // the dependency levels and the leaf block behind them
+  out.rows = pot.rows_by_level;
+  out.level_offset = pot.level_offset;
+  out.scalar_map = pot.mapping_lds;
+  out.basic_pack = pot.basic_pack_lds;
+  out.force_map.assign((size_t) out.S, -1);
+  std::vector<int> last((size_t) std::max(out.A, 1), -1);
+  for (int s = 0; s < out.S; s++) last[(size_t) pot.mapping_lds[(size_t) s]] = s;
+  for (int s = 0; s < out.S; s++)
+    if (last[(size_t) pot.mapping_lds[(size_t) s]] == s) out.force_map[(size_t) s] = pot.mapping_lds[(size_t) s];
+}
+
+namespace {
+
+void copy_message(const std::string &s, char *err, int errlen)
+{
+  if (err && errlen > 0) std::snprintf(err, (size_t) errlen, "%s", s.c_str());
+}
+
+// first word of a line under the parser's separators, comments stripped as the reader strips them
+std::string first_word(const std::string &line, bool strip_comment)
+{
+  std::string s = line;
+  if (strip_comment) {
+    const size_t p = s.find('#');
+    if (p != std::string::npos) s.erase(p);
+  }
+  const char *seps = " \t\r\n\f=,{}";
+  const size_t b = s.find_first_not_of(seps);
+  if (b == std::string::npos) return "";
+  const size_t e = s.find_first_of(seps, b);
+  return s.substr(b, (e == std::string::npos ? s.size() : e) - b);
+}
+
+std::string coeff_line(const char *key, const double *v, int n, const std::string &eol)
+{
+  std::string s = std::string(key) + " = {";
+  char num[40];
+  for (int i = 0; i < n; i++) {
+    std::snprintf(num, sizeof num, "%.16e", v[i]);   // 17 significant digits: strtod returns the same bits
+    if (i) s += ", ";
+    s += num;
+  }
+  return s + "}" + eol;
+}
+
+}   // namespace
+
+extern "C" {
+
+int mtp_potential_design_table(const mtp_potential *pot, int32_t *counts, int32_t *rows, int32_t *level_offset,
+                               int32_t *scalar_map, int32_t *force_map, int32_t *basic_pack)
+{
+  if (!pot) return MTP_ERR_ARG;
+  mtp_design_table t;
+  mtp_build_design_table(*pot, t);
+  if (counts) {
+    counts[0] = (int32_t) t.rows.size();
+    counts[1] = t.nblocks;
+    counts[2] = t.A;
+    counts[3] = t.B;
+  }
+  if (rows)
+    for (size_t k = 0; k < t.rows.size(); k++) {
+      rows[4 * k] = t.rows[k].a0;
+      rows[4 * k + 1] = t.rows[k].a1;
+      rows[4 * k + 2] = t.rows[k].mult;
+      rows[4 * k + 3] = t.rows[k].a3;
+    }
+  if (level_offset) std::copy(t.level_offset.begin(), t.level_offset.end(), level_offset);
+  if (scalar_map) std::copy(t.scalar_map.begin(), t.scalar_map.end(), scalar_map);
+  if (force_map) std::copy(t.force_map.begin(), t.force_map.end(), force_map);
+  if (basic_pack) std::copy(t.basic_pack.begin(), t.basic_pack.end(), basic_pack);
+  return MTP_OK;
+}
+
+int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const double *species_coeffs,
+                               const double *moment_coeffs, int species_count, int scalar_count, char *err, int errlen)
+{
+  if (!src_path || !dst_path || !moment_coeffs) {
+    copy_message("mtp_potential_write_coeffs: null argument", err, errlen);
+    return MTP_ERR_ARG;
+  }
+  mtp_potential src;
+  std::string msg;
+  int rc = mtp_parse_text_file(src_path, false, src, msg);   // (the tables as read: no schedule is needed here)
+  if (rc != MTP_OK) {
+    copy_message(msg, err, errlen);
+    return rc;
+  }
+  if ((species_coeffs && species_count != src.species_count) || scalar_count != src.alpha_scalar_count) {
+    copy_message("mtp_potential_write_coeffs: " + std::to_string(species_count) + " species and " +
+                     std::to_string(scalar_count) + " moment coefficients given, the file has " +
+                     std::to_string(src.species_count) + " and " + std::to_string(src.alpha_scalar_count),
+                 err, errlen);
+    return MTP_ERR_ARG;
+  }
+  bool finite = true;
+  for (int i = 0; i < scalar_count; i++) finite = finite && std::isfinite(moment_coeffs[i]);
+  for (int i = 0; species_coeffs && i < species_count; i++) finite = finite && std::isfinite(species_coeffs[i]);
+  if (!finite) {
+    copy_message("mtp_potential_write_coeffs: a coefficient is not finite", err, errlen);
+    return MTP_ERR_ARG;
+  }
+  std::string text;
+  {
+    FILE *in = std::fopen(src_path, "rb");
+    char chunk[65536];
+    size_t got = 0;
+    while (in && (got = std::fread(chunk, 1, sizeof chunk, in)) > 0) text.append(chunk, got);
+    const bool bad = !in || std::ferror(in);
+    if (in) std::fclose(in);
+    if (bad) {
+      copy_message(std::string("Cannot read potential file ") + src_path, err, errlen);
+      return MTP_ERR_IO;
+    }
+  }
+  // the last species_coeffs line, the moment_coeffs line behind it and, if there is one, the "#MVS_v1.1" line: the text
+  // in front of the tail is kept byte for byte except for the two coefficient lines; the tail is left out
+  size_t sp_b = std::string::npos, sp_e = 0, mo_b = std::string::npos, mo_e = 0, tail = std::string::npos;
+  for (size_t b = 0; b < text.size();) {
+    size_t e = text.find('\n', b);
+    e = e == std::string::npos ? text.size() : e + 1;
+    const std::string line = text.substr(b, e - b);
+    if (mo_b != std::string::npos && first_word(line, false) == "#MVS_v1.1") {
+      tail = b;
+      break;
+    }
+    const std::string w = first_word(line, true);
+    if (w == "species_coeffs") {
+      sp_b = b;
+      sp_e = e;
+      mo_b = std::string::npos;
+    } else if (w == "moment_coeffs" && sp_b != std::string::npos) {
+      mo_b = b;
+      mo_e = e;
+    }
+    b = e;
+  }
+  if (sp_b == std::string::npos || mo_b == std::string::npos || mo_b < sp_e) {
+    copy_message("mtp_potential_write_coeffs: species_coeffs / moment_coeffs lines not found", err, errlen);
+    return MTP_ERR_PARSE;
+  }
+  auto eol_of = [&](size_t b, size_t e) {
+    size_t k = e;
+    while (k > b && (text[k - 1] == '\n' || text[k - 1] == '\r')) k--;
+    return text.substr(k, e - k);
+  };
+  std::string out = text.substr(0, sp_b);
+  out += species_coeffs ? coeff_line("species_coeffs", species_coeffs, species_count, eol_of(sp_b, sp_e))
+                        : text.substr(sp_b, sp_e - sp_b);
+  out += text.substr(sp_e, mo_b - sp_e);
+  out += coeff_line("moment_coeffs", moment_coeffs, scalar_count, eol_of(mo_b, mo_e));
+  out += text.substr(mo_e, (tail == std::string::npos ? text.size() : tail) - mo_e);
+
+  const std::string tmp = std::string(dst_path) + ".tmp" + std::to_string((long) getpid());
+  FILE *fo = std::fopen(tmp.c_str(), "wb");
+  if (!fo) {
+    copy_message("Cannot open " + tmp + " for writing: " + std::strerror(errno), err, errlen);
+    return MTP_ERR_IO;
+  }
+  bool ok = std::fwrite(out.data(), 1, out.size(), fo) == out.size();
+  int why = ok ? 0 : errno;
+  if (std::fclose(fo) != 0 && ok) {
+    ok = false;
+    why = errno;
+  }
+  if (ok) {
+    // what a reader gets back: its line buffer is sized from the table (T * 32 + 20 characters), so a long coefficient line
+    // of a very small table comes back in pieces -- such a file is refused, not written
+    mtp_potential back;
+    rc = mtp_parse_text_file(tmp.c_str(), false, back, msg);
+    bool same = rc == MTP_OK && back.linear_coeffs.size() == (size_t) scalar_count &&
+        std::memcmp(back.linear_coeffs.data(), moment_coeffs, sizeof(double) * (size_t) scalar_count) == 0 &&
+        back.alpha_index_basic == src.alpha_index_basic && back.alpha_index_times == src.alpha_index_times &&
+        back.alpha_moment_mapping == src.alpha_moment_mapping && back.alpha_moment_count == src.alpha_moment_count &&
+        back.radial_basis_coeffs.size() == src.radial_basis_coeffs.size() &&
+        std::memcmp(back.radial_basis_coeffs.data(), src.radial_basis_coeffs.data(),
+                    sizeof(double) * src.radial_basis_coeffs.size()) == 0;
+    const std::vector<double> &want_sp = src.species_coeffs;
+    if (same)
+      same = back.species_coeffs.size() == want_sp.size() &&
+          std::memcmp(back.species_coeffs.data(), species_coeffs ? species_coeffs : want_sp.data(),
+                      sizeof(double) * want_sp.size()) == 0;
+    if (!same) {
+      std::remove(tmp.c_str());
+      copy_message("mtp_potential_write_coeffs: the written coefficients do not read back (the reader's line buffer of " +
+                       std::to_string((long) src.alpha_index_times_count * 32 + 20) +
+                       " characters, sized from alpha_index_times_count, is shorter than a coefficient line)" +
+                       (rc != MTP_OK ? ": " + msg : std::string()),
+                   err, errlen);
+      return MTP_ERR_LIMIT;
+    }
+  }
+  if (ok && std::rename(tmp.c_str(), dst_path) != 0) {
+    ok = false;
+    why = errno;
+  }
+  if (!ok) {
+    copy_message(std::string("Cannot write potential file ") + dst_path + ": " + std::strerror(why), err, errlen);
+    std::remove(tmp.c_str());
+    return MTP_ERR_IO;
+  }
+  return tail == std::string::npos ? MTP_OK : MTP_WROTE_WITHOUT_SELECTION;
+}
+
+}   // extern "C"

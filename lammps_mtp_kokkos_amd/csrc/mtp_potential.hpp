@@ -86,3 +86,18 @@ struct mtp_potential {
 };
 
 int mtp_parse_file(const char *path, bool want_selection, mtp_potential &pot, std::string &err);
+// the "as read" part only: no input checks beyond the grammar, no native schedule (the coefficient writer's two reads)
+int mtp_parse_text_file(const char *path, bool want_selection, mtp_potential &pot, std::string &err);
+
+// The tangent (design-row) kernel's own table, csrc/mtp_design.hip: the times rows in dependency-level order over an image
+// in which EVERY moment has a slot (leaves included: the leaf block is the last level), in the LDS numbering of finalize.
+// Nothing in it depends on the linear or the species coefficients.  level_offset has nblocks + 1 entries (padded rows,
+// as pad_levels leaves them: multiplicity-0 rows on stored moments fill every level to whole 64-row blocks).
+// force_map[s] = scalar_map[s] where scalar s is the LAST one mapped to its moment, else -1: the reference seeds the
+// adjoint by assignment (pair_mtp.cpp:217-218), so an earlier scalar on the same moment counts in the energy only.
+struct mtp_design_table {
+  int A = 0, B = 0, S = 0, nblocks = 0;
+  std::vector<MtpRow> rows;
+  std::vector<int32_t> level_offset, scalar_map, force_map, basic_pack;
+};
+void mtp_build_design_table(const mtp_potential &pot, mtp_design_table &out);

@@ -219,3 +219,93 @@ def maxvol_select_numpy(V, S, W, threshold, max_swaps):
         S[:, j] = V[i, :C]
         swaps.append((i, j, p))
     return S, Wt.T.copy(), swaps, G
+
+
+def design_twin(tables, system):
+    """numpy twin of the design-row kernel (csrc/mtp_design.hip; include/mtp_mi355x.h, "linear refit"): forward mode from
+    the parsed tables (capi.Potential.tables()), direction by direction.  For every centre atom the basics and their
+    derivatives with respect to each in-cutoff neighbour vector (pair_mtp.cpp:163-191) are pushed through the times rows in
+    FILE order, dM[a3] += mult (dM[a0] M[a1] + M[a0] dM[a1]) with M the moments after ALL rows -- the transpose of the
+    reference's reverse sweep (:221-233), which multiplies by the final moments even where a row read a partial one;
+    G = dM[alpha_moment_mapping] goes to the owner row of the
+    neighbour with a minus sign and to the centre's row with a plus sign, and into the virial with the sign and
+    symmetrisation of pair_mtp.cpp:257-276.  A scalar whose moment a later scalar is mapped to as well gets zero force and
+    virial columns (the reference seeds the adjoint by assignment, :217-218).  `system`: driver.System (owner folding).
+    Returns dict(basis [nlocal, Sp + S], energy [Sp + S], force [3 nlocal, Sp + S], virial [6, Sp + S], virial_atom
+    [nlocal, 6, Sp + S]); columns [species | moments]."""
+    basic = np.asarray(tables["alpha_index_basic"], dtype=np.int64).reshape(-1, 4)
+    times = np.asarray(tables["alpha_index_times"], dtype=np.int64).reshape(-1, 4)
+    mapping = np.asarray(tables["alpha_moment_mapping"], dtype=np.int64)
+    Sp, S, B = len(tables["species_coeffs"]), len(mapping), len(basic)
+    Mu = int(basic[:, 0].max()) + 1
+    R = len(tables["radial_coeffs"]) // (Sp * Sp * Mu)
+    radial = np.asarray(tables["radial_coeffs"], dtype=np.float64).reshape(Sp, Sp, Mu, R)
+    A = int(max(B, times[:, [0, 1, 3]].max() + 1 if len(times) else 0, mapping.max() + 1 if S else 0))
+    scaling, rmin, rmax = float(tables["scaling"]), float(tables["min_cutoff"]), float(tables["max_cutoff"])
+    last = {int(m): s for s, m in enumerate(mapping)}
+    fcol = np.array([last[int(m)] == s for s, m in enumerate(mapping)], dtype=bool)
+    n = system.nlocal
+    ncol = Sp + S
+    basis = np.zeros((n, ncol))
+    force = np.zeros((3 * n, ncol))
+    vatom = np.zeros((n, 6, ncol))
+    mu_k, ea, eb, ec = basic[:, 0], basic[:, 1], basic[:, 2], basic[:, 3]
+    nu_k = ea + eb + ec
+    P = int(nu_k.max()) + 1
+    for ii, i in enumerate(system.ilist):
+        it = int(system.types[i]) - 1
+        js = system.neigh[system.first[ii]:system.first[ii + 1]] & 0x1FFFFFFF
+        u = system.x[js] - system.x[i]
+        r2 = u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1] + u[:, 2] * u[:, 2]
+        keep = ~(r2 > rmax * rmax)
+        js, u = js[keep], u[keep]
+        K = len(js)
+        basis[ii, it] = 1.0
+        M = np.zeros(A)
+        dM = np.zeros((A, K, 3))
+        if K:
+            r = np.sqrt(r2[keep])
+            inv = 1.0 / r
+            jt = system.types[js].astype(np.int64) - 1
+            d, ksi, mult = r - rmax, (2.0 * r - (rmin + rmax)) / (rmax - rmin), 2.0 / (rmax - rmin)
+            q = np.zeros((R, K))
+            e = np.zeros((R, K))
+            q[0], e[0] = scaling * (d * d), scaling * 2.0 * d
+            if R > 1:
+                q[1], e[1] = scaling * (ksi * d * d), scaling * (mult * d * d + 2.0 * ksi * d)
+            for ri in range(2, R):
+                q[ri] = 2.0 * ksi * q[ri - 1] - q[ri - 2]
+                e[ri] = 2.0 * (mult * q[ri - 1] + ksi * e[ri - 1]) - e[ri - 2]
+            c = radial[it, jt]                                   # [K, Mu, R]
+            val_mu = np.einsum("kmr,rk->mk", c, q)
+            der_mu = np.einsum("kmr,rk->mk", c, e)
+            rinv = inv[None, :] ** np.arange(P)[:, None]          # [P, K]
+            pw = u.T[:, None, :] ** np.arange(P)[None, :, None]   # [3, P, K]
+            val = val_mu[mu_k] * rinv[nu_k]                       # [B, K]
+            der = der_mu[mu_k] * rinv[nu_k] - nu_k[:, None] * val * inv
+            pa, pb, pc = pw[0][ea], pw[1][eb], pw[2][ec]
+            M[:B] = (val * (pa * pb * pc)).sum(1)
+            jac = ((pa * pb * pc) * der * inv)[:, :, None] * u[None, :, :]
+            jac[:, :, 0] += val * ea[:, None] * pw[0][np.maximum(ea - 1, 0)] * pb * pc
+            jac[:, :, 1] += val * eb[:, None] * pa * pw[1][np.maximum(eb - 1, 0)] * pc
+            jac[:, :, 2] += val * ec[:, None] * pa * pb * pw[2][np.maximum(ec - 1, 0)]
+            dM[:B] = jac
+        for a0, a1, mlt, a3 in times:
+            M[a3] += mlt * M[a0] * M[a1]
+        for a0, a1, mlt, a3 in times:                            # (with the FINAL moments, as the reference's reverse sweep)
+            dM[a3] += mlt * (dM[a0] * M[a1] + M[a0] * dM[a1])
+        basis[ii, Sp:] = M[mapping]
+        G = dM[mapping] * fcol[:, None, None]                     # [S, K, 3]
+        own = np.asarray(system.owner)[js]
+        io = int(np.asarray(system.owner)[i])
+        for c3 in range(3):
+            np.subtract.at(force[:, Sp:], 3 * own + c3, G[:, :, c3].T)
+            force[3 * io + c3, Sp:] += G[:, :, c3].sum(1)
+        if K:
+            vatom[ii, 0, Sp:] = -(G[:, :, 0] * u[:, 0]).sum(1)
+            vatom[ii, 1, Sp:] = -(G[:, :, 1] * u[:, 1]).sum(1)
+            vatom[ii, 2, Sp:] = -(G[:, :, 2] * u[:, 2]).sum(1)
+            vatom[ii, 3, Sp:] = -0.5 * (G[:, :, 0] * u[:, 1] + G[:, :, 1] * u[:, 0]).sum(1)
+            vatom[ii, 4, Sp:] = -0.5 * (G[:, :, 0] * u[:, 2] + G[:, :, 2] * u[:, 0]).sum(1)
+            vatom[ii, 5, Sp:] = -0.5 * (G[:, :, 1] * u[:, 2] + G[:, :, 2] * u[:, 1]).sum(1)
+    return dict(basis=basis, energy=basis.sum(0), force=force, virial=vatom.sum(0), virial_atom=vatom)

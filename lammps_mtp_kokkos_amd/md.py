@@ -296,25 +296,15 @@ def _cell_passes(ctx, configs, list_cutoff, vflag, grades, max_atoms_per_pass, d
     cut = float(list_cutoff)
     cfg_mode = bool(grades) and bool(ctx.pot.info.configuration_mode)
     C = int(ctx.pot.info.coeff_count)
-    items = []
-    for k, c in enumerate(configs):
-        pos = np.ascontiguousarray(c[0], dtype=np.float64).reshape(-1, 3)
-        types = c[2] if len(c) > 2 else None
-        types = np.ones(len(pos), dtype=np.int32) if types is None else np.ascontiguousarray(types, dtype=np.int32).reshape(-1)
-        if len(types) != len(pos):
-            raise ValueError("configuration %d: %d types for %d atoms" % (k, len(types), len(pos)))
-        items.append((pos, types))
-    all_cells = np.array([np.asarray(c[1], dtype=np.float64).reshape(3, 3) for c in configs], dtype=np.float64).reshape(-1, 3, 3)
-    natoms = np.array([len(it[0]) for it in items], dtype=np.int64)
+    items, all_cells, natoms = _batch_items(configs)
     passes, volume, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
     ghosts = capi.Ghosts(dev.index or 0)
     buf = _BatchBuffers(torch, dev)
     results = [None] * len(items)
     npass = 0
+    na = lambda nall: nall + (nall & 1)
     for k0, k1, lay in passes:
-        cells = all_cells[k0:k1]
         npass += 1
-        part = items[k0:k1]
         ncfg = k1 - k0
         counts = natoms[k0:k1]
         cf = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
@@ -323,24 +313,10 @@ def _cell_passes(ctx, configs, list_cutoff, vflag, grades, max_atoms_per_pass, d
             for k in range(k0, k1):
                 results[k] = _empty_result(float(volume[k]), grades, cfg_mode)
             continue
-        cap = n + int(max_rows[k0:k1].sum())
-        na = lambda nall: nall + (nall & 1)
-        buf.reserve(cap, ncfg, 10 * na(cap) + 10 + C + (C & 1), 7 * n + 8 * ncfg)
-        buf.xall[:n] = torch.from_numpy(np.concatenate([it[0] for it in part])).to(dev)
-        buf.tall[:n] = torch.from_numpy(np.concatenate([it[1] for it in part])).to(dev)
         cf_t = torch.from_numpy(cf).to(dev)
-        try:
-            nall = ghosts.build_batch(buf.xall, cf, cells, lay["origins"], cut, stream=st)
-        except capi.MtpError as e:                            # (the capacity protocol; `cap` is an upper bound)
-            if e.code != -24 or ghosts.nall <= buf.cap or ghosts.nall >= 2 ** 31 - 1:
-                raise
-            keep = buf.xall[:n].clone()
-            buf.reserve(ghosts.nall, ncfg, 10 * na(ghosts.nall) + 10 + C + (C & 1), 0)
-            buf.xall[:n] = keep
-            buf.tall[:n] = torch.from_numpy(np.concatenate([it[1] for it in part])).to(dev)
-            nall = ghosts.build_batch(buf.xall, cf, cells, lay["origins"], cut, stream=st)
-        ghosts.types(buf.tall, stream=st)
-        ctx.build_neighbors_device(buf.xall, n, nall, cut, lay["lo"], lay["hi"], stream=st)
+        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items[k0:k1], cf, all_cells[k0:k1], lay, cut, n + int(max_rows[k0:k1].sum()),
+                                     lambda rows, first: buf.reserve(rows, ncfg, 10 * na(rows) + 10 + C + (C & 1),
+                                                                     7 * n + 8 * ncfg if first else 0), st)
         # f | ev | eatom | vatom | max grade | coeff_ders: one allocation, zeroed by one launch
         m = na(nall)
         work = buf.work[: 10 * m + 10 + C + (C & 1)]
@@ -385,6 +361,46 @@ def _cell_passes(ctx, configs, list_cutoff, vflag, grades, max_atoms_per_pass, d
                 r["grades"], r["max_grade"] = gh[a:b], float(ch[j])
             results[k0 + j] = r
     return results
+
+
+def _batch_items(configs):
+    """[(pos [n, 3], types [n])], cells [ncfg, 3, 3] and atom counts of a sequence of (pos, cell, types) configurations"""
+    items = []
+    for k, c in enumerate(configs):
+        pos = np.ascontiguousarray(c[0], dtype=np.float64).reshape(-1, 3)
+        types = c[2] if len(c) > 2 else None
+        types = np.ones(len(pos), dtype=np.int32) if types is None else np.ascontiguousarray(types, dtype=np.int32).reshape(-1)
+        if len(types) != len(pos):
+            raise ValueError("configuration %d: %d types for %d atoms" % (k, len(types), len(pos)))
+        items.append((pos, types))
+    all_cells = np.array([np.asarray(c[1], dtype=np.float64).reshape(3, 3) for c in configs], dtype=np.float64).reshape(-1, 3, 3)
+    natoms = np.array([len(it[0]) for it in items], dtype=np.int64)
+    return items, all_cells, natoms
+
+
+def _pass_ghosts_and_list(ctx, ghosts, buf, part, cf, cells, lay, cut, cap, reserve, st):
+    """the ghost and list part of one pass over a batch of cells (shared by evaluate_cells / select_cells and design_cells):
+    owned positions and types into buf.xall / buf.tall, the ghost build with the cell looked up per atom, ghost types and
+    the full list, installed in the context.  `reserve(rows, first)` sizes the caller's buffers for `rows` owned + ghost
+    rows (`cap` is an upper bound; the capacity protocol grows them once more if it has to).  Returns nall."""
+    torch, dev = buf.torch, buf.dev
+    n = int(cf[-1])
+    reserve(cap, True)
+    buf.xall[:n] = torch.from_numpy(np.concatenate([it[0] for it in part])).to(dev)
+    buf.tall[:n] = torch.from_numpy(np.concatenate([it[1] for it in part])).to(dev)
+    try:
+        nall = ghosts.build_batch(buf.xall, cf, cells, lay["origins"], cut, stream=st)
+    except capi.MtpError as e:                            # (the capacity protocol; `cap` is an upper bound)
+        if e.code != -24 or ghosts.nall <= buf.cap or ghosts.nall >= 2 ** 31 - 1:
+            raise
+        keep = buf.xall[:n].clone()
+        reserve(ghosts.nall, False)
+        buf.xall[:n] = keep
+        buf.tall[:n] = torch.from_numpy(np.concatenate([it[1] for it in part])).to(dev)
+        nall = ghosts.build_batch(buf.xall, cf, cells, lay["origins"], cut, stream=st)
+    ghosts.types(buf.tall, stream=st)
+    ctx.build_neighbors_device(buf.xall, n, nall, cut, lay["lo"], lay["hi"], stream=st)
+    return nall
 
 
 def _empty_result(volume, grades, cfg_mode):
@@ -449,3 +465,157 @@ def select_cells(ctx, configs, threshold=1.1, out_path=None, list_cutoff=7.0, ma
                 grade_before=np.array([r["cfg_grade"] if cfg_mode else r["max_grade"] for r in res]),
                 max_grade_after=sel["max_grade_after"], active_set=sel["active_set"],
                 inverse_active_set=sel["inverse_active_set"], slot_source=source, swaps=sel["swaps"])
+
+
+def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None):
+    """The design matrix of the linear refit over a batch of configurations (include/mtp_mi355x.h, "linear refit"): the
+    passes of evaluate_cells -- ghost build, list build -- with the design call (Context.design_rows, the ghost owner
+    map folding every neighbour's term onto its owned row) in place of the force call, then the per-configuration sums
+    (capi.batch_design_reduce).  Columns are [species (Sp) | moments (S)]; with theta = the potential's species_coeffs and
+    moment_coeffs, energy @ theta, force @ theta and virial @ theta are what evaluate_cells returns.
+
+    Returns dict(energy [ncfg, Sp + S], force [3 sum n, Sp + S] (row 3 (cfg_first[k] + a) + c: atom a of configuration k,
+    component c, atoms in the order of `pos`), virial [ncfg, 6, Sp + S] (None with virial=False), cfg_first [ncfg + 1],
+    columns = Sp + S) as DEVICE tensors (views of allocations whose rows are `ld` = columns rounded up to even apart),
+    plus natoms.  ValueError when these three matrices together with the per-atom basis and virial rows of the largest
+    pass (7 n ld doubles for a pass of n atoms; `max_atoms_per_pass` bounds them) would exceed `max_design_bytes`: the caller
+    shards the training set.  An atom type outside the potential is reported at the synchronise of its pass; the message names it."""
+    import torch
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    cut = float(list_cutoff)
+    info = ctx.pot.info
+    cols = int(info.species_count + info.alpha_scalar_count)
+    ld = cols + (cols & 1)
+    items, all_cells, natoms = _batch_items(configs)
+    ncfg_all = len(items)
+    first = np.concatenate([[0], np.cumsum(natoms)]).astype(np.int64)
+    ntot = int(first[-1])
+    passes, _, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
+    # the three matrices and, beside them, the per-atom basis and virial rows of the largest pass
+    pass_atoms = max([int(first[k1] - first[k0]) for k0, k1, _ in passes], default=0)
+    need = 8 * ld * (ncfg_all + 3 * ntot + (6 * ncfg_all if virial else 0) + (7 if virial else 1) * pass_atoms)
+    if need > max_design_bytes:
+        raise ValueError("design_cells: the design matrix of %d configurations with %d atoms (and the per-atom rows of its "
+                         "largest pass, %d atoms) needs %d bytes, max_design_bytes is %d; shard the training set, or lower "
+                         "max_atoms_per_pass" % (ncfg_all, ntot, pass_atoms, need, max_design_bytes))
+    energy = torch.zeros((ncfg_all, ld), dtype=torch.float64, device=dev)
+    force = torch.zeros((3 * ntot, ld), dtype=torch.float64, device=dev)
+    vir = torch.zeros((ncfg_all, 6, ld), dtype=torch.float64, device=dev) if virial else None
+    ghosts = capi.Ghosts(dev.index or 0)
+    buf = _BatchBuffers(torch, dev)
+    npass = 0
+    for k0, k1, lay in passes:
+        npass += 1
+        cf = (first[k0:k1 + 1] - first[k0]).astype(np.int32)
+        n = int(cf[-1])
+        if n == 0:
+            continue
+        cf_t = torch.from_numpy(cf).to(dev)
+        # per-atom rows of the pass: basis [n, ld] | virial [n, 6, ld]
+        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items[k0:k1], cf, all_cells[k0:k1], lay, cut, n + int(max_rows[k0:k1].sum()),
+                                     lambda rows, first_: buf.reserve(rows, 0, (7 if virial else 1) * n * ld, 0), st)
+        basis = buf.work[: n * ld].view(n, ld)
+        vatom = buf.work[n * ld: 7 * n * ld].view(n, 6, ld) if virial else None
+        owner, nown = ghosts.owner(stream=st)
+        assert nown == nall
+        ctx.design_rows(0, n, buf.xall, buf.tall, force[3 * int(first[k0]): 3 * int(first[k1])], n, ld, basis_t=basis, virial_t=vatom,
+                        owner=owner, stream=st)
+        capi.batch_design_reduce(cf_t, ld, basis_t=basis, virial_atom_t=vatom, energy_t=energy[k0:k1],
+                                 virial_t=vir[k0:k1] if virial else None, stream=st)
+        try:
+            ctx.synchronize(stream=st)                        # an atom type outside the potential is reported here
+        except capi.MtpError as e:
+            raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
+    torch.cuda.current_stream(dev).synchronize()
+    return dict(energy=energy[:, :cols], force=force[:, :cols], virial=vir[:, :, :cols] if virial else None,
+                cfg_first=torch.from_numpy(first.astype(np.int32)).to(dev), columns=cols, natoms=natoms)
+
+
+def fit_linear(ctx, configs, labels, weights=(1.0, 0.01, 0.001), rcond=1e-12, out_path=None, list_cutoff=7.0,
+               max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None):
+    """The linear refit: species_coeffs and moment_coeffs fitted to reference energies, forces and virials with the radial
+    coefficients fixed.  labels[k] = dict(energy=float or None, f=[n, 3] or None, virial=[6] or None) for configs[k]
+    (virial in the sign and order evaluate_cells returns).  With N_k atoms in configuration k the rows of design_cells
+    and their labels are scaled by sqrt(w_e) / N_k (energy), sqrt(w_f) (forces) and sqrt(w_s) / N_k (virial), weights =
+    (w_e, w_f, w_s) -- this project's definition, not pinned to MLIP's --, rows without a label are dropped, and the
+    solve is for the CHANGE of the coefficients: delta = lstsq(A_w, y_w - A_w theta_0, rcond), theta = theta_0 + delta,
+    theta_0 the potential's current coefficients, so that directions the data do not determine (the complete tables are
+    rank deficient by construction) keep their values.  The weighted matrix is copied to the host and solved with
+    numpy.linalg.lstsq (SVD); it is bounded by max_design_bytes and the fit runs once per round.
+
+    Returns dict(species_coeffs, moment_coeffs, rank, singular_values, rmse_before, rmse_after: dicts energy (per atom),
+    force, virial (per atom) over the labelled rows, None for a kind without labels) and, with out_path, writes the
+    potential file through capi.write_coeffs ("wrote" = its return value).  The context keeps its old coefficients:
+    reload the written file, as after a selection."""
+    if len(labels) != len(configs):
+        raise ValueError("fit_linear: %d labels for %d configurations" % (len(labels), len(configs)))
+    want_v = float(weights[2]) > 0.0 and any(l.get("virial") is not None for l in labels)
+    d = design_cells(ctx, configs, list_cutoff=list_cutoff, virial=want_v, max_design_bytes=max_design_bytes,
+                     max_atoms_per_pass=max_atoms_per_pass, device=device)
+    t = ctx.pot.tables()
+    res = solve_linear(d["energy"].cpu().numpy(), d["force"].cpu().numpy(), d["virial"].cpu().numpy() if want_v else None,
+                       d["natoms"], labels, np.concatenate([t["species_coeffs"], t["moment_coeffs"]]), weights, rcond)
+    Sp = int(ctx.pot.info.species_count)
+    theta = res.pop("theta")
+    res.update(species_coeffs=theta[:Sp].copy(), moment_coeffs=theta[Sp:].copy())
+    if out_path is not None:
+        res["wrote"] = capi.write_coeffs(ctx.pot.path, out_path, res["moment_coeffs"], res["species_coeffs"])
+    return res
+
+
+def solve_linear(energy, force, virial, natoms, labels, theta0, weights=(1.0, 0.01, 0.001), rcond=1e-12):
+    """The host part of fit_linear (numpy only): energy [ncfg, cols], force [3 sum n, cols], virial [ncfg, 6, cols] or None
+    are the design matrices of design_cells, natoms [ncfg].  Labelled rows are scaled as fit_linear documents, and
+    delta = lstsq(A_w, y_w - A_w theta0, rcond) (SVD).  Returns dict(theta = theta0 + delta, rank, singular_values,
+    rmse_before, rmse_after)."""
+    w_e, w_f, w_s = (float(w) for w in weights)
+    natoms = np.asarray(natoms, dtype=np.int64)
+    ncfg = len(natoms)
+    first = np.concatenate([[0], np.cumsum(natoms)])
+    cols = energy.shape[1]
+    e_rows = [k for k in range(ncfg) if labels[k].get("energy") is not None and natoms[k] > 0 and w_e > 0.0]
+    f_cfg = [k for k in range(ncfg) if labels[k].get("f") is not None and natoms[k] > 0 and w_f > 0.0]
+    v_cfg = [k for k in range(ncfg) if virial is not None and w_s > 0.0 and labels[k].get("virial") is not None and natoms[k] > 0]
+    blocks, ys, scales, kinds = [], [], [], []
+    if e_rows:
+        blocks.append(energy[e_rows])
+        ys.append(np.array([float(labels[k]["energy"]) for k in e_rows]))
+        scales.append(np.sqrt(w_e) / natoms[e_rows])
+        kinds.append(("energy", w_e))
+    if f_cfg:
+        for k in f_cfg:
+            if np.shape(labels[k]["f"]) != (natoms[k], 3):
+                raise ValueError("fit_linear: labels[%d]['f'] must be [%d, 3]" % (k, natoms[k]))
+        rows = np.concatenate([np.arange(3 * first[k], 3 * first[k + 1]) for k in f_cfg])
+        blocks.append(force[rows])
+        ys.append(np.concatenate([np.asarray(labels[k]["f"], dtype=np.float64).reshape(-1) for k in f_cfg]))
+        scales.append(np.full(len(rows), np.sqrt(w_f)))
+        kinds.append(("force", w_f))
+    if v_cfg:
+        blocks.append(virial[v_cfg].reshape(-1, cols))
+        ys.append(np.concatenate([np.asarray(labels[k]["virial"], dtype=np.float64).reshape(6) for k in v_cfg]))
+        scales.append(np.repeat(np.sqrt(w_s) / natoms[v_cfg], 6))
+        kinds.append(("virial", w_s))
+    if not blocks:
+        raise ValueError("fit_linear: no labelled rows with a positive weight")
+    scale = np.concatenate(scales)
+    Aw = np.concatenate(blocks) * scale[:, None]
+    yw = np.concatenate(ys) * scale
+    theta0 = np.asarray(theta0, dtype=np.float64)
+    resid0 = yw - Aw @ theta0
+    delta, _, rank, sv = np.linalg.lstsq(Aw, resid0, rcond=rcond)
+    theta = theta0 + delta
+    resid1 = yw - Aw @ theta
+
+    def rmse(resid):
+        # per kind, with the weight taken out: energy and virial per atom, forces per component
+        out, at = dict(energy=None, force=None, virial=None), 0
+        for (kind, w), sc in zip(kinds, scales):
+            out[kind] = float(np.sqrt(np.mean((resid[at:at + len(sc)] / np.sqrt(w)) ** 2)))
+            at += len(sc)
+        return out
+
+    return dict(theta=theta, rank=int(rank), singular_values=sv, rmse_before=rmse(resid0), rmse_after=rmse(resid1))
