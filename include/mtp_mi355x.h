@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 6
+#define MTP_MI355X_ABI_VERSION 7
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -567,6 +567,57 @@ int mtp_potential_design_table(const mtp_potential *pot, int32_t *counts, int32_
 int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const double *species_coeffs /*[Sp] or NULL*/,
                                const double *moment_coeffs /*[S]*/, int species_count, int scalar_count, char *err,
                                int errlen);
+
+/* ---- training gradient: loss derivatives for ALL coefficients -------------------------------------------------------
+ *
+ * theta [C] holds every coefficient in candidate-vector order: radial [Sp][Sp][Mu][R] | species [Sp] | moments [S],
+ * C = Sp^2 Mu R + Sp + S.  It is a device vector of the caller's and is read by every call: a trainer steps theta without
+ * reloading a potential, and the context's force tables keep the file's coefficients.  The model is not linear in the
+ * radial block, so the gradient is produced in reverse: for cotangents ebar (per atom), fbar (per owned atom) and vbar
+ * (per atom, six components)
+ *     grad = d/dtheta [ sum_i ebar_i eatom_i + sum_j fbar_j . F_j + sum_i vbar_i . vatom_i ],   F the folded force,
+ * which, summed over centre atoms, is the derivative of each centre's candidate vector along ONE displacement field
+ * du_n = fbar_owner(i) - fbar_owner(n) - Vs u_n (Vs: the symmetric matrix of vbar_i with halved off-diagonals) plus ebar_i
+ * times the candidate vector itself.  One workgroup of four wavefronts per centre atom; the structural
+ * table is built and uploaded by the first training call on a context.
+ *
+ * Tables the formulas do not cover are refused with MTP_ERR_UNSUPPORTED before anything is launched (mtp_last_error names
+ * the row or the scalar): a row of alpha_index_times that reads a moment which the same or a later row still adds to, and
+ * two scalars mapped to one moment.  For both the reference's forces are not the gradient of its energy.
+ *
+ * Arguments, the NULL-stream rule and the deferred reports are those of mtp_design_rows_device: MTP_ERR_STATE before a
+ * list is installed; MTP_ERR_ARG for a row range outside the list, nowned < 0, a missing required array, and in vjp mode
+ * ld < C or an odd ld; MTP_ERR_LIMIT when the workgroup's LDS image (four moment images, the tile tables, the list's
+ * longest row) exceeds 160 KB.  Reported by the next mtp_synchronize: an atom type outside the potential, a row longer
+ * than max_numneigh, a centre or an owner outside [0, nowned) or a list entry outside [0, nall); a refused centre is
+ * skipped as a whole and its rows are not assigned. */
+/* value: d_eatom [row_count] and d_vatom [row_count][6] (either may be NULL) are ASSIGNED per row ii - row_begin; d_force
+ * [nowned][3] is ACCUMULATED straight onto owner rows with fp64 atomic adds (the caller zeroes it): +t on the centre, -t on
+ * owner(n).  Semantics, signs and cutoff test are those of PairMTP::compute (pair_mtp.cpp:196-276). */
+int mtp_train_value_device(mtp_context *ctx, void *stream, const double *d_x, const int *d_type, int row_begin,
+                           int row_count, const int *d_owner, const double *d_theta, double *d_eatom, double *d_force,
+                           int nowned, double *d_vatom);
+/* vjp: d_ebar [row_count], d_fbar [nowned][3], d_vbar [row_count][6] -- any of them may be NULL, meaning zero.
+ * d_grad_rows [row_count][ld] is ASSIGNED, columns [C, ld) zero; no atomics to global memory.  Per-configuration sums of
+ * the rows: mtp_batch_design_reduce (d_basis = d_grad_rows). */
+int mtp_train_vjp_device(mtp_context *ctx, void *stream, const double *d_x, const int *d_type, int row_begin, int row_count,
+                         const int *d_owner, const double *d_theta, const double *d_ebar, const double *d_fbar, int nowned,
+                         const double *d_vbar, int ld, double *d_grad_rows);
+/* The training kernel's structural table (host only, for inspection): counts[6] = {rows (padded), level blocks, A, B, Mu,
+ * C}; the rows, level offsets, scalar map and basic descriptors are those of mtp_potential_design_table; bymu [B]: the
+ * basics ordered by mu, mufirst [Mu + 1] its offsets; refused[2] = {first row of alpha_index_times, in file order, that
+ * reads a moment which the same or a later row still adds to, first scalar mapped to a moment an earlier scalar is mapped
+ * to as well}, -1 for none.  Returns MTP_ERR_UNSUPPORTED and a message in err when either is set.  Any pointer may be
+ * NULL. */
+int mtp_potential_train_table(const mtp_potential *pot, int32_t *counts, int32_t *bymu, int32_t *mufirst, int32_t *refused,
+                              char *err, int errlen);
+/* mtp_potential_write_coeffs with the radial block as well: the lines between the radial_coeffs line and the
+ * alpha_moments_count line are replaced by every t1-t2 pair in row-major order, Mu brace lines of R numbers each, 17
+ * significant digits, indented as the source's first pair line and first brace line (radial_coeffs == NULL keeps the
+ * block).  The read-back through the text parser must return all three arrays bit for bit, or nothing is written. */
+int mtp_potential_write_all_coeffs(const char *src_path, const char *dst_path, const double *radial_coeffs /*[Sp^2 Mu R] or NULL*/,
+                                   const double *species_coeffs /*[Sp] or NULL*/, const double *moment_coeffs /*[S]*/,
+                                   int radial_count, int species_count, int scalar_count, char *err, int errlen);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@ EXPORTS = [
     "mtp_batch_cfg_candidates", "mtp_maxvol_select",
     "mtp_design_rows_device", "mtp_ghosts_owner_device", "mtp_batch_design_reduce", "mtp_potential_design_table",
     "mtp_potential_write_coeffs",
+    "mtp_train_value_device", "mtp_train_vjp_device", "mtp_potential_train_table", "mtp_potential_write_all_coeffs",
 ]
 WROTE_WITHOUT_SELECTION = 1   # mtp_potential_write_coeffs: the source's #MVS tail was left out
 # mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
@@ -223,6 +224,29 @@ class Potential:
         out.update(A=int(cnt[2]), B=int(cnt[3]))
         return out
 
+    def train_table(self):
+        """the training kernel's structural table as the host builds it (mtp_potential_train_table): dict(rows (padded),
+        levels, A, B, Mu, C, bymu [B], mufirst [Mu + 1], late_row, dup_scalar (-1: none), supported, message).  A table the
+        gradient formulas do not cover is reported here (supported = False, message names the row or the scalar) and
+        refused by the training calls with MtpError(UNSUPPORTED)."""
+        cnt = np.zeros(6, np.int32)
+        lib().mtp_potential_train_table(self.h, _np(cnt, C.c_int32), None, None, None, None, 0)
+        bymu, mufirst = np.zeros(int(cnt[3]), np.int32), np.zeros(int(cnt[4]) + 1, np.int32)
+        refused = np.zeros(2, np.int32)
+        err = C.create_string_buffer(512)
+        rc = lib().mtp_potential_train_table(self.h, None, _np(bymu, C.c_int32), _np(mufirst, C.c_int32),
+                                             _np(refused, C.c_int32), err, 512)
+        if rc not in (0, -6):
+            raise MtpError(rc, "train_table")
+        return dict(rows=int(cnt[0]), levels=int(cnt[1]), A=int(cnt[2]), B=int(cnt[3]), Mu=int(cnt[4]), C=int(cnt[5]),
+                    bymu=bymu, mufirst=mufirst, late_row=int(refused[0]), dup_scalar=int(refused[1]), supported=rc == 0,
+                    message=err.value.decode())
+
+    def theta(self):
+        """the file's coefficients as one [C] vector in candidate-vector order [radial | species | moments]"""
+        t = self.tables()
+        return np.concatenate([t["radial_coeffs"], t["species_coeffs"], t["moment_coeffs"]])
+
     def kernel_shape(self):
         """the force kernel instantiation a context of this potential launches (mtp_potential_kernel_shape)"""
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -390,6 +414,25 @@ class Context:
         self._check(lib().mtp_design_rows_device(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t), _ptr(type_t),
                                                  int(row_begin), int(row_count), C.c_void_p(owner) if owner else None, int(ld),
                                                  _ptr(basis_t), _ptr(force_t), int(nowned), _ptr(virial_t)))
+
+    def train_value(self, row_begin, row_count, x_t, type_t, theta_t, force_t, nowned, eatom_t=None, vatom_t=None, owner=None,
+                    stream=None):
+        """Energies, forces and virials at the coefficients theta_t [C] (device, candidate-vector order) for rows [row_begin,
+        row_begin + row_count) of the installed list (mtp_train_value_device): force_t [nowned, 3] is accumulated into (zero
+        it first), eatom_t [row_count] and vatom_t [row_count, 6] are assigned; `owner` as for design_rows."""
+        self._check(lib().mtp_train_value_device(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t), _ptr(type_t),
+                                                 int(row_begin), int(row_count), C.c_void_p(owner) if owner else None,
+                                                 _ptr(theta_t), _ptr(eatom_t), _ptr(force_t), int(nowned), _ptr(vatom_t)))
+
+    def train_vjp(self, row_begin, row_count, x_t, type_t, theta_t, grad_t, nowned, ld, ebar_t=None, fbar_t=None, vbar_t=None,
+                  owner=None, stream=None):
+        """Per-atom rows of the gradient with respect to all C coefficients (mtp_train_vjp_device): grad_t [row_count, ld]
+        is assigned, row i = d/dtheta of ebar_i eatom_i + the centre's share of fbar . F and vbar_i . vatom_i; ebar_t
+        [row_count], fbar_t [nowned, 3], vbar_t [row_count, 6], None = zero."""
+        self._check(lib().mtp_train_vjp_device(self.h, C.c_void_p(stream) if stream else None, _ptr(x_t), _ptr(type_t),
+                                               int(row_begin), int(row_count), C.c_void_p(owner) if owner else None,
+                                               _ptr(theta_t), _ptr(ebar_t), _ptr(fbar_t), int(nowned), _ptr(vbar_t), int(ld),
+                                               _ptr(grad_t)))
 
     def synchronize(self, stream=None):
         self._check(lib().mtp_synchronize(self.h, C.c_void_p(stream) if stream else None))
@@ -773,6 +816,21 @@ def write_coeffs(src, dst, moment_coeffs, species_coeffs=None):
     err = C.create_string_buffer(512)
     rc = lib().mtp_potential_write_coeffs(os.fsencode(src), os.fsencode(dst), _np(sp, C.c_double), _np(m, C.c_double),
                                           -1 if sp is None else len(sp), len(m), err, 512)
+    if rc < 0:
+        raise MtpError(rc, err.value.decode())
+    return rc
+
+
+def write_all_coeffs(src, dst, moment_coeffs, species_coeffs=None, radial_coeffs=None):
+    """write_coeffs with the radial block as well ([Sp, Sp, Mu, R] in any shape of that order; None keeps the source's):
+    mtp_potential_write_all_coeffs (host only).  Returns 0 or WROTE_WITHOUT_SELECTION."""
+    m = np.ascontiguousarray(moment_coeffs, dtype=np.float64).reshape(-1)
+    sp = None if species_coeffs is None else np.ascontiguousarray(species_coeffs, dtype=np.float64).reshape(-1)
+    ra = None if radial_coeffs is None else np.ascontiguousarray(radial_coeffs, dtype=np.float64).reshape(-1)
+    err = C.create_string_buffer(512)
+    rc = lib().mtp_potential_write_all_coeffs(os.fsencode(src), os.fsencode(dst), _np(ra, C.c_double), _np(sp, C.c_double),
+                                              _np(m, C.c_double), -1 if ra is None else len(ra), -1 if sp is None else len(sp),
+                                              len(m), err, 512)
     if rc < 0:
         raise MtpError(rc, err.value.decode())
     return rc

@@ -132,6 +132,11 @@ struct mtp_context {
   DevBuf<int32_t> d_design_ints;     // level offsets | basic descriptors | scalar map | force map
   DevBuf<double> d_design_radial;
   MtpDesignParams design{};
+  // training gradient (mtp_train_*_device): the structural table, built and uploaded by the first training call
+  bool train_ready = false;
+  DevBuf<MtpRow8> d_train_rows;
+  DevBuf<int32_t> d_train_ints;      // level offsets | basic descriptors | scalar map | basics by mu | mu offsets
+  MtpTrainParams train{};
 
   MtpDevParams base{};
   const char *last_shape = "";   // name of the fixed-shape kernel the last force launch ran ("": a generic kernel)
@@ -1547,6 +1552,168 @@ int mtp_batch_design_reduce(void *stream, int ncfg, const int *d_cfg_first, int 
                                         reinterpret_cast<hipStream_t>(stream)) == hipSuccess
       ? MTP_OK
       : MTP_ERR_DEVICE;
+}
+
+// ---- training gradient (include/mtp_mi355x.h) -------------------------------------------------------------------------
+static int train_prepare(mtp_context *c, hipStream_t st)
+{
+  if (c->train_ready) return MTP_OK;
+  const mtp_potential &pot = *c->pot;
+  mtp_train_table t;
+  std::string msg;
+  const int rc = mtp_build_train_table(pot, t, msg);
+  if (rc != MTP_OK) {
+    c->last_error = msg;
+    return rc;
+  }
+  const mtp_design_table &dt = t.design;
+  if (dt.A > 8191) {
+    c->last_error = "training gradient: alpha_moments_count above 8191 is not supported by the packed times rows";
+    return MTP_ERR_LIMIT;
+  }
+  if (pot.radial_func_count > 16 || pot.max_alpha_index_basic > 16) {
+    c->last_error = "training gradient: radial_funcs_count or a basic index above 16 does not fit the packed basics";
+    return MTP_ERR_LIMIT;
+  }
+  std::vector<MtpRow8> rows8(dt.rows.size());
+  for (size_t k = 0; k < rows8.size(); k++) {
+    const MtpRow &r = dt.rows[k];
+    if (r.mult > 32767 || r.mult < -32768) {
+      c->last_error = "training gradient: a multiplicity of alpha_index_times does not fit 16 bits";
+      return MTP_ERR_LIMIT;
+    }
+    rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
+    rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
+  }
+  std::vector<int32_t> ints(dt.level_offset);
+  ints.insert(ints.end(), dt.basic_pack.begin(), dt.basic_pack.end());
+  ints.insert(ints.end(), dt.scalar_map.begin(), dt.scalar_map.end());
+  ints.insert(ints.end(), t.bymu.begin(), t.bymu.end());
+  ints.insert(ints.end(), t.mufirst.begin(), t.mufirst.end());
+  c->d_train_rows.upload(rows8, st);
+  c->d_train_ints.upload(ints, st);
+  HIP_CHECK(hipStreamSynchronize(st));   // (the staging vectors go out of scope)
+  MtpTrainParams &d = c->train;
+  d = MtpTrainParams{};
+  d.Sp = pot.species_count;
+  d.R = pot.radial_basis_size;
+  d.Mu = pot.radial_func_count;
+  d.P = pot.max_alpha_index_basic;
+  d.A = dt.A;
+  d.B = dt.B;
+  d.S = dt.S;
+  d.nblocks = dt.nblocks;
+  d.rmin = pot.min_cutoff;
+  d.rmax = pot.max_cutoff;
+  d.scaling = pot.scaling;
+  d.cutsq = pot.max_cutoff * pot.max_cutoff;
+  d.inv_span = 1.0 / (pot.max_cutoff - pot.min_cutoff);
+  d.rows = c->d_train_rows.ptr;
+  d.level = c->d_train_ints.ptr;
+  d.pack = d.level + dt.level_offset.size();
+  d.map = d.pack + dt.B;
+  d.bymu = d.map + dt.S;
+  d.mufirst = d.bymu + dt.B;
+  d.err_flag = c->d_err.ptr;
+  c->train_ready = true;
+  return MTP_OK;
+}
+
+// the checks and the launch both training calls share; `who` names the call in messages
+static int train_launch(mtp_context *c, const char *who, bool vjp, void *stream, const double *d_x, const int *d_type, int row_begin,
+                        int row_count, const int *d_owner, const double *d_theta, int nowned, MtpTrainParams io, int ld)
+{
+  if (!c) return MTP_ERR_ARG;
+  const std::string w(who);
+  if (!c->have_list) {
+    c->last_error = w + " before a neighbour list is installed";
+    return MTP_ERR_STATE;
+  }
+  const mtp_potential &pot = *c->pot;
+  const int cols = pot.species_count * pot.species_count * pot.radial_func_count * pot.radial_basis_size + pot.species_count +
+      pot.alpha_scalar_count;
+  if (vjp && (ld < cols || (ld & 1))) {
+    c->last_error = w + ": ld = " + std::to_string(ld) + " must be even and at least C = " + std::to_string(cols);
+    return MTP_ERR_ARG;
+  }
+  if (row_begin < 0 || row_count < 0 || row_begin + row_count > c->inum || nowned < 0) {
+    c->last_error = w + ": row range outside the neighbour list, or nowned < 0";
+    return MTP_ERR_ARG;
+  }
+  if (row_count > 0 && (!d_x || !d_type || !d_theta || (vjp ? !io.grad : !io.force))) {
+    c->last_error = w + ": positions, types, theta and " + (vjp ? "the gradient rows" : "the force array") + " are required";
+    return MTP_ERR_ARG;
+  }
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+  try {
+    const int rc = train_prepare(c, st);   // (a refused table is reported even for an empty row range)
+    if (rc != MTP_OK) return rc;
+    if (row_count == 0) return MTP_OK;
+    MtpTrainParams p = c->train;
+    p.row0 = row_begin;
+    p.nrows = row_count;
+    p.nowned = nowned;
+    p.nall = c->nall;
+    p.ld = ld;
+    p.cj_cap = std::max(c->max_numneigh, 1);
+    p.ilist = c->ilist;
+    p.first = c->first;
+    p.neigh = c->neigh;
+    p.type = d_type;
+    p.owner = d_owner;
+    p.x = d_x;
+    p.theta = d_theta;
+    p.eatom = io.eatom;
+    p.force = io.force;
+    p.vatom = io.vatom;
+    p.ebar = io.ebar;
+    p.fbar = io.fbar;
+    p.vbar = io.vbar;
+    p.grad = io.grad;
+    const size_t lds = mtp_train_lds_layout(p);
+    if (lds > 160 * 1024) {
+      const size_t fixed = lds - (size_t) p.cj_cap * sizeof(int);
+      c->last_error = w + ": the workgroup's LDS image needs " + std::to_string(lds) + " of 163840 bytes: " +
+          (fixed > 160 * 1024 ? "four moment images of alpha_moments_count = " + std::to_string(p.A) + " doubles and " +
+                   std::to_string(p.tab_rows) + " table rows are too large"
+                              : "the list's longest row, max_numneigh = " + std::to_string(c->max_numneigh) + ", is too large");
+      return MTP_ERR_LIMIT;
+    }
+    const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+    const int grid = std::max(1, std::min(row_count, c->num_cus * per_cu));
+    HIP_CHECK(mtp_launch_train_kernel(p, vjp, grid, lds, st));
+  } catch (const HipFail &f) {
+    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
+    return MTP_ERR_DEVICE;
+  }
+  return MTP_OK;
+}
+
+int mtp_train_value_device(mtp_context *c, void *stream, const double *d_x, const int *d_type, int row_begin, int row_count,
+                           const int *d_owner, const double *d_theta, double *d_eatom, double *d_force, int nowned,
+                           double *d_vatom)
+{
+  MtpTrainParams io{};
+  io.eatom = d_eatom;
+  io.force = d_force;
+  io.vatom = d_vatom;
+  return train_launch(c, "mtp_train_value_device", false, stream, d_x, d_type, row_begin, row_count, d_owner, d_theta, nowned, io, 0);
+}
+
+int mtp_train_vjp_device(mtp_context *c, void *stream, const double *d_x, const int *d_type, int row_begin, int row_count,
+                         const int *d_owner, const double *d_theta, const double *d_ebar, const double *d_fbar, int nowned,
+                         const double *d_vbar, int ld, double *d_grad_rows)
+{
+  MtpTrainParams io{};
+  io.ebar = d_ebar;
+  io.fbar = d_fbar;
+  io.vbar = d_vbar;
+  io.grad = d_grad_rows;
+  return train_launch(c, "mtp_train_vjp_device", true, stream, d_x, d_type, row_begin, row_count, d_owner, d_theta, nowned, io, ld);
 }
 
 // ---- MaxVol selection (include/mtp_mi355x.h) -------------------------------------------------------------------------

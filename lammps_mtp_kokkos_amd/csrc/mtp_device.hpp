@@ -215,3 +215,32 @@ size_t mtp_design_lds_layout(MtpDesignParams &p);
 hipError_t mtp_launch_design_kernel(const MtpDesignParams &p, int grid, size_t lds, hipStream_t st);
 hipError_t mtp_launch_batch_design_reduce(int ncfg, const int *cfg_first, int ld, const double *basis, const double *virial_atom,
                                           double *energy, double *virial, hipStream_t st);
+
+// ---- training gradient (mtp_train.hip; include/mtp_mi355x.h, "training gradient") ---------------------------------------
+#define MTP_TRAIN_WAVES 4     // wavefronts per workgroup = per centre atom
+#define MTP_TRAIN_NT 32       // neighbours per LDS tile (table row pitch MTP_PITCH doubles)
+struct MtpTrainParams {
+  int Sp, R, Mu, P, A, B, S, nblocks;   // nblocks: level blocks of the row table, the leaf block included
+  double rmin, rmax, scaling, cutsq, inv_span;
+  // the structural table (mtp_train_table: the design table and the basics sorted by mu), HBM / L2
+  const MtpRow8 *rows;
+  const int *level;      // [nblocks + 1] padded row offsets
+  const int *pack;       // [B] slot | a << 8 | b << 12 | c << 16 | mu << 20
+  const int *map;        // [S] moment of every scalar (no two scalars share one)
+  const int *bymu;       // [B] basics ordered by mu
+  const int *mufirst;    // [Mu + 1] offsets into bymu
+  const double *theta;   // [C] radial [Sp][Sp][Mu][R] | species [Sp] | moments [S]
+  // system
+  int row0, nrows, nowned, nall, ld, cj_cap;
+  const int *ilist, *first, *neigh, *type, *owner;
+  const double *x;
+  double *eatom, *force, *vatom;             // value
+  const double *ebar, *fbar, *vbar;          // vjp (each may be null: zero)
+  double *grad;                              // vjp: [nrows][ld]
+  int *err_flag;
+  // workgroup LDS image, offsets in doubles: M | dM | D | dD [a_pad each] | tab[tab_rows][MTP_PITCH] | u, 1/r, du, dr
+  // [8][MTP_TRAIN_NT] | scratch | radial block [Sp Mu R] | ints
+  int a_pad, off_tab, off_nb, off_scr, off_rad, off_int, tab_rows;
+};
+size_t mtp_train_lds_layout(MtpTrainParams &p);
+hipError_t mtp_launch_train_kernel(const MtpTrainParams &p, bool vjp, int grid, size_t lds, hipStream_t st);

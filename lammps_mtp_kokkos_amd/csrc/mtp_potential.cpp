@@ -1310,6 +1310,51 @@ void mtp_build_design_table(const mtp_potential &pot, mtp_design_table &out)
     if (last[(size_t) pot.mapping_lds[(size_t) s]] == s) out.force_map[(size_t) s] = pot.mapping_lds[(size_t) s];
 }
 
+// the training kernel's table: the design table, the basics ordered by mu, and the two shapes its formulas do not cover
+int mtp_build_train_table(const mtp_potential &pot, mtp_train_table &out, std::string &err)
+{
+  mtp_build_design_table(pot, out.design);
+  const int B = out.design.B, Mu = pot.radial_func_count;
+  out.mufirst.assign((size_t) Mu + 1, 0);
+  out.bymu.clear();
+  for (int mu = 0; mu < Mu; mu++) {
+    for (int k = 0; k < B; k++)
+      if (((out.design.basic_pack[(size_t) k] >> 20) & 15) == mu) out.bymu.push_back(k);
+    out.mufirst[(size_t) mu + 1] = (int32_t) out.bymu.size();
+  }
+  out.late_row = -1;
+  out.dup_scalar = -1;
+  // in FILE order: a row that reads a moment a later row (or itself) still adds to -- the reference's reverse sweep is then
+  // not the transpose of its forward sweep (pair_mtp.cpp:196-233)
+  const int T = pot.alpha_index_times_count;
+  std::vector<int> last_writer((size_t) std::max(pot.alpha_moment_count, 1), -1);
+  for (int k = 0; k < T; k++) last_writer[(size_t) pot.alpha_index_times[4 * (size_t) k + 3]] = k;
+  for (int k = 0; k < T && out.late_row < 0; k++)
+    if (last_writer[(size_t) pot.alpha_index_times[4 * (size_t) k]] >= k || last_writer[(size_t) pot.alpha_index_times[4 * (size_t) k + 1]] >= k)
+      out.late_row = k;
+  // two scalars on one moment: the energy sums them, the adjoint keeps the last (:204-218)
+  std::vector<int> seen((size_t) std::max(pot.alpha_moment_count, 1), -1);
+  for (int s = 0; s < pot.alpha_scalar_count && out.dup_scalar < 0; s++) {
+    int &q = seen[(size_t) pot.alpha_moment_mapping[(size_t) s]];
+    if (q >= 0) out.dup_scalar = s;
+    q = s;
+  }
+  if (out.late_row >= 0) {
+    err = "training gradient: row " + std::to_string(out.late_row) + " of alpha_index_times reads a moment that row " +
+        std::to_string(std::max(last_writer[(size_t) pot.alpha_index_times[4 * (size_t) out.late_row]],
+                                last_writer[(size_t) pot.alpha_index_times[4 * (size_t) out.late_row + 1]])) +
+        " still adds to: the forces of such a table are not the gradient of its energy";
+    return MTP_ERR_UNSUPPORTED;
+  }
+  if (out.dup_scalar >= 0) {
+    err = "training gradient: scalar " + std::to_string(out.dup_scalar) + " of alpha_moment_mapping is mapped to moment " +
+        std::to_string(pot.alpha_moment_mapping[(size_t) out.dup_scalar]) +
+        ", which an earlier scalar is mapped to as well: the forces of such a table are not the gradient of its energy";
+    return MTP_ERR_UNSUPPORTED;
+  }
+  return MTP_OK;
+}
+
 namespace {
 
 void copy_message(const std::string &s, char *err, int errlen)
@@ -1374,11 +1419,13 @@ int mtp_potential_design_table(const mtp_potential *pot, int32_t *counts, int32_
   return MTP_OK;
 }
 
-int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const double *species_coeffs,
-                               const double *moment_coeffs, int species_count, int scalar_count, char *err, int errlen)
+// the two writers: `radial` == nullptr keeps the radial block of the source byte for byte
+static int write_coeffs_common(const std::string &who, const char *src_path, const char *dst_path, const double *radial,
+                               int radial_count, const double *species_coeffs, const double *moment_coeffs, int species_count,
+                               int scalar_count, char *err, int errlen)
 {
   if (!src_path || !dst_path || !moment_coeffs) {
-    copy_message("mtp_potential_write_coeffs: null argument", err, errlen);
+    copy_message(who + ": null argument", err, errlen);
     return MTP_ERR_ARG;
   }
   mtp_potential src;
@@ -1389,17 +1436,24 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
     return rc;
   }
   if ((species_coeffs && species_count != src.species_count) || scalar_count != src.alpha_scalar_count) {
-    copy_message("mtp_potential_write_coeffs: " + std::to_string(species_count) + " species and " +
+    copy_message(who + ": " + std::to_string(species_count) + " species and " +
                      std::to_string(scalar_count) + " moment coefficients given, the file has " +
                      std::to_string(src.species_count) + " and " + std::to_string(src.alpha_scalar_count),
                  err, errlen);
     return MTP_ERR_ARG;
   }
+  if (radial && (size_t) radial_count != src.radial_basis_coeffs.size()) {
+    copy_message(who + ": " + std::to_string(radial_count) + " radial coefficients given, the file has " +
+                     std::to_string(src.radial_basis_coeffs.size()),
+                 err, errlen);
+    return MTP_ERR_ARG;
+  }
   bool finite = true;
+  for (int i = 0; radial && i < radial_count; i++) finite = finite && std::isfinite(radial[i]);
   for (int i = 0; i < scalar_count; i++) finite = finite && std::isfinite(moment_coeffs[i]);
   for (int i = 0; species_coeffs && i < species_count; i++) finite = finite && std::isfinite(species_coeffs[i]);
   if (!finite) {
-    copy_message("mtp_potential_write_coeffs: a coefficient is not finite", err, errlen);
+    copy_message(who + ": a coefficient is not finite", err, errlen);
     return MTP_ERR_ARG;
   }
   std::string text;
@@ -1418,6 +1472,7 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
   // the last species_coeffs line, the moment_coeffs line behind it and, if there is one, the "#MVS_v1.1" line: the text
   // in front of the tail is kept byte for byte except for the two coefficient lines; the tail is left out
   size_t sp_b = std::string::npos, sp_e = 0, mo_b = std::string::npos, mo_e = 0, tail = std::string::npos;
+  size_t ra_b = std::string::npos, ra_e = 0, am_b = std::string::npos;   // the radial_coeffs line, the alpha_moments_count line
   for (size_t b = 0; b < text.size();) {
     size_t e = text.find('\n', b);
     e = e == std::string::npos ? text.size() : e + 1;
@@ -1427,6 +1482,12 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
       break;
     }
     const std::string w = first_word(line, true);
+    if (w == "radial_coeffs" && ra_b == std::string::npos) {
+      ra_b = b;
+      ra_e = e;
+    } else if (w == "alpha_moments_count" && ra_b != std::string::npos && am_b == std::string::npos) {
+      am_b = b;
+    }
     if (w == "species_coeffs") {
       sp_b = b;
       sp_e = e;
@@ -1438,7 +1499,7 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
     b = e;
   }
   if (sp_b == std::string::npos || mo_b == std::string::npos || mo_b < sp_e) {
-    copy_message("mtp_potential_write_coeffs: species_coeffs / moment_coeffs lines not found", err, errlen);
+    copy_message(who + ": species_coeffs / moment_coeffs lines not found", err, errlen);
     return MTP_ERR_PARSE;
   }
   auto eol_of = [&](size_t b, size_t e) {
@@ -1446,7 +1507,43 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
     while (k > b && (text[k - 1] == '\n' || text[k - 1] == '\r')) k--;
     return text.substr(k, e - k);
   };
-  std::string out = text.substr(0, sp_b);
+  if (radial && (ra_b == std::string::npos || am_b == std::string::npos || am_b < ra_e || am_b > sp_b)) {
+    copy_message(who + ": radial_coeffs / alpha_moments_count lines not found", err, errlen);
+    return MTP_ERR_PARSE;
+  }
+  std::string out;
+  if (radial) {
+    // every t1-t2 pair in row-major order, Mu brace lines of R numbers each; indentation of the source's first pair line
+    // and first brace line
+    auto indent_of = [&](size_t b) {
+      size_t k = b;
+      while (k < text.size() && (text[k] == ' ' || text[k] == '\t')) k++;
+      return text.substr(b, k - b);
+    };
+    const std::string eol = eol_of(ra_b, ra_e);
+    const std::string ind1 = indent_of(ra_e);
+    size_t l2 = text.find('\n', ra_e);
+    const std::string ind2 = l2 != std::string::npos && l2 + 1 < am_b ? indent_of(l2 + 1) : ind1 + "\t";
+    out = text.substr(0, ra_e);
+    const int Sp = src.species_count, Mu = src.radial_func_count, R = src.radial_basis_size;
+    char num[40];
+    for (int t1 = 0; t1 < Sp; t1++)
+      for (int t2 = 0; t2 < Sp; t2++) {
+        out += ind1 + std::to_string(t1) + "-" + std::to_string(t2) + eol;
+        for (int mu = 0; mu < Mu; mu++) {
+          out += ind2 + "{";
+          for (int ri = 0; ri < R; ri++) {
+            std::snprintf(num, sizeof num, "%.16e", radial[((size_t) (t1 * Sp + t2) * Mu + mu) * R + ri]);
+            if (ri) out += ", ";
+            out += num;
+          }
+          out += "}" + eol;
+        }
+      }
+    out += text.substr(am_b, sp_b - am_b);
+  } else {
+    out = text.substr(0, sp_b);
+  }
   out += species_coeffs ? coeff_line("species_coeffs", species_coeffs, species_count, eol_of(sp_b, sp_e))
                         : text.substr(sp_b, sp_e - sp_b);
   out += text.substr(sp_e, mo_b - sp_e);
@@ -1475,7 +1572,7 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
         back.alpha_index_basic == src.alpha_index_basic && back.alpha_index_times == src.alpha_index_times &&
         back.alpha_moment_mapping == src.alpha_moment_mapping && back.alpha_moment_count == src.alpha_moment_count &&
         back.radial_basis_coeffs.size() == src.radial_basis_coeffs.size() &&
-        std::memcmp(back.radial_basis_coeffs.data(), src.radial_basis_coeffs.data(),
+        std::memcmp(back.radial_basis_coeffs.data(), radial ? radial : src.radial_basis_coeffs.data(),
                     sizeof(double) * src.radial_basis_coeffs.size()) == 0;
     const std::vector<double> &want_sp = src.species_coeffs;
     if (same)
@@ -1484,7 +1581,7 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
                       sizeof(double) * want_sp.size()) == 0;
     if (!same) {
       std::remove(tmp.c_str());
-      copy_message("mtp_potential_write_coeffs: the written coefficients do not read back (the reader's line buffer of " +
+      copy_message(who + ": the written coefficients do not read back (the reader's line buffer of " +
                        std::to_string((long) src.alpha_index_times_count * 32 + 20) +
                        " characters, sized from alpha_index_times_count, is shorter than a coefficient line)" +
                        (rc != MTP_OK ? ": " + msg : std::string()),
@@ -1502,6 +1599,47 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
     return MTP_ERR_IO;
   }
   return tail == std::string::npos ? MTP_OK : MTP_WROTE_WITHOUT_SELECTION;
+}
+
+int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const double *species_coeffs,
+                               const double *moment_coeffs, int species_count, int scalar_count, char *err, int errlen)
+{
+  return write_coeffs_common("mtp_potential_write_coeffs", src_path, dst_path, nullptr, 0, species_coeffs, moment_coeffs,
+                             species_count, scalar_count, err, errlen);
+}
+
+int mtp_potential_write_all_coeffs(const char *src_path, const char *dst_path, const double *radial_coeffs,
+                                   const double *species_coeffs, const double *moment_coeffs, int radial_count, int species_count,
+                                   int scalar_count, char *err, int errlen)
+{
+  return write_coeffs_common("mtp_potential_write_all_coeffs", src_path, dst_path, radial_coeffs, radial_count, species_coeffs,
+                             moment_coeffs, species_count, scalar_count, err, errlen);
+}
+
+int mtp_potential_train_table(const mtp_potential *pot, int32_t *counts, int32_t *bymu, int32_t *mufirst, int32_t *refused,
+                              char *err, int errlen)
+{
+  if (!pot) return MTP_ERR_ARG;
+  mtp_train_table t;
+  std::string msg;
+  const int rc = mtp_build_train_table(*pot, t, msg);
+  if (counts) {
+    counts[0] = (int32_t) t.design.rows.size();
+    counts[1] = t.design.nblocks;
+    counts[2] = t.design.A;
+    counts[3] = t.design.B;
+    counts[4] = pot->radial_func_count;
+    counts[5] = pot->species_count * pot->species_count * pot->radial_func_count * pot->radial_basis_size + pot->species_count +
+        pot->alpha_scalar_count;
+  }
+  if (bymu) std::copy(t.bymu.begin(), t.bymu.end(), bymu);
+  if (mufirst) std::copy(t.mufirst.begin(), t.mufirst.end(), mufirst);
+  if (refused) {
+    refused[0] = t.late_row;
+    refused[1] = t.dup_scalar;
+  }
+  copy_message(msg, err, errlen);
+  return rc;
 }
 
 }   // extern "C"

@@ -101,3 +101,15 @@ struct mtp_design_table {
   std::vector<int32_t> level_offset, scalar_map, force_map, basic_pack;
 };
 void mtp_build_design_table(const mtp_potential &pot, mtp_design_table &out);
+
+// The training kernel's table, csrc/mtp_train.hip: the design table (force_map is not used), the basics ordered by mu
+// (bymu [B], mufirst [Mu + 1]) and the two table shapes the gradient formulas do not cover, found in FILE order: late_row =
+// the first row of alpha_index_times that reads a moment which the same or a later row still adds to, dup_scalar = the first
+// scalar mapped to a moment an earlier scalar is mapped to as well (-1: none).  Returns MTP_ERR_UNSUPPORTED with a message
+// that names the row or the scalar if there is one; the table is filled either way.
+struct mtp_train_table {
+  mtp_design_table design;
+  std::vector<int32_t> bymu, mufirst;
+  int late_row = -1, dup_scalar = -1;
+};
+int mtp_build_train_table(const mtp_potential &pot, mtp_train_table &out, std::string &err);

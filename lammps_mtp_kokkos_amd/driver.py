@@ -309,3 +309,121 @@ def design_twin(tables, system):
             vatom[ii, 4, Sp:] = -0.5 * (G[:, :, 0] * u[:, 2] + G[:, :, 2] * u[:, 0]).sum(1)
             vatom[ii, 5, Sp:] = -0.5 * (G[:, :, 1] * u[:, 2] + G[:, :, 2] * u[:, 1]).sum(1)
     return dict(basis=basis, energy=basis.sum(0), force=force, virial=vatom.sum(0), virial_atom=vatom)
+
+
+def train_twin(tables, system, theta=None, ebar=None, fbar=None, vbar=None):
+    """numpy twin of both modes of the training kernel (csrc/mtp_train.hip; include/mtp_mi355x.h, "training gradient";
+    DESIGN.md 5.3.2).  `theta` [C] holds ALL coefficients in candidate-vector order [radial Sp Sp Mu R | species Sp |
+    moments S] (None: the file's).  value: eatom, folded forces and vatom with the semantics of PairMTP::compute.  vjp:
+    for cotangents ebar [nlocal], fbar [nlocal, 3] (owned atoms) and vbar [nlocal, 6] (None = zero), row i is the derivative
+    with respect to theta of  ebar_i eatom_i + sum_n t_n . (fbar_owner(i) - fbar_owner(n) - Vs u_n),  t_n the centre's force
+    term on neighbour n and Vs the symmetric matrix of vbar_i with halved off-diagonals: ONE tangent direction du_n per
+    centre pushed through the basics and the times rows (FILE order, final moments), and through the reverse sweep with its
+    tangent dD.  Tables in which a row reads a moment a later row adds to, or two scalars share a moment, are outside
+    these formulas (mtp_potential_train_table refuses them).
+    Returns dict(eatom [nlocal], force [nlocal, 3], vatom [nlocal, 6], rows [nlocal, C])."""
+    basic = np.asarray(tables["alpha_index_basic"], dtype=np.int64).reshape(-1, 4)
+    times = np.asarray(tables["alpha_index_times"], dtype=np.int64).reshape(-1, 4)
+    mapping = np.asarray(tables["alpha_moment_mapping"], dtype=np.int64)
+    Sp, S, B = len(tables["species_coeffs"]), len(mapping), len(basic)
+    Mu = int(basic[:, 0].max()) + 1
+    R = len(tables["radial_coeffs"]) // (Sp * Sp * Mu)
+    nrad = Sp * Sp * Mu * R
+    C = nrad + Sp + S
+    if theta is None:
+        theta = np.concatenate([tables["radial_coeffs"], tables["species_coeffs"], tables["moment_coeffs"]])
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    assert len(theta) == C, (len(theta), C)
+    radial = theta[:nrad].reshape(Sp, Sp, Mu, R)
+    species, xi = theta[nrad:nrad + Sp], theta[nrad + Sp:]
+    A = int(max(B, times[:, [0, 1, 3]].max() + 1 if len(times) else 0, mapping.max() + 1 if S else 0))
+    scaling, rmin, rmax = float(tables["scaling"]), float(tables["min_cutoff"]), float(tables["max_cutoff"])
+    n = system.nlocal
+    ebar = np.zeros(n) if ebar is None else np.asarray(ebar, dtype=np.float64).reshape(n)
+    fbar = np.zeros((n, 3)) if fbar is None else np.asarray(fbar, dtype=np.float64).reshape(n, 3)
+    vbar = np.zeros((n, 6)) if vbar is None else np.asarray(vbar, dtype=np.float64).reshape(n, 6)
+    eatom, force, vatom, rows = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 6)), np.zeros((n, C))
+    mu_k, ea, eb, ec = basic[:, 0], basic[:, 1], basic[:, 2], basic[:, 3]
+    nu_k = ea + eb + ec
+    P = int(nu_k.max()) + 1
+    owner = np.asarray(system.owner)
+    for ii, i in enumerate(system.ilist):
+        it = int(system.types[i]) - 1
+        js = system.neigh[system.first[ii]:system.first[ii + 1]] & 0x1FFFFFFF
+        u = system.x[js] - system.x[i]
+        r2 = u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1] + u[:, 2] * u[:, 2]
+        keep = ~(r2 > rmax * rmax)
+        js, u = js[keep], u[keep]
+        K = len(js)
+        io = int(owner[i])
+        M, dM = np.zeros(A), np.zeros(A)
+        if K:
+            r = np.sqrt(r2[keep])
+            inv = 1.0 / r
+            jt = system.types[js].astype(np.int64) - 1
+            d, ksi, mult = r - rmax, (2.0 * r - (rmin + rmax)) / (rmax - rmin), 2.0 / (rmax - rmin)
+            q = np.zeros((R, K))
+            e = np.zeros((R, K))
+            q[0], e[0] = scaling * (d * d), scaling * 2.0 * d
+            if R > 1:
+                q[1], e[1] = scaling * (ksi * d * d), scaling * (mult * d * d + 2.0 * ksi * d)
+            for ri in range(2, R):
+                q[ri] = 2.0 * ksi * q[ri - 1] - q[ri - 2]
+                e[ri] = 2.0 * (mult * q[ri - 1] + ksi * e[ri - 1]) - e[ri - 2]
+            c = radial[it, jt]                                   # [K, Mu, R]
+            val_mu = np.einsum("kmr,rk->mk", c, q)
+            der_mu = np.einsum("kmr,rk->mk", c, e)
+            v = vbar[ii]
+            Vs = np.array([[v[0], 0.5 * v[3], 0.5 * v[4]], [0.5 * v[3], v[1], 0.5 * v[5]], [0.5 * v[4], 0.5 * v[5], v[2]]])
+            du = fbar[io][None, :] - fbar[owner[js]] - u @ Vs     # [K, 3]
+            dr = (u * du).sum(1) * inv
+            rinv = inv[None, :] ** np.arange(P)[:, None]          # [P, K]
+            pw = u.T[:, None, :] ** np.arange(P)[None, :, None]   # [3, P, K]
+            pa, pb, pc = pw[0][ea], pw[1][eb], pw[2][ec]
+            mono = pa * pb * pc                                   # [B, K]
+            grad = np.stack([ea[:, None] * pw[0][np.maximum(ea - 1, 0)] * pb * pc,
+                             eb[:, None] * pa * pw[1][np.maximum(eb - 1, 0)] * pc,
+                             ec[:, None] * pa * pb * pw[2][np.maximum(ec - 1, 0)]], axis=2)   # [B, K, 3]
+            w = rinv[nu_k] * mono
+            gw = rinv[nu_k][:, :, None] * grad - (nu_k[:, None] * w * inv)[:, :, None] * (u * inv[:, None])[None, :, :]
+            dw = (gw * du[None, :, :]).sum(2)                     # [B, K]
+            fv, fd = val_mu[mu_k], der_mu[mu_k]
+            M[:B] = (fv * w).sum(1)
+            dM[:B] = (fd * dr * w + fv * dw).sum(1)
+        for a0, a1, mlt, a3 in times:
+            M[a3] += mlt * M[a0] * M[a1]
+        for a0, a1, mlt, a3 in times:
+            dM[a3] += mlt * (dM[a0] * M[a1] + M[a0] * dM[a1])
+        D, dD = np.zeros(A), np.zeros(A)
+        for s in range(S):
+            D[mapping[s]] = xi[s]
+        for a0, a1, mlt, a3 in times[::-1]:
+            dD[a1] += mlt * (dD[a3] * M[a0] + D[a3] * dM[a0])
+            dD[a0] += mlt * (dD[a3] * M[a1] + D[a3] * dM[a1])
+            D[a1] += mlt * D[a3] * M[a0]
+            D[a0] += mlt * D[a3] * M[a1]
+        eatom[ii] = species[it] + (xi * M[mapping]).sum()
+        rows[ii, nrad + it] = ebar[ii]
+        rows[ii, nrad + Sp:] = ebar[ii] * M[mapping] + dM[mapping]
+        if K:
+            # force term of the centre on every neighbour: t_n = sum_k D_k dM_k / du_n
+            jac = fd[:, :, None] * w[:, :, None] * (u * inv[:, None])[None, :, :] + fv[:, :, None] * gw
+            t = (D[:B, None, None] * jac).sum(0)                 # [K, 3]
+            force[io] += t.sum(0)
+            np.subtract.at(force, owner[js], t)
+            vatom[ii, 0] = -(t[:, 0] * u[:, 0]).sum()
+            vatom[ii, 1] = -(t[:, 1] * u[:, 1]).sum()
+            vatom[ii, 2] = -(t[:, 2] * u[:, 2]).sum()
+            vatom[ii, 3] = -0.5 * (t[:, 0] * u[:, 1] + t[:, 1] * u[:, 0]).sum()
+            vatom[ii, 4] = -0.5 * (t[:, 0] * u[:, 2] + t[:, 2] * u[:, 0]).sum()
+            vatom[ii, 5] = -0.5 * (t[:, 1] * u[:, 2] + t[:, 2] * u[:, 1]).sum()
+            Db, dDb = D[:B, None], dD[:B, None]
+            ta = (ebar[ii] * Db + dDb) * w + Db * dw             # [B, K]
+            tb = Db * w * dr[None, :]
+            for m in range(Mu):
+                sel = mu_k == m
+                a_mu, b_mu = ta[sel].sum(0), tb[sel].sum(0)       # [K]
+                blk = q * a_mu[None, :] + e * b_mu[None, :]       # [R, K]
+                for tj in range(Sp):
+                    rows[ii, ((it * Sp + tj) * Mu + m) * R:((it * Sp + tj) * Mu + m + 1) * R] += blk[:, jt == tj].sum(1)
+    return dict(eatom=eatom, force=force, vatom=vatom, rows=rows)

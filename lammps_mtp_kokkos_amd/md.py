@@ -619,3 +619,187 @@ def solve_linear(energy, force, virial, natoms, labels, theta0, weights=(1.0, 0.
         return out
 
     return dict(theta=theta, rank=int(rank), singular_values=sv, rmse_before=rmse(resid0), rmse_after=rmse(resid1))
+
+
+def _label_arrays(labels, natoms, weights):
+    """host arrays of the labels and the masks of the labelled kinds (the rules of solve_linear: a kind counts where its
+    label is not None, its weight positive and the configuration not empty)"""
+    w_e, w_f, w_s = (float(w) for w in weights)
+    ncfg = len(natoms)
+    first = np.concatenate([[0], np.cumsum(natoms)]).astype(np.int64)
+    e_ref, e_on = np.zeros(ncfg), np.zeros(ncfg)
+    f_ref, f_on = np.zeros((int(first[-1]), 3)), np.zeros(int(first[-1]))
+    v_ref, v_on = np.zeros((ncfg, 6)), np.zeros(ncfg)
+    for k, l in enumerate(labels):
+        if natoms[k] == 0:
+            continue
+        if l.get("energy") is not None and w_e > 0.0:
+            e_ref[k], e_on[k] = float(l["energy"]), 1.0
+        if l.get("f") is not None and w_f > 0.0:
+            if np.shape(l["f"]) != (natoms[k], 3):
+                raise ValueError("loss_cells: labels[%d]['f'] must be [%d, 3]" % (k, natoms[k]))
+            f_ref[first[k]:first[k + 1]], f_on[first[k]:first[k + 1]] = np.asarray(l["f"], dtype=np.float64), 1.0
+        if l.get("virial") is not None and w_s > 0.0:
+            v_ref[k], v_on[k] = np.asarray(l["virial"], dtype=np.float64).reshape(6), 1.0
+    return first, e_ref, e_on, f_ref, f_on, v_ref, v_on
+
+
+def loss_cells(ctx, configs, labels, theta=None, weights=(1.0, 0.01, 0.001), grad=True, list_cutoff=7.0, max_atoms_per_pass=None,
+               device=None):
+    """The training loss and its gradient with respect to ALL coefficients (include/mtp_mi355x.h, "training gradient").
+    `theta` [C] in candidate-vector order [radial | species | moments] (None: the potential's own, Potential.theta()); the
+    context's force tables are not involved.  The loss is the objective fit_linear minimises, with N_k atoms in
+    configuration k and weights = (w_e, w_f, w_s):
+        L = sum_k [ w_e ((E_k - E*_k) / N_k)^2 + w_f sum |F - F*|^2 + w_s sum_6 ((V_k - V*_k) / N_k)^2 ]  over the labelled kinds.
+    The passes are those of evaluate_cells and design_cells (ghost build, list build, the ghost owner map).  Per pass: the
+    value kernel (Context.train_value), per-configuration totals (capi.batch_reduce), residuals and cotangents
+    ebar_i = 2 w_e (E_k - E*_k) / N_k^2, fbar_j = 2 w_f (F_j - F*_j), vbar_i = 2 w_s (V_k - V*_k) / N_k^2 (torch, on the
+    device), the vjp kernel (Context.train_vjp) and the per-configuration sums of its rows (capi.batch_design_reduce).
+
+    Returns dict(loss, grad [C] host float64 (None with grad=False), grad_cfg [ncfg, C] device (None with grad=False), rmse:
+    dict energy (per atom), force, virial (per atom) over the labelled rows as fit_linear reports them, None for a kind
+    without labels; energy [ncfg], forces [sum n, 3] in the order of `pos`, virial [ncfg, 6] as host arrays)."""
+    import torch
+    if len(labels) != len(configs):
+        raise ValueError("loss_cells: %d labels for %d configurations" % (len(labels), len(configs)))
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    cut = float(list_cutoff)
+    info = ctx.pot.info
+    C = int(info.species_count ** 2 * info.radial_func_count * info.radial_basis_size + info.species_count + info.alpha_scalar_count)
+    ld = C + (C & 1)
+    theta_h = ctx.pot.theta() if theta is None else np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+    if len(theta_h) != C:
+        raise ValueError("loss_cells: theta has %d entries, the potential has C = %d coefficients" % (len(theta_h), C))
+    w_e, w_f, w_s = (float(w) for w in weights)
+    items, all_cells, natoms = _batch_items(configs)
+    ncfg_all = len(items)
+    first, e_ref, e_on, f_ref, f_on, v_ref, v_on = _label_arrays(labels, natoms, weights)
+    ntot = int(first[-1])
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    theta_t = to(theta_h)
+    e_ref_t, e_on_t, f_ref_t, f_on_t, v_ref_t, v_on_t = to(e_ref), to(e_on), to(f_ref), to(f_on), to(v_ref), to(v_on)
+    inv_n = to(1.0 / np.maximum(natoms, 1).astype(np.float64))
+    counts_t = to(natoms)
+    energy = torch.zeros(ncfg_all, dtype=torch.float64, device=dev)
+    virial = torch.zeros((ncfg_all, 6), dtype=torch.float64, device=dev)
+    forces = torch.zeros((ntot, 3), dtype=torch.float64, device=dev)
+    grad_cfg = torch.zeros((ncfg_all, ld), dtype=torch.float64, device=dev) if grad else None
+    passes, _, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
+    ghosts = capi.Ghosts(dev.index or 0)
+    buf = _BatchBuffers(torch, dev)
+    npass = 0
+    for k0, k1, lay in passes:
+        npass += 1
+        cf = (first[k0:k1 + 1] - first[k0]).astype(np.int32)
+        n = int(cf[-1])
+        if n == 0:
+            continue
+        a0, a1 = int(first[k0]), int(first[k1])
+        cf_t = torch.from_numpy(cf).to(dev)
+        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items[k0:k1], cf, all_cells[k0:k1], lay, cut, n + int(max_rows[k0:k1].sum()),
+                                     lambda rows, first_: buf.reserve(rows, 0, 0, 0), st)
+        owner, nown = ghosts.owner(stream=st)
+        assert nown == nall
+        eatom = torch.empty(n, dtype=torch.float64, device=dev)
+        vatom = torch.empty((n, 6), dtype=torch.float64, device=dev)
+        f_pass = forces[a0:a1]                                # (zero: accumulated into)
+        ctx.train_value(0, n, buf.xall, buf.tall, theta_t, f_pass, n, eatom_t=eatom, vatom_t=vatom, owner=owner, stream=st)
+        capi.batch_reduce(cf_t, eatom_t=eatom, vatom_t=vatom, energy_t=energy[k0:k1], virial_t=virial[k0:k1], stream=st)
+        if grad:
+            reps = counts_t[k0:k1]
+            ebar = torch.repeat_interleave(2.0 * w_e * (energy[k0:k1] - e_ref_t[k0:k1]) * e_on_t[k0:k1] * inv_n[k0:k1] ** 2, reps)
+            vbar = torch.repeat_interleave(2.0 * w_s * (virial[k0:k1] - v_ref_t[k0:k1]) * (v_on_t[k0:k1] * inv_n[k0:k1] ** 2)[:, None],
+                                           reps, dim=0).contiguous()
+            fbar = (2.0 * w_f * (f_pass - f_ref_t[a0:a1]) * f_on_t[a0:a1, None]).contiguous()
+            rows = torch.empty((n, ld), dtype=torch.float64, device=dev)
+            ctx.train_vjp(0, n, buf.xall, buf.tall, theta_t, rows, n, ld, ebar_t=ebar, fbar_t=fbar, vbar_t=vbar, owner=owner,
+                          stream=st)
+            capi.batch_design_reduce(cf_t, ld, basis_t=rows, energy_t=grad_cfg[k0:k1], stream=st)
+        try:
+            ctx.synchronize(stream=st)                        # an atom type outside the potential is reported here
+        except capi.MtpError as e:
+            raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
+    re = (energy - e_ref_t) * e_on_t * inv_n
+    rf = (forces - f_ref_t) * f_on_t[:, None]
+    rv = (virial - v_ref_t) * (v_on_t * inv_n)[:, None]
+    sums = torch.stack([(re * re).sum(), (rf * rf).sum(), (rv * rv).sum()]).cpu().numpy()
+    torch.cuda.current_stream(dev).synchronize()
+    loss = float(w_e * sums[0] + w_f * sums[1] + w_s * sums[2])
+    nrow = (e_on.sum(), 3.0 * f_on.sum(), 6.0 * v_on.sum())
+    rmse = {k: (float(np.sqrt(s / m)) if m > 0 else None) for k, s, m in zip(("energy", "force", "virial"), sums, nrow)}
+    return dict(loss=loss, grad=grad_cfg.sum(0)[:C].cpu().numpy() if grad else None, grad_cfg=grad_cfg[:, :C] if grad else None,
+                rmse=rmse, energy=energy.cpu().numpy(), forces=forces.cpu().numpy(), virial=virial.cpu().numpy())
+
+
+def minimize_lbfgs(fun, theta0, mask=None, max_iter=200, history_size=20, tolerance_grad=1e-10, tolerance_change=0.0, max_ls=25):
+    """The optimiser of fit_full on its own (host only): torch.optim.LBFGS with the strong-Wolfe line search on a CPU
+    float64 tensor, one L-BFGS iteration (with up to max_ls line-search evaluations) per outer step so that the loss at the
+    start of every iteration is recorded; the optimiser's state (curvature pairs, step length) carries over between them.
+    fun(theta [C] numpy) -> (loss, grad [C] numpy); entries of the gradient where `mask` is False are zeroed (those
+    coefficients do not move).  Stops after max_iter iterations, or when the largest gradient entry at the start of an
+    iteration is at most tolerance_grad, or when the loss changed by at most tolerance_change over the last iteration.
+    Returns (theta [C], history: the loss at the start of every iteration and the loss at the returned theta)."""
+    import torch
+    p = torch.tensor(np.asarray(theta0, dtype=np.float64).reshape(-1), dtype=torch.float64, requires_grad=True)
+    keep = None if mask is None else torch.from_numpy(np.asarray(mask, dtype=np.float64))
+    opt = torch.optim.LBFGS([p], lr=1.0, max_iter=1, max_eval=int(max_ls) + 1, history_size=history_size, tolerance_grad=0.0,
+                            tolerance_change=0.0, line_search_fn="strong_wolfe")
+    seen = []                                                 # (loss, largest gradient entry) of this step's evaluations
+
+    def closure():
+        opt.zero_grad()
+        loss, g = fun(p.detach().numpy().copy())
+        g = torch.from_numpy(np.asarray(g, dtype=np.float64).reshape(-1).copy())
+        p.grad = g if keep is None else g * keep
+        seen.append((float(loss), float(p.grad.abs().max())))
+        return torch.tensor(float(loss), dtype=torch.float64)
+
+    history = []
+    for _ in range(int(max_iter)):
+        del seen[:]
+        history.append(float(opt.step(closure)))
+        if seen[0][1] <= tolerance_grad or (len(history) > 1 and abs(history[-2] - history[-1]) <= tolerance_change):
+            break
+    theta = p.detach().numpy().copy()
+    history.append(float(fun(theta)[0]))
+    return theta, history
+
+
+def fit_full(ctx, configs, labels, weights=(1.0, 0.01, 0.001), theta0=None, fit=("radial", "species", "moments"), max_iter=200,
+             out_path=None, list_cutoff=7.0, max_atoms_per_pass=None, history_size=20, tolerance_grad=1e-10, tolerance_change=0.0,
+             device=None):
+    """Non-linear training: ALL coefficients -- the radial block included -- fitted to reference energies, forces and
+    virials by L-BFGS (minimize_lbfgs) on the loss of loss_cells, whose closure is one loss_cells call on the device.
+    labels and weights as for fit_linear; theta0 [C] in candidate-vector order (None: the potential's coefficients); `fit`
+    names the blocks that move, the gradient of the others is zeroed.
+
+    Returns dict(theta [C], radial_coeffs [Sp, Sp, Mu, R], species_coeffs, moment_coeffs, history: the loss at the start of
+    every iteration and at the end, rmse_before, rmse_after) and, with out_path, writes the potential file through
+    capi.write_all_coeffs ("wrote" = its return value).  The context keeps its old coefficients, as after fit_linear:
+    reload the written file."""
+    unknown = set(fit) - {"radial", "species", "moments"}
+    if unknown:
+        raise ValueError("fit_full: unknown block(s) %s" % sorted(unknown))
+    info = ctx.pot.info
+    Sp, S = int(info.species_count), int(info.alpha_scalar_count)
+    Mu, R = int(info.radial_func_count), int(info.radial_basis_size)
+    nrad = Sp * Sp * Mu * R
+    theta0 = ctx.pot.theta() if theta0 is None else np.ascontiguousarray(theta0, dtype=np.float64).reshape(-1)
+    mask = np.concatenate([np.full(nrad, "radial" in fit), np.full(Sp, "species" in fit), np.full(S, "moments" in fit)])
+    kw = dict(weights=weights, list_cutoff=list_cutoff, max_atoms_per_pass=max_atoms_per_pass, device=device)
+    before = loss_cells(ctx, configs, labels, theta=theta0, grad=False, **kw)
+
+    def fun(theta):
+        r = loss_cells(ctx, configs, labels, theta=theta, **kw)
+        return r["loss"], r["grad"]
+
+    theta, history = minimize_lbfgs(fun, theta0, mask, max_iter, history_size, tolerance_grad, tolerance_change)
+    after = loss_cells(ctx, configs, labels, theta=theta, grad=False, **kw)
+    res = dict(theta=theta, radial_coeffs=theta[:nrad].reshape(Sp, Sp, Mu, R).copy(), species_coeffs=theta[nrad:nrad + Sp].copy(),
+               moment_coeffs=theta[nrad + Sp:].copy(), history=history, rmse_before=before["rmse"], rmse_after=after["rmse"])
+    if out_path is not None:
+        res["wrote"] = capi.write_all_coeffs(ctx.pot.path, out_path, res["moment_coeffs"], res["species_coeffs"], res["radial_coeffs"])
+    return res

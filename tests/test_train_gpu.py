@@ -1,0 +1,424 @@
+"""The training gradient on the device (csrc/mtp_train.hip; Context.train_value, Context.train_vjp, md.loss_cells,
+md.fit_full).  Every entry is judged against the numpy twin (driver.train_twin, itself judged against the oracle's
+finite differences in tests/test_train_cpu.py): values with the rule of tests/_batch.close, rows of the gradient with the
+bound of _design.column_ratio, 1e-9 + 1e-10 max |column|, per block of columns."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _batch  # noqa: E402
+import _cells  # noqa: E402
+import _design  # noqa: E402
+import _mutate  # noqa: E402
+import _stars  # noqa: E402
+import _train  # noqa: E402
+from lammps_mtp_kokkos_amd import capi, md  # noqa: E402
+from lammps_mtp_kokkos_amd.driver import periodic_system_cell, train_twin  # noqa: E402
+
+POT = _design.POT
+
+
+def _device_stream():
+    import torch
+    dev = torch.device("cuda:0")
+    return dev, capi.use_private_torch_stream(dev).cuda_stream
+
+
+@functools.lru_cache(maxsize=None)
+def _pot(fname):
+    return capi.Potential(os.path.join(POT, fname))
+
+
+@functools.lru_cache(maxsize=None)
+def _ctx(fname):
+    return capi.Context(_pot(fname), 0)
+
+
+@functools.lru_cache(maxsize=None)
+def _tables(fname):
+    return _pot(fname).tables()
+
+
+def _two_species(cell3, seed):
+    pos, cell, types = cell3
+    return pos, cell, (1 + (np.random.default_rng(seed).random(len(pos)) < 0.4)).astype(np.int32)
+
+
+CELLS = dict(isolated=_design.isolated_cell, primitive=_cells.primitive_cell, cubic2=_cells.cubic2_cell,
+             replica16=_design.replica16_cell, compressed=_design.compressed_cell,
+             replica16_two=lambda: _two_species(_design.replica16_cell(), 4))
+
+
+@functools.lru_cache(maxsize=None)
+def _system(cell):
+    return periodic_system_cell(*CELLS[cell](), _cells.LIST_CUTOFF)
+
+
+def _perturbed_theta(fname, seed=2):
+    th = _pot(fname).theta()
+    return th * (1.0 + 0.05 * np.random.default_rng(seed).normal(size=len(th)))
+
+
+@functools.lru_cache(maxsize=None)
+def _twin(fname, cell):
+    """(theta, cotangents, twin) of one case: computed once, shared, never written to"""
+    s = _system(cell)
+    theta = _perturbed_theta(fname)
+    cots = _train.cotangents(s.nlocal, 7)
+    return theta, cots, train_twin(_tables(fname), s, theta, *cots)
+
+
+def _device_call(fname, s, theta, ebar, fbar, vbar, row_begin=0, row_count=None, pad=0, value=True, vjp=True):
+    """Context.train_value / train_vjp over rows of a driver.System installed as a host list, the owner map given"""
+    import torch
+    dev, stream = _device_stream()
+    ctx = _ctx(fname)
+    C = len(theta)
+    ld = C + (C & 1) + pad
+    n = s.nlocal
+    nrows = n - row_begin if row_count is None else row_count
+    ctx.set_neighbors(s.ilist, s.first, s.neigh, s.nall)
+    to = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x_t, t_t, th_t = to(s.x), to(s.types), to(theta)
+    own_t = to(np.asarray(s.owner, dtype=np.int32))
+    out = {}
+    if value:
+        force = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        eatom = torch.full((nrows,), 7.0, dtype=torch.float64, device=dev)
+        vatom = torch.full((nrows, 6), 7.0, dtype=torch.float64, device=dev)
+        ctx.train_value(row_begin, nrows, x_t, t_t, th_t, force, n, eatom_t=eatom, vatom_t=vatom, owner=own_t.data_ptr(), stream=stream)
+        ctx.synchronize(stream=stream)
+        out.update(eatom=eatom.cpu().numpy(), force=force.cpu().numpy(), vatom=vatom.cpu().numpy())
+    if vjp:
+        rows = torch.full((nrows, ld), 7.0, dtype=torch.float64, device=dev)
+        sl = slice(row_begin, row_begin + nrows)
+        ctx.train_vjp(row_begin, nrows, x_t, t_t, th_t, rows, n, ld, ebar_t=to(None if ebar is None else ebar[sl]), fbar_t=to(fbar),
+                      vbar_t=to(None if vbar is None else vbar[sl]), owner=own_t.data_ptr(), stream=stream)
+        ctx.synchronize(stream=stream)
+        r = rows.cpu().numpy()
+        assert not r[:, C:].any(), "padding columns must be zero"
+        out.update(rows=r[:, :C])
+    return out
+
+
+def _check_rows(fname, got, want, what):
+    info = _ctx(fname).pot.info
+    Sp = info.species_count
+    nrad = Sp * Sp * info.radial_func_count * info.radial_basis_size
+    assert np.isfinite(got).all()
+    ratio = _train.block_ratio(got, want, nrad, Sp, what)
+    assert ratio <= 1.0, "%s: misses 1e-9 + 1e-10 max|column| %.2f-fold" % (what, ratio)
+
+
+CASES = [("W_L8.mtp", "isolated"), ("W_L8.mtp", "primitive"), ("W_L8.mtp", "cubic2"), ("W_L8.mtp", "replica16"),
+         ("W_L16.mtp", "replica16"), ("W_L16.mtp", "compressed"), ("WRe_L10_cfg.almtp", "replica16_two"),
+         ("WRe_L20.mtp", "replica16_two")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fname,cell", CASES)
+def test_value_and_gradient_rows_against_the_twin(fname, cell):
+    s = _system(cell)
+    theta, (ebar, fbar, vbar), tw = _twin(fname, cell)
+    got = _device_call(fname, s, theta, ebar, fbar, vbar)
+    _batch.close(got["eatom"], tw["eatom"], "%s %s eatom" % (fname, cell), atol=1e-10)
+    _batch.close(got["force"], tw["force"], "%s %s force" % (fname, cell))
+    _batch.close(got["vatom"], tw["vatom"], "%s %s vatom" % (fname, cell), atol=1e-8)
+    _check_rows(fname, got["rows"], tw["rows"], "%s %s rows" % (fname, cell))
+    nrad = len(_tables(fname)["radial_coeffs"])
+    if cell == "isolated":                                   # K = 0: ebar in the species column and nothing else
+        assert got["rows"][0, nrad] == ebar[0] and np.count_nonzero(got["rows"]) == 1
+        assert not got["force"].any() and not got["vatom"].any()
+    if cell == "primitive":                                  # every neighbour an image of the centre: no force, a virial
+        assert np.abs(got["force"]).max() <= 1e-12 and np.abs(got["vatom"]).max() > 1e-3
+
+
+@pytest.mark.gpu
+def test_row_range_padding_and_null_cotangents():
+    fname, cell = "W_L16.mtp", "replica16"
+    s = _system(cell)
+    theta, (ebar, fbar, vbar), tw = _twin(fname, cell)
+    got = _device_call(fname, s, theta, ebar, fbar, vbar, row_begin=5, row_count=7, pad=4)
+    _batch.close(got["eatom"], tw["eatom"][5:12], "eatom of rows 5..11", atol=1e-10)
+    _batch.close(got["vatom"], tw["vatom"][5:12], "vatom of rows 5..11", atol=1e-8)
+    _check_rows(fname, got["rows"], tw["rows"][5:12], "rows 5..11, ld = C + 4")
+    only = train_twin(_tables(fname), s, theta)              # forces of a row range: those rows' terms only
+    part = train_twin(_tables(fname), _rows_of(s, 5, 12), theta)
+    _batch.close(got["force"], part["force"], "force terms of rows 5..11")
+    assert np.abs(part["force"] - only["force"]).max() > 1e-3
+    z = np.zeros
+    n = s.nlocal
+    for name, cots, zero in (("ebar", (None, fbar, vbar), (z(n), fbar, vbar)), ("fbar", (ebar, None, vbar), (ebar, z((n, 3)), vbar)),
+                             ("vbar", (ebar, fbar, None), (ebar, fbar, z((n, 6))))):
+        got = _device_call(fname, s, theta, *cots, value=False)
+        _check_rows(fname, got["rows"], train_twin(_tables(fname), s, theta, *zero)["rows"], "NULL %s" % name)
+
+
+def _rows_of(s, a, b):
+    import copy
+    t = copy.copy(s)
+    t.ilist = s.ilist[a:b]
+    t.first = (s.first[a:b + 1] - s.first[a]).astype(np.int32)
+    t.neigh = s.neigh[s.first[a]:s.first[b]]
+    return _RowView(t, s.nlocal)
+
+
+class _RowView:
+    """a driver.System whose list holds some rows only, for the twin: outputs per listed row, forces over all owned atoms"""
+
+    def __init__(self, t, nlocal):
+        self.__dict__.update(t.__dict__)
+        self._n = nlocal
+
+    @property
+    def nlocal(self):
+        return self._n
+
+
+# ---- independent checks against existing device code ----------------------------------------------------------------------
+def _batch3():
+    return [_cells.cubic2_cell(), _batch.empty_cell(), _design.replica16_cell()]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fname", ["W_L16.mtp", "WRe_L20.mtp"])
+def test_value_at_the_files_theta_is_what_evaluate_cells_returns(fname):
+    dev, _ = _device_stream()
+    batch = _batch3() if fname == "W_L16.mtp" else [_two_species(_design.replica16_cell(), 4)]
+    ctx = _ctx(fname)
+    labels = [dict(energy=0.0, f=np.zeros((len(p), 3)), virial=np.zeros(6)) for p, _, _ in batch]
+    got = md.loss_cells(ctx, batch, labels, grad=False, device=dev)
+    res = md.evaluate_cells(ctx, batch, device=dev)
+    first = np.concatenate([[0], np.cumsum([len(p) for p, _, _ in batch])])
+    for k, r in enumerate(res):
+        _batch.close(got["forces"][first[k]:first[k + 1]], r["f"], "forces of configuration %d" % k)
+        _batch.close_energy(float(got["energy"][k]), r["energy"], len(r["f"]), "energy of configuration %d" % k)
+        _batch.close(got["virial"][k], r["virial"], "virial of configuration %d" % k, atol=1e-8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fname,cell", [("W_L16_nbh.almtp", "replica16"), ("WRe_L10_cfg.almtp", "replica16_two")])
+def test_unit_energy_cotangent_rows_are_the_candidate_vectors_of_a_grade_call(fname, cell):
+    s = _system(cell)
+    ctx = capi.Context(capi.Potential(os.path.join(POT, fname), selection=True), 0)
+    ctx.set_neighbors(s.ilist, s.first, s.neigh, s.nall)
+    ctx.compute(s.x, s.types, grade=True)
+    want = ctx.candidates()[:s.nlocal].cpu().numpy()
+    theta = ctx.pot.theta()
+    C = len(theta)
+    got = _device_call(fname, s, theta, np.ones(s.nlocal), None, None, value=False)
+    _check_rows(fname, got["rows"], want[:, :C], "%s: ebar = 1 rows against the candidate vectors" % fname)
+
+
+@pytest.mark.gpu
+def test_linear_columns_of_the_gradient_are_the_design_matrix_transposed():
+    """independent of the twin: the species and moment columns of grad are A^T (cotangents) with A from md.design_cells;
+    with no energy labels (ebar = 0) and with all three kinds"""
+    dev, _ = _device_stream()
+    fname = "W_L16.mtp"
+    ctx = _ctx(fname)
+    batch = _batch3()
+    orc_labels = _labels(fname, batch)
+    nrad = len(_tables(fname)["radial_coeffs"])
+    theta = _perturbed_theta(fname)
+    theta[:nrad] = _pot(fname).theta()[:nrad]                # (the design matrix is that of the context's radial coefficients)
+    d = md.design_cells(ctx, batch, device=dev)
+    A_e, A_f, A_v = d["energy"].cpu().numpy(), d["force"].cpu().numpy(), d["virial"].cpu().numpy()
+    nat = np.array([len(p) for p, _, _ in batch])
+    w = (1.0, 0.01, 0.001)
+    for drop_energy in (True, False):
+        labels = [dict(l, energy=None) if drop_energy else l for l in orc_labels]
+        got = md.loss_cells(ctx, batch, labels, theta=theta, weights=w, device=dev)
+        ce = np.array([0.0 if (l["energy"] is None or n == 0) else 2 * w[0] * (e - l["energy"]) / n ** 2
+                       for l, n, e in zip(labels, nat, got["energy"])])
+        cf = 2 * w[1] * (got["forces"] - np.concatenate([l["f"] for l in labels]))
+        cv = np.array([np.zeros(6) if n == 0 else 2 * w[2] * (v - l["virial"]) / n ** 2 for l, n, v in zip(labels, nat, got["virial"])])
+        want = A_e.T @ ce + A_f.T @ cf.reshape(-1) + np.einsum("kac,ka->c", A_v, cv)
+        # the bound: every entry of a design matrix is held to 1e-9 + 1e-10 max |column| of its kind (tests/_design.py), so
+        # A^T c is known to that times sum |c| per kind; the vjp rows are held to the same bound per atom (see _train.sum_ratio)
+        bound = sum((1e-9 + 1e-10 * np.abs(A).reshape(-1, A.shape[-1]).max(0)) * np.abs(c).sum()
+                    for A, c in ((A_e, ce), (A_f, cf), (A_v, cv)))
+        bound = 2.0 * bound + 1e-9 * nat.sum()
+        r = float((np.abs(got["grad"][nrad:] - want) / bound).max())
+        print("linear columns against design_cells^T (energy labels %s): worst error / bound %.3e" % (not drop_energy, r))
+        assert r <= 1.0 and np.abs(want).max() > 1e-3
+
+
+# ---- loss_cells ------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _oracle(fname):
+    from oracle.pyoracle import Oracle
+    return Oracle(os.path.join(POT, fname))
+
+
+def _labels(fname, batch):
+    """oracle labels; an empty configuration gets placeholders (it has no labelled row)"""
+    full = iter(_design.oracle_labels(_oracle(fname), [b for b in batch if len(b[0])]))
+    return [next(full) if len(p) else dict(energy=0.0, f=np.zeros((0, 3)), virial=np.zeros(6)) for p, _, _ in batch]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("split", [None, 1])
+def test_loss_cells_against_the_twin_with_an_empty_configuration_in_the_batch(split):
+    dev, _ = _device_stream()
+    fname = "W_L16.mtp"
+    batch = _batch3()
+    labels = _labels(fname, batch)
+    theta = _perturbed_theta(fname)
+    systems = [None if len(p) == 0 else periodic_system_cell(p, c, t, _cells.LIST_CUTOFF) for p, c, t in batch]
+    want = _train.twin_loss(_tables(fname), systems, labels, theta)
+    got = md.loss_cells(_ctx(fname), batch, labels, theta=theta, max_atoms_per_pass=split, device=dev)
+    print("loss %.12e (twin %.12e)" % (got["loss"], want["loss"]))
+    # the loss is a sum of w r^2: with every value held to the bounds of tests/_batch.py (energy 1e-10 per atom, forces
+    # 1e-9 + 1e-10 max |F|, virial 1e-8 + 1e-10 max |V|) it is held to sum 2 w |r| d
+    nat = np.array([len(p) for p, _, _ in batch])
+    keep = nat > 0
+    e_lab = np.array([l["energy"] for l in labels])
+    f_lab, v_lab = np.concatenate([l["f"] for l in labels]), np.array([l["virial"] for l in labels])
+    d_e = 1e-10 * np.maximum(1.0, np.abs(want["energy"][keep]) / nat[keep])
+    d_f = 1e-9 + 1e-10 * max(1.0, np.abs(want["forces"]).max())
+    d_v = 1e-8 + 1e-10 * max(1.0, np.abs(want["virial"]).max())
+    tol = 2.0 * ((np.abs(want["energy"] - e_lab)[keep] / nat[keep] * d_e).sum() + 0.01 * np.abs(want["forces"] - f_lab).sum() * d_f
+                 + 0.001 * (np.abs(want["virial"] - v_lab)[keep] / nat[keep, None] ** 2).sum() * d_v)
+    print("loss difference %.3e, bound %.3e" % (abs(got["loss"] - want["loss"]), tol))
+    assert abs(got["loss"] - want["loss"]) <= tol
+    gc = got["grad_cfg"].cpu().numpy()
+    assert gc.shape == want["grad_cfg"].shape and not gc[1].any()
+    assert max(_train.sum_ratio(gc[k], want["grad_cfg"][k], nat[k], want["row_absmax"], "grad_cfg[%d]" % k) for k in range(len(batch))) <= 1.0
+    assert _train.sum_ratio(got["grad"], want["grad"], nat.sum(), want["row_absmax"], "grad") <= 1.0
+    # the loss is the objective of solve_linear's scaling: sum of squared weighted residuals
+    obj = (((got["energy"][keep] - [l["energy"] for l, k in zip(labels, keep) if k]) / nat[keep]) ** 2).sum() \
+        + 0.01 * ((got["forces"] - np.concatenate([l["f"] for l in labels])) ** 2).sum() \
+        + 0.001 * (((got["virial"][keep] - np.array([l["virial"] for l, k in zip(labels, keep) if k])) / nat[keep, None]) ** 2).sum()
+    assert abs(got["loss"] - obj) <= 1e-12 * max(1.0, obj)
+    rm = got["rmse"]
+    assert abs(rm["force"] - np.sqrt(((got["forces"] - np.concatenate([l["f"] for l in labels])) ** 2).mean())) <= 1e-12
+
+
+# ---- fit_full --------------------------------------------------------------------------------------------------------------
+def _fit_batch():
+    """four jittered cells of 2 to 16 atoms"""
+    return [_cells.cubic2_cell(), _cells.tilted5_cell(1), _batch.sheared8_cell(1), _design.replica16_cell(5)]
+
+
+FIT_ITER = 30
+
+
+@pytest.mark.gpu
+def test_fit_full_level8_from_a_perturbed_radial_block(tmp_path):
+    """W_L8.mtp, labels from the oracle at the file's theta, start with the radial block scaled by 1 + 1e-2 N(0, 1), 30
+    L-BFGS iterations over all 26 coefficients.  The same optimiser driven by the numpy twin on the CPU takes the loss from
+    2.084e-3 to 9.89e-7 (recorded in DESIGN.md 5.3.2; it is computed again here, so the bound follows the test's own
+    inputs); L-BFGS paths diverge on rounding, hence the factor 10."""
+    dev, _ = _device_stream()
+    fname = "W_L8.mtp"
+    src = os.path.join(POT, fname)
+    batch = _fit_batch()
+    labels = _design.oracle_labels(_oracle(fname), batch)
+    theta0 = capi.Potential(src).theta()
+    nrad = len(_tables(fname)["radial_coeffs"])
+    theta0[:nrad] *= 1.0 + 1e-2 * np.random.default_rng(41).normal(size=nrad)
+    systems = [periodic_system_cell(p, c, t, _cells.LIST_CUTOFF) for p, c, t in batch]
+
+    def fun(theta):
+        r = _train.twin_loss(_tables(fname), systems, labels, theta)
+        return r["loss"], r["grad"]
+
+    _, cpu_hist = md.minimize_lbfgs(fun, theta0, None, FIT_ITER)
+    out = str(tmp_path / "full.mtp")
+    ctx = capi.Context(capi.Potential(src), 0)
+    res = md.fit_full(ctx, batch, labels, theta0=theta0, max_iter=FIT_ITER, out_path=out, device=dev)
+    h = res["history"]
+    print("fit_full: loss %.6e -> %.6e in %d iterations; twin on the CPU: %.6e -> %.6e in %d; rmse before %s after %s"
+          % (h[0], h[-1], len(h) - 1, cpu_hist[0], cpu_hist[-1], len(cpu_hist) - 1, res["rmse_before"], res["rmse_after"]))
+    assert all(b <= a for a, b in zip(h, h[1:])), "the loss history must be non-increasing"
+    assert h[-1] < h[0]
+    assert h[-1] <= 10.0 * cpu_hist[-1]
+    assert res["wrote"] == 0
+    back = capi.Potential(out)
+    np.testing.assert_array_equal(back.theta(), res["theta"])
+    fitted = md.loss_cells(ctx, batch, labels, theta=res["theta"], grad=False, device=dev)
+    ev = md.evaluate_cells(capi.Context(back, 0), batch, device=dev)
+    for k, r in enumerate(ev):
+        _batch.close_energy(r["energy"], float(fitted["energy"][k]), len(r["f"]), "energy of configuration %d from the written file" % k)
+
+
+# ---- error paths and untouched paths ---------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_train_error_paths(tmp_path):
+    import torch
+    dev, stream = _device_stream()
+    pot = capi.Potential(os.path.join(POT, "W_L8.mtp"))
+    ctx = capi.Context(pot, 0)
+    C = len(pot.theta())
+    st = _stars.stars([(3, 4), (2, 2)], np.random.default_rng(5))
+    x_t, t_t = torch.from_numpy(st.x).to(dev), torch.from_numpy(st.types).to(dev)
+    th_t = torch.from_numpy(pot.theta()).to(dev)
+    force = torch.zeros((st.nall, 3), dtype=torch.float64, device=dev)
+    rows = torch.zeros((2, C + 2), dtype=torch.float64, device=dev)
+    with pytest.raises(capi.MtpError) as ei:                                  # no list installed
+        ctx.train_value(0, 2, x_t, t_t, th_t, force, st.nall, stream=stream)
+    assert ei.value.code == -23
+    with pytest.raises(capi.MtpError) as ei:
+        ctx.train_vjp(0, 2, x_t, t_t, th_t, rows, st.nall, C, stream=stream)
+    assert ei.value.code == -23
+    ctx.set_neighbors(st.ilist, st.first, st.neigh, st.nall)
+    for ld in (C - 2, C + 1):                                                # too small, odd
+        with pytest.raises(capi.MtpError) as ei:
+            ctx.train_vjp(0, 2, x_t, t_t, th_t, rows, st.nall, ld, stream=stream)
+        assert ei.value.code == -20
+    with pytest.raises(capi.MtpError) as ei:                                  # rows outside the list
+        ctx.train_vjp(1, 2, x_t, t_t, th_t, rows, st.nall, C, stream=stream)
+    assert ei.value.code == -20
+    with pytest.raises(capi.MtpError) as ei:
+        ctx.train_value(1, 2, x_t, t_t, th_t, force, st.nall, stream=stream)
+    assert ei.value.code == -20
+    with pytest.raises(capi.MtpError) as ei:                                  # no force array, no theta
+        ctx.train_value(0, 2, x_t, t_t, th_t, None, st.nall, stream=stream)
+    assert ei.value.code == -20
+    with pytest.raises(capi.MtpError) as ei:
+        ctx.train_vjp(0, 2, x_t, t_t, None, rows, st.nall, C, stream=stream)
+    assert ei.value.code == -20
+    # a type outside the potential: the kernel skips the centre, the synchronise reports it, the message names the pass
+    pos, cell, types = _cells.cubic2_cell()
+    lab = lambda n: dict(energy=0.0, f=np.zeros((n, 3)), virial=np.zeros(6))
+    with pytest.raises(capi.MtpError, match="pass 2") as ei:
+        md.loss_cells(ctx, [_cells.primitive_cell(), (pos, cell, np.array([1, 2], dtype=np.int32))], [lab(1), lab(2)],
+                      max_atoms_per_pass=1, device=dev)
+    assert ei.value.code == -22
+    assert np.isfinite(md.loss_cells(ctx, [_cells.primitive_cell()], [lab(1)], device=dev)["loss"])   # the flag was cleared
+    # the refused table: nothing is launched
+    bad = str(tmp_path / "mutated.mtp")
+    _mutate.mutate_mtp(os.path.join(POT, "W_L16.mtp"), bad)
+    bctx = capi.Context(capi.Potential(bad), 0)
+    with pytest.raises(capi.MtpError, match="alpha_index_times") as ei:
+        md.loss_cells(bctx, [_cells.primitive_cell()], [lab(1)], device=dev)
+    assert ei.value.code == -6
+
+
+@pytest.mark.gpu
+def test_a_training_call_leaves_the_force_plan_alone():
+    """launch_info / plan_info / layout_mode of a context before and after its first training calls, and of one that never
+    makes one: the training table is uploaded lazily and shares nothing with the force kernel's plan or coefficients"""
+    import torch
+    dev, stream = _device_stream()
+    pot = capi.Potential(os.path.join(POT, "W_L16.mtp"))
+    st = _stars.stars([(5, 6), (33, 40)], np.random.default_rng(6))
+    a, b = capi.Context(pot, 0), capi.Context(pot, 0)
+    for c in (a, b):
+        c.set_neighbors(st.ilist, st.first, st.neigh, st.nall)
+    before = (a.launch_info(), a.plan_info(), a.layout_mode())
+    x_t, t_t = torch.from_numpy(st.x).to(dev), torch.from_numpy(st.types).to(dev)
+    th_t = torch.from_numpy(2.0 * pot.theta()).to(dev)       # (another theta: the context's coefficients must not move)
+    force = torch.zeros((st.nall, 3), dtype=torch.float64, device=dev)
+    rows = torch.zeros((2, 150), dtype=torch.float64, device=dev)
+    a.train_value(0, 2, x_t, t_t, th_t, force, st.nall, stream=stream)
+    a.train_vjp(0, 2, x_t, t_t, th_t, rows, st.nall, 150, ebar_t=torch.ones(2, dtype=torch.float64, device=dev), stream=stream)
+    a.synchronize(stream=stream)
+    assert (a.launch_info(), a.plan_info(), a.layout_mode()) == before == (b.launch_info(), b.plan_info(), b.layout_mode())
+    ra, rb = a.compute(st.x, st.types), b.compute(st.x, st.types)
+    assert np.array_equal(ra["eatom"], rb["eatom"]) and abs(ra["f"] - rb["f"]).max() <= 1e-12 * max(1.0, abs(rb["f"]).max())
