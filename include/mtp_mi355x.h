@@ -12,7 +12,8 @@
  * Streams.  Device work is ordered on the `stream` (a hipStream_t) given to an entry point.  ONE rule for NULL:
  *   - entry points that take a context (mtp_compute_device[_rows], mtp_build_neighbors_device,
  *     mtp_set_neighbors_device_2d, mtp_synchronize, mtp_halo_force_step, mtp_ghosts_reverse_finish,
- *     mtp_batch_cfg_grades, mtp_batch_cfg_candidates, mtp_maxvol_select, mtp_design_rows_device): NULL means the
+ *     mtp_batch_cfg_grades, mtp_batch_cfg_candidates, mtp_maxvol_select, mtp_design_rows_device, the installs and
+ *     mtp_context_coeff_tables_device): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
  *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce): NULL is
@@ -20,6 +21,17 @@
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
  * whose other GPU work runs on the default stream (PyTorch's default) must pass a real stream handle that its own
  * work is ordered on, or synchronise around the calls.
+ *
+ * Installs (mtp_context_install_coeffs, mtp_context_install_selection, mtp_context_install_file) rewrite, IN PLACE, device
+ * tables that every launch of the context reads.  Their ordering contract:
+ *   - an install is ordered after all earlier work on `stream` (NULL: the context's own stream, as above);
+ *   - it returns after that stream has drained -- ONE hipStreamSynchronize per call, whatever it installs -- so every later
+ *     launch of the context, on any stream, reads the new values;
+ *   - the caller's arrays are free on return;
+ *   - the caller must have NO launch of this context in flight on ANOTHER stream while it installs: nothing orders such a
+ *     launch against the copies, and it would read tables half old, half new.  A caller whose force calls are queued on
+ *     its own stream installs on that stream (or synchronises first); NULL is right only for work that ran on the
+ *     context's stream.
  */
 #ifndef MTP_MI355X_H
 #define MTP_MI355X_H
@@ -31,7 +43,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 7
+#define MTP_MI355X_ABI_VERSION 8
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -475,19 +487,19 @@ int mtp_context_candidates_device(const mtp_context *ctx, const double **d_rows,
 int mtp_batch_cfg_candidates(mtp_context *ctx, void *stream, int ncfg, const int *d_cfg_first, int nrows,
                              const double **d_rows, int *ld);
 /* MaxVol over a pool of nrows candidate vectors d_rows[nrows][ld] (device, the first C of each row used), starting from
- * the potential's S and W: while some |G[i][j]| exceeds `threshold`, the largest one (ties to the smaller n * C + j) is
+ * the context's S and W (the potential's until an install): while some |G[i][j]| exceeds `threshold`, the largest one (ties to the smaller n * C + j) is
  * swapped in.  Per swap one pivot kernel and one pass over the (C + nrows) x cpad stacked matrix run on `stream`; the host
  * reads a 16-byte status once per 16 swaps.  Every `refresh` swaps, and always before the call ends, G is recomputed from
  * the pool and the current W: *converged = 1 only when freshly computed grades hold no entry above the threshold, and
- * *max_grade_after is their maximum -- what a later grade call with the written file reports.  The context's own inverse
- * is NOT changed: selection is followed by a reload of the written file, as in the MLIP loop.
+ * *max_grade_after is their maximum -- what a later grade call with the new set reports.  The context's own inverse
+ * is NOT changed by the call: selection is followed by mtp_context_install_selection, or by a reload of the written file.
  *   active_set, inverse_active_set [C*C]  S' and W' (host); every changed column of S' is a pool row bit for bit
  *   slot_source [C]                      the pool row now in slot j, -1 where the original column was kept
  *   swap_rows, swap_slots, swap_pivots   [max_swaps] the log: swap k put row i into slot j with pivot p
  *   log_volume_gain                      sum log |p| = log |det S'| - log |det S|
  * NULL stream = the context's.  MTP_ERR_STATE without a selection block; MTP_ERR_ARG for threshold < 1, ld < C,
  * max_swaps < 0, refresh < 1 (nothing launched), and for a non-finite candidate: the outputs then describe the state
- * before the offending pivot.  nrows == 0 is valid: zero swaps, outputs equal to the potential's blocks bit for bit.
+ * before the offending pivot.  nrows == 0 is valid: zero swaps, outputs equal to the context's blocks bit for bit.
  * Reaching max_swaps is no error: *converged = 0 and the outputs are the state reached.  The device memory of a call
  * ((C + nrows) x cpad doubles and a little more) is the context's and is kept for the next one; MTP_ERR_LIMIT when it
  * cannot be had. */
@@ -572,7 +584,7 @@ int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const
  *
  * theta [C] holds every coefficient in candidate-vector order: radial [Sp][Sp][Mu][R] | species [Sp] | moments [S],
  * C = Sp^2 Mu R + Sp + S.  It is a device vector of the caller's and is read by every call: a trainer steps theta without
- * reloading a potential, and the context's force tables keep the file's coefficients.  The model is not linear in the
+ * reloading a potential, and the context's force tables keep their coefficients until mtp_context_install_coeffs.  The model is not linear in the
  * radial block, so the gradient is produced in reverse: for cotangents ebar (per atom), fbar (per owned atom) and vbar
  * (per atom, six components)
  *     grad = d/dtheta [ sum_i ebar_i eatom_i + sum_j fbar_j . F_j + sum_i vbar_i . vatom_i ],   F the folded force,
@@ -618,6 +630,70 @@ int mtp_potential_train_table(const mtp_potential *pot, int32_t *counts, int32_t
 int mtp_potential_write_all_coeffs(const char *src_path, const char *dst_path, const double *radial_coeffs /*[Sp^2 Mu R] or NULL*/,
                                    const double *species_coeffs /*[Sp] or NULL*/, const double *moment_coeffs /*[S]*/,
                                    int radial_count, int species_count, int scalar_count, char *err, int errlen);
+
+/* ---- installing new coefficients and a new active set into a LIVE context ------------------------------------------
+ *
+ * The native schedule of a potential (dependency levels, LDS numbering, gather programs, head x tail blocks) is a
+ * function of its alpha tables only; the coefficient values enter a context through a handful of small device arrays
+ * (DESIGN.md 5.3.3).  A context keeps its own host copy of {radial, species, moment coefficients, S, W}, initialised from
+ * the potential it was created on, and from then on that copy is the only source of values for what the context does; the
+ * potential itself is const, may be shared by several contexts and is never written.  An install rewrites every device
+ * copy of the values and nothing else: no re-plan, no allocation of launch state, the same kernels afterwards.
+ *
+ * All arguments of an install are validated before the first byte is written: a refused install leaves the context
+ * exactly as it was.  The ordering contract of an install (after earlier work on `stream`, one wait, the caller's arrays
+ * free on return, no launch of the context in flight on another stream) stands in the Streams paragraph at the top.
+ *
+ * A coefficient change makes the columns of the installed active set stale (candidate vectors depend on the
+ * coefficients); rebuilding the set is the caller's selection step, not something an install does.
+ */
+/* The coefficient-dependent tables of the native schedule for a (radial, species, moment) triple on the FIXED structure of
+ * `pot` (host only): arrays in the sizes and order of mtp_potential_write_all_coeffs, NULL = the potential's own values.
+ * counts[6] = lengths of radial_out, species_out, seed_val, e_lin, leaf_cf, leaf_cb (seed_val: the last scalar mapped to a
+ * stored moment; e_lin: the scalars of stored moments; leaf_cf / leaf_cb: per leaf row mult x the sum of the coefficients
+ * mapped to the leaf moment, respectively the last one).  Any output may be NULL.  MTP_ERR_ARG for non-finite input. */
+int mtp_potential_coeff_tables(const mtp_potential *pot, const double *radial_coeffs, const double *species_coeffs,
+                               const double *moment_coeffs, int32_t *counts /*[6]*/, double *radial_out, double *species_out,
+                               double *seed_val, double *e_lin, double *leaf_cf, double *leaf_cb);
+/* MTP_OK when the file at `path` (read by the text parser: no schedule is built) equals `pot` in everything the schedule
+ * and the kernels' argument block were built from: scaling, both cutoffs, species_count, radial_basis_size,
+ * radial_funcs_count, every alpha count and the three alpha tables entry by entry (the parser accepts one radial basis
+ * type only) and, with want_selection != 0, coeff_count and the selection mode.  Otherwise MTP_ERR_UNSUPPORTED, err names the
+ * first difference; the parser's codes for a file that does not read. */
+int mtp_potential_compatible(const mtp_potential *pot, const char *path, int want_selection, char *err, int errlen);
+/* New coefficients (HOST arrays; NULL keeps that block): the radial block and the scalar-side tables in the LDS table blob,
+ * in place at their recorded offsets, their HBM / L2 copies, the species coefficients and, if a design call has uploaded
+ * it, the design kernel's radial block.  MTP_ERR_ARG for non-finite values.  MTP_ERR_UNSUPPORTED when the context was
+ * created on values for which every leaf row's energy and adjoint constants are equal -- the blob then holds ONE table for
+ * both -- and the new values make them differ (two scalars on one leaf moment whose first coefficient was zero). */
+int mtp_context_install_coeffs(mtp_context *ctx, void *stream, const double *radial_coeffs /*[Sp^2 Mu R] or NULL*/,
+                               const double *species_coeffs /*[Sp] or NULL*/, const double *moment_coeffs /*[S] or NULL*/);
+/* New S and W = S^-1 ([C*C] host arrays, both required): the padded and the MFMA-ordered copy of W on the device, and the
+ * context's S, W.  MTP_ERR_STATE when the context's potential was loaded without its selection state, MTP_ERR_ARG for a
+ * coeff_count that is not the potential's and for non-finite entries. */
+int mtp_context_install_selection(mtp_context *ctx, void *stream, const double *active_set, const double *inverse_active_set,
+                                  int coeff_count);
+/* The gate of mtp_potential_compatible, then the file's coefficients and -- one wait for both -- the file's selection.  The
+ * file is read with the context's selection wish; where the context has a selection state and the file has NO #MVS tail at
+ * all (what the coefficient writers leave), the coefficients alone are installed and the context keeps its set.  A tail
+ * that is there but does not read (wrong version, a weight line missing, short blocks) is MTP_ERR_SELECTION / MTP_ERR_IO
+ * and nothing is installed. */
+int mtp_context_install_file(mtp_context *ctx, void *stream, const char *path);
+/* the context's current values (host copies; any pointer may be NULL); get_selection: MTP_ERR_STATE without one */
+int mtp_context_get_coeffs(const mtp_context *ctx, double *radial_coeffs, double *species_coeffs, double *moment_coeffs);
+int mtp_context_get_selection(const mtp_context *ctx, double *active_set, double *inverse_active_set);
+/* What the kernels will read, copied back from DEVICE memory (ordered on `stream`, waited for).  counts[10] = doubles of
+ * {radial, seed_val, e_lin, leaf_cf, leaf_cb, species, design radial, ainv_pad, ainv_tiled, scalars_in_lds}: the radial
+ * block and the four scalar-side tables as they stand in the blob (blob_seed_val / blob_e_lin: only when scalars_in_lds,
+ * else nothing is written), the same four from the separate HBM copies, d_species, the design kernel's radial block (count
+ * 0 before the first design call) and the two copies of W (0 without a selection state).  With every output NULL the call
+ * only fills counts. */
+int mtp_context_coeff_tables_device(mtp_context *ctx, void *stream, int32_t *counts /*[10]*/, double *blob_radial,
+                                    double *blob_seed_val, double *blob_e_lin, double *blob_leaf_cf, double *blob_leaf_cb,
+                                    double *hbm_seed_val, double *hbm_e_lin, double *hbm_leaf_cf, double *hbm_leaf_cb,
+                                    double *species, double *design_radial, double *ainv_pad, double *ainv_tiled);
+/* mtp_cfg_grade on the context's W */
+int mtp_context_cfg_grade(const mtp_context *ctx, const double *coeff_ders, double *grade);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,9 @@ EXPORTS = [
     "mtp_design_rows_device", "mtp_ghosts_owner_device", "mtp_batch_design_reduce", "mtp_potential_design_table",
     "mtp_potential_write_coeffs",
     "mtp_train_value_device", "mtp_train_vjp_device", "mtp_potential_train_table", "mtp_potential_write_all_coeffs",
+    "mtp_potential_coeff_tables", "mtp_potential_compatible", "mtp_context_install_coeffs", "mtp_context_install_selection",
+    "mtp_context_install_file", "mtp_context_get_coeffs", "mtp_context_get_selection", "mtp_context_coeff_tables_device",
+    "mtp_context_cfg_grade",
 ]
 WROTE_WITHOUT_SELECTION = 1   # mtp_potential_write_coeffs: the source's #MVS tail was left out
 # mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
@@ -246,6 +249,45 @@ class Potential:
         """the file's coefficients as one [C] vector in candidate-vector order [radial | species | moments]"""
         t = self.tables()
         return np.concatenate([t["radial_coeffs"], t["species_coeffs"], t["moment_coeffs"]])
+
+    def coeff_tables(self, radial_coeffs=None, species_coeffs=None, moment_coeffs=None):
+        """the coefficient-dependent tables of the native schedule for the given blocks on this potential's structure (None:
+        the file's own values), host only: dict(radial, species, seed_val, e_lin, leaf_cf, leaf_cb) -- what a context
+        created on a file with these values uploads (mtp_potential_coeff_tables).  Non-finite input: MtpError(ARG)."""
+        i = self.info
+        want = (i.species_count ** 2 * i.radial_func_count * i.radial_basis_size, i.species_count, i.alpha_scalar_count)
+        arrs = []
+        for a, n, name in zip((radial_coeffs, species_coeffs, moment_coeffs), want, ("radial", "species", "moment")):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a is not None and len(a) != n:
+                raise MtpError(-20, "coeff_tables: %d %s coefficients given, the potential has %d" % (len(a), name, n))
+            arrs.append(a)
+        cnt = np.zeros(6, np.int32)
+        rc = lib().mtp_potential_coeff_tables(self.h, *[_np(a, C.c_double) for a in arrs], _np(cnt, C.c_int32),
+                                              None, None, None, None, None, None)
+        if rc:
+            raise MtpError(rc, "coeff_tables: a coefficient is not finite")
+        names = ("radial", "species", "seed_val", "e_lin", "leaf_cf", "leaf_cb")
+        out = {n: np.zeros(int(k)) for n, k in zip(names, cnt)}
+        rc = lib().mtp_potential_coeff_tables(self.h, *[_np(a, C.c_double) for a in arrs], None,
+                                              *[_np(out[n], C.c_double) for n in names])
+        if rc:
+            raise MtpError(rc, "coeff_tables")
+        return out
+
+    def compatible(self, path, selection=None):
+        """None when the file at `path` has this potential's structure -- everything the native schedule and the kernels'
+        argument block were built from -- so that a context of this potential can install it; otherwise the message that
+        names the first difference (mtp_potential_compatible).  selection (default: as this potential was loaded) also
+        compares coeff_count and the selection mode.  A file that does not parse raises."""
+        sel = bool(self.info.has_selection) if selection is None else bool(selection)
+        err = C.create_string_buffer(512)
+        rc = lib().mtp_potential_compatible(self.h, os.fsencode(path), int(sel), err, 512)
+        if rc == -6:
+            return err.value.decode()
+        if rc:
+            raise MtpError(rc, err.value.decode())
+        return None
 
     def kernel_shape(self):
         """the force kernel instantiation a context of this potential launches (mtp_potential_kernel_shape)"""
@@ -463,7 +505,7 @@ class Context:
 
     def maxvol_select(self, rows_t, threshold, max_swaps=None, refresh=64, stream=None):
         """MaxVol over the pool rows_t [N, ld] (fp64 device tensor, rows ld >= C doubles apart, the first C used), starting
-        from the potential's active set: mtp_maxvol_select.  max_swaps defaults to 4 C.  Returns dict(active_set,
+        from the context's active set (the potential's until install_selection): mtp_maxvol_select.  max_swaps defaults to 4 C.  Returns dict(active_set,
         inverse_active_set [C, C], slot_source [C], swaps [(row, slot, pivot)], nswaps, converged, log_volume_gain,
         max_grade_after).  A non-finite candidate raises MtpError(ARG) whose .result is that dict for the state before the
         offending pivot."""
@@ -494,6 +536,128 @@ class Context:
             e.result = out
             raise e
         return out
+
+    # ---- installs: new values into this live context (include/mtp_mi355x.h, "installing ...") -------------------------
+    # The ordering contract of all three (include/mtp_mi355x.h, "Streams"): an install is ordered after all earlier work on
+    # `stream` (None: the context's own non-blocking stream); it returns after that stream has drained (one wait per call);
+    # the arrays handed over are free on return; and the caller must have NO launch of this context in flight on ANOTHER
+    # stream -- nothing orders such a launch against the in-place copies.  With torch work queued on a stream of the
+    # caller's, pass that stream's handle (or synchronise first).
+    def _sizes3(self):
+        i = self.pot.info
+        return (i.species_count ** 2 * i.radial_func_count * i.radial_basis_size, i.species_count, i.alpha_scalar_count)
+
+    def install_coeffs(self, radial_coeffs=None, species_coeffs=None, moment_coeffs=None, stream=None):
+        """New coefficients (host arrays in the file's order, any shape; None keeps that block) into every device table the
+        kernels read; no re-plan, the same kernels afterwards: mtp_context_install_coeffs.  Ordered after earlier work on
+        `stream`, returns after it has drained, the arrays are free on return; no launch of this context may be in flight
+        on another stream (the contract above).  All arguments are checked before anything is written: wrong lengths and
+        non-finite values raise MtpError(ARG) and leave the context as it was.  The installed active set's columns were
+        candidate vectors of the OLD coefficients: rebuilding it is a select_cells call, not part of an install."""
+        arrs = []
+        for a, n, name in zip((radial_coeffs, species_coeffs, moment_coeffs), self._sizes3(), ("radial", "species", "moment")):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a is not None and len(a) != n:
+                raise MtpError(-20, "install_coeffs: %d %s coefficients given, the potential has %d" % (len(a), name, n))
+            arrs.append(a)
+        self._check(lib().mtp_context_install_coeffs(self.h, C.c_void_p(stream) if stream else None,
+                                                     *[_np(a, C.c_double) for a in arrs]))
+
+    def install_selection(self, active_set, inverse_active_set, stream=None):
+        """A new active set S and its inverse W ([C, C] host arrays) into the grade kernels' two copies of W and the start of
+        the next maxvol_select: mtp_context_install_selection.  Stream ordering as for install_coeffs: after earlier work
+        on `stream`, one wait, arrays free on return, no launch of this context in flight on another stream.  MtpError(STATE) when the potential was loaded without its
+        selection state, MtpError(ARG) for a wrong size or non-finite entries; the context is then unchanged."""
+        S = np.ascontiguousarray(active_set, dtype=np.float64)
+        W = np.ascontiguousarray(inverse_active_set, dtype=np.float64)
+        C_ = int(self.pot.info.coeff_count)
+        n = int(S.shape[0]) if S.ndim == 2 and S.shape[0] == S.shape[1] and W.shape == S.shape else -1
+        if n < 0 and self.pot.info.has_selection:
+            raise MtpError(-20, "install_selection: active_set and inverse_active_set must be [%d, %d]" % (C_, C_))
+        self._check(lib().mtp_context_install_selection(self.h, C.c_void_p(stream) if stream else None, _np(S, C.c_double),
+                                                        _np(W, C.c_double), n))
+
+    def install_file(self, path, stream=None):
+        """The coefficients of the file at `path` and, if this context has a selection state and the file carries one, its
+        active set, with one wait for both: mtp_context_install_file.  Stream ordering as for install_coeffs (no launch of
+        this context in flight on another stream).  A file with no #MVS tail at all installs its coefficients only; a tail
+        that does not read is the parser's error and nothing is installed.  MtpError(UNSUPPORTED) naming the first difference when the file's structure
+        (Potential.compatible) is not this potential's -- such a file needs a new Potential and Context."""
+        self._check(lib().mtp_context_install_file(self.h, C.c_void_p(stream) if stream else None, os.fsencode(path)))
+
+    def coeffs(self):
+        """the context's current coefficients: dict(radial_coeffs, species_coeffs, moment_coeffs), flat host arrays"""
+        out = [np.zeros(n) for n in self._sizes3()]
+        self._check(lib().mtp_context_get_coeffs(self.h, *[_np(a, C.c_double) for a in out]))
+        return dict(radial_coeffs=out[0], species_coeffs=out[1], moment_coeffs=out[2])
+
+    def theta(self):
+        """the context's current coefficients as one [C] vector in candidate-vector order [radial | species | moments]: the
+        file's until an install (Potential.theta() stays the file's)"""
+        c = self.coeffs()
+        return np.concatenate([c["radial_coeffs"], c["species_coeffs"], c["moment_coeffs"]])
+
+    def selection(self):
+        """the context's current (active_set S, inverse_active_set W), [C, C] each: mtp_context_get_selection"""
+        C_ = int(self.pot.info.coeff_count)
+        S, W = np.zeros((C_, C_)), np.zeros((C_, C_))
+        rc = lib().mtp_context_get_selection(self.h, _np(S, C.c_double), _np(W, C.c_double))
+        if rc:
+            raise MtpError(rc, "selection: the potential was loaded without its selection state")
+        return S, W
+
+    def cfg_grade(self, coeff_ders):
+        """configuration-mode grade max_i |sum_j W[i][j] c_j| on the context's W: mtp_context_cfg_grade"""
+        g = C.c_double(0)
+        c = np.ascontiguousarray(coeff_ders, dtype=np.float64)
+        rc = lib().mtp_context_cfg_grade(self.h, _np(c, C.c_double), C.byref(g))
+        if rc:
+            raise MtpError(rc, "cfg_grade")
+        return g.value
+
+    def coeff_tables_device(self, stream=None):
+        """what the kernels will read, copied back from device memory (mtp_context_coeff_tables_device): dict of host arrays
+        blob_radial, blob_seed_val, blob_e_lin (None unless scalars_in_lds), blob_leaf_cf, blob_leaf_cb, hbm_seed_val,
+        hbm_e_lin, hbm_leaf_cf, hbm_leaf_cb, species, design_radial (None before the first design call), ainv_pad, ainv_tiled
+        (None without a selection state), plus scalars_in_lds"""
+        st = C.c_void_p(stream) if stream else None
+        cnt = np.zeros(10, np.int32)
+        self._check(lib().mtp_context_coeff_tables_device(self.h, st, _np(cnt, C.c_int32), *([None] * 13)))
+        n_rad, n_seed, n_lin, n_cf, n_cb, n_sp, n_dr, n_pad, n_til, in_lds = [int(v) for v in cnt]
+        names = ("blob_radial", "blob_seed_val", "blob_e_lin", "blob_leaf_cf", "blob_leaf_cb", "hbm_seed_val", "hbm_e_lin",
+                 "hbm_leaf_cf", "hbm_leaf_cb", "species", "design_radial", "ainv_pad", "ainv_tiled")
+        sizes = (n_rad, n_seed if in_lds else None, n_lin if in_lds else None, n_cf, n_cb, n_seed, n_lin, n_cf, n_cb, n_sp,
+                 n_dr or None, n_pad or None, n_til or None)
+        out = {n: (None if k is None else np.zeros(k)) for n, k in zip(names, sizes)}
+        self._check(lib().mtp_context_coeff_tables_device(self.h, st, None, *[_np(out[n], C.c_double) for n in names]))
+        out["scalars_in_lds"] = bool(in_lds)
+        return out
+
+    def save(self, dst):
+        """Writes the potential file of the context's CURRENT state to `dst` through the existing writers: the source file
+        (Potential.path) supplies the structure, write_all_coeffs the three coefficient blocks and, for a potential loaded
+        with its selection state, write_selection the two raw blocks behind the source's #MVS header lines.  A Context
+        created on `dst` holds bit for bit the tables this one holds."""
+        c = self.coeffs()
+        dst = os.fspath(dst)
+        if not self.pot.info.has_selection:
+            write_all_coeffs(self.pot.path, dst, c["moment_coeffs"], c["species_coeffs"], c["radial_coeffs"])
+            return
+        S, W = self.selection()
+        tmp_sel, tmp_txt = dst + ".sel%d" % os.getpid(), dst + ".txt%d" % os.getpid()
+        try:
+            write_selection(self.pot.path, tmp_sel, S, W)           # the source's text, '#', the new blocks
+            write_all_coeffs(tmp_sel, tmp_txt, c["moment_coeffs"], c["species_coeffs"], c["radial_coeffs"])   # new text, no tail
+            data = open(tmp_sel, "rb").read()
+            k = data.find(b"#MVS_v1.1")
+            k = data.rfind(b"\n", 0, k) + 1                         # (the writer ends its file at the start of that line)
+            with open(tmp_txt, "ab") as f:
+                f.write(data[k:])
+            os.replace(tmp_txt, dst)
+        finally:
+            for t in (tmp_sel, tmp_txt):
+                if os.path.exists(t):
+                    os.remove(t)
 
     def last_shape(self):
         """name of the fixed-shape kernel the last force launch ran, "" for a generic kernel"""

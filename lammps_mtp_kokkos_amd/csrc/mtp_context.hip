@@ -138,6 +138,10 @@ struct mtp_context {
   DevBuf<int32_t> d_train_ints;      // level offsets | basic descriptors | scalar map | basics by mu | mu offsets
   MtpTrainParams train{};
 
+  // The context's own values (include/mtp_mi355x.h, "installing ..."): initialised from the potential, replaced by the
+  // installs, and the only source of values for what the context does after its creation -- `pot` is read for structure.
+  std::vector<double> h_radial, h_species, h_moments, h_active_set, h_inverse;
+
   MtpDevParams base{};
   const char *last_shape = "";   // name of the fixed-shape kernel the last force launch ran ("": a generic kernel)
 
@@ -514,6 +518,40 @@ void fill_sizes(const mtp_potential &pot, MtpDevParams &b)
   b.Se = (int) pot.e_map.size();
 }
 
+// W [C][C] zero padded to [cpad][cpad] for the MFMA grade kernel, and the same matrix in MFMA operand order for the
+// LDS-staged grade kernel: [tile][k-step][lane], lane (j = l & 15, k = l >> 4) <- Ainv[16 tile + j][4 kstep + k]
+void pad_and_tile(const double *W, int C, int cpad, std::vector<double> &pad, std::vector<double> &tiled)
+{
+  pad.assign((size_t) cpad * cpad, 0.0);
+  for (int r = 0; r < C; r++) std::memcpy(&pad[(size_t) r * cpad], &W[(size_t) r * C], (size_t) C * sizeof(double));
+  tiled.assign((size_t) cpad * cpad, 0.0);
+  const int ks_n = cpad / 4;
+  for (int t = 0; t < cpad / 16; t++)
+    for (int ks = 0; ks < ks_n; ks++)
+      for (int l = 0; l < 64; l++)
+        tiled[((size_t) t * ks_n + ks) * 64 + l] = pad[(size_t) (16 * t + (l & 15)) * cpad + 4 * ks + (l >> 4)];
+}
+
+// calculate_extrapolation_grade for configuration mode (mtp_cfg_grade, mtp_context_cfg_grade)
+double cfg_grade_of(const double *W, int C, const double *c)
+{
+  double mx = 0.0;
+  for (int i = 0; i < C; i++) {
+    const double *row = &W[(size_t) i * C];
+    double g = 0.0;
+    for (int j = 0; j < C; j++) g += c[j] * row[j];
+    mx = std::max(mx, g < 0 ? -g : g);
+  }
+  return mx;
+}
+
+bool all_finite(const double *v, size_t n)   // (a null array is an argument left out)
+{
+  for (size_t i = 0; v && i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
 }   // namespace
 
 extern "C" {
@@ -659,15 +697,7 @@ int mtp_cfg_grade(const mtp_potential *p, const double *c, double *grade)
 {
   if (!p || !c || !grade) return MTP_ERR_ARG;
   if (!p->has_selection) return MTP_ERR_STATE;
-  const int C = p->coeff_count;
-  double mx = 0.0;
-  for (int i = 0; i < C; i++) {
-    const double *row = &p->inverse_active_set[(size_t) i * C];
-    double g = 0.0;
-    for (int j = 0; j < C; j++) g += c[j] * row[j];
-    mx = std::max(mx, g < 0 ? -g : g);
-  }
-  *grade = mx;
+  *grade = cfg_grade_of(p->inverse_active_set.data(), p->coeff_count, c);
   return MTP_OK;
 }
 
@@ -696,6 +726,13 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
     }
     c = new mtp_context();
     c->pot = pot;
+    c->h_radial = pot->radial_basis_coeffs;
+    c->h_species = pot->species_coeffs;
+    c->h_moments = pot->linear_coeffs;
+    if (pot->has_selection) {
+      c->h_active_set = pot->active_set;
+      c->h_inverse = pot->inverse_active_set;
+    }
     c->device = device_id;
     c->num_cus = prop.multiProcessorCount;
     if (const char *e = std::getenv("MTP_XCD_MAP")) c->xcd_map = std::atoi(e) != 0;
@@ -760,18 +797,9 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
     if (pot->has_selection) {   // inverse active set zero padded to a multiple of 16 for the MFMA grade kernel
       const int C = pot->coeff_count;
       c->cpad = (C + 15) / 16 * 16;
-      std::vector<double> pad((size_t) c->cpad * c->cpad, 0.0);
-      for (int r = 0; r < C; r++)
-        std::memcpy(&pad[(size_t) r * c->cpad], &pot->inverse_active_set[(size_t) r * C], (size_t) C * sizeof(double));
+      std::vector<double> pad, tiled;
+      pad_and_tile(pot->inverse_active_set.data(), C, c->cpad, pad, tiled);
       c->d_ainv_pad.upload(pad, st);
-      // the same matrix in MFMA operand order for the LDS-staged grade kernel: [tile][k-step][lane],
-      // lane (j = l & 15, k = l >> 4) <- Ainv[16 tile + j][4 kstep + k]
-      std::vector<double> tiled((size_t) c->cpad * c->cpad, 0.0);
-      const int ks_n = c->cpad / 4;
-      for (int t = 0; t < c->cpad / 16; t++)
-        for (int ks = 0; ks < ks_n; ks++)
-          for (int l = 0; l < 64; l++)
-            tiled[((size_t) t * ks_n + ks) * 64 + l] = pad[(size_t) (16 * t + (l & 15)) * c->cpad + 4 * ks + (l >> 4)];
       c->d_ainv_tiled.upload(tiled, st);
       HIP_CHECK(hipStreamSynchronize(st));
     }
@@ -1449,7 +1477,7 @@ static int design_prepare(mtp_context *c, hipStream_t st)
   ints.insert(ints.end(), t.force_map.begin(), t.force_map.end());
   c->d_design_rows.upload(rows8, st);
   c->d_design_ints.upload(ints, st);
-  c->d_design_radial.upload(pot.radial_basis_coeffs, st);
+  c->d_design_radial.upload(c->h_radial, st);   // (the context's values: an install may precede the first design call)
   HIP_CHECK(hipStreamSynchronize(st));   // (the staging vectors go out of scope)
   MtpDesignParams &d = c->design;
   d = MtpDesignParams{};
@@ -1788,9 +1816,9 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
   int bad = 0;
   *nswaps = 0;
   *converged = 1;
-  if (nrows == 0) {   // nothing to select from: the potential's own blocks, bit for bit
-    std::memcpy(active_set, p.active_set.data(), p.active_set.size() * sizeof(double));
-    std::memcpy(inverse_active_set, p.inverse_active_set.data(), p.inverse_active_set.size() * sizeof(double));
+  if (nrows == 0) {   // nothing to select from: the context's own blocks (the potential's until an install), bit for bit
+    std::memcpy(active_set, c->h_active_set.data(), c->h_active_set.size() * sizeof(double));
+    std::memcpy(inverse_active_set, c->h_inverse.data(), c->h_inverse.size() * sizeof(double));
     for (int j = 0; j < C; j++) slot_source[j] = -1;
   } else {
     if (hipSetDevice(c->device) != hipSuccess) {
@@ -1801,7 +1829,7 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
     hipError_t e = hipSuccess;
     try {   // the arena is the context's and is kept: a selection loop allocates once
       c->d_maxvol.reserve(mtp_maxvol_arena_doubles(c->num_cus, C, nrows, max_swaps));
-      e = mtp_maxvol_run(st, c->num_cus, c->d_maxvol.ptr, C, p.active_set.data(), p.inverse_active_set.data(), d_rows, nrows,
+      e = mtp_maxvol_run(st, c->num_cus, c->d_maxvol.ptr, C, c->h_active_set.data(), c->h_inverse.data(), d_rows, nrows,
                          ld, threshold, max_swaps, refresh, active_set, inverse_active_set, slot_source, swap_rows, swap_slots,
                          swap_pivots, nswaps, converged, &mg, &bad);
     } catch (const HipFail &f) {
@@ -1822,6 +1850,273 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
   if (bad) {
     c->last_error = "mtp_maxvol_select: a candidate vector (or a grade computed from it) is not finite";
     return MTP_ERR_ARG;
+  }
+  return MTP_OK;
+}
+
+// ---- installs into a live context (include/mtp_mi355x.h) ----------------------------------------------------------------
+namespace {
+
+// the checks of an install of coefficients, with nothing written: the tables a context of these values reads
+int check_coeffs(mtp_context *c, const char *who, const double *radial, const double *species, const double *moments,
+                 mtp_coeff_tables &t)
+{
+  const mtp_potential &p = *c->pot;
+  if (!all_finite(radial, p.radial_basis_coeffs.size()) || !all_finite(species, p.species_coeffs.size()) ||
+      !all_finite(moments, p.linear_coeffs.size())) {
+    c->last_error = std::string(who) + ": a coefficient is not finite";
+    return MTP_ERR_ARG;
+  }
+  mtp_build_coeff_tables(p, radial ? radial : c->h_radial.data(), species ? species : c->h_species.data(),
+                         moments ? moments : c->h_moments.data(), t);
+  if (c->base.off_leaf_cb == c->base.off_leaf_cf && t.leaf_cb != t.leaf_cf) {
+    c->last_error = std::string(who) + ": the context was created on values whose leaf rows have one constant for the energy and "
+        "the adjoint, and its table blob holds one table for both; the new moment coefficients make them differ (two scalars on "
+        "one leaf moment): load the file instead";
+    return MTP_ERR_UNSUPPORTED;
+  }
+  return MTP_OK;
+}
+
+int check_selection(mtp_context *c, const char *who, const double *active_set, const double *inverse_active_set, int coeff_count)
+{
+  const mtp_potential &p = *c->pot;
+  if (!p.has_selection) {
+    c->last_error = std::string(who) + ": the context's potential was loaded without its selection state";
+    return MTP_ERR_STATE;
+  }
+  if (!active_set || !inverse_active_set || coeff_count != p.coeff_count) {
+    c->last_error = std::string(who) + ": needs both blocks, and coeff_count = " + std::to_string(p.coeff_count);
+    return MTP_ERR_ARG;
+  }
+  const size_t n = (size_t) p.coeff_count * p.coeff_count;
+  if (!all_finite(active_set, n) || !all_finite(inverse_active_set, n)) {
+    c->last_error = std::string(who) + ": an entry of the active set or of its inverse is not finite";
+    return MTP_ERR_ARG;
+  }
+  return MTP_OK;
+}
+
+// An install in three steps, so that one call waits ONCE however much it installs: queue_* issue the copies into every
+// device copy of the tables from staging memory the caller keeps alive, the caller drains the stream, and
+// commit_* replace the context's host copies.  queue_* throw HipFail.
+void queue_coeffs(mtp_context *c, hipStream_t st, const mtp_coeff_tables &t)
+{
+  auto put = [&](void *dst, const std::vector<double> &v) {
+    if (!v.empty()) HIP_CHECK(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  };
+  const MtpDevParams &b = c->base;
+  unsigned char *blob = c->d_blob.ptr;
+  put(blob + b.off_radial, t.radial);
+  if (b.scalars_in_lds) {
+    put(blob + b.off_seed_val, t.seed_val);
+    put(blob + b.off_lin, t.e_lin);
+  }
+  put(blob + b.off_leaf_cf, t.leaf_cf);
+  if (b.off_leaf_cb != b.off_leaf_cf) put(blob + b.off_leaf_cb, t.leaf_cb);
+  put(c->d_seed_val.ptr, t.seed_val);
+  put(c->d_lin.ptr, t.e_lin);
+  put(c->d_leaf_cf.ptr, t.leaf_cf);
+  put(c->d_leaf_cb.ptr, t.leaf_cb);
+  put(c->d_species.ptr, t.species);
+  if (c->design_ready) put(c->d_design_radial.ptr, t.radial);
+}
+
+void commit_coeffs(mtp_context *c, const mtp_coeff_tables &t, const double *moments)
+{
+  c->h_radial = t.radial;
+  c->h_species = t.species;
+  if (moments) c->h_moments.assign(moments, moments + c->h_moments.size());
+}
+
+struct StagedSelection {
+  std::vector<double> pad, tiled;
+};
+
+void queue_selection(mtp_context *c, hipStream_t st, const double *inverse_active_set, StagedSelection &stage)
+{
+  pad_and_tile(inverse_active_set, c->pot->coeff_count, c->cpad, stage.pad, stage.tiled);
+  HIP_CHECK(hipMemcpyAsync(c->d_ainv_pad.ptr, stage.pad.data(), stage.pad.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(c->d_ainv_tiled.ptr, stage.tiled.data(), stage.tiled.size() * sizeof(double), hipMemcpyHostToDevice, st));
+}
+
+void commit_selection(mtp_context *c, const double *active_set, const double *inverse_active_set)
+{
+  const size_t n = (size_t) c->pot->coeff_count * c->pot->coeff_count;
+  c->h_active_set.assign(active_set, active_set + n);
+  c->h_inverse.assign(inverse_active_set, inverse_active_set + n);
+}
+
+int device_fail(mtp_context *c, const HipFail &f)
+{
+  c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
+  return MTP_ERR_DEVICE;
+}
+
+}   // namespace
+
+int mtp_context_install_coeffs(mtp_context *c, void *stream, const double *radial_coeffs, const double *species_coeffs,
+                               const double *moment_coeffs)
+{
+  if (!c) return MTP_ERR_ARG;
+  mtp_coeff_tables t;
+  const int rc = check_coeffs(c, "mtp_context_install_coeffs", radial_coeffs, species_coeffs, moment_coeffs, t);
+  if (rc != MTP_OK) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  try {
+    hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
+    queue_coeffs(c, st, t);
+    HIP_CHECK(hipStreamSynchronize(st));   // the one wait: earlier work on the stream and these copies
+    commit_coeffs(c, t, moment_coeffs);
+  } catch (const HipFail &f) {
+    return device_fail(c, f);
+  }
+  return MTP_OK;
+}
+
+int mtp_context_install_selection(mtp_context *c, void *stream, const double *active_set, const double *inverse_active_set,
+                                  int coeff_count)
+{
+  if (!c) return MTP_ERR_ARG;
+  const int rc = check_selection(c, "mtp_context_install_selection", active_set, inverse_active_set, coeff_count);
+  if (rc != MTP_OK) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  try {
+    hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
+    StagedSelection stage;
+    queue_selection(c, st, inverse_active_set, stage);
+    HIP_CHECK(hipStreamSynchronize(st));
+    commit_selection(c, active_set, inverse_active_set);
+  } catch (const HipFail &f) {
+    return device_fail(c, f);
+  }
+  return MTP_OK;
+}
+
+int mtp_context_install_file(mtp_context *c, void *stream, const char *path)
+{
+  if (!c || !path) return MTP_ERR_ARG;
+  const mtp_potential &p = *c->pot;
+  // the gate is mtp_potential_compatible's: one text parse, no schedule.  A file with NO #MVS tail at all (what the
+  // coefficient writers leave) still installs its coefficients into a context that has a selection state; a tail that is
+  // there but does not read (wrong version, a weight line missing, short blocks) is the parser's error.
+  mtp_potential file;
+  std::string msg;
+  bool with_selection = p.has_selection;
+  int rc = mtp_parse_text_file(path, with_selection, file, msg);
+  if (rc == MTP_ERR_SELECTION && with_selection && file.selection_absent) {   // (a damaged tail stays an error)
+    with_selection = false;
+    file = mtp_potential();
+    msg.clear();
+    rc = mtp_parse_text_file(path, false, file, msg);
+  }
+  if (rc == MTP_OK) rc = mtp_check_compatible(p, file, with_selection, msg);
+  if (rc != MTP_OK) {
+    c->last_error = "mtp_context_install_file: " + msg;
+    return rc;
+  }
+  mtp_coeff_tables t;
+  rc = check_coeffs(c, "mtp_context_install_file", file.radial_basis_coeffs.data(), file.species_coeffs.data(),
+                    file.linear_coeffs.data(), t);
+  if (rc == MTP_OK && with_selection)
+    rc = check_selection(c, "mtp_context_install_file", file.active_set.data(), file.inverse_active_set.data(), file.coeff_count);
+  if (rc != MTP_OK) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  try {
+    hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
+    StagedSelection stage;
+    queue_coeffs(c, st, t);
+    if (with_selection) queue_selection(c, st, file.inverse_active_set.data(), stage);
+    HIP_CHECK(hipStreamSynchronize(st));   // one wait for both
+    commit_coeffs(c, t, file.linear_coeffs.data());
+    if (with_selection) commit_selection(c, file.active_set.data(), file.inverse_active_set.data());
+  } catch (const HipFail &f) {
+    return device_fail(c, f);
+  }
+  return MTP_OK;
+}
+
+int mtp_context_get_coeffs(const mtp_context *c, double *radial_coeffs, double *species_coeffs, double *moment_coeffs)
+{
+  if (!c) return MTP_ERR_ARG;
+  auto cp = [](double *dst, const std::vector<double> &v) {
+    if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(double));
+  };
+  cp(radial_coeffs, c->h_radial);
+  cp(species_coeffs, c->h_species);
+  cp(moment_coeffs, c->h_moments);
+  return MTP_OK;
+}
+
+int mtp_context_get_selection(const mtp_context *c, double *active_set, double *inverse_active_set)
+{
+  if (!c) return MTP_ERR_ARG;
+  if (!c->pot->has_selection) return MTP_ERR_STATE;
+  if (active_set) std::memcpy(active_set, c->h_active_set.data(), c->h_active_set.size() * sizeof(double));
+  if (inverse_active_set) std::memcpy(inverse_active_set, c->h_inverse.data(), c->h_inverse.size() * sizeof(double));
+  return MTP_OK;
+}
+
+int mtp_context_cfg_grade(const mtp_context *c, const double *coeff_ders, double *grade)
+{
+  if (!c || !coeff_ders || !grade) return MTP_ERR_ARG;
+  if (!c->pot->has_selection) return MTP_ERR_STATE;
+  *grade = cfg_grade_of(c->h_inverse.data(), c->pot->coeff_count, coeff_ders);
+  return MTP_OK;
+}
+
+int mtp_context_coeff_tables_device(mtp_context *c, void *stream, int32_t *counts, double *blob_radial, double *blob_seed_val,
+                                    double *blob_e_lin, double *blob_leaf_cf, double *blob_leaf_cb, double *hbm_seed_val,
+                                    double *hbm_e_lin, double *hbm_leaf_cf, double *hbm_leaf_cb, double *species,
+                                    double *design_radial, double *ainv_pad, double *ainv_tiled)
+{
+  if (!c) return MTP_ERR_ARG;
+  const mtp_potential &p = *c->pot;
+  const MtpDevParams &b = c->base;
+  const size_t n_rad = p.radial_basis_coeffs.size(), n_seed = p.seed_val.size(), n_lin = p.e_lin.size(), n_leaf = p.leaf_cf.size();
+  const size_t n_w = p.has_selection ? (size_t) c->cpad * c->cpad : 0;
+  if (counts) {
+    const size_t v[10] = {n_rad, n_seed, n_lin, n_leaf, n_leaf, p.species_coeffs.size(), c->design_ready ? n_rad : 0, n_w, n_w,
+                          (size_t) (b.scalars_in_lds ? 1 : 0)};
+    for (int k = 0; k < 10; k++) counts[k] = (int32_t) v[k];
+  }
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->last_error = "hipSetDevice failed";
+    return MTP_ERR_DEVICE;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
+  try {
+    auto get = [&](double *dst, const void *src, size_t n) {
+      if (dst && n) HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    };
+    const unsigned char *blob = c->d_blob.ptr;
+    get(blob_radial, blob + b.off_radial, n_rad);
+    if (b.scalars_in_lds) {
+      get(blob_seed_val, blob + b.off_seed_val, n_seed);
+      get(blob_e_lin, blob + b.off_lin, n_lin);
+    }
+    get(blob_leaf_cf, blob + b.off_leaf_cf, n_leaf);
+    get(blob_leaf_cb, blob + b.off_leaf_cb, n_leaf);
+    get(hbm_seed_val, c->d_seed_val.ptr, n_seed);
+    get(hbm_e_lin, c->d_lin.ptr, n_lin);
+    get(hbm_leaf_cf, c->d_leaf_cf.ptr, n_leaf);
+    get(hbm_leaf_cb, c->d_leaf_cb.ptr, n_leaf);
+    get(species, c->d_species.ptr, p.species_coeffs.size());
+    if (c->design_ready) get(design_radial, c->d_design_radial.ptr, n_rad);
+    get(ainv_pad, c->d_ainv_pad.ptr, n_w);
+    get(ainv_tiled, c->d_ainv_tiled.ptr, n_w);
+    HIP_CHECK(hipStreamSynchronize(st));
+  } catch (const HipFail &f) {
+    return device_fail(c, f);
   }
   return MTP_OK;
 }

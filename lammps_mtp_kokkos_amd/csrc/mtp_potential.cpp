@@ -258,9 +258,11 @@ void parse_text(FILE *fp, bool want_selection, mtp_potential &p)
   // selection state (pair_mtp_extrapolation.cpp:545-612)
   rd.ignore_comments = false;
   std::string ln;
-  if (!rd.next(ln))
+  if (!rd.next(ln)) {
+    p.selection_absent = true;
     throw ParseError{MTP_ERR_SELECTION,
                      "No selection state found! Consider training/retraining or disabling extrapolation!"};
+  }
   {
     Tokens t(ln, kSeps);
     std::string w;
@@ -322,6 +324,101 @@ int mtp_parse_text_file(const char *path, bool want_selection, mtp_potential &po
   }
   std::fclose(fp);
   return rc;
+}
+
+// ---- the coefficient-dependent tables of the schedule (mtp_potential.hpp) ---------------------------------------------
+// Reads the structure only as relabel leaves it: rows_by_level in LDS numbering, level_offset / normal_levels,
+// moment_perm and stored_moment_count (a moment is a leaf iff its LDS number is not below stored_moment_count).
+void mtp_build_coeff_tables(const mtp_potential &p, const double *radial, const double *species, const double *moments,
+                            mtp_coeff_tables &out)
+{
+  const int A = p.alpha_moment_count, S = p.alpha_scalar_count;
+  const std::vector<int32_t> &perm = p.moment_perm;
+  const double *lin = moments ? moments : p.linear_coeffs.data();
+  const double *ra = radial ? radial : p.radial_basis_coeffs.data();
+  const double *sp = species ? species : p.species_coeffs.data();
+  out.radial.assign(ra, ra + p.radial_basis_coeffs.size());
+  out.species.assign(sp, sp + p.species_coeffs.size());
+  auto is_leaf = [&](int m) { return perm[(size_t) m] >= p.stored_moment_count; };
+  // adjoint seeds: assignment, so the last scalar mapped to a moment wins (:217-218)
+  std::vector<int> last((size_t) A, -1);
+  for (int i = 0; i < S; i++) last[(size_t) p.alpha_moment_mapping[(size_t) i]] = i;
+  out.seed_val.clear();
+  for (int m = 0; m < A; m++)
+    if (last[(size_t) m] >= 0 && !is_leaf(m)) out.seed_val.push_back(lin[last[(size_t) m]]);
+  // constants of the leaf rows and the energy table of the stored scalars
+  std::vector<double> c_energy((size_t) A, 0.0), c_seed((size_t) A, 0.0);   // by LDS number
+  out.e_lin.clear();
+  for (int i = 0; i < S; i++) {
+    const int m = p.alpha_moment_mapping[(size_t) i], ml = perm[(size_t) m];
+    if (is_leaf(m)) {
+      c_energy[(size_t) ml] += lin[i];
+      c_seed[(size_t) ml] = lin[i];   // the last one wins (:217-218)
+    } else {
+      out.e_lin.push_back(lin[i]);
+    }
+  }
+  const size_t leaf_row0 = (size_t) p.level_offset[(size_t) p.normal_levels];
+  const size_t nleaf_rows = p.rows_by_level.size() - leaf_row0;
+  out.leaf_cf.assign(nleaf_rows, 0.0);
+  out.leaf_cb.assign(nleaf_rows, 0.0);
+  for (size_t r = 0; r < nleaf_rows; r++) {
+    const MtpRow &row = p.rows_by_level[leaf_row0 + r];
+    if (row.mult == 0) continue;   // padding
+    out.leaf_cf[r] = c_energy[(size_t) row.a3] * row.mult;
+    out.leaf_cb[r] = c_seed[(size_t) row.a3] * row.mult;
+  }
+}
+
+// first difference between `a` and another potential "as read" in what the schedule and the argument block depend on
+int mtp_check_compatible(const mtp_potential &a, const mtp_potential &b, bool want_selection, std::string &err)
+{
+  auto differ = [&](const std::string &name, const std::string &x, const std::string &y) {
+    err = "the new file differs in " + name + ": " + y + ", the loaded potential has " + x;
+    return (int) MTP_ERR_UNSUPPORTED;
+  };
+  auto num = [](double v) {
+    char t[40];
+    std::snprintf(t, sizeof t, "%.17g", v);
+    return std::string(t);
+  };
+#define MTP_SAME_INT(field, name) \
+  if (a.field != b.field) return differ(name, std::to_string(a.field), std::to_string(b.field))
+#define MTP_SAME_REAL(field, name) \
+  if (!(a.field == b.field)) return differ(name, num(a.field), num(b.field))
+  MTP_SAME_REAL(scaling, "scaling");
+  MTP_SAME_INT(species_count, "species_count");
+  MTP_SAME_REAL(min_cutoff, "min_dist");
+  MTP_SAME_REAL(max_cutoff, "max_dist");
+  MTP_SAME_INT(radial_basis_size, "radial_basis_size");
+  MTP_SAME_INT(radial_func_count, "radial_funcs_count");
+  MTP_SAME_INT(alpha_moment_count, "alpha_moments_count");
+  MTP_SAME_INT(alpha_index_basic_count, "alpha_index_basic_count");
+  MTP_SAME_INT(alpha_index_times_count, "alpha_index_times_count");
+  MTP_SAME_INT(alpha_scalar_count, "alpha_scalar_moments");
+#undef MTP_SAME_INT
+#undef MTP_SAME_REAL
+  auto table = [&](const char *name, const std::vector<int32_t> &x, const std::vector<int32_t> &y, size_t width) {
+    if (x.size() != y.size()) return differ(name, std::to_string(x.size()) + " entries", std::to_string(y.size()) + " entries");
+    for (size_t k = 0; k < x.size(); k++)
+      if (x[k] != y[k])
+        return differ(std::string(name) + "[" + std::to_string(k / width) + (width > 1 ? "][" + std::to_string(k % width) + "]" : "]"),
+                      std::to_string(x[k]), std::to_string(y[k]));
+    return (int) MTP_OK;
+  };
+  int rc = table("alpha_index_basic", a.alpha_index_basic, b.alpha_index_basic, 4);
+  if (rc == MTP_OK) rc = table("alpha_index_times", a.alpha_index_times, b.alpha_index_times, 4);
+  if (rc == MTP_OK) rc = table("alpha_moment_mapping", a.alpha_moment_mapping, b.alpha_moment_mapping, 1);
+  if (rc != MTP_OK) return rc;
+  if (want_selection) {
+    const char *modes[2] = {"neighbourhood (site_en_weight = 1)", "configuration (energy_weight = 1)"};
+    if (a.coeff_count != b.coeff_count) return differ("coeff_count", std::to_string(a.coeff_count), std::to_string(b.coeff_count));
+    if (a.has_selection != b.has_selection)
+      return differ("selection state", a.has_selection ? "present" : "absent", b.has_selection ? "present" : "absent");
+    if (a.configuration_mode != b.configuration_mode)
+      return differ("selection mode", modes[a.configuration_mode ? 1 : 0], modes[b.configuration_mode ? 1 : 0]);
+  }
+  return MTP_OK;
 }
 
 // ---- native schedule: the passes of mtp_potential::finalize, in the order it runs them -----------------------------
@@ -897,40 +994,23 @@ void relabel(mtp_potential &p, const std::vector<char> &leaf)
     row.a1 = perm[row.a1];
     row.a3 = perm[row.a3];
   }
-  // adjoint seeds: assignment, so the last scalar mapped to a moment wins (:217-218)
+  // the index side of the scalar tables (structure only); their values: mtp_build_coeff_tables
   std::vector<int> last((size_t) A, -1);
   for (int i = 0; i < S; i++) last[p.alpha_moment_mapping[i]] = i;
   p.seed_idx.clear();
-  p.seed_val.clear();
-  for (int m = 0; m < A; m++)
-    if (last[m] >= 0 && !leaf[m]) {
-      p.seed_idx.push_back(perm[m]);
-      p.seed_val.push_back(p.linear_coeffs[last[m]]);
-    }
-  // constants of the leaf rows and the energy tables of the stored scalars
-  std::vector<double> c_energy((size_t) A, 0.0), c_seed((size_t) A, 0.0);   // by LDS number
+  for (int m = 0; m < A; m++) {
+    assert((leaf[m] != 0) == (perm[m] >= p.stored_moment_count));   // numbers swap inside a class only
+    if (last[m] >= 0 && !leaf[m]) p.seed_idx.push_back(perm[m]);
+  }
   p.e_map.clear();
-  p.e_lin.clear();
-  for (int i = 0; i < S; i++) {
-    const int m = p.alpha_moment_mapping[i], ml = perm[m];
-    if (leaf[m]) {
-      c_energy[(size_t) ml] += p.linear_coeffs[i];
-      c_seed[(size_t) ml] = p.linear_coeffs[i];   // the last one wins (:217-218)
-    } else {
-      p.e_map.push_back(ml);
-      p.e_lin.push_back(p.linear_coeffs[i]);
-    }
-  }
-  const size_t leaf_row0 = (size_t) p.level_offset[(size_t) p.normal_levels];
-  const size_t nleaf_rows = p.rows_by_level.size() - leaf_row0;
-  p.leaf_cf.assign(nleaf_rows, 0.0);
-  p.leaf_cb.assign(nleaf_rows, 0.0);
-  for (size_t r = 0; r < nleaf_rows; r++) {
-    const MtpRow &row = p.rows_by_level[leaf_row0 + r];
-    if (row.mult == 0) continue;   // padding
-    p.leaf_cf[r] = c_energy[(size_t) row.a3] * row.mult;
-    p.leaf_cb[r] = c_seed[(size_t) row.a3] * row.mult;
-  }
+  for (int i = 0; i < S; i++)
+    if (!leaf[p.alpha_moment_mapping[i]]) p.e_map.push_back(perm[p.alpha_moment_mapping[i]]);
+  mtp_coeff_tables ct;
+  mtp_build_coeff_tables(p, nullptr, nullptr, nullptr, ct);
+  p.seed_val.swap(ct.seed_val);
+  p.e_lin.swap(ct.e_lin);
+  p.leaf_cf.swap(ct.leaf_cf);
+  p.leaf_cb.swap(ct.leaf_cb);
   p.mapping_lds.resize((size_t) S);
   for (int i = 0; i < S; i++) p.mapping_lds[i] = perm[p.alpha_moment_mapping[i]];
   // packed basic descriptors (mtp_cvec_kernel pairs them with dbasic[k] = D[k]) and coefficient targets at the basic's
@@ -1638,6 +1718,41 @@ int mtp_potential_train_table(const mtp_potential *pot, int32_t *counts, int32_t
     refused[0] = t.late_row;
     refused[1] = t.dup_scalar;
   }
+  copy_message(msg, err, errlen);
+  return rc;
+}
+
+int mtp_potential_coeff_tables(const mtp_potential *pot, const double *radial_coeffs, const double *species_coeffs,
+                               const double *moment_coeffs, int32_t *counts, double *radial_out, double *species_out,
+                               double *seed_val, double *e_lin, double *leaf_cf, double *leaf_cb)
+{
+  if (!pot) return MTP_ERR_ARG;
+  bool finite = true;
+  for (size_t i = 0; radial_coeffs && i < pot->radial_basis_coeffs.size(); i++) finite = finite && std::isfinite(radial_coeffs[i]);
+  for (size_t i = 0; species_coeffs && i < pot->species_coeffs.size(); i++) finite = finite && std::isfinite(species_coeffs[i]);
+  for (size_t i = 0; moment_coeffs && i < pot->linear_coeffs.size(); i++) finite = finite && std::isfinite(moment_coeffs[i]);
+  if (!finite) return MTP_ERR_ARG;
+  mtp_coeff_tables t;
+  mtp_build_coeff_tables(*pot, radial_coeffs, species_coeffs, moment_coeffs, t);
+  const std::vector<double> *v[6] = {&t.radial, &t.species, &t.seed_val, &t.e_lin, &t.leaf_cf, &t.leaf_cb};
+  double *dst[6] = {radial_out, species_out, seed_val, e_lin, leaf_cf, leaf_cb};
+  for (int k = 0; k < 6; k++) {
+    if (counts) counts[k] = (int32_t) v[k]->size();
+    if (dst[k] && !v[k]->empty()) std::memcpy(dst[k], v[k]->data(), v[k]->size() * sizeof(double));
+  }
+  return MTP_OK;
+}
+
+int mtp_potential_compatible(const mtp_potential *pot, const char *path, int want_selection, char *err, int errlen)
+{
+  if (!pot || !path) {
+    copy_message("mtp_potential_compatible: null argument", err, errlen);
+    return MTP_ERR_ARG;
+  }
+  mtp_potential other;
+  std::string msg;
+  int rc = mtp_parse_text_file(path, want_selection != 0, other, msg);
+  if (rc == MTP_OK) rc = mtp_check_compatible(*pot, other, want_selection != 0, msg);
   copy_message(msg, err, errlen);
   return rc;
 }

@@ -28,6 +28,7 @@ struct mtp_potential {
   bool has_selection = false, configuration_mode = false;
   int coeff_count = 0;
   std::vector<double> active_set, inverse_active_set;   // [C][C]
+  bool selection_absent = false;   // a selection was asked for and the file ends behind moment_coeffs: no #MVS tail at all
   long selection_offset = 0;   // bytes of the file up to and including the '#' in front of the two raw blocks
 
   // --- native schedule (built by finalize) -------------------------------------------------
@@ -113,3 +114,17 @@ struct mtp_train_table {
   int late_row = -1, dup_scalar = -1;
 };
 int mtp_build_train_table(const mtp_potential &pot, mtp_train_table &out, std::string &err);
+
+// The coefficient-dependent tables of the native schedule: the values a context uploads beside (and inside) its table
+// blob.  Filled from the FIXED structure of a finalized potential and a (radial, species, moment) triple in the file's
+// array order, nullptr = the potential's own values; finalize() itself fills seed_val, e_lin, leaf_cf and leaf_cb through
+// this function, so a live context that takes new values gets exactly what a load of the written file would build.
+struct mtp_coeff_tables {
+  std::vector<double> radial, species, seed_val, e_lin, leaf_cf, leaf_cb;
+};
+void mtp_build_coeff_tables(const mtp_potential &pot, const double *radial, const double *species, const double *moments,
+                            mtp_coeff_tables &out);
+// MTP_OK when `other` (as read: no schedule needed) equals `pot` in everything the schedule and the kernels' argument block
+// were built from; MTP_ERR_UNSUPPORTED and the first difference in err otherwise (include/mtp_mi355x.h,
+// mtp_potential_compatible)
+int mtp_check_compatible(const mtp_potential &pot, const mtp_potential &other, bool want_selection, std::string &err);

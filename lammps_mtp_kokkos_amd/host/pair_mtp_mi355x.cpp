@@ -42,11 +42,25 @@ void PairMTP::require(int rc, const char *what)
 void PairMTP::load(const char *file, bool selection)
 {
   char err[512] = "";
+  // pair_style re-issued in a running simulation with a retrained file: when the file has the structure of the loaded one
+  // (and the same selection wish) its values are installed into the live context -- the potential's native schedule, the
+  // context, the installed neighbour list and the launch plan are kept (include/mtp_mi355x.h, "installing ...").  Anything
+  // else -- another table, cutoff, scaling, species count, selection mode, or a file that does not read -- takes the full load.
+  if (pot_ && ctx_ && selection == (info.has_selection != 0) &&
+      mtp_potential_compatible(pot_, file, selection ? 1 : 0, err, (int) sizeof(err)) == MTP_OK) {
+    require(mtp_context_install_file(ctx_, resident_ ? datom.stream : nullptr, file), "mtp_context_install_file");
+    installs_++;
+    logmesg(log_scaling(info.scaling));          // the reference logs both on every read (pair_mtp.cpp:383, 389)
+    logmesg(log_species(info.species_count));
+    return;
+  }
+  err[0] = 0;
   if (pot_) {
     if (ctx_) mtp_context_destroy(ctx_);
     mtp_potential_free(pot_);
     pot_ = nullptr;
     ctx_ = nullptr;
+    list_set_ = false;   // (the list lived in the context)
   }
   int rc = mtp_potential_load(file, selection ? 1 : 0, &pot_, err, (int) sizeof(err));
   if (rc != MTP_OK) throw Error(rc, err);
@@ -203,6 +217,7 @@ void PairMTPExtrapolation::settings(int narg, char **arg)
   logmesg(log_extrapolation_mode(mlip3_style, configuration_mode, select_threshold, break_threshold));   // :508-517
   energy_ders_wrt_coeffs.assign((size_t) info.coeff_count, 0.0);
   if (mlip3_style && red.me == 0) {
+    if (preselected_file) std::fclose(preselected_file);   // (settings re-issued)
     preselected_file = std::fopen(arg[1], "w");
     if (!preselected_file) throw Error(MTP_ERR_IO, std::string("cannot open ") + arg[1]);
   }
@@ -244,7 +259,7 @@ void PairMTPExtrapolation::compile_grades()
   if (configuration_mode) {   // :366-376
     if (red.sum) red.sum(energy_ders_wrt_coeffs.data(), (int) energy_ders_wrt_coeffs.size(), red.ctx);
     double g = 0.0;
-    require(mtp_cfg_grade(pot_, energy_ders_wrt_coeffs.data(), &g), "mtp_cfg_grade");
+    require(mtp_context_cfg_grade(ctx_, energy_ders_wrt_coeffs.data(), &g), "mtp_context_cfg_grade");   // the context's W: an install may have replaced the file's
     max_grade = atom.natoms > 0 ? g / (double) atom.natoms : 0.0;
   } else {                    // :378-380
     if (red.max) red.max(&max_grade, 1, red.ctx);

@@ -106,6 +106,11 @@ class PairMTP {
   bool resident() const { return resident_; }
   void set_log(const LogSink &l) { log_ = l; }
   void set_rank(int me) { me_ = me; }               // comm->me: only rank 0 logs
+  // settings() on a mirror that already runs: a file with the loaded potential's structure is INSTALLED into the live
+  // context (same handle, list and plan kept; installs() counts them), any other file is loaded in full and needs
+  // init_style() and a neighbour list again
+  const mtp_context *context() const { return ctx_; }
+  int installs() const { return installs_; }
 
   // what LAMMPS reads back (pair.h)
   double eng_vdwl = 0.0, virial[6] = {0, 0, 0, 0, 0, 0};
@@ -129,6 +134,7 @@ class PairMTP {
   bool resident_ = false;   // bound to device views: compute() runs mtp_compute_resident
   void compute_resident(int eflag, int vflag, int grade, double *max_grade, double *coeff_ders);
   bool list_set_ = false;
+  int installs_ = 0;
   int eflag_either = 0, eflag_global = 0, eflag_atom = 0, vflag_either = 0, vflag_global = 0, vflag_atom = 0;
 };
 

@@ -413,13 +413,15 @@ def _empty_result(volume, grades, cfg_mode):
 
 
 def select_cells(ctx, configs, threshold=1.1, out_path=None, list_cutoff=7.0, max_swaps=None, max_pool_bytes=2 ** 31,
-                 max_atoms_per_pass=None, device=None):
+                 max_atoms_per_pass=None, device=None, install=False):
     """The selection step of the active-learning loop over a batch of candidate configurations: the passes of
     evaluate_cells(grades=True), every pass's candidate vectors copied into one pool on the device (one row per atom in
     neighbourhood mode, one per configuration -- the sum over its atoms divided by their number -- in configuration mode),
-    ONE MaxVol selection over that pool starting from the potential's active set (Context.maxvol_select), and, with
-    `out_path`, the potential file with the new active set and its inverse (capi.write_selection; the context itself keeps
-    its old set: reload the written file to grade with the new one).  The pool is selected as a whole, because later swaps
+    ONE MaxVol selection over that pool starting from the context's active set (Context.maxvol_select), and, with
+    `out_path`, the potential file with the new active set and its inverse (capi.write_selection: the source's text, so
+    its coefficients are the file's).  The new set reaches a context by either of two routes: install=True puts it into
+    `ctx` (Context.install_selection, after any out_path write) -- plan, list and buffers are kept --, or a new Potential
+    and Context are loaded from the written file.  The pool is selected as a whole, because later swaps
     change earlier grades: ValueError when it would exceed `max_pool_bytes` (the selection needs as much again for its
     grade matrix).
 
@@ -457,6 +459,8 @@ def select_cells(ctx, configs, threshold=1.1, out_path=None, list_cutoff=7.0, ma
     sel = ctx.maxvol_select(pool, threshold, max_swaps=max_swaps, stream=st)
     if out_path is not None:
         capi.write_selection(ctx.pot.path, out_path, sel["active_set"], sel["inverse_active_set"])
+    if install:
+        ctx.install_selection(sel["active_set"], sel["inverse_active_set"], stream=st)
     owner = [None if r < 0 else (int(r) if cfg_mode else int(np.searchsorted(first, r, side="right") - 1))
              for r in sel["slot_source"]]
     source = [None if k is None else (k if cfg_mode else (k, int(r - first[k]))) for k, r in zip(owner, sel["slot_source"])]
@@ -471,8 +475,8 @@ def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 
     """The design matrix of the linear refit over a batch of configurations (include/mtp_mi355x.h, "linear refit"): the
     passes of evaluate_cells -- ghost build, list build -- with the design call (Context.design_rows, the ghost owner
     map folding every neighbour's term onto its owned row) in place of the force call, then the per-configuration sums
-    (capi.batch_design_reduce).  Columns are [species (Sp) | moments (S)]; with theta = the potential's species_coeffs and
-    moment_coeffs, energy @ theta, force @ theta and virial @ theta are what evaluate_cells returns.
+    (capi.batch_design_reduce).  Columns are [species (Sp) | moments (S)]; with theta = the context's species_coeffs and
+    moment_coeffs (Context.coeffs), energy @ theta, force @ theta and virial @ theta are what evaluate_cells returns.
 
     Returns dict(energy [ncfg, Sp + S], force [3 sum n, Sp + S] (row 3 (cfg_first[k] + a) + c: atom a of configuration k,
     component c, atoms in the order of `pos`), virial [ncfg, 6, Sp + S] (None with virial=False), cfg_first [ncfg + 1],
@@ -535,34 +539,44 @@ def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 
 
 
 def fit_linear(ctx, configs, labels, weights=(1.0, 0.01, 0.001), rcond=1e-12, out_path=None, list_cutoff=7.0,
-               max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None):
+               max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None, install=False):
     """The linear refit: species_coeffs and moment_coeffs fitted to reference energies, forces and virials with the radial
     coefficients fixed.  labels[k] = dict(energy=float or None, f=[n, 3] or None, virial=[6] or None) for configs[k]
     (virial in the sign and order evaluate_cells returns).  With N_k atoms in configuration k the rows of design_cells
     and their labels are scaled by sqrt(w_e) / N_k (energy), sqrt(w_f) (forces) and sqrt(w_s) / N_k (virial), weights =
     (w_e, w_f, w_s) -- this project's definition, not pinned to MLIP's --, rows without a label are dropped, and the
     solve is for the CHANGE of the coefficients: delta = lstsq(A_w, y_w - A_w theta_0, rcond), theta = theta_0 + delta,
-    theta_0 the potential's current coefficients, so that directions the data do not determine (the complete tables are
+    theta_0 the context's current coefficients (Context.coeffs: the file's until an install), so that directions the data do not determine (the complete tables are
     rank deficient by construction) keep their values.  The weighted matrix is copied to the host and solved with
     numpy.linalg.lstsq (SVD); it is bounded by max_design_bytes and the fit runs once per round.
 
     Returns dict(species_coeffs, moment_coeffs, rank, singular_values, rmse_before, rmse_after: dicts energy (per atom),
     force, virial (per atom) over the labelled rows, None for a kind without labels) and, with out_path, writes the
-    potential file through capi.write_coeffs ("wrote" = its return value).  The context keeps its old coefficients:
-    reload the written file, as after a selection."""
+    potential file: through capi.write_coeffs while the context's radial block is the file's, through
+    capi.write_all_coeffs with the context's radial block once an install has made them differ (the written file is always
+    the context's model).  "wrote" is the return value of the writer used; both return 0, or
+    capi.WROTE_WITHOUT_SELECTION where the source's #MVS tail was left out.  The result reaches a context by either of two routes: install=True puts it
+    into `ctx` (Context.install_coeffs, after any out_path write), or a new Potential and Context are loaded from the written
+    file.  Either way the active set's columns are candidate vectors of the OLD coefficients and are stale: rebuilding the
+    set is the caller's select_cells call, not something an install does."""
     if len(labels) != len(configs):
         raise ValueError("fit_linear: %d labels for %d configurations" % (len(labels), len(configs)))
     want_v = float(weights[2]) > 0.0 and any(l.get("virial") is not None for l in labels)
     d = design_cells(ctx, configs, list_cutoff=list_cutoff, virial=want_v, max_design_bytes=max_design_bytes,
                      max_atoms_per_pass=max_atoms_per_pass, device=device)
-    t = ctx.pot.tables()
+    t = ctx.coeffs()
     res = solve_linear(d["energy"].cpu().numpy(), d["force"].cpu().numpy(), d["virial"].cpu().numpy() if want_v else None,
                        d["natoms"], labels, np.concatenate([t["species_coeffs"], t["moment_coeffs"]]), weights, rcond)
     Sp = int(ctx.pot.info.species_count)
     theta = res.pop("theta")
     res.update(species_coeffs=theta[:Sp].copy(), moment_coeffs=theta[Sp:].copy())
     if out_path is not None:
-        res["wrote"] = capi.write_coeffs(ctx.pot.path, out_path, res["moment_coeffs"], res["species_coeffs"])
+        if np.array_equal(t["radial_coeffs"], ctx.pot.tables()["radial_coeffs"]):
+            res["wrote"] = capi.write_coeffs(ctx.pot.path, out_path, res["moment_coeffs"], res["species_coeffs"])
+        else:                                                   # (an installed radial block: the file's is not the context's)
+            res["wrote"] = capi.write_all_coeffs(ctx.pot.path, out_path, res["moment_coeffs"], res["species_coeffs"], t["radial_coeffs"])
+    if install:                                                 # (design_cells ended in a synchronise of the current stream)
+        ctx.install_coeffs(species_coeffs=res["species_coeffs"], moment_coeffs=res["moment_coeffs"])
     return res
 
 
@@ -647,7 +661,7 @@ def _label_arrays(labels, natoms, weights):
 def loss_cells(ctx, configs, labels, theta=None, weights=(1.0, 0.01, 0.001), grad=True, list_cutoff=7.0, max_atoms_per_pass=None,
                device=None):
     """The training loss and its gradient with respect to ALL coefficients (include/mtp_mi355x.h, "training gradient").
-    `theta` [C] in candidate-vector order [radial | species | moments] (None: the potential's own, Potential.theta()); the
+    `theta` [C] in candidate-vector order [radial | species | moments] (None: the context's own, Context.theta()); the
     context's force tables are not involved.  The loss is the objective fit_linear minimises, with N_k atoms in
     configuration k and weights = (w_e, w_f, w_s):
         L = sum_k [ w_e ((E_k - E*_k) / N_k)^2 + w_f sum |F - F*|^2 + w_s sum_6 ((V_k - V*_k) / N_k)^2 ]  over the labelled kinds.
@@ -670,7 +684,7 @@ def loss_cells(ctx, configs, labels, theta=None, weights=(1.0, 0.01, 0.001), gra
     info = ctx.pot.info
     C = int(info.species_count ** 2 * info.radial_func_count * info.radial_basis_size + info.species_count + info.alpha_scalar_count)
     ld = C + (C & 1)
-    theta_h = ctx.pot.theta() if theta is None else np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+    theta_h = ctx.theta() if theta is None else np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
     if len(theta_h) != C:
         raise ValueError("loss_cells: theta has %d entries, the potential has C = %d coefficients" % (len(theta_h), C))
     w_e, w_f, w_s = (float(w) for w in weights)
@@ -770,16 +784,17 @@ def minimize_lbfgs(fun, theta0, mask=None, max_iter=200, history_size=20, tolera
 
 def fit_full(ctx, configs, labels, weights=(1.0, 0.01, 0.001), theta0=None, fit=("radial", "species", "moments"), max_iter=200,
              out_path=None, list_cutoff=7.0, max_atoms_per_pass=None, history_size=20, tolerance_grad=1e-10, tolerance_change=0.0,
-             device=None):
+             device=None, install=False):
     """Non-linear training: ALL coefficients -- the radial block included -- fitted to reference energies, forces and
     virials by L-BFGS (minimize_lbfgs) on the loss of loss_cells, whose closure is one loss_cells call on the device.
-    labels and weights as for fit_linear; theta0 [C] in candidate-vector order (None: the potential's coefficients); `fit`
+    labels and weights as for fit_linear; theta0 [C] in candidate-vector order (None: the context's coefficients); `fit`
     names the blocks that move, the gradient of the others is zeroed.
 
     Returns dict(theta [C], radial_coeffs [Sp, Sp, Mu, R], species_coeffs, moment_coeffs, history: the loss at the start of
     every iteration and at the end, rmse_before, rmse_after) and, with out_path, writes the potential file through
-    capi.write_all_coeffs ("wrote" = its return value).  The context keeps its old coefficients, as after fit_linear:
-    reload the written file."""
+    capi.write_all_coeffs ("wrote" = its return value).  The two routes into a context are those of fit_linear: install=True
+    (Context.install_coeffs on `ctx`, after any out_path write) or a load of the written file; the active set is stale
+    afterwards either way."""
     unknown = set(fit) - {"radial", "species", "moments"}
     if unknown:
         raise ValueError("fit_full: unknown block(s) %s" % sorted(unknown))
@@ -787,7 +802,7 @@ def fit_full(ctx, configs, labels, weights=(1.0, 0.01, 0.001), theta0=None, fit=
     Sp, S = int(info.species_count), int(info.alpha_scalar_count)
     Mu, R = int(info.radial_func_count), int(info.radial_basis_size)
     nrad = Sp * Sp * Mu * R
-    theta0 = ctx.pot.theta() if theta0 is None else np.ascontiguousarray(theta0, dtype=np.float64).reshape(-1)
+    theta0 = ctx.theta() if theta0 is None else np.ascontiguousarray(theta0, dtype=np.float64).reshape(-1)
     mask = np.concatenate([np.full(nrad, "radial" in fit), np.full(Sp, "species" in fit), np.full(S, "moments" in fit)])
     kw = dict(weights=weights, list_cutoff=list_cutoff, max_atoms_per_pass=max_atoms_per_pass, device=device)
     before = loss_cells(ctx, configs, labels, theta=theta0, grad=False, **kw)
@@ -802,4 +817,6 @@ def fit_full(ctx, configs, labels, weights=(1.0, 0.01, 0.001), theta0=None, fit=
                moment_coeffs=theta[nrad + Sp:].copy(), history=history, rmse_before=before["rmse"], rmse_after=after["rmse"])
     if out_path is not None:
         res["wrote"] = capi.write_all_coeffs(ctx.pot.path, out_path, res["moment_coeffs"], res["species_coeffs"], res["radial_coeffs"])
+    if install:
+        ctx.install_coeffs(res["radial_coeffs"], res["species_coeffs"], res["moment_coeffs"])
     return res
