@@ -113,6 +113,85 @@ def twin_loss(tables, systems, labels, theta, weights=(1.0, 0.01, 0.001), grad=T
     return dict(loss=float(loss), grad=g.sum(0), grad_cfg=g, row_absmax=absmax, energy=np.array(es), forces=np.concatenate(fs), virial=np.array(vs))
 
 
+def star_system(st, neigh=None):
+    """a star set of tests/_stars.py as a driver.System in which every atom is owned and is its own owner (nlocal = nall,
+    owner = arange): list row k belongs to atom ilist[k], so per-row and per-atom arrays no longer coincide"""
+    from lammps_mtp_kokkos_amd.driver import System
+    return System(x=st.x, types=st.types, nlocal=st.nall, owner=np.arange(st.nall), box=np.zeros(3), ilist=st.ilist,
+                  first=st.first, neigh=st.neigh if neigh is None else neigh, cutoff=st.rc)
+
+
+def star_set(tables, KL, seed, special=None, order="mixed", shuffle=True):
+    """stars of tests/_stars.py for a potential's species count and cutoff, their exact counts asserted, rows shuffled (not where the order of a row is the point: shuffle = False)"""
+    import _stars
+    Sp, rc = len(tables["species_coeffs"]), float(tables["max_cutoff"])
+    rng = np.random.default_rng(seed)
+    st = _stars.stars(KL, rng, species=Sp, rc=rc, rin=(2.1, rc), rout=(rc, rc + 2.0), order=order, special=special)
+    assert _stars.counts(st) == KL
+    if shuffle:
+        st.neigh = _stars.shuffled_rows(st, rng)
+    return st
+
+
+def row_cotangents(st, seed):
+    """ebar [stars], fbar [nall, 3], vbar [stars, 6]: by list row, by atom, by list row"""
+    rng = np.random.default_rng(seed)
+    n = len(st.ilist)
+    return rng.normal(size=n), rng.normal(size=(st.nall, 3)), rng.normal(size=(n, 6))
+
+
+def by_atom(st, a):
+    """a per-row array on the atoms: out[ilist[k]] = a[k], zero elsewhere (the twin and the device take ebar and vbar by
+    ROW, the oracle's scalar of _train.fd_gradient by ATOM)"""
+    out = np.zeros((st.nall,) + a.shape[1:])
+    out[st.ilist] = a
+    return out
+
+
+def padded_rows(st, a):
+    """a per-row array at the length the twin asks for (nlocal = nall); rows past the list are never read"""
+    out = np.zeros((st.nall,) + a.shape[1:])
+    out[:len(a)] = a
+    return out
+
+
+# K and L of the training and design kernels' edges: tiles of 32 survivors, a compaction sweep of 64 listed entries
+STAR_EDGE_KL = [(K, L) for K in (0, 1, 2, 31, 32, 33, 63, 64, 65, 96, 97) for L in (K, K + 1, 129)] + \
+    [(K, L) for K in (1, 33) for L in (63, 64, 65, 128)]
+
+
+def grid_stride_KL(num_cus, rng):
+    """8 num_cus + 64 rows: more than any launch of the training or design kernel has workgroups (at most 8 per CU), so
+    the last rows are second trips of the first workgroups.  With the full 8 per CU workgroup b < 64 takes row b and then
+    row 8 num_cus + b: a K = 0 row after a three-tile row, a three-tile row after a one-neighbour row, one tile after four"""
+    head = [(K, K + 1) for K in (65, 64, 33, 32, 1, 0, 97, 2)] * 8
+    tail = [(K, K + 1) for K in (0, 1, 33, 2, 65, 0, 3, 1)] * 8
+    mid = [(int(K), int(K)) for K in rng.integers(0, 4, 8 * num_cus - 64)]
+    return head + mid + tail
+
+
+def star_block_ratio(got_rows, want_rows, nrad, Sp, KL, what):
+    """gradient rows of a star set, one row per star: |got - want| / (1e-9 + 1e-10 max |want| over THAT star's row in the
+    block), per block of columns (radial, species, moments) -- the bound of _design.column_ratio with the scale taken per
+    star, so that a three-tile star with entries of 1e6 cannot hide a one-neighbour star (the rule of
+    _stars.per_star_check).  Prints and returns the worst ratio; a miss names the star's (K, L)."""
+    got, want = np.asarray(got_rows, dtype=np.float64), np.asarray(want_rows, dtype=np.float64)
+    assert got.shape == want.shape == (len(KL), want.shape[-1]), (got.shape, want.shape, len(KL))
+    assert np.isfinite(got).all(), what + ": a gradient row is not finite"
+    worst = 0.0
+    for name, a, b in (("radial", 0, nrad), ("species", nrad, nrad + Sp), ("moments", nrad + Sp, want.shape[-1])):
+        if len(KL) == 0 or b == a:
+            continue
+        w = want[:, a:b]
+        ratio = (np.abs(got[:, a:b] - w) / (1e-9 + 1e-10 * np.abs(w).max(1))[:, None]).max(1)
+        s = int(np.argmax(ratio))
+        print("%s %s: worst error / bound %.3e at star %d (K, L) = %s" % (what, name, ratio[s], s, KL[s]))
+        assert ratio[s] <= 1.0, "%s %s: star %d (K, L) = %s misses 1e-9 + 1e-10 max|its row| %.2f-fold" % (
+            what, name, s, KL[s], ratio[s])
+        worst = max(worst, float(ratio[s]))
+    return worst
+
+
 def block_ratio(got, want, nrad, Sp, what):
     """_design.column_ratio per block of columns (radial, species, moments); prints and returns the worst"""
     import _design

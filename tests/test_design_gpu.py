@@ -14,6 +14,7 @@ import _batch  # noqa: E402
 import _cells  # noqa: E402
 import _design  # noqa: E402
 import _stars  # noqa: E402
+import _train  # noqa: E402
 from lammps_mtp_kokkos_amd import capi, md  # noqa: E402
 
 POT = _design.POT
@@ -141,6 +142,19 @@ def test_level16_stars_with_leaf_moments():
     assert _stars.counts(st) == KL
     st.neigh = _stars.shuffled_rows(st, rng)
     _check_stars("W_L16.mtp", st, _design_rows_of_stars("W_L16.mtp", st), "level 16 stars")
+
+
+@pytest.mark.gpu
+def test_more_rows_than_workgroups_second_trips_of_the_grid_stride_loop():
+    """8 CUs + 64 rows, the star set of the training kernel's test of the same name (tests/_train.grid_stride_KL): the
+    launch has at most 8 workgroups per CU, so a workgroup that has done a three-tile row goes on to a K = 0 or one-tile row"""
+    import torch
+    rng = np.random.default_rng(23)
+    KL = _train.grid_stride_KL(torch.cuda.get_device_properties(0).multi_processor_count, rng)
+    st = _stars.stars(KL, rng)
+    assert _stars.counts(st) == KL
+    st.neigh = _stars.shuffled_rows(st, rng)
+    _check_stars("W_L8.mtp", st, _design_rows_of_stars("W_L8.mtp", st), "grid stride, %d stars" % len(KL))
 
 
 # ---- through md.design_cells: the owner fold and the batch -------------------------------------------------------------------

@@ -6,7 +6,8 @@ oracle's scalar with one coefficient changed through its Model pointers (tests/_
 max |gradient|, the floor of the finite difference (it disagrees with itself between its last two extrapolations by up to
 a few 1e-12 of that scale), not of the twin.  Worst ratios measured, |twin - fd| / max |gradient|:
 W_L8 3.4e-12, WRe_L10_cfg 3.8e-13, W_L16 6.2e-13, WRe_L20 3.9e-15, scaling 2.5 1.9e-13, three tiles 8.7e-13, K = 0 2.7e-13,
-1-atom cell 3.8e-12: none above 1e-10."""
+1-atom cell 3.8e-12: none above 1e-10.  Star by star (list row k is not atom k): W_L8 5.1e-12, with an entry on the cutoff
+2.3e-12, five species 1.0e-11, three species R = 9 with an entry on the cutoff 3.2e-12."""
 import functools
 import os
 import subprocess
@@ -20,6 +21,7 @@ import _batch  # noqa: E402
 import _cells  # noqa: E402
 import _design  # noqa: E402
 import _mutate  # noqa: E402
+import _stars  # noqa: E402
 import _train  # noqa: E402
 from lammps_mtp_kokkos_amd import capi, mtpgen  # noqa: E402
 from lammps_mtp_kokkos_amd.driver import design_twin, periodic_system_cell, train_twin  # noqa: E402
@@ -105,6 +107,85 @@ def test_twin_value_is_the_oracle_at_the_files_and_at_a_perturbed_theta(fname, c
         _batch.close(got["eatom"], want["eatom"], "%s %s eatom" % (fname, what), atol=1e-10)
         _batch.close(got["force"], want["force"], "%s %s force" % (fname, what))
         _batch.close(got["vatom"], want["vatom"], "%s %s vatom" % (fname, what), atol=1e-8)
+
+
+# ---- stars: list row k is not atom k, neighbour types missing from a row, an entry on the cutoff ---------------------------
+def _w8(tmp):
+    return os.path.join(POT, "W_L8.mtp")
+
+
+def _five_species(tmp):
+    path = os.path.join(tmp, "five.mtp")
+    mtpgen.write_mtp(mtpgen.random_potential(mtpgen.build_table(6), 5, 4242), path)
+    return path
+
+
+def _nine_radial(tmp):
+    path = os.path.join(tmp, "nine.mtp")
+    mtpgen.write_mtp(mtpgen.random_potential(mtpgen.build_table(8), 3, 7, 1.7, 5.5, 9, 0.37), path)
+    return path
+
+
+STAR_FD_KL = [(1, 1), (1, 2), (2, 3), (33, 40), (65, 129)]
+STAR_FD_CASES = [("W_L8 plain", _w8, None), ("W_L8 edge", _w8, "edge"), ("5 species level 6", _five_species, None),
+                 ("3 species R = 9 edge", _nine_radial, "edge")]
+
+
+@pytest.mark.parametrize("label,make,special", STAR_FD_CASES, ids=[c[0] for c in STAR_FD_CASES])
+def test_twin_rows_of_stars_against_the_oracles_finite_difference_star_by_star(tmp_path, label, make, special):
+    """row k of the twin against the finite difference of the oracle's scalar with the cotangents of star k ONLY, at a
+    perturbed theta; |twin - fd| <= 1e-9 max |row|.  Worst measured 1.1e-11."""
+    path = make(str(tmp_path))
+    orc = Oracle(path)
+    tables = capi.Potential(path).tables()
+    st = _train.star_set(tables, STAR_FD_KL, 61, special)
+    s = _train.star_system(st)
+    theta0 = _train.get_theta(orc)
+    theta = theta0 * (1.0 + 0.05 * np.random.default_rng(2).normal(size=len(theta0)))
+    ebar, fbar, vbar = _train.row_cotangents(st, 8)
+    rows = train_twin(tables, s, theta, _train.padded_rows(st, ebar), fbar, _train.padded_rows(st, vbar))["rows"][:len(st.ilist)]
+    cols = list(range(len(theta))) if len(theta) < 40 else _train.sample_columns(orc, 24)
+    worst = 0.0
+    try:
+        _train.set_theta(orc, theta)
+        for k in range(len(st.ilist)):
+            mine = st.sid == k
+            e_k, v_k = np.zeros(st.nall), np.zeros((st.nall, 6))
+            e_k[st.ilist[k]], v_k[st.ilist[k]] = ebar[k], vbar[k]
+            fd, floor = _train.fd_gradient(orc, s, e_k, fbar * mine[:, None], v_k, cols)
+            scale = np.abs(rows[k]).max()
+            ratio = np.abs(rows[k, cols] - fd).max() / scale
+            print("%s star %d (K, L) = %s: %d columns, worst |twin - fd| / max|row| = %.3e (finite-difference floor %.3e)"
+                  % (label, k, st.KL[k], len(cols), ratio, floor / scale))
+            assert ratio <= 1e-9, (label, k, st.KL[k], ratio)
+            worst = max(worst, ratio)
+    finally:
+        _train.set_theta(orc, theta0)
+    print("%s: worst over the stars %.3e" % (label, worst))
+
+
+@pytest.mark.parametrize("special,order", [(None, "mixed"), ("edge", "mixed"), (None, "straddle")])
+def test_twin_value_of_stars_is_the_oracle_at_a_perturbed_theta(special, order):
+    path = os.path.join(POT, "W_L8.mtp")
+    orc = Oracle(path)
+    tables = _pot(path).tables()
+    st = _train.star_set(tables, _train.STAR_EDGE_KL, 62, special, order, shuffle=order != "straddle")
+    s = _train.star_system(st)
+    theta0 = _train.get_theta(orc)
+    theta = theta0 * (1.0 + 0.05 * np.random.default_rng(2).normal(size=len(theta0)))
+    try:
+        _train.set_theta(orc, theta)
+        r = orc.compute(s.x, s.types, s.ilist, s.first, s.neigh)
+    finally:
+        _train.set_theta(orc, theta0)
+    tw = train_twin(tables, s, theta)
+    n = len(st.ilist)
+    got = dict(f=tw["force"], eatom=_train.by_atom(st, tw["eatom"][:n]), vatom=_train.by_atom(st, tw["vatom"][:n]))
+    ratios = _stars.per_star_ratios(st, got, r)
+    for k, v in ratios.items():
+        w = int(np.argmax(v))
+        print("twin value %s %s %s: worst error / tolerance %.3e at star %d (K, L) = %s" % (special, order, k, v[w], w, st.KL[w]))
+        assert np.isfinite(v).all() and v[w] <= 1.0, (k, w, st.KL[w], v[w])
 
 
 def test_unit_energy_cotangent_rows_are_the_oracles_coeff_ders():

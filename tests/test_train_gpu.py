@@ -1,7 +1,9 @@
 """The training gradient on the device (csrc/mtp_train.hip; Context.train_value, Context.train_vjp, md.loss_cells,
 md.fit_full).  Every entry is judged against the numpy twin (driver.train_twin, itself judged against the oracle's
 finite differences in tests/test_train_cpu.py): values with the rule of tests/_batch.close, rows of the gradient with the
-bound of _design.column_ratio, 1e-9 + 1e-10 max |column|, per block of columns."""
+bound of _design.column_ratio, 1e-9 + 1e-10 max |column|, per block of columns.  The star tests (exact neighbour counts at
+every tile and row-length edge, three and five species, more rows than workgroups) judge values against the oracle and
+rows against the twin per star; their worst ratios are in DESIGN.md 5.3.2."""
 import functools
 import os
 import sys
@@ -16,7 +18,7 @@ import _design  # noqa: E402
 import _mutate  # noqa: E402
 import _stars  # noqa: E402
 import _train  # noqa: E402
-from lammps_mtp_kokkos_amd import capi, md  # noqa: E402
+from lammps_mtp_kokkos_amd import capi, md, mtpgen  # noqa: E402
 from lammps_mtp_kokkos_amd.driver import periodic_system_cell, train_twin  # noqa: E402
 
 POT = _design.POT
@@ -345,6 +347,197 @@ def test_fit_full_level8_from_a_perturbed_radial_block(tmp_path):
     ev = md.evaluate_cells(capi.Context(back, 0), batch, device=dev)
     for k, r in enumerate(ev):
         _batch.close_energy(r["energy"], float(fitted["energy"][k]), len(r["f"]), "energy of configuration %d from the written file" % k)
+
+
+# ---- stars: exact neighbour counts, list rows that are not atoms, more rows than workgroups ----------------------------------
+# Every star is a driver.System with owner = arange(nall) and nlocal = nall (tests/_train.star_system): the device call has
+# nowned = nall, d_owner = NULL, ebar / vbar / eatom / vatom / the gradient rows by LIST ROW and fbar / force by ATOM, and list
+# row k is atom ilist[k] != k.  Value mode is judged against the ORACLE at the perturbed theta, per star
+# (_stars.per_star_ratios); the gradient rows against the twin, per star and block of columns (_train.star_block_ratio; the
+# twin's rows on such stars against the oracle's finite differences: tests/test_train_cpu.py).
+class _Handles:
+    """context, parsed tables and oracle of one potential file"""
+
+    def __init__(self, path):
+        from oracle.pyoracle import Oracle
+        self.pot = capi.Potential(path)
+        self.ctx = capi.Context(self.pot, 0)
+        self.tables = self.pot.tables()
+        self.orc = Oracle(path)
+        self.Sp = len(self.tables["species_coeffs"])
+        self.nrad = len(self.tables["radial_coeffs"])
+
+    def perturbed_theta(self, seed=2):
+        th = self.pot.theta()
+        return th * (1.0 + 0.05 * np.random.default_rng(seed).normal(size=len(th)))
+
+
+@functools.lru_cache(maxsize=None)
+def _handles(fname):
+    return _Handles(os.path.join(POT, fname))
+
+
+def _star_call(ctx, st, theta, ebar, fbar, vbar, owner_t=None, pad=2, value=True, vjp=True):
+    """both modes over all rows of a star set; outputs filled with 7.0 beforehand (forces are accumulated into: zero)"""
+    import torch
+    dev, stream = _device_stream()
+    C = len(theta)
+    ld = C + (C & 1) + pad
+    nrows, nall = len(st.ilist), st.nall
+    ctx.set_neighbors(st.ilist, st.first, st.neigh, nall)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x_t, t_t, th_t = to(st.x), to(st.types), to(theta)
+    own = None if owner_t is None else owner_t.data_ptr()
+    out = {}
+    if value:
+        force = torch.zeros((nall, 3), dtype=torch.float64, device=dev)
+        eatom = torch.full((nrows,), 7.0, dtype=torch.float64, device=dev)
+        vatom = torch.full((nrows, 6), 7.0, dtype=torch.float64, device=dev)
+        ctx.train_value(0, nrows, x_t, t_t, th_t, force, nall, eatom_t=eatom, vatom_t=vatom, owner=own, stream=stream)
+        ctx.synchronize(stream=stream)
+        out.update(eatom=eatom.cpu().numpy(), force=force.cpu().numpy(), vatom=vatom.cpu().numpy())
+    if vjp:
+        rows = torch.full((nrows, ld), 7.0, dtype=torch.float64, device=dev)
+        ctx.train_vjp(0, nrows, x_t, t_t, th_t, rows, nall, ld, ebar_t=to(ebar), fbar_t=to(fbar), vbar_t=to(vbar), owner=own,
+                      stream=stream)
+        ctx.synchronize(stream=stream)
+        r = rows.cpu().numpy()
+        assert not r[:, C:].any(), "padding columns must be zero"
+        out.update(rows=r[:, :C])
+    return out
+
+
+def _judge_stars(h, st, theta, cots, got, what):
+    """value against the oracle at theta, rows against the twin; the exact K = 0 rows; no vacuous comparison"""
+    ebar, fbar, vbar = cots
+    n = len(st.ilist)
+    s = _train.star_system(st)
+    theta0 = _train.get_theta(h.orc)
+    try:
+        _train.set_theta(h.orc, theta)
+        want = h.orc.compute(s.x, s.types, s.ilist, s.first, s.neigh)
+    finally:
+        _train.set_theta(h.orc, theta0)
+    assert got["eatom"].shape == (n,) and got["vatom"].shape == (n, 6) and got["force"].shape == (st.nall, 3)
+    mine = dict(f=got["force"], eatom=_train.by_atom(st, got["eatom"]), vatom=_train.by_atom(st, got["vatom"]))
+    worst = {}
+    for k, v in _stars.per_star_ratios(st, mine, want).items():
+        w = int(np.argmax(v))
+        worst[k] = float(v[w])
+        print("%s value %s: worst error / tolerance %.3e at star %d (K, L) = %s" % (what, k, v[w], w, st.KL[w]))
+        assert np.isfinite(v).all() and v[w] <= 1.0, "%s %s: star %d (K, L) = %s misses its tolerance %.2f-fold" % (
+            what, k, w, st.KL[w], v[w])
+    tw = train_twin(h.tables, s, theta, _train.padded_rows(st, ebar), fbar, _train.padded_rows(st, vbar))["rows"][:n]
+    worst["rows"] = _train.star_block_ratio(got["rows"], tw, h.nrad, h.Sp, st.KL, what + " rows")
+    assert worst["rows"] <= 1.0
+    for k, (K, L) in enumerate(st.KL):
+        c = st.ilist[k]
+        if K == 0:                                           # ebar in the species column and nothing else
+            assert got["rows"][k, h.nrad + st.types[c] - 1] == ebar[k] and np.count_nonzero(got["rows"][k]) == 1, (what, k)
+            assert got["eatom"][k] == theta[h.nrad + st.types[c] - 1] and not got["vatom"][k].any(), (what, k)
+            assert not got["force"][st.sid == k].any(), (what, k)
+        if K >= 2:
+            assert np.abs(tw[k]).max() > 1e-3, (what, k, st.KL[k])
+    return worst
+
+
+def _stars_case(h, KL, seed, special=None, order="mixed", what=""):
+    st = _train.star_set(h.tables, KL, seed, special, order, shuffle=order != "straddle")
+    theta = h.perturbed_theta()
+    cots = _train.row_cotangents(st, seed + 100)
+    _judge_stars(h, st, theta, cots, _star_call(h.ctx, st, theta, *cots), what)
+    return st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("special,order", [(None, "mixed"), ("edge", "mixed"), (None, "straddle")])
+def test_level8_stars_every_tile_and_row_length_edge(special, order):
+    """K in {0, 1, 2, 31, 32, 33, 63, 64, 65, 96, 97} x L in {K, K + 1, 129}, and L in {63, 64, 65, 128} for K in {1, 33}: one
+    to four tiles of 32 on both sides of the "a single tile still holds its tables" shortcut, compaction sweeps of 64.
+    "edge": the last in-cutoff entry at r^2 == r_c^2 bit-exact (kept, contributes exactly zero) and one listed entry a
+    representable step outside (dropped); the plain set is what tests K = 1 and 2 with a neighbour that contributes.
+    "straddle": survivors touching entry 128 on both sides, rows in that order.  Worst ratios: DESIGN.md 5.3.2."""
+    _stars_case(_handles("W_L8.mtp"), _train.STAR_EDGE_KL, 71, special, order, "level 8 stars %s %s" % (special, order))
+
+
+SMALL_KL = [(K, L) for K in (0, 1, 32, 33, 65) for L in (K, K + 1, 129)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("special", [None, "edge"])
+@pytest.mark.parametrize("fname", ["W_L16.mtp", "WRe_L20.mtp"])
+def test_level16_and_two_species_level20_stars(fname, special):
+    _stars_case(_handles(fname), SMALL_KL, 72, special, what="%s stars %s" % (fname, special))
+
+
+# (table level, species, seed, min_dist, max_dist, radial basis size, scaling)
+GENERATED = dict(five_species=(6, 5, 4242, 2.0, 5.0, 8, 1.0), scaling=(10, 2, 99, 2.0, 5.0, 8, 2.5), nine_radial=(8, 3, 7, 1.7, 5.5, 9, 0.37))
+GENERATED_KL = [(K, L) for K in (0, 1, 2, 4, 5, 6, 33, 65) for L in (K, K + 1, 129)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("special", [None, "edge"])
+@pytest.mark.parametrize("which", sorted(GENERATED))
+def test_generated_potentials_three_and_five_species_nine_radial_functions_and_a_scaling(tmp_path, which, special):
+    """Sp = 5 / Sp = 2, scaling = 2.5 / Sp = 3, R = 9, scaling = 0.37, cutoff 5.5: the index of theta's radial block, the
+    scatter by neighbour type with types absent from a tile (stars of 1 to 6 neighbours), the centre's window of the row"""
+    level, Sp, seed, rmin, rmax, R, scaling = GENERATED[which]
+    path = str(tmp_path / (which + ".mtp"))
+    mtpgen.write_mtp(mtpgen.random_potential(mtpgen.build_table(level), Sp, seed, rmin, rmax, R, scaling), path)
+    h = _Handles(path)
+    assert (h.Sp, h.tables["scaling"], h.tables["max_cutoff"]) == (Sp, scaling, rmax) and h.nrad % (Sp * Sp * R) == 0
+    st = _stars_case(h, GENERATED_KL, 73, special, what="%s stars %s" % (which, special))
+    assert set(st.types[st.ilist]) == set(range(1, Sp + 1)), "a centre of every species"
+    small = [k for k, (K, L) in enumerate(st.KL) if 0 < K <= 6]
+    if Sp >= 3:
+        assert any(len(set(st.types[st.neigh[st.first[k]:st.first[k + 1]]])) < Sp for k in small), "a row that lacks a neighbour type"
+
+
+@pytest.mark.gpu
+def test_more_rows_than_workgroups_second_trips_of_the_grid_stride_loop():
+    """8 CUs + 64 rows (the launch has at most 8 workgroups per CU): the images, the radial block and the count are zeroed
+    again and stale tables are not read when a K = 0 or one-tile row follows a three-tile row on the same workgroup"""
+    import torch
+    h = _handles("W_L8.mtp")
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    KL = _train.grid_stride_KL(ncu, np.random.default_rng(74))
+    assert len(KL) == 8 * ncu + 64
+    _stars_case(h, KL, 75, what="grid stride, %d rows" % len(KL))
+
+
+@pytest.mark.gpu
+def test_two_calls_on_one_context_the_second_keeps_nothing_of_the_first():
+    h = _handles("W_L8.mtp")
+    a = _train.star_set(h.tables, [(97, 129), (65, 66), (33, 33)], 76)
+    _star_call(h.ctx, a, h.perturbed_theta(5), *_train.row_cotangents(a, 77))
+    b = _train.star_set(h.tables, [(0, 3), (1, 2), (33, 40), (2, 2), (64, 70), (0, 0)], 78)
+    theta, cots = h.perturbed_theta(6), _train.row_cotangents(b, 79)
+    _judge_stars(h, b, theta, cots, _star_call(h.ctx, b, theta, *cots), "second call")
+
+
+@pytest.mark.gpu
+def test_an_owner_outside_the_owned_atoms_is_reported_and_the_flag_cleared():
+    """a device owner map in which one in-cutoff neighbour's entry equals nowned: build_tile raises flag 3 and gives the
+    neighbour no force row and no fbar (own = -1, never an index); the synchronise reports MTP_ERR_ARG and clears the flag,
+    and the next call with the identity map GIVEN (the d_owner != NULL branch) agrees with the oracle and the twin"""
+    import torch
+    dev, _ = _device_stream()
+    h = _handles("W_L8.mtp")
+    ctx = capi.Context(h.pot, 0)
+    st = _train.star_set(h.tables, [(3, 4), (2, 2), (33, 34), (0, 1)], 80)
+    theta, cots = h.perturbed_theta(), _train.row_cotangents(st, 81)
+    d = st.x[st.neigh[st.first[0]:st.first[1]]] - st.x[st.ilist[0]]
+    j = int(st.neigh[st.first[0] + int(np.argmin((d * d).sum(1)))])           # an in-cutoff neighbour of star 0
+    owner = np.arange(st.nall, dtype=np.int32)
+    bad = owner.copy()
+    bad[j] = st.nall
+    for mode in (dict(vjp=False), dict(value=False)):
+        with pytest.raises(capi.MtpError, match="outside") as ei:
+            _star_call(ctx, st, theta, *cots, owner_t=torch.from_numpy(bad).to(dev), **mode)
+        assert ei.value.code == -20
+    h2 = _Handles.__new__(_Handles)
+    h2.__dict__.update(h.__dict__, ctx=ctx)
+    _judge_stars(h2, st, theta, cots, _star_call(ctx, st, theta, *cots, owner_t=torch.from_numpy(owner).to(dev)), "after the flag")
 
 
 # ---- error paths and untouched paths ---------------------------------------------------------------------------------------
