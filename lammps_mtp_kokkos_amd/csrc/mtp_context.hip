@@ -512,6 +512,18 @@ void fill_sizes(const mtp_potential &pot, MtpDevParams &b)
   // the same table in the argument block when it fits (mtp_device.hpp); all zero otherwise
   const bool lv_fit = pot.level_offset.size() == (size_t) pot.normal_levels + 2 && pot.level_offset.size() <= MTP_SHAPE_ARR_LEN;
   for (int k = 0; k < MTP_SHAPE_ARR_LEN; k++) b.level_rows[k] = lv_fit && k < (int) pot.level_offset.size() ? pot.level_offset[k] : 0;
+  // the slot tables likewise (mtp_device.hpp): table structure only, numbered by build_slots from the alpha tables
+  unsigned long long mu_bits = 0;
+  if (pot.radial_func_count <= 4 && pot.slot_count <= 32)
+    for (int s = 0; s < pot.slot_count; s++) mu_bits |= (unsigned long long) (pot.slot_mu[s] & 3) << (2 * s);
+  b.slot_mu_lo = (int) (unsigned) mu_bits;
+  b.slot_mu_hi = (int) (unsigned) (mu_bits >> 32);
+  const bool sr_fit = pot.radial_func_count <= MTP_SLOT_ROWS_MU && pot.slot_count <= 127 && pot.max_alpha_index_basic <= MTP_PSTRIDE;
+  for (int k = 0; k < MTP_SHAPE_TAB_LEN; k++) {
+    const int mu = k / MTP_PSTRIDE, nu = k % MTP_PSTRIDE;
+    const bool in = sr_fit && mu < pot.radial_func_count && nu < pot.max_alpha_index_basic;
+    b.slot_row[k] = (signed char) (in ? pot.slot_of[(size_t) mu * pot.max_alpha_index_basic + nu] : -1);
+  }
   b.nseed = (int) pot.seed_idx.size();
   b.Ad = pot.stored_moment_count;
   b.Am = b.Ad;                      // per launch: the grade instantiation keeps the leaves' values too
@@ -2307,6 +2319,14 @@ int mtp_plan_fixed_fields(const mtp_potential *pot, int num_cus, int inum, int m
     s += "\n";                                                                            \
   }
   MTP_SHAPE_ARR_FIELDS(MTP_X)
+#undef MTP_X
+#define MTP_X(f)                                                                               \
+  {                                                                                            \
+    s += #f "=";                                                                               \
+    for (int k = 0; k < MTP_SHAPE_TAB_LEN; k++) s += (k ? "," : "") + std::to_string((int) p.f[k]); \
+    s += "\n";                                                                                 \
+  }
+  MTP_SHAPE_TAB_FIELDS(MTP_X)
 #undef MTP_X
   if ((int) s.size() + 1 > buflen) return MTP_ERR_LIMIT;
   std::memcpy(buf, s.c_str(), s.size() + 1);

@@ -11,6 +11,7 @@
 #define MTP_MAX_WPB 12      // wavefronts per workgroup: 8 (512 threads) in the 2-per-SIMD build, 12 in the 3-per-SIMD build
 #define MTP_PITCH 33        // doubles per row of the per-wavefront LDS tables (32 neighbour columns + 1: odd pitch)
 #define MTP_PSTRIDE 12      // slot ids per mu in the LDS blob (nu = 0..11, -1 padded)
+#define MTP_SLOT_ROWS_MU 4  // radial functions whose slot ids the argument block repeats (slot_row): the nodg layouts' Mu <= 4
 
 // A times row packed in 8 bytes: lo = 8 a0 | 8 a1 << 16, hi = 8 a3 | (mult & 0xffff) << 16 -- BYTE offsets of the moments
 // in the per-atom LDS image (moment indices below 8192)
@@ -112,7 +113,16 @@ struct MtpDevParams {
   int m_doubles;           // doubles of the moment region = max(A, coef_total, 16)
   int d_doubles;           // doubles of the adjoint region = A
   float inv_mu;            // 1 / Mu
+  // The slot tables of the blob once more, behind everything else (no field above moves).  Shape fields: a fixed-shape
+  // kernel has the g row of every (mu, nu) and the radial function of every slot as constants, and the launcher matches
+  // them here.  The generic kernels read the blob's copies.
+  // slot_mu_lo / _hi: mu of slot s in bits [2 s, 2 s + 2) of the 64-bit word (off_smu; SlotMu::bits), zero unless
+  // Mu <= 4 and nslot <= 32; slot_row[mu * MTP_PSTRIDE + nu]: the slot (= g row) of f_mu / r^nu or -1 (off_slot), all -1
+  // unless Mu <= MTP_SLOT_ROWS_MU and nslot <= 127
+  int slot_mu_lo, slot_mu_hi;
+  signed char slot_row[MTP_SLOT_ROWS_MU * MTP_PSTRIDE];
 };
+static_assert(sizeof(MtpDevParams) <= 12 * 64, "the force kernel's argument block: twelve 64-byte lines (kernarg_touch)");
 
 // lane-grid shape of the candidate-vector kernel for B basics: KL k-lanes x KB basics per lane; -1 when B is too large
 int mtp_pick_shape(int B, int *KL, int *KB);

@@ -748,6 +748,12 @@ const char *mtp_kernel_build_flags()
 #if MTP_LEVEL_ARGS != 1
       "MTP_LEVEL_ARGS=" MTP_STR(MTP_LEVEL_ARGS) " "
 #endif
+#if MTP_SLOT_ARGS != 1
+      "MTP_SLOT_ARGS=" MTP_STR(MTP_SLOT_ARGS) " "
+#endif
+#if MTP_FP_REGS != 1
+      "MTP_FP_REGS=" MTP_STR(MTP_FP_REGS) " "
+#endif
 
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
       "MTP_GRADE_TPB=" MTP_STR(MTP_GRADE_TPB) " "

@@ -4,8 +4,8 @@
 // A candidate field is decided by the potential's table structure (the alpha_* tables, the species count, R) and by
 // the LDS plan (mtp_plan_launch), never by the fit, the system or the call.  A shape is a struct with one static
 // constexpr member per field it fixes (and a name and the kernel's template arguments); a field it does not list stays a
-// read of the argument block.  The two lists below are the only enumeration of the candidates: the kernel's accessor
-// (SHF / SHA, mtp_wave_body.hpp), the launcher's field-by-field match (mtp_shape_matches) and the generator of
+// read of the argument block.  The three lists below are the only enumeration of the candidates: the kernel's accessor
+// (SHF / SHA / SHT, mtp_wave_body.hpp), the launcher's field-by-field match (mtp_shape_matches) and the generator of
 // mtp_fixed_shapes.hpp (mtp_plan_fixed_fields -> scripts/gen_fixed_shapes.py) are all expanded from them.
 #pragma once
 
@@ -19,10 +19,14 @@
   X(coef_total) X(coef_dense) X(blob_bytes) X(off_rows) X(off_level) X(off_slot) X(off_radial) X(off_seed_idx)        \
   X(off_seed_val) X(off_map) X(off_lin) X(off_pack) X(off_fwd) X(off_smu) X(off_coef) X(off_leaf_cf) X(off_leaf_cb)   \
   X(off_seg_fwd) X(off_seg_bwd) X(rows_in_lds) X(tgt_in_lds) X(scalars_in_lds) X(dg_mode) X(fp_row) X(pow_row)        \
-  X(dg_off) X(w_m) X(w_d) X(w_coef) X(w_nb) X(tab_rows) X(ov_doubles) X(m_doubles) X(d_doubles)
+  X(dg_off) X(w_m) X(w_d) X(w_coef) X(w_nb) X(tab_rows) X(ov_doubles) X(m_doubles) X(d_doubles)                     \
+  X(slot_mu_lo) X(slot_mu_hi)
 // int[MTP_PSTRIDE + 2] fields (a shape gives them as static constexpr int f(int k))
 #define MTP_SHAPE_ARR_FIELDS(X) X(deg_first) X(deg_coef) X(level_rows)
 #define MTP_SHAPE_ARR_LEN (MTP_PSTRIDE + 2)
+// signed char[MTP_SLOT_ROWS_MU * MTP_PSTRIDE] fields, indexed mu * MTP_PSTRIDE + nu (a shape gives them like the arrays)
+#define MTP_SHAPE_TAB_FIELDS(X) X(slot_row)
+#define MTP_SHAPE_TAB_LEN (MTP_SLOT_ROWS_MU * MTP_PSTRIDE)
 
 // the generic shape: nothing fixed
 struct ShapeGeneric {
@@ -36,6 +40,7 @@ namespace mtp_shape {
   template <class SH> struct has_##f<SH, std::void_t<decltype(&SH::f)>> : std::true_type {};
 MTP_SHAPE_INT_FIELDS(MTP_X)
 MTP_SHAPE_ARR_FIELDS(MTP_X)
+MTP_SHAPE_TAB_FIELDS(MTP_X)
 #undef MTP_X
 
 // the launch's values equal the shape's over exactly the fields the shape fixes
@@ -50,6 +55,11 @@ template <class SH> bool matches(const MtpDevParams &p)
   if constexpr (has_##f<SH>::value) \
     for (int k = 0; k < MTP_SHAPE_ARR_LEN; k++) ok = ok && p.f[k] == SH::f(k);
   MTP_SHAPE_ARR_FIELDS(MTP_X)
+#undef MTP_X
+#define MTP_X(f)                    \
+  if constexpr (has_##f<SH>::value) \
+    for (int k = 0; k < MTP_SHAPE_TAB_LEN; k++) ok = ok && p.f[k] == SH::f(k);
+  MTP_SHAPE_TAB_FIELDS(MTP_X)
 #undef MTP_X
   return ok;
 }

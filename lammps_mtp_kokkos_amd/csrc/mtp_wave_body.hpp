@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "mtp_device.hpp"
 
@@ -45,10 +46,69 @@ MTP_SHAPE_INT_FIELDS(MTP_X)
     else return kp->f[k];                                                         \
   }
 MTP_SHAPE_ARR_FIELDS(MTP_X)
+MTP_SHAPE_TAB_FIELDS(MTP_X)
 #undef MTP_X
 }   // namespace shape_get
 #define SHF(f) (shape_get::f<SH>(kp))
 #define SHA(f, k) (shape_get::f<SH>(kp, (k)))
+#define SHT(f, k) (shape_get::f<SH>(kp, (k)))
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
+template <class F, int... I> __device__ __forceinline__ void static_for(F &&f, std::integer_sequence<int, I...>)
+{
+  (f(std::integral_constant<int, I>()), ...);
+}
+
+// The slot tables of a shape that fixes them (MtpDevParams::slot_row, slot_mu_lo / _hi).  Both are atom-invariant table
+// structure, yet read from the LDS blob the tile build waits for three 16-byte reads of slot[] at the head of every
+// radial function before a store address exists, tests every row index (an EXEC region each) and multiplies it by
+// the pitch, and the kernel entry forms the slot -> mu word by two ballots.  slot_ct: the tile build takes the rows
+// from the shape (build_tile) and SlotMu::bits is the shape's constant.  The generic kernels keep the reads.
+#ifndef MTP_SLOT_ARGS
+#define MTP_SLOT_ARGS 1   // 0: the fixed shapes read slot[] and smu[] from the blob too, for A/B runs
+#endif
+template <class SH>
+constexpr bool slot_rows_ct = MTP_SLOT_ARGS && mtp_shape::has_slot_row<SH>::value && mtp_shape::has_Mu<SH>::value &&
+    mtp_shape::has_P<SH>::value && mtp_shape::has_R<SH>::value;
+template <class SH>
+constexpr bool slot_mu_shape = mtp_shape::has_slot_mu_lo<SH>::value && mtp_shape::has_slot_mu_hi<SH>::value &&
+    mtp_shape::has_nslot<SH>::value && mtp_shape::has_Mu<SH>::value;
+template <class SH> constexpr bool slot_mu_ct = MTP_SLOT_ARGS && slot_mu_shape<SH>;
+template <class SH> constexpr unsigned long long slot_mu_bits()
+{
+  if constexpr (slot_mu_shape<SH>) return ((unsigned long long) (unsigned) SH::slot_mu_hi << 32) | (unsigned) SH::slot_mu_lo;
+  else return 0ull;   // (never used: a shape without the map)
+}
+template <class SH> __device__ __forceinline__ int slot_mu_of(int s) { return (int) (slot_mu_bits<SH>() >> (2 * s)) & 3; }
+// f' rows of the force phase from registers (nodg layouts): the radial derivatives never left the wavefront -- lane
+// (n, h) parked f'_h and f'_{h+2} of neighbour n in the tile build, lane (n, 1 - h) the other two.  One exchange between
+// the halves (v_permlane32_swap with both operands equal leaves the low half's value in one register and the high
+// half's in the other, in every lane: pair_sum32) hands all four to both, and where the shape fixes the slot -> mu map
+// and the slots of every rank, each slot visit takes the register of its mu: no f' rows are written (fp_from_parked),
+// no fence, no read per slot visit.  Same bits as the stored and re-read value, same arithmetic after it.
+#ifndef MTP_FP_REGS
+#define MTP_FP_REGS 1   // 0: the f' rows go through LDS in the fixed shapes too, for A/B runs
+#endif
+template <class SH>
+constexpr bool fp_regs_ct = MTP_FP_REGS && slot_mu_shape<SH> && mtp_shape::has_deg_first<SH>::value;
+#define MTP_FP_N 4   // f'_0 .. f'_3: Mu <= 4 in the nodg layouts
+__device__ __forceinline__ void fp_exchange(const double (&park)[2], double (&F)[MTP_FP_N])
+{
+#pragma unroll
+  for (int mi = 0; mi < 2; mi++) {
+    const long long b = __double_as_longlong(park[mi]);
+    const unsigned lo = (unsigned) b, hi = (unsigned) (b >> 32);
+    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto c = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    F[2 * mi] = __longlong_as_double((long long) (((unsigned long long) c[0] << 32) | a[0]));       // half 0 parked mu = 2 mi
+    F[2 * mi + 1] = __longlong_as_double((long long) (((unsigned long long) c[1] << 32) | a[1]));   // half 1: mu = 2 mi + 1
+  }
+}
+// F[mu]: a chain of selects, so that F stays in registers whatever mu is; it folds to one register where mu is a constant
+__device__ __forceinline__ double fp_pick(const double (&F)[MTP_FP_N], int mu)
+{
+  return mu == 0 ? F[0] : mu == 1 ? F[1] : mu == 2 ? F[2] : F[3];
+}
 
 // f[idx] += v.  Default: native fp64 HBM atomics (the sum depends on the arrival order in the last bits).
 // Deterministic mode (mtp_context_set_deterministic, tests / reproducible goldens): the contributions are added as
@@ -105,6 +165,16 @@ template <int PITCH> struct WaveLds {
 // with_dg: write the dg rows; do_park (nodg layouts): park[] receives f'_mu(r) of this lane's neighbour for its radial
 // functions mu = h, h + 2 (park[0..1]), from which fp_from_parked() writes the f' rows ahead of the force phase.
 #define MTP_PARK 2   // radial functions per half-wavefront that can be parked: Mu <= 4
+// rows between the g rows of radial functions 2 mi and 2 mi + 1 at the first nu where both have one (0: nowhere)
+template <class SH, int MI> constexpr int slot_delta()
+{
+  if (2 * MI + 1 < SH::Mu)
+    for (int nu = 0; nu < SH::P; nu++) {
+      const int r0 = SH::slot_row(2 * MI * MTP_PSTRIDE + nu), r1 = SH::slot_row((2 * MI + 1) * MTP_PSTRIDE + nu);
+      if (r0 >= 0 && r1 >= 0) return r1 - r0;
+    }
+  return 0;
+}
 template <int PITCH, class SH>
 __device__ __forceinline__ void build_tile(KP kp, const BlockTables &bt, const WaveLds<PITCH> &w,
                                            int t0, int cnt, int ntp, bool gather, bool powers, bool with_dg, bool do_park,
@@ -168,6 +238,58 @@ __device__ __forceinline__ void build_tile(KP kp, const BlockTables &bt, const W
         qv[ri] = 2.0 * ksi * qv[ri - 1] - qv[ri - 2];
         ev[ri] = 2.0 * (mult * qv[ri - 1] + ksi * ev[ri - 1]) - ev[ri - 2];
       }
+      if constexpr (slot_rows_ct<SH>) {
+        // rows from the shape: radial functions 2 mi (half 0) and 2 mi + 1 (half 1) of step mi.  Where both have a row
+        // for nu and the two rows lie DELTA apart like the first such pair, the address is this half's column base
+        // (col, + DELTA rows in half 1) plus an immediate; other pairs take one select between two constants; a row
+        // of one half only is stored by that half; (mu, nu) without a row emit nothing.
+        static_assert(SH::Mu <= 2 * MTP_PARK && SH::Mu <= MTP_SLOT_ROWS_MU && SH::P <= MTP_PSTRIDE && SH::R == 8, "slot_row: the nodg tables");
+        double dpark[MTP_PARK] = {0.0, 0.0};
+        static_for([&](auto MI) {
+          constexpr int mi = decltype(MI)::value, mu0 = 2 * mi, mu1 = 2 * mi + 1;
+          if constexpr (mu0 < SH::Mu) {
+            constexpr bool two = mu1 < SH::Mu;
+            const int mu = two ? mu0 + h : mu0;
+            if (two || h == 0) {
+              const double2 *c2 = reinterpret_cast<const double2 *>(bt.radial + (mul24(itype * SHF(Sp) + jt, Mu) + mu) * 8);
+              const double2 c01 = c2[0], c23 = c2[1], c45 = c2[2], c67 = c2[3];
+              const double cc[8] = {c01.x, c01.y, c23.x, c23.y, c45.x, c45.y, c67.x, c67.y};
+              double val = cc[0] * qv[0], der = cc[0] * ev[0];
+#pragma unroll
+              for (int ri = 1; ri < 8; ri++) {
+                val = fma(cc[ri], qv[ri], val);
+                der = fma(cc[ri], ev[ri], der);
+              }
+              constexpr int delta = slot_delta<SH, mi>();
+              double *colh = col + (h ? delta * PITCH : 0);
+              double rp = 1.0;
+              static_for([&](auto NU) {
+                constexpr int nu = decltype(NU)::value;
+                constexpr int r0 = SH::slot_row(mu0 * MTP_PSTRIDE + nu), r1 = two ? SH::slot_row(mu1 * MTP_PSTRIDE + nu) : -1;
+                const double g = val * rp;
+                auto put = [&](double *gp) {
+                  *gp = g;                                                       // f_mu / r^nu
+                  if (with_dg) gp[SHF(dg_off)] = der * rp - nu * g * inv;         // d/dr (f_mu / r^nu)
+                };
+                if constexpr (r0 >= 0 && r1 >= 0) {
+                  if constexpr (r1 - r0 == delta) put(colh + r0 * PITCH);
+                  else put(col + (h ? r1 * PITCH : r0 * PITCH));
+                } else if constexpr (r0 >= 0) {
+                  if (h == 0) put(col + r0 * PITCH);
+                } else if constexpr (r1 >= 0) {
+                  if (h == 1) put(col + r1 * PITCH);
+                }
+                rp *= inv;
+              }, std::make_integer_sequence<int, SH::P>());
+              dpark[mi] = der;
+            }
+          }
+        }, std::make_integer_sequence<int, MTP_PARK>());
+        if (do_park) {
+          park[0] = dpark[0];
+          park[1] = dpark[1];
+        }
+      } else
       each_mu([&](int mu) {
         const int4 *sl4 = reinterpret_cast<const int4 *>(bt.slot + mu * MTP_PSTRIDE);
         const int4 sa = sl4[0], sb = sl4[1], sc = sl4[2];
@@ -706,10 +828,12 @@ template <bool PACKED> struct SlotMu {
   }
 };
 
-template <int NU, int DEG, int PITCH, bool GRADE, bool NODG, class SH, class SMU>
+// FPR (fp_regs_ct, NODG only): f'_mu of this lane's neighbour comes from F[mu] instead of row fp_row + mu.
+template <int NU, int DEG, int PITCH, bool GRADE, bool NODG, class SH, class SMU, bool FPR = false>
 __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoef, unsigned pcoef_l, int part, double x,
                                              double y, double z, double *m, double &UA, double &VA, double &UB,
-                                             double &VB, const SMU &smu, double inv, double rw, double *W)
+                                             double &VB, const SMU &smu, double inv, double rw, double *W,
+                                             const double (&F)[MTP_FP_N])
 {
   if constexpr (NU <= DEG) {
     constexpr int C = NU * (NU + 1) / 2;   // monomials of degree NU-1
@@ -728,7 +852,9 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
           // the slot, hence mu, is wave-uniform in this pass
           const int mu = smu.template uniform<NODG, GRADE>(s0 + it);
           const double g = lds_ld(cg, 0);
-          const double dg = NODG ? lds_ld(pfp + 8u * (unsigned) (mu * PITCH), 0) : lds_ld(cg + dgo, 0);   // NODG: f'_mu (mu: SGPR)
+          double dg;
+          if constexpr (FPR) dg = fp_pick(F, slot_mu_of<SH>(s0 + it));
+          else dg = NODG ? lds_ld(pfp + 8u * (unsigned) (mu * PITCH), 0) : lds_ld(cg + dgo, 0);   // NODG: f'_mu (mu: SGPR)
           const double G = poly_sum<C>(ca, m);
           UA = fma(g, G, UA);
           VA = fma(dg * (NODG ? rwn : inv_nu), G, VA);
@@ -753,7 +879,14 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
         // (the halves hold different slots, hence different mu: a per-lane value here)
         const int mu_raw = smu.template per_lane<NODG, GRADE>(s0 + sc);
         const double g_raw = lds_ld(cg, 0);
-        const double dg_raw = NODG ? lds_ld(pfp + (unsigned) mul24(mu_raw, 8 * PITCH), 0) : lds_ld(cg + dgo, 0);
+        double dg_raw;
+        if constexpr (FPR) {   // the halves' slots s0 + 2 it and s0 + 2 it + 1 are uniform: one select between their registers
+          const double f0 = fp_pick(F, slot_mu_of<SH>(s0 + 2 * it));
+          const double f1 = 2 * it + 1 < cnt ? fp_pick(F, slot_mu_of<SH>(s0 + 2 * it + 1)) : 0.0;
+          dg_raw = part ? f1 : f0;
+        } else {
+          dg_raw = NODG ? lds_ld(pfp + (unsigned) mul24(mu_raw, 8 * PITCH), 0) : lds_ld(cg + dgo, 0);
+        }
         const double G = poly_sum<C>(cb, m);
         const double g = ok ? g_raw : 0.0, dg = ok ? dg_raw : 0.0;
         UB = fma(g, G, UB);
@@ -773,7 +906,7 @@ __device__ __forceinline__ void force_degree(KP kp, unsigned pcol, unsigned pcoe
         m[C + NU] = z * m[T0 + NU - 1];
 #pragma unroll
         for (int i = 0; i < C; i++) m[i] *= x;
-        force_degree<NU + 1, DEG, PITCH, GRADE, NODG, SH>(kp, pcol, pcoef, pcoef_l, part, x, y, z, m, UA, VA, UB, VB, smu, inv, rw * inv, W);
+        force_degree<NU + 1, DEG, PITCH, GRADE, NODG, SH, SMU, FPR>(kp, pcol, pcoef, pcoef_l, part, x, y, z, m, UA, VA, UB, VB, smu, inv, rw * inv, W, F);
       }
     }
   }

@@ -18,6 +18,8 @@
   // The 3-per-SIMD build is planned with the dg-free layouts only (its table shapes have Mu <= 4), so the dg paths are
   // compiled out of it; the 2-per-SIMD build takes either (uniform flag).
   constexpr bool NODG_CT = WPS == 3;
+  // f' of the force phase from registers: the dg-free build of a shape that fixes the slot -> mu map (mtp_wave_body.hpp)
+  constexpr bool FP_REGS = NODG_CT && MTP_MU_BITS && fp_regs_ct<SH>;
   constexpr int NG = 64 / KL;            // neighbour groups in the wavefront
   constexpr int NPG = NT / NG;           // neighbours per group per tile
   static_assert(NT == 32, "the force phase maps lanes to (32 neighbours) x (2 halves)");
@@ -91,7 +93,9 @@
   // (not in the KL = 16 grade build: there the SGPR pair costs a twelfth spilled VGPR dword)
   constexpr bool MU_PACKED = MTP_MU_BITS && WPS == 3 && !(GRADE && KL == 16);
   SlotMu<MU_PACKED> smu{bt.smu, 0ull};
-  if constexpr (MU_PACKED) {   // lane s holds mu(s): bit 0 of every slot by one ballot, bit 1 by another, interleaved
+  if constexpr (MU_PACKED && slot_mu_ct<SH>) {   // the shape's constant
+    smu.bits = slot_mu_bits<SH>();
+  } else if constexpr (MU_PACKED) {   // lane s holds mu(s): bit 0 of every slot by one ballot, bit 1 by another, interleaved
     const int mu_l = lane < min(SHF(nslot), 32) ? bt.smu[lane] : 0;
     const unsigned long long b0 = __ballot((mu_l & 1) != 0), b1 = __ballot((mu_l & 2) != 0);
     auto spread = [](unsigned long long x) {   // bit k -> bit 2 k (k < 32)
@@ -469,7 +473,10 @@
         const int t0 = tile * NT, nt = min(NT, cnt - t0), ntp = ((nt + NG - 1) / NG) * NG;
         if (ntiles > 1 || rebuild)   // (single-tile atoms in the persistent layouts: the g rows and park[] of the tile build stand)
           build_tile<PITCH, SH>(kp, bt, w, t0, cnt, ntp, ntiles > 1, false, !nodg, nodg, park, xi0, xi1, xi2, i, itype, lane);
-        if (nodg) fp_from_parked<PITCH, SH>(kp, w, ntp, park, lane);
+        // f' of the tile: the Mu rows behind the coefficient blocks, or all four in registers of both halves (fp_regs_ct)
+        double Fp[MTP_FP_N] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (FP_REGS) fp_exchange(park, Fp);
+        else if (nodg) fp_from_parked<PITCH, SH>(kp, w, ntp, park, lane);
         // columns past ntp hold stale (finite or not) data: their lanes are masked at the end
         const double x = w.nbx[n], y = w.nby[n], z = w.nbz[n], inv = w.nbi[n];
         double UA = 0.0, VA = 0.0, UB = 0.0, VB = 0.0, S0 = 0.0;
@@ -488,7 +495,8 @@
               const int sidx = s4 + i;
               if (i == 0 || sidx < n0) {   // (uniform)
                 const int mu = nodg ? smu.template uniform<true, GRADE>(sidx) : smu.template uniform<false, GRADE>(sidx);
-                fmac_row_bcast1<i>(S0, c, lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0));
+                if constexpr (FP_REGS) fmac_row_bcast1<i>(S0, c, fp_pick(Fp, slot_mu_of<SH>(sidx)));
+                else fmac_row_bcast1<i>(S0, c, lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0));
                 if (GRADE) {
                   const double dk = row_bcast<i>(c);
 #pragma unroll
@@ -505,7 +513,8 @@
           for (int sidx = 0; sidx < n0; sidx++) {
             const double dk = w.coef[SHA(deg_coef, 0) + sidx];
             const int mu = nodg ? smu.template uniform<true, GRADE>(sidx) : smu.template uniform<false, GRADE>(sidx);
-            S0 = fma(lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0), dk, S0);
+            if constexpr (FP_REGS) S0 = fma(fp_pick(Fp, slot_mu_of<SH>(sidx)), dk, S0);
+            else S0 = fma(lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0), dk, S0);
             if (GRADE) {
 #pragma unroll
               for (int v = 0; v < 4; v++) Wm[v] += (mu == v && part == 0) ? dk : 0.0;
@@ -516,12 +525,12 @@
         double mono[DEG * (DEG + 1) / 2];
         mono[0] = 1.0;
         if (nodg) {
-          force_degree<1, DEG, PITCH, GRADE, true, SH>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, smu, inv, inv, Wm);
+          force_degree<1, DEG, PITCH, GRADE, true, SH, SlotMu<MU_PACKED>, FP_REGS>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, smu, inv, inv, Wm, Fp);
           // dg_s / nu = f'_mu r^-nu / nu - g_s / r: the second term of every slot at once
           VA = fma(-inv, UA, VA);
           VB = fma(-inv, UB, VB);
         } else if constexpr (!NODG_CT) {
-          force_degree<1, DEG, PITCH, GRADE, false, SH>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, smu, inv, inv, Wm);
+          force_degree<1, DEG, PITCH, GRADE, false, SH>(kp, pcol, pcoef, pcoef_l, part, x, y, z, mono, UA, VA, UB, VB, smu, inv, inv, Wm, Fp);
         }
         if (fused) {
           // c[jt][mu][ri] += sum_n [type_n = jt] Q_ri(r_n) W_mu(n)  (pair_mtp_extrapolation.cpp:193-198, 323-329):
