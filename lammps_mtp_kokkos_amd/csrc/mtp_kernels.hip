@@ -754,6 +754,12 @@ const char *mtp_kernel_build_flags()
 #if MTP_FP_REGS != 1
       "MTP_FP_REGS=" MTP_STR(MTP_FP_REGS) " "
 #endif
+#if MTP_BLOCK_REGS != 1
+      "MTP_BLOCK_REGS=" MTP_STR(MTP_BLOCK_REGS) " "
+#endif
+#if MTP_ROW_REGS != 1
+      "MTP_ROW_REGS=" MTP_STR(MTP_ROW_REGS) " "
+#endif
 
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
       "MTP_GRADE_TPB=" MTP_STR(MTP_GRADE_TPB) " "

@@ -109,6 +109,23 @@ __device__ __forceinline__ double fp_pick(const double (&F)[MTP_FP_N], int mu)
 {
   return mu == 0 ? F[0] : mu == 1 ? F[1] : mu == 2 ? F[2] : F[3];
 }
+// Row offsets of the basic-moment blocks kept across the atom loop (3-per-SIMD force build, one block per lane).  The
+// twelve LDS addresses of a lane's block are the wavefront's table base plus row x pitch, the rows decoded from three
+// descriptor words of the blob: the same for every atom, yet formed per atom since the twelve finished addresses did
+// not fit beside the rest of the loop.  Their row byte offsets (below 2^16: tab_rows x 8 PITCH) do, as 16-bit halves of
+// six registers, and an address per atom is then one add of the base and a 16-bit word.  The descriptors are table
+// contents and are still read from the blob, once per wavefront.  Not in the grade shape: that build has no register
+// to spare.
+#ifndef MTP_BLOCK_REGS
+#define MTP_BLOCK_REGS 1   // 0: the block addresses are decoded from the blob per atom, for A/B runs
+#endif
+template <class SH> constexpr bool block_regs_shape()
+{
+  if constexpr (mtp_shape::has_pow_row<SH>::value && mtp_shape::has_P<SH>::value && mtp_shape::has_tab_rows<SH>::value)
+    return !SH::kGRADE && SH::kWPS == 3 && SH::kNB == 1 && SH::tab_rows * 8 * SH::kPITCH < 65536;
+  else return false;
+}
+template <class SH> constexpr bool block_regs_ct = MTP_BLOCK_REGS && block_regs_shape<SH>();
 
 // f[idx] += v.  Default: native fp64 HBM atomics (the sum depends on the arrival order in the last bits).
 // Deterministic mode (mtp_context_set_deterministic, tests / reproducible goldens): the contributions are added as
@@ -513,6 +530,100 @@ __device__ __forceinline__ void products_backward(KP kp, const MtpRow8 *rows, co
       backward_level<U>(rows + beg + lane, (level_row<SH>(level, l + 1) - beg) >> 6, M, D);
       wave_fence();
     }
+  }
+}
+
+// Packed rows of the short levels kept across the atom loop.  A level of one or two blocks is one trip of its pass, and
+// the trip starts with a row read that its operand reads wait for: latency the level cannot hide.  The rows are the
+// same for every atom, so where the shape fixes the level table (level_ct: which levels are short is then a constant)
+// and keeps the rows in the LDS blob, each lane loads the rows of those blocks once per wavefront, from the blob (rows
+// are table contents, not shape), and both passes take them from registers: same rows, same lanes, same order.
+#ifndef MTP_ROW_REGS
+#define MTP_ROW_REGS 1   // 0: every level reads its rows per atom, for A/B runs
+#endif
+constexpr int ROW_KEEP_LEVEL = 2;   // blocks of a level that is kept (one trip at MTP_PU = 2)
+constexpr int ROW_KEEP_MAX = 3;     // blocks kept in all: two registers each
+template <class SH> constexpr int level_blocks(int l) { return (SH::level_rows(l + 1) - SH::level_rows(l)) >> 6; }
+template <class SH> constexpr bool level_kept(int l) { return level_blocks<SH>(l) >= 1 && level_blocks<SH>(l) <= ROW_KEEP_LEVEL; }
+// blocks kept of the levels below l (l = nlevels: of all levels)
+template <class SH> constexpr int kept_before(int l)
+{
+  int n = 0;
+  for (int k = 0; k < l; k++)
+    if (level_kept<SH>(k)) n += level_blocks<SH>(k);
+  return n;
+}
+template <class SH> constexpr bool row_regs_shape()
+{
+  if constexpr (level_ct<SH> && mtp_shape::has_rows_in_lds<SH>::value)
+    return !SH::kGRADE && SH::rows_in_lds == 1 && kept_before<SH>(SH::nlevels) >= 1 &&
+        kept_before<SH>(SH::nlevels) <= ROW_KEEP_MAX;
+  else return false;
+}
+template <class SH> constexpr bool row_regs_ct = MTP_ROW_REGS && row_regs_shape<SH>();
+template <class SH> constexpr int kept_count()
+{
+  if constexpr (row_regs_ct<SH>) return kept_before<SH>(SH::nlevels);
+  else return 1;   // (an array nobody reads)
+}
+template <class SH, int L, int NK> __device__ __forceinline__ void load_kept_rows(const MtpRow8 *rows, MtpRow8 (&kr)[NK], int lane)
+{
+  if constexpr (L < SH::nlevels) {
+    if constexpr (level_kept<SH>(L)) {
+#pragma unroll
+      for (int b = 0; b < level_blocks<SH>(L); b++) kr[kept_before<SH>(L) + b] = rows[SH::level_rows(L) + 64 * b + lane];
+    }
+    load_kept_rows<SH, L + 1>(rows, kr, lane);
+  }
+}
+// forward_level / backward_level of a kept level: block b of the level is kr[b]
+template <int U, int NIT> __device__ __forceinline__ void forward_level_kept(const MtpRow8 *kr, double *M)
+{
+  static_assert(NIT <= U, "one trip");
+  double v[NIT];
+#pragma unroll
+  for (int u = 0; u < NIT; u++) v[u] = at8(M, kr[u].lo & 0xffffu) * at8(M, kr[u].lo >> 16);
+#pragma unroll
+  for (int u = 0; u < NIT; u++) lds_add(&at8(M, kr[u].hi & 0xffffu), (double) ((int) kr[u].hi >> 16) * v[u]);
+}
+template <int U, int NIT> __device__ __forceinline__ void backward_level_kept(const MtpRow8 *kr, const double *M, double *D)
+{
+  static_assert(NIT <= U, "one trip");
+  double d3[NIT], m0[NIT], m1[NIT];
+#pragma unroll
+  for (int u = 0; u < NIT; u++) {
+    d3[u] = at8(D, kr[u].hi & 0xffffu) * (double) ((int) kr[u].hi >> 16);
+    m0[u] = at8(M, kr[u].lo & 0xffffu);
+    m1[u] = at8(M, kr[u].lo >> 16);
+  }
+#pragma unroll
+  for (int u = 0; u < NIT; u++) {
+    lds_add(&at8(D, kr[u].lo >> 16), d3[u] * m0[u]);
+    lds_add(&at8(D, kr[u].lo & 0xffffu), d3[u] * m1[u]);
+  }
+}
+template <int U, class SH, int L, int NK>
+__device__ __forceinline__ void forward_levels_kept(const MtpRow8 *rows, const MtpRow8 (&kr)[NK], double *M, int lane)
+{
+  if constexpr (L < SH::nlevels) {
+    constexpr int beg = SH::level_rows(L), nit = level_blocks<SH>(L);
+    if constexpr (level_kept<SH>(L)) forward_level_kept<U, nit>(&kr[kept_before<SH>(L)], M);
+    else forward_level<U>(rows + beg + lane, nit, M);
+    wave_fence();
+    forward_levels_kept<U, SH, L + 1>(rows, kr, M, lane);
+  }
+}
+// (K counts the levels done: level L = nlevels - 1 - K, so that the call site names no member of SH)
+template <int U, class SH, int K, int NK>
+__device__ __forceinline__ void backward_levels_kept(const MtpRow8 *rows, const MtpRow8 (&kr)[NK], const double *M, double *D, int lane)
+{
+  if constexpr (K < SH::nlevels) {
+    constexpr int L = SH::nlevels - 1 - K;
+    constexpr int beg = SH::level_rows(L), nit = level_blocks<SH>(L);
+    if constexpr (level_kept<SH>(L)) backward_level_kept<U, nit>(&kr[kept_before<SH>(L)], M, D);
+    else backward_level<U>(rows + beg + lane, nit, M, D);
+    wave_fence();
+    backward_levels_kept<U, SH, K + 1>(rows, kr, M, D, lane);
   }
 }
 

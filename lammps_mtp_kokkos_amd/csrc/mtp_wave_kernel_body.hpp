@@ -90,6 +90,10 @@
   bt.leaf_cf = reinterpret_cast<const double *>(sh + SHF(off_leaf_cf));   // (behind the rows: valid when rows_in_lds)
   bt.leaf_cb = reinterpret_cast<const double *>(sh + SHF(off_leaf_cb));
   const bool rows_lds = SHF(rows_in_lds) != 0;
+  // row_regs_ct: the packed rows of the short product levels, this lane's row of each of their blocks
+  constexpr bool ROW_REGS = !GATHER && MTP_PU >= ROW_KEEP_LEVEL && row_regs_ct<SH>;   // (the gather passes have no rows per level)
+  MtpRow8 krow[kept_count<SH>()];
+  if constexpr (ROW_REGS) load_kept_rows<SH, 0>(bt.rows, krow, lane);
   // (not in the KL = 16 grade build: there the SGPR pair costs a twelfth spilled VGPR dword)
   constexpr bool MU_PACKED = MTP_MU_BITS && WPS == 3 && !(GRADE && KL == 16);
   SlotMu<MU_PACKED> smu{bt.smu, 0ull};
@@ -143,6 +147,36 @@
     }
   };
   if constexpr (WPS != 3) block_addresses(kl);
+  // block_regs_ct: the row byte offsets of this lane's block, {g | x power} and {y power | z power} of head / tail h as
+  // the 16-bit halves of bpk[h] and bpk[3 + h], decoded once per wavefront; block_offsets_to_addresses() per atom
+  constexpr bool BLOCK_REGS = WPS == 3 && NB == 1 && block_regs_ct<SH>;
+  unsigned bpk[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  if constexpr (BLOCK_REGS) {
+    const int *bd = bt.fwd + 8 * (kl < SHF(nfb) ? kl : 0);
+    const unsigned w0 = (unsigned) bd[0], w1 = (unsigned) bd[1], w2 = (unsigned) bd[2];
+#pragma unroll
+    for (int h = 0; h < 3; h++) {
+      const unsigned og = (unsigned) mul24((int) ((w0 >> (8 * h)) & 255u), 8 * PITCH);
+      const unsigned ox = (unsigned) mul24(SHF(pow_row) + (int) ((w1 >> (4 * h)) & 15u), 8 * PITCH);
+      const unsigned oy = (unsigned) mul24(SHF(pow_row) + P + (int) ((w1 >> (12 + 4 * h)) & 15u), 8 * PITCH);
+      const unsigned oz = (unsigned) mul24(SHF(pow_row) + 2 * P + (int) ((w2 >> (4 * h)) & 15u), 8 * PITCH);
+      bpk[h] = og | (ox << 16);
+      bpk[3 + h] = oy | (oz << 16);
+    }
+  }
+  auto block_offsets_to_addresses = [&]() {
+    bval[0] = kl < SHF(nfb);
+    const unsigned tq = w.addr(w.tab + q);
+#pragma unroll
+    for (int h = 0; h < 3; h++) {
+      asm volatile("" : "+v"(bpk[h]), "+v"(bpk[3 + h]));   // opaque per atom: the adds stay inside the loop
+      hg[0][h] = tq + (bpk[h] & 0xffffu);
+      hx[0][h] = tq + (bpk[h] >> 16);
+      ty[0][h] = tq + (bpk[3 + h] & 0xffffu);
+      tz[0][h] = tq + (bpk[3 + h] >> 16);
+      asm volatile("" : "+v"(hg[0][h]), "+v"(hx[0][h]), "+v"(ty[0][h]), "+v"(tz[0][h]));
+    }
+  };
 
   double tally = 0.0;   // lane 9: energy, lanes 3..8: virial components of this wave's atoms
   // Global-only tallies need no per-atom reduction: the per-lane partial sums of the virial (and of the energy) run
@@ -281,7 +315,9 @@
     for (int t = 0; t < NB; t++)
 #pragma unroll
       for (int e = 0; e < 9; e++) acc[t][e] = 0.0;
-    if constexpr (WPS == 3) {
+    if constexpr (BLOCK_REGS) {
+      block_offsets_to_addresses();
+    } else if constexpr (WPS == 3) {
       int kl_o = kl;
       asm volatile("" : "+v"(kl_o));   // opaque per atom: keeps the address arithmetic inside the loop
       block_addresses(kl_o);
@@ -373,7 +409,8 @@
     if constexpr (GATHER) {
       gather_pass(kp->prog_fwd, bt.seg_fwd, SHF(nlevels), w.M, w.M, w.M, lane);
     } else {
-      if (rows_lds) products_forward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, lane);
+      if constexpr (ROW_REGS) forward_levels_kept<MTP_PU, SH, 0>(bt.rows, krow, w.M, lane);
+      else if (rows_lds) products_forward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, lane);
       else products_forward<MTP_PU, SH>(kp, kp->rows, bt.level, w.M, lane);
     }
     // ---- site energy (pair_mtp.cpp:204-212): the leaf rows' share first ------------------------------------
@@ -423,7 +460,8 @@
     if constexpr (GATHER) {
       gather_pass(kp->prog_bwd, bt.seg_bwd, SHF(nlevels), w.D, w.M, w.D, lane);
     } else {
-      if (rows_lds) products_backward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, w.D, lane);
+      if constexpr (ROW_REGS) backward_levels_kept<MTP_PU, SH, 0>(bt.rows, krow, w.M, w.D, lane);
+      else if (rows_lds) products_backward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, w.D, lane);
       else products_backward<MTP_PU, SH>(kp, kp->rows, bt.level, w.M, w.D, lane);
     }
 
