@@ -16,7 +16,7 @@
  *     mtp_context_coeff_tables_device): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
- *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce): NULL is
+ *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
  * whose other GPU work runs on the default stream (PyTorch's default) must pass a real stream handle that its own
@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 8
+#define MTP_MI355X_ABI_VERSION 9
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -450,6 +450,67 @@ int mtp_batch_reduce(void *stream, int ncfg, const int *d_cfg_first, const doubl
  * neighbourhood grades (calculate_extrapolation_grade, :347-358) and divided by the configuration's atom count, 0 for an
  * empty one (:373-376).  NULL stream = the context's. */
 int mtp_batch_cfg_grades(mtp_context *ctx, void *stream, int ncfg, const int *d_cfg_first, int nrows, double *d_cfg_grade);
+
+/* ---- batched sampling: finite-temperature MD of a whole batch of cells, grades watched on the device ----------------
+ *
+ * The step of the active-learning loop that PRODUCES candidate configurations: MD under the current potential that
+ * watches the extrapolation grade (the reference does it inside LAMMPS: pair_style mtp/extrapolation ... threshold_select /
+ * threshold_break, pair_mtp_extrapolation.cpp:389-399, under fix langevin + fix nve).  These are the integrator pieces
+ * over the layout of the batched configurations: per-atom arrays hold the owned rows [cfg_first[k], cfg_first[k + 1]) of
+ * configuration k, positions are in SLOT coordinates (cell coordinates + origins[k], as mtp_ghosts_build_batch leaves them)
+ * between re-neighbourings, and the force / grade call in the middle of a step is the stock one over all rows.  Per
+ * configuration, device arrays [ncfg]: the target temperature, a 64-bit noise key chosen by the caller, frozen (0 / 1) and
+ * last_capture (a step; start it at -2^30).  Every array is the caller's; no context: NULL stream is rejected.  A step is
+ *   mtp_sample_initial -> mtp_ghosts_forward -> force call -> mtp_ghosts_reverse[_finish] -> mtp_sample_final
+ * and, on a grade step, the per-configuration grades (mtp_batch_reduce / mtp_batch_cfg_grades) -> mtp_sample_capture.
+ */
+/* d_row_cfg[i] = the configuration of owned row i, i < nrows = cfg_first[ncfg] (device arrays).  Once per pass: the three
+ * per-step kernels read it instead of searching cfg_first. */
+int mtp_sample_row_map(void *stream, int ncfg, const int *d_cfg_first, int nrows, int *d_row_cfg);
+/* fix nve, first half (metal units, dtf = 0.5 dt ftm2v): v += dtf f / m; x += dt v for the rows of unfrozen configurations
+ * -- bit for bit what mtp_nve_initial does to them; rows of a frozen configuration are not written. */
+int mtp_sample_initial(void *stream, int nrows, const int *d_row_cfg, const int *d_frozen, double *d_x, double *d_v,
+                       const double *d_f, const int *d_type, const double *d_inv_mass, double dtf, double dt);
+/* fix langevin (post_force, its default uniform noise) and then fix nve's second half, in that order, one launch:
+ *     gamma1 = -m / t_damp / ftm2v,   gamma2 = sqrt(m) sqrt(24 kB T[k] / t_damp / dt / mvv2e) / ftm2v
+ *     f += gamma1 v + gamma2 (u - 0.5)     (stored back: the next first half kicks with it, as in LAMMPS)
+ *     v += dtf f / m
+ * for the rows of unfrozen configurations.  u per atom, step and component is counter-based: Philox4x32-10 with the counter
+ * (step, index of the atom within its configuration, low word of key[k], high word of key[k]) and the key (low word of
+ * seed, high word of seed); output words 0, 1, 2 give x, y, z as u = (w + 0.5) 2^-32, so u - 0.5 is exact, symmetric and
+ * never at an end point.  A configuration's noise therefore does not depend on the batch it sits in or where.  t_damp <= 0
+ * or non-finite: no thermostat -- nothing drawn, f not written, v bit for bit mtp_nve_final's (d_mass, d_temperature, d_key
+ * may then be NULL).  masses per type; 0 <= step < 2^31. */
+int mtp_sample_final(void *stream, int nrows, const int *d_row_cfg, const int *d_cfg_first, const int *d_frozen, double *d_v,
+                     double *d_f, const int *d_type, const double *d_mass, const double *d_inv_mass,
+                     const double *d_temperature, const unsigned long long *d_key, unsigned long long seed, int step, double dtf,
+                     double dt, double t_damp);
+/* Per configuration d_mv2[k] = sum m v^2 over its rows (an empty one: 0) and d_d2[k] = the largest |x - x_ref|^2 of its
+ * rows, 0 for a frozen configuration; one wavefront per configuration (its workgroup above 256 rows, as mtp_batch_reduce),
+ * fixed order, no atomics.  Then d_block4 = {max_k d_d2[k], frozen, captured, dropped} with the three counts taken from
+ * d_counts (mtp_sample_capture's): the one thing a driver reads between re-neighbourings. */
+int mtp_sample_monitor(void *stream, int ncfg, const int *d_cfg_first, const int *d_frozen, const double *d_x,
+                       const double *d_x_ref, const double *d_v, const int *d_type, const double *d_mass, const int *d_counts,
+                       double *d_mv2, double *d_d2, double *d_block4);
+/* The capture decisions of a grade step at `step`, from the per-configuration grades g = d_cfg_grade[k], on the device:
+ *   - configuration k wants a slot if it is neither frozen nor empty, !(g < threshold_select) and
+ *     step - last_capture[k] >= capture_gap (a NaN grade therefore captures);
+ *   - slots of the candidate buffer go out in ascending (step, configuration) order: slot = the number of configurations
+ *     that wanted one before it (an exclusive scan over the configurations, any ncfg; no atomic counter);
+ *   - a slot below max_candidates is filled: d_rec[slot] = {k, step}, d_rec_grade[slot] = g, last_capture[k] = step,
+ *     d_cand_x[slot][j][3] = x - origins[k] of its j-th owned row (`stride` rows a slot, stride >= the largest
+ *     configuration), and the configuration freezes if !(g < threshold_break);
+ *   - otherwise NOTHING of it is written, it is counted as dropped and it does not freeze.
+ * d_counts[3] = {captured, dropped, frozen} accumulate over the calls of a run (zero them first); d_slot [ncfg] is scratch
+ * (the slot of each configuration at this step, -1 for none). */
+int mtp_sample_capture(void *stream, int ncfg, const int *d_cfg_first, int nrows, const int *d_row_cfg,
+                       const double *d_cfg_grade, int step, double threshold_select, double threshold_break, int capture_gap,
+                       const double *d_x, const double *d_origins /*[ncfg][3]*/, int *d_frozen, int *d_last_capture, int *d_slot,
+                       int max_candidates, int stride, double *d_cand_x, int *d_rec /*[max_candidates][2]*/, double *d_rec_grade,
+                       int *d_counts);
+/* x -= origins[row_cfg]: slot coordinates back to cell coordinates, in front of a re-neighbouring --
+ * mtp_ghosts_build_batch wraps cell coordinates and translates them again. */
+int mtp_sample_to_cell(void *stream, int nrows, const int *d_row_cfg, const double *d_origins, double *d_x);
 
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------

@@ -45,6 +45,8 @@ EXPORTS = [
     "mtp_potential_coeff_tables", "mtp_potential_compatible", "mtp_context_install_coeffs", "mtp_context_install_selection",
     "mtp_context_install_file", "mtp_context_get_coeffs", "mtp_context_get_selection", "mtp_context_coeff_tables_device",
     "mtp_context_cfg_grade",
+    "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
+    "mtp_sample_to_cell",
 ]
 WROTE_WITHOUT_SELECTION = 1   # mtp_potential_write_coeffs: the source's #MVS tail was left out
 # mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
@@ -105,7 +107,7 @@ def kernel_source_hash():
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
-    other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip")
+    other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1019,3 +1021,68 @@ def nve_monitor(nlocal, x_t, x_ref_t, v_t, type_t, mass_t, out2_t, stream=None):
                                _ptr(type_t), _ptr(mass_t), _ptr(out2_t))
     if rc:
         raise MtpError(rc, "mtp_nve_monitor")
+
+
+# ---- batched sampling (include/mtp_mi355x.h): all arguments are device tensors in the layout of the batched configurations
+
+def _st(stream):
+    return C.c_void_p(stream) if stream else None
+
+
+def sample_row_map(cfg_first_t, row_cfg_t, stream=None):
+    """row_cfg_t[i] = the configuration of owned row i, for all rows of row_cfg_t: mtp_sample_row_map"""
+    rc = lib().mtp_sample_row_map(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), int(row_cfg_t.numel()),
+                                  _ptr(row_cfg_t))
+    if rc:
+        raise MtpError(rc, "mtp_sample_row_map")
+
+
+def sample_initial(nrows, row_cfg_t, frozen_t, x_t, v_t, f_t, type_t, inv_mass_t, dtf, dt, stream=None):
+    """first half step of the unfrozen configurations: mtp_sample_initial"""
+    rc = lib().mtp_sample_initial(_st(stream), int(nrows), _ptr(row_cfg_t), _ptr(frozen_t), _ptr(x_t), _ptr(v_t), _ptr(f_t),
+                                  _ptr(type_t), _ptr(inv_mass_t), C.c_double(dtf), C.c_double(dt))
+    if rc:
+        raise MtpError(rc, "mtp_sample_initial")
+
+
+def sample_final(nrows, row_cfg_t, cfg_first_t, frozen_t, v_t, f_t, type_t, mass_t, inv_mass_t, temperature_t, key_t, seed, step,
+                 dtf, dt, t_damp, stream=None):
+    """fix langevin's force (Philox4x32-10 noise keyed by key_t [ncfg] int64 and `seed`) and the second half step of the
+    unfrozen configurations in one launch; t_damp <= 0 or infinite: the second half step alone.  mtp_sample_final"""
+    rc = lib().mtp_sample_final(_st(stream), int(nrows), _ptr(row_cfg_t), _ptr(cfg_first_t), _ptr(frozen_t), _ptr(v_t), _ptr(f_t),
+                                _ptr(type_t), _ptr(mass_t), _ptr(inv_mass_t), _ptr(temperature_t), _ptr(key_t),
+                                C.c_ulonglong(int(seed) & (2 ** 64 - 1)), int(step), C.c_double(dtf), C.c_double(dt),
+                                C.c_double(t_damp))
+    if rc:
+        raise MtpError(rc, "mtp_sample_final")
+
+
+def sample_monitor(cfg_first_t, frozen_t, x_t, x_ref_t, v_t, type_t, mass_t, counts_t, mv2_t, d2_t, block_t, stream=None):
+    """mv2_t[k] = sum m v^2, d2_t[k] = largest squared displacement from x_ref_t (0 where frozen), block_t [4] = (max d2,
+    frozen, captured, dropped): mtp_sample_monitor"""
+    rc = lib().mtp_sample_monitor(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), _ptr(frozen_t), _ptr(x_t),
+                                  _ptr(x_ref_t), _ptr(v_t), _ptr(type_t), _ptr(mass_t), _ptr(counts_t), _ptr(mv2_t), _ptr(d2_t),
+                                  _ptr(block_t))
+    if rc:
+        raise MtpError(rc, "mtp_sample_monitor")
+
+
+def sample_capture(cfg_first_t, nrows, row_cfg_t, cfg_grade_t, step, threshold_select, threshold_break, capture_gap, x_t,
+                   origins_t, frozen_t, last_capture_t, slot_t, max_candidates, stride, cand_x_t, rec_t, rec_grade_t, counts_t,
+                   stream=None):
+    """the capture and freeze decisions of a grade step with their snapshots, on the device: mtp_sample_capture.  cand_x_t
+    [max_candidates, stride, 3], rec_t [max_candidates, 2] int32 (configuration, step), rec_grade_t [max_candidates],
+    counts_t [3] int32 (captured, dropped, frozen; accumulated)"""
+    rc = lib().mtp_sample_capture(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), int(nrows), _ptr(row_cfg_t),
+                                  _ptr(cfg_grade_t), int(step), C.c_double(threshold_select), C.c_double(threshold_break),
+                                  int(capture_gap), _ptr(x_t), _ptr(origins_t), _ptr(frozen_t), _ptr(last_capture_t), _ptr(slot_t),
+                                  int(max_candidates), int(stride), _ptr(cand_x_t), _ptr(rec_t), _ptr(rec_grade_t), _ptr(counts_t))
+    if rc:
+        raise MtpError(rc, "mtp_sample_capture")
+
+
+def sample_to_cell(nrows, row_cfg_t, origins_t, x_t, stream=None):
+    """slot coordinates back to cell coordinates in front of a re-neighbouring: mtp_sample_to_cell"""
+    rc = lib().mtp_sample_to_cell(_st(stream), int(nrows), _ptr(row_cfg_t), _ptr(origins_t), _ptr(x_t))
+    if rc:
+        raise MtpError(rc, "mtp_sample_to_cell")

@@ -13,7 +13,9 @@ the library's HIP kernels (include/mtp_mi355x.h, "standalone MD support"):
 benchmark times) or a 3x3 cell whose rows are the lattice vectors (any periodic cell, triclinic or smaller than the
 cutoff: mtp_ghosts_build_cell, list bounds from mtp_ghosts_cell_bounds).  evaluate_cell is one such evaluation
 without the integrator; evaluate_cells does many of them -- training or candidate configurations, each with its own
-cell -- in one device pass (include/mtp_mi355x.h, "batched configurations").
+cell -- in one device pass (include/mtp_mi355x.h, "batched configurations").  sample_cells is the integrator over that
+batch layout: Langevin (or NVE) MD of all the cells at once with the extrapolation grade watched, and the extrapolating
+configurations captured, on the device (include/mtp_mi355x.h, "batched sampling").
 
 torch only allocates the arrays and provides the stream; the host sees the ghost count and the list size at a
 re-neighbouring (they size arrays) and nothing else.
@@ -26,6 +28,7 @@ from . import capi
 
 MVV2E = 1.0364269e-4          # (g/mol)(A/ps)^2 -> eV     (LAMMPS metal units)
 FTM2V = 1.0 / MVV2E           # eV/A / (g/mol) -> A/ps^2
+KB = 8.617343e-5              # eV/K
 
 
 class DeviceNVE:
@@ -820,3 +823,293 @@ def fit_full(ctx, configs, labels, weights=(1.0, 0.01, 0.001), theta0=None, fit=
     if install:
         ctx.install_coeffs(res["radial_coeffs"], res["species_coeffs"], res["moment_coeffs"])
     return res
+
+
+def maxwell_boltzmann(items, mass_of_type, temperature, seed, keys):
+    """Host only: Maxwell-Boltzmann velocities [A/ps] per configuration of `items` = [(pos, types)], each from a generator
+    of its own seeded by (seed, keys[k]) -- a configuration's draw does not depend on the batch around it -- with the
+    configuration's centre-of-mass velocity removed."""
+    out = []
+    for k, (pos, types) in enumerate(items):
+        rng = np.random.default_rng([int(seed) & (2 ** 64 - 1), int(keys[k]) & (2 ** 64 - 1)])
+        m = mass_of_type[types - 1]
+        v = rng.normal(size=(len(pos), 3)) * np.sqrt(KB * float(temperature[k]) / (m * MVV2E))[:, None]
+        if len(pos) == 1:                                     # (its own centre of mass: at rest exactly)
+            v[:] = 0.0
+        elif len(pos):
+            v -= (m[:, None] * v).sum(0) / m.sum()
+        out.append(v)
+    return out
+
+
+def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break, capture_gap,
+                      max_candidates, velocities, grade_every, every, check_every):
+    """the host-side checks of sample_cells (nothing here touches the device); returns the normalised arguments"""
+    items, all_cells, natoms = _batch_items(configs)
+    ncfg = len(items)
+    if not (float(dt) > 0.0 and np.isfinite(float(dt))):
+        raise ValueError("sample_cells: dt must be positive and finite, got %r" % (dt,))
+    if int(steps) < 0 or int(steps) >= 2 ** 30:
+        raise ValueError("sample_cells: steps must be in [0, 2^30)")
+    select = 2.0 if threshold_select is None else float(threshold_select)
+    brk = 10.0 if threshold_break is None else float(threshold_break)
+    if select > brk:
+        raise ValueError("sample_cells: threshold_select (%g) is above threshold_break (%g)" % (select, brk))
+    if keys is None:
+        keys = np.arange(ncfg, dtype=np.uint64)
+    else:
+        if len(keys) != ncfg:
+            raise ValueError("sample_cells: %d keys for %d configurations" % (len(keys), ncfg))
+        keys = np.array([int(q) & (2 ** 64 - 1) for q in keys], dtype=np.uint64)
+    temperature = np.asarray(temperature, dtype=np.float64)
+    if temperature.ndim == 0:
+        temperature = np.full(ncfg, float(temperature))
+    if temperature.shape != (ncfg,) or not (np.isfinite(temperature).all() and (temperature >= 0.0).all()):
+        raise ValueError("sample_cells: temperature is a non-negative scalar or one per configuration (%d)" % ncfg)
+    ntypes = max([int(t.max()) for _, t in items if len(t)], default=1)
+    if min([int(t.min()) for _, t in items if len(t)], default=1) < 1:
+        raise ValueError("sample_cells: atom types count from 1")
+    mass_of_type = np.atleast_1d(np.asarray(masses, dtype=np.float64)).reshape(-1)
+    if len(mass_of_type) == 1:
+        mass_of_type = np.full(ntypes, float(mass_of_type[0]))
+    if len(mass_of_type) < ntypes or not (mass_of_type > 0.0).all():
+        raise ValueError("sample_cells: masses is one positive mass, or one per atom type (%d)" % ntypes)
+    if velocities is not None:
+        if len(velocities) != ncfg:
+            raise ValueError("sample_cells: %d velocity arrays for %d configurations" % (len(velocities), ncfg))
+        velocities = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]
+        for k, v in enumerate(velocities):
+            if len(v) != natoms[k]:
+                raise ValueError("sample_cells: velocities[%d] must be [%d, 3]" % (k, natoms[k]))
+    if int(capture_gap) < 0 or int(grade_every or 0) < 0 or int(every) < 1 or int(check_every or 0) < 0:
+        raise ValueError("sample_cells: capture_gap, grade_every and check_every must not be negative, every at least 1")
+    max_candidates = 4 * ncfg if max_candidates is None else int(max_candidates)
+    if max_candidates < 0:
+        raise ValueError("sample_cells: max_candidates must not be negative")
+    return items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities, max_candidates
+
+
+def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=None, masses=183.84, grade_every=10,
+                 threshold_select=None, threshold_break=None, capture_gap=0, max_candidates=None, velocities=None,
+                 list_cutoff=7.0, every=10, check_every=4, max_atoms_per_pass=None, device=None, trace=False):
+    """The sampling step of the active-learning loop: finite-temperature MD of a whole batch of independent periodic cells
+    under the context's potential, device-resident, with the extrapolation grade checked every `grade_every` steps and the
+    extrapolating configurations captured on the device (what LAMMPS does one cell at a time with pair_style
+    mtp/extrapolation ... threshold_select threshold_break under fix langevin + fix nve).  `configs` as for evaluate_cells;
+    the passes are planned by plan_cell_passes and run one after another, every pass a complete run of `steps`.
+
+    One step (metal units, dt in ps) is mtp_sample_initial (kick + drift) -> ghosts follow -> ONE force call over all rows
+    -> ghost fold -> mtp_sample_final (fix langevin's force with t_damp [ps] and the target `temperature` [K], a scalar or
+    one per configuration, then the second kick).  t_damp <= 0, None or infinite: plain NVE.  The noise is Philox4x32-10 on
+    the counter (step, atom within its configuration, keys[k]) and the key `seed` (include/mtp_mi355x.h): the trajectory of
+    a configuration depends on its keys[k] (default: its index in `configs`), not on the batch around it.  As in LAMMPS the
+    thermostat force is also applied to the forces of step 0 (fix langevin's setup).  velocities=None draws Maxwell-Boltzmann
+    velocities per configuration on the host (maxwell_boltzmann: from seed and keys[k], centre-of-mass velocity removed);
+    otherwise a list of [n, 3] arrays in A/ps.  masses: one, or one per atom type [g/mol].
+
+    Lists are rebuilt every `every` steps, or when an atom of an unfrozen configuration moved more than half the skin
+    (list_cutoff - the potential's cutoff) -- seen in the 32-byte block mtp_sample_monitor leaves, which is read every
+    `check_every` steps since the last rebuild, and once at every rebuild, and is the only thing the host reads between
+    rebuilds.
+
+    Grade steps (0, grade_every, 2 grade_every, ...; a potential loaded with its selection state) take the grade of every
+    configuration -- the largest per-atom grade in neighbourhood mode, the configuration's grade in configuration mode --
+    and mtp_sample_capture decides on the device: a non-empty, unfrozen configuration with !(grade < threshold_select) (default 2)
+    whose last capture is at least capture_gap steps back is captured -- a snapshot of its positions in the next slot of the
+    candidate buffer, slots in ascending (step, configuration) order -- and then frozen (it no longer moves) if
+    !(grade < threshold_break) (default 10).  With the buffer (max_candidates slots, default 4 per configuration) full, a
+    configuration is dropped: counted, nothing of it written, not frozen.  A potential without selection state skips the
+    grade steps; naming a threshold then raises MtpError(-23), as select_cells does.  The run ends early once every non-empty
+    configuration of the pass is frozen, which is seen at the next read of the monitor block (so at the latest at the next
+    rebuild; frozen configurations do not move in between, and steps_done counts the steps up to that read).
+
+    Returns dict(candidates: [(pos, cell, types)] in capture order (by pass, then step, then configuration), ready for
+    select_cells; records: [(configuration, step, grade)]; dropped; frozen [ncfg] bool; final: per configuration dict(x [n, 3]
+    cell coordinates, wrapped at the last rebuild; v [n, 3]; energy: the potential energy; temperature = sum m v^2 / (3 n kB));
+    steps_done: the steps made (the largest over the passes); builds: the list builds of all passes) and, with the diagnostic trace=True
+    (two more launches a step), trace: dict(energy, kinetic [steps_done
+    + 1, ncfg]) -- potential and kinetic energy per configuration after every step, step 0 first."""
+    (items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities,
+     max_candidates) = _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break,
+                                         capture_gap, max_candidates, velocities, grade_every, every, check_every)
+    info = ctx.pot.info
+    grade_every = int(grade_every or 0)
+    if not info.has_selection:
+        if threshold_select is not None or threshold_break is not None:
+            raise capi.MtpError(-23, "sample_cells: thresholds need a potential loaded with its selection state")
+        grade_every = 0
+    import torch
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    steps, dt, cut, seed = int(steps), float(dt), float(list_cutoff), int(seed) & (2 ** 64 - 1)
+    every, check_every, capture_gap = int(every), int(check_every or 0), int(capture_gap)
+    t_damp = 0.0 if t_damp is None or not np.isfinite(float(t_damp)) or float(t_damp) <= 0.0 else float(t_damp)
+    dtf = 0.5 * dt * FTM2V
+    half_skin2 = (0.5 * (cut - float(info.max_cutoff))) ** 2
+    cfg_mode = bool(grade_every) and bool(info.configuration_mode)
+    C = int(info.coeff_count)
+    ncfg_all = len(items)
+    if velocities is None:
+        velocities = maxwell_boltzmann(items, mass_of_type, temperature, seed, keys)
+    passes, volume, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
+    ghosts = capi.Ghosts(dev.index or 0)
+    buf = _BatchBuffers(torch, dev)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    mass_t, inv_mass_t = to(mass_of_type), to(1.0 / mass_of_type)
+    candidates, records, final = [], [], [None] * ncfg_all
+    frozen_all = np.zeros(ncfg_all, dtype=bool)
+    dropped, steps_done, npass, builds = 0, 0, 0, [0]
+    tr_e = np.zeros((steps + 1, ncfg_all)) if trace else None
+    tr_k = np.zeros((steps + 1, ncfg_all)) if trace else None
+    na = lambda rows: rows + (rows & 1)
+    for k0, k1, lay in passes:
+        npass += 1
+        ncfg = k1 - k0
+        counts = natoms[k0:k1]
+        cf = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        n = int(cf[-1])
+        if n == 0:
+            for k in range(k0, k1):
+                final[k] = dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0)
+            continue
+        nonempty = int((counts > 0).sum())
+        stride = int(counts.max())
+        room = max(max_candidates - len(records), 0)
+        cells = all_cells[k0:k1]
+        cf_t, org_t = to(cf), to(lay["origins"])
+        work_size = lambda rows: 4 * na(rows) + 10 + C + (C & 1)
+        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items[k0:k1], cf, cells, lay, cut, n + int(max_rows[k0:k1].sum()),
+                                     lambda rows, first: buf.reserve(rows, ncfg, work_size(rows), 0), st)
+        builds[0] += 1
+        x = buf.xall
+        row_cfg = torch.empty(n, dtype=torch.int32, device=dev)
+        capi.sample_row_map(cf_t, row_cfg, stream=st)
+        v = to(np.concatenate(velocities[k0:k1]))
+        x_ref = x[:n].clone()
+        frozen = torch.zeros(ncfg, dtype=torch.int32, device=dev)
+        last_capture = torch.full((ncfg,), -2 ** 30, dtype=torch.int32, device=dev)
+        slot = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
+        counts_t = torch.zeros(3, dtype=torch.int32, device=dev)         # captured, dropped, frozen
+        temp_t = to(temperature[k0:k1])
+        key_t = to(keys[k0:k1].view(np.int64))
+        g_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
+        mon = torch.zeros(2 * ncfg + 4, dtype=torch.float64, device=dev)
+        mv2, d2, block = mon[:ncfg], mon[ncfg: 2 * ncfg], mon[2 * ncfg:]
+        cand_x = torch.zeros((max(room, 1), stride, 3), dtype=torch.float64, device=dev)
+        rec = torch.zeros((max(room, 1), 2), dtype=torch.int32, device=dev)
+        rec_grade = torch.zeros(max(room, 1), dtype=torch.float64, device=dev)
+        e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
+        tr_dev = torch.zeros((2, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
+        lay_now = {}
+
+        def layout(rows):
+            # f | ev | eatom | max grade | coeff_ders: one allocation, zeroed by one launch every step
+            m = na(rows)
+            w = buf.work[: work_size(rows)]
+            lay_now.update(work=w, f=w[: 3 * rows].view(rows, 3), ev=w[3 * m: 3 * m + 8], eatom=w[3 * m + 8: 4 * m + 8],
+                           maxg=w[4 * m + 8: 4 * m + 9], coeff=w[4 * m + 10: 4 * m + 10 + C])
+
+        def forces(grade):
+            L = lay_now
+            ghosts.forward(x, stream=st)
+            capi.zero_async(L["work"], stream=st)
+            ctx.compute_device_rows(0, n, False, x, buf.tall, L["f"], eflag=3, vflag=0, grade=grade, eatom_t=L["eatom"], ev_t=L["ev"],
+                                    grades_t=buf.grades if grade and not cfg_mode else None, maxg_t=L["maxg"] if grade else None,
+                                    coeff_t=L["coeff"] if grade and cfg_mode else None, stream=st)
+            ghosts.reverse_finish(ctx, L["f"], L["ev"], eflag=3, vflag=0, stream=st)
+            if grade and cfg_mode:
+                ctx.batch_cfg_grades(cf_t, n, g_t, stream=st)
+            elif grade:
+                capi.batch_reduce(cf_t, grades_t=buf.grades, cfg_grade_t=g_t, stream=st)
+
+        def second_half(step, kick):
+            capi.sample_final(n, row_cfg, cf_t, frozen, v, lay_now["f"], buf.tall, mass_t, inv_mass_t, temp_t, key_t, seed, step,
+                              kick, dt, t_damp, stream=st)
+
+        def capture(step):
+            capi.sample_capture(cf_t, n, row_cfg, g_t, step, select, brk, capture_gap, x, org_t, frozen, last_capture, slot, room,
+                                stride, cand_x, rec, rec_grade, counts_t, stream=st)
+
+        def monitor(mv2_t=mv2):
+            capi.sample_monitor(cf_t, frozen, x, x_ref, v, buf.tall, mass_t, counts_t, mv2_t, d2, block, stream=st)
+
+        def record(step):
+            capi.batch_reduce(cf_t, eatom_t=lay_now["eatom"], energy_t=tr_dev[0, step], stream=st)
+            monitor(tr_dev[1, step])
+
+        def reneighbor():
+            capi.sample_to_cell(n, row_cfg, org_t, x, stream=st)
+            rows = ghosts.build_batch(x, cf, cells, lay["origins"], cut, stream=st)
+            ghosts.types(buf.tall, stream=st)
+            ctx.build_neighbors_device(x, n, rows, cut, lay["lo"], lay["hi"], stream=st)
+            layout(rows)
+            x_ref.copy_(x[:n])
+            builds[0] += 1
+
+        graded = lambda step: bool(grade_every) and step % grade_every == 0
+        layout(nall)
+        forces(graded(0))
+        if t_damp > 0.0:
+            second_half(0, 0.0)                               # (fix langevin's setup: the thermostat force of step 0, no kick)
+        stop = False
+        if graded(0):
+            capture(0)
+            monitor()
+            stop = float(block.cpu()[1]) >= nonempty
+        if trace:
+            record(0)
+        s, since = 0, 0
+        while s < steps and not stop:
+            s += 1
+            capi.sample_initial(n, row_cfg, frozen, x, v, lay_now["f"], buf.tall, inv_mass_t, dtf, dt, stream=st)
+            since += 1
+            need = since >= every
+            if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
+                monitor()
+                b = block.cpu().numpy()
+                if b[1] >= nonempty:                          # everything is frozen: this first half wrote nothing
+                    s -= 1
+                    break
+                need = need or b[0] > half_skin2
+            if need:
+                reneighbor()
+                since = 0
+            forces(graded(s))
+            second_half(s, dtf)
+            if graded(s):
+                capture(s)
+            if trace:
+                record(s)
+        steps_done = max(steps_done, s)
+        capi.batch_reduce(cf_t, eatom_t=lay_now["eatom"], energy_t=e_t, stream=st)
+        monitor()
+        try:
+            ctx.synchronize(stream=st)                        # an atom type outside the potential is reported here
+        except capi.MtpError as e:
+            raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
+        ch = counts_t.cpu().numpy()
+        ncap = int(ch[0])
+        dropped += int(ch[1])
+        xh = x[:n].cpu().numpy() - np.repeat(lay["origins"], counts, axis=0)
+        vh, eh, mh, fh = v.cpu().numpy(), e_t.cpu().numpy(), mv2.cpu().numpy(), frozen.cpu().numpy()
+        frozen_all[k0:k1] = fh != 0
+        for j in range(ncfg):
+            a, b = int(cf[j]), int(cf[j + 1])
+            final[k0 + j] = dict(x=xh[a:b], v=vh[a:b], energy=float(eh[j]),
+                                 temperature=float(mh[j]) * MVV2E / (3.0 * (b - a) * KB) if b > a else 0.0)
+        rh, gh, snap = rec[:ncap].cpu().numpy(), rec_grade[:ncap].cpu().numpy(), cand_x[:ncap].cpu().numpy()
+        for j in range(ncap):
+            k = int(rh[j, 0])
+            records.append((k0 + k, int(rh[j, 1]), float(gh[j])))
+            candidates.append((snap[j, : int(counts[k])].copy(), cells[k].copy(), items[k0 + k][1].copy()))
+        if trace:
+            th = tr_dev.cpu().numpy()
+            tr_e[: s + 1, k0:k1] = th[0, : s + 1]
+            tr_k[: s + 1, k0:k1] = 0.5 * MVV2E * th[1, : s + 1]
+    out = dict(candidates=candidates, records=records, dropped=dropped, frozen=frozen_all, final=final, steps_done=steps_done,
+               builds=builds[0])
+    if trace:
+        out["trace"] = dict(energy=tr_e[: steps_done + 1], kinetic=tr_k[: steps_done + 1])
+    return out
