@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -126,17 +127,16 @@ struct mtp_context {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
 
-  // design rows (mtp_design_rows_device): the tangent kernel's own table, built and uploaded by the first design call
-  bool design_ready = false;
-  DevBuf<MtpRow8> d_design_rows;
-  DevBuf<int32_t> d_design_ints;     // level offsets | basic descriptors | scalar map | force map
+  // design rows and training gradient (mtp_design_rows_device, mtp_train_*_device): the one structural table of the
+  // kernels with a workgroup per centre, built and uploaded by the first call of either kind
+  bool centre_ready = false;
+  DevBuf<MtpRow8> d_centre_rows;
+  DevBuf<int32_t> d_centre_ints;     // level offsets | basic descriptors | scalar map | force map | basics by mu | mu offsets
   DevBuf<double> d_design_radial;
-  MtpDesignParams design{};
-  // training gradient (mtp_train_*_device): the structural table, built and uploaded by the first training call
-  bool train_ready = false;
-  DevBuf<MtpRow8> d_train_rows;
-  DevBuf<int32_t> d_train_ints;      // level offsets | basic descriptors | scalar map | basics by mu | mu offsets
-  MtpTrainParams train{};
+  MtpCentreParams centre{};          // shape and table; the system fields are bound per call (centre_bind)
+  const int *centre_fmap = nullptr, *centre_bymu = nullptr, *centre_mufirst = nullptr;
+  int train_rc = MTP_OK;             // what the training formulas say to this table (mtp_build_train_table, the packed basics)
+  std::string train_msg;
 
   // The context's own values (include/mtp_mi355x.h, "installing ..."): initialised from the potential, replaced by the
   // installs, and the only source of values for what the context does after its creation -- `pot` is read for structure.
@@ -1463,57 +1463,115 @@ int mtp_batch_cfg_grades(mtp_context *c, void *stream, int ncfg, const int *d_cf
 }
 
 // ---- design rows of the linear refit (include/mtp_mi355x.h) ----------------------------------------------------------
-static int design_prepare(mtp_context *c, hipStream_t st)
+// builds and uploads the table of both kinds of call; `train`: the call is a training call (a design call succeeds on a
+// table the training formulas refuse; a training call is refused every time, with the same code and message)
+static int centre_prepare(mtp_context *c, hipStream_t st, bool train)
 {
-  if (c->design_ready) return MTP_OK;
-  const mtp_potential &pot = *c->pot;
-  mtp_design_table t;
-  mtp_build_design_table(pot, t);
-  if (t.A > 8191) {
-    c->last_error = "design rows: alpha_moments_count above 8191 is not supported by the packed times rows";
-    return MTP_ERR_LIMIT;
-  }
-  std::vector<MtpRow8> rows8(t.rows.size());
-  for (size_t k = 0; k < rows8.size(); k++) {
-    const MtpRow &r = t.rows[k];
-    if (r.mult > 32767 || r.mult < -32768) {
-      c->last_error = "design rows: a multiplicity of alpha_index_times does not fit 16 bits";
+  if (!c->centre_ready) {
+    const mtp_potential &pot = *c->pot;
+    const std::string who = train ? "training gradient" : "design rows";
+    mtp_train_table built;   // (its design part is filled either way)
+    std::string tmsg;
+    int trc = mtp_build_train_table(pot, built, tmsg);
+    const mtp_train_table &t = built;
+    const mtp_design_table &dt = t.design;
+    if (train && trc != MTP_OK) {
+      c->last_error = tmsg;
+      return trc;
+    }
+    if (dt.A > 8191) {
+      c->last_error = who + ": alpha_moments_count above 8191 is not supported by the packed times rows";
       return MTP_ERR_LIMIT;
     }
-    rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
-    rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
+    if (trc == MTP_OK && (pot.radial_func_count > 16 || pot.max_alpha_index_basic > 16)) {
+      trc = MTP_ERR_LIMIT;
+      tmsg = "training gradient: radial_funcs_count or a basic index above 16 does not fit the packed basics";
+      if (train) {
+        c->last_error = tmsg;
+        return trc;
+      }
+    }
+    std::vector<MtpRow8> rows8(dt.rows.size());
+    for (size_t k = 0; k < rows8.size(); k++) {
+      const MtpRow &r = dt.rows[k];
+      if (r.mult > 32767 || r.mult < -32768) {
+        c->last_error = who + ": a multiplicity of alpha_index_times does not fit 16 bits";
+        return MTP_ERR_LIMIT;
+      }
+      rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
+      rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
+    }
+    std::vector<int32_t> ints(dt.level_offset);
+    for (const std::vector<int32_t> *v : {&dt.basic_pack, &dt.scalar_map, &dt.force_map, &t.bymu, &t.mufirst})
+      ints.insert(ints.end(), v->begin(), v->end());
+    c->d_centre_rows.upload(rows8, st);
+    c->d_centre_ints.upload(ints, st);
+    c->d_design_radial.upload(c->h_radial, st);   // (the context's values: an install may precede the first call)
+    HIP_CHECK(hipStreamSynchronize(st));   // (the staging vectors go out of scope)
+    MtpCentreParams &d = c->centre;
+    d = MtpCentreParams{};
+    d.Sp = pot.species_count;
+    d.R = pot.radial_basis_size;
+    d.Mu = pot.radial_func_count;
+    d.P = pot.max_alpha_index_basic;
+    d.A = dt.A;
+    d.B = dt.B;
+    d.S = dt.S;
+    d.nblocks = dt.nblocks;
+    d.rmin = pot.min_cutoff;
+    d.rmax = pot.max_cutoff;
+    d.scaling = pot.scaling;
+    d.cutsq = pot.max_cutoff * pot.max_cutoff;
+    d.inv_span = 1.0 / (pot.max_cutoff - pot.min_cutoff);
+    d.rows = c->d_centre_rows.ptr;
+    d.level = c->d_centre_ints.ptr;
+    d.pack = d.level + dt.level_offset.size();
+    d.map = d.pack + dt.B;
+    c->centre_fmap = d.map + dt.S;
+    c->centre_bymu = c->centre_fmap + dt.S;
+    c->centre_mufirst = c->centre_bymu + dt.B;
+    d.err_flag = c->d_err.ptr;
+    c->train_rc = trc;
+    c->train_msg = tmsg;
+    c->centre_ready = true;
   }
-  std::vector<int32_t> ints(t.level_offset);
-  ints.insert(ints.end(), t.basic_pack.begin(), t.basic_pack.end());
-  ints.insert(ints.end(), t.scalar_map.begin(), t.scalar_map.end());
-  ints.insert(ints.end(), t.force_map.begin(), t.force_map.end());
-  c->d_design_rows.upload(rows8, st);
-  c->d_design_ints.upload(ints, st);
-  c->d_design_radial.upload(c->h_radial, st);   // (the context's values: an install may precede the first design call)
-  HIP_CHECK(hipStreamSynchronize(st));   // (the staging vectors go out of scope)
-  MtpDesignParams &d = c->design;
-  d = MtpDesignParams{};
-  d.Sp = pot.species_count;
-  d.R = pot.radial_basis_size;
-  d.Mu = pot.radial_func_count;
-  d.P = pot.max_alpha_index_basic;
-  d.A = t.A;
-  d.B = t.B;
-  d.S = t.S;
-  d.nblocks = t.nblocks;
-  d.rmin = pot.min_cutoff;
-  d.rmax = pot.max_cutoff;
-  d.scaling = pot.scaling;
-  d.cutsq = pot.max_cutoff * pot.max_cutoff;
-  d.inv_span = 1.0 / (pot.max_cutoff - pot.min_cutoff);
-  d.rows = c->d_design_rows.ptr;
-  d.level = c->d_design_ints.ptr;
-  d.pack = d.level + t.level_offset.size();
-  d.map = d.pack + t.B;
-  d.fmap = d.map + t.S;
-  d.radial = c->d_design_radial.ptr;
-  d.err_flag = c->d_err.ptr;
-  c->design_ready = true;
+  if (train && c->train_rc != MTP_OK) c->last_error = c->train_msg;
+  return train ? c->train_rc : MTP_OK;
+}
+
+// the table and the system of one call
+static void centre_bind(const mtp_context *c, MtpCentreParams &p, const double *d_x, const int *d_type, int row_begin, int row_count,
+                        const int *d_owner, int nowned, int ld)
+{
+  p = c->centre;
+  p.row0 = row_begin;
+  p.nrows = row_count;
+  p.nowned = nowned;
+  p.nall = c->nall;
+  p.ld = ld;
+  p.cj_cap = std::max(c->max_numneigh, 1);
+  p.ilist = c->ilist;
+  p.first = c->first;
+  p.neigh = c->neigh;
+  p.type = d_type;
+  p.owner = d_owner;
+  p.x = d_x;
+}
+
+// the workgroups of a launch whose LDS image takes `lds` bytes, or the refusal of an image beyond the CU's 160 KB: `fixed`
+// gives the caller's sentence for an image that is too large without the list's ids
+static int centre_grid(mtp_context *c, const std::string &who, size_t lds, int cj_cap, int row_count, int *grid,
+                       const std::function<std::string()> &fixed)
+{
+  if (lds > 160 * 1024) {
+    c->last_error = who + ": the workgroup's LDS image needs " + std::to_string(lds) + " of 163840 bytes: " +
+        (lds - (size_t) cj_cap * sizeof(int) > 160 * 1024
+             ? fixed()
+             : "the list's longest row, max_numneigh = " + std::to_string(c->max_numneigh) + ", is too large");
+    return MTP_ERR_LIMIT;
+  }
+  const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+  *grid = std::max(1, std::min(row_count, c->num_cus * per_cu));
   return MTP_OK;
 }
 
@@ -1545,35 +1603,21 @@ int mtp_design_rows_device(mtp_context *c, void *stream, const double *d_x, cons
   }
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
-    const int rc = design_prepare(c, st);
+    int rc = centre_prepare(c, st, false), grid = 0;
     if (rc != MTP_OK) return rc;
-    MtpDesignParams p = c->design;
-    p.row0 = row_begin;
-    p.nrows = row_count;
-    p.nowned = nowned;
-    p.nall = c->nall;
-    p.ld = ld;
-    p.cj_cap = std::max(c->max_numneigh, 1);
-    p.ilist = c->ilist;
-    p.first = c->first;
-    p.neigh = c->neigh;
-    p.type = d_type;
-    p.owner = d_owner;
-    p.x = d_x;
+    MtpDesignParams p{};
+    centre_bind(c, p, d_x, d_type, row_begin, row_count, d_owner, nowned, ld);
+    p.fmap = c->centre_fmap;
+    p.radial = c->d_design_radial.ptr;
     p.basis = d_basis;
     p.force = d_force;
     p.virial = d_virial_atom;
     const size_t lds = mtp_design_lds_layout(p);
-    if (lds > 160 * 1024) {
-      const size_t fixed = lds - (size_t) p.cj_cap * sizeof(int);
-      c->last_error = "mtp_design_rows_device: the workgroup's LDS image needs " + std::to_string(lds) + " of 163840 bytes: " +
-          (fixed > 160 * 1024 ? std::to_string(MTP_DESIGN_WAVES + 1) + " moment images of alpha_moments_count = " + std::to_string(p.A) +
-                   " doubles and nine rows of alpha_scalar_moments = " + std::to_string(p.S) + " are too large"
-                              : "the list's longest row, max_numneigh = " + std::to_string(c->max_numneigh) + ", is too large");
-      return MTP_ERR_LIMIT;
-    }
-    const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
-    const int grid = std::max(1, std::min(row_count, c->num_cus * per_cu));
+    rc = centre_grid(c, "mtp_design_rows_device", lds, p.cj_cap, row_count, &grid, [&] {
+      return std::to_string(MTP_DESIGN_WAVES + 1) + " moment images of alpha_moments_count = " + std::to_string(p.A) +
+          " doubles and nine rows of alpha_scalar_moments = " + std::to_string(p.S) + " are too large";
+    });
+    if (rc != MTP_OK) return rc;
     HIP_CHECK(mtp_launch_design_kernel(p, grid, lds, st));
   } catch (const HipFail &f) {
     c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
@@ -1595,70 +1639,6 @@ int mtp_batch_design_reduce(void *stream, int ncfg, const int *d_cfg_first, int 
 }
 
 // ---- training gradient (include/mtp_mi355x.h) -------------------------------------------------------------------------
-static int train_prepare(mtp_context *c, hipStream_t st)
-{
-  if (c->train_ready) return MTP_OK;
-  const mtp_potential &pot = *c->pot;
-  mtp_train_table t;
-  std::string msg;
-  const int rc = mtp_build_train_table(pot, t, msg);
-  if (rc != MTP_OK) {
-    c->last_error = msg;
-    return rc;
-  }
-  const mtp_design_table &dt = t.design;
-  if (dt.A > 8191) {
-    c->last_error = "training gradient: alpha_moments_count above 8191 is not supported by the packed times rows";
-    return MTP_ERR_LIMIT;
-  }
-  if (pot.radial_func_count > 16 || pot.max_alpha_index_basic > 16) {
-    c->last_error = "training gradient: radial_funcs_count or a basic index above 16 does not fit the packed basics";
-    return MTP_ERR_LIMIT;
-  }
-  std::vector<MtpRow8> rows8(dt.rows.size());
-  for (size_t k = 0; k < rows8.size(); k++) {
-    const MtpRow &r = dt.rows[k];
-    if (r.mult > 32767 || r.mult < -32768) {
-      c->last_error = "training gradient: a multiplicity of alpha_index_times does not fit 16 bits";
-      return MTP_ERR_LIMIT;
-    }
-    rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
-    rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
-  }
-  std::vector<int32_t> ints(dt.level_offset);
-  ints.insert(ints.end(), dt.basic_pack.begin(), dt.basic_pack.end());
-  ints.insert(ints.end(), dt.scalar_map.begin(), dt.scalar_map.end());
-  ints.insert(ints.end(), t.bymu.begin(), t.bymu.end());
-  ints.insert(ints.end(), t.mufirst.begin(), t.mufirst.end());
-  c->d_train_rows.upload(rows8, st);
-  c->d_train_ints.upload(ints, st);
-  HIP_CHECK(hipStreamSynchronize(st));   // (the staging vectors go out of scope)
-  MtpTrainParams &d = c->train;
-  d = MtpTrainParams{};
-  d.Sp = pot.species_count;
-  d.R = pot.radial_basis_size;
-  d.Mu = pot.radial_func_count;
-  d.P = pot.max_alpha_index_basic;
-  d.A = dt.A;
-  d.B = dt.B;
-  d.S = dt.S;
-  d.nblocks = dt.nblocks;
-  d.rmin = pot.min_cutoff;
-  d.rmax = pot.max_cutoff;
-  d.scaling = pot.scaling;
-  d.cutsq = pot.max_cutoff * pot.max_cutoff;
-  d.inv_span = 1.0 / (pot.max_cutoff - pot.min_cutoff);
-  d.rows = c->d_train_rows.ptr;
-  d.level = c->d_train_ints.ptr;
-  d.pack = d.level + dt.level_offset.size();
-  d.map = d.pack + dt.B;
-  d.bymu = d.map + dt.S;
-  d.mufirst = d.bymu + dt.B;
-  d.err_flag = c->d_err.ptr;
-  c->train_ready = true;
-  return MTP_OK;
-}
-
 // the checks and the launch both training calls share; `who` names the call in messages
 static int train_launch(mtp_context *c, const char *who, bool vjp, void *stream, const double *d_x, const int *d_type, int row_begin,
                         int row_count, const int *d_owner, const double *d_theta, int nowned, MtpTrainParams io, int ld)
@@ -1690,41 +1670,20 @@ static int train_launch(mtp_context *c, const char *who, bool vjp, void *stream,
   }
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
-    const int rc = train_prepare(c, st);   // (a refused table is reported even for an empty row range)
+    int rc = centre_prepare(c, st, true), grid = 0;   // (a refused table is reported even for an empty row range)
     if (rc != MTP_OK) return rc;
     if (row_count == 0) return MTP_OK;
-    MtpTrainParams p = c->train;
-    p.row0 = row_begin;
-    p.nrows = row_count;
-    p.nowned = nowned;
-    p.nall = c->nall;
-    p.ld = ld;
-    p.cj_cap = std::max(c->max_numneigh, 1);
-    p.ilist = c->ilist;
-    p.first = c->first;
-    p.neigh = c->neigh;
-    p.type = d_type;
-    p.owner = d_owner;
-    p.x = d_x;
+    MtpTrainParams p = io;   // (the caller's outputs and cotangents)
+    centre_bind(c, p, d_x, d_type, row_begin, row_count, d_owner, nowned, ld);
+    p.bymu = c->centre_bymu;
+    p.mufirst = c->centre_mufirst;
     p.theta = d_theta;
-    p.eatom = io.eatom;
-    p.force = io.force;
-    p.vatom = io.vatom;
-    p.ebar = io.ebar;
-    p.fbar = io.fbar;
-    p.vbar = io.vbar;
-    p.grad = io.grad;
     const size_t lds = mtp_train_lds_layout(p);
-    if (lds > 160 * 1024) {
-      const size_t fixed = lds - (size_t) p.cj_cap * sizeof(int);
-      c->last_error = w + ": the workgroup's LDS image needs " + std::to_string(lds) + " of 163840 bytes: " +
-          (fixed > 160 * 1024 ? "four moment images of alpha_moments_count = " + std::to_string(p.A) + " doubles and " +
-                   std::to_string(p.tab_rows) + " table rows are too large"
-                              : "the list's longest row, max_numneigh = " + std::to_string(c->max_numneigh) + ", is too large");
-      return MTP_ERR_LIMIT;
-    }
-    const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
-    const int grid = std::max(1, std::min(row_count, c->num_cus * per_cu));
+    rc = centre_grid(c, w, lds, p.cj_cap, row_count, &grid, [&] {
+      return "four moment images of alpha_moments_count = " + std::to_string(p.A) + " doubles and " + std::to_string(p.tab_rows) +
+          " table rows are too large";
+    });
+    if (rc != MTP_OK) return rc;
     HIP_CHECK(mtp_launch_train_kernel(p, vjp, grid, lds, st));
   } catch (const HipFail &f) {
     c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
@@ -1931,7 +1890,7 @@ void queue_coeffs(mtp_context *c, hipStream_t st, const mtp_coeff_tables &t)
   put(c->d_leaf_cf.ptr, t.leaf_cf);
   put(c->d_leaf_cb.ptr, t.leaf_cb);
   put(c->d_species.ptr, t.species);
-  if (c->design_ready) put(c->d_design_radial.ptr, t.radial);
+  if (c->centre_ready) put(c->d_design_radial.ptr, t.radial);
 }
 
 void commit_coeffs(mtp_context *c, const mtp_coeff_tables &t, const double *moments)
@@ -2097,7 +2056,7 @@ int mtp_context_coeff_tables_device(mtp_context *c, void *stream, int32_t *count
   const size_t n_rad = p.radial_basis_coeffs.size(), n_seed = p.seed_val.size(), n_lin = p.e_lin.size(), n_leaf = p.leaf_cf.size();
   const size_t n_w = p.has_selection ? (size_t) c->cpad * c->cpad : 0;
   if (counts) {
-    const size_t v[10] = {n_rad, n_seed, n_lin, n_leaf, n_leaf, p.species_coeffs.size(), c->design_ready ? n_rad : 0, n_w, n_w,
+    const size_t v[10] = {n_rad, n_seed, n_lin, n_leaf, n_leaf, p.species_coeffs.size(), c->centre_ready ? n_rad : 0, n_w, n_w,
                           (size_t) (b.scalars_in_lds ? 1 : 0)};
     for (int k = 0; k < 10; k++) counts[k] = (int32_t) v[k];
   }
@@ -2123,7 +2082,7 @@ int mtp_context_coeff_tables_device(mtp_context *c, void *stream, int32_t *count
     get(hbm_leaf_cf, c->d_leaf_cf.ptr, n_leaf);
     get(hbm_leaf_cb, c->d_leaf_cb.ptr, n_leaf);
     get(species, c->d_species.ptr, p.species_coeffs.size());
-    if (c->design_ready) get(design_radial, c->d_design_radial.ptr, n_rad);
+    if (c->centre_ready) get(design_radial, c->d_design_radial.ptr, n_rad);
     get(ainv_pad, c->d_ainv_pad.ptr, n_w);
     get(ainv_tiled, c->d_ainv_tiled.ptr, n_w);
     HIP_CHECK(hipStreamSynchronize(st));

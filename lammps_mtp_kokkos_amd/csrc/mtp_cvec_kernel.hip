@@ -226,13 +226,9 @@ __global__ void __launch_bounds__(512, 2) mtp_cvec_kernel(const MtpDevParams p)
 
 template <int KL, int KB> hipError_t launch_cvec(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st)
 {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mtp_cvec_kernel<KL, KB, 34>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  static std::atomic<unsigned long long> attr_mask{0};
+  const hipError_t e = mtp_raise_lds_limit(reinterpret_cast<const void *>(&mtp_cvec_kernel<KL, KB, 34>), attr_mask);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((mtp_cvec_kernel<KL, KB, 34>), dim3(grid), dim3(64 * wpb), lds, st, p);
   return hipGetLastError();
 }

@@ -15,9 +15,7 @@
 // are read from HBM / L2, lane-contiguous: at level 20 they are 51 KB, which would halve the directions in flight.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
-#include "mtp_kernel_common.hpp"
+#include "mtp_centre_common.hpp"
 
 namespace {
 
@@ -30,8 +28,7 @@ struct DesignInts {   // the integer tail of the image
   int *pack, *fmap, *map, *level, *nbown, *cj, *cnt;
 };
 
-// tile tables: val_mu | der_mu [Mu each] | r^-nu [P] | x^e, y^e, z^e [P each], one column per neighbour; eight threads
-// share a neighbour: the radial functions are dealt from the top of the eight, the power rows from the bottom
+// tile tables (mtp_centre_common.hpp; no rows of the kernel's own: the powers start at row 2 Mu); nb: u [3] | 1/r
 __device__ __forceinline__ void build_tile(const MtpDesignParams &p, double *tab, double *nb, const DesignInts &it, int t0, int nt,
                                            int itype, double xi0, double xi1, double xi2, int tid)
 {
@@ -39,57 +36,14 @@ __device__ __forceinline__ void build_tile(const MtpDesignParams &p, double *tab
   static_assert(NTHREADS / NT == 8, "eight threads per neighbour column");
   if (n < nt) {
     const int j = it.cj[t0 + n];
-    const double dx = p.x[3 * (size_t) j] - xi0, dy = p.x[3 * (size_t) j + 1] - xi1, dz = p.x[3 * (size_t) j + 2] - xi2;
-    const double r = sqrt(dx * dx + dy * dy + dz * dz);
-    const double inv = 1.0 / r;
-    const int Mu = p.Mu, P = p.P, R = p.R;
-    double *col = tab + n;
+    const CentreGeom g = tile_geom(p, j, xi0, xi1, xi2);
     if (part == 0) {
-      nb[n] = dx;
-      nb[NT + n] = dy;
-      nb[2 * NT + n] = dz;
-      nb[3 * NT + n] = inv;
+      tile_nb<NT>(nb, n, g.dx, g.dy, g.dz, g.inv);
       it.nbown[n] = p.owner ? p.owner[j] : j;
-      double rp = 1.0;
-      for (int nu = 0; nu < P; nu++) {
-        col[(2 * Mu + nu) * PITCH] = rp;
-        rp *= inv;
-      }
-    } else if (part <= 3) {
-      const double u = part == 1 ? dx : part == 2 ? dy : dz;
-      double cur = 1.0;
-      double *cp = col + (size_t) (2 * Mu + part * P) * PITCH;
-      for (int e = 0; e < P; e++) {
-        cp[e * PITCH] = cur;
-        cur *= u;
-      }
     }
+    tile_powers(tab + n, 2 * p.Mu, p.P, part, g.dx, g.dy, g.dz, g.inv);
     const int jt = p.type[j] - 1;   // (inside the potential: the compaction dropped the others)
-    // Q_ri(r) and dQ_ri/dr (mtp_rb_chevbyshev_basis.cpp:29-54)
-    const double d = r - p.rmax, mult = 2.0 * p.inv_span;
-    const double ksi = (2.0 * r - (p.rmin + p.rmax)) * p.inv_span;
-    for (int mu = 7 - part; mu < Mu; mu += 8) {
-      const double *c = p.radial + (size_t) ((itype * p.Sp + jt) * Mu + mu) * R;
-      double q0 = p.scaling * (d * d), q1 = p.scaling * (ksi * d * d);
-      double e0 = p.scaling * 2.0 * d, e1 = p.scaling * (mult * d * d + 2.0 * ksi * d);
-      double val = c[0] * q0, der = c[0] * e0;
-      if (R > 1) {
-        val += c[1] * q1;
-        der += c[1] * e1;
-      }
-      for (int ri = 2; ri < R; ri++) {
-        const double q2 = 2.0 * ksi * q1 - q0;
-        const double e2 = 2.0 * (mult * q1 + ksi * e1) - e0;
-        val += c[ri] * q2;
-        der += c[ri] * e2;
-        q0 = q1;
-        q1 = q2;
-        e0 = e1;
-        e1 = e2;
-      }
-      col[mu * PITCH] = val;
-      col[(Mu + mu) * PITCH] = der;
-    }
+    tile_radial<false>(p, p.radial, itype * p.Sp + jt, g.r, tab + n, part);
   }
 }
 
@@ -124,45 +78,12 @@ __global__ void __launch_bounds__(NTHREADS) mtp_design_kernel(const MtpDesignPar
   for (int ii = p.row0 + blockIdx.x; ii < p.row0 + p.nrows; ii += gridDim.x) {
     const int i = p.ilist[ii];
     const int itype = p.type[i] - 1;
-    if (itype < 0 || itype >= Sp || (unsigned) i >= (unsigned) p.nowned) {   // (uniform) pair_mtp.cpp:91-93
-      if (tid == 0) atomicExch(p.err_flag, itype < 0 || itype >= Sp ? 1 : 3);
-      continue;   // its basis and virial rows are left unassigned: the call has failed, the synchronise says so
-    }
+    if (!centre_ok(p, i, itype, tid)) continue;
     const double xi0 = p.x[3 * (size_t) i], xi1 = p.x[3 * (size_t) i + 1], xi2 = p.x[3 * (size_t) i + 2];
     const int jbeg = p.first[ii], jnum = p.first[ii + 1] - jbeg;
 
     // ---- compaction (wavefront 0, in list order), M and the accumulators zeroed by all
-    if (wave == 0) {
-      int cnt = 0;
-      for (int c0 = 0; c0 < jnum; c0 += 64) {
-        const int jj = c0 + lane;
-        bool in = false;
-        int j = 0;
-        if (jj < jnum) {
-          j = p.neigh[jbeg + jj] & MTP_NEIGHMASK;
-          if ((unsigned) j >= (unsigned) p.nall) {
-            atomicExch(p.err_flag, 3);
-          } else {
-            const int jt = p.type[j] - 1;
-            if (jt < 0 || jt >= Sp) {   // pair_mtp.cpp:116-118
-              atomicExch(p.err_flag, 1);
-            } else {
-              const double dx = p.x[3 * (size_t) j] - xi0, dy = p.x[3 * (size_t) j + 1] - xi1, dz = p.x[3 * (size_t) j + 2] - xi2;
-              in = !(dx * dx + dy * dy + dz * dz > p.cutsq);
-            }
-          }
-        }
-        const unsigned long long m = __ballot(in);
-        const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-        if (in && pos < p.cj_cap) it.cj[pos] = j;
-        cnt += __popcll(m);
-      }
-      if (cnt > p.cj_cap) {   // the list's max_numneigh sized the id array: refuse instead of overrunning LDS
-        if (lane == 0) atomicExch(p.err_flag, 2);
-        cnt = p.cj_cap;
-      }
-      if (lane == 0) it.cnt[0] = cnt;
-    }
+    if (wave == 0) compact_neighbours(p, jbeg, jnum, xi0, xi1, xi2, lane, it.cj, it.cnt);
     for (int k = tid; k < A; k += NTHREADS) M[k] = 0.0;
     for (int k = tid; k < 9 * S; k += NTHREADS) acc[k] = 0.0;
     __syncthreads();
@@ -176,26 +97,18 @@ __global__ void __launch_bounds__(NTHREADS) mtp_design_kernel(const MtpDesignPar
       build_tile(p, tab, nb, it, t0, nt, itype, xi0, xi1, xi2, tid);
       __syncthreads();
       for (int k = tid; k < B; k += NTHREADS) {
-        const int pk = it.pack[k];
-        const int a = (pk >> 8) & 15, b = (pk >> 12) & 15, c = (pk >> 16) & 15, mu = (pk >> 20) & 15;
-        const double *rv = tab + mu * PITCH, *ri = tab + (2 * Mu + a + b + c) * PITCH;
-        const double *xa = tab + (2 * Mu + P + a) * PITCH, *yb = tab + (2 * Mu + 2 * P + b) * PITCH,
-                     *zc = tab + (2 * Mu + 3 * P + c) * PITCH;
+        const CentreBasic bk = decode_basic(it.pack[k]);
+        const double *rv = tab + bk.mu * PITCH, *ri = tab + (2 * Mu + bk.a + bk.b + bk.c) * PITCH;
+        const double *xa = tab + (2 * Mu + P + bk.a) * PITCH, *yb = tab + (2 * Mu + 2 * P + bk.b) * PITCH,
+                     *zc = tab + (2 * Mu + 3 * P + bk.c) * PITCH;
         double s = 0.0;
         for (int n = 0; n < nt; n++) s += (rv[n] * ri[n]) * (xa[n] * (yb[n] * zc[n]));
         M[k] += s;
       }
     }
     __syncthreads();
-    // ---- products of M, one dependency level at a time (rows of a level commute; padding rows add zero)
-    for (int l = 0; l < p.nblocks; l++) {
-      for (int r = it.level[l] + tid; r < it.level[l + 1]; r += NTHREADS) {
-        const MtpRow8 rw = p.rows[r];
-        const double v = M[(rw.lo & 0xffffu) >> 3] * M[rw.lo >> 19];
-        lds_add(&M[(rw.hi & 0xffffu) >> 3], (double) ((int) rw.hi >> 16) * v);
-      }
-      __syncthreads();
-    }
+    // ---- products of M
+    product_pass<true, false, NTHREADS>(p.rows, it.level, p.nblocks, M, nullptr, tid);
     // ---- site-energy design row
     if (p.basis) {
       double *row = p.basis + (size_t) (ii - p.row0) * p.ld;
@@ -219,33 +132,19 @@ __global__ void __launch_bounds__(NTHREADS) mtp_design_kernel(const MtpDesignPar
         for (int k = lane; k < A; k += 64) {
           double v = 0.0;
           if (k < B) {
-            const int pk = it.pack[k];
-            const int a = (pk >> 8) & 15, b = (pk >> 12) & 15, cc = (pk >> 16) & 15, mu = (pk >> 20) & 15, nu = a + b + cc;
-            const double nf = col[(2 * Mu + nu) * PITCH];
-            const double val = col[mu * PITCH] * nf;
-            const double der = col[(Mu + mu) * PITCH] * nf - (double) nu * val * inv;
-            const double pa = col[(2 * Mu + P + a) * PITCH], pb = col[(2 * Mu + 2 * P + b) * PITCH],
-                         pc = col[(2 * Mu + 3 * P + cc) * PITCH];
-            v = (pa * pb * pc) * (der * inv) * uc;
-            const int e = c == 0 ? a : c == 1 ? b : cc;
+            const CentreBasic bk = decode_basic(it.pack[k]);
+            const CentreTangent t = basic_tangent(col, Mu, 2 * Mu, P, bk, inv);
+            v = (t.pa * t.pb * t.pc) * (t.der * inv) * uc;
+            const int e = c == 0 ? bk.a : c == 1 ? bk.b : bk.c;
             if (e > 0) {   // chain rule for the monomial
-              const double low = col[(2 * Mu + (1 + c) * P + e - 1) * PITCH];
-              const double others = c == 0 ? pb * pc : c == 1 ? pa * pc : pa * pb;
-              v += val * (double) e * low * others;
+              const double others = c == 0 ? t.pb * t.pc : c == 1 ? t.pa * t.pc : t.pa * t.pb;
+              v += t.val * (double) e * tangent_low(col, 2 * Mu, P, c, e) * others;
             }
           }
           dM[k] = v;
         }
         wave_fence();
-        for (int l = 0; l < p.nblocks; l++) {
-          for (int r = it.level[l] + lane; r < it.level[l + 1]; r += 64) {
-            const MtpRow8 rw = p.rows[r];
-            const int a0 = (rw.lo & 0xffffu) >> 3, a1 = rw.lo >> 19;
-            const double v = dM[a0] * M[a1] + M[a0] * dM[a1];
-            lds_add(&dM[(rw.hi & 0xffffu) >> 3], (double) ((int) rw.hi >> 16) * v);
-          }
-          wave_fence();
-        }
+        product_pass<false, true, 64>(p.rows, it.level, p.nblocks, M, dM, lane);
         // scatter: lanes = scalars.  An image of the centre itself takes the two force terms to the same row: they cancel
         const int own = it.nbown[n];
         const bool own_ok = (unsigned) own < (unsigned) p.nowned;
@@ -329,19 +228,9 @@ size_t mtp_design_lds_layout(MtpDesignParams &p)
 
 hipError_t mtp_launch_design_kernel(const MtpDesignParams &p, int grid, size_t lds, hipStream_t st)
 {
-  // the dynamic-LDS limit is a per-device attribute of the function: one bit per device id (as the force launchers);
-  // contexts on different devices may launch from different host threads, so the mask is atomic (setting the attribute
-  // twice is harmless, losing a bit would only repeat it)
   static std::atomic<unsigned long long> attr_mask{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = mtp_raise_lds_limit(reinterpret_cast<const void *>(&mtp_design_kernel), attr_mask);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev > 63 || !((attr_mask.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mtp_design_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev <= 63) attr_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
   hipLaunchKernelGGL(mtp_design_kernel, dim3(grid), dim3(NTHREADS), lds, st, p);
   return hipGetLastError();
 }

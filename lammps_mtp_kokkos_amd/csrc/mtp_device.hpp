@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 
@@ -198,24 +199,37 @@ hipError_t mtp_launch_list_from_2d(int inum, const int *d_ilist, const int *d_nu
                                    long long stride_i, long long stride_jj, int cap, int *counts, void *cub_tmp,
                                    size_t cub_bytes, int *first, int *neigh, int *d_info, hipStream_t st);
 
-// ---- design rows (mtp_design.hip; include/mtp_mi355x.h, "linear refit") ------------------------------------------------
-#define MTP_DESIGN_WAVES 4    // wavefronts per workgroup = per centre atom
-#define MTP_DESIGN_NT 32      // neighbours per LDS tile (table row pitch MTP_PITCH doubles)
-struct MtpDesignParams {
-  int Sp, R, Mu, P, A, B, S, nblocks;   // nblocks: level blocks of the row table, the leaf block included
-  double rmin, rmax, scaling, cutsq, inv_span;
-  // the kernel's own table (mtp_design_table, HBM / L2; the small integer tables are copied into LDS once per workgroup)
-  const MtpRow8 *rows;   // byte offsets into a moment image with a slot for every moment
-  const int *level;      // [nblocks + 1] padded row offsets
-  const int *pack;       // [B] slot | a << 8 | b << 12 | c << 16 | mu << 20
-  const int *map, *fmap; // [S] moment of every scalar; the same or -1 (no force column)
-  const double *radial;  // [Sp][Sp][Mu][R]
+// ---- the kernels with one workgroup per centre atom (mtp_centre_common.hpp) -----------------------------------------------
+// What the design and the training kernel share: the system of one call, the error flag, the shape and the structural
+// table (mtp_train_table, HBM / L2; the small integer tables are copied into LDS once per workgroup).  The order of the
+// blocks is the one of five tried that leaves no register column of the three kernels above the flat blocks it replaces
+// (profiles/r11_code_objects.txt): both kernels sit at the SGPR ceiling, and the order decides what is spilled
+struct MtpCentreParams {
   // system
   int row0, nrows, nowned, nall, ld, cj_cap;
   const int *ilist, *first, *neigh, *type, *owner;
   const double *x;
-  double *basis, *force, *virial;
   int *err_flag;
+  int Sp, R, Mu, P, A, B, S, nblocks;   // nblocks: level blocks of the row table, the leaf block included
+  double rmin, rmax, scaling, cutsq, inv_span;
+  const MtpRow8 *rows;   // byte offsets into a moment image with a slot for every moment
+  const int *level;      // [nblocks + 1] padded row offsets
+  const int *pack;       // [B] slot | a << 8 | b << 12 | c << 16 | mu << 20
+  const int *map;        // [S] moment of every scalar
+};
+// Raises the dynamic-LDS limit of kernel `fn` to the CU's 160 KB, once per device.  The limit is a per-device attribute of
+// the function: `mask` (the launcher's own, static) has one bit per device id.  Contexts on different devices may launch
+// from different host threads, so the mask is atomic (setting the attribute twice is harmless, losing a bit would only
+// repeat it)
+hipError_t mtp_raise_lds_limit(const void *fn, std::atomic<unsigned long long> &mask);
+
+// ---- design rows (mtp_design.hip; include/mtp_mi355x.h, "linear refit") ------------------------------------------------
+#define MTP_DESIGN_WAVES 4    // wavefronts per workgroup = per centre atom
+#define MTP_DESIGN_NT 32      // neighbours per LDS tile (table row pitch MTP_PITCH doubles)
+struct MtpDesignParams : MtpCentreParams {
+  const int *fmap;       // [S] map, or -1 (no force column)
+  const double *radial;  // [Sp][Sp][Mu][R]
+  double *basis, *force, *virial;
   // workgroup LDS image, offsets in doubles: M[a_pad] | dM[MTP_DESIGN_WAVES][a_pad] | acc[9][S] | tab[tab_rows][MTP_PITCH] |
   // nbx, nby, nbz, 1/r [MTP_DESIGN_NT each] | ints
   int a_pad, off_dm, off_acc, off_tab, off_nb, off_int, tab_rows;
@@ -229,25 +243,13 @@ hipError_t mtp_launch_batch_design_reduce(int ncfg, const int *cfg_first, int ld
 // ---- training gradient (mtp_train.hip; include/mtp_mi355x.h, "training gradient") ---------------------------------------
 #define MTP_TRAIN_WAVES 4     // wavefronts per workgroup = per centre atom
 #define MTP_TRAIN_NT 32       // neighbours per LDS tile (table row pitch MTP_PITCH doubles)
-struct MtpTrainParams {
-  int Sp, R, Mu, P, A, B, S, nblocks;   // nblocks: level blocks of the row table, the leaf block included
-  double rmin, rmax, scaling, cutsq, inv_span;
-  // the structural table (mtp_train_table: the design table and the basics sorted by mu), HBM / L2
-  const MtpRow8 *rows;
-  const int *level;      // [nblocks + 1] padded row offsets
-  const int *pack;       // [B] slot | a << 8 | b << 12 | c << 16 | mu << 20
-  const int *map;        // [S] moment of every scalar (no two scalars share one)
+struct MtpTrainParams : MtpCentreParams {   // (no two scalars share a moment of map: the table was checked)
   const int *bymu;       // [B] basics ordered by mu
   const int *mufirst;    // [Mu + 1] offsets into bymu
   const double *theta;   // [C] radial [Sp][Sp][Mu][R] | species [Sp] | moments [S]
-  // system
-  int row0, nrows, nowned, nall, ld, cj_cap;
-  const int *ilist, *first, *neigh, *type, *owner;
-  const double *x;
   double *eatom, *force, *vatom;             // value
   const double *ebar, *fbar, *vbar;          // vjp (each may be null: zero)
   double *grad;                              // vjp: [nrows][ld]
-  int *err_flag;
   // workgroup LDS image, offsets in doubles: M | dM | D | dD [a_pad each] | tab[tab_rows][MTP_PITCH] | u, 1/r, du, dr
   // [8][MTP_TRAIN_NT] | scratch | radial block [Sp Mu R] | ints
   int a_pad, off_tab, off_nb, off_scr, off_rad, off_int, tab_rows;

@@ -521,17 +521,9 @@ __global__ void __launch_bounds__(256) mtp_batch_grade_scale_kernel(int ncfg, co
 template <int KL, int NB, int PITCH, bool GRADE, int DEG, int WPS>
 hipError_t launch_one(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st)
 {
-  // the dynamic-LDS limit is a per-device attribute of the function: one bit per device id
-  static unsigned long long attr_mask = 0;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static std::atomic<unsigned long long> attr_mask{0};
+  const hipError_t e = mtp_raise_lds_limit(reinterpret_cast<const void *>(&mtp_wave_kernel<KL, NB, PITCH, GRADE, DEG, WPS>), attr_mask);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev > 63 || !((attr_mask >> dev) & 1ull)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mtp_wave_kernel<KL, NB, PITCH, GRADE, DEG, WPS>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev <= 63) attr_mask |= 1ull << dev;
-  }
   hipLaunchKernelGGL((mtp_wave_kernel<KL, NB, PITCH, GRADE, DEG, WPS>), dim3(grid), dim3(64 * wpb), lds, st, p);
   return hipGetLastError();
 }
@@ -695,6 +687,19 @@ hipError_t mtp_launch_batch_grade_scale(int ncfg, const int *cfg_first, double *
 {
   hipLaunchKernelGGL(mtp_batch_grade_scale_kernel, dim3((ncfg + 255) / 256), dim3(256), 0, st, ncfg, cfg_first, cfg_grade);
   return hipGetLastError();
+}
+
+hipError_t mtp_raise_lds_limit(const void *fn, std::atomic<unsigned long long> &mask)
+{
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev > 63 || !((mask.load(std::memory_order_acquire) >> dev) & 1ull)) {
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev <= 63) mask.fetch_or(1ull << dev, std::memory_order_release);
+  }
+  return hipSuccess;
 }
 
 hipError_t mtp_launch_fixed_to_force(long long *fq, double *f, int nall, hipStream_t st)

@@ -37,17 +37,10 @@ template <class SH> bool selects(const MtpDevParams &p)
 
 template <class SH> hipError_t launch_shape(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st)
 {
-  // the dynamic-LDS limit is a per-device attribute of the function: one bit per device id
-  static unsigned long long attr_mask = 0;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
+  static std::atomic<unsigned long long> attr_mask{0};
   auto *fn = &mtp_wave_kernel_fixed<SH::kKL, SH::kNB, SH::kPITCH, SH::kGRADE, SH::kDEG, SH::kWPS, SH>;
-  if (dev < 0 || dev > 63 || !((attr_mask >> dev) & 1ull)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev <= 63) attr_mask |= 1ull << dev;
-  }
+  const hipError_t e = mtp_raise_lds_limit(reinterpret_cast<const void *>(fn), attr_mask);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * wpb), lds, st, p);
   return hipGetLastError();
 }

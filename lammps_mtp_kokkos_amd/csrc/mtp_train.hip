@@ -15,9 +15,7 @@
 // one level share a target.  The gradient row is assigned by its workgroup: no atomics to global memory in vjp mode.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
-#include "mtp_kernel_common.hpp"
+#include "mtp_centre_common.hpp"
 
 namespace {
 
@@ -41,33 +39,15 @@ __device__ __forceinline__ void build_tile(const MtpTrainParams &p, double *tab,
   const int n = tid & (NT - 1), part = tid / NT;
   if (n < nt) {
     const int j = it.cj[t0 + n];
-    const double dx = p.x[3 * (size_t) j] - xi0, dy = p.x[3 * (size_t) j + 1] - xi1, dz = p.x[3 * (size_t) j + 2] - xi2;
-    const double r = sqrt(dx * dx + dy * dy + dz * dz);
-    const double inv = 1.0 / r;
-    const int Mu = p.Mu, P = p.P, R = p.R;
-    const int pw0 = 2 * Mu + 2 * R;
-    double *col = tab + n;
+    const CentreGeom g = tile_geom(p, j, xi0, xi1, xi2);
+    const double dx = g.dx, dy = g.dy, dz = g.dz, inv = g.inv;
     const int jt = p.type[j] - 1;   // (inside the potential: the compaction dropped the others)
     if (part == 0) {
-      nb[n] = dx;
-      nb[NT + n] = dy;
-      nb[2 * NT + n] = dz;
-      nb[3 * NT + n] = inv;
+      tile_nb<NT>(nb, n, dx, dy, dz, inv);
       it.nbtype[n] = jt;
-      double rp = 1.0;
-      for (int nu = 0; nu < P; nu++) {
-        col[(pw0 + nu) * PITCH] = rp;
-        rp *= inv;
-      }
-    } else if (part <= 3) {
-      const double u = part == 1 ? dx : part == 2 ? dy : dz;
-      double cur = 1.0;
-      double *cp = col + (size_t) (pw0 + part * P) * PITCH;
-      for (int e = 0; e < P; e++) {
-        cp[e * PITCH] = cur;
-        cur *= u;
-      }
-    } else if (part == 4) {
+    }
+    tile_powers(tab + n, 2 * p.Mu + 2 * p.R, p.P, part, dx, dy, dz, inv);
+    if (part == 4) {
       int own = p.owner ? p.owner[j] : j;
       if ((unsigned) own >= (unsigned) p.nowned) {
         atomicExch(p.err_flag, 3);
@@ -93,44 +73,7 @@ __device__ __forceinline__ void build_tile(const MtpTrainParams &p, double *tab,
         nb[7 * NT + n] = (dx * d0 + dy * d1 + dz * d2) * inv;
       }
     }
-    // Q_ri(r) and dQ_ri/dr (mtp_rb_chevbyshev_basis.cpp:29-54); the thread of mu = 0 keeps them
-    const double d = r - p.rmax, mult = 2.0 * p.inv_span;
-    const double ksi = (2.0 * r - (p.rmin + p.rmax)) * p.inv_span;
-    for (int mu = 7 - part; mu < Mu; mu += 8) {
-      const double *c = p.theta + (size_t) ((itype * p.Sp + jt) * Mu + mu) * R;
-      const bool keep = mu == 0;
-      double q0 = p.scaling * (d * d), q1 = p.scaling * (ksi * d * d);
-      double e0 = p.scaling * 2.0 * d, e1 = p.scaling * (mult * d * d + 2.0 * ksi * d);
-      double val = c[0] * q0, der = c[0] * e0;
-      if (keep) {
-        col[(2 * Mu) * PITCH] = q0;
-        col[(2 * Mu + R) * PITCH] = e0;
-      }
-      if (R > 1) {
-        val += c[1] * q1;
-        der += c[1] * e1;
-        if (keep) {
-          col[(2 * Mu + 1) * PITCH] = q1;
-          col[(2 * Mu + R + 1) * PITCH] = e1;
-        }
-      }
-      for (int ri = 2; ri < R; ri++) {
-        const double q2 = 2.0 * ksi * q1 - q0;
-        const double e2 = 2.0 * (mult * q1 + ksi * e1) - e0;
-        val += c[ri] * q2;
-        der += c[ri] * e2;
-        if (keep) {
-          col[(2 * Mu + ri) * PITCH] = q2;
-          col[(2 * Mu + R + ri) * PITCH] = e2;
-        }
-        q0 = q1;
-        q1 = q2;
-        e0 = e1;
-        e1 = e2;
-      }
-      col[mu * PITCH] = val;
-      col[(Mu + mu) * PITCH] = der;
-    }
+    tile_radial<true>(p, p.theta, itype * p.Sp + jt, g.r, tab + n, part);   // (Q_rho and Q'_rho kept)
   }
 }
 
@@ -172,46 +115,13 @@ template <bool VJP> __global__ void __launch_bounds__(NTHREADS) mtp_train_kernel
     const int i = p.ilist[ii];
     const int row = ii - p.row0;
     const int itype = p.type[i] - 1;
-    if (itype < 0 || itype >= Sp || (unsigned) i >= (unsigned) p.nowned) {   // (uniform) pair_mtp.cpp:91-93
-      if (tid == 0) atomicExch(p.err_flag, itype < 0 || itype >= Sp ? 1 : 3);
-      continue;   // its outputs are left unassigned: the call has failed, the synchronise says so
-    }
+    if (!centre_ok(p, i, itype, tid)) continue;
     const double xi0 = p.x[3 * (size_t) i], xi1 = p.x[3 * (size_t) i + 1], xi2 = p.x[3 * (size_t) i + 2];
     const int jbeg = p.first[ii], jnum = p.first[ii + 1] - jbeg;
     const double eb = VJP && p.ebar ? p.ebar[row] : 0.0;
 
     // ---- compaction (wavefront 0, in list order); the images zeroed by all
-    if (wave == 0) {
-      int cnt = 0;
-      for (int c0 = 0; c0 < jnum; c0 += 64) {
-        const int jj = c0 + lane;
-        bool in = false;
-        int j = 0;
-        if (jj < jnum) {
-          j = p.neigh[jbeg + jj] & MTP_NEIGHMASK;
-          if ((unsigned) j >= (unsigned) p.nall) {
-            atomicExch(p.err_flag, 3);
-          } else {
-            const int jt = p.type[j] - 1;
-            if (jt < 0 || jt >= Sp) {   // pair_mtp.cpp:116-118
-              atomicExch(p.err_flag, 1);
-            } else {
-              const double dx = p.x[3 * (size_t) j] - xi0, dy = p.x[3 * (size_t) j + 1] - xi1, dz = p.x[3 * (size_t) j + 2] - xi2;
-              in = !(dx * dx + dy * dy + dz * dz > p.cutsq);
-            }
-          }
-        }
-        const unsigned long long m = __ballot(in);
-        const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-        if (in && pos < p.cj_cap) it.cj[pos] = j;
-        cnt += __popcll(m);
-      }
-      if (cnt > p.cj_cap) {   // the list's max_numneigh sized the id array: refuse instead of overrunning LDS
-        if (lane == 0) atomicExch(p.err_flag, 2);
-        cnt = p.cj_cap;
-      }
-      if (lane == 0) it.cnt[0] = cnt;
-    }
+    if (wave == 0) compact_neighbours(p, jbeg, jnum, xi0, xi1, xi2, lane, it.cj, it.cnt);
     for (int k = tid; k < 4 * p.a_pad; k += NTHREADS) M[k] = 0.0;   // M | dM | D | dD
     for (int k = tid; k < blk; k += NTHREADS) rad[k] = 0.0;
     __syncthreads();
@@ -225,8 +135,8 @@ template <bool VJP> __global__ void __launch_bounds__(NTHREADS) mtp_train_kernel
       build_tile<VJP>(p, tab, nb, it, t0, nt, i, itype, row, xi0, xi1, xi2, tid);
       __syncthreads();
       for (int k = tid; k < B; k += NTHREADS) {
-        const int pk = it.pack[k];
-        const int a = (pk >> 8) & 15, b = (pk >> 12) & 15, c = (pk >> 16) & 15, mu = (pk >> 20) & 15, nu = a + b + c;
+        const CentreBasic bk = decode_basic(it.pack[k]);
+        const int a = bk.a, b = bk.b, c = bk.c, mu = bk.mu, nu = bk.nu;
         const double *rv = tab + mu * PITCH, *rd = tab + (Mu + mu) * PITCH, *ri = tab + (pw0 + nu) * PITCH;
         const double *xa = tab + (pw0 + P + a) * PITCH, *yb = tab + (pw0 + 2 * P + b) * PITCH, *zc = tab + (pw0 + 3 * P + c) * PITCH;
         double s = 0.0, ds = 0.0;
@@ -249,27 +159,17 @@ template <bool VJP> __global__ void __launch_bounds__(NTHREADS) mtp_train_kernel
       }
     }
     __syncthreads();
-    // ---- products, one dependency level at a time (rows of a level commute; padding rows add zero)
-    for (int l = 0; l < p.nblocks; l++) {
-      for (int r = it.level[l] + tid; r < it.level[l + 1]; r += NTHREADS) {
-        const MtpRow8 rw = p.rows[r];
-        const int a0 = (rw.lo & 0xffffu) >> 3, a1 = rw.lo >> 19, a3 = (rw.hi & 0xffffu) >> 3;
-        const double m = (double) ((int) rw.hi >> 16);
-        lds_add(&M[a3], m * (M[a0] * M[a1]));
-        if (VJP) lds_add(&dM[a3], m * (dM[a0] * M[a1] + M[a0] * dM[a1]));
-      }
-      __syncthreads();
-    }
+    // ---- products of M (and of dM)
+    product_pass<true, VJP, NTHREADS>(p.rows, it.level, p.nblocks, M, dM, tid);
     // ---- adjoint: seeded by assignment with the moment coefficients (one scalar per moment: the table was checked), swept
     // through the levels in reverse; a row's target is complete before its level is reached
     for (int s = tid; s < S; s += NTHREADS) D[it.map[s]] = xi[s];
     __syncthreads();
     for (int l = p.nblocks - 1; l >= 0; l--) {
       for (int r = it.level[l] + tid; r < it.level[l + 1]; r += NTHREADS) {
-        const MtpRow8 rw = p.rows[r];
-        const int a0 = (rw.lo & 0xffffu) >> 3, a1 = rw.lo >> 19, a3 = (rw.hi & 0xffffu) >> 3;
-        const double m = (double) ((int) rw.hi >> 16);
-        const double d3 = m * D[a3], m0 = M[a0], m1 = M[a1];
+        const CentreRow w = decode_row(p.rows[r]);
+        const int a0 = w.a0(), a1 = w.a1(), a3 = w.a3();
+        const double m = w.mult(), d3 = m * D[a3], m0 = M[a0], m1 = M[a1];
         if (VJP) {
           const double dd3 = m * dD[a3];
           lds_add(&dD[a1], dd3 * m0 + d3 * dM[a0]);
@@ -306,19 +206,17 @@ template <bool VJP> __global__ void __launch_bounds__(NTHREADS) mtp_train_kernel
             const double u0 = nb[n], u1 = nb[NT + n], u2 = nb[2 * NT + n], inv = nb[3 * NT + n];
             const double *col = tab + n;
             for (int k = part; k < B; k += NPART) {
-              const int pk = it.pack[k];
-              const int a = (pk >> 8) & 15, b = (pk >> 12) & 15, c = (pk >> 16) & 15, mu = (pk >> 20) & 15, nu = a + b + c;
-              const double nf = col[(pw0 + nu) * PITCH];
-              const double val = col[mu * PITCH] * nf;
-              const double der = col[(Mu + mu) * PITCH] * nf - (double) nu * val * inv;
-              const double pa = col[(pw0 + P + a) * PITCH], pb = col[(pw0 + 2 * P + b) * PITCH], pc = col[(pw0 + 3 * P + c) * PITCH];
+              const CentreBasic bk = decode_basic(it.pack[k]);
+              const int a = bk.a, b = bk.b, c = bk.c;
+              const CentreTangent t = basic_tangent(col, Mu, pw0, P, bk, inv);
+              const double pa = t.pa, pb = t.pb, pc = t.pc;
               const double dk = D[k];
-              const double rad_part = dk * (pa * pb * pc) * (der * inv);
+              const double rad_part = dk * (pa * pb * pc) * (t.der * inv);
               double g0 = rad_part * u0, g1 = rad_part * u1, g2 = rad_part * u2;
-              const double dv = dk * val;
-              if (a > 0) g0 += dv * (double) a * col[(pw0 + P + a - 1) * PITCH] * pb * pc;
-              if (b > 0) g1 += dv * (double) b * pa * col[(pw0 + 2 * P + b - 1) * PITCH] * pc;
-              if (c > 0) g2 += dv * (double) c * pa * pb * col[(pw0 + 3 * P + c - 1) * PITCH];
+              const double dv = dk * t.val;
+              if (a > 0) g0 += dv * (double) a * tangent_low(col, pw0, P, 0, a) * pb * pc;
+              if (b > 0) g1 += dv * (double) b * pa * tangent_low(col, pw0, P, 1, b) * pc;
+              if (c > 0) g2 += dv * (double) c * pa * pb * tangent_low(col, pw0, P, 2, c);
               t0x += g0;
               t1x += g1;
               t2x += g2;
@@ -373,16 +271,16 @@ template <bool VJP> __global__ void __launch_bounds__(NTHREADS) mtp_train_kernel
             const double *col = tab + n;
             for (int q = it.mufirst[mu]; q < it.mufirst[mu + 1]; q++) {
               const int k = it.bymu[q];
-              const int pk = it.pack[k];
-              const int a = (pk >> 8) & 15, b = (pk >> 12) & 15, c = (pk >> 16) & 15, nu = a + b + c;
-              const double nf = col[(pw0 + nu) * PITCH];
-              const double pa = col[(pw0 + P + a) * PITCH], pb = col[(pw0 + 2 * P + b) * PITCH], pc = col[(pw0 + 3 * P + c) * PITCH];
-              const double w = nf * (pa * (pb * pc));
+              const CentreBasic bk = decode_basic(it.pack[k]);
+              const int a = bk.a, b = bk.b, c = bk.c;
+              const CentreTangent t = basic_tangent(col, Mu, pw0, P, bk, inv);   // (f_mu is Q_rho's factor here: nf and the powers)
+              const double pa = t.pa, pb = t.pb, pc = t.pc;
+              const double w = t.nf * (pa * (pb * pc));
               double gm = 0.0;
-              if (a > 0) gm += (double) a * col[(pw0 + P + a - 1) * PITCH] * pb * pc * du0;
-              if (b > 0) gm += (double) b * pa * col[(pw0 + 2 * P + b - 1) * PITCH] * pc * du1;
-              if (c > 0) gm += (double) c * pa * pb * col[(pw0 + 3 * P + c - 1) * PITCH] * du2;
-              const double dw = nf * gm - (double) nu * w * inv * dr;
+              if (a > 0) gm += (double) a * tangent_low(col, pw0, P, 0, a) * pb * pc * du0;
+              if (b > 0) gm += (double) b * pa * tangent_low(col, pw0, P, 1, b) * pc * du1;
+              if (c > 0) gm += (double) c * pa * pb * tangent_low(col, pw0, P, 2, c) * du2;
+              const double dw = t.nf * gm - (double) bk.nu * w * inv * dr;
               const double dk = D[k];
               sa += (eb * dk + dD[k]) * w + dk * dw;
               sb += dk * w;
@@ -442,20 +340,10 @@ size_t mtp_train_lds_layout(MtpTrainParams &p)
 
 hipError_t mtp_launch_train_kernel(const MtpTrainParams &p, bool vjp, int grid, size_t lds, hipStream_t st)
 {
-  // the dynamic-LDS limit is a per-device attribute of each function: one bit per device id (as the design launcher)
-  static std::atomic<unsigned long long> attr_mask{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  static std::atomic<unsigned long long> attr_mask[2];   // (value, vjp: two functions, each with its own limit)
+  const void *fn = vjp ? reinterpret_cast<const void *>(&mtp_train_kernel<true>) : reinterpret_cast<const void *>(&mtp_train_kernel<false>);
+  const hipError_t e = mtp_raise_lds_limit(fn, attr_mask[vjp]);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev > 63 || !((attr_mask.load(std::memory_order_acquire) >> dev) & 1ull)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mtp_train_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mtp_train_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev <= 63) attr_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
   if (vjp) hipLaunchKernelGGL(mtp_train_kernel<true>, dim3(grid), dim3(NTHREADS), lds, st, p);
   else hipLaunchKernelGGL(mtp_train_kernel<false>, dim3(grid), dim3(NTHREADS), lds, st, p);
   return hipGetLastError();

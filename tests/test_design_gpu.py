@@ -78,12 +78,12 @@ def _host(d):
 
 
 # ---- entries through the low-level call, on stars with exact neighbour counts ----------------------------------------------
-def _design_rows_of_stars(fname, st, neigh=None):
+def _design_rows_of_stars(fname, st, neigh=None, ctx=None):
     """Context.design_rows over a star system with d_owner = NULL (every atom is its own owner): dict(basis [stars, cols],
-    force [nall, 3, cols], virial [stars, 6, cols])"""
+    force [nall, 3, cols], virial [stars, 6, cols]); ctx: another context than the shared one of the file"""
     import torch
     dev, stream = _device_stream()
-    ctx = _ctx(fname)
+    ctx = ctx or _ctx(fname)
     info = ctx.pot.info
     cols = info.species_count + info.alpha_scalar_count
     ld = cols + (cols & 1) + 2                               # (a leading dimension above the columns: the pad is zeroed)
@@ -101,10 +101,10 @@ def _design_rows_of_stars(fname, st, neigh=None):
     return dict(basis=b[:, :cols], force=f[:, :cols].reshape(st.nall, 3, cols), virial=v[:, :, :cols])
 
 
-def _check_stars(fname, st, got, label):
+def _check_stars(fname, st, got, label, orc=None):
     """per star and per column with the star's own scale (the rule of _stars.per_star_check): a three-tile star must not be
-    able to hide a one-neighbour one"""
-    want = _design.oracle_columns(_oracle(fname), st.x, st.types, st.ilist, st.first, st.neigh)
+    able to hide a one-neighbour one; orc: another oracle than the shared one of the file"""
+    want = _design.oracle_columns(orc or _oracle(fname), st.x, st.types, st.ilist, st.first, st.neigh)
     worst = 0.0
     bounds = list(st.start) + [st.nall]
     for s in range(len(st.ilist)):

@@ -540,6 +540,102 @@ def test_an_owner_outside_the_owned_atoms_is_reported_and_the_flag_cleared():
     _judge_stars(h2, st, theta, cots, _star_call(ctx, st, theta, *cots, owner_t=torch.from_numpy(owner).to(dev)), "after the flag")
 
 
+# ---- design and training calls on one context: one table, one prepare ------------------------------------------------------
+# Stars of 1, 32, 33 and 65 neighbours (one, two and three tiles): the smallest rows at which an offset into the shared
+# integer table that is wrong for one kind of call, or a part of it that only one order of first use fills, shows.  Design
+# rows against the oracle's columns (test_design_gpu._check_stars), training calls as everywhere above (_judge_stars).
+from test_design_gpu import _check_stars, _design_rows_of_stars  # noqa: E402
+
+SHARED_KL = [(1, 2), (32, 33), (33, 33), (65, 129)]
+
+
+def _fresh(h):
+    """the handles of h with a context of their own: nothing prepared yet"""
+    f = _Handles.__new__(_Handles)
+    f.__dict__.update(h.__dict__, ctx=capi.Context(h.pot, 0))
+    return f
+
+
+def _train_both(h, st, what, theta=None):
+    theta = h.perturbed_theta() if theta is None else theta
+    cots = _train.row_cotangents(st, 83)
+    _judge_stars(h, st, theta, cots, _star_call(h.ctx, st, theta, *cots), what)
+
+
+def _design_at(h, st, what, theta=None):
+    """the design rows of h.ctx against the oracle's columns at theta's radial block (None: the file's)"""
+    got = _design_rows_of_stars(None, st, ctx=h.ctx)
+    theta0 = _train.get_theta(h.orc)
+    try:
+        if theta is not None:
+            _train.set_theta(h.orc, theta)
+        _check_stars(None, st, got, what, orc=h.orc)
+    finally:
+        _train.set_theta(h.orc, theta0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first", ["design", "train"])
+def test_design_and_training_calls_in_either_order_on_one_context(first):
+    h = _fresh(_handles("W_L8.mtp"))
+    st = _train.star_set(h.tables, SHARED_KL, 82)
+    if first == "design":
+        _design_at(h, st, "design first")
+        _train_both(h, st, "value and vjp after a design call")
+        _design_at(h, st, "design again")
+    else:
+        _train_both(h, st, "training first")
+        _design_at(h, st, "design after the training calls")
+
+
+@pytest.mark.gpu
+def test_an_install_between_a_training_and_a_design_call_reaches_the_design_radial_block():
+    """the one prepare ran on the training call, so the install has to refresh the design kernel's copy of the radial block"""
+    h = _fresh(_handles("W_L8.mtp"))
+    st = _train.star_set(h.tables, SHARED_KL, 84)
+    _train_both(h, st, "training call ahead of the install")
+    theta = h.pot.theta()
+    theta[:h.nrad] *= 1.0 + 0.05 * np.random.default_rng(85).normal(size=h.nrad)
+    h.ctx.install_coeffs(radial_coeffs=theta[:h.nrad])
+    _design_at(h, st, "design at the installed radial block", theta)
+    stale = _design_rows_of_stars("W_L8.mtp", st)            # (the shared context of the file: the old block gives other rows)
+    assert np.abs(stale["force"] - _design_rows_of_stars(None, st, ctx=h.ctx)["force"]).max() > 1e-6
+
+
+@pytest.mark.gpu
+def test_design_calls_succeed_on_a_table_the_training_calls_refuse(tmp_path):
+    """tests/_mutate.py on W_L16.mtp (the table of test_train_error_paths): every training call returns the refusal and its
+    message, before and after a design call on the same context and for an empty row range as well; the design call matches
+    the oracle's columns"""
+    import torch
+    dev, stream = _device_stream()
+    bad = str(tmp_path / "mutated.mtp")
+    _mutate.mutate_mtp(os.path.join(POT, "W_L16.mtp"), bad)
+    h = _Handles(bad)
+    msg = h.pot.train_table()["message"]
+    assert "alpha_index_times" in msg
+    st = _train.star_set(h.tables, SHARED_KL, 86)
+    h.ctx.set_neighbors(st.ilist, st.first, st.neigh, st.nall)
+    n, C = len(st.ilist), len(h.pot.theta())
+    x_t, t_t = torch.from_numpy(st.x).to(dev), torch.from_numpy(st.types).to(dev)
+    th_t = torch.from_numpy(h.pot.theta()).to(dev)
+    force = torch.zeros((st.nall, 3), dtype=torch.float64, device=dev)
+    rows = torch.zeros((n, C + (C & 1)), dtype=torch.float64, device=dev)
+
+    def refused():
+        for count in (n, 0):
+            for call in (lambda: h.ctx.train_value(0, count, x_t, t_t, th_t, force, st.nall, stream=stream),
+                         lambda: h.ctx.train_vjp(0, count, x_t, t_t, th_t, rows, st.nall, C + (C & 1), stream=stream)):
+                with pytest.raises(capi.MtpError) as ei:
+                    call()
+                assert ei.value.code == -6 and msg in str(ei.value), (count, str(ei.value))
+        assert not force.any().item() and not rows.any().item()          # nothing was launched
+
+    refused()
+    _design_at(h, st, "design on the refused table")
+    refused()
+
+
 # ---- error paths and untouched paths ---------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_train_error_paths(tmp_path):
