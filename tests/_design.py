@@ -3,11 +3,16 @@ design matrix is the reference algorithm itself, by linearity.  Column Sp + a of
 oracle's {energy, folded forces, virial} for the same potential with species_coeffs = 0 and moment_coeffs = e_a; column t
 is the same with species_coeffs = e_t and moment_coeffs = 0.  The coefficients are set in place through the oracle's
 Model.linear_coeffs / species_coeffs pointers and restored afterwards."""
+import functools
 import os
+import tempfile
+from types import SimpleNamespace
 
 import numpy as np
 
 import _cells
+import _stars
+import _train
 from lammps_mtp_kokkos_amd.driver import periodic_system_cell
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,6 +90,146 @@ def check_columns(got, want, what, kinds=("energy", "force", "virial")):
         assert np.isfinite(g).all() and ratio <= 1.0, "%s %s: misses 1e-9 + 1e-10 max|column| %.2f-fold" % (what, k, ratio)
         worst = max(worst, ratio)
     return worst
+
+
+def star_ratios(st, got, want, per_star=True):
+    """the rule of test_design_gpu._check_stars: dict(basis, force, virial) of error / bound per star, each kind with the
+    column's maximum over the star's own rows of that kind, so that a three-tile star cannot hide a one-neighbour one.
+    got: dict(basis [stars, cols], force [owned atoms, 3, cols], virial [stars, 6, cols]); want: oracle_columns.
+    per_star = False (an owner map that folds atoms of several stars onto one row): the force rows are judged once, with
+    the column's scale over all owned rows, and every star carries that figure.  A non-finite entry gives inf."""
+    n, ncol = len(st.ilist), want["energy"].size
+    wf = want["force"].reshape(-1, 3, ncol)
+    assert got["basis"].shape == (n, ncol) and got["virial"].shape == (n, 6, ncol) and got["force"].shape == wf.shape, (
+        got["basis"].shape, got["virial"].shape, got["force"].shape, wf.shape)
+
+    def ratio(g, w):
+        return column_ratio(g, w) if np.isfinite(g).all() else np.inf
+
+    out = dict(basis=np.zeros(n), force=np.zeros(n), virial=np.zeros(n))
+    bounds = None if not per_star else list(st.start) + [st.nall]
+    for s in range(n):
+        c = st.ilist[s]
+        out["basis"][s] = ratio(got["basis"][s][None, :], want["eatom"][c][None, :])
+        out["virial"][s] = ratio(got["virial"][s], want["vatom"][c])
+        if per_star:
+            a, b = bounds[s], bounds[s + 1]
+            out["force"][s] = ratio(got["force"][a:b].reshape(-1, ncol), wf[a:b].reshape(-1, ncol))
+    if not per_star and n:
+        out["force"][:] = ratio(got["force"].reshape(-1, ncol), wf.reshape(-1, ncol))
+    return out
+
+
+# ---- the star sets of the design kernel's edge tests: tests/test_design_gpu.py runs the kernel on them, tests/test_design_cpu.py
+# the numpy twin and damaged copies of its output.  Built once, shared, never written to. -----------------------------------
+LEVEL8_MODES = [(None, "mixed"), ("edge", "mixed"), (None, "straddle")]
+# K = 0, 1, 33 and 65 mixed; the cuts make a K = 0 row the first and a three-tile row the last of a range
+RANGE_KL = [(0, 2), (1, 3), (33, 40), (65, 70), (0, 0), (1, 1), (33, 33), (65, 129), (1, 5), (33, 64), (0, 1), (65, 66)]
+RANGE_CUTS = (4, 10)
+OWNER_FORMS = ("identity", "fold", "self")
+SHARED_ROWS = 8
+BITS_KL = [(0, 1), (1, 2), (33, 40), (5, 9), (2, 2)]
+SECOND_KL = [(0, 3), (1, 2), (33, 40), (2, 2), (64, 70), (0, 0)]
+UNDERSTATED_KL = [(9, 9), (3, 3)]
+SPECIAL_BITS = np.int32(-2 ** 31 + 2 ** 30)                      # the top two bits of a list entry
+
+
+@functools.lru_cache(maxsize=None)
+def handles(name):
+    """namespace(path, pot, tables, orc) of a file of potentials/ or of a key of test_train_gpu.GENERATED, which is written
+    once into a directory that lives as long as the process"""
+    from lammps_mtp_kokkos_amd import capi, mtpgen
+    from oracle.pyoracle import Oracle
+    path, keep = os.path.join(POT, name), None
+    if not os.path.exists(path):
+        from test_train_gpu import GENERATED
+        level, Sp, seed, rmin, rmax, R, scaling = GENERATED[name]
+        keep = tempfile.TemporaryDirectory()
+        path = os.path.join(keep.name, name + ".mtp")
+        mtpgen.write_mtp(mtpgen.random_potential(mtpgen.build_table(level), Sp, seed, rmin, rmax, R, scaling), path)
+    pot = capi.Potential(path)
+    return SimpleNamespace(path=path, pot=pot, tables=pot.tables(), orc=Oracle(path), keep=keep)
+
+
+def star_cases():
+    """name -> (potential, [(K, L)], seed, special, order) of every plain star set of the edge tests"""
+    from test_train_gpu import GENERATED, GENERATED_KL, SMALL_KL
+    cases = {}
+    for special, order in LEVEL8_MODES:
+        cases["level8-%s-%s" % (special, order)] = ("W_L8.mtp", _train.STAR_EDGE_KL, 71, special, order)
+    for special in (None, "edge"):
+        for fname in ("W_L16.mtp", "WRe_L20.mtp"):
+            cases["%s-%s" % (fname, special)] = (fname, SMALL_KL, 72, special, "mixed")
+        for which in sorted(GENERATED):
+            cases["%s-%s" % (which, special)] = (which, GENERATED_KL, 73, special, "mixed")
+    cases["ranges"] = ("W_L8.mtp", RANGE_KL, 91, None, "mixed")
+    cases["bits"] = ("W_L8.mtp", BITS_KL, 93, None, "mixed")
+    cases["second"] = ("W_L8.mtp", SECOND_KL, 94, None, "mixed")
+    cases["understated"] = ("W_L8.mtp", UNDERSTATED_KL, 95, None, "mixed")
+    return cases
+
+
+def all_cases():
+    return sorted(star_cases()) + ["owner-" + f for f in OWNER_FORMS]
+
+
+@functools.lru_cache(maxsize=None)
+def star_case(name):
+    """namespace(name, pot, h, st, owner, nowned, per_star) of a case of all_cases().  The owner cases are the stars of
+    RANGE_KL under a map that is (identity) arange, GIVEN; (fold) many-to-one: the atoms renumbered centres first, the owned
+    atoms are the centres and the SHARED_ROWS outer atoms behind them, every other outer atom j is folded onto owned row
+    stars + j % SHARED_ROWS; (self) the identity, except that in the first K = 33 star the first in-cutoff entry of the row
+    (tile 0) and the 33rd (tile 1) are owned by the star's own centre"""
+    if name.startswith("owner-"):
+        pot, form = "W_L8.mtp", name[len("owner-"):]
+        st = _train.star_set(handles(pot).tables, RANGE_KL, 92)
+        owner, nowned = np.arange(st.nall, dtype=np.int32), st.nall
+        if form == "fold":
+            st = _stars.centres_first(st)
+            n = len(st.ilist)
+            nowned = n + SHARED_ROWS
+            owner[nowned:] = n + np.arange(nowned, st.nall) % SHARED_ROWS
+        elif form == "self":
+            s = [K for K, L in st.KL].index(33)
+            e = _stars.in_cutoff_entries(st, s)
+            owner[st.neigh[e[[0, 32]]]] = st.ilist[s]
+        else:
+            assert form == "identity"
+        return SimpleNamespace(name=name, pot=pot, h=handles(pot), st=st, owner=owner, nowned=nowned, per_star=form != "fold")
+    pot, KL, seed, special, order = star_cases()[name]
+    st = _train.star_set(handles(pot).tables, KL, seed, special, order, shuffle=order != "straddle")
+    return SimpleNamespace(name=name, pot=pot, h=handles(pot), st=st, owner=None, nowned=st.nall, per_star=True)
+
+
+@functools.lru_cache(maxsize=None)
+def case_want(name):
+    """oracle_columns of a case: one oracle call per column, made once"""
+    c = star_case(name)
+    st = c.st
+    return oracle_columns(c.h.orc, st.x, st.types, st.ilist, st.first, st.neigh, c.owner, c.nowned)
+
+
+def marked_list(st):
+    """a copy of the list with the top two bits set on every third entry, the 33rd in-cutoff entry of the K = 33 star among
+    them: the marked entries span both tiles of that star"""
+    s = [K for K, L in st.KL].index(33)
+    in33 = _stars.in_cutoff_entries(st, s)
+    ne = st.neigh.copy()
+    ne[int(in33[32]) % 3::3] |= SPECIAL_BITS
+    pos = np.flatnonzero(ne[in33] < 0)
+    assert (pos < 32).any() and pos[-1] == 32 and ((ne & 0x1FFFFFFF) == st.neigh).all() and (ne < 0).sum() >= len(ne) // 3
+    return ne
+
+
+def twin_rows(tables, st, owner=None, nowned=None, neigh=None):
+    """driver.design_twin over a star set, in the form star_ratios takes"""
+    from lammps_mtp_kokkos_amd.driver import System, design_twin
+    s = System(x=st.x, types=st.types, nlocal=st.nall if nowned is None else nowned,
+               owner=np.arange(st.nall) if owner is None else owner, box=np.zeros(3), ilist=st.ilist, first=st.first,
+               neigh=st.neigh if neigh is None else neigh, cutoff=st.rc)
+    t = design_twin(tables, s)
+    n, ncol = len(st.ilist), t["basis"].shape[1]
+    return dict(basis=t["basis"][:n].copy(), force=t["force"].reshape(-1, 3, ncol).copy(), virial=t["virial_atom"][:n].copy())
 
 
 def replica16_cell(seed=5):

@@ -123,6 +123,29 @@ def shuffled_rows(st, rng):
     return ne
 
 
+def in_cutoff_entries(st, s, neigh=None):
+    """positions in the list (indices into neigh) of star s's entries inside the cutoff, in row order: the order in which
+    the compaction of the centre kernels keeps them, entry k of it in tile k // 32"""
+    ne = st.neigh if neigh is None else neigh
+    a, b = int(st.first[s]), int(st.first[s + 1])
+    d = st.x[ne[a:b]] - st.x[st.ilist[s]]
+    return a + np.flatnonzero(~(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2] > st.rc * st.rc))
+
+
+def centres_first(st):
+    """the same stars with the atoms renumbered: the centres are atoms 0 .. stars - 1 in row order (ilist = arange), the
+    outer atoms follow in their old order.  For owner maps that fold the outer atoms onto a few owned rows behind the
+    centres.  The atoms of a star are no longer contiguous: start is None."""
+    n = len(st.ilist)
+    outer = np.setdiff1d(np.arange(st.nall), st.ilist)
+    old = np.concatenate([st.ilist, outer]).astype(np.int64)       # old[new]
+    new = np.empty(st.nall, dtype=np.int64)
+    new[old] = np.arange(st.nall)
+    return SimpleNamespace(x=np.ascontiguousarray(st.x[old]), types=st.types[old].copy(), ilist=np.arange(n, dtype=np.int32),
+                           first=st.first.copy(), neigh=new[st.neigh].astype(np.int32), nall=st.nall, sid=st.sid[old],
+                           KL=list(st.KL), start=None, rc=st.rc)
+
+
 def _star_max(st, a):
     """max |a| over the atoms of every star -> [stars]"""
     a = np.abs(np.asarray(a, dtype=np.float64)).reshape(len(a), -1).max(1)

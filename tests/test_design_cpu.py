@@ -1,9 +1,11 @@
 """CPU checks of the linear refit (include/mtp_mi355x.h, "linear refit"): the numpy twin of the design-row kernel against
 the oracle's unit-coefficient columns, the coefficient writer, the tangent kernel's host-side table, and both under the
 sanitizers in a stand-alone program."""
+import functools
 import os
 import subprocess
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -11,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _cells  # noqa: E402
 import _design  # noqa: E402
+import _stars  # noqa: E402
 import _tables  # noqa: E402
 from _mutate import mutate_mtp  # noqa: E402
 from lammps_mtp_kokkos_amd import capi, driver, mtpgen  # noqa: E402
@@ -41,6 +44,212 @@ def test_design_twin_with_scaling_and_another_window(tmp_path):
     path = _tables.write(tab, nfac, str(tmp_path / "scaled.mtp"), species=2, R=6, scaling=2.5, min_dist=1.9, max_dist=4.6)
     assert capi.Potential(path).info.scaling == 2.5
     _twin_against_oracle(path, _cells.tilted5_cell(2), "scaled")
+
+
+# ---- the star sets of tests/test_design_gpu.py: the twin alone, and the judge on damaged copies of the twin's rows -------------
+# tests/_design.star_case builds every set the GPU tests run (tile, row-length and straddle edges up to four tiles, levels 16
+# and 20, the generated potentials with five and three species, a scaling, nine radial functions and a 5.5 A cutoff, the
+# row-range set and the three owner maps); star_ratios is the rule of test_design_gpu._check_stars.  First the reference
+# alone: the twin must be inside 1e-9 + 1e-10 max |column| on every one of them, else the INPUT is wrong for the bound.
+# Then the twin's rows damaged the way a subtly wrong kernel would damage them: the rule must reject the damaged star, and
+# no other.  The GPU entries land a thousand times inside the bound; this is what shows the bound still bites.
+@functools.lru_cache(maxsize=None)
+def _twin(name):
+    c = _design.star_case(name)
+    return _design.twin_rows(c.h.tables, c.st, c.owner, c.nowned)
+
+
+def _ratios(name, got):
+    c = _design.star_case(name)
+    return _design.star_ratios(c.st, got, _design.case_want(name), c.per_star)
+
+
+def _copy(rows):
+    return {k: v.copy() for k, v in rows.items()}
+
+
+def _only(r, stars, kinds=("basis", "force", "virial"), what=""):
+    """the listed kinds miss the bound at every listed star; every other star, and the other kinds, are inside it"""
+    stars = np.atleast_1d(stars)
+    assert len(stars), what + ": no star is damaged"
+    for k in ("basis", "force", "virial"):
+        hit = np.zeros(len(r[k]), dtype=bool)
+        if k in kinds:
+            hit[stars] = True
+        print("%s %s: error / bound at the damaged stars %.3e .. %.3e, elsewhere at most %.3e" % (
+            what, k, r[k][hit].min() if hit.any() else 0.0, r[k][hit].max() if hit.any() else 0.0,
+            r[k][~hit].max() if (~hit).any() else 0.0))
+        assert (r[k][hit] > 1.0).all(), (what, k, "accepted at star", int(np.flatnonzero(hit)[np.argmin(r[k][hit])]))
+        assert (r[k][~hit] <= 1.0).all(), (what, k, "rejected at star", int(np.flatnonzero(~hit)[np.argmax(r[k][~hit])]))
+
+
+@pytest.mark.parametrize("name", _design.all_cases())
+def test_twin_alone_is_inside_the_bound_on_every_star_set_of_the_gpu_tests(name):
+    r = _ratios(name, _twin(name))
+    worst = max(float(v.max()) for v in r.values())
+    print("%s: twin against the oracle's columns, worst error / bound over %d stars %.3e" % (name, len(r["basis"]), worst))
+    assert worst <= 1.0
+
+
+def _virial_of(G, u):
+    """the six virial rows [6, cols] of one neighbour at u with tangent G [3, cols] (pair_mtp.cpp:257-276)"""
+    return -np.array([G[0] * u[0], G[1] * u[1], G[2] * u[2], 0.5 * (G[0] * u[1] + G[1] * u[0]),
+                      0.5 * (G[0] * u[2] + G[2] * u[0]), 0.5 * (G[1] * u[2] + G[2] * u[1])])
+
+
+PLAIN8 = "level8-None-mixed"
+
+
+def _star_with(name, K):
+    return [k for k, l in _design.star_case(name).st.KL].index(K)
+
+
+def test_judge_rejects_the_33rd_neighbour_left_out_of_the_basics():
+    """the one column of a second tile: the twin over a list without the entry; basis row, force rows and virial rows of
+    that star all lack it"""
+    c = _design.star_case(PLAIN8)
+    st, s = c.st, _star_with(PLAIN8, 33)
+    e = int(_stars.in_cutoff_entries(st, s)[32])
+    first = st.first.copy()
+    first[s + 1:] -= 1
+    cut = SimpleNamespace(**dict(vars(st), first=first, neigh=np.delete(st.neigh, e)))
+    _only(_ratios(PLAIN8, _design.twin_rows(c.h.tables, cut)), s, what="33rd neighbour not in the basics")
+
+
+def test_judge_rejects_the_33rd_neighbour_left_out_of_the_directions():
+    """its direction never run: the basis row is right, its own force row stays zero, the centre's row and the virial
+    rows lack its term"""
+    c = _design.star_case(PLAIN8)
+    st, s = c.st, _star_with(PLAIN8, 33)
+    j, i = int(st.neigh[_stars.in_cutoff_entries(st, s)[32]]), int(st.ilist[s])
+    got = _copy(_twin(PLAIN8))
+    G = -got["force"][j]
+    got["force"][j] = 0.0
+    got["force"][i] -= G
+    got["virial"][s] -= _virial_of(G, st.x[j] - st.x[i])
+    _only(_ratios(PLAIN8, got), s, ("force", "virial"), "33rd neighbour not in the directions")
+
+
+@pytest.mark.parametrize("name", ["scaling-None", "nine_radial-None"])
+def test_judge_rejects_the_radial_block_of_the_transposed_species_pair(name):
+    """jt * Sp + itype for itype * Sp + jt, on two and on three species: every star with an in-cutoff neighbour of another
+    species than its centre is rejected, every other one (K = 0, one species throughout) is untouched"""
+    c = _design.star_case(name)
+    st, t = c.st, dict(c.h.tables)
+    Sp = len(t["species_coeffs"])
+    assert Sp == (2 if name.startswith("scaling") else 3)
+    t["radial_coeffs"] = np.asarray(t["radial_coeffs"]).reshape(Sp, Sp, -1).transpose(1, 0, 2).reshape(-1).copy()
+    mixed = [s for s in range(len(st.ilist))
+             if (st.types[st.neigh[_stars.in_cutoff_entries(st, s)]] != st.types[st.ilist[s]]).any()]
+    assert 0 < len(mixed) < len(st.ilist) and any(st.KL[s][0] == 1 for s in mixed)
+    _only(_ratios(name, _design.twin_rows(t, st)), mixed, what="transposed pair, %d species" % Sp)
+
+
+def test_judge_rejects_a_scaling_taken_as_one():
+    c = _design.star_case("scaling-None")
+    assert c.h.tables["scaling"] == 2.5
+    some = [s for s, (K, L) in enumerate(c.st.KL) if K > 0]
+    _only(_ratios("scaling-None", _design.twin_rows(dict(c.h.tables, scaling=1.0), c.st)), some, what="scaling = 1")
+
+
+def _chain_term(tables, st, s, coord):
+    """(G [K, cols], js, u): the part of the tangents of star s that comes from the e - 1 term of coordinate `coord` alone
+    (val e u_c^(e-1) times the other two powers, pair_mtp.cpp:163-191), pushed through the times rows as the twin does"""
+    basic = np.asarray(tables["alpha_index_basic"], dtype=np.int64).reshape(-1, 4)
+    times = np.asarray(tables["alpha_index_times"], dtype=np.int64).reshape(-1, 4)
+    mapping = np.asarray(tables["alpha_moment_mapping"], dtype=np.int64)
+    Sp, B = len(tables["species_coeffs"]), len(basic)
+    Mu = int(basic[:, 0].max()) + 1
+    radial = np.asarray(tables["radial_coeffs"], dtype=np.float64).reshape(Sp, Sp, Mu, -1)
+    R = radial.shape[-1]
+    A = int(max(B, times[:, [0, 1, 3]].max() + 1, mapping.max() + 1))
+    rmin, rmax = float(tables["min_cutoff"]), float(tables["max_cutoff"])
+    i = int(st.ilist[s])
+    js = st.neigh[_stars.in_cutoff_entries(st, s)]
+    u = st.x[js] - st.x[i]
+    r = np.sqrt((u * u).sum(1))
+    d, ksi = r - rmax, (2.0 * r - (rmin + rmax)) / (rmax - rmin)
+    q = np.zeros((R, len(js)))
+    q[0], q[1] = float(tables["scaling"]) * d * d, float(tables["scaling"]) * ksi * d * d
+    for ri in range(2, R):
+        q[ri] = 2.0 * ksi * q[ri - 1] - q[ri - 2]
+    val_mu = np.einsum("kmr,rk->mk", radial[st.types[i] - 1, st.types[js] - 1], q)
+    ex = basic[:, 1:4]
+    P = int(ex.sum(1).max()) + 1
+    pw = u.T[:, None, :] ** np.arange(P)[None, :, None]
+    val = val_mu[basic[:, 0]] * (1.0 / r)[None, :] ** ex.sum(1)[:, None]
+    p = [pw[0][ex[:, 0]], pw[1][ex[:, 1]], pw[2][ex[:, 2]]]
+    M, dM = np.zeros(A), np.zeros((A, len(js)))
+    M[:B] = (val * p[0] * p[1] * p[2]).sum(1)
+    p[coord] = ex[:, coord][:, None] * pw[coord][np.maximum(ex[:, coord] - 1, 0)]
+    dM[:B] = val * p[0] * p[1] * p[2]
+    for a0, a1, mlt, a3 in times:
+        M[a3] += mlt * M[a0] * M[a1]
+    for a0, a1, mlt, a3 in times:
+        dM[a3] += mlt * (dM[a0] * M[a1] + M[a0] * dM[a1])
+    last = {int(m): k for k, m in enumerate(mapping)}
+    fcol = np.array([last[int(m)] == k for k, m in enumerate(mapping)])
+    return np.concatenate([np.zeros((Sp, len(js))), dM[mapping] * fcol[:, None]]).T, js, u
+
+
+@pytest.mark.parametrize("coord", [0, 2])
+def test_judge_rejects_a_dropped_chain_rule_term_of_one_coordinate(coord):
+    c = _design.star_case(PLAIN8)
+    st, s = c.st, _star_with(PLAIN8, 2)
+    Gc, js, u = _chain_term(c.h.tables, st, s, coord)
+    got = _copy(_twin(PLAIN8))
+    # the twin's rows are right with the term: taking it out of a copy and putting it back must give the rows again
+    for sign in (1.0, -1.0):
+        for n, j in enumerate(js):
+            G = np.zeros((3, Gc.shape[1]))
+            G[coord] = sign * Gc[n]
+            got["force"][j] += G
+            got["force"][st.ilist[s]] -= G
+            got["virial"][s] -= _virial_of(G, u[n])
+        if sign > 0:
+            _only(_ratios(PLAIN8, got), s, ("force", "virial"), "e - 1 term of coordinate %d dropped" % coord)
+    assert max(float(v.max()) for v in _ratios(PLAIN8, got).values()) <= 1.0
+
+
+def test_judge_rejects_exchanged_xz_and_yz_virial_halves():
+    c = _design.star_case(PLAIN8)
+    got = _copy(_twin(PLAIN8))
+    got["virial"][:, [4, 5]] = got["virial"][:, [5, 4]]
+    _only(_ratios(PLAIN8, got), [s for s, (K, L) in enumerate(c.st.KL) if K > 0], ("virial",), "xz and yz exchanged")
+
+
+def test_judge_rejects_rows_of_a_ranged_call_placed_at_ii():
+    """rows [a, b) of the row-range set written at ii where they belong at ii - a, into arrays of b - a rows filled with
+    7.0: the rows that still land inside the array are other stars' rows, the rest keeps the fill"""
+    a, b = _design.RANGE_CUTS
+    got = _copy(_twin("ranges"))
+    for kind in ("basis", "virial"):
+        out = np.full((b - a,) + got[kind].shape[1:], 7.0)
+        for ii in range(a, b):
+            if ii < b - a:
+                out[ii] = got[kind][ii]
+        got[kind][a:b] = out
+    _only(_ratios("ranges", got), np.arange(a, b), ("basis", "virial"), "rows at ii")
+
+
+def test_judge_rejects_1e8_relative_on_one_column_of_a_one_neighbour_star_beside_four_tile_stars():
+    """the per-star scale is what catches it: with the column's scale taken over all stars, the 97-neighbour stars' entries
+    would let it pass"""
+    c = _design.star_case(PLAIN8)
+    st, want = c.st, _design.case_want(PLAIN8)
+    bounds = list(st.start) + [st.nall]
+    best = (0.0, None, None)
+    for s, (K, L) in enumerate(st.KL):
+        if K == 1:
+            m = np.abs(want["f_all"][bounds[s]:bounds[s + 1]]).max((0, 1))
+            best = max(best, (float(m.max()), s, int(np.argmax(m))))
+    m, s, col = best
+    # 1e-8 m > 1e-9 + 1e-10 m needs m > 0.102
+    assert m > 0.2 and max(K for K, L in st.KL) == 97, m
+    got = _copy(_twin(PLAIN8))
+    got["force"][bounds[s]:bounds[s + 1], :, col] *= 1.0 + 1e-8
+    _only(_ratios(PLAIN8, got), s, ("force",), "1e-8 relative on column %d of star %d" % (col, s))
+    assert _design.column_ratio(got["force"], want["f_all"]) <= 1.0
 
 
 # ---- the tangent kernel's table ----------------------------------------------------------------------------------------

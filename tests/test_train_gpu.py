@@ -377,15 +377,20 @@ def _handles(fname):
     return _Handles(os.path.join(POT, fname))
 
 
-def _star_call(ctx, st, theta, ebar, fbar, vbar, owner_t=None, pad=2, value=True, vjp=True):
-    """both modes over all rows of a star set; outputs filled with 7.0 beforehand (forces are accumulated into: zero)"""
+def _star_call(ctx, st, theta, ebar, fbar, vbar, owner_t=None, pad=2, value=True, vjp=True, neigh=None, max_numneigh=None):
+    """both modes over all rows of a star set; outputs filled with 7.0 beforehand (forces are accumulated into: zero).  neigh:
+    another list than st.neigh; max_numneigh: install the list as DEVICE arrays with this declared row length"""
     import torch
     dev, stream = _device_stream()
     C = len(theta)
     ld = C + (C & 1) + pad
     nrows, nall = len(st.ilist), st.nall
-    ctx.set_neighbors(st.ilist, st.first, st.neigh, nall)
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ne = st.neigh if neigh is None else neigh
+    if max_numneigh is None:
+        ctx.set_neighbors(st.ilist, st.first, ne, nall)
+    else:
+        ctx.set_neighbors_device(to(st.ilist.astype(np.int32)), to(st.first.astype(np.int32)), to(ne.astype(np.int32)), nall, max_numneigh)
     x_t, t_t, th_t = to(st.x), to(st.types), to(theta)
     own = None if owner_t is None else owner_t.data_ptr()
     out = {}
@@ -538,6 +543,32 @@ def test_an_owner_outside_the_owned_atoms_is_reported_and_the_flag_cleared():
     h2 = _Handles.__new__(_Handles)
     h2.__dict__.update(h.__dict__, ctx=ctx)
     _judge_stars(h2, st, theta, cots, _star_call(ctx, st, theta, *cots, owner_t=torch.from_numpy(owner).to(dev)), "after the flag")
+
+
+@pytest.mark.gpu
+def test_understated_max_numneigh_is_reported_not_overrun():
+    """a device list of stars (9, 9), (3, 3) declared with max_numneigh = 8 (tests/_design.star_case): cj_cap is 8 and the row
+    keeps 9, so compact_neighbours stores 8 ids, clips the count and raises flag 2; the synchronise after either mode
+    reports MTP_ERR_LIMIT and clears the flag.  The same list with the honest length then agrees with the oracle and the twin"""
+    h = _fresh(_handles("W_L8.mtp"))
+    st = _design.star_case("understated").st
+    assert _stars.counts(st) == [(9, 9), (3, 3)]
+    theta, cots = h.perturbed_theta(), _train.row_cotangents(st, 87)
+    for mode in (dict(vjp=False), dict(value=False)):
+        with pytest.raises(capi.MtpError, match="max_numneigh") as ei:
+            _star_call(h.ctx, st, theta, *cots, max_numneigh=8, **mode)
+        assert ei.value.code == -24
+    _judge_stars(h, st, theta, cots, _star_call(h.ctx, st, theta, *cots, max_numneigh=9), "honest max_numneigh")
+
+
+@pytest.mark.gpu
+def test_list_entries_with_special_bond_bits_give_the_values_and_rows_of_the_clean_list():
+    """& MTP_NEIGHMASK in compact_neighbours: the top two bits set on a third of the entries, in both tiles of a K = 33 star;
+    both modes are judged as on the clean list"""
+    h = _handles("W_L8.mtp")
+    st = _design.star_case("bits").st
+    theta, cots = h.perturbed_theta(), _train.row_cotangents(st, 88)
+    _judge_stars(h, st, theta, cots, _star_call(h.ctx, st, theta, *cots, neigh=_design.marked_list(st)), "marked list")
 
 
 # ---- design and training calls on one context: one table, one prepare ------------------------------------------------------
