@@ -17,7 +17,10 @@
 #include "../../include/mtp_mi355x.h"
 #include "mtp_device.hpp"
 #include "mtp_shape_fields.hpp"
+#include "mtp_plan.hpp"
 #include "mtp_potential.hpp"
+
+using namespace mtp_plan;
 
 namespace {
 
@@ -69,9 +72,7 @@ struct mtp_context {
   std::string last_error;
   int variant = MTP_VARIANT_AUTO;
   int num_cus = 256;
-  // LDS table blob: the pieces a launch plan may leave in HBM / L2 are its tail -- [core | adjoint scatter targets |
-  // basic descriptors (candidate-vector kernel) | packed times rows]; a plan copies one of these four prefixes
-  int blob_bytes_core = 0, blob_bytes_tgt = 0, blob_bytes_norows = 0, blob_bytes_rows = 0;
+  BlobSizes blob_sizes;   // the four prefixes of the table blob a launch plan may copy (mtp_plan.hpp)
   bool xcd_map = true;   // MTP_XCD_MAP=0 (tuning override) turns the XCD-aware atom map off
   // potential tables
   DevBuf<double> d_species;
@@ -99,19 +100,7 @@ struct mtp_context {
   DevBuf<int> d_err;
   DevBuf<unsigned long long> d_stamps;
   // launch geometry
-  struct Layout {   // per-atom LDS image, offsets in doubles (MtpDevParams: dg_mode, pow_row, dg_off, off_*)
-    int mode = 0, pow_row = 0, dg_off = 0, fp_row = 0, off_m = 0, off_d = 0, off_coef = 0, off_nb = 0, m_doubles = 0;
-  };
-  struct LaunchPlan {
-    Layout layout;
-    int wpb = 1, grid = 1, wave_doubles = 0, tab_rows = 0, g_doubles = 0, m_doubles = 0, ov_doubles = 0;
-    bool rebuild = false;
-    int wps = 2;
-    bool rows_lds = false, tgt_lds = true;
-    int blob_bytes = 0;   // the blob prefix this plan copies
-    size_t lds_bytes = 0;
-  } lp[3];   // [0] force calls (wavefront per atom), [1] candidate-vector kernel of grade calls, [2] the fused kernel's
-             // grade instantiation (its image also holds the leaf moments' values)
+  LaunchPlan lp[3];   // [0] force calls, [1] candidate-vector kernel of grade calls, [2] the grade instantiation (mtp_plan.hpp)
   DevBuf<double> d_cvec, d_ainv_pad, d_ainv_tiled, d_dbasic;
   DevBuf<double> d_csum;   // mtp_batch_cfg_grades: [ncfg][cpad] candidate vectors summed per configuration
   DevBuf<int> d_ident;     // and the identity ilist its grade launch reads them by
@@ -145,389 +134,35 @@ struct mtp_context {
   MtpDevParams base{};
   const char *last_shape = "";   // name of the fixed-shape kernel the last force launch ran ("": a generic kernel)
 
-  void plan();
+  int plan();   // the plans of the installed list; MTP_ERR_LIMIT and last_error when it does not fit
 };
 
-namespace {
-
-// the four prefixes of the table blob a launch plan may copy into LDS (mtp_context: blob_bytes_*)
-struct BlobSizes {
-  int core = 0, tgt = 0, norows = 0, rows = 0;
-};
-
-}   // namespace
-
-// Choose the workgroup shape from the LDS budget (160 KiB / CU): every workgroup carries one copy
-// of the table blob plus one private region per wavefront.  Grade calls need extra table rows
-// (r^-nu, Q_ri) and scratch, so they get their own plan.
-//
-// Host only: the arithmetic needs the potential, the prefixes of its table blob, the CU count and the size of the list
-// (mtp_plan_fixed_fields asks it on machines without a device).
-static void plan_launch(const mtp_potential &p, const BlobSizes &bs, int num_cus, int inum, int max_numneigh, int variant,
-                        mtp_context::LaunchPlan (&lp)[3], MtpDevParams &base)
+int mtp_context::plan()
 {
-  using Layout = mtp_context::Layout;
-  using LaunchPlan = mtp_context::LaunchPlan;
-  const int blob_bytes_core = bs.core, blob_bytes_tgt = bs.tgt, blob_bytes_norows = bs.norows, blob_bytes_rows = bs.rows;
-  const int A = p.alpha_moment_count, P = p.max_alpha_index_basic;
-  int KL = 16, KB = 1;
-  (void) mtp_pick_shape(p.alpha_index_basic_count, &KL, &KB);
-  const int cap = std::max(64, (max_numneigh + 31) / 32 * 32);
-  const size_t LDS = 160 * 1024;
-  const int nt = 32;
-  // One plan for a given table-blob prefix; returns the wavefronts per CU it reaches (0: does not fit).
-  auto plan_one = [&](int which, size_t blob, LaunchPlan &L) -> int {
-    L.tab_rows = 2 * p.slot_count + 3 * P;
-    L.g_doubles = 0;
-    // leaf moments have no LDS slot in force calls; grade calls keep their values (candidate vector), not their adjoints
-    const int d_doubles = p.stored_moment_count, Am = which == 2 ? A : p.stored_moment_count;
-    const size_t ints = (size_t) 2 * nt + cap;
-    const int grows = p.slot_count * MTP_PITCH;   // g rows; the dg rows take as much again
-    const int trows = 2 * grows;
-    const size_t tail = 5 * (size_t) nt * 8 + ints * 4;   // neighbour arrays behind the tables
-    // Three layouts of the per-atom LDS image (mtp_kernels.hip, WaveLds), sizes in doubles:
-    //   keep     [g rows | dg rows | overlay]; coordinate-power rows and moments / adjoints share the overlay
-    //            (never live together); the derivative-polynomial coefficients later take the moments' place
-    const int m_keep = std::max(std::max(Am, p.coef_total), 16);
-    Layout keep;
-    keep.mode = 0;
-    keep.pow_row = 2 * p.slot_count;
-    keep.dg_off = grows;
-    keep.off_m = trows;
-    keep.off_d = trows + m_keep;
-    keep.off_coef = trows;
-    keep.m_doubles = m_keep;
-    keep.off_nb = trows + std::max(3 * P * MTP_PITCH, d_doubles + m_keep);
-    //   nodg     [g rows | overlay] (Mu <= 4): no dg rows; Mu rows f'_mu (written ahead of the force phase from radial
-    //            derivatives the tile build parked in registers) sit behind the coefficient blocks: 11.7 instead of
-    //            15.7 KB per atom at level 16, and neither the 16 dg rows nor a second evaluation of the radial functions
-    const int Mu_ = p.radial_func_count;
-    const bool nodg_ok = Mu_ <= 4;
-    Layout lean = keep;
-    lean.mode = 1;
-    lean.pow_row = p.slot_count;
-    lean.dg_off = 0;
-    lean.off_m = grows;
-    lean.off_d = grows + m_keep;
-    lean.off_coef = grows;
-    lean.fp_row = (grows + p.coef_total + MTP_PITCH - 1) / MTP_PITCH;
-    lean.off_nb = std::max(grows + std::max(3 * P * MTP_PITCH, d_doubles + m_keep), (lean.fp_row + Mu_) * MTP_PITCH);
-    //   rebuild  everything overlays everything (many moments): first table build = g rows and power rows only;
-    //            moments and adjoints then take the front of the region; ahead of the force phase the g and dg rows
-    //            are built again (coefficient blocks behind them, D[0, B) in front).  One more pass over the
-    //            neighbours' radial functions buys LDS: level 20 goes from 37 to 24 KB per atom.
-    const int m_reb = std::max(Am, 16);
-    Layout reb;
-    reb.mode = 2;
-    reb.pow_row = p.slot_count;
-    reb.dg_off = grows;
-    reb.off_d = 0;
-    reb.off_m = d_doubles;
-    reb.off_coef = trows;
-    reb.m_doubles = m_reb;
-    reb.off_nb = std::max(std::max(grows + 3 * P * MTP_PITCH, trows + p.coef_total), d_doubles + m_reb);
-    const bool reb_ok = trows >= p.alpha_index_basic_count;
-    //   rebuild without dg rows (Mu <= 4): the second build writes the g rows only, the f' rows follow the coefficients
-    Layout rebn = reb;
-    rebn.mode = 3;
-    rebn.dg_off = 0;
-    rebn.off_coef = grows;
-    rebn.fp_row = (grows + p.coef_total + MTP_PITCH - 1) / MTP_PITCH;
-    rebn.off_nb = std::max(std::max(grows + 3 * P * MTP_PITCH, (rebn.fp_row + Mu_) * MTP_PITCH), d_doubles + m_reb);
-    const bool rebn_ok = nodg_ok && grows >= p.alpha_index_basic_count;
-    // (the force phase reads its coefficient blocks 16 at a time, up to 15 doubles past the last block: every layout keeps
-    // off_coef + coef_total <= off_nb, and the neighbour arrays behind off_nb are longer than that, so those reads stay
-    // inside the wave's image without slack)
-    auto bytes_of = [&](const Layout &y) { return ((size_t) y.off_nb * 8 + tail + 15) / 16 * 16; };
-    // registers: 8 wavefronts per CU (2 per SIMD at <= 256 VGPRs) in workgroups of up to 8, or -- for the table
-    // shapes that have the 168-VGPR build -- 12 (3 per SIMD).  Measured on MI355X: a workgroup is only admitted when
-    // every SIMD it lands on has room, and workgroups of 5..7 wavefronts load the SIMDs unevenly (two 6-wavefront
-    // workgroups never shared a CU at 3 per SIMD); so the 3-per-SIMD plan uses one workgroup of 12 or three of 4.
-    int wave_cap = 32;
-    if (const char *e = std::getenv("MTP_MAX_WAVES")) wave_cap = std::max(1, std::min(16, std::atoi(e)));
-    auto waves2 = [&](int w, size_t wbytes) {   // 2-per-SIMD build, w wavefronts per workgroup
-      const size_t blk = blob + w * wbytes;
-      if (w > 8 || blk > LDS) return 0;
-      return std::min<int>(std::min(wave_cap, 8), (int) (LDS / blk) * w);
-    };
-    auto best2 = [&](size_t wbytes) {
-      int v = 0;
-      for (int w = 1; w <= 8; w++) v = std::max(v, waves2(w, wbytes));
-      return v;
-    };
-    auto shape3 = [&](size_t wbytes) {   // 3-per-SIMD build: wavefronts per workgroup that reach 12 per CU, or 0
-      if (wave_cap < 12) return 0;
-      if (blob + 12 * wbytes <= LDS) return 12;
-      if (3 * (blob + 4 * wbytes) <= LDS) return 4;
-      return 0;
-    };
-    const bool fine = variant == MTP_VARIANT_SMALL || (variant == MTP_VARIANT_AUTO && inum < num_cus * 16);
-    // candidates in order of preference at equal occupancy: nodg (least work), keep, then the rebuilding ones
-    std::vector<const Layout *> cands;
-    if (nodg_ok) cands.push_back(&lean);
-    cands.push_back(&keep);
-    if (rebn_ok) cands.push_back(&rebn);
-    if (reb_ok) cands.push_back(&reb);
-    if (const char *e = std::getenv("MTP_LAYOUT")) {   // tuning override (benchmarks, tests): keep | nodg | rebuild | rebuild-nodg
-      const std::string v(e);
-      if (v == "keep") cands = {&keep};
-      else if ((v == "nodg" || v == "lean") && nodg_ok) cands = {&lean};
-      else if (v == "rebuild" && reb_ok) cands = {&reb};
-      else if (v == "rebuild-nodg" && rebn_ok) cands = {&rebn};
-      else if (v == "rebuild" && rebn_ok) cands = {&rebn};
-    }
-    // the 3-per-SIMD build pays when there are atoms enough to fill twelve wavefronts per CU
-    // (slots: the 3-per-SIMD build keeps mu of every slot in one SGPR pair, two bits each; Mu <= 4 and ranks <= 6 give 28)
-    bool has3 = mtp_wave_kernel_has_wps3(p.fwd_block_count, P) && p.slot_count <= 32;
-    if (const char *e = std::getenv("MTP_WPS")) has3 = has3 && std::atoi(e) == 3;   // tuning override: 2 = never, 3 = whenever it fits
-    else has3 = has3 && !fine;
-    // (the grade instantiation spilled 52 dwords at 168 VGPRs and was 2.6 % slower there until the force totals were
-    // reduced per tile: 35 now, and 12 wavefronts per CU make the grade call 8 % faster; MTP_GRADE_WPS3=0 turns it off)
-    if (which == 2)
-      if (const char *e = std::getenv("MTP_GRADE_WPS3")) has3 = has3 && std::atoi(e) != 0;
-    const Layout *pick = nullptr;
-    int wps = 2, w3 = 0, pick_waves = 0;
-    for (const Layout *y : cands) {
-      int v = best2(bytes_of(*y)), vw3 = 0;
-      // (the 3-per-SIMD build carries the dg-free force phase only)
-      if (has3 && (y->mode & 1) && (vw3 = shape3(bytes_of(*y))) > 0) v = 12;
-      if (v > pick_waves) {
-        pick = y;
-        pick_waves = v;
-        wps = vw3 > 0 ? 3 : 2;
-        w3 = vw3;
-      }
-    }
-    if (!pick) return 0;
-    L.layout = *pick;
-    L.rebuild = (pick->mode & 2) != 0;
-    L.wps = wps;
-    L.m_doubles = pick->m_doubles;
-    L.ov_doubles = pick->off_nb;
-    const size_t wb = bytes_of(*pick);
-    int best_w = 0, best = 0;
-    if (wps == 3) {
-      best_w = w3;
-      best = 12;
-    } else {
-      // few atoms (or the "small" variant): the finest spread that still reaches the best occupancy;
-      // many atoms: as many wavefronts per workgroup as possible (fewer copies of the table blob)
-      for (int w = 1; w <= 8; w++) {
-        int v = waves2(w, wb);
-        if (v > best || (v == best && v > 0 && !fine)) {
-          best = v;
-          best_w = w;
-        }
-      }
-      if (best == 0) return 0;
-      if (fine) {
-        // ... every atom its own wavefront, in the WIDEST workgroups that still leave no CU without one (fewer copies of
-        // the table blob, fewer workgroups to dispatch: 2,048 atoms in 256 workgroups of 8 wavefronts run 3 % faster than
-        // in 1,024 of 2); narrower only when the atoms would not cover the CUs
-        int pick_w = 0;
-        for (int w = 1; w <= 8; w++)
-          if (waves2(w, wb) > 0 && (long long) num_cus * waves2(w, wb) >= inum && (inum + w - 1) / w >= num_cus) pick_w = w;
-        if (pick_w == 0)
-          for (int w = 1; w < best_w && pick_w == 0; w++)
-            if ((long long) num_cus * waves2(w, wb) >= inum) pick_w = w;
-        if (pick_w > 0) best_w = pick_w;
-      }
-      if (const char *e = std::getenv("MTP_WPB")) {   // tuning override (benchmarks only)
-        int v = std::atoi(e);
-        if (v >= 1 && v <= 8 && waves2(v, wb) > 0) best_w = v;
-      }
-      best = std::max(1, waves2(best_w, wb));
-    }
-    const int blocks_per_cu = std::max(1, best / best_w);
-    // packed times rows in LDS when the chosen shape still fits with them (or when they are tiny)
-    auto fits = [&](int bytes) { return (size_t) blocks_per_cu * ((size_t) bytes + best_w * wb) <= LDS; };
-    const bool forced = std::getenv("MTP_BLOB_PREFIX") != nullptr;   // (then exactly the planned prefix is copied)
-    L.rows_lds = forced ? (int) blob == blob_bytes_rows : fits(blob_bytes_rows);
-    if (const char *e = std::getenv("MTP_ROWS_LDS")) L.rows_lds = L.rows_lds && std::atoi(e) != 0;   // tuning override
-    L.tgt_lds = forced ? (int) blob >= blob_bytes_tgt : (L.rows_lds || fits(blob_bytes_tgt));
-    if (forced) L.blob_bytes = L.rows_lds ? blob_bytes_rows : std::min((int) blob, blob_bytes_norows);
-    else L.blob_bytes = L.rows_lds ? blob_bytes_rows : (fits(blob_bytes_norows) ? blob_bytes_norows : (L.tgt_lds ? blob_bytes_tgt : blob_bytes_core));
-    L.wpb = best_w;
-    L.wave_doubles = (int) (wb / 8);
-    L.lds_bytes = (size_t) L.blob_bytes + wb * best_w;
-    const int need = (inum + best_w - 1) / best_w;
-    L.grid = std::max(1, std::min(need, num_cus * blocks_per_cu));
-    return best;
-  };
-  // The shape is planned against each prefix of the table blob, longest first: a shorter prefix (tables read from
-  // HBM / L2 instead) is taken only when it buys wavefronts per CU (level 20: 8 instead of 7 with the core prefix).
-  for (int which : {0, 2}) {   // [0] fused force kernel, [2] its grade instantiation
-    int best_waves = 0;
-    std::vector<int> prefixes = {blob_bytes_rows, blob_bytes_norows, blob_bytes_tgt, blob_bytes_core};
-    if (const char *e = std::getenv("MTP_BLOB_PREFIX")) {   // tuning / test override: plan against one prefix only
-      const std::string v(e);
-      if (v == "core") prefixes = {blob_bytes_core};
-      else if (v == "tgt") prefixes = {blob_bytes_tgt};
-      else if (v == "norows") prefixes = {blob_bytes_norows};
-      else if (v == "rows") prefixes = {blob_bytes_rows};
-    }
-    for (int bytes : prefixes) {
-      LaunchPlan L;
-      const int v = plan_one(which, (size_t) bytes, L);
-      if (v > best_waves) {
-        best_waves = v;
-        lp[which] = L;
-      }
-    }
-    if (best_waves == 0) throw HipFail{hipErrorInvalidValue, "potential + neighbour list exceed one CU's LDS"};
-  }
-  {   // [1] candidate-vector kernel of grade calls: small table (r^-nu, Q_ri, powers), 8 wavefronts per workgroup
-    LaunchPlan &L = lp[1];
-    const int Mu = p.radial_func_count, R = p.radial_basis_size, Sp = p.species_count;
-    const size_t dbl = (size_t) KL * KB + (size_t) (4 * P + R) * (nt + 2) + 4 * (size_t) nt + (size_t) Mu * nt + (size_t) Sp * Mu * R;
-    const size_t ints = (size_t) nt + cap;
-    const size_t wb = (dbl * 8 + ints * 4 + 15) / 16 * 16;
-    const size_t blob1 = (size_t) blob_bytes_norows;   // (this kernel reads the basic descriptors)
-    int w = 8;
-    while (w > 1 && blob1 + w * wb > LDS) w--;
-    L.wpb = w;
-    L.wave_doubles = (int) (wb / 8);
-    L.lds_bytes = blob1 + wb * w;
-    const int blocks_per_cu = std::max<int>(1, std::min<int>(8 / w, (int) (LDS / L.lds_bytes)));
-    L.grid = std::max(1, std::min((inum + w - 1) / w, num_cus * blocks_per_cu));
-    L.tab_rows = 4 * P + R;
-    L.m_doubles = KL * KB;
-    L.g_doubles = 0;
-  }
-  base.NT = nt;
-  base.cj_cap = cap;
-  base.d_doubles = p.stored_moment_count;
-}
-
-void mtp_context::plan()
-{
-  BlobSizes bs;
-  bs.core = blob_bytes_core;
-  bs.tgt = blob_bytes_tgt;
-  bs.norows = blob_bytes_norows;
-  bs.rows = blob_bytes_rows;
-  plan_launch(*pot, bs, num_cus, inum, max_numneigh, variant, lp, base);
-}
-
-// the part of a launch's argument block that its plan decides
-static void apply_plan(MtpDevParams &p, const mtp_context::LaunchPlan &L, const mtp_potential &pot, bool grade)
-{
-  p.tab_rows = L.tab_rows;
-  p.m_doubles = L.m_doubles;
-  p.Am = grade ? pot.alpha_moment_count : pot.stored_moment_count;
-  p.ov_doubles = L.ov_doubles;
-  p.rebuild_tables = L.rebuild ? 1 : 0;
-  p.rows_in_lds = L.rows_lds ? 1 : 0;
-  p.blob_bytes = L.blob_bytes;
-  p.tgt_in_lds = L.tgt_lds ? 1 : 0;
-  p.dg_mode = L.layout.mode;
-  p.pow_row = L.layout.pow_row;
-  p.dg_off = L.layout.dg_off;
-  p.fp_row = L.layout.fp_row;
-  p.w_m = L.layout.off_m;
-  p.w_d = L.layout.off_d;
-  p.w_coef = L.layout.off_coef;
-  p.w_nb = L.layout.off_nb;
-  p.wps = L.wps;
-  p.wave_doubles = L.wave_doubles;
-  p.grade_flag = grade ? 1 : 0;
+  if (plan_launch(*pot, blob_sizes, num_cus, inum, max_numneigh, variant, lp, base)) return MTP_OK;
+  last_error = NO_FIT;
+  return MTP_ERR_LIMIT;
 }
 
 namespace {
 
-// The table blob every workgroup copies into LDS and its offsets in the argument block (host only; the pointers of the
-// HBM / L2 copies are the context's business).
-void build_blob(const mtp_potential &pot, const std::vector<MtpRow8> &rows8, MtpDevParams &bb, BlobSizes &bs,
-                std::vector<unsigned char> &blob)
+bool set_device(mtp_context *c)
 {
-  // The packed rows are the LAST piece of the blob: a launch plan copies them into LDS (blob_bytes_rows) or leaves
-  // them in HBM/L2 (blob_bytes_norows) -- measured at level 16: rows in LDS are 1.2 % faster when they fit beside
-  // the wavefronts' private regions anyway, and < 1 % slower otherwise (row reads do not depend on data).
-  auto put = [&](const void *src, size_t bytes) {
-    size_t off = (blob.size() + 15) / 16 * 16;
-    blob.resize(off + bytes, 0);
-    if (bytes) std::memcpy(blob.data() + off, src, bytes);
-    return (int) off;
-  };
-  bb.off_level = put(pot.level_offset.data(), pot.level_offset.size() * sizeof(int32_t));
-  bb.off_seg_fwd = put(pot.seg_fwd.data(), pot.seg_fwd.size() * sizeof(int32_t));
-  bb.off_seg_bwd = put(pot.seg_bwd.data(), pot.seg_bwd.size() * sizeof(int32_t));
-  std::vector<int32_t> slot_pad((size_t) pot.radial_func_count * MTP_PSTRIDE, -1);
-  for (int mu = 0; mu < pot.radial_func_count; mu++)
-    for (int nu = 0; nu < pot.max_alpha_index_basic; nu++)
-      slot_pad[(size_t) mu * MTP_PSTRIDE + nu] = pot.slot_of[(size_t) mu * pot.max_alpha_index_basic + nu];
-  bb.off_slot = put(slot_pad.data(), slot_pad.size() * sizeof(int32_t));
-  bb.off_radial = put(pot.radial_basis_coeffs.data(), pot.radial_basis_coeffs.size() * sizeof(double));
-  // scalar-side tables (24 B per basis function): LDS when they are small, HBM/L2 otherwise
-  bb.scalars_in_lds = (pot.e_map.size() + pot.seed_idx.size()) * 12 <= 4096;
-  if (const char *e = std::getenv("MTP_SCALARS_LDS")) bb.scalars_in_lds = std::atoi(e) != 0;   // tuning override
-  if (bb.scalars_in_lds) {
-    bb.off_seed_idx = put(pot.seed_idx.data(), pot.seed_idx.size() * sizeof(int32_t));
-    bb.off_seed_val = put(pot.seed_val.data(), pot.seed_val.size() * sizeof(double));
-    bb.off_map = put(pot.e_map.data(), pot.e_map.size() * sizeof(int32_t));
-    bb.off_lin = put(pot.e_lin.data(), pot.e_lin.size() * sizeof(double));
-  } else {
-    bb.off_seed_idx = bb.off_seed_val = bb.off_map = bb.off_lin = 0;
-  }
-  bb.off_smu = put(pot.slot_mu.data(), pot.slot_mu.size() * sizeof(int32_t));
-  bb.off_fwd = put(pot.fwd_blocks.data(), pot.fwd_blocks.size() * sizeof(int32_t));
-  bb.nfb = pot.fwd_block_count;
-  blob.resize((blob.size() + 15) / 16 * 16, 0);
-  bs.core = (int) blob.size();
-  bb.off_coef = put(pot.basic_tgt.data(), pot.basic_tgt.size() * sizeof(int32_t));
-  blob.resize((blob.size() + 15) / 16 * 16, 0);
-  bs.tgt = (int) blob.size();
-  bb.off_pack = put(pot.basic_pack_lds.data(), pot.basic_pack_lds.size() * sizeof(int32_t));
-  blob.resize((blob.size() + 15) / 16 * 16, 0);
-  bs.norows = (int) blob.size();
-  bb.off_rows = put(rows8.data(), rows8.size() * sizeof(MtpRow8));
-  bb.off_leaf_cf = put(pot.leaf_cf.data(), pot.leaf_cf.size() * sizeof(double));
-  bb.off_leaf_cb = pot.leaf_cb == pot.leaf_cf ? bb.off_leaf_cf : put(pot.leaf_cb.data(), pot.leaf_cb.size() * sizeof(double));
-  blob.resize((blob.size() + 15) / 16 * 16, 0);
-  bs.rows = (int) blob.size();
-  bb.blob_bytes = bs.norows;   // plan() decides per launch plan
-  bb.rows_in_lds = 0;
+  if (hipSetDevice(c->device) == hipSuccess) return true;
+  c->last_error = "hipSetDevice failed";
+  return false;
 }
 
-// the sizes and counts of the potential's tables in the argument block (host only)
-void fill_sizes(const mtp_potential &pot, MtpDevParams &b)
+int fail(mtp_context *c, int rc, const std::string &msg)   // a refusal: the code, and the message for mtp_last_error
 {
-  b.Sp = pot.species_count;
-  b.R = pot.radial_basis_size;
-  b.Mu = pot.radial_func_count;
-  b.P = pot.max_alpha_index_basic;
-  b.A = pot.alpha_moment_count;
-  b.B = pot.alpha_index_basic_count;
-  b.T = pot.alpha_index_times_count;
-  b.S = pot.alpha_scalar_count;
-  b.C = pot.coeff_count;
-  b.nslot = pot.slot_count;
-  b.coef_total = pot.coef_total;
-  b.coef_dense = pot.coef_dense;
-  for (int d = 0; d <= MTP_PSTRIDE; d++) {
-    b.deg_first[d] = pot.deg_first[d];
-    b.deg_coef[d] = pot.deg_coef[d];
-  }
-  b.nlevels = pot.normal_levels;   // (the level table has one more entry: the leaf rows)
-  // the same table in the argument block when it fits (mtp_device.hpp); all zero otherwise
-  const bool lv_fit = pot.level_offset.size() == (size_t) pot.normal_levels + 2 && pot.level_offset.size() <= MTP_SHAPE_ARR_LEN;
-  for (int k = 0; k < MTP_SHAPE_ARR_LEN; k++) b.level_rows[k] = lv_fit && k < (int) pot.level_offset.size() ? pot.level_offset[k] : 0;
-  // the slot tables likewise (mtp_device.hpp): table structure only, numbered by build_slots from the alpha tables
-  unsigned long long mu_bits = 0;
-  if (pot.radial_func_count <= 4 && pot.slot_count <= 32)
-    for (int s = 0; s < pot.slot_count; s++) mu_bits |= (unsigned long long) (pot.slot_mu[s] & 3) << (2 * s);
-  b.slot_mu_lo = (int) (unsigned) mu_bits;
-  b.slot_mu_hi = (int) (unsigned) (mu_bits >> 32);
-  const bool sr_fit = pot.radial_func_count <= MTP_SLOT_ROWS_MU && pot.slot_count <= 127 && pot.max_alpha_index_basic <= MTP_PSTRIDE;
-  for (int k = 0; k < MTP_SHAPE_TAB_LEN; k++) {
-    const int mu = k / MTP_PSTRIDE, nu = k % MTP_PSTRIDE;
-    const bool in = sr_fit && mu < pot.radial_func_count && nu < pot.max_alpha_index_basic;
-    b.slot_row[k] = (signed char) (in ? pot.slot_of[(size_t) mu * pot.max_alpha_index_basic + nu] : -1);
-  }
-  b.nseed = (int) pot.seed_idx.size();
-  b.Ad = pot.stored_moment_count;
-  b.Am = b.Ad;                      // per launch: the grade instantiation keeps the leaves' values too
-  b.Se = (int) pot.e_map.size();
+  c->last_error = msg;
+  return rc;
+}
+
+int device_fail(mtp_context *c, const HipFail &f)
+{
+  c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
+  return MTP_ERR_DEVICE;
 }
 
 // W [C][C] zero padded to [cpad][cpad] for the MFMA grade kernel, and the same matrix in MFMA operand order for the
@@ -757,38 +392,22 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
       delete c;
       return MTP_ERR_LIMIT;
     }
-    std::vector<MtpRow8> rows8(pot->rows_by_level.size());
-    for (size_t k = 0; k < rows8.size(); k++) {
-      const MtpRow &r = pot->rows_by_level[k];
-      if (r.mult > 32767 || r.mult < -32768) {
-        copy_err("alpha_index_times multiplicity outside 16 bits is not supported by this build", err, errlen);
-        delete c;
-        return MTP_ERR_LIMIT;
-      }
-      rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
-      rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
+    std::vector<MtpRow8> rows8, fwd8, bwd8;
+    const char *refusal = pack_rows(pot->rows_by_level, rows8);
+    if (!refusal) refusal = pack_rows(pot->prog_fwd, fwd8);
+    if (!refusal) refusal = pack_rows(pot->prog_bwd, bwd8);
+    if (refusal) {
+      copy_err(refusal, err, errlen);
+      delete c;
+      return MTP_ERR_LIMIT;
     }
-    c->d_rows.upload(rows8.data(), rows8.size(), st);
-    auto pack_prog = [&](const std::vector<MtpRow> &prog, DevBuf<MtpRow8> &buf) {
-      std::vector<MtpRow8> p8(prog.size());
-      for (size_t k = 0; k < prog.size(); k++) {
-        const MtpRow &r = prog[k];
-        p8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
-        p8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
-      }
-      buf.upload(p8.data(), p8.size(), st);
-    };
-    pack_prog(pot->prog_fwd, c->d_prog_fwd);
-    pack_prog(pot->prog_bwd, c->d_prog_bwd);
+    c->d_rows.upload(rows8, st);
+    c->d_prog_fwd.upload(fwd8, st);
+    c->d_prog_bwd.upload(bwd8, st);
     // table blob copied into LDS by every workgroup
     MtpDevParams &bb = c->base;
     std::vector<unsigned char> blob;
-    BlobSizes bs;
-    build_blob(*pot, rows8, bb, bs, blob);
-    c->blob_bytes_core = bs.core;
-    c->blob_bytes_tgt = bs.tgt;
-    c->blob_bytes_norows = bs.norows;
-    c->blob_bytes_rows = bs.rows;
+    build_blob(*pot, rows8, read_tuning(), bb, c->blob_sizes, blob);
     c->d_seed_idx.upload(pot->seed_idx, st);
     c->d_seed_val.upload(pot->seed_val, st);
     c->d_map.upload(pot->e_map, st);
@@ -881,14 +500,7 @@ int mtp_context_set_variant(mtp_context *c, int variant)
 {
   if (!c || variant < MTP_VARIANT_AUTO || variant > MTP_VARIANT_SMALL) return MTP_ERR_ARG;
   c->variant = variant;
-  if (c->have_list) {
-    try {
-      c->plan();
-    } catch (const HipFail &f) {
-      c->last_error = f.what;
-      return MTP_ERR_LIMIT;
-    }
-  }
+  if (c->have_list) return c->plan();
   return MTP_OK;
 }
 
@@ -899,8 +511,12 @@ static int finish_list(mtp_context *c, int inum, int nall, int max_numneigh)
   c->max_numneigh = max_numneigh;
   c->have_list = true;
   c->cvec_rows = 0;
+  const int rc = c->plan();
+  if (rc != MTP_OK) {
+    c->have_list = false;
+    return rc;
+  }
   try {
-    c->plan();
     if (c->pot->has_selection && inum > 0) {   // candidate vectors, zero padded rows of cpad doubles
       const size_t n = (size_t) inum * c->cpad;
       if (n > c->d_cvec.cap) {
@@ -915,7 +531,7 @@ static int finish_list(mtp_context *c, int inum, int nall, int max_numneigh)
   } catch (const HipFail &f) {
     c->last_error = f.what;
     c->have_list = false;
-    return f.e == hipErrorInvalidValue ? MTP_ERR_LIMIT : MTP_ERR_DEVICE;
+    return MTP_ERR_DEVICE;
   }
   return MTP_OK;
 }
@@ -940,8 +556,7 @@ int mtp_set_neighbors_csr(mtp_context *c, int inum, const int *ilist, const int 
     c->neigh = c->d_neigh.ptr;
     return finish_list(c, inum, nall, mx);
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
 }
 
@@ -952,10 +567,7 @@ int mtp_set_neighbors(mtp_context *c, int inum, const int *ilist, const int *num
   std::vector<int> first((size_t) inum + 1, 0);
   long long total = 0;
   for (int ii = 0; ii < inum; ii++) total += numneigh[ilist[ii]];
-  if (total > 2147483647LL) {
-    c->last_error = "neighbour list has more than 2^31-1 entries on this rank";
-    return MTP_ERR_LIMIT;
-  }
+  if (total > 2147483647LL) return fail(c, MTP_ERR_LIMIT, "neighbour list has more than 2^31-1 entries on this rank");
   for (int ii = 0; ii < inum; ii++) first[ii + 1] = first[ii] + numneigh[ilist[ii]];
   std::vector<int> neigh((size_t) first[inum]);
   for (int ii = 0; ii < inum; ii++) {
@@ -982,10 +594,7 @@ int mtp_build_neighbors_device(mtp_context *c, void *stream, const double *d_x, 
                                int *max_numneigh_out)
 {
   if (!c || inum < 0 || nall < inum || !lo || !hi || !(list_cutoff > 0.0) || (nall > 0 && !d_x)) return MTP_ERR_ARG;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   int n3[3];
   long long ncell = 1;
@@ -994,10 +603,8 @@ int mtp_build_neighbors_device(mtp_context *c, void *stream, const double *d_x, 
     n3[a] = std::max(1, (int) std::ceil((hi[a] - lo[a]) / list_cutoff));
     ncell *= n3[a];
   }
-  if (ncell > (1ll << 26)) {
-    c->last_error = "neighbour build: more than 2^26 cells (box much larger than the atoms it holds?)";
-    return MTP_ERR_LIMIT;
-  }
+  if (ncell > (1ll << 26))
+    return fail(c, MTP_ERR_LIMIT, "neighbour build: more than 2^26 cells (box much larger than the atoms it holds?)");
   try {
     const size_t scan_n = (size_t) std::max<long long>(ncell, inum) + 1;
     const size_t cub_bytes = mtp_neighbor_scan_bytes((int) scan_n, nall);
@@ -1013,10 +620,8 @@ int mtp_build_neighbors_device(mtp_context *c, void *stream, const double *d_x, 
     int info[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(info, c->d_nb_info.ptr, sizeof(info), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    if (info[0] < 0 || (long long) inum * info[1] > 0x7fffffffll) {
-      c->last_error = "neighbour list has more than 2^31-1 entries on this rank";
-      return MTP_ERR_LIMIT;
-    }
+    if (info[0] < 0 || (long long) inum * info[1] > 0x7fffffffll)
+      return fail(c, MTP_ERR_LIMIT, "neighbour list has more than 2^31-1 entries on this rank");
     c->d_neigh.reserve((size_t) std::max(info[0], 1));
     HIP_CHECK(mtp_launch_neighbor_build(d_x, inum, nall, list_cutoff, lo, n3, c->d_nb_scratch.ptr, c->d_nb_xs.ptr,
                                         c->d_nb_tmp.ptr, c->d_nb_tmp.cap, c->d_ilist.ptr, c->d_first.ptr, c->d_neigh.ptr,
@@ -1031,8 +636,7 @@ int mtp_build_neighbors_device(mtp_context *c, void *stream, const double *d_x, 
     if (max_numneigh_out) *max_numneigh_out = info[1];
     return finish_list(c, inum, nall, info[1]);
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
 }
 
@@ -1041,14 +645,9 @@ int mtp_set_neighbors_device_2d(mtp_context *c, void *stream, int inum, const in
 {
   if (!c || inum < 0 || nall < inum || max_neighs < 0 || (inum > 0 && (!d_ilist || !d_numneigh)) || stride_i < 0 || stride_jj < 0)
     return MTP_ERR_ARG;
-  if (inum > 0 && max_neighs > 0 && (!d_neighbors || (stride_i != 1 && stride_jj != 1))) {
-    c->last_error = "mtp_set_neighbors_device_2d: one of the two strides must be 1 (LayoutLeft or LayoutRight view)";
-    return MTP_ERR_ARG;
-  }
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (inum > 0 && max_neighs > 0 && (!d_neighbors || (stride_i != 1 && stride_jj != 1)))
+    return fail(c, MTP_ERR_ARG, "mtp_set_neighbors_device_2d: one of the two strides must be 1 (LayoutLeft or LayoutRight view)");
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
     const size_t cub_bytes = mtp_neighbor_scan_bytes(inum + 1, 1);
@@ -1062,14 +661,10 @@ int mtp_set_neighbors_device_2d(mtp_context *c, void *stream, int inum, const in
     int info[3] = {0, 0, 0};
     HIP_CHECK(hipMemcpyAsync(info, c->d_nb_info.ptr, sizeof(info), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));   // one read-back per re-neighbouring sizes the entry array and the LDS plan
-    if (info[2]) {
-      c->last_error = "mtp_set_neighbors_device_2d: a d_numneigh entry is negative or exceeds the view's second extent";
-      return MTP_ERR_ARG;
-    }
-    if (info[0] < 0) {
-      c->last_error = "neighbour list has more than 2^31-1 entries on this rank";
-      return MTP_ERR_LIMIT;
-    }
+    if (info[2])
+      return fail(c, MTP_ERR_ARG,
+                  "mtp_set_neighbors_device_2d: a d_numneigh entry is negative or exceeds the view's second extent");
+    if (info[0] < 0) return fail(c, MTP_ERR_LIMIT, "neighbour list has more than 2^31-1 entries on this rank");
     c->d_neigh.reserve((size_t) std::max(info[0], 1));
     HIP_CHECK(mtp_launch_list_from_2d(inum, d_ilist, d_numneigh, d_neighbors, stride_i, stride_jj, max_neighs,
                                       c->d_nb_scratch.ptr, c->d_nb_tmp.ptr, c->d_nb_tmp.cap, c->d_first.ptr, c->d_neigh.ptr,
@@ -1080,8 +675,7 @@ int mtp_set_neighbors_device_2d(mtp_context *c, void *stream, int inum, const in
     c->list_stream = st;
     return finish_list(c, inum, nall, info[1]);
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
 }
 
@@ -1090,14 +684,8 @@ int mtp_compute_resident(mtp_context *c, void *stream, const double *d_x, const 
                          int grade_flag)
 {
   if (!c || !d_x || !d_type || !d_f) return MTP_ERR_ARG;
-  if (!c->have_list) {
-    c->last_error = "mtp_compute before mtp_set_neighbors";
-    return MTP_ERR_STATE;
-  }
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!c->have_list) return fail(c, MTP_ERR_STATE, "mtp_compute before mtp_set_neighbors");
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   const size_t nall = (size_t) c->nall, C = (size_t) c->pot->coeff_count;
   const bool want_ea = (eflag & MTP_ENERGY_ATOM) != 0, want_va = (vflag & MTP_VIRIAL_ATOM) != 0;
@@ -1123,8 +711,7 @@ int mtp_compute_resident(mtp_context *c, void *stream, const double *d_x, const 
       }
     }
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
   double *tot = c->d_res_tot.ptr;
   const int rc = mtp_compute_device(c, reinterpret_cast<void *>(st), d_x, d_type, eflag, vflag, grade_flag, d_f,
@@ -1142,10 +729,7 @@ int mtp_compute_resident(mtp_context *c, void *stream, const double *d_x, const 
 int mtp_resident_totals(mtp_context *c, void *stream, double *ev7, double *max_grade, double *coeff_ders)
 {
   if (!c) return MTP_ERR_ARG;
-  if (!c->res_valid) {
-    c->last_error = "mtp_resident_totals before mtp_compute_resident";
-    return MTP_ERR_STATE;
-  }
+  if (!c->res_valid) return fail(c, MTP_ERR_STATE, "mtp_resident_totals before mtp_compute_resident");
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   const size_t C = (size_t) c->pot->coeff_count, n = 9 + (coeff_ders && c->res_grade ? C : 0);
   c->h_tmp.resize(std::max<size_t>(c->h_tmp.size(), 9 + C));
@@ -1166,10 +750,7 @@ int mtp_resident_totals(mtp_context *c, void *stream, double *ev7, double *max_g
 
 static int resident_array(mtp_context *c, int what, const double **ptr, int *ncol)
 {
-  if (!c->res_valid) {
-    c->last_error = "per-atom outputs asked for before mtp_compute_resident";
-    return MTP_ERR_STATE;
-  }
+  if (!c->res_valid) return fail(c, MTP_ERR_STATE, "per-atom outputs asked for before mtp_compute_resident");
   switch (what) {
     case MTP_PERATOM_EATOM:
       if (!(c->res_eflag & MTP_ENERGY_ATOM)) break;
@@ -1272,40 +853,22 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
                             double *d_coeff_ders)
 {
   if (!c) return MTP_ERR_ARG;
-  if (row_begin < 0 || row_count < 0 || (c->have_list && row_begin + row_count > c->inum)) {
-    c->last_error = "row range outside the neighbour list";
-    return MTP_ERR_ARG;
-  }
-  if (!c->have_list) {
-    c->last_error = "mtp_compute before mtp_set_neighbors";
-    return MTP_ERR_STATE;
-  }
+  if (row_begin < 0 || row_count < 0 || (c->have_list && row_begin + row_count > c->inum))
+    return fail(c, MTP_ERR_ARG, "row range outside the neighbour list");
+  if (!c->have_list) return fail(c, MTP_ERR_STATE, "mtp_compute before mtp_set_neighbors");
   if (!d_x || !d_type || !d_f) return MTP_ERR_ARG;
-  if (grade_flag && !c->pot->has_selection) {
-    c->last_error = "extrapolation grades requested but the potential has no #MVS_v1.1 selection state";
-    return MTP_ERR_STATE;
-  }
+  if (grade_flag && !c->pot->has_selection)
+    return fail(c, MTP_ERR_STATE, "extrapolation grades requested but the potential has no #MVS_v1.1 selection state");
   const bool cfg = c->pot->configuration_mode;
   if (grade_flag) {
-    if (!cfg && !d_grades) {
-      c->last_error = "neighbourhood-mode grades need a grades array";
-      return MTP_ERR_ARG;
-    }
-    if (cfg && !d_coeff_ders) {
-      c->last_error = "configuration-mode grades need a coeff_ders array";
-      return MTP_ERR_ARG;
-    }
-    if (c->pot->species_count * c->pot->radial_func_count * c->pot->radial_basis_size > 256) {
-      c->last_error = "Sp*Mu*R above 256 is not supported by the grade kernels of this build";
-      return MTP_ERR_LIMIT;
-    }
+    if (!cfg && !d_grades) return fail(c, MTP_ERR_ARG, "neighbourhood-mode grades need a grades array");
+    if (cfg && !d_coeff_ders) return fail(c, MTP_ERR_ARG, "configuration-mode grades need a coeff_ders array");
+    if (c->pot->species_count * c->pot->radial_func_count * c->pot->radial_basis_size > 256)
+      return fail(c, MTP_ERR_LIMIT, "Sp*Mu*R above 256 is not supported by the grade kernels of this build");
   }
   if (((eflag & MTP_ENERGY_GLOBAL) || vflag) && finish_tallies && !d_ev) return MTP_ERR_ARG;
   if (c->inum == 0) return MTP_OK;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   MtpDevParams p = c->base;
   p.inum = row_count;      // rows of THIS launch: [row0, row0 + inum) of the installed list
@@ -1324,25 +887,8 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
   p.vflag = vflag;
   p.grade_flag = grade_flag ? 1 : 0;
   p.xcd_map = c->xcd_map && row_count >= 8 * 64 ? 1 : 0;
-  const mtp_context::LaunchPlan &L = c->lp[grade_flag ? 2 : 0];
-  // The plan covers the whole list.  A row range too short to fill it (the interior / boundary pieces of a small
-  // domain, strong scaling) runs in smaller workgroups, so that its atoms spread over all CUs instead of filling a
-  // few of them: per-atom latency, not throughput, is what such a launch waits for.
-  int wpb_launch = L.wpb;
-  const int waves_per_cu = L.wpb * std::max(1, L.grid / std::max(1, c->num_cus));
-  if (row_count < c->num_cus * waves_per_cu && L.grid >= c->num_cus) {
-    const int small = L.wps == 3 ? 4 : 2;   // (multiples of 4 keep the SIMDs balanced at 3 per SIMD)
-    if (small < wpb_launch) wpb_launch = small;
-  }
-  const size_t blob_launch = (size_t) L.blob_bytes;
-  const size_t lds_launch = blob_launch + (size_t) wpb_launch * L.wave_doubles * 8;
-  auto grid_for = [&](const mtp_context::LaunchPlan &lp_, int wpb_) {
-    int g = (row_count + wpb_ - 1) / wpb_;
-    if (wpb_ == lp_.wpb) g = std::min(lp_.grid, g);
-    else g = std::min(g, c->num_cus * (int) std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds_launch, 1)));
-    if (g >= 8) g = (g + 7) / 8 * 8;   // whole rounds of the 8 XCDs for the XCD-aware atom map
-    return std::max(1, g);
-  };
+  const LaunchPlan &L = c->lp[grade_flag ? 2 : 0];
+  const RowRange rr = plan_row_range(L, c->num_cus, row_count);
   apply_plan(p, L, *c->pot, grade_flag != 0);
   p.cvec = grade_flag ? c->d_cvec.ptr : nullptr;
   p.cpad = c->cpad;
@@ -1371,7 +917,7 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
     }
     if (row_count > 0) {
       const char *used = nullptr;
-      HIP_CHECK(mtp_launch_wave_kernel(p, grid_for(L, wpb_launch), wpb_launch, lds_launch, st, &used));
+      HIP_CHECK(mtp_launch_wave_kernel(p, rr.grid, rr.wpb, rr.lds_bytes, st, &used));
       c->last_shape = used ? used : "";
     }
     if (p.fq) HIP_CHECK(mtp_launch_fixed_to_force(p.fq, d_f, c->nall, st));
@@ -1384,12 +930,12 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
     if (grade_flag && row_count > 0) {
       if (!fused) {
         MtpDevParams pc = p;   // radial block of the candidate vectors from the adjoints left in HBM
-        pc.blob_bytes = c->blob_bytes_norows;
+        pc.blob_bytes = c->blob_sizes.norows;
         pc.rows_in_lds = 0;
         pc.wave_doubles = c->lp[1].wave_doubles;
         pc.tab_rows = c->lp[1].tab_rows;
-        HIP_CHECK(mtp_launch_cvec_kernel(pc, std::max(1, std::min(c->lp[1].grid, (row_count + c->lp[1].wpb - 1) / c->lp[1].wpb)),
-                                         c->lp[1].wpb, c->lp[1].lds_bytes, st));
+        const RowRange rc1 = plan_cvec_range(c->lp[1], row_count);
+        HIP_CHECK(mtp_launch_cvec_kernel(pc, rc1.grid, rc1.wpb, rc1.lds_bytes, st));
       }
       const double *cv = c->d_cvec.ptr + (size_t) row_begin * c->cpad;
       if (row_begin <= c->cvec_rows) c->cvec_rows = std::max(c->cvec_rows, row_begin + row_count);   // (no gap below)
@@ -1400,8 +946,7 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
                                           c->ilist + row_begin, d_grades, d_max_grade, st));
     }
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
   return MTP_OK;
 }
@@ -1434,19 +979,13 @@ int mtp_batch_cfg_grades(mtp_context *c, void *stream, int ncfg, const int *d_cf
 {
   if (!c) return MTP_ERR_ARG;
   if (ncfg < 0 || nrows < 0 || (ncfg > 0 && (!d_cfg_first || !d_cfg_grade))) return MTP_ERR_ARG;
-  if (!c->pot->has_selection || !c->pot->configuration_mode) {
-    c->last_error = "mtp_batch_cfg_grades: the potential carries no configuration-mode selection state";
-    return MTP_ERR_STATE;
-  }
-  if (!c->have_list || nrows > c->inum || (size_t) nrows * c->cpad > c->d_cvec.cap) {
-    c->last_error = "mtp_batch_cfg_grades: no candidate vectors for these rows (call after a grade call on the installed list)";
-    return MTP_ERR_STATE;
-  }
+  if (!c->pot->has_selection || !c->pot->configuration_mode)
+    return fail(c, MTP_ERR_STATE, "mtp_batch_cfg_grades: the potential carries no configuration-mode selection state");
+  if (!c->have_list || nrows > c->inum || (size_t) nrows * c->cpad > c->d_cvec.cap)
+    return fail(c, MTP_ERR_STATE,
+                "mtp_batch_cfg_grades: no candidate vectors for these rows (call after a grade call on the installed list)");
   if (ncfg == 0) return MTP_OK;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
     c->d_csum.reserve((size_t) ncfg * c->cpad);
@@ -1456,8 +995,7 @@ int mtp_batch_cfg_grades(mtp_context *c, void *stream, int ncfg, const int *d_cf
                                       c->d_ident.ptr, d_cfg_grade, nullptr, st));
     HIP_CHECK(mtp_launch_batch_grade_scale(ncfg, d_cfg_first, d_cfg_grade, st));
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
   return MTP_OK;
 }
@@ -1479,10 +1017,8 @@ static int centre_prepare(mtp_context *c, hipStream_t st, bool train)
       c->last_error = tmsg;
       return trc;
     }
-    if (dt.A > 8191) {
-      c->last_error = who + ": alpha_moments_count above 8191 is not supported by the packed times rows";
-      return MTP_ERR_LIMIT;
-    }
+    if (dt.A > 8191)
+      return fail(c, MTP_ERR_LIMIT, who + ": alpha_moments_count above 8191 is not supported by the packed times rows");
     if (trc == MTP_OK && (pot.radial_func_count > 16 || pot.max_alpha_index_basic > 16)) {
       trc = MTP_ERR_LIMIT;
       tmsg = "training gradient: radial_funcs_count or a basic index above 16 does not fit the packed basics";
@@ -1491,16 +1027,9 @@ static int centre_prepare(mtp_context *c, hipStream_t st, bool train)
         return trc;
       }
     }
-    std::vector<MtpRow8> rows8(dt.rows.size());
-    for (size_t k = 0; k < rows8.size(); k++) {
-      const MtpRow &r = dt.rows[k];
-      if (r.mult > 32767 || r.mult < -32768) {
-        c->last_error = who + ": a multiplicity of alpha_index_times does not fit 16 bits";
-        return MTP_ERR_LIMIT;
-      }
-      rows8[k].lo = (uint32_t) (8 * r.a0) | ((uint32_t) (8 * r.a1) << 16);
-      rows8[k].hi = (uint32_t) (8 * r.a3) | (((uint32_t) r.mult & 0xffffu) << 16);
-    }
+    std::vector<MtpRow8> rows8;
+    if (pack_rows(dt.rows, rows8))
+      return fail(c, MTP_ERR_LIMIT, who + ": a multiplicity of alpha_index_times does not fit 16 bits");
     std::vector<int32_t> ints(dt.level_offset);
     for (const std::vector<int32_t> *v : {&dt.basic_pack, &dt.scalar_map, &dt.force_map, &t.bymu, &t.mufirst})
       ints.insert(ints.end(), v->begin(), v->end());
@@ -1563,14 +1092,14 @@ static void centre_bind(const mtp_context *c, MtpCentreParams &p, const double *
 static int centre_grid(mtp_context *c, const std::string &who, size_t lds, int cj_cap, int row_count, int *grid,
                        const std::function<std::string()> &fixed)
 {
-  if (lds > 160 * 1024) {
+  if (lds > CU_LDS_BYTES) {
     c->last_error = who + ": the workgroup's LDS image needs " + std::to_string(lds) + " of 163840 bytes: " +
-        (lds - (size_t) cj_cap * sizeof(int) > 160 * 1024
+        (lds - (size_t) cj_cap * sizeof(int) > CU_LDS_BYTES
              ? fixed()
              : "the list's longest row, max_numneigh = " + std::to_string(c->max_numneigh) + ", is too large");
     return MTP_ERR_LIMIT;
   }
-  const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds));
+  const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, CU_LDS_BYTES / lds));
   *grid = std::max(1, std::min(row_count, c->num_cus * per_cu));
   return MTP_OK;
 }
@@ -1579,28 +1108,17 @@ int mtp_design_rows_device(mtp_context *c, void *stream, const double *d_x, cons
                            const int *d_owner, int ld, double *d_basis, double *d_force, int nowned, double *d_virial_atom)
 {
   if (!c) return MTP_ERR_ARG;
-  if (!c->have_list) {
-    c->last_error = "mtp_design_rows_device before a neighbour list is installed";
-    return MTP_ERR_STATE;
-  }
+  if (!c->have_list) return fail(c, MTP_ERR_STATE, "mtp_design_rows_device before a neighbour list is installed");
   const int cols = c->pot->species_count + c->pot->alpha_scalar_count;
-  if (ld < cols || (ld & 1)) {
-    c->last_error = "mtp_design_rows_device: ld = " + std::to_string(ld) + " must be even and at least Sp + S = " + std::to_string(cols);
-    return MTP_ERR_ARG;
-  }
-  if (row_begin < 0 || row_count < 0 || row_begin + row_count > c->inum || nowned < 0) {
-    c->last_error = "mtp_design_rows_device: row range outside the neighbour list, or nowned < 0";
-    return MTP_ERR_ARG;
-  }
-  if (row_count > 0 && (!d_x || !d_type || !d_force)) {
-    c->last_error = "mtp_design_rows_device: positions, types and the force rows are required";
-    return MTP_ERR_ARG;
-  }
+  if (ld < cols || (ld & 1))
+    return fail(c, MTP_ERR_ARG,
+                "mtp_design_rows_device: ld = " + std::to_string(ld) + " must be even and at least Sp + S = " + std::to_string(cols));
+  if (row_begin < 0 || row_count < 0 || row_begin + row_count > c->inum || nowned < 0)
+    return fail(c, MTP_ERR_ARG, "mtp_design_rows_device: row range outside the neighbour list, or nowned < 0");
+  if (row_count > 0 && (!d_x || !d_type || !d_force))
+    return fail(c, MTP_ERR_ARG, "mtp_design_rows_device: positions, types and the force rows are required");
   if (row_count == 0) return MTP_OK;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
     int rc = centre_prepare(c, st, false), grid = 0;
@@ -1620,8 +1138,7 @@ int mtp_design_rows_device(mtp_context *c, void *stream, const double *d_x, cons
     if (rc != MTP_OK) return rc;
     HIP_CHECK(mtp_launch_design_kernel(p, grid, lds, st));
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
   return MTP_OK;
 }
@@ -1645,29 +1162,18 @@ static int train_launch(mtp_context *c, const char *who, bool vjp, void *stream,
 {
   if (!c) return MTP_ERR_ARG;
   const std::string w(who);
-  if (!c->have_list) {
-    c->last_error = w + " before a neighbour list is installed";
-    return MTP_ERR_STATE;
-  }
+  if (!c->have_list) return fail(c, MTP_ERR_STATE, w + " before a neighbour list is installed");
   const mtp_potential &pot = *c->pot;
   const int cols = pot.species_count * pot.species_count * pot.radial_func_count * pot.radial_basis_size + pot.species_count +
       pot.alpha_scalar_count;
-  if (vjp && (ld < cols || (ld & 1))) {
-    c->last_error = w + ": ld = " + std::to_string(ld) + " must be even and at least C = " + std::to_string(cols);
-    return MTP_ERR_ARG;
-  }
-  if (row_begin < 0 || row_count < 0 || row_begin + row_count > c->inum || nowned < 0) {
-    c->last_error = w + ": row range outside the neighbour list, or nowned < 0";
-    return MTP_ERR_ARG;
-  }
-  if (row_count > 0 && (!d_x || !d_type || !d_theta || (vjp ? !io.grad : !io.force))) {
-    c->last_error = w + ": positions, types, theta and " + (vjp ? "the gradient rows" : "the force array") + " are required";
-    return MTP_ERR_ARG;
-  }
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (vjp && (ld < cols || (ld & 1)))
+    return fail(c, MTP_ERR_ARG, w + ": ld = " + std::to_string(ld) + " must be even and at least C = " + std::to_string(cols));
+  if (row_begin < 0 || row_count < 0 || row_begin + row_count > c->inum || nowned < 0)
+    return fail(c, MTP_ERR_ARG, w + ": row range outside the neighbour list, or nowned < 0");
+  if (row_count > 0 && (!d_x || !d_type || !d_theta || (vjp ? !io.grad : !io.force)))
+    return fail(c, MTP_ERR_ARG,
+                w + ": positions, types, theta and " + (vjp ? "the gradient rows" : "the force array") + " are required");
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
     int rc = centre_prepare(c, st, true), grid = 0;   // (a refused table is reported even for an empty row range)
@@ -1686,8 +1192,7 @@ static int train_launch(mtp_context *c, const char *who, bool vjp, void *stream,
     if (rc != MTP_OK) return rc;
     HIP_CHECK(mtp_launch_train_kernel(p, vjp, grid, lds, st));
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
   return MTP_OK;
 }
@@ -1732,18 +1237,11 @@ int mtp_batch_cfg_candidates(mtp_context *c, void *stream, int ncfg, const int *
 {
   if (!c) return MTP_ERR_ARG;
   if (ncfg < 0 || nrows < 0 || !d_rows || !ld || (ncfg > 0 && !d_cfg_first)) return MTP_ERR_ARG;
-  if (!c->pot->has_selection) {
-    c->last_error = "mtp_batch_cfg_candidates: the potential carries no selection state";
-    return MTP_ERR_STATE;
-  }
-  if (!c->have_list || nrows > c->cvec_rows || (size_t) nrows * c->cpad > c->d_cvec.cap) {
-    c->last_error = "mtp_batch_cfg_candidates: no candidate vectors for these rows (call after a grade call on the installed list)";
-    return MTP_ERR_STATE;
-  }
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!c->pot->has_selection) return fail(c, MTP_ERR_STATE, "mtp_batch_cfg_candidates: the potential carries no selection state");
+  if (!c->have_list || nrows > c->cvec_rows || (size_t) nrows * c->cpad > c->d_cvec.cap)
+    return fail(c, MTP_ERR_STATE,
+                "mtp_batch_cfg_candidates: no candidate vectors for these rows (call after a grade call on the installed list)");
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
   try {
     c->d_csum.reserve((size_t) std::max(ncfg, 1) * c->cpad);
@@ -1753,8 +1251,7 @@ int mtp_batch_cfg_candidates(mtp_context *c, void *stream, int ncfg, const int *
       HIP_CHECK(mtp_launch_maxvol_scale_rows(c->d_csum.ptr, c->cpad, ncfg, d_cfg_first, st));
     }
   } catch (const HipFail &f) {
-    c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, f);
   }
   *d_rows = c->d_csum.ptr;
   *ld = c->cpad;
@@ -1768,10 +1265,7 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
 {
   if (!c) return MTP_ERR_ARG;
   const mtp_potential &p = *c->pot;
-  if (!p.has_selection) {
-    c->last_error = "mtp_maxvol_select: the potential carries no selection state";
-    return MTP_ERR_STATE;
-  }
+  if (!p.has_selection) return fail(c, MTP_ERR_STATE, "mtp_maxvol_select: the potential carries no selection state");
   const int C = p.coeff_count;
   if (!(threshold >= 1.0) || !std::isfinite(threshold) || nrows < 0 || ld < C || max_swaps < 0 || refresh < 1 ||
       (nrows > 0 && !d_rows) || !active_set || !inverse_active_set || !slot_source || !nswaps || !converged ||
@@ -1779,10 +1273,7 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
     c->last_error = "mtp_maxvol_select: needs threshold >= 1, ld >= coeff_count, max_swaps >= 0, refresh >= 1 and its outputs";
     return MTP_ERR_ARG;
   }
-  if (nrows * (long long) C > (1ll << 62) / C) {
-    c->last_error = "mtp_maxvol_select: too many rows";
-    return MTP_ERR_LIMIT;
-  }
+  if (nrows * (long long) C > (1ll << 62) / C) return fail(c, MTP_ERR_LIMIT, "mtp_maxvol_select: too many rows");
   double mg = 0.0;
   int bad = 0;
   *nswaps = 0;
@@ -1792,10 +1283,7 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
     std::memcpy(inverse_active_set, c->h_inverse.data(), c->h_inverse.size() * sizeof(double));
     for (int j = 0; j < C; j++) slot_source[j] = -1;
   } else {
-    if (hipSetDevice(c->device) != hipSuccess) {
-      c->last_error = "hipSetDevice failed";
-      return MTP_ERR_DEVICE;
-    }
+    if (!set_device(c)) return MTP_ERR_DEVICE;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
     hipError_t e = hipSuccess;
     try {   // the arena is the context's and is kept: a selection loop allocates once
@@ -1818,10 +1306,7 @@ int mtp_maxvol_select(mtp_context *c, void *stream, const double *d_rows, long l
   for (int k = 0; k < *nswaps; k++) gain += std::log(std::fabs(swap_pivots[k]));
   if (log_volume_gain) *log_volume_gain = gain;
   if (max_grade_after) *max_grade_after = mg;
-  if (bad) {
-    c->last_error = "mtp_maxvol_select: a candidate vector (or a grade computed from it) is not finite";
-    return MTP_ERR_ARG;
-  }
+  if (bad) return fail(c, MTP_ERR_ARG, "mtp_maxvol_select: a candidate vector (or a grade computed from it) is not finite");
   return MTP_OK;
 }
 
@@ -1852,19 +1337,13 @@ int check_coeffs(mtp_context *c, const char *who, const double *radial, const do
 int check_selection(mtp_context *c, const char *who, const double *active_set, const double *inverse_active_set, int coeff_count)
 {
   const mtp_potential &p = *c->pot;
-  if (!p.has_selection) {
-    c->last_error = std::string(who) + ": the context's potential was loaded without its selection state";
-    return MTP_ERR_STATE;
-  }
-  if (!active_set || !inverse_active_set || coeff_count != p.coeff_count) {
-    c->last_error = std::string(who) + ": needs both blocks, and coeff_count = " + std::to_string(p.coeff_count);
-    return MTP_ERR_ARG;
-  }
+  if (!p.has_selection)
+    return fail(c, MTP_ERR_STATE, std::string(who) + ": the context's potential was loaded without its selection state");
+  if (!active_set || !inverse_active_set || coeff_count != p.coeff_count)
+    return fail(c, MTP_ERR_ARG, std::string(who) + ": needs both blocks, and coeff_count = " + std::to_string(p.coeff_count));
   const size_t n = (size_t) p.coeff_count * p.coeff_count;
-  if (!all_finite(active_set, n) || !all_finite(inverse_active_set, n)) {
-    c->last_error = std::string(who) + ": an entry of the active set or of its inverse is not finite";
-    return MTP_ERR_ARG;
-  }
+  if (!all_finite(active_set, n) || !all_finite(inverse_active_set, n))
+    return fail(c, MTP_ERR_ARG, std::string(who) + ": an entry of the active set or of its inverse is not finite");
   return MTP_OK;
 }
 
@@ -1918,12 +1397,6 @@ void commit_selection(mtp_context *c, const double *active_set, const double *in
   c->h_inverse.assign(inverse_active_set, inverse_active_set + n);
 }
 
-int device_fail(mtp_context *c, const HipFail &f)
-{
-  c->last_error = std::string(f.what) + ": " + hipGetErrorString(f.e);
-  return MTP_ERR_DEVICE;
-}
-
 }   // namespace
 
 int mtp_context_install_coeffs(mtp_context *c, void *stream, const double *radial_coeffs, const double *species_coeffs,
@@ -1933,10 +1406,7 @@ int mtp_context_install_coeffs(mtp_context *c, void *stream, const double *radia
   mtp_coeff_tables t;
   const int rc = check_coeffs(c, "mtp_context_install_coeffs", radial_coeffs, species_coeffs, moment_coeffs, t);
   if (rc != MTP_OK) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   try {
     hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
     queue_coeffs(c, st, t);
@@ -1954,10 +1424,7 @@ int mtp_context_install_selection(mtp_context *c, void *stream, const double *ac
   if (!c) return MTP_ERR_ARG;
   const int rc = check_selection(c, "mtp_context_install_selection", active_set, inverse_active_set, coeff_count);
   if (rc != MTP_OK) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   try {
     hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
     StagedSelection stage;
@@ -1998,10 +1465,7 @@ int mtp_context_install_file(mtp_context *c, void *stream, const char *path)
   if (rc == MTP_OK && with_selection)
     rc = check_selection(c, "mtp_context_install_file", file.active_set.data(), file.inverse_active_set.data(), file.coeff_count);
   if (rc != MTP_OK) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   try {
     hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
     StagedSelection stage;
@@ -2060,10 +1524,7 @@ int mtp_context_coeff_tables_device(mtp_context *c, void *stream, int32_t *count
                           (size_t) (b.scalars_in_lds ? 1 : 0)};
     for (int k = 0; k < 10; k++) counts[k] = (int32_t) v[k];
   }
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->last_error = "hipSetDevice failed";
-    return MTP_ERR_DEVICE;
-  }
+  if (!set_device(c)) return MTP_ERR_DEVICE;
   hipStream_t st = reinterpret_cast<hipStream_t>(mtp_internal_resolve_stream(c, stream));
   try {
     auto get = [&](double *dst, const void *src, size_t n) {
@@ -2099,21 +1560,14 @@ int mtp_synchronize(mtp_context *c, void *stream)
   int flag = 0;
   hipError_t e = hipMemcpyAsync(&flag, c->d_err.ptr, sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    c->last_error = std::string("synchronize: ") + hipGetErrorString(e);
-    return MTP_ERR_DEVICE;
-  }
+  if (e != hipSuccess) return fail(c, MTP_ERR_DEVICE, std::string("synchronize: ") + hipGetErrorString(e));
   if (flag) {
     (void) hipMemsetAsync(c->d_err.ptr, 0, sizeof(int), st);
     (void) hipStreamSynchronize(st);
-    if (flag == 2) {
-      c->last_error = "a neighbour list row holds more in-cutoff neighbours than the declared max_numneigh";
-      return MTP_ERR_LIMIT;
-    }
-    if (flag == 3) {
-      c->last_error = "design rows: a centre or an owner outside [0, nowned), or a list entry outside [0, nall)";
-      return MTP_ERR_ARG;
-    }
+    if (flag == 2)
+      return fail(c, MTP_ERR_LIMIT, "a neighbour list row holds more in-cutoff neighbours than the declared max_numneigh");
+    if (flag == 3)
+      return fail(c, MTP_ERR_ARG, "design rows: a centre or an owner outside [0, nowned), or a list entry outside [0, nall)");
     c->last_error = "Too few species count in the MTP potential!";   // pair_mtp.cpp:92-93
     return MTP_ERR_SPECIES;
   }
@@ -2125,10 +1579,7 @@ int mtp_compute(mtp_context *c, const double *x, const int *type, int eflag, int
                 double *max_grade, double *coeff_ders)
 {
   if (!c || !x || !type || !f) return MTP_ERR_ARG;
-  if (!c->have_list) {
-    c->last_error = "mtp_compute before mtp_set_neighbors";
-    return MTP_ERR_STATE;
-  }
+  if (!c->have_list) return fail(c, MTP_ERR_STATE, "mtp_compute before mtp_set_neighbors");
   const size_t nall = (size_t) c->nall;
   try {
     HIP_CHECK(hipSetDevice(c->device));
@@ -2180,8 +1631,7 @@ int mtp_compute(mtp_context *c, const double *x, const int *type, int eflag, int
                             hipMemcpyDeviceToHost));
     }
   } catch (const HipFail &fl) {
-    c->last_error = std::string(fl.what) + ": " + hipGetErrorString(fl.e);
-    return MTP_ERR_DEVICE;
+    return device_fail(c, fl);
   }
   return MTP_OK;
 }
@@ -2190,7 +1640,7 @@ int mtp_context_launch_info(const mtp_context *c, int32_t *lds_bytes_per_wave, i
                             int32_t *grid_blocks, int32_t *neighbor_tile)
 {
   if (!c || !c->have_list) return MTP_ERR_STATE;
-  const mtp_context::LaunchPlan &L = c->lp[0];
+  const LaunchPlan &L = c->lp[0];
   if (lds_bytes_per_wave) *lds_bytes_per_wave = L.wave_doubles * 8;   // per atom image
   if (waves_per_block) *waves_per_block = L.wpb;
   if (grid_blocks) *grid_blocks = L.grid;
@@ -2224,73 +1674,8 @@ int mtp_debug_read_stamps(mtp_context *c, unsigned long long *out16)
 
 }   // extern "C"
 
-// ---- the plan without a device -------------------------------------------------------------------------------------
-// the argument block of a force (or grade) launch as far as the potential and the plan decide it; pointers stay null
-static int plan_params(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade, MtpDevParams &p)
-{
-  if (!pot || num_cus < 1 || inum < 0 || max_numneigh < 0 || variant < MTP_VARIANT_AUTO || variant > MTP_VARIANT_SMALL)
-    return MTP_ERR_ARG;
-  p = MtpDevParams{};
-  const std::vector<MtpRow8> rows8(pot->rows_by_level.size());   // (only their size matters here)
-  BlobSizes bs;
-  std::vector<unsigned char> blob;
-  build_blob(*pot, rows8, p, bs, blob);
-  fill_sizes(*pot, p);
-  int kl_ = 0, kb_ = 0;
-  if (mtp_pick_fwd_shape(pot->fwd_block_count, &kl_, &kb_) != 0) return MTP_ERR_LIMIT;
-  mtp_context::LaunchPlan lp[3];
-  try {
-    plan_launch(*pot, bs, num_cus, inum, max_numneigh, variant, lp, p);
-  } catch (const HipFail &) {
-    return MTP_ERR_LIMIT;
-  }
-  apply_plan(p, lp[grade ? 2 : 0], *pot, grade != 0);
-  return MTP_OK;
-}
-
+// ---- the plan without a device (mtp_plan.cpp; the name of a fixed-shape kernel belongs to the kernel unit) --------------
 extern "C" {
-
-int mtp_plan_fixed_fields(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade,
-                          char *buf, int buflen)
-{
-  MtpDevParams p;
-  int rc = plan_params(pot, num_cus, inum, max_numneigh, variant, grade, p);
-  if (rc != MTP_OK) return rc;
-  if (!buf || buflen <= 0) return MTP_ERR_ARG;
-  int KL = 0, NB = 0;
-  (void) mtp_pick_fwd_shape(p.nfb, &KL, &NB);
-  const int dlow = mtp_wave_kernel_deg(KL, p.P) == mtp_wave_kernel_dlow(KL);
-  std::string s;
-  auto put = [&](const char *k, int v) { s += std::string(k) + "=" + std::to_string(v) + "\n"; };
-  put("KL", KL);
-  put("NB", NB);
-  put("PITCH", MTP_PITCH);
-  put("GRADE", grade ? 1 : 0);
-  put("DEG", mtp_wave_kernel_deg(KL, p.P));
-  put("WPS", dlow && p.wps == 3 ? 3 : 2);
-#define MTP_X(f) put(#f, p.f);
-  MTP_SHAPE_INT_FIELDS(MTP_X)
-#undef MTP_X
-#define MTP_X(f)                                                                          \
-  {                                                                                       \
-    s += #f "=";                                                                          \
-    for (int k = 0; k < MTP_SHAPE_ARR_LEN; k++) s += (k ? "," : "") + std::to_string(p.f[k]); \
-    s += "\n";                                                                            \
-  }
-  MTP_SHAPE_ARR_FIELDS(MTP_X)
-#undef MTP_X
-#define MTP_X(f)                                                                               \
-  {                                                                                            \
-    s += #f "=";                                                                               \
-    for (int k = 0; k < MTP_SHAPE_TAB_LEN; k++) s += (k ? "," : "") + std::to_string((int) p.f[k]); \
-    s += "\n";                                                                                 \
-  }
-  MTP_SHAPE_TAB_FIELDS(MTP_X)
-#undef MTP_X
-  if ((int) s.size() + 1 > buflen) return MTP_ERR_LIMIT;
-  std::memcpy(buf, s.c_str(), s.size() + 1);
-  return MTP_OK;
-}
 
 int mtp_plan_fixed_shape(const mtp_potential *pot, int num_cus, int inum, int max_numneigh, int variant, int grade,
                          char *name, int namelen)
@@ -2360,10 +1745,7 @@ int mtp_context_last_kernel_ms(mtp_context *c, float *ms)
   if (!c->timed) return MTP_ERR_STATE;
   hipError_t e = hipEventSynchronize(c->ev1);
   if (e == hipSuccess) e = hipEventElapsedTime(ms, c->ev0, c->ev1);
-  if (e != hipSuccess) {
-    c->last_error = std::string("event timing: ") + hipGetErrorString(e);
-    return MTP_ERR_DEVICE;
-  }
+  if (e != hipSuccess) return fail(c, MTP_ERR_DEVICE, std::string("event timing: ") + hipGetErrorString(e));
   return MTP_OK;
 }
 

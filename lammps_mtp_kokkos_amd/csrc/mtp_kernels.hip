@@ -555,52 +555,6 @@ template <int KL, int NB> hipError_t launch_pitch(const MtpDevParams &p, int gri
 
 }   // namespace
 
-// Lane grids of the candidate-vector kernel (KL k-lanes x KB basics per lane); also sizes dbasic rows.
-int mtp_pick_shape(int B, int *KL, int *KB)
-{
-  static const int kb16[] = {2, 3, 5, 7, 9, 10}, kbw[] = {6, 7, 8, 10};
-  for (int v : kb16)
-    if (B <= 16 * v) {
-      *KL = 16;
-      *KB = v;
-      return 0;
-    }
-  for (int kl : {32, 64})
-    for (int v : kbw)
-      if (B <= kl * v) {
-        *KL = kl;
-        *KB = v;
-        return 0;
-      }
-  return -1;
-}
-
-// Lane grids of the force kernel's basic-moment pass: KL block lanes x NB 3x3 blocks per lane (KL * NB >= blocks);
-// mtp_pick_fwd_shape() is the single source of truth for the host.
-int mtp_pick_fwd_shape(int nblk, int *KL, int *NB)
-{
-  for (int kl : {16, 32, 64})
-    if (nblk <= kl) {
-      *KL = kl;
-      *NB = 1;
-      return 0;
-    }
-  for (int nb : {2, 3, 4})
-    if (nblk <= 64 * nb) {
-      *KL = 64;
-      *NB = nb;
-      return 0;
-    }
-  return -1;
-}
-
-// whether the three-wavefronts-per-SIMD build exists for this table shape (see launch_pitch)
-bool mtp_wave_kernel_has_wps3(int nfb, int P)
-{
-  int KL = 0, NB = 0;
-  return mtp_pick_fwd_shape(nfb, &KL, &NB) == 0 && KL <= 32 && NB == 1 && mtp_wave_kernel_deg(KL, P) == mtp_wave_kernel_dlow(KL);
-}
-
 hipError_t mtp_launch_wave_kernel(const MtpDevParams &p, int grid, int wpb, size_t lds, hipStream_t st, const char **used)
 {
   int KL = 0, NB = 0;

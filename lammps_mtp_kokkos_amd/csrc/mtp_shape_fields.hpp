@@ -2,7 +2,7 @@
 // constants of a fixed-shape instantiation of the kernel (mtp_kernels_fixed.hip).
 //
 // A candidate field is decided by the potential's table structure (the alpha_* tables, the species count, R) and by
-// the LDS plan (mtp_plan_launch), never by the fit, the system or the call.  A shape is a struct with one static
+// the LDS plan (mtp_plan.hpp, plan_launch), never by the fit, the system or the call.  A shape is a struct with one static
 // constexpr member per field it fixes (and a name and the kernel's template arguments); a field it does not list stays a
 // read of the argument block.  The three lists below are the only enumeration of the candidates: the kernel's accessor
 // (SHF / SHA / SHT, mtp_wave_body.hpp), the launcher's field-by-field match (mtp_shape_matches) and the generator of

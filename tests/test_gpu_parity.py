@@ -111,7 +111,7 @@ def test_schedule_corner_cases_late_writer_and_shared_scalar(tmp_path, monkeypat
 @pytest.mark.parametrize("prefix", ["core", "tgt", "norows", "rows"])
 def test_every_table_blob_prefix(monkeypatch, prefix):
     """The workgroup-shared tables are copied into LDS as one of four prefixes [core | scatter targets | basic
-    descriptors | rows + leaf constants]; what is left out is read from HBM / L2 (csrc/mtp_context.hip, plan()).  Each
+    descriptors | rows + leaf constants]; what is left out is read from HBM / L2 (csrc/mtp_plan.cpp, choose_prefix).  Each
     prefix, forced, against the oracle -- levels 16 (row-per-lane passes) and 20 (gather passes)."""
     monkeypatch.setenv("MTP_BLOB_PREFIX", prefix)
     _compare(os.path.join(POT, "W_L16.mtp"), _system((3, 3, 3)))

@@ -186,3 +186,35 @@ def test_many_species(tmp_path, species):
     path = str(tmp_path / "p.mtp")
     mtpgen.write_mtp(mtpgen.random_potential(mtpgen.build_table(10), species, 4242), path)
     _check(path, _system((3, 3, 3), species=species))
+
+
+# ---- the context's plan is the host-only planner's (csrc/mtp_plan.hpp, tests/plan_dump.cpp) ------------------------------
+
+
+@pytest.mark.parametrize("name", ["W_L8", "W_L16"])
+@pytest.mark.parametrize("layout", [None, "rebuild"])
+def test_context_plan_is_what_plan_dump_prints(tmp_path, monkeypatch, name, layout):
+    """a context on the 54-atom cell of the golden fixtures reports the plan that the planner, built without the HIP
+    runtime, prints for the same potential, CU count, list size, longest row and environment"""
+    import torch
+    from test_plan_cpu import dump
+
+    g = np.load(os.path.join(ROOT, "tests", "golden", name + "_54.npz"))
+    if layout:
+        monkeypatch.setenv("MTP_LAYOUT", layout)
+    ctx = capi.Context(capi.Potential(os.path.join(POT, name + ".mtp")), 0)
+    ctx.set_neighbors(g["ilist"], g["first"], g["neigh"], len(g["x"]))
+    got = ctx.compute(g["x"], g["types"])
+    _close(got["f"], g["f"], "forces")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    inum, longest = len(g["ilist"]), int(np.diff(g["first"]).max())
+    listf = tmp_path / "one.txt"
+    listf.write_text("%s.mtp %d %d %d 0 %d%s\n" % (name, cus, inum, longest, inum, " MTP_LAYOUT=" + layout if layout else ""))
+    header, line = dump(str(listf), tmp_path)
+    rc, lp0, _, _, force = [part.split() for part in line.split(" | ")[:5]]
+    assert rc == ["0", "0"]
+    mode, wpb, grid, wave_doubles, rebuild, wps = (int(lp0[k]) for k in (0, 9, 10, 11, 16, 17))
+    assert ctx.launch_info() == dict(lds_bytes_per_wave=8 * wave_doubles, waves_per_block=wpb, grid_blocks=grid,
+                                     neighbor_tile=int(force[-3]))
+    assert ctx.plan_info() == dict(waves_per_simd=wps, rebuild_tables=rebuild)
+    assert ctx.layout_mode() == mode
