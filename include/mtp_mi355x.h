@@ -16,7 +16,8 @@
  *     mtp_context_coeff_tables_device): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
- *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls): NULL is
+ *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls, mtp_normal_clear,
+ *     mtp_normal_accumulate, mtp_normal_get, mtp_normal_set): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
  * whose other GPU work runs on the default stream (PyTorch's default) must pass a real stream handle that its own
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 9
+#define MTP_MI355X_ABI_VERSION 10
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -640,6 +641,67 @@ int mtp_potential_design_table(const mtp_potential *pot, int32_t *counts, int32_
 int mtp_potential_write_coeffs(const char *src_path, const char *dst_path, const double *species_coeffs /*[Sp] or NULL*/,
                                const double *moment_coeffs /*[S]*/, int species_count, int scalar_count, char *err,
                                int errlen);
+
+/* ---- linear refit without the design matrix: double-double normal equations ----------------------------------------
+ *
+ * The state (opaque handle mtp_normal) holds, per kind of row (0 energy, 1 force, 2 virial), the augmented Gram matrix
+ * G = B^T B of n = ncols + 1 columns as two [n][n] fp64 planes hi and lo -- the entry is the unevaluated sum hi + lo, about
+ * 106 bits (csrc/mtp_dd.hpp) -- and the number of rows that entered.  Column ncols of B is the target.  For a call with
+ * rows [nrows][ld], scale [nrows] and target [nrows]
+ *     b[i][c] = fl(scale[i] * rows[i][c]) for c < ncols,   b[i][ncols] = fl(scale[i] * target[i])
+ * (ONE fp64 multiply), and sum_i b[i][j] b[i][k] is added to entry (j, k).  A row with scale[i] == 0 is skipped by a test
+ * on scale (it may hold NaN) and is not counted; columns [ncols, ld) of rows are never read.  Neither the weights of a fit
+ * nor its starting coefficients enter a state, so it can be kept between rounds and extended by new rows only.
+ *
+ * Sum order: rows are taken in slices of a compile-time length (mtp_normal_sizes), every slice is summed in row order in
+ * registers and the slices are added to the state in slice order.  Both triangles are written from one value, so entry
+ * (j, k) equals entry (k, j) bit for bit, and the result is the same on any device, for any workspace size and however a
+ * row range is split into calls at multiples of the slice length.  No atomics; fp64 VALU arithmetic only. */
+typedef struct mtp_normal mtp_normal;
+/* tile edge of the kernel, rows of an LDS panel, rows of a slice and the fixed cap of a state's workspace in bytes (any
+ * pointer may be NULL); host only */
+int mtp_normal_sizes(int *tile, int *panel, int *slice, long long *workspace_cap_bytes);
+/* A zeroed state for ncols columns on a device, with its workspace of partial tiles: workspace_bytes (0: the cap) is
+ * rounded down to whole rounds of slices -- at least one slice, at most the cap and 256 slices.  A call with more slices
+ * than the workspace holds runs several rounds; the result does not depend on that.  Nothing is allocated after this. */
+int mtp_normal_create(int device, int ncols, long long workspace_bytes, mtp_normal **out);
+void mtp_normal_destroy(mtp_normal *h);
+const char *mtp_normal_last_error(const mtp_normal *h);
+/* ncols, the slices one round holds, the workspace's and the state's device bytes (any pointer may be NULL) */
+int mtp_normal_info(const mtp_normal *h, int *ncols, int *round_slices, long long *workspace_bytes, long long *state_bytes);
+/* fewer slices a round than the workspace holds (a diagnostic: the result must not change); MTP_ERR_ARG for more */
+int mtp_normal_set_round_slices(mtp_normal *h, int slices);
+/* zeroes the three matrices and the row counts, one launch */
+int mtp_normal_clear(mtp_normal *h, void *stream);
+/* Adds the rows of one kind.  Device arrays of the caller; nothing waits on the host.  MTP_ERR_ARG (the state is left as
+ * it was) for a NULL stream, ld < ncols, a kind outside 0..2, nrows < 0 or a NULL array with nrows > 0; nrows == 0
+ * launches nothing. */
+int mtp_normal_accumulate(mtp_normal *h, void *stream, int kind, long long nrows, int ld, const double *d_rows,
+                          const double *d_scale, const double *d_target);
+/* Host copies: hi and lo are [3][n][n] (kind, row, column), counts [3].  Both synchronise on `stream`; get: any pointer may
+ * be NULL. */
+int mtp_normal_get(mtp_normal *h, void *stream, double *hi, double *lo, long long counts[3]);
+int mtp_normal_set(mtp_normal *h, void *stream, const double *hi, const double *lo, const long long counts[3]);
+/* The solve's first half (HOST ONLY, no device): G = sum_k weights[k] G_k in double-double (hi[k] / lo[k] [n][n]; a kind
+ * with weight 0 or hi[k] == NULL is left out), then a Cholesky factorisation with diagonal pivoting over the first
+ * ncols = n - 1 columns, the target column riding along.  The pivot of a step is the remaining column with the largest
+ * (remaining diagonal) / (original diagonal); the factorisation stops when that ratio is <= drop, and a column with a zero
+ * diagonal is dropped at once.  Outputs, rounded to fp64 at the end:
+ *   R [ncols][ncols]     rows [0, *rank): the factor in the ORIGINAL column order, zero where a column was eliminated
+ *                        by an earlier row (R^T R = G on the kept part; R has the singular values of the weighted matrix)
+ *   q [ncols]            entries [0, *rank): Q^T y - R theta0, formed in double-double
+ *   pivot_order [ncols]  entries [0, *rank): the column each row eliminated
+ *   dropped [ncols]      entries [0, *ndropped): the columns left out, *rank + *ndropped = ncols
+ *   pivot_ratios [ncols] the ratio of every kept pivot, then that of every dropped column in the order of `dropped`
+ * (pivot_order, dropped, ndropped and pivot_ratios may be NULL).  lstsq(R, q) is the change of the coefficients that
+ * lstsq(A_w, y_w - A_w theta0) gives.  MTP_ERR_ARG for non-finite input, a negative weight, no kind with a positive
+ * weight or a diagonal entry below zero; MTP_ERR_LIMIT when the host is out of memory. */
+int mtp_normal_factor(int n, const double *const hi[3], const double *const lo[3], const double weights[3], const double *theta0,
+                      double drop, double *R, double *q, int *rank, int *pivot_order, int *dropped, int *ndropped,
+                      double *pivot_ratios);
+/* y^T y - 2 theta^T g + theta^T G theta of ONE kind, evaluated in double-double and clamped at 0: the sum of squared
+ * (scaled) residuals at theta (host only).  MTP_ERR_ARG for non-finite input. */
+int mtp_normal_quadratic(int n, const double *hi, const double *lo, const double *theta, double *out);
 
 /* ---- training gradient: loss derivatives for ALL coefficients -------------------------------------------------------
  *

@@ -47,6 +47,9 @@ EXPORTS = [
     "mtp_context_cfg_grade",
     "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
     "mtp_sample_to_cell",
+    "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
+    "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
+    "mtp_normal_factor", "mtp_normal_quadratic",
 ]
 WROTE_WITHOUT_SELECTION = 1   # mtp_potential_write_coeffs: the source's #MVS tail was left out
 # mtp_batch_reduce: segments of up to BATCH_WAVE_ROWS rows are reduced by one wavefront (64 lanes), longer ones by a
@@ -92,6 +95,8 @@ def lib():
         L.mtp_build_flags.restype = C.c_char_p
         L.mtp_halo_last_error.restype = C.c_char_p
         L.mtp_ghosts_last_error.restype = C.c_char_p
+        L.mtp_normal_last_error.restype = C.c_char_p
+        L.mtp_normal_destroy.restype = None
         L.mtp_ghosts_destroy.restype = None
         L.mtp_potential_free.restype = None
         L.mtp_context_destroy.restype = None
@@ -1086,3 +1091,112 @@ def sample_to_cell(nrows, row_cfg_t, origins_t, x_t, stream=None):
     rc = lib().mtp_sample_to_cell(_st(stream), int(nrows), _ptr(row_cfg_t), _ptr(origins_t), _ptr(x_t))
     if rc:
         raise MtpError(rc, "mtp_sample_to_cell")
+
+
+# ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------
+NORMAL_KINDS = ("energy", "force", "virial")
+
+
+def normal_sizes():
+    """dict(tile, panel, slice, workspace_cap) of the loaded build's accumulate kernel: the tile edge, the rows of an LDS
+    panel, the rows of a slice (the unit of the sum order) and the fixed cap of a state's workspace in bytes"""
+    t, p, s, w = C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+    lib().mtp_normal_sizes(C.byref(t), C.byref(p), C.byref(s), C.byref(w))
+    return dict(tile=t.value, panel=p.value, slice=s.value, workspace_cap=w.value)
+
+
+class Normal:
+    """The device-side state of the normal equations (mtp_normal_*): per kind of row (0 energy, 1 force, 2 virial) the
+    augmented Gram matrix of ncols + 1 columns in double-double and the number of rows that entered."""
+
+    def __init__(self, ncols, device=0, workspace_bytes=0):
+        self.h = C.c_void_p()
+        rc = lib().mtp_normal_create(int(device), int(ncols), C.c_longlong(int(workspace_bytes)), C.byref(self.h))
+        if rc:
+            raise MtpError(rc, "mtp_normal_create(ncols = %d)" % ncols)
+        self.ncols, self.n, self.device = int(ncols), int(ncols) + 1, int(device)
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.mtp_normal_destroy(self.h)
+            self.h = None
+
+    def _check(self, rc):
+        if rc:
+            raise MtpError(rc, lib().mtp_normal_last_error(self.h).decode())
+
+    def info(self):
+        """dict(ncols, round_slices, workspace_bytes, state_bytes)"""
+        a, b, c, d = C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+        self._check(lib().mtp_normal_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(ncols=a.value, round_slices=b.value, workspace_bytes=c.value, state_bytes=d.value)
+
+    def set_round_slices(self, slices):
+        """fewer slices a round than the workspace holds: several rounds of accumulate + fold, the same bits"""
+        rc = lib().mtp_normal_set_round_slices(self.h, int(slices))
+        if rc:
+            raise MtpError(rc, "mtp_normal_set_round_slices: between 1 and what the workspace holds")
+
+    def clear(self, stream=None):
+        self._check(lib().mtp_normal_clear(self.h, _st(stream)))
+
+    def accumulate(self, kind, nrows, ld, rows_t, scale_t, target_t, stream=None):
+        """adds sum_i b[i][j] b[i][k], b = scale[:, None] * [rows[:, :ncols] | target], of nrows rows of leading dimension
+        ld to the matrix of `kind` (device tensors; rows of scale 0 are skipped and not counted)"""
+        self._check(lib().mtp_normal_accumulate(self.h, _st(stream), int(kind), C.c_longlong(int(nrows)), int(ld), _ptr(rows_t),
+                                                _ptr(scale_t), _ptr(target_t)))
+
+    def get(self, stream=None):
+        """host copies (hi [3, n, n], lo [3, n, n], counts [3]); synchronises on `stream`"""
+        hi, lo = np.zeros((3, self.n, self.n)), np.zeros((3, self.n, self.n))
+        cnt = (C.c_longlong * 3)()
+        self._check(lib().mtp_normal_get(self.h, _st(stream), _np(hi, C.c_double), _np(lo, C.c_double), cnt))
+        return hi, lo, np.array(cnt[:], dtype=np.int64)
+
+    def set(self, hi, lo, counts, stream=None):
+        hi, lo = (np.ascontiguousarray(a, dtype=np.float64) for a in (hi, lo))
+        if hi.shape != (3, self.n, self.n) or lo.shape != hi.shape or len(counts) != 3:
+            raise MtpError(-20, "Normal.set: hi and lo must be [3, %d, %d], counts [3]" % (self.n, self.n))
+        cnt = (C.c_longlong * 3)(*[int(c) for c in counts])
+        self._check(lib().mtp_normal_set(self.h, _st(stream), _np(hi, C.c_double), _np(lo, C.c_double), cnt))
+
+
+def normal_factor(hi, lo, weights, theta0, drop=2.0 ** -80):
+    """mtp_normal_factor (host only): hi, lo [3, n, n].  Returns dict(R [rank, ncols], q [rank], rank, pivot_order [rank],
+    dropped_columns, pivot_ratios [ncols]: the kept pivots' ratios, then those of the dropped columns)."""
+    hi, lo = (np.ascontiguousarray(a, dtype=np.float64) for a in (hi, lo))
+    n = int(hi.shape[-1])
+    if hi.shape != (3, n, n) or lo.shape != hi.shape:
+        raise MtpError(-20, "normal_factor: hi and lo must be [3, n, n]")
+    ncols = n - 1
+    theta0 = np.ascontiguousarray(theta0, dtype=np.float64).reshape(-1)
+    if len(theta0) != ncols:
+        raise MtpError(-20, "normal_factor: theta0 must have %d entries" % ncols)
+    P = C.POINTER(C.c_double)
+    hp = (P * 3)(*[hi[k].ctypes.data_as(P) for k in range(3)])
+    lp = (P * 3)(*[lo[k].ctypes.data_as(P) for k in range(3)])
+    w = (C.c_double * 3)(*[float(x) for x in weights])
+    R, q, ratios = np.zeros((ncols, ncols)), np.zeros(ncols), np.zeros(ncols)
+    order, dropped = np.zeros(ncols, np.int32), np.zeros(ncols, np.int32)
+    rank, nd = C.c_int(0), C.c_int(0)
+    rc = lib().mtp_normal_factor(n, hp, lp, w, _np(theta0, C.c_double), C.c_double(drop), _np(R, C.c_double), _np(q, C.c_double),
+                                 C.byref(rank), _np(order, C.c_int), _np(dropped, C.c_int), C.byref(nd), _np(ratios, C.c_double))
+    if rc:
+        raise MtpError(rc, "mtp_normal_factor: needs finite input, weights >= 0 (one of them positive) and no negative diagonal")
+    r = rank.value
+    return dict(R=R[:r].copy(), q=q[:r].copy(), rank=r, pivot_order=order[:r].copy(), dropped_columns=dropped[:nd.value].copy(),
+                pivot_ratios=ratios)
+
+
+def normal_quadratic(hi, lo, theta):
+    """mtp_normal_quadratic (host only): the sum of squared scaled residuals of ONE kind (hi, lo [n, n]) at theta"""
+    hi, lo = (np.ascontiguousarray(a, dtype=np.float64) for a in (hi, lo))
+    theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+    n = int(hi.shape[-1])
+    if hi.shape != (n, n) or lo.shape != hi.shape or len(theta) != n - 1:
+        raise MtpError(-20, "normal_quadratic: hi and lo must be [n, n], theta [n - 1]")
+    out = C.c_double(0.0)
+    rc = lib().mtp_normal_quadratic(n, _np(hi, C.c_double), _np(lo, C.c_double), _np(theta, C.c_double), C.byref(out))
+    if rc:
+        raise MtpError(rc, "mtp_normal_quadratic: non-finite input")
+    return out.value

@@ -823,6 +823,7 @@ const char *mtp_build_flags(void)
 #endif
     f += mtp_kernel_build_flags();
     f += mtp_maxvol_build_flags();
+    f += mtp_normal_build_flags();
     if (!f.empty() && f.back() == ' ') f.pop_back();
     return f;
   }();

@@ -179,6 +179,7 @@ hipError_t mtp_launch_batch_grade_scale(int ncfg, const int *cfg_first, double *
 // mtp_maxvol_arena_doubles(...) doubles, the caller's ((C + N) x cpad of them hold the stacked matrix).  Waits on `st`
 // once per 16 swaps; may throw std::bad_alloc (host staging of the two blocks).
 const char *mtp_maxvol_build_flags();   // "" for the shipped defaults (mtp_build_flags)
+const char *mtp_normal_build_flags();   // the same of mtp_normal.hip
 size_t mtp_maxvol_arena_doubles(int num_cus, int C, long long N, int max_swaps);
 hipError_t mtp_maxvol_run(hipStream_t st, int num_cus, double *arena, int C, const double *S, const double *W,
                           const double *d_rows, long long N, int ld, double threshold, int max_swaps, int refresh, double *S_out,

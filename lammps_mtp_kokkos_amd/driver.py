@@ -427,3 +427,52 @@ def train_twin(tables, system, theta=None, ebar=None, fbar=None, vbar=None):
                 for tj in range(Sp):
                     rows[ii, ((it * Sp + tj) * Mu + m) * R:((it * Sp + tj) * Mu + m + 1) * R] += blk[:, jt == tj].sum(1)
     return dict(eatom=eatom, force=force, vatom=vatom, rows=rows)
+
+
+# ---- numpy twin of the normal-equation kernels (csrc/mtp_normal.hip, csrc/mtp_dd.hpp) ---------------------------------------
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _two_prod(a, b):
+    """p + e = a b exactly without an fma (Dekker / Veltkamp splitting): the same e an fma returns, barring overflow"""
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _dd_add(ahi, alo, bhi, blo):
+    s, e = _two_sum(ahi, bhi)
+    t, f = _two_sum(alo, blo)
+    s, e = _two_sum(s, e + t)
+    return _two_sum(s, e + f)
+
+
+def normal_twin(rows, scale, target, ncols, state=None, slice_rows=256):
+    """numpy twin of mtp_normal_accumulate, operation for operation: b = fl(scale * [rows[:, :ncols] | target]), rows of
+    scale 0 skipped (they may hold NaN) and not counted, columns [ncols, ld) never read; slices of `slice_rows` rows summed
+    in row order with dd_mac (hi by TwoSum, lo by plain additions), normalised, and added in slice order to the state with
+    dd_add.  `state` = (hi [n, n], lo [n, n], count) or None for zeros; returns the new (hi, lo, count)."""
+    n = ncols + 1
+    rows = np.asarray(rows, dtype=np.float64)
+    rows = rows.reshape(len(scale), rows.size // max(len(scale), 1))
+    scale, target = np.asarray(scale, dtype=np.float64), np.asarray(target, dtype=np.float64)
+    hi, lo, count = (np.zeros((n, n)), np.zeros((n, n)), 0) if state is None else (state[0].copy(), state[1].copy(), int(state[2]))
+    with np.errstate(invalid="ignore"):
+        for s0 in range(0, len(scale), slice_rows):
+            ahi, alo = np.zeros((n, n)), np.zeros((n, n))
+            for i in range(s0, min(s0 + slice_rows, len(scale))):
+                if scale[i] == 0.0:
+                    continue
+                count += 1
+                b = np.concatenate([scale[i] * rows[i, :ncols], [scale[i] * target[i]]])
+                p, e = _two_prod(b[:, None], b[None, :])
+                ahi, t = _two_sum(ahi, p)
+                alo = alo + (t + e)
+            ahi, alo = _two_sum(ahi, alo)
+            hi, lo = _dd_add(hi, lo, ahi, alo)
+    return hi, lo, count

@@ -474,19 +474,15 @@ def select_cells(ctx, configs, threshold=1.1, out_path=None, list_cutoff=7.0, ma
                 inverse_active_set=sel["inverse_active_set"], slot_source=source, swaps=sel["swaps"])
 
 
-def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None):
-    """The design matrix of the linear refit over a batch of configurations (include/mtp_mi355x.h, "linear refit"): the
-    passes of evaluate_cells -- ghost build, list build -- with the design call (Context.design_rows, the ghost owner
-    map folding every neighbour's term onto its owned row) in place of the force call, then the per-configuration sums
-    (capi.batch_design_reduce).  Columns are [species (Sp) | moments (S)]; with theta = the context's species_coeffs and
-    moment_coeffs (Context.coeffs), energy @ theta, force @ theta and virial @ theta are what evaluate_cells returns.
-
-    Returns dict(energy [ncfg, Sp + S], force [3 sum n, Sp + S] (row 3 (cfg_first[k] + a) + c: atom a of configuration k,
-    component c, atoms in the order of `pos`), virial [ncfg, 6, Sp + S] (None with virial=False), cfg_first [ncfg + 1],
-    columns = Sp + S) as DEVICE tensors (views of allocations whose rows are `ld` = columns rounded up to even apart),
-    plus natoms.  ValueError when these three matrices together with the per-atom basis and virial rows of the largest
-    pass (7 n ld doubles for a pass of n atoms; `max_atoms_per_pass` bounds them) would exceed `max_design_bytes`: the caller
-    shards the training set.  An atom type outside the potential is reported at the synchronise of its pass; the message names it."""
+def _design_passes(ctx, configs, list_cutoff, virial, max_atoms_per_pass, device, begin):
+    """The passes design_cells and normal_cells share: ghost build, list build, the design call with the ghost owner map,
+    the per-configuration sums (capi.batch_design_reduce) and the synchronise that reports an atom type outside the
+    potential.  `begin(plan)` is called once, after the planning and before anything is allocated, with plan = dict(dev,
+    stream, cols, ld, natoms, first, passes, pass_atoms, pass_cfgs: the atoms and configurations of the largest pass); it
+    raises where the caller's byte bound is exceeded and returns (rows_of, on_pass).  rows_of(k0, k1) gives the ZEROED
+    destination (force [3 n, ld], energy [k1 - k0, ld], virial [k1 - k0, 6, ld] or None) of a pass;
+    on_pass(k0, k1, force, energy, virial, stream) (or None) runs after the sums are queued, before the synchronise.
+    Returns the plan."""
     import torch
     dev = device or torch.device("cuda:0")
     if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
@@ -497,20 +493,12 @@ def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 
     cols = int(info.species_count + info.alpha_scalar_count)
     ld = cols + (cols & 1)
     items, all_cells, natoms = _batch_items(configs)
-    ncfg_all = len(items)
     first = np.concatenate([[0], np.cumsum(natoms)]).astype(np.int64)
-    ntot = int(first[-1])
     passes, _, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
-    # the three matrices and, beside them, the per-atom basis and virial rows of the largest pass
-    pass_atoms = max([int(first[k1] - first[k0]) for k0, k1, _ in passes], default=0)
-    need = 8 * ld * (ncfg_all + 3 * ntot + (6 * ncfg_all if virial else 0) + (7 if virial else 1) * pass_atoms)
-    if need > max_design_bytes:
-        raise ValueError("design_cells: the design matrix of %d configurations with %d atoms (and the per-atom rows of its "
-                         "largest pass, %d atoms) needs %d bytes, max_design_bytes is %d; shard the training set, or lower "
-                         "max_atoms_per_pass" % (ncfg_all, ntot, pass_atoms, need, max_design_bytes))
-    energy = torch.zeros((ncfg_all, ld), dtype=torch.float64, device=dev)
-    force = torch.zeros((3 * ntot, ld), dtype=torch.float64, device=dev)
-    vir = torch.zeros((ncfg_all, 6, ld), dtype=torch.float64, device=dev) if virial else None
+    plan = dict(dev=dev, stream=st, cols=cols, ld=ld, natoms=natoms, first=first, passes=passes,
+                pass_atoms=max([int(first[k1] - first[k0]) for k0, k1, _ in passes], default=0),
+                pass_cfgs=max([k1 - k0 for k0, k1, _ in passes], default=0))
+    rows_of, on_pass = begin(plan)
     ghosts = capi.Ghosts(dev.index or 0)
     buf = _BatchBuffers(torch, dev)
     npass = 0
@@ -528,21 +516,60 @@ def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 
         vatom = buf.work[n * ld: 7 * n * ld].view(n, 6, ld) if virial else None
         owner, nown = ghosts.owner(stream=st)
         assert nown == nall
-        ctx.design_rows(0, n, buf.xall, buf.tall, force[3 * int(first[k0]): 3 * int(first[k1])], n, ld, basis_t=basis, virial_t=vatom,
-                        owner=owner, stream=st)
-        capi.batch_design_reduce(cf_t, ld, basis_t=basis, virial_atom_t=vatom, energy_t=energy[k0:k1],
-                                 virial_t=vir[k0:k1] if virial else None, stream=st)
+        force, energy, vir = rows_of(k0, k1)
+        ctx.design_rows(0, n, buf.xall, buf.tall, force, n, ld, basis_t=basis, virial_t=vatom, owner=owner, stream=st)
+        capi.batch_design_reduce(cf_t, ld, basis_t=basis, virial_atom_t=vatom, energy_t=energy,
+                                 virial_t=vir if virial else None, stream=st)
+        if on_pass is not None:
+            on_pass(k0, k1, force, energy, vir, st)
         try:
             ctx.synchronize(stream=st)                        # an atom type outside the potential is reported here
         except capi.MtpError as e:
             raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
     torch.cuda.current_stream(dev).synchronize()
-    return dict(energy=energy[:, :cols], force=force[:, :cols], virial=vir[:, :, :cols] if virial else None,
-                cfg_first=torch.from_numpy(first.astype(np.int32)).to(dev), columns=cols, natoms=natoms)
+    return plan
+
+
+def design_cells(ctx, configs, list_cutoff=7.0, virial=True, max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None):
+    """The design matrix of the linear refit over a batch of configurations (include/mtp_mi355x.h, "linear refit"): the
+    passes of evaluate_cells -- ghost build, list build -- with the design call (Context.design_rows, the ghost owner
+    map folding every neighbour's term onto its owned row) in place of the force call, then the per-configuration sums
+    (capi.batch_design_reduce).  Columns are [species (Sp) | moments (S)]; with theta = the context's species_coeffs and
+    moment_coeffs (Context.coeffs), energy @ theta, force @ theta and virial @ theta are what evaluate_cells returns.
+
+    Returns dict(energy [ncfg, Sp + S], force [3 sum n, Sp + S] (row 3 (cfg_first[k] + a) + c: atom a of configuration k,
+    component c, atoms in the order of `pos`), virial [ncfg, 6, Sp + S] (None with virial=False), cfg_first [ncfg + 1],
+    columns = Sp + S) as DEVICE tensors (views of allocations whose rows are `ld` = columns rounded up to even apart),
+    plus natoms.  ValueError when these three matrices together with the per-atom basis and virial rows of the largest
+    pass (7 n ld doubles for a pass of n atoms; `max_atoms_per_pass` bounds them) would exceed `max_design_bytes`: the caller
+    shards the training set, or fits through normal_cells, which keeps no matrix.  An atom type outside the potential is
+    reported at the synchronise of its pass; the message names it."""
+    import torch
+    out = {}
+
+    def begin(plan):
+        dev, ld, first = plan["dev"], plan["ld"], plan["first"]
+        ncfg_all, ntot, pass_atoms = len(plan["natoms"]), int(first[-1]), plan["pass_atoms"]
+        # the three matrices and, beside them, the per-atom basis and virial rows of the largest pass
+        need = 8 * ld * (ncfg_all + 3 * ntot + (6 * ncfg_all if virial else 0) + (7 if virial else 1) * pass_atoms)
+        if need > max_design_bytes:
+            raise ValueError("design_cells: the design matrix of %d configurations with %d atoms (and the per-atom rows of its "
+                             "largest pass, %d atoms) needs %d bytes, max_design_bytes is %d; shard the training set, or lower "
+                             "max_atoms_per_pass" % (ncfg_all, ntot, pass_atoms, need, max_design_bytes))
+        energy = torch.zeros((ncfg_all, ld), dtype=torch.float64, device=dev)
+        force = torch.zeros((3 * ntot, ld), dtype=torch.float64, device=dev)
+        vir = torch.zeros((ncfg_all, 6, ld), dtype=torch.float64, device=dev) if virial else None
+        out.update(energy=energy, force=force, vir=vir)
+        return (lambda k0, k1: (force[3 * int(first[k0]): 3 * int(first[k1])], energy[k0:k1], vir[k0:k1] if virial else None)), None
+
+    plan = _design_passes(ctx, configs, list_cutoff, virial, max_atoms_per_pass, device, begin)
+    cols = plan["cols"]
+    return dict(energy=out["energy"][:, :cols], force=out["force"][:, :cols], virial=out["vir"][:, :, :cols] if virial else None,
+                cfg_first=torch.from_numpy(plan["first"].astype(np.int32)).to(plan["dev"]), columns=cols, natoms=plan["natoms"])
 
 
 def fit_linear(ctx, configs, labels, weights=(1.0, 0.01, 0.001), rcond=1e-12, out_path=None, list_cutoff=7.0,
-               max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None, install=False):
+               max_design_bytes=2 ** 31, max_atoms_per_pass=None, device=None, install=False, method="svd", state=None):
     """The linear refit: species_coeffs and moment_coeffs fitted to reference energies, forces and virials with the radial
     coefficients fixed.  labels[k] = dict(energy=float or None, f=[n, 3] or None, virial=[6] or None) for configs[k]
     (virial in the sign and order evaluate_cells returns).  With N_k atoms in configuration k the rows of design_cells
@@ -552,6 +579,13 @@ def fit_linear(ctx, configs, labels, weights=(1.0, 0.01, 0.001), rcond=1e-12, ou
     theta_0 the context's current coefficients (Context.coeffs: the file's until an install), so that directions the data do not determine (the complete tables are
     rank deficient by construction) keep their values.  The weighted matrix is copied to the host and solved with
     numpy.linalg.lstsq (SVD); it is bounded by max_design_bytes and the fit runs once per round.
+
+    method="normal" keeps no design matrix: normal_cells adds every pass's rows to the double-double normal equations on
+    the device (max_design_bytes is its max_bytes and bounds one pass, the state and its workspace), and solve_normal
+    factors them on the host and hands the triangular factor to the same SVD solve -- the same coefficients from cols^2
+    numbers instead of rows x cols.  `state` (a NormalState of an earlier call, method="normal" only) is extended by these
+    configurations, so that a round costs its new configurations only; the state is returned under "state", with
+    "dropped_columns" and "pivot_ratios" beside the keys below.
 
     Returns dict(species_coeffs, moment_coeffs, rank, singular_values, rmse_before, rmse_after: dicts energy (per atom),
     force, virial (per atom) over the labelled rows, None for a kind without labels) and, with out_path, writes the
@@ -564,12 +598,21 @@ def fit_linear(ctx, configs, labels, weights=(1.0, 0.01, 0.001), rcond=1e-12, ou
     set is the caller's select_cells call, not something an install does."""
     if len(labels) != len(configs):
         raise ValueError("fit_linear: %d labels for %d configurations" % (len(labels), len(configs)))
+    if method not in ("svd", "normal") or (state is not None and method != "normal"):
+        raise ValueError("fit_linear: method is 'svd' or 'normal', and a state goes with 'normal' only")
     want_v = float(weights[2]) > 0.0 and any(l.get("virial") is not None for l in labels)
-    d = design_cells(ctx, configs, list_cutoff=list_cutoff, virial=want_v, max_design_bytes=max_design_bytes,
-                     max_atoms_per_pass=max_atoms_per_pass, device=device)
     t = ctx.coeffs()
-    res = solve_linear(d["energy"].cpu().numpy(), d["force"].cpu().numpy(), d["virial"].cpu().numpy() if want_v else None,
-                       d["natoms"], labels, np.concatenate([t["species_coeffs"], t["moment_coeffs"]]), weights, rcond)
+    theta0 = np.concatenate([t["species_coeffs"], t["moment_coeffs"]])
+    if method == "normal":
+        state = normal_cells(ctx, configs, labels, state=state, list_cutoff=list_cutoff, virial=want_v, max_bytes=max_design_bytes,
+                             max_atoms_per_pass=max_atoms_per_pass, device=device)
+        res = solve_normal(state, theta0, weights, rcond)
+        res["state"] = state
+    else:
+        d = design_cells(ctx, configs, list_cutoff=list_cutoff, virial=want_v, max_design_bytes=max_design_bytes,
+                         max_atoms_per_pass=max_atoms_per_pass, device=device)
+        res = solve_linear(d["energy"].cpu().numpy(), d["force"].cpu().numpy(), d["virial"].cpu().numpy() if want_v else None,
+                           d["natoms"], labels, theta0, weights, rcond)
     Sp = int(ctx.pot.info.species_count)
     theta = res.pop("theta")
     res.update(species_coeffs=theta[:Sp].copy(), moment_coeffs=theta[Sp:].copy())
@@ -636,6 +679,202 @@ def solve_linear(energy, force, virial, natoms, labels, theta0, weights=(1.0, 0.
         return out
 
     return dict(theta=theta, rank=int(rank), singular_values=sv, rmse_before=rmse(resid0), rmse_after=rmse(resid1))
+
+
+# ---- the same fit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -----------------------
+def _torch_stream(dev):
+    import torch
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def design_fingerprint(ctx, list_cutoff=7.0):
+    """sha256 over everything the design matrix of a configuration depends on: the context's CURRENT radial coefficients,
+    scaling, the cutoffs, the species count, the alpha tables and the list cutoff.  The linear coefficients do not enter:
+    a NormalState stays valid across installs of species_coeffs / moment_coeffs and goes stale with the radial block."""
+    import hashlib
+    t, i = ctx.pot.tables(), ctx.pot.info
+    h = hashlib.sha256()
+    h.update(np.ascontiguousarray(ctx.coeffs()["radial_coeffs"], dtype=np.float64).tobytes())
+    h.update(np.array([i.scaling, i.min_cutoff, i.max_cutoff, float(list_cutoff)], dtype=np.float64).tobytes())
+    h.update(np.array([i.species_count, i.radial_basis_size, i.radial_func_count], dtype=np.int64).tobytes())
+    for key in ("alpha_index_basic", "alpha_index_times", "alpha_moment_mapping"):
+        h.update(np.ascontiguousarray(t[key], dtype=np.int32).tobytes())
+    return h.hexdigest()
+
+
+class NormalState:
+    """The normal equations of a training set on the device: `normal` (capi.Normal: per kind the augmented Gram matrix in
+    double-double and its row count), ncols and the fingerprint (design_fingerprint; None for a state that
+    normal_from_design made from bare matrices) of what the rows depended on.  Neither weights nor coefficients enter, so a
+    state is extended round by round (normal_cells(state=...)) and solved for any weights (solve_normal)."""
+
+    def __init__(self, normal, fingerprint, device):
+        self.normal, self.fingerprint, self.device = normal, fingerprint, device
+        self.ncols = normal.ncols
+
+    def arrays(self):
+        """host copies (hi [3, n, n], lo [3, n, n], counts [3]) after a synchronise of the current stream"""
+        return self.normal.get(stream=_torch_stream(self.device))
+
+    @property
+    def counts(self):
+        """rows that entered per kind: dict(energy, force, virial)"""
+        return dict(zip(capi.NORMAL_KINDS, (int(c) for c in self.normal.get(stream=_torch_stream(self.device))[2])))
+
+    @staticmethod
+    def write_arrays(path, hi, lo, counts, fingerprint):
+        """the file of save(): an .npz at exactly `path` (host only)"""
+        with open(path, "wb") as f:
+            np.savez(f, hi=np.asarray(hi, dtype=np.float64), lo=np.asarray(lo, dtype=np.float64),
+                     counts=np.asarray(counts, dtype=np.int64), fingerprint=np.array("" if fingerprint is None else fingerprint))
+
+    @staticmethod
+    def read_arrays(path):
+        """(hi, lo, counts, fingerprint or None) of a file of save() (host only)"""
+        with np.load(path) as z:
+            return z["hi"], z["lo"], z["counts"], str(z["fingerprint"]) or None
+
+    def save(self, path):
+        """hi, lo, counts and the fingerprint as an .npz, bit for bit"""
+        NormalState.write_arrays(path, *self.arrays(), self.fingerprint)
+
+    @staticmethod
+    def load(path, device=None, workspace_bytes=0):
+        import torch
+        dev = device or torch.device("cuda:0")
+        hi, lo, counts, fp = NormalState.read_arrays(path)
+        normal = capi.Normal(hi.shape[-1] - 1, dev.index or 0, workspace_bytes)
+        normal.set(hi, lo, counts, stream=_torch_stream(dev))
+        return NormalState(normal, fp, dev)
+
+
+def _normal_labels(labels, natoms):
+    """scale and target of every row of the three kinds (the rules of _label_arrays; no weights): energy rows 1 / N_k and
+    E_k, force rows 1 and f, virial rows 1 / N_k and the six components; scale 0 where there is no label or no atom"""
+    first, e_ref, e_on, f_ref, f_on, v_ref, v_on = _label_arrays(labels, natoms, (1.0, 1.0, 1.0))
+    inv = np.where(natoms > 0, 1.0 / np.maximum(natoms, 1), 0.0)
+    return first, (e_on * inv, e_ref), (np.repeat(f_on, 3), f_ref.reshape(-1)), (np.repeat(v_on * inv, 6), v_ref.reshape(-1))
+
+
+def _normal_state(state, ncols, fingerprint, dev, budget, who):
+    """the state to extend, or a new one whose workspace takes at most a quarter of `budget` bytes"""
+    if state is None:
+        return NormalState(capi.Normal(ncols, dev.index or 0, max(1, int(budget) // 4)), fingerprint, dev)
+    if state.ncols != ncols or state.fingerprint != fingerprint:
+        raise ValueError("%s: the state was accumulated for %d columns with fingerprint %s, these rows have %d columns and "
+                         "fingerprint %s (a state is stale once the radial coefficients, the cutoffs or the tables changed)"
+                         % (who, state.ncols, state.fingerprint, ncols, fingerprint))
+    return state
+
+
+def normal_cells(ctx, configs, labels, state=None, list_cutoff=7.0, virial=True, max_bytes=2 ** 31, max_atoms_per_pass=None,
+                 device=None):
+    """The normal equations of the linear refit over a batch of configurations, WITHOUT the design matrix: the passes of
+    design_cells with the three matrices of one pass only, and after each pass's sums three Normal.accumulate calls --
+    energy rows with scale 1 / N_k and target E_k, force rows with scale 1 and target f, virial rows with scale 1 / N_k,
+    six per configuration.  The scale is 0 (the row is skipped) where the label is None or the configuration is empty;
+    the weights of a fit are NOT applied here (solve_normal applies them).  labels as for fit_linear.
+
+    `max_bytes` bounds the rows of one pass (8 ld (7 cfgs + 10 atoms) with virials), the state (48 n^2, n = columns + 1) and
+    its workspace together; nothing grows with the number of configurations.  With max_atoms_per_pass=None the passes are
+    sized to fit.  ValueError when a single pass cannot fit, when labels are malformed, or when `state` (a NormalState to
+    extend by these rows) carries another fingerprint (design_fingerprint).  Returns the NormalState."""
+    import torch
+    if len(labels) != len(configs):
+        raise ValueError("normal_cells: %d labels for %d configurations" % (len(labels), len(configs)))
+    dev = device or torch.device("cuda:0")
+    info = ctx.pot.info
+    cols = int(info.species_count + info.alpha_scalar_count)
+    ld = cols + (cols & 1)
+    per_atom, per_cfg = 8 * ld * (3 + (7 if virial else 1)) + 48, 8 * ld * (7 if virial else 1) + 112
+    state = _normal_state(state, cols, design_fingerprint(ctx, list_cutoff), dev, max_bytes, "normal_cells")
+    ninfo = state.normal.info()
+    fixed = ninfo["state_bytes"] + ninfo["workspace_bytes"]
+    if max_atoms_per_pass is None:
+        max_atoms_per_pass = max(1, (int(max_bytes) - fixed) // (per_atom + per_cfg))
+    natoms = np.array([len(np.asarray(c[0], dtype=np.float64).reshape(-1, 3)) for c in configs], dtype=np.int64)
+    first, (e_sc, e_tg), (f_sc, f_tg), (v_sc, v_tg) = _normal_labels(labels, natoms)
+    buf = {}
+
+    def begin(plan):
+        need = fixed + per_atom * plan["pass_atoms"] + per_cfg * plan["pass_cfgs"]
+        if need > max_bytes:
+            raise ValueError("normal_cells: the state (%d bytes), its workspace (%d) and the rows of the largest pass (%d atoms "
+                             "in %d configurations) need %d bytes, max_bytes is %d; lower max_atoms_per_pass"
+                             % (ninfo["state_bytes"], ninfo["workspace_bytes"], plan["pass_atoms"], plan["pass_cfgs"], need, max_bytes))
+        z = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        buf.update(force=z(3 * plan["pass_atoms"], ld), energy=z(plan["pass_cfgs"], ld),
+                   vir=z(plan["pass_cfgs"], 6, ld) if virial else None)
+
+        def rows_of(k0, k1):
+            n, ncfg = int(first[k1] - first[k0]), k1 - k0
+            force = buf["force"][: 3 * n]
+            capi.zero_async(force, stream=plan["stream"])      # (the design call accumulates into its force rows)
+            return force, buf["energy"][:ncfg], buf["vir"][:ncfg] if virial else None
+
+        def on_pass(k0, k1, force, energy, vir, st):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            a, b = int(first[k0]), int(first[k1])
+            state.normal.accumulate(0, k1 - k0, ld, energy, up(e_sc[k0:k1]), up(e_tg[k0:k1]), stream=st)
+            state.normal.accumulate(1, 3 * (b - a), ld, force, up(f_sc[3 * a: 3 * b]), up(f_tg[3 * a: 3 * b]), stream=st)
+            if virial:
+                state.normal.accumulate(2, 6 * (k1 - k0), ld, vir, up(v_sc[6 * k0: 6 * k1]), up(v_tg[6 * k0: 6 * k1]), stream=st)
+
+        return rows_of, on_pass
+
+    _design_passes(ctx, configs, list_cutoff, virial, max_atoms_per_pass, dev, begin)
+    return state
+
+
+def normal_from_design(d, labels, state=None):
+    """The accumulation of normal_cells from the DEVICE tensors design_cells returned (`d`), so that both solvers can be
+    handed the same rows.  A new state carries no fingerprint (None): normal_cells does not extend it."""
+    natoms = np.asarray(d["natoms"], dtype=np.int64)
+    if len(labels) != len(natoms):
+        raise ValueError("normal_from_design: %d labels for %d configurations" % (len(labels), len(natoms)))
+    e, f, v = d["energy"], d["force"], d["virial"]
+    dev, cols, ld = e.device, int(d["columns"]), int(e.stride(0))
+    st = _torch_stream(dev)
+    state = _normal_state(state, cols, None if state is None else state.fingerprint, dev, 2 ** 30, "normal_from_design")
+    _, e_l, f_l, v_l = _normal_labels(labels, natoms)
+    import torch
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    state.normal.accumulate(0, len(natoms), ld, e, up(e_l[0]), up(e_l[1]), stream=st)
+    state.normal.accumulate(1, int(f.shape[0]), ld, f, up(f_l[0]), up(f_l[1]), stream=st)
+    if v is not None:
+        state.normal.accumulate(2, 6 * len(natoms), ld, v, up(v_l[0]), up(v_l[1]), stream=st)
+    torch.cuda.current_stream(dev).synchronize()
+    return state
+
+
+def solve_normal(state, theta0, weights=(1.0, 0.01, 0.001), rcond=1e-12, drop=2.0 ** -80):
+    """The host part of fit_linear(method="normal"): `state` is a NormalState, or host arrays (hi [3, n, n], lo [3, n, n],
+    counts [3]).  capi.normal_factor forms G = sum_k w_k G_k and its diagonally pivoted Cholesky factor R in double-double
+    -- a column is dropped when its pivot falls to `drop` times its original diagonal --, then delta = lstsq(R, q, rcond)
+    (SVD) with q = Q^T y - R theta0: R has the singular values of the weighted design matrix, and delta is what solve_linear
+    computes from that matrix.  Other weights cost this call only.
+
+    Returns the keys of solve_linear -- theta = theta0 + delta, rank, singular_values (of R), rmse_before, rmse_after: per
+    kind sqrt(capi.normal_quadratic / rows), None for a kind without rows or with weight 0 -- and dropped_columns,
+    pivot_ratios (the kept pivots' ratios in elimination order, then the dropped columns')."""
+    hi, lo, counts = state.arrays() if isinstance(state, NormalState) else state
+    w = [float(x) for x in weights]
+    theta0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
+    live = [k for k in range(3) if w[k] > 0.0 and int(counts[k]) > 0]
+    if min(w) < 0.0 or not live:
+        raise ValueError("fit_linear: no labelled rows with a positive weight")
+    f = capi.normal_factor(hi, lo, [w[k] if k in live else 0.0 for k in range(3)], theta0, drop)
+    delta, _, rank, sv = np.linalg.lstsq(f["R"], f["q"], rcond=rcond)
+    theta = theta0 + delta
+
+    def rmse(th):
+        return {name: float(np.sqrt(capi.normal_quadratic(hi[k], lo[k], th) / int(counts[k]))) if k in live else None
+                for k, name in enumerate(capi.NORMAL_KINDS)}
+
+    return dict(theta=theta, rank=int(rank), singular_values=sv, rmse_before=rmse(theta0), rmse_after=rmse(theta),
+                dropped_columns=f["dropped_columns"], pivot_ratios=f["pivot_ratios"])
 
 
 def _label_arrays(labels, natoms, weights):
