@@ -16,8 +16,8 @@
  *     mtp_context_coeff_tables_device): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
- *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls, mtp_normal_clear,
- *     mtp_normal_accumulate, mtp_normal_get, mtp_normal_set): NULL is
+ *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls, mtp_relax_step,
+ *     mtp_normal_clear, mtp_normal_accumulate, mtp_normal_get, mtp_normal_set): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
  * whose other GPU work runs on the default stream (PyTorch's default) must pass a real stream handle that its own
@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define MTP_MI355X_ABI_VERSION 10
+#define MTP_MI355X_ABI_VERSION 11
 
 /* status codes (the reference aborts through error->one/all, pair_mtp.cpp:92,354-358;
  * the adapter turns a non-zero status + mtp_last_error() into error->all) */
@@ -512,6 +512,51 @@ int mtp_sample_capture(void *stream, int ncfg, const int *d_cfg_first, int nrows
 /* x -= origins[row_cfg]: slot coordinates back to cell coordinates, in front of a re-neighbouring --
  * mtp_ghosts_build_batch wraps cell coordinates and translates them again. */
 int mtp_sample_to_cell(void *stream, int nrows, const int *d_row_cfg, const double *d_origins, double *d_x);
+
+/* ---- batched relaxation: FIRE minimisation of a whole batch of cells, convergence decided on the device -------------
+ *
+ * The other producer of configurations: relaxing many small cells to their local minima under the current potential while
+ * the extrapolation grade is watched (MLIP's `relax`).  The layout, the slot coordinates, the force / grade call, the
+ * capture and the monitor block are those of the batched sampling; the minimiser is FIRE (Bitzek et al., PRL 97, 170201)
+ * with the per-step displacement cap of LAMMPS' min_style fire, one state machine per configuration.  A step s = 0, 1, ... is
+ *   mtp_ghosts_forward -> force call -> mtp_ghosts_reverse[_finish]
+ *   -> on a grade step: the per-configuration grades -> mtp_sample_capture   (BEFORE the minimiser: a configuration over
+ *      threshold_break freezes at the positions that were graded)
+ *   -> mtp_relax_step(s)
+ * d_frozen[k] is the status of configuration k: 0 running, 1 frozen by mtp_sample_capture, 2 converged, 3 failed (non-finite
+ * forces).  Any non-zero status means that no row of the configuration is written again, by this call or by the mtp_sample_*
+ * ones; d_counts[2] (mtp_sample_capture's, and what mtp_sample_monitor reports as "frozen") counts all three.
+ */
+typedef struct mtp_relax_params {
+  double ftol;        /* >= 0: converged when the largest |f_i| of the configuration is <= ftol [eV/A] */
+  double dt_max;      /* > 0: the largest time step [ps] */
+  double dmax;        /* > 0: the largest displacement of a coordinate in one step [A] */
+  double f_inc;       /* >= 1 */
+  double f_dec;       /* in (0, 1) */
+  double alpha_start; /* in [0, 1] */
+  double f_alpha;     /* in (0, 1] */
+  int n_min;          /* >= 0: downhill steps before dt grows */
+} mtp_relax_params;
+/* One FIRE step of every non-empty configuration k with d_frozen[k] == 0, from the folded forces d_f of its rows (metal
+ * units; masses per type as 1 / m in d_inv_mass).  One launch; a workgroup of four wavefronts owns four consecutive
+ * configurations, a wavefront serves a segment of up to 256 rows and the whole workgroup a longer one (as mtp_batch_reduce),
+ * every sum in a fixed order without floating-point atomics: a configuration's result depends on its own rows only.
+ *   1. P = sum f.v, vv = sum v.v, ff = sum f.f, fmax2 = max_i |f_i|^2;  d_fmax[k] = sqrt(fmax2)
+ *   2. ff not finite:       d_frozen[k] = 3, d_done_step[k] = step, ++d_counts[2]; no row is written
+ *      fmax2 <= ftol^2:     d_frozen[k] = 2, d_done_step[k] = step, ++d_counts[2]; its rows of v are set to 0, x is not written
+ *      (with `last` != 0 the call ends here: it only decides; neither the state nor a row of a running configuration is written)
+ *   3. P > 0:   a = 1 - alpha, b = alpha sqrt(vv / ff), ++npos; if npos > n_min: dt = min(dt f_inc, dt_max), alpha *= f_alpha
+ *      else:    a = b = 0, npos = 0, alpha = alpha_start; dt *= f_dec only if vv > 0 (a configuration at rest, as at step 0,
+ *               is not punished)
+ *   4. v' = a v + b f;  vmax = the largest |v'| component of the configuration;  dtv = dt, or dmax / vmax if dt vmax > dmax;
+ *      x += dtv v';  v = v' + (dtv ftm2v / m) f
+ * d_dt, d_alpha, d_npos [ncfg] are the state (the caller starts them at dt, alpha_start and 0; velocities at 0).  d_fmax and
+ * d_done_step of a configuration that is empty or already frozen are not written.  ncfg == 0 launches nothing.  MTP_ERR_ARG,
+ * nothing launched, for a NULL stream (no context), ncfg < 0, step < 0, a missing array or parameters that are not finite
+ * or outside the ranges above. */
+int mtp_relax_step(void *stream, int ncfg, const int *d_cfg_first, const mtp_relax_params *params, int step, int last,
+                   double *d_x, double *d_v, const double *d_f, const int *d_type, const double *d_inv_mass, double *d_dt,
+                   double *d_alpha, int *d_npos, int *d_frozen, int *d_done_step, double *d_fmax, int *d_counts /*[3]*/);
 
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------

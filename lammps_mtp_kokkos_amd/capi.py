@@ -46,7 +46,7 @@ EXPORTS = [
     "mtp_context_install_file", "mtp_context_get_coeffs", "mtp_context_get_selection", "mtp_context_coeff_tables_device",
     "mtp_context_cfg_grade",
     "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
-    "mtp_sample_to_cell",
+    "mtp_sample_to_cell", "mtp_relax_step",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -112,7 +112,7 @@ def kernel_source_hash():
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
-    other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip")
+    other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1091,6 +1091,28 @@ def sample_to_cell(nrows, row_cfg_t, origins_t, x_t, stream=None):
     rc = lib().mtp_sample_to_cell(_st(stream), int(nrows), _ptr(row_cfg_t), _ptr(origins_t), _ptr(x_t))
     if rc:
         raise MtpError(rc, "mtp_sample_to_cell")
+
+
+# ---- batched relaxation (include/mtp_mi355x.h): device tensors in the layout of the batched configurations
+
+RELAX_STATUS = ("running", "captured-frozen", "converged", "failed")       # frozen_t[k] = 0, 1, 2, 3
+
+
+class RelaxParams(C.Structure):
+    """mtp_relax_params"""
+    _fields_ = [(n, C.c_double) for n in ("ftol", "dt_max", "dmax", "f_inc", "f_dec", "alpha_start", "f_alpha")] + [("n_min", C.c_int)]
+
+
+def relax_step(cfg_first_t, params, step, x_t, v_t, f_t, type_t, inv_mass_t, dt_t, alpha_t, npos_t, frozen_t, done_step_t, fmax_t,
+               counts_t, last=False, stream=None):
+    """one FIRE step of every running configuration, with the convergence decision, in one launch: mtp_relax_step.  `params`
+    is a RelaxParams; dt_t, alpha_t, fmax_t [ncfg] float64 and npos_t, frozen_t, done_step_t [ncfg] int32 are per configuration,
+    counts_t [3] int32 is sample_capture's.  last=True only decides."""
+    rc = lib().mtp_relax_step(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), C.byref(params), int(step), int(bool(last)),
+                              _ptr(x_t), _ptr(v_t), _ptr(f_t), _ptr(type_t), _ptr(inv_mass_t), _ptr(dt_t), _ptr(alpha_t),
+                              _ptr(npos_t), _ptr(frozen_t), _ptr(done_step_t), _ptr(fmax_t), _ptr(counts_t))
+    if rc:
+        raise MtpError(rc, "mtp_relax_step")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

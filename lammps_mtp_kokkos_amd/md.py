@@ -1081,6 +1081,126 @@ def maxwell_boltzmann(items, mass_of_type, temperature, seed, keys):
     return out
 
 
+class _CellRun:
+    """One pass of sample_cells / relax_cells -- a batch of cells that stays on the device for a whole run: the first ghost and
+    list build, the per-configuration arrays every such run keeps (frozen, the capture state and its candidate buffer, the
+    monitor block) and the launches around the integrator or minimiser: the force call with the ghost fold, the capture, the
+    monitor, the re-neighbouring in slot coordinates, the energies, and the harvest of what was captured."""
+
+    def __init__(self, ctx, ghosts, buf, items, cells, counts, lay, cut, max_rows, cfg_mode, room, st):
+        torch, dev = buf.torch, buf.dev
+        self.ctx, self.ghosts, self.buf, self.items, self.cells, self.counts = ctx, ghosts, buf, items, cells, counts
+        self.lay, self.cut, self.cfg_mode, self.room, self.st = lay, cut, cfg_mode, room, st
+        self.C = C = int(ctx.pot.info.coeff_count)
+        self.ncfg = ncfg = len(counts)
+        self.cf = cf = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        self.n = n = int(cf[-1])
+        self.stride = int(counts.max())
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self.cf_t, self.org_t = to(cf), to(lay["origins"])
+        na = lambda rows: rows + (rows & 1)
+        self.work_size = lambda rows: 4 * na(rows) + 10 + C + (C & 1)
+        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items, cf, cells, lay, cut, n + max_rows,
+                                     lambda rows, first: buf.reserve(rows, ncfg, self.work_size(rows), 0), st)
+        self.x = buf.xall
+        self.row_cfg = torch.empty(n, dtype=torch.int32, device=dev)
+        capi.sample_row_map(self.cf_t, self.row_cfg, stream=st)
+        self.x_ref = self.x[:n].clone()
+        self.frozen = torch.zeros(ncfg, dtype=torch.int32, device=dev)
+        self.last_capture = torch.full((ncfg,), -2 ** 30, dtype=torch.int32, device=dev)
+        self.slot = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
+        self.counts_t = torch.zeros(3, dtype=torch.int32, device=dev)    # captured, dropped, frozen
+        self.g_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
+        mon = torch.zeros(2 * ncfg + 4, dtype=torch.float64, device=dev)
+        self.mv2, self.d2, self.block = mon[:ncfg], mon[ncfg: 2 * ncfg], mon[2 * ncfg:]
+        self.cand_x = torch.zeros((max(room, 1), self.stride, 3), dtype=torch.float64, device=dev)
+        self.rec = torch.zeros((max(room, 1), 2), dtype=torch.int32, device=dev)
+        self.rec_grade = torch.zeros(max(room, 1), dtype=torch.float64, device=dev)
+        self.layout(nall)
+
+    def layout(self, rows):
+        # f | ev | eatom | max grade | coeff_ders: one allocation, zeroed by one launch every step
+        m, C = rows + (rows & 1), self.C
+        w = self.buf.work[: self.work_size(rows)]
+        self.work, self.f, self.ev, self.eatom = w, w[: 3 * rows].view(rows, 3), w[3 * m: 3 * m + 8], w[3 * m + 8: 4 * m + 8]
+        self.maxg, self.coeff = w[4 * m + 8: 4 * m + 9], w[4 * m + 10: 4 * m + 10 + C]
+
+    def forces(self, grade):
+        ctx, buf, st, n, cfg_mode = self.ctx, self.buf, self.st, self.n, self.cfg_mode
+        self.ghosts.forward(self.x, stream=st)
+        capi.zero_async(self.work, stream=st)
+        ctx.compute_device_rows(0, n, False, self.x, buf.tall, self.f, eflag=3, vflag=0, grade=grade, eatom_t=self.eatom, ev_t=self.ev,
+                                grades_t=buf.grades if grade and not cfg_mode else None, maxg_t=self.maxg if grade else None,
+                                coeff_t=self.coeff if grade and cfg_mode else None, stream=st)
+        self.ghosts.reverse_finish(ctx, self.f, self.ev, eflag=3, vflag=0, stream=st)
+        if grade and cfg_mode:
+            ctx.batch_cfg_grades(self.cf_t, n, self.g_t, stream=st)
+        elif grade:
+            capi.batch_reduce(self.cf_t, grades_t=buf.grades, cfg_grade_t=self.g_t, stream=st)
+
+    def capture(self, step, select, brk, gap):
+        capi.sample_capture(self.cf_t, self.n, self.row_cfg, self.g_t, step, select, brk, gap, self.x, self.org_t, self.frozen,
+                            self.last_capture, self.slot, self.room, self.stride, self.cand_x, self.rec, self.rec_grade,
+                            self.counts_t, stream=self.st)
+
+    def monitor(self, v, mass_t, mv2_t=None):
+        capi.sample_monitor(self.cf_t, self.frozen, self.x, self.x_ref, v, self.buf.tall, mass_t, self.counts_t,
+                            self.mv2 if mv2_t is None else mv2_t, self.d2, self.block, stream=self.st)
+
+    def energies(self, out_t):
+        capi.batch_reduce(self.cf_t, eatom_t=self.eatom, energy_t=out_t, stream=self.st)
+
+    def reneighbor(self):
+        x, n, lay, st = self.x, self.n, self.lay, self.st
+        capi.sample_to_cell(n, self.row_cfg, self.org_t, x, stream=st)
+        rows = self.ghosts.build_batch(x, self.cf, self.cells, lay["origins"], self.cut, stream=st)
+        self.ghosts.types(self.buf.tall, stream=st)
+        self.ctx.build_neighbors_device(x, n, rows, self.cut, lay["lo"], lay["hi"], stream=st)
+        self.layout(rows)
+        self.x_ref.copy_(x[:n])
+
+    def synchronize(self, npass, k0, k1):
+        try:
+            self.ctx.synchronize(stream=self.st)              # an atom type outside the potential is reported here
+        except capi.MtpError as e:
+            raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
+
+    def harvest(self, k0, records, candidates):
+        """appends this pass's records (configuration numbers from k0) and candidates; returns the number dropped"""
+        ch = self.counts_t.cpu().numpy()
+        ncap = int(ch[0])
+        rh, gh, snap = self.rec[:ncap].cpu().numpy(), self.rec_grade[:ncap].cpu().numpy(), self.cand_x[:ncap].cpu().numpy()
+        for j in range(ncap):
+            k = int(rh[j, 0])
+            records.append((k0 + k, int(rh[j, 1]), float(gh[j])))
+            candidates.append((snap[j, : int(self.counts[k])].copy(), self.cells[k].copy(), self.items[k][1].copy()))
+        return int(ch[1])
+
+
+def _run_arguments(who, items, masses, threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every,
+                   check_every):
+    """the host-side checks sample_cells and relax_cells (`who`) share: thresholds, atom types and masses, the capture and
+    list arguments.  Returns (select, brk, mass_of_type, max_candidates)."""
+    select = 2.0 if threshold_select is None else float(threshold_select)
+    brk = 10.0 if threshold_break is None else float(threshold_break)
+    if select > brk:
+        raise ValueError("%s: threshold_select (%g) is above threshold_break (%g)" % (who, select, brk))
+    ntypes = max([int(t.max()) for _, t in items if len(t)], default=1)
+    if min([int(t.min()) for _, t in items if len(t)], default=1) < 1:
+        raise ValueError("%s: atom types count from 1" % who)
+    mass_of_type = np.atleast_1d(np.asarray(masses, dtype=np.float64)).reshape(-1)
+    if len(mass_of_type) == 1:
+        mass_of_type = np.full(ntypes, float(mass_of_type[0]))
+    if len(mass_of_type) < ntypes or not (mass_of_type > 0.0).all():
+        raise ValueError("%s: masses is one positive mass, or one per atom type (%d)" % (who, ntypes))
+    if int(capture_gap) < 0 or int(grade_every or 0) < 0 or int(every) < 1 or int(check_every or 0) < 0:
+        raise ValueError("%s: capture_gap, grade_every and check_every must not be negative, every at least 1" % who)
+    max_candidates = 4 * len(items) if max_candidates is None else int(max_candidates)
+    if max_candidates < 0:
+        raise ValueError("%s: max_candidates must not be negative" % who)
+    return select, brk, mass_of_type, max_candidates
+
+
 def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break, capture_gap,
                       max_candidates, velocities, grade_every, every, check_every):
     """the host-side checks of sample_cells (nothing here touches the device); returns the normalised arguments"""
@@ -1090,10 +1210,8 @@ def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_s
         raise ValueError("sample_cells: dt must be positive and finite, got %r" % (dt,))
     if int(steps) < 0 or int(steps) >= 2 ** 30:
         raise ValueError("sample_cells: steps must be in [0, 2^30)")
-    select = 2.0 if threshold_select is None else float(threshold_select)
-    brk = 10.0 if threshold_break is None else float(threshold_break)
-    if select > brk:
-        raise ValueError("sample_cells: threshold_select (%g) is above threshold_break (%g)" % (select, brk))
+    select, brk, mass_of_type, max_candidates = _run_arguments("sample_cells", items, masses, threshold_select, threshold_break,
+                                                               capture_gap, max_candidates, grade_every, every, check_every)
     if keys is None:
         keys = np.arange(ncfg, dtype=np.uint64)
     else:
@@ -1105,14 +1223,6 @@ def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_s
         temperature = np.full(ncfg, float(temperature))
     if temperature.shape != (ncfg,) or not (np.isfinite(temperature).all() and (temperature >= 0.0).all()):
         raise ValueError("sample_cells: temperature is a non-negative scalar or one per configuration (%d)" % ncfg)
-    ntypes = max([int(t.max()) for _, t in items if len(t)], default=1)
-    if min([int(t.min()) for _, t in items if len(t)], default=1) < 1:
-        raise ValueError("sample_cells: atom types count from 1")
-    mass_of_type = np.atleast_1d(np.asarray(masses, dtype=np.float64)).reshape(-1)
-    if len(mass_of_type) == 1:
-        mass_of_type = np.full(ntypes, float(mass_of_type[0]))
-    if len(mass_of_type) < ntypes or not (mass_of_type > 0.0).all():
-        raise ValueError("sample_cells: masses is one positive mass, or one per atom type (%d)" % ntypes)
     if velocities is not None:
         if len(velocities) != ncfg:
             raise ValueError("sample_cells: %d velocity arrays for %d configurations" % (len(velocities), ncfg))
@@ -1120,11 +1230,6 @@ def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_s
         for k, v in enumerate(velocities):
             if len(v) != natoms[k]:
                 raise ValueError("sample_cells: velocities[%d] must be [%d, 3]" % (k, natoms[k]))
-    if int(capture_gap) < 0 or int(grade_every or 0) < 0 or int(every) < 1 or int(check_every or 0) < 0:
-        raise ValueError("sample_cells: capture_gap, grade_every and check_every must not be negative, every at least 1")
-    max_candidates = 4 * ncfg if max_candidates is None else int(max_candidates)
-    if max_candidates < 0:
-        raise ValueError("sample_cells: max_candidates must not be negative")
     return items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities, max_candidates
 
 
@@ -1188,7 +1293,6 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
     dtf = 0.5 * dt * FTM2V
     half_skin2 = (0.5 * (cut - float(info.max_cutoff))) ** 2
     cfg_mode = bool(grade_every) and bool(info.configuration_mode)
-    C = int(info.coeff_count)
     ncfg_all = len(items)
     if velocities is None:
         velocities = maxwell_boltzmann(items, mass_of_type, temperature, seed, keys)
@@ -1202,7 +1306,6 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
     dropped, steps_done, npass, builds = 0, 0, 0, [0]
     tr_e = np.zeros((steps + 1, ncfg_all)) if trace else None
     tr_k = np.zeros((steps + 1, ncfg_all)) if trace else None
-    na = lambda rows: rows + (rows & 1)
     for k0, k1, lay in passes:
         npass += 1
         ncfg = k1 - k0
@@ -1214,81 +1317,32 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
                 final[k] = dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0)
             continue
         nonempty = int((counts > 0).sum())
-        stride = int(counts.max())
-        room = max(max_candidates - len(records), 0)
-        cells = all_cells[k0:k1]
-        cf_t, org_t = to(cf), to(lay["origins"])
-        work_size = lambda rows: 4 * na(rows) + 10 + C + (C & 1)
-        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items[k0:k1], cf, cells, lay, cut, n + int(max_rows[k0:k1].sum()),
-                                     lambda rows, first: buf.reserve(rows, ncfg, work_size(rows), 0), st)
+        run = _CellRun(ctx, ghosts, buf, items[k0:k1], all_cells[k0:k1], counts, lay, cut, int(max_rows[k0:k1].sum()), cfg_mode,
+                       max(max_candidates - len(records), 0), st)
         builds[0] += 1
-        x = buf.xall
-        row_cfg = torch.empty(n, dtype=torch.int32, device=dev)
-        capi.sample_row_map(cf_t, row_cfg, stream=st)
+        cf_t, row_cfg, x, frozen, block, mv2 = run.cf_t, run.row_cfg, run.x, run.frozen, run.block, run.mv2
         v = to(np.concatenate(velocities[k0:k1]))
-        x_ref = x[:n].clone()
-        frozen = torch.zeros(ncfg, dtype=torch.int32, device=dev)
-        last_capture = torch.full((ncfg,), -2 ** 30, dtype=torch.int32, device=dev)
-        slot = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
-        counts_t = torch.zeros(3, dtype=torch.int32, device=dev)         # captured, dropped, frozen
         temp_t = to(temperature[k0:k1])
         key_t = to(keys[k0:k1].view(np.int64))
-        g_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
-        mon = torch.zeros(2 * ncfg + 4, dtype=torch.float64, device=dev)
-        mv2, d2, block = mon[:ncfg], mon[ncfg: 2 * ncfg], mon[2 * ncfg:]
-        cand_x = torch.zeros((max(room, 1), stride, 3), dtype=torch.float64, device=dev)
-        rec = torch.zeros((max(room, 1), 2), dtype=torch.int32, device=dev)
-        rec_grade = torch.zeros(max(room, 1), dtype=torch.float64, device=dev)
         e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
         tr_dev = torch.zeros((2, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
-        lay_now = {}
-
-        def layout(rows):
-            # f | ev | eatom | max grade | coeff_ders: one allocation, zeroed by one launch every step
-            m = na(rows)
-            w = buf.work[: work_size(rows)]
-            lay_now.update(work=w, f=w[: 3 * rows].view(rows, 3), ev=w[3 * m: 3 * m + 8], eatom=w[3 * m + 8: 4 * m + 8],
-                           maxg=w[4 * m + 8: 4 * m + 9], coeff=w[4 * m + 10: 4 * m + 10 + C])
-
-        def forces(grade):
-            L = lay_now
-            ghosts.forward(x, stream=st)
-            capi.zero_async(L["work"], stream=st)
-            ctx.compute_device_rows(0, n, False, x, buf.tall, L["f"], eflag=3, vflag=0, grade=grade, eatom_t=L["eatom"], ev_t=L["ev"],
-                                    grades_t=buf.grades if grade and not cfg_mode else None, maxg_t=L["maxg"] if grade else None,
-                                    coeff_t=L["coeff"] if grade and cfg_mode else None, stream=st)
-            ghosts.reverse_finish(ctx, L["f"], L["ev"], eflag=3, vflag=0, stream=st)
-            if grade and cfg_mode:
-                ctx.batch_cfg_grades(cf_t, n, g_t, stream=st)
-            elif grade:
-                capi.batch_reduce(cf_t, grades_t=buf.grades, cfg_grade_t=g_t, stream=st)
+        forces = run.forces
+        capture = lambda step: run.capture(step, select, brk, capture_gap)
+        monitor = lambda mv2_t=None: run.monitor(v, mass_t, mv2_t)
 
         def second_half(step, kick):
-            capi.sample_final(n, row_cfg, cf_t, frozen, v, lay_now["f"], buf.tall, mass_t, inv_mass_t, temp_t, key_t, seed, step,
+            capi.sample_final(n, row_cfg, cf_t, frozen, v, run.f, buf.tall, mass_t, inv_mass_t, temp_t, key_t, seed, step,
                               kick, dt, t_damp, stream=st)
 
-        def capture(step):
-            capi.sample_capture(cf_t, n, row_cfg, g_t, step, select, brk, capture_gap, x, org_t, frozen, last_capture, slot, room,
-                                stride, cand_x, rec, rec_grade, counts_t, stream=st)
-
-        def monitor(mv2_t=mv2):
-            capi.sample_monitor(cf_t, frozen, x, x_ref, v, buf.tall, mass_t, counts_t, mv2_t, d2, block, stream=st)
-
         def record(step):
-            capi.batch_reduce(cf_t, eatom_t=lay_now["eatom"], energy_t=tr_dev[0, step], stream=st)
+            run.energies(tr_dev[0, step])
             monitor(tr_dev[1, step])
 
         def reneighbor():
-            capi.sample_to_cell(n, row_cfg, org_t, x, stream=st)
-            rows = ghosts.build_batch(x, cf, cells, lay["origins"], cut, stream=st)
-            ghosts.types(buf.tall, stream=st)
-            ctx.build_neighbors_device(x, n, rows, cut, lay["lo"], lay["hi"], stream=st)
-            layout(rows)
-            x_ref.copy_(x[:n])
+            run.reneighbor()
             builds[0] += 1
 
         graded = lambda step: bool(grade_every) and step % grade_every == 0
-        layout(nall)
         forces(graded(0))
         if t_damp > 0.0:
             second_half(0, 0.0)                               # (fix langevin's setup: the thermostat force of step 0, no kick)
@@ -1302,7 +1356,7 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
         s, since = 0, 0
         while s < steps and not stop:
             s += 1
-            capi.sample_initial(n, row_cfg, frozen, x, v, lay_now["f"], buf.tall, inv_mass_t, dtf, dt, stream=st)
+            capi.sample_initial(n, row_cfg, frozen, x, v, run.f, buf.tall, inv_mass_t, dtf, dt, stream=st)
             since += 1
             need = since >= every
             if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
@@ -1322,15 +1376,9 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
             if trace:
                 record(s)
         steps_done = max(steps_done, s)
-        capi.batch_reduce(cf_t, eatom_t=lay_now["eatom"], energy_t=e_t, stream=st)
+        run.energies(e_t)
         monitor()
-        try:
-            ctx.synchronize(stream=st)                        # an atom type outside the potential is reported here
-        except capi.MtpError as e:
-            raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
-        ch = counts_t.cpu().numpy()
-        ncap = int(ch[0])
-        dropped += int(ch[1])
+        run.synchronize(npass, k0, k1)
         xh = x[:n].cpu().numpy() - np.repeat(lay["origins"], counts, axis=0)
         vh, eh, mh, fh = v.cpu().numpy(), e_t.cpu().numpy(), mv2.cpu().numpy(), frozen.cpu().numpy()
         frozen_all[k0:k1] = fh != 0
@@ -1338,11 +1386,7 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
             a, b = int(cf[j]), int(cf[j + 1])
             final[k0 + j] = dict(x=xh[a:b], v=vh[a:b], energy=float(eh[j]),
                                  temperature=float(mh[j]) * MVV2E / (3.0 * (b - a) * KB) if b > a else 0.0)
-        rh, gh, snap = rec[:ncap].cpu().numpy(), rec_grade[:ncap].cpu().numpy(), cand_x[:ncap].cpu().numpy()
-        for j in range(ncap):
-            k = int(rh[j, 0])
-            records.append((k0 + k, int(rh[j, 1]), float(gh[j])))
-            candidates.append((snap[j, : int(counts[k])].copy(), cells[k].copy(), items[k0 + k][1].copy()))
+        dropped += run.harvest(k0, records, candidates)
         if trace:
             th = tr_dev.cpu().numpy()
             tr_e[: s + 1, k0:k1] = th[0, : s + 1]
@@ -1351,4 +1395,153 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
                builds=builds[0])
     if trace:
         out["trace"] = dict(energy=tr_e[: steps_done + 1], kinetic=tr_k[: steps_done + 1])
+    return out
+
+
+def _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses, threshold_select,
+                     threshold_break, capture_gap, max_candidates, grade_every, every, check_every):
+    """the host-side checks of relax_cells (nothing here touches the device); returns the normalised arguments"""
+    items, all_cells, natoms = _batch_items(configs)
+    if int(steps) < 0 or int(steps) >= 2 ** 30:
+        raise ValueError("relax_cells: steps must be in [0, 2^30)")
+    num = dict(ftol=ftol, dt=dt, dt_max=dt_max, dmax=dmax, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha_start, f_alpha=f_alpha)
+    num = {k: float(q) for k, q in num.items()}
+    for k, q in num.items():
+        if not np.isfinite(q):
+            raise ValueError("relax_cells: %s must be finite, got %r" % (k, q))
+    if not (num["ftol"] >= 0.0 and num["dt"] > 0.0 and num["dt_max"] > 0.0 and num["dmax"] > 0.0):
+        raise ValueError("relax_cells: ftol >= 0, dt > 0, dt_max > 0 and dmax > 0 are required")
+    if not (num["f_inc"] >= 1.0 and 0.0 < num["f_dec"] < 1.0 and 0.0 <= num["alpha_start"] <= 1.0 and 0.0 < num["f_alpha"] <= 1.0):
+        raise ValueError("relax_cells: f_inc >= 1, f_dec in (0, 1), alpha_start in [0, 1] and f_alpha in (0, 1] are required")
+    if int(n_min) < 0:
+        raise ValueError("relax_cells: n_min must not be negative")
+    select, brk, mass_of_type, max_candidates = _run_arguments("relax_cells", items, masses, threshold_select, threshold_break,
+                                                               capture_gap, max_candidates, grade_every, every, check_every)
+    params = capi.RelaxParams(num["ftol"], num["dt_max"], num["dmax"], num["f_inc"], num["f_dec"], num["alpha_start"], num["f_alpha"],
+                              int(n_min))
+    return items, all_cells, natoms, select, brk, mass_of_type, max_candidates, params, num["dt"]
+
+
+def relax_cells(ctx, configs, steps, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1,
+                f_alpha=0.99, masses=183.84, grade_every=0, threshold_select=None, threshold_break=None, capture_gap=0,
+                max_candidates=None, list_cutoff=7.0, every=10, check_every=4, max_atoms_per_pass=None, device=None, trace=False):
+    """The relaxation step of the active-learning loop: every cell of a batch of independent periodic cells is taken to its
+    local minimum under the context's potential (fixed cells), device-resident, with FIRE (Bitzek et al., PRL 97, 170201)
+    and the per-step displacement cap of LAMMPS' min_style fire -- one state machine per configuration, run by
+    mtp_relax_step -- while the extrapolation grade is watched as in sample_cells (what MLIP's `relax` does one cell at a
+    time).  `configs`, the passes, the lists (`list_cutoff`, `every`, `check_every`: rebuilt every `every` steps or when an atom
+    of a running configuration moved more than half the skin, seen in the monitor block) and the capture arguments
+    (`grade_every`, here 0 = never by default, `threshold_select`, `threshold_break`, `capture_gap`, `max_candidates`) are
+    those of sample_cells.
+
+    Velocities start at 0, the time step at `dt` [ps].  Step s = 0 ... steps is: ONE force call over all rows (graded on
+    grade steps) -> ghost fold -> on a grade step mtp_sample_capture, BEFORE the minimiser, so that a configuration over
+    threshold_break freezes at the positions that were graded -> mtp_relax_step(s), which reduces P = sum f.v, sum v.v,
+    sum f.f and the largest |f_i| per configuration and decides on the device: non-finite forces -> "failed"; largest
+    |f_i| <= ftol [eV/A] -> "converged" (its velocities are set to 0); otherwise the FIRE update of dt and alpha (dt_max,
+    n_min, f_inc, f_dec, alpha_start, f_alpha), the mixed velocity, a move of at most `dmax` [A] per coordinate and the kick
+    (masses: one, or one per atom type [g/mol]).  A frozen, converged or failed configuration is not written again.  After
+    step `steps` no move is made: the last launch only decides.  The run of a pass ends early once every non-empty
+    configuration is frozen, converged or failed, seen at the next read of the monitor block (after step 0, every
+    `check_every` steps since the last rebuild, and at every rebuild).
+
+    Returns dict(final: per configuration dict(x [n, 3] cell coordinates, wrapped at the last rebuild; energy: the potential
+    energy at x; fmax: the largest |f_i| at the last step the minimiser looked at it (0 if it never did); status: "running",
+    "captured-frozen", "converged" or "failed"; step: the step of convergence or failure, -1 otherwise; dt: its time step);
+    candidates, records, dropped: as sample_cells; steps_done: the last step whose forces were computed (the largest over the
+    passes); builds) and, with trace=True (one more launch and a copy a step), trace: dict(energy, fmax [steps_done + 1, ncfg]) --
+    per configuration and step, step 0 first, fmax as in `final`."""
+    (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, params,
+     dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
+                            threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every)
+    info = ctx.pot.info
+    grade_every = int(grade_every or 0)
+    if not info.has_selection:
+        if threshold_select is not None or threshold_break is not None:
+            raise capi.MtpError(-23, "relax_cells: thresholds need a potential loaded with its selection state")
+        grade_every = 0
+    import torch
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    steps, cut = int(steps), float(list_cutoff)
+    every, check_every, capture_gap = int(every), int(check_every or 0), int(capture_gap)
+    half_skin2 = (0.5 * (cut - float(info.max_cutoff))) ** 2
+    cfg_mode = bool(grade_every) and bool(info.configuration_mode)
+    ncfg_all = len(items)
+    passes, volume, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
+    ghosts = capi.Ghosts(dev.index or 0)
+    buf = _BatchBuffers(torch, dev)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    mass_t, inv_mass_t = to(mass_of_type), to(1.0 / mass_of_type)
+    candidates, records, final = [], [], [None] * ncfg_all
+    dropped, steps_done, npass, builds = 0, 0, 0, 0
+    tr_e = np.zeros((steps + 1, ncfg_all)) if trace else None
+    tr_f = np.zeros((steps + 1, ncfg_all)) if trace else None
+    graded = lambda step: bool(grade_every) and step % grade_every == 0
+    for k0, k1, lay in passes:
+        npass += 1
+        ncfg = k1 - k0
+        counts = natoms[k0:k1]
+        if int(counts.sum()) == 0:
+            for k in range(k0, k1):
+                final[k] = dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt)
+            continue
+        nonempty = int((counts > 0).sum())
+        run = _CellRun(ctx, ghosts, buf, items[k0:k1], all_cells[k0:k1], counts, lay, cut, int(max_rows[k0:k1].sum()), cfg_mode,
+                       max(max_candidates - len(records), 0), st)
+        builds += 1
+        n, cf = run.n, run.cf
+        v = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        state = torch.zeros((3, ncfg), dtype=torch.float64, device=dev)
+        dt_t, alpha_t, fmax_t = state[0], state[1], state[2]
+        dt_t.fill_(dt)
+        alpha_t.fill_(params.alpha_start)
+        npos_t = torch.zeros(ncfg, dtype=torch.int32, device=dev)
+        done_t = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
+        e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
+        tr_dev = torch.zeros((2, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
+        s, since = 0, 0
+        while True:
+            run.forces(graded(s))
+            if graded(s):
+                run.capture(s, select, brk, capture_gap)
+            capi.relax_step(run.cf_t, params, s, run.x, v, run.f, buf.tall, inv_mass_t, dt_t, alpha_t, npos_t, run.frozen, done_t,
+                            fmax_t, run.counts_t, last=s == steps, stream=st)
+            if trace:
+                run.energies(tr_dev[0, s])
+                tr_dev[1, s].copy_(fmax_t)
+            if s == steps:
+                break
+            since += 1
+            need = since >= every
+            if s == 0 or need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
+                run.monitor(v, mass_t)
+                b = run.block.cpu().numpy()
+                if b[1] >= nonempty:                          # nothing is running any more: this step moved nothing
+                    break
+                need = need or b[0] > half_skin2
+            if need:
+                run.reneighbor()
+                builds += 1
+                since = 0
+            s += 1
+        steps_done = max(steps_done, s)
+        run.energies(e_t)
+        run.synchronize(npass, k0, k1)
+        xh = run.x[:n].cpu().numpy() - np.repeat(lay["origins"], counts, axis=0)
+        eh, sh, fh, dh = e_t.cpu().numpy(), state.cpu().numpy(), run.frozen.cpu().numpy(), done_t.cpu().numpy()
+        for j in range(ncfg):
+            a, b = int(cf[j]), int(cf[j + 1])
+            final[k0 + j] = dict(x=xh[a:b], energy=float(eh[j]), fmax=float(sh[2, j]), status=capi.RELAX_STATUS[int(fh[j])],
+                                 step=int(dh[j]), dt=float(sh[0, j]))
+        dropped += run.harvest(k0, records, candidates)
+        if trace:
+            th = tr_dev.cpu().numpy()
+            tr_e[: s + 1, k0:k1] = th[0, : s + 1]
+            tr_f[: s + 1, k0:k1] = th[1, : s + 1]
+    out = dict(candidates=candidates, records=records, dropped=dropped, final=final, steps_done=steps_done, builds=builds)
+    if trace:
+        out["trace"] = dict(energy=tr_e[: steps_done + 1], fmax=tr_f[: steps_done + 1])
     return out
