@@ -296,7 +296,9 @@ int mtp_halo_layout(int nranks, int nlocal, int nghost, const int *send_idx, con
                     int errlen);
 /* ncclCommInitRank + device copies of the index lists: collective over all nranks processes.  unique_id == NULL
  * creates the halo WITHOUT a communicator (no collective call): it packs, unpacks and answers mtp_halo_get_layout,
- * and its segments are moved by mtp_halo_local_exchange or by the caller; the RCCL entry points then fail. */
+ * and its segments are moved by mtp_halo_local_exchange or by the caller; the RCCL entry points (mtp_halo_forward_begin,
+ * mtp_halo_forward, mtp_halo_reverse_begin, mtp_halo_reverse, mtp_halo_force_step, mtp_halo_allreduce) then return
+ * MTP_ERR_STATE before anything is launched. */
 int mtp_halo_create(int device_id, int nranks, int rank, const void *unique_id, int nlocal, int nghost,
                     const int *send_idx /*[sum send_counts]*/, const double *send_shift /*[sum send_counts][3]*/,
                     const int *send_counts /*[nranks]*/, const int *recv_counts /*[nranks]*/, mtp_halo **out,
@@ -306,7 +308,8 @@ const char *mtp_halo_last_error(const mtp_halo *halo);
 /* what RCCL itself reports for the communicator (ncclCommCount, ncclCommUserRank, ncclGetVersion) */
 int mtp_halo_comm_count(const mtp_halo *halo, int *nranks, int *rank, int *rccl_version);
 /* Comm::forward_comm: d_x[nlocal + k] <- owner's x + shift.  begin: pack on `stream`, exchange on the halo's
- * stream; end: `stream` waits for the exchange.  Work queued on `stream` in between overlaps it. */
+ * stream; end: `stream` waits for the exchange.  Work queued on `stream` in between overlaps it.  A halo without a
+ * communicator: MTP_ERR_STATE from begin, before the pack (likewise mtp_halo_reverse_begin). */
 int mtp_halo_forward_begin(mtp_halo *halo, void *stream, double *d_x /*[nall][3]*/);
 int mtp_halo_forward_end(mtp_halo *halo, void *stream);
 int mtp_halo_forward(mtp_halo *halo, void *stream, double *d_x);
@@ -322,7 +325,13 @@ int mtp_halo_reverse(mtp_halo *halo, void *stream, double *d_f);
  * on `stream` -- pack, forward group, one launch over all rows, reverse group, unpack (measured faster on MI355X than
  * the overlapped one at every domain size tried).  mtp_halo_set_overlap(halo, 1): both exchanges overlapped -- the
  * installed list must then be ordered interior | boundary | interior (interior = no ghost in the atom's list): forward
- * halo || rows [0, rows_a), boundary rows, reverse halo || the last rows_c rows, on `stream` and the halo's stream. */
+ * halo || rows [0, rows_a), boundary rows, reverse halo || the last rows_c rows, on `stream` and the halo's stream.
+ * Every refusal comes before the first launch, so a refused call has written neither d_f nor d_x and issued no group:
+ * MTP_ERR_ARG for a misaligned d_f, a negative row count, rows_a + rows_b + rows_c != inum of the installed list, or a
+ * NULL d_ev when (eflag & MTP_ENERGY_GLOBAL) || vflag; MTP_ERR_STATE for a halo without a communicator or a context
+ * without a list; and the grade refusals of mtp_compute_device_rows (no selection state: MTP_ERR_STATE, no d_grades /
+ * d_coeff_ders array for the potential's mode: MTP_ERR_ARG, Sp*Mu*R > 256: MTP_ERR_LIMIT; text in mtp_last_error(ctx),
+ * the others' in mtp_halo_last_error).  Only a failure of the device or of RCCL can end the call later. */
 int mtp_halo_force_step(mtp_halo *halo, mtp_context *ctx, void *stream, int rows_a, int rows_b, int rows_c,
                         double *d_x, const int *d_type, int eflag, int vflag, int grade_flag, double *d_f,
                         double *d_eatom, double *d_vatom, double *d_ev, double *d_grades, double *d_max_grade,

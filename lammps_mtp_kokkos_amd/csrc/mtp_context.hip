@@ -858,15 +858,8 @@ int mtp_compute_device_rows(mtp_context *c, void *stream, int row_begin, int row
     return fail(c, MTP_ERR_ARG, "row range outside the neighbour list");
   if (!c->have_list) return fail(c, MTP_ERR_STATE, "mtp_compute before mtp_set_neighbors");
   if (!d_x || !d_type || !d_f) return MTP_ERR_ARG;
-  if (grade_flag && !c->pot->has_selection)
-    return fail(c, MTP_ERR_STATE, "extrapolation grades requested but the potential has no #MVS_v1.1 selection state");
+  if (const int grc = mtp_internal_check_grade_args(c, grade_flag, d_grades, d_coeff_ders)) return grc;
   const bool cfg = c->pot->configuration_mode;
-  if (grade_flag) {
-    if (!cfg && !d_grades) return fail(c, MTP_ERR_ARG, "neighbourhood-mode grades need a grades array");
-    if (cfg && !d_coeff_ders) return fail(c, MTP_ERR_ARG, "configuration-mode grades need a coeff_ders array");
-    if (c->pot->species_count * c->pot->radial_func_count * c->pot->radial_basis_size > 256)
-      return fail(c, MTP_ERR_LIMIT, "Sp*Mu*R above 256 is not supported by the grade kernels of this build");
-  }
   if (((eflag & MTP_ENERGY_GLOBAL) || vflag) && finish_tallies && !d_ev) return MTP_ERR_ARG;
   if (c->inum == 0) return MTP_OK;
   if (!set_device(c)) return MTP_ERR_DEVICE;
@@ -1702,6 +1695,22 @@ int mtp_context_last_shape(const mtp_context *c, char *name, int namelen)
 void *mtp_internal_resolve_stream(mtp_context *c, void *stream)
 {
   return stream ? stream : (c ? reinterpret_cast<void *>(c->stream) : nullptr);
+}
+
+int mtp_internal_installed_rows(const mtp_context *c) { return c && c->have_list ? c->inum : -1; }
+
+int mtp_internal_check_grade_args(mtp_context *c, int grade_flag, const double *d_grades, const double *d_coeff_ders)
+{
+  if (!c) return MTP_ERR_ARG;
+  if (!grade_flag) return MTP_OK;
+  if (!c->pot->has_selection)
+    return fail(c, MTP_ERR_STATE, "extrapolation grades requested but the potential has no #MVS_v1.1 selection state");
+  const bool cfg = c->pot->configuration_mode;
+  if (!cfg && !d_grades) return fail(c, MTP_ERR_ARG, "neighbourhood-mode grades need a grades array");
+  if (cfg && !d_coeff_ders) return fail(c, MTP_ERR_ARG, "configuration-mode grades need a coeff_ders array");
+  if (c->pot->species_count * c->pot->radial_func_count * c->pot->radial_basis_size > 256)
+    return fail(c, MTP_ERR_LIMIT, "Sp*Mu*R above 256 is not supported by the grade kernels of this build");
+  return MTP_OK;
 }
 
 int mtp_internal_finish_unpack(mtp_context *c, void *stream, int eflag, int vflag, double *d_ev, double *d_f, const int *d_idx,

@@ -149,6 +149,12 @@ int mtp_internal_finish_unpack(mtp_context *c, void *stream, int eflag, int vfla
                                const double *d_frecv, int n3);
 // NULL -> the context's own stream; anything else unchanged (the one place the C ABI's NULL-stream rule is resolved)
 void *mtp_internal_resolve_stream(mtp_context *c, void *stream);
+// rows of the installed neighbour list (the `inum` a row split has to add up to), -1 before a list is installed
+int mtp_internal_installed_rows(const mtp_context *c);
+// the refusals of a grade call that depend on the potential and the output pointers alone (no selection state, no grades /
+// coeff_ders array, Sp*Mu*R above the grade kernels' limit): MTP_OK or the code, with the context's last_error set.  The
+// one copy of these checks: mtp_compute_device_rows makes them through it, mtp_halo_force_step ahead of its first launch.
+int mtp_internal_check_grade_args(mtp_context *c, int grade_flag, const double *d_grades, const double *d_coeff_ders);
 hipError_t mtp_launch_fixed_to_force(long long *fq, double *f, int nall, hipStream_t st);
 hipError_t mtp_launch_zero(double *p, size_t n, hipStream_t st);
 // non-default compile-time tunables of mtp_kernels.hip, "NAME=value " each ("" for the shipped build)

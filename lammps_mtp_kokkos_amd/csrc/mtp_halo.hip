@@ -282,6 +282,14 @@ static void unpack_reverse(mtp_halo *h, hipStream_t st, double *d_f)
   }
 }
 
+// The RCCL entry points of a halo created with unique_id == NULL refuse before anything is launched (as
+// mtp_halo_allreduce does): a pack or a zeroed force array left behind by a call that then fails helps nobody.
+static int no_comm(mtp_halo *h, const char *fn)
+{
+  h->last_error = std::string(fn) + ": this halo was created without a communicator (unique_id == NULL): use mtp_halo_local_exchange";
+  return MTP_ERR_STATE;
+}
+
 static int null_stream(mtp_halo *h, const char *fn)
 {
   h->last_error = std::string(fn) + ": a NULL stream is not accepted (the halo has no stream of its own to order the "
@@ -293,6 +301,7 @@ int mtp_halo_forward_begin(mtp_halo *h, void *stream, double *d_x)
 {
   if (!h || !d_x) return MTP_ERR_ARG;
   if (!stream) return null_stream(h, "mtp_halo_forward_begin");
+  if (!h->comm) return no_comm(h, "mtp_halo_forward_begin");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   try {
     HIP_OK(hipSetDevice(h->device));
@@ -325,6 +334,7 @@ int mtp_halo_reverse_begin(mtp_halo *h, void *stream, const double *d_f)
 {
   if (!h || !d_f) return MTP_ERR_ARG;
   if (!stream) return null_stream(h, "mtp_halo_reverse_begin");
+  if (!h->comm) return no_comm(h, "mtp_halo_reverse_begin");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   try {
     HIP_OK(hipSetDevice(h->device));
@@ -372,13 +382,33 @@ int mtp_halo_reverse(mtp_halo *h, void *stream, double *d_f)
 // One domain-decomposed force call (one entry point instead of eight, so a driver's per-call overhead is paid once
 // per step).  Once the forward exchange has been issued the reverse exchange is ALWAYS issued too, whatever the
 // force launches returned: a rank that skipped it would leave its peers blocked in their ncclRecv.  The first error
-// is returned afterwards.
+// is returned afterwards.  Whatever can be refused from the arguments and the state of the two objects is therefore
+// refused BEFORE the first launch: a refused call has touched neither d_f nor d_x and has issued no group.
 int mtp_halo_force_step(mtp_halo *h, mtp_context *ctx, void *stream, int rows_a, int rows_b, int rows_c, double *d_x,
                         const int *d_type, int eflag, int vflag, int grade_flag, double *d_f, double *d_eatom,
                         double *d_vatom, double *d_ev, double *d_grades, double *d_max_grade, double *d_coeff_ders)
 {
-  if (!h || !ctx || !d_x || !d_f || rows_a < 0 || rows_b < 0 || rows_c < 0) return MTP_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(d_f) & 15u) return MTP_ERR_ARG;
+  if (!h) return MTP_ERR_ARG;
+  auto refuse = [&](int code, const char *what) {
+    h->last_error = std::string("mtp_halo_force_step: ") + what;
+    return code;
+  };
+  if (!ctx) return refuse(MTP_ERR_ARG, "no context");
+  if (!d_x || !d_type || !d_f) return refuse(MTP_ERR_ARG, "d_x, d_type and d_f must not be NULL");
+  if (rows_a < 0 || rows_b < 0 || rows_c < 0) return refuse(MTP_ERR_ARG, "a negative row count");
+  if (reinterpret_cast<uintptr_t>(d_f) & 15u) return refuse(MTP_ERR_ARG, "d_f is not 16-byte aligned");
+  if (!h->comm) return no_comm(h, "mtp_halo_force_step");
+  if (((eflag & MTP_ENERGY_GLOBAL) || vflag) && !d_ev)
+    return refuse(MTP_ERR_ARG, "a global energy or a virial is asked for without d_ev");
+  if (const int grc = mtp_internal_check_grade_args(ctx, grade_flag, d_grades, d_coeff_ders)) {
+    h->last_error.clear();   // the text is the context's (mtp_last_error), as for every refusal of the force call itself
+    return grc;
+  }
+  const int inum = mtp_internal_installed_rows(ctx);
+  if (inum < 0) return refuse(MTP_ERR_STATE, "called before mtp_set_neighbors");
+  if ((long long) rows_a + rows_b + rows_c != inum)
+    return refuse(MTP_ERR_ARG, ("rows_a + rows_b + rows_c = " + std::to_string((long long) rows_a + rows_b + rows_c) +
+                                " is not the row count of the installed list, " + std::to_string(inum)).c_str());
   // NULL -> the context's stream, resolved once: every launch and both groups below use `sv`
   void *sv = mtp_internal_resolve_stream(ctx, stream);
   hipStream_t st = reinterpret_cast<hipStream_t>(sv);
