@@ -440,8 +440,13 @@ int mtp_context_create(const mtp_potential *pot, int device_id, mtp_context **ou
     c->d_maxg.reserve(1);
     c->d_err.reserve(1);
     HIP_CHECK(hipMemsetAsync(c->d_err.ptr, 0, sizeof(int), st));
-    c->d_stamps.reserve(16);
-    HIP_CHECK(hipMemsetAsync(c->d_stamps.ptr, 0, 16 * sizeof(unsigned long long), st));
+#ifdef MTP_STAMPS
+    constexpr size_t stamp_words = 16 + MTP_TRACE_WORDS;   // the phase sums, then the per-wavefront trace
+#else
+    constexpr size_t stamp_words = 16;
+#endif
+    c->d_stamps.reserve(stamp_words);
+    HIP_CHECK(hipMemsetAsync(c->d_stamps.ptr, 0, stamp_words * sizeof(unsigned long long), st));
     HIP_CHECK(hipStreamSynchronize(st));
 
     MtpDevParams &b = c->base;
@@ -1665,6 +1670,17 @@ int mtp_debug_read_stamps(mtp_context *c, unsigned long long *out16)
   (void) hipMemset(c->d_stamps.ptr, 0, 16 * sizeof(unsigned long long));
   return MTP_OK;
 }
+
+#ifdef MTP_STAMPS
+// the per-wavefront phase trace of the last force launch (mtp_device.hpp, MTP_TRACE_*): `words` must be MTP_TRACE_WORDS
+int mtp_debug_read_trace(mtp_context *c, unsigned long long *out, int words)
+{
+  if (!c || !out || words != MTP_TRACE_WORDS) return MTP_ERR_ARG;
+  if (hipMemcpy(out, c->d_stamps.ptr + 16, (size_t) words * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
+    return MTP_ERR_DEVICE;
+  return MTP_OK;
+}
+#endif
 
 }   // extern "C"
 

@@ -14,6 +14,16 @@
 #define MTP_PSTRIDE 12      // slot ids per mu in the LDS blob (nu = 0..11, -1 padded)
 #define MTP_SLOT_ROWS_MU 4  // radial functions whose slot ids the argument block repeats (slot_row): the nodg layouts' Mu <= 4
 
+// Diagnostic build only (MTP_STAMPS): behind the 16 phase sums of MtpDevParams::stamps, the wavefronts of workgroups 0..7
+// (one per XCD) leave the clock at which each entered each stamped phase of each of their atoms -- one record per
+// (workgroup, wavefront): {hardware id, XCC id, atoms, clock at kernel entry, behind the prologue, at the first atom,
+// 2 unused}, then 10 clocks per atom (scripts/wave_phase_trace.py).  The shipped library allocates and writes none of it.
+#define MTP_TRACE_WGS 8
+#define MTP_TRACE_HDR 8
+#define MTP_TRACE_ATOMS 24
+#define MTP_TRACE_WAVE_WORDS (MTP_TRACE_HDR + 10 * MTP_TRACE_ATOMS)
+#define MTP_TRACE_WORDS (MTP_TRACE_WGS * MTP_MAX_WPB * MTP_TRACE_WAVE_WORDS)
+
 // A times row packed in 8 bytes: lo = 8 a0 | 8 a1 << 16, hi = 8 a3 | (mult & 0xffff) << 16 -- BYTE offsets of the moments
 // in the per-atom LDS image (moment indices below 8192)
 struct alignas(8) MtpRow8 {   // 8-byte aligned: one ds_read_b64 / global_load_dwordx2 per row, not two dword reads

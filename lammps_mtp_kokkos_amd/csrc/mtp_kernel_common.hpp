@@ -9,6 +9,7 @@
 
 // Diagnostic build only (make stamps): per-phase s_memtime sums per launch into p.stamps[16].
 // The shipped library is built without MTP_STAMPS and executes no stamp.
+// The traced wavefronts (st_trace != nullptr: mtp_device.hpp, MTP_TRACE_*) also leave every clock itself, per atom.
 #ifdef MTP_STAMPS
 #define STAMP(k)                                                         \
   do {                                                                   \
@@ -16,6 +17,8 @@
     __builtin_amdgcn_s_waitcnt(0xC07F);                                  \
     st_acc[k] += _t - st_prev;                                           \
     st_prev = _t;                                                        \
+    if (st_trace && st_atom < MTP_TRACE_ATOMS && lane == 0)              \
+      st_trace[MTP_TRACE_HDR + 10 * st_atom + (k)] = _t;                 \
   } while (0)
 #else
 #define STAMP(k) ((void) 0)

@@ -127,6 +127,33 @@ template <class SH> constexpr bool block_regs_shape()
 }
 template <class SH> constexpr bool block_regs_ct = MTP_BLOCK_REGS && block_regs_shape<SH>();
 
+// Issue priority by phase (s_setprio), in the fixed FORCE shapes of the 3-per-SIMD build.  The phases of an atom want
+// opposite things of the SIMD: tile tables, basic moments, coefficient blocks and forces are VALU bursts; the loop head,
+// the compaction and both product passes with the leaf sweep and the energy issue a few instructions between dependent
+// memory or LDS round trips.  At equal priority the issue arbiter favours the oldest wavefront of a SIMD, so a chain's
+// next instruction queues behind another wavefront's burst and the younger wavefronts fall behind by whole atoms (the
+// per-wavefront phase trace: scripts/wave_phase_trace.py, profiles/r13_ab_wave_phases.txt).  Raised in the chains and
+// lowered in the bursts: four s_setprio per atom, -5.7 % per step on the headline launch.  The generic kernels and the
+// grade shape compile as they did.  (A start offset per SIMD slot, MTP_WAVE_STAGGER, was measured beside it, lost, and
+// is not in the sources: the same record.)
+#ifndef MTP_PHASE_PRIO
+#define MTP_PHASE_PRIO 1   // 0: every phase at the launch's priority, for A/B runs
+#endif
+template <class SH, class = void> struct has_kernel_args : std::false_type {};
+template <class SH> struct has_kernel_args<SH, std::void_t<decltype(&SH::kGRADE), decltype(&SH::kWPS)>> : std::true_type {};
+template <class SH> constexpr bool phase_prio_shape()
+{
+  if constexpr (has_kernel_args<SH>::value) return !SH::kGRADE && SH::kWPS == 3;   // (ShapeGeneric names no kernel)
+  else return false;
+}
+template <class SH> constexpr bool phase_prio_ct = MTP_PHASE_PRIO && phase_prio_shape<SH>();
+#define MTP_PRIO_CHAIN 2
+#define MTP_PRIO_BURST 0
+template <bool ON, int PRIO> __device__ __forceinline__ void phase_prio()
+{
+  if constexpr (ON) __builtin_amdgcn_s_setprio(PRIO);
+}
+
 // f[idx] += v.  Default: native fp64 HBM atomics (the sum depends on the arrival order in the last bits).
 // Deterministic mode (mtp_context_set_deterministic, tests / reproducible goldens): the contributions are added as
 // 64-bit fixed-point integers (2^-40 eV/A resolution, |f| < 2^23), which commute exactly, and converted once at the end.

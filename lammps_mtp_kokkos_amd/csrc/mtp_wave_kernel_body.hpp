@@ -20,6 +20,7 @@
   constexpr bool NODG_CT = WPS == 3;
   // f' of the force phase from registers: the dg-free build of a shape that fixes the slot -> mu map (mtp_wave_body.hpp)
   constexpr bool FP_REGS = NODG_CT && MTP_MU_BITS && fp_regs_ct<SH>;
+  constexpr bool PHASE_PRIO = phase_prio_ct<SH>;   // s_setprio by phase (mtp_wave_body.hpp)
   constexpr int NG = 64 / KL;            // neighbour groups in the wavefront
   constexpr int NPG = NT / NG;           // neighbours per group per tile
   static_assert(NT == 32, "the force phase maps lanes to (32 neighbours) x (2 halves)");
@@ -192,6 +193,20 @@
   unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long st_prev = __builtin_amdgcn_s_memtime();
   const unsigned long long st_prologue = st_prev - st_entry;   // argument block, table copy, barrier, first list head
+  // the trace record of this wavefront (workgroups 0..7: one per XCD), and the atom it is at
+  unsigned long long *st_trace = nullptr;
+  int st_atom = 0;
+  if (kp->stamps && blockIdx.x < MTP_TRACE_WGS && wave < MTP_MAX_WPB)
+    st_trace = kp->stamps + 16 + (size_t) (blockIdx.x * MTP_MAX_WPB + wave) * MTP_TRACE_WAVE_WORDS;
+  if (st_trace && lane == 0) {
+    st_trace[0] = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_ID: wave slot [3:0], SIMD [5:4], CU [11:8], SE [15:13]
+    st_trace[1] = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // XCC_ID
+    st_trace[2] = ii_beg < ii_end ? (unsigned long long) ((ii_end - ii_beg + ii_step - 1) / ii_step) : 0ull;
+    st_trace[3] = st_entry;
+    st_trace[4] = st_prev;
+    st_trace[5] = __builtin_amdgcn_s_memtime();   // the first atom starts here
+  }
+  st_prev = __builtin_amdgcn_s_memtime();
 #endif
 
   auto store_seeds = [&]() {   // D[seed_idx[k]] = seed_val[k]: the adjoints of the stored scalars
@@ -204,6 +219,7 @@
   int nx_i = __builtin_amdgcn_readfirstlane(hd_i), nx_b = __builtin_amdgcn_readfirstlane(hd_b);
   int nx_n = __builtin_amdgcn_readfirstlane(hd_e) - nx_b;
   for (int ii = ii_beg; ii < ii_end; ii += ii_step) {
+    phase_prio<PHASE_PRIO, MTP_PRIO_CHAIN>();   // loop head and compaction: dependent memory round trips
     // ii is wave-uniform, so is everything loaded through it: keep it in SGPRs.  Two dependent memory round trips per
     // atom: {type_i, x_i, the row's first 128 neighbour ids; the NEXT atom's ilist, first} -> {x_j, type_j}: every load
     // of a stage is requested before the first wait, and before the type check branches.
@@ -309,6 +325,7 @@
     wave_fence();
 
     STAMP(1);   // compaction
+    phase_prio<PHASE_PRIO, MTP_PRIO_BURST>();   // tile tables and basic moments: bursts
     // ---- 2+3. tiles: tables, then basic moments in registers ------------------------------
     double acc[NB][9];
 #pragma unroll
@@ -362,6 +379,7 @@
       if (ntiles > 1) wave_fence();
     }
     STAMP(3);   // basic moments
+    phase_prio<PHASE_PRIO, MTP_PRIO_CHAIN>();   // product passes, leaf sweep, energy: a few instructions between LDS round trips
     // sum over the neighbour groups, then moments + adjoints into LDS
 #pragma unroll
     for (int t = 0; t < NB; t++)
@@ -466,6 +484,7 @@
     }
 
     STAMP(6);   // products backward
+    phase_prio<PHASE_PRIO, MTP_PRIO_BURST>();   // coefficient blocks and forces: bursts
     // ---- 5. forces ---------------------------------------------------------------------------
     // the (now free) moment region receives the coefficient blocks of the derivative polynomials:
     // basic k = (slot s; a, b, c) puts a D_k at the d/dx coefficient of x^(a-1) y^b z^c, b D_k and c D_k alike
@@ -672,7 +691,11 @@
     STAMP(7);   // forces
     wave_fence();
     STAMP(8);   // per-atom totals
+#ifdef MTP_STAMPS
+    st_atom++;
+#endif
   }
+  phase_prio<PHASE_PRIO, MTP_PRIO_BURST>();
 #ifdef MTP_STAMPS
   if (lane == 0 && kp->stamps)
     for (int k = 0; k < 10; k++) atomicAdd(kp->stamps + k, st_acc[k]);
