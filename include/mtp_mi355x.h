@@ -16,7 +16,8 @@
  *     mtp_context_coeff_tables_device): NULL means the
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
- *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls, mtp_relax_step,
+ *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls, mtp_relax_step, the
+ *     mtp_relax_cell_* calls,
  *     mtp_normal_clear, mtp_normal_accumulate, mtp_normal_get, mtp_normal_set): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
@@ -566,6 +567,93 @@ typedef struct mtp_relax_params {
 int mtp_relax_step(void *stream, int ncfg, const int *d_cfg_first, const mtp_relax_params *params, int step, int last,
                    double *d_x, double *d_v, const double *d_f, const int *d_type, const double *d_inv_mass, double *d_dt,
                    double *d_alpha, int *d_npos, int *d_frozen, int *d_done_step, double *d_fmax, int *d_counts /*[3]*/);
+
+/* ---- batched variable-cell relaxation: the cells relax with their atoms, under a pressure ----------------------------
+ *
+ * mtp_relax_step with the cell among the degrees of freedom.  Row-vector convention throughout: a cell h has the lattice
+ * vectors as rows, x = s . h, and the virial is W = -dE/d(eps) for x -> x (I + eps), components xx yy zz xy xz yz (what
+ * mtp_batch_reduce leaves per configuration from a force call with MTP_VIRIAL_ATOM).  Per configuration k:
+ *   h0 [9]     the cell given;  D [9], starting at I: the current cell is h = h0 . D
+ *   xt [n][3]  reference-frame positions: x - origin = xt . D
+ *   the generalised coordinates are the n rows of xt and the three rows of L D, L [A] = cell_factor (times the
+ *   configuration's atom count with factor_per_atom != 0); the generalised velocities are vt [n][3] and vq [9] [A/ps].
+ * Generalised forces from the folded forces f and the virial W:
+ *   ft_i = f_i . D^T
+ *   W'   = (W - p V I) o mask,  V = det h, mask the symmetric 0/1 matrix of cell_mask[6] (order as W);
+ *          isotropic != 0:  W' <- (tr W' / 3) I
+ *   G    = D^-T . W' / L        [eV/A]  (= -d(E + p V)/d(L D) when the mask is all ones)
+ * `pressure` is in eV/A^3 (1 GPa = 1 / 160.21766 eV/A^3).  A step s is
+ *   mtp_ghosts_forward -> force call with per-atom virial -> mtp_ghosts_reverse_finish -> mtp_batch_reduce (W)
+ *   -> on a grade step: the grades -> mtp_sample_capture -> mtp_relax_cell_capture_cells
+ *   -> mtp_relax_cell_step(s) -> mtp_ghosts_deform
+ * and a re-neighbouring reads d_h back, builds ghosts and list for those cells and calls mtp_relax_cell_rebase.
+ */
+typedef struct mtp_relax_cell_params {
+  mtp_relax_params fire; /* as for mtp_relax_step; dmax caps every generalised component: |dD_ab| <= dmax / L a step */
+  double stol;           /* >= 0: converged needs max_ab |W'_ab| / V <= stol [eV/A^3] as well */
+  double pressure;       /* finite [eV/A^3] */
+  double cell_factor;    /* > 0, finite: L [A], or L per atom */
+  double cell_mass;      /* > 0, finite: the mass of the cell coordinates [g/mol] */
+  int cell_mask[6];      /* 0 or 1 each: which components of W' drive the cell (xx yy zz xy xz yz) */
+  int isotropic;         /* != 0: the cell changes its volume only */
+  int factor_per_atom;   /* != 0: L = cell_factor times the atom count of the configuration */
+} mtp_relax_cell_params;
+/* The device arrays of mtp_relax_cell_step: per owned row, per atom type, per configuration.  All are the caller's. */
+typedef struct mtp_relax_cell_arrays {
+  const int *cfg_first;   /* [ncfg + 1] */
+  double *x;              /* [n][3] slot coordinates: written as origin + xt . D for the rows that move */
+  double *xt, *vt;        /* [n][3] */
+  const double *f;        /* [n][3] folded forces */
+  const int *type;        /* [n] */
+  const double *inv_mass; /* per type */
+  const double *virial;   /* [ncfg][6] W */
+  const double *h0;       /* [ncfg][9] */
+  const double *origins;  /* [ncfg][3] */
+  double *D, *vq;         /* [ncfg][9] */
+  const double *Dbinv;    /* [ncfg][9] inverse of D at the last rebuild (mtp_relax_cell_rebase; I at the start) */
+  const double *href;     /* [ncfg][9] the cell at the last rebuild */
+  const int *nimg;        /* [ncfg][3] images per direction and sign at the last rebuild (mtp_ghosts_cell_bounds) */
+  double *dt, *alpha;     /* [ncfg] FIRE state, as for mtp_relax_step */
+  int *npos, *frozen, *done_step;
+  double *fmax, *smax;    /* [ncfg] */
+  double *gcell;          /* [ncfg][9] G */
+  double *h;              /* [ncfg][9] the current cell: start it at h0 */
+  double *T;              /* [ncfg][9] Dbinv . D after the move: what mtp_ghosts_deform takes */
+  double *cellmove;       /* [ncfg] the list-validity measure of the cell, below */
+  int *counts;            /* [3] mtp_sample_capture's */
+} mtp_relax_cell_arrays;
+/* One FIRE step over the extended degrees of freedom of every non-empty configuration with frozen[k] == 0.  One launch, the
+ * layout, the wavefront / workgroup split and the fixed-order reductions of mtp_relax_step:
+ *   1. P, vv, ff over the n + 3 generalised rows (ft, vt; then G, vq: the cell rows are added to the atom total, entry by
+ *      entry in storage order) and fmax2 = max_i |f_i|^2 over the TRUE forces
+ *   2. smax = max_ab |W'_ab| / V;  fmax[k] = sqrt(fmax2), smax[k], gcell[k] = G, h[k] = h0 . D are written
+ *   3. ff, a component of W, V or det D not finite, or det D <= 0:  frozen[k] = 3 (failed), as in mtp_relax_step
+ *   4. fmax2 <= ftol^2 and smax <= stol:  frozen[k] = 2 (converged); vt and vq are set to 0, nothing else is written
+ *   5. with `last` != 0 the call ends here
+ *   6. the FIRE rules of mtp_relax_step (a, b, npos, dt, alpha), vmax and ONE dtv with the dmax cap over all generalised
+ *      components
+ *   7. xt += dtv vt';  D += dtv vq' / L;  vt = vt' + (dtv ftm2v / m_i) ft;  vq = vq' + (dtv ftm2v / cell_mass) G;
+ *      x = origin + xt . D (the new ones);  h[k] = h0 . D and T[k] = Dbinv . D for the new D
+ *   8. cellmove[k] = sum_a (nimg[k][a] + 1) |h_a - href_a|  [A], rows a of the new cell: an image that is not a ghost of the
+ *      last build has |n_a| <= nimg_a + 1 (or lies a whole plane spacing further out) and moves by n . (h - href) against
+ *      its owner, so a pair distance changes by at most two atom displacements plus cellmove.
+ * MTP_ERR_ARG, nothing launched: as mtp_relax_step, and stol < 0, pressure / cell_factor / cell_mass not finite,
+ * cell_factor <= 0, cell_mass <= 0, a mask entry that is neither 0 nor 1, a missing array. */
+int mtp_relax_cell_step(void *stream, int ncfg, const mtp_relax_cell_params *params, int step, int last,
+                        const mtp_relax_cell_arrays *arrays);
+/* After a re-neighbouring (which wrapped d_x and translated it to d_origins): xt = (x - origin) . D^-1 for every owned row
+ * and Dbinv[k] = D[k]^-1, for the configurations with det D > 0 (the others are left as they are). */
+int mtp_relax_cell_rebase(void *stream, int ncfg, int nrows, const int *d_row_cfg, const double *d_origins, const double *d_x,
+                          const double *d_D, double *d_xt, double *d_Dbinv);
+/* Right after mtp_sample_capture: d_cand_cell[slot[k]][9] = d_h[k] for 0 <= slot[k] < max_candidates, so that a candidate
+ * carries the cell it was graded in. */
+int mtp_relax_cell_capture_cells(void *stream, int ncfg, const int *d_slot, int max_candidates, const double *d_h,
+                                 double *d_cand_cell);
+/* Ghosts that follow a deforming cell between re-neighbourings: shift[k] = shift_at_build[k] . T[cfg(owner[k])] with
+ * d_row_cfg [nlocal] (mtp_sample_row_map) and d_T [ncfg][9] (T = D_build^-1 . D_now, written by mtp_relax_cell_step).  The
+ * handle keeps a copy of the shifts of the last build (made by the first call after it), so rounding does not accumulate
+ * over the steps; mtp_ghosts_forward / reverse / reverse_finish / types work unchanged. */
+int mtp_ghosts_deform(mtp_ghosts *g, void *stream, const int *d_row_cfg, const double *d_T /*[ncfg][9]*/);
 
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------

@@ -47,6 +47,7 @@ EXPORTS = [
     "mtp_context_cfg_grade",
     "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
     "mtp_sample_to_cell", "mtp_relax_step",
+    "mtp_relax_cell_step", "mtp_relax_cell_rebase", "mtp_relax_cell_capture_cells", "mtp_ghosts_deform",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -112,7 +113,8 @@ def kernel_source_hash():
     import hashlib
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
-    other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip")
+    other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
+                      "mtp_relax_cell.hip", "mtp_relax_common.hpp")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -921,6 +923,11 @@ class Ghosts:
     def types(self, type_t, stream=None):
         self._check(lib().mtp_ghosts_types(self.h, C.c_void_p(stream) if stream else None, _ptr(type_t)))
 
+    def deform(self, row_cfg_t, T_t, stream=None):
+        """the ghosts follow a deforming cell: shift = (shift of the last build) . T_t[configuration of the owner], T_t
+        [ncfg, 3, 3] as relax_cell_step leaves it (mtp_ghosts_deform)"""
+        self._check(lib().mtp_ghosts_deform(self.h, C.c_void_p(stream) if stream else None, _ptr(row_cfg_t), _ptr(T_t)))
+
     def owner(self, stream=None):
         """(device pointer, nall) of the owner map of the last build over ALL rows -- identity on the owned rows -- in
         storage of the handle, valid until the next build (mtp_ghosts_owner_device)"""
@@ -1113,6 +1120,59 @@ def relax_step(cfg_first_t, params, step, x_t, v_t, f_t, type_t, inv_mass_t, dt_
                               _ptr(npos_t), _ptr(frozen_t), _ptr(done_step_t), _ptr(fmax_t), _ptr(counts_t))
     if rc:
         raise MtpError(rc, "mtp_relax_step")
+
+
+# ---- batched variable-cell relaxation (include/mtp_mi355x.h)
+
+GPA = 1.0 / 160.21766                                                       # 1 GPa in eV/A^3
+
+
+class RelaxCellParams(C.Structure):
+    """mtp_relax_cell_params"""
+    _fields_ = [("fire", RelaxParams)] + [(n, C.c_double) for n in ("stol", "pressure", "cell_factor", "cell_mass")] + \
+               [("cell_mask", C.c_int * 6), ("isotropic", C.c_int), ("factor_per_atom", C.c_int)]
+
+
+RELAX_CELL_ARRAYS = ("cfg_first", "x", "xt", "vt", "f", "type", "inv_mass", "virial", "h0", "origins", "D", "vq", "Dbinv", "href",
+                     "nimg", "dt", "alpha", "npos", "frozen", "done_step", "fmax", "smax", "gcell", "h", "T", "cellmove", "counts")
+
+
+class RelaxCellArrays(C.Structure):
+    """mtp_relax_cell_arrays: device pointers, in the order of RELAX_CELL_ARRAYS"""
+    _fields_ = [(n, C.c_void_p) for n in RELAX_CELL_ARRAYS]
+
+
+def relax_cell_params(fire, stol, pressure, cell_factor, cell_mass, cell_mask=(1, 1, 1, 1, 1, 1), isotropic=False,
+                      factor_per_atom=False):
+    """a RelaxCellParams from a RelaxParams and the cell arguments (no check: mtp_relax_cell_step makes them)"""
+    return RelaxCellParams(fire, float(stol), float(pressure), float(cell_factor), float(cell_mass),
+                           (C.c_int * 6)(*[int(m) for m in cell_mask]), int(bool(isotropic)), int(bool(factor_per_atom)))
+
+
+def relax_cell_step(ncfg, params, step, arrays, last=False, stream=None):
+    """one FIRE step over atoms and cell of every running configuration, in one launch: mtp_relax_cell_step.  `params` is a
+    RelaxCellParams, `arrays` a dict of device tensors with the keys RELAX_CELL_ARRAYS (float64; type, nimg, npos, frozen,
+    done_step, counts and cfg_first int32)."""
+    A = RelaxCellArrays(*[_ptr(arrays.get(n)) for n in RELAX_CELL_ARRAYS])
+    rc = lib().mtp_relax_cell_step(_st(stream), int(ncfg), C.byref(params), int(step), int(bool(last)), C.byref(A))
+    if rc:
+        raise MtpError(rc, "mtp_relax_cell_step")
+
+
+def relax_cell_rebase(ncfg, row_cfg_t, origins_t, x_t, D_t, xt_t, Dbinv_t, stream=None):
+    """after a re-neighbouring: xt = (x - origin) . D^-1 for every owned row, Dbinv = D^-1: mtp_relax_cell_rebase"""
+    rc = lib().mtp_relax_cell_rebase(_st(stream), int(ncfg), int(row_cfg_t.numel()), _ptr(row_cfg_t), _ptr(origins_t), _ptr(x_t),
+                                     _ptr(D_t), _ptr(xt_t), _ptr(Dbinv_t))
+    if rc:
+        raise MtpError(rc, "mtp_relax_cell_rebase")
+
+
+def relax_cell_capture_cells(slot_t, max_candidates, h_t, cand_cell_t, stream=None):
+    """cand_cell_t[slot] = h_t[k] for the configurations sample_capture just gave a slot: mtp_relax_cell_capture_cells"""
+    rc = lib().mtp_relax_cell_capture_cells(_st(stream), int(slot_t.numel()), _ptr(slot_t), int(max_candidates), _ptr(h_t),
+                                            _ptr(cand_cell_t))
+    if rc:
+        raise MtpError(rc, "mtp_relax_cell_capture_cells")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

@@ -304,6 +304,19 @@ __global__ void __launch_bounds__(256) ghosts_types_kernel(int *__restrict__ typ
   if (k < nghost) type[nlocal + k] = type[owner[k]];
 }
 
+// shift[k] = shift0[k] . T[cfg of owner[k]]   (one lane per coordinate; rows are vectors)
+__global__ void __launch_bounds__(256) ghosts_deform_kernel(const int *__restrict__ owner, const int *__restrict__ row_cfg,
+                                                           const double *__restrict__ T, const double *__restrict__ shift0,
+                                                           double *__restrict__ shift, int n3)
+{
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n3) return;
+  const int k = e / 3, c = e - 3 * k;
+  const double *__restrict__ t = T + 9 * (size_t) row_cfg[owner[k]];
+  const double *__restrict__ s = shift0 + 3 * (size_t) k;
+  shift[e] = s[0] * t[c] + s[1] * t[3 + c] + s[2] * t[6 + c];
+}
+
 // fix nve, first half: v += dtf f / m; x += dt v.  second half: v += dtf f / m.  (metal units: dtf = dt/2 * ftm2v)
 __global__ void __launch_bounds__(256) nve_initial_kernel(double *__restrict__ x, double *__restrict__ v,
                                                          const double *__restrict__ f, const int *__restrict__ type,
@@ -361,6 +374,9 @@ struct mtp_ghosts {
   int *d_owner_all = nullptr;                // mtp_ghosts_owner_device only: [cap_owner_all] identity | d_owner
   int cap_owner_all = 0;
   double *d_shift = nullptr;
+  double *d_shift0 = nullptr;                // mtp_ghosts_deform only: [cap_shift0][3] the shifts as the last build left them
+  int cap_shift0 = 0;
+  bool shift0_valid = false;                 // d_shift0 holds the shifts of the last build
   ShiftRange *d_range = nullptr;             // mtp_ghosts_build_cell only: [cap_range] + one 64-bit total behind them
   int cap_range = 0;
   CellSlot *d_slot = nullptr;                // mtp_ghosts_build_batch only: [cap_slot] cells + origins, and the
@@ -374,7 +390,7 @@ struct mtp_ghosts {
   {
     (void) hipSetDevice(device);
     for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, (void *) d_range, (void *) d_slot,
-                    (void *) d_cfg_first, (void *) d_owner_all, d_tmp})
+                    (void *) d_cfg_first, (void *) d_owner_all, (void *) d_shift0, d_tmp})
       if (p) (void) hipFree(p);
   }
 };
@@ -500,6 +516,7 @@ int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x, int nlocal, int c
   MD_HIP(ghosts_reserve_ghosts(g, total));
   g->nlocal = nlocal;
   g->nghost = total;
+  g->shift0_valid = false;
   *nall_out = nlocal + total;
   if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written
     g->last_error = "mtp_ghosts_build: capacity of the position array is smaller than owned + ghost atoms";
@@ -587,6 +604,7 @@ int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x, int nlocal, 
     if (total64 > 0x7fffffffull - (unsigned long long) nlocal) {   // never wrapped: the scanned offsets are not used
       g->nlocal = nlocal;
       g->nghost = 0;
+      g->shift0_valid = false;
       *nall_out = 0x7fffffff;
       g->last_error = "mtp_ghosts_build_cell: owned + ghost atoms do not fit a 32-bit count (cell far smaller than rghost?)";
       return MTP_ERR_LIMIT;
@@ -595,6 +613,7 @@ int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x, int nlocal, 
   }
   g->nlocal = nlocal;
   g->nghost = 0;
+  g->shift0_valid = false;
   *nall_out = nlocal + total;
   if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written or kept
     g->last_error = "mtp_ghosts_build_cell: capacity of the position array is smaller than owned + ghost atoms";
@@ -602,6 +621,7 @@ int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x, int nlocal, 
   }
   MD_HIP(ghosts_reserve_ghosts(g, total));
   g->nghost = total;
+  g->shift0_valid = false;
   if (total > 0) {
     hipLaunchKernelGGL(ghosts_cell_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c, nlocal, total, g->d_first,
                        g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
@@ -747,6 +767,7 @@ int mtp_ghosts_build_batch(mtp_ghosts *g, void *stream, double *d_x, int ncfg, c
   }
   g->nlocal = nlocal;
   g->nghost = 0;
+  g->shift0_valid = false;
   *nall_out = nlocal;
   if (nlocal == 0) return MTP_OK;   // nothing to wrap, no images
   const bool sum64 = !(bound < 2147483647.0);
@@ -806,6 +827,7 @@ int mtp_ghosts_build_batch(mtp_ghosts *g, void *stream, double *d_x, int ncfg, c
   }
   MD_HIP(ghosts_reserve_ghosts(g, total));
   g->nghost = total;
+  g->shift0_valid = false;
   if (total > 0) {
     hipLaunchKernelGGL(ghosts_batch_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, g->d_slot, nlocal, total, g->d_first,
                        g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
@@ -853,6 +875,30 @@ int mtp_ghosts_types(mtp_ghosts *g, void *stream, int *d_type)
   if (g->nghost > 0)
     hipLaunchKernelGGL(ghosts_types_kernel, dim3((g->nghost + 255) / 256), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), d_type, g->nlocal, g->d_owner, g->nghost);
+  MD_HIP(hipGetLastError());
+  return MTP_OK;
+}
+
+int mtp_ghosts_deform(mtp_ghosts *g, void *stream, const int *d_row_cfg, const double *d_T)
+{
+  if (!g || !d_row_cfg || !d_T) return MTP_ERR_ARG;
+  if (!stream) return ghosts_null_stream(g, "mtp_ghosts_deform");
+  if (g->nghost == 0) return MTP_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  MD_HIP(hipSetDevice(g->device));
+  if (!g->shift0_valid) {   // the first call after a build keeps that build's shifts
+    if (g->nghost > g->cap_shift0) {
+      if (g->d_shift0) (void) hipFree(g->d_shift0);
+      g->d_shift0 = nullptr;
+      g->cap_shift0 = 0;
+      MD_HIP(hipMalloc((void **) &g->d_shift0, 3 * (size_t) g->cap_ghost * sizeof(double)));
+      g->cap_shift0 = g->cap_ghost;
+    }
+    MD_HIP(hipMemcpyAsync(g->d_shift0, g->d_shift, 3 * (size_t) g->nghost * sizeof(double), hipMemcpyDeviceToDevice, st));
+    g->shift0_valid = true;
+  }
+  hipLaunchKernelGGL(ghosts_deform_kernel, dim3((3 * g->nghost + 255) / 256), dim3(256), 0, st, g->d_owner, d_row_cfg, d_T,
+                     g->d_shift0, g->d_shift, 3 * g->nghost);
   MD_HIP(hipGetLastError());
   return MTP_OK;
 }

@@ -4,48 +4,11 @@
 // the ghost fold: the per-configuration reductions, the FIRE state machine, the convergence decision and the move, so that
 // nothing is read back between re-neighbourings.  No context, no handle: every array is the caller's, and the entry point
 // takes the stream and rejects NULL (the rule of mtp_sample_*).
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-
-#include "../../include/mtp_mi355x.h"
-#include "mtp_device.hpp"
+#include "mtp_relax_common.hpp"
 
 namespace {
 
-constexpr double RELAX_FTM2V = 1.0 / 1.0364269e-4;   // LAMMPS metal units (update.cpp), as mtp_sample.hip
-
-constexpr int RELAX_WAVES = MTP_BATCH_BLOCK / 64;
-
-// the wavefront reductions of mtp_sample.hip: xor butterfly, a fixed order, the same bits in every lane
-__device__ __forceinline__ double wave_sum64(double v)
-{
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max64(double v)
-{
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v = fmax(v, __shfl_xor(v, s, 64));
-  return v;
-}
-
-// the total over NT co-operating threads, the same bits in every one of them: the wavefront's own (NT = 64), or the
-// wavefronts' partials combined in wave order through `part` (NT = MTP_BATCH_BLOCK: every thread of the workgroup calls)
-template <int NT, bool MAX>
-__device__ __forceinline__ double relax_total(double val, double *part)
-{
-  val = MAX ? wave_max64(val) : wave_sum64(val);
-  if (NT == 64) return val;
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = val;
-  __syncthreads();
-  double t = part[0];
-#pragma unroll
-  for (int u = 1; u < RELAX_WAVES; u++) t = MAX ? fmax(t, part[u]) : t + part[u];
-  __syncthreads();
-  return t;
-}
+using namespace relax_common;   // the reductions and the parameter check, shared with mtp_relax_cell.hip
 
 // One configuration, served by thread t of NT (all of them take every branch together: each decision is made from totals
 // that are the same in all).  Rows are read one per thread, consecutive threads consecutive rows; v' = a v + b f is computed
@@ -165,15 +128,6 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) relax_step_kernel(int ncfg, c
       relax_configuration<MTP_BATCH_BLOCK>(threadIdx.x, k, r0, r1, p, step, last, x, v, f, type, inv_mass, d_dt, d_alpha, d_npos,
                                            d_frozen, d_done_step, d_fmax, d_counts, part);
   }
-}
-
-bool in_range(const mtp_relax_params &p)
-{
-  const double all[7] = {p.ftol, p.dt_max, p.dmax, p.f_inc, p.f_dec, p.alpha_start, p.f_alpha};
-  for (double q : all)
-    if (!std::isfinite(q)) return false;
-  return p.ftol >= 0.0 && p.dt_max > 0.0 && p.dmax > 0.0 && p.f_inc >= 1.0 && p.f_dec > 0.0 && p.f_dec < 1.0 &&
-      p.alpha_start >= 0.0 && p.alpha_start <= 1.0 && p.f_alpha > 0.0 && p.f_alpha <= 1.0 && p.n_min >= 0;
 }
 
 }   // namespace

@@ -1087,8 +1087,9 @@ class _CellRun:
     monitor block) and the launches around the integrator or minimiser: the force call with the ghost fold, the capture, the
     monitor, the re-neighbouring in slot coordinates, the energies, and the harvest of what was captured."""
 
-    def __init__(self, ctx, ghosts, buf, items, cells, counts, lay, cut, max_rows, cfg_mode, room, st):
+    def __init__(self, ctx, ghosts, buf, items, cells, counts, lay, cut, max_rows, cfg_mode, room, st, vatom=False):
         torch, dev = buf.torch, buf.dev
+        self.per_row = 10 if vatom else 4                     # (vatom: relax_cells_vc, the work layout of evaluate_cells)
         self.ctx, self.ghosts, self.buf, self.items, self.cells, self.counts = ctx, ghosts, buf, items, cells, counts
         self.lay, self.cut, self.cfg_mode, self.room, self.st = lay, cut, cfg_mode, room, st
         self.C = C = int(ctx.pot.info.coeff_count)
@@ -1099,7 +1100,7 @@ class _CellRun:
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         self.cf_t, self.org_t = to(cf), to(lay["origins"])
         na = lambda rows: rows + (rows & 1)
-        self.work_size = lambda rows: 4 * na(rows) + 10 + C + (C & 1)
+        self.work_size = lambda rows: self.per_row * na(rows) + 10 + C + (C & 1)
         nall = _pass_ghosts_and_list(ctx, ghosts, buf, items, cf, cells, lay, cut, n + max_rows,
                                      lambda rows, first: buf.reserve(rows, ncfg, self.work_size(rows), 0), st)
         self.x = buf.xall
@@ -1111,19 +1112,21 @@ class _CellRun:
         self.slot = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
         self.counts_t = torch.zeros(3, dtype=torch.int32, device=dev)    # captured, dropped, frozen
         self.g_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
-        mon = torch.zeros(2 * ncfg + 4, dtype=torch.float64, device=dev)
-        self.mv2, self.d2, self.block = mon[:ncfg], mon[ncfg: 2 * ncfg], mon[2 * ncfg:]
+        mon = torch.zeros((3 if vatom else 2) * ncfg + 4, dtype=torch.float64, device=dev)
+        self.mv2, self.d2, self.block = mon[:ncfg], mon[ncfg: 2 * ncfg], mon[2 * ncfg: 2 * ncfg + 4]
+        self.cellmove, self.monitor_read = mon[2 * ncfg + 4:], mon[ncfg:]     # (vatom: d2 | block | cellmove is ONE read)
         self.cand_x = torch.zeros((max(room, 1), self.stride, 3), dtype=torch.float64, device=dev)
         self.rec = torch.zeros((max(room, 1), 2), dtype=torch.int32, device=dev)
         self.rec_grade = torch.zeros(max(room, 1), dtype=torch.float64, device=dev)
         self.layout(nall)
 
     def layout(self, rows):
-        # f | ev | eatom | max grade | coeff_ders: one allocation, zeroed by one launch every step
-        m, C = rows + (rows & 1), self.C
+        # f | ev | eatom | (vatom) | max grade | coeff_ders: one allocation, zeroed by one launch every step
+        m, C, p = rows + (rows & 1), self.C, self.per_row
         w = self.buf.work[: self.work_size(rows)]
         self.work, self.f, self.ev, self.eatom = w, w[: 3 * rows].view(rows, 3), w[3 * m: 3 * m + 8], w[3 * m + 8: 4 * m + 8]
-        self.maxg, self.coeff = w[4 * m + 8: 4 * m + 9], w[4 * m + 10: 4 * m + 10 + C]
+        self.vatom = w[4 * m + 8: p * m + 8]
+        self.maxg, self.coeff = w[p * m + 8: p * m + 9], w[p * m + 10: p * m + 10 + C]
 
     def forces(self, grade):
         ctx, buf, st, n, cfg_mode = self.ctx, self.buf, self.st, self.n, self.cfg_mode
@@ -1165,15 +1168,18 @@ class _CellRun:
         except capi.MtpError as e:
             raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
 
-    def harvest(self, k0, records, candidates):
-        """appends this pass's records (configuration numbers from k0) and candidates; returns the number dropped"""
+    def harvest(self, k0, records, candidates, cand_cell=None):
+        """appends this pass's records (configuration numbers from k0) and candidates; returns the number dropped.  cand_cell
+        [slots, 9]: the cell every candidate was captured in, where cells change during the run"""
         ch = self.counts_t.cpu().numpy()
         ncap = int(ch[0])
         rh, gh, snap = self.rec[:ncap].cpu().numpy(), self.rec_grade[:ncap].cpu().numpy(), self.cand_x[:ncap].cpu().numpy()
+        ch9 = None if cand_cell is None else cand_cell[:ncap].cpu().numpy().reshape(ncap, 3, 3)
         for j in range(ncap):
             k = int(rh[j, 0])
             records.append((k0 + k, int(rh[j, 1]), float(gh[j])))
-            candidates.append((snap[j, : int(self.counts[k])].copy(), self.cells[k].copy(), self.items[k][1].copy()))
+            cell = self.cells[k] if ch9 is None else ch9[j]
+            candidates.append((snap[j, : int(self.counts[k])].copy(), cell.copy(), self.items[k][1].copy()))
         return int(ch[1])
 
 
@@ -1399,23 +1405,24 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
 
 
 def _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses, threshold_select,
-                     threshold_break, capture_gap, max_candidates, grade_every, every, check_every):
-    """the host-side checks of relax_cells (nothing here touches the device); returns the normalised arguments"""
+                     threshold_break, capture_gap, max_candidates, grade_every, every, check_every, who="relax_cells"):
+    """the host-side checks of relax_cells and relax_cells_vc (`who`; nothing here touches the device); returns the normalised
+    arguments"""
     items, all_cells, natoms = _batch_items(configs)
     if int(steps) < 0 or int(steps) >= 2 ** 30:
-        raise ValueError("relax_cells: steps must be in [0, 2^30)")
+        raise ValueError(who + ": steps must be in [0, 2^30)")
     num = dict(ftol=ftol, dt=dt, dt_max=dt_max, dmax=dmax, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha_start, f_alpha=f_alpha)
     num = {k: float(q) for k, q in num.items()}
     for k, q in num.items():
         if not np.isfinite(q):
-            raise ValueError("relax_cells: %s must be finite, got %r" % (k, q))
+            raise ValueError("%s: %s must be finite, got %r" % (who, k, q))
     if not (num["ftol"] >= 0.0 and num["dt"] > 0.0 and num["dt_max"] > 0.0 and num["dmax"] > 0.0):
-        raise ValueError("relax_cells: ftol >= 0, dt > 0, dt_max > 0 and dmax > 0 are required")
+        raise ValueError(who + ": ftol >= 0, dt > 0, dt_max > 0 and dmax > 0 are required")
     if not (num["f_inc"] >= 1.0 and 0.0 < num["f_dec"] < 1.0 and 0.0 <= num["alpha_start"] <= 1.0 and 0.0 < num["f_alpha"] <= 1.0):
-        raise ValueError("relax_cells: f_inc >= 1, f_dec in (0, 1), alpha_start in [0, 1] and f_alpha in (0, 1] are required")
+        raise ValueError(who + ": f_inc >= 1, f_dec in (0, 1), alpha_start in [0, 1] and f_alpha in (0, 1] are required")
     if int(n_min) < 0:
-        raise ValueError("relax_cells: n_min must not be negative")
-    select, brk, mass_of_type, max_candidates = _run_arguments("relax_cells", items, masses, threshold_select, threshold_break,
+        raise ValueError(who + ": n_min must not be negative")
+    select, brk, mass_of_type, max_candidates = _run_arguments(who, items, masses, threshold_select, threshold_break,
                                                                capture_gap, max_candidates, grade_every, every, check_every)
     params = capi.RelaxParams(num["ftol"], num["dt_max"], num["dmax"], num["f_inc"], num["f_dec"], num["alpha_start"], num["f_alpha"],
                               int(n_min))
@@ -1544,4 +1551,251 @@ def relax_cells(ctx, configs, steps, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, 
     out = dict(candidates=candidates, records=records, dropped=dropped, final=final, steps_done=steps_done, builds=builds)
     if trace:
         out["trace"] = dict(energy=tr_e[: steps_done + 1], fmax=tr_f[: steps_done + 1])
+    return out
+
+
+def cell_list_stale(d2, cellmove, skin):
+    """Host arithmetic: the rebuild rule of relax_cells_vc.  d2 [ncfg]: the largest squared displacement of an atom of each
+    configuration since the last rebuild; cellmove [ncfg]: mtp_relax_cell_step's sum_a (nimg_a + 1) |h_a - href_a|; skin =
+    list_cutoff - the potential's cutoff.  A pair changes its distance by at most two atom displacements plus |n . (h - href)|,
+    and an image that was no ghost at the last build has |n_a| <= nimg_a + 1 (or lies a whole plane spacing further out): the
+    lists are stale once max_k (2 sqrt(d2[k]) + cellmove[k]) > skin.  With cellmove = 0 this is the half-skin test."""
+    d2, cellmove = np.asarray(d2, dtype=np.float64), np.asarray(cellmove, dtype=np.float64)
+    return bool(d2.size) and bool(np.max(2.0 * np.sqrt(d2) + cellmove) > float(skin))
+
+
+def _relax_vc_arguments(natoms, mass_of_type, pressure, stol, cell_mask, isotropic, cell_factor, cell_mass):
+    """the host-side checks of relax_cells_vc's own arguments (nothing here touches the device); returns (stol, pressure,
+    cell_factor, cell_mass, cell_mask [6], factor_per_atom)"""
+    stol, pressure = float(stol), float(pressure)
+    if not (np.isfinite(stol) and stol >= 0.0):
+        raise ValueError("relax_cells_vc: stol must be finite and not negative, got %r" % (stol,))
+    if not np.isfinite(pressure):
+        raise ValueError("relax_cells_vc: pressure must be finite, got %r" % (pressure,))
+    per_atom = cell_factor is None
+    cell_factor = 1.0 if per_atom else float(cell_factor)
+    if not (np.isfinite(cell_factor) and cell_factor > 0.0):
+        raise ValueError("relax_cells_vc: cell_factor must be positive and finite, got %r" % (cell_factor,))
+    cell_mass = float(np.mean(mass_of_type)) if cell_mass is None else float(cell_mass)
+    if not (np.isfinite(cell_mass) and cell_mass > 0.0):
+        raise ValueError("relax_cells_vc: cell_mass must be positive and finite, got %r" % (cell_mass,))
+    try:
+        mask = [int(m) for m in cell_mask]
+        exact = all(float(m) == q for m, q in zip(cell_mask, mask))
+    except (TypeError, ValueError):
+        mask, exact = [], False
+    if len(mask) != 6 or not exact or any(m not in (0, 1) for m in mask):
+        raise ValueError("relax_cells_vc: cell_mask is six entries 0 or 1 (xx yy zz xy xz yz), got %r" % (cell_mask,))
+    return stol, pressure, cell_factor, cell_mass, mask, per_atom
+
+
+def _cell_images(cells, rghost):
+    """mtp_ghosts_cell_bounds' nimage of many cells at once, int32 [ncfg, 3]: ceil(rghost / plane spacing) per direction, the
+    margins of plan_cell_passes (a rebuild of relax_cells_vc needs them for every cell of the pass)"""
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    cross = np.stack([np.cross(cells[:, 1], cells[:, 2]), np.cross(cells[:, 2], cells[:, 0]), np.cross(cells[:, 0], cells[:, 1])], axis=1)
+    volume = (cells[:, 0] * cross[:, 0]).sum(1)
+    m = float(rghost) * np.sqrt((cross * cross).sum(2)) / volume[:, None]
+    return np.minimum(np.ceil(m), 2147483647.0).astype(np.int32)
+
+
+def _det3(h):
+    """determinants of [..., 3, 3] arrays or tensors, elementwise products (no factorisation)"""
+    return (h[..., 0, 0] * (h[..., 1, 1] * h[..., 2, 2] - h[..., 1, 2] * h[..., 2, 1])
+            - h[..., 0, 1] * (h[..., 1, 0] * h[..., 2, 2] - h[..., 1, 2] * h[..., 2, 0])
+            + h[..., 0, 2] * (h[..., 1, 0] * h[..., 2, 1] - h[..., 1, 1] * h[..., 2, 0]))
+
+
+def relax_cells_vc(ctx, configs, steps, pressure=0.0, stol=1e-4, cell_mask=(1, 1, 1, 1, 1, 1), isotropic=False, cell_factor=None,
+                   cell_mass=None, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1,
+                   f_alpha=0.99, masses=183.84, grade_every=0, threshold_select=None, threshold_break=None, capture_gap=0,
+                   max_candidates=None, list_cutoff=7.0, every=10, check_every=4, max_atoms_per_pass=None, device=None,
+                   trace=False):
+    """relax_cells with the cell among the degrees of freedom: every cell of the batch is taken, together with its atoms, to a
+    local minimum of the enthalpy E + p V under the context's potential, device-resident, one state machine per configuration
+    run by mtp_relax_cell_step (include/mtp_mi355x.h, "batched variable-cell relaxation").  Every argument of relax_cells has
+    its meaning there.  `pressure` [eV/A^3; 1 GPa = capi.GPA = 1 / 160.21766 eV/A^3]; `stol` [eV/A^3]: a configuration has
+    converged when its largest |f_i| <= ftol AND the largest |W'_ab| / V <= stol, W' = (W - p V I) o mask the virial that drives
+    the cell.  `cell_mask` (xx yy zz xy xz yz; 0 or 1): which components do; all 0 keeps the cells fixed.  `isotropic`: the cell
+    changes its volume only.  `cell_factor` [A]: the length L that turns the deformation D (the cell is h = h0 . D, the atoms sit
+    at x = xt . D) into the coordinates L D the minimiser moves -- default the configuration's atom count -- and `cell_mass`
+    [g/mol] their mass, default the mean of `masses`.  `dmax` caps every generalised coordinate: |dD_ab| <= dmax / L per step.
+
+    Step s = 0 ... steps: ghosts follow (their shifts deformed with the cell by mtp_ghosts_deform after every move) -> ONE force
+    call with per-atom energies and virials -> ghost fold -> the virial per configuration (mtp_batch_reduce) -> on a grade step
+    the grades, mtp_sample_capture and the cells of the captured (a candidate is positions, the cell AT the graded step, types)
+    -> mtp_relax_cell_step(s).  The lists are rebuilt every `every` steps or when max_k (2 sqrt(d2[k]) + cellmove[k]) exceeds the
+    skin (cell_list_stale), seen in the one read of the monitor: its block, d2 and cellmove.  A rebuild reads the cells back,
+    lays the pass out again for them -- MtpError(-24) naming the configuration if they no longer fit one pass -- and builds
+    ghosts and lists for them.
+
+    Returns what relax_cells returns; final[k] also has cell [3, 3], virial [6] (W at x and cell), volume, enthalpy = energy +
+    pressure * volume and smax (as fmax: at the last step the minimiser looked at it), and trace=True adds smax and volume
+    [steps_done + 1, ncfg] (volume: of the cell the step's forces were taken in)."""
+    who = "relax_cells_vc"
+    (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, fire,
+     dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
+                            threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every, who)
+    stol, pressure, cell_factor, cell_mass, mask, per_atom = _relax_vc_arguments(natoms, mass_of_type, pressure, stol, cell_mask,
+                                                                                 isotropic, cell_factor, cell_mass)
+    params = capi.relax_cell_params(fire, stol, pressure, cell_factor, cell_mass, mask, isotropic, per_atom)
+    info = ctx.pot.info
+    grade_every = int(grade_every or 0)
+    if not info.has_selection:
+        if threshold_select is not None or threshold_break is not None:
+            raise capi.MtpError(-23, who + ": thresholds need a potential loaded with its selection state")
+        grade_every = 0
+    import torch
+    dev = device or torch.device("cuda:0")
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    steps, cut = int(steps), float(list_cutoff)
+    every, check_every, capture_gap = int(every), int(check_every or 0), int(capture_gap)
+    skin = cut - float(info.max_cutoff)
+    cfg_mode = bool(grade_every) and bool(info.configuration_mode)
+    ncfg_all = len(items)
+    passes, volume0, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
+    ghosts = capi.Ghosts(dev.index or 0)
+    buf = _BatchBuffers(torch, dev)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    mass_t, inv_mass_t = to(mass_of_type), to(1.0 / mass_of_type)
+    candidates, records, final = [], [], [None] * ncfg_all
+    dropped, steps_done, npass, builds = 0, 0, 0, 0
+    tr = np.zeros((4, steps + 1, ncfg_all)) if trace else None            # energy, fmax, smax, volume
+    graded = lambda step: bool(grade_every) and step % grade_every == 0
+    for k0, k1, lay in passes:
+        npass += 1
+        ncfg = k1 - k0
+        counts = natoms[k0:k1]
+        if int(counts.sum()) == 0:
+            for k in range(k0, k1):
+                final[k] = dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt,
+                                cell=all_cells[k].copy(), virial=np.zeros(6), volume=float(volume0[k]),
+                                enthalpy=pressure * float(volume0[k]), smax=0.0)
+            continue
+        nonempty = int((counts > 0).sum())
+        run = _CellRun(ctx, ghosts, buf, items[k0:k1], all_cells[k0:k1].copy(), counts, lay, cut, int(max_rows[k0:k1].sum()),
+                       cfg_mode, max(max_candidates - len(records), 0), st, vatom=True)
+        builds += 1
+        n, cf, cf_t, row_cfg = run.n, run.cf, run.cf_t, run.row_cfg
+        eye = torch.eye(3, dtype=torch.float64, device=dev).reshape(1, 9).repeat(ncfg, 1)
+        h0_t = to(all_cells[k0:k1].reshape(ncfg, 9))
+        A = dict(cfg_first=cf_t, x=run.x, xt=torch.zeros((n, 3), dtype=torch.float64, device=dev),
+                 vt=torch.zeros((n, 3), dtype=torch.float64, device=dev), f=run.f, type=buf.tall, inv_mass=inv_mass_t,
+                 virial=torch.zeros((ncfg, 6), dtype=torch.float64, device=dev), h0=h0_t, origins=run.org_t, D=eye.clone(),
+                 vq=torch.zeros((ncfg, 9), dtype=torch.float64, device=dev), Dbinv=eye.clone(), href=h0_t.clone(),
+                 nimg=to(_cell_images(run.cells, cut)),
+                 dt=torch.full((ncfg,), dt, dtype=torch.float64, device=dev),
+                 alpha=torch.full((ncfg,), fire.alpha_start, dtype=torch.float64, device=dev),
+                 npos=torch.zeros(ncfg, dtype=torch.int32, device=dev), frozen=run.frozen,
+                 done_step=torch.full((ncfg,), -1, dtype=torch.int32, device=dev),
+                 fmax=torch.zeros(ncfg, dtype=torch.float64, device=dev), smax=torch.zeros(ncfg, dtype=torch.float64, device=dev),
+                 gcell=torch.zeros((ncfg, 9), dtype=torch.float64, device=dev), h=h0_t.clone(), T=eye.clone(),
+                 cellmove=run.cellmove, counts=run.counts_t)
+        capi.relax_cell_rebase(ncfg, row_cfg, run.org_t, run.x, A["D"], A["xt"], A["Dbinv"], stream=st)   # xt = x - origin
+        cand_cell = torch.zeros((max(run.room, 1), 9), dtype=torch.float64, device=dev)
+        e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
+        tr_dev = torch.zeros((4, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
+
+        def forces(grade):
+            ghosts.forward(run.x, stream=st)
+            capi.zero_async(run.work, stream=st)
+            ctx.compute_device_rows(0, n, False, run.x, buf.tall, run.f, eflag=3, vflag=4, grade=grade, eatom_t=run.eatom,
+                                    vatom_t=run.vatom, ev_t=run.ev, grades_t=buf.grades if grade and not cfg_mode else None,
+                                    maxg_t=run.maxg if grade else None, coeff_t=run.coeff if grade and cfg_mode else None, stream=st)
+            ghosts.reverse_finish(ctx, run.f, run.ev, eflag=3, vflag=4, stream=st)
+            nbh = grade and not cfg_mode
+            capi.batch_reduce(cf_t, vatom_t=run.vatom, grades_t=buf.grades if nbh else None, virial_t=A["virial"],
+                              cfg_grade_t=run.g_t if nbh else None, stream=st)
+            if grade and cfg_mode:
+                ctx.batch_cfg_grades(cf_t, n, run.g_t, stream=st)
+
+        def reneighbor():
+            hh = A["h"].cpu().numpy().reshape(ncfg, 3, 3)             # the cells the atoms sit in now
+            with np.errstate(all="ignore"):
+                bad = ~(np.isfinite(hh).all((1, 2)) & (_det3(hh) > 0.0))
+            hh[bad] = run.cells[bad]                                  # (such a configuration fails at its next step)
+            capi.sample_to_cell(n, row_cfg, run.org_t, run.x, stream=st)     # with the OLD origins
+            try:
+                new = capi.batch_layout(hh, cut, cut)
+            except capi.MtpError as e:
+                if e.code != -24:
+                    raise
+                raise capi.MtpError(-24, "%s: pass %d: configuration %d no longer fits the pass with its relaxed cell: %s"
+                                    % (who, npass, k0 + int(getattr(e, "nfit", 0)), e)) from e
+            org_t = to(new["origins"])
+            try:
+                rows = ghosts.build_batch(run.x, cf, hh, new["origins"], cut, stream=st)
+            except capi.MtpError as e:                                # (the capacity protocol: a shrinking cell has more images)
+                if e.code != -24 or ghosts.nall <= buf.cap or ghosts.nall >= 2 ** 31 - 1:
+                    raise
+                keep_x, keep_t = run.x[:n].clone(), buf.tall[:n].clone()
+                buf.reserve(ghosts.nall, ncfg, run.work_size(ghosts.nall), 0)
+                buf.xall[:n], buf.tall[:n] = keep_x, keep_t
+                run.x = buf.xall
+                capi.sample_to_cell(n, row_cfg, org_t, run.x, stream=st)     # (the refused build wrapped and translated already)
+                rows = ghosts.build_batch(run.x, cf, hh, new["origins"], cut, stream=st)
+            ghosts.types(buf.tall, stream=st)
+            ctx.build_neighbors_device(run.x, n, rows, cut, new["lo"], new["hi"], stream=st)
+            buf.reserve(0, ncfg, run.work_size(rows), 0)              # (rows may exceed what the work array was sized for)
+            run.layout(rows)
+            run.x_ref.copy_(run.x[:n])
+            run.cells, run.lay, run.org_t = hh, new, org_t
+            A.update(x=run.x, f=run.f, type=buf.tall, origins=org_t, href=to(hh.reshape(ncfg, 9)),
+                     nimg=to(_cell_images(hh, cut)))
+            A["T"].copy_(eye)
+            run.cellmove.zero_()
+            capi.relax_cell_rebase(ncfg, row_cfg, org_t, run.x, A["D"], A["xt"], A["Dbinv"], stream=st)
+
+        s, since = 0, 0
+        while True:
+            forces(graded(s))
+            if graded(s):
+                run.capture(s, select, brk, capture_gap)
+                capi.relax_cell_capture_cells(run.slot, run.room, A["h"], cand_cell, stream=st)
+            if trace:
+                tr_dev[3, s].copy_(_det3(A["h"].view(ncfg, 3, 3)))
+            capi.relax_cell_step(ncfg, params, s, A, last=s == steps, stream=st)
+            if trace:
+                run.energies(tr_dev[0, s])
+                tr_dev[1, s].copy_(A["fmax"])
+                tr_dev[2, s].copy_(A["smax"])
+            if s == steps:
+                break
+            ghosts.deform(row_cfg, A["T"], stream=st)
+            since += 1
+            need = since >= every
+            if s == 0 or need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
+                run.monitor(A["vt"], mass_t)
+                m = run.monitor_read.cpu().numpy()                # d2 [ncfg] | block [4] | cellmove [ncfg]
+                if m[ncfg + 1] >= nonempty:                       # nothing is running any more: this step moved nothing
+                    break
+                need = need or cell_list_stale(m[:ncfg], m[ncfg + 4:], skin)
+            if need:
+                reneighbor()
+                builds += 1
+                since = 0
+            s += 1
+        steps_done = max(steps_done, s)
+        run.energies(e_t)
+        run.synchronize(npass, k0, k1)
+        xh = run.x[:n].cpu().numpy() - np.repeat(run.lay["origins"], counts, axis=0)
+        eh, fh, dh = e_t.cpu().numpy(), run.frozen.cpu().numpy(), A["done_step"].cpu().numpy()
+        hh, wh = A["h"].cpu().numpy().reshape(ncfg, 3, 3), A["virial"].cpu().numpy()
+        dth, fmh, smh = A["dt"].cpu().numpy(), A["fmax"].cpu().numpy(), A["smax"].cpu().numpy()
+        with np.errstate(all="ignore"):
+            vol = _det3(hh)
+        for j in range(ncfg):
+            a, b = int(cf[j]), int(cf[j + 1])
+            final[k0 + j] = dict(x=xh[a:b], energy=float(eh[j]), fmax=float(fmh[j]), status=capi.RELAX_STATUS[int(fh[j])],
+                                 step=int(dh[j]), dt=float(dth[j]), cell=hh[j].copy(), virial=wh[j].copy(), volume=float(vol[j]),
+                                 enthalpy=float(eh[j]) + pressure * float(vol[j]), smax=float(smh[j]))
+        dropped += run.harvest(k0, records, candidates, cand_cell)
+        if trace:
+            tr[:, : s + 1, k0:k1] = tr_dev.cpu().numpy()[:, : s + 1]
+    out = dict(candidates=candidates, records=records, dropped=dropped, final=final, steps_done=steps_done, builds=builds)
+    if trace:
+        out["trace"] = dict(energy=tr[0, : steps_done + 1], fmax=tr[1, : steps_done + 1], smax=tr[2, : steps_done + 1],
+                            volume=tr[3, : steps_done + 1])
     return out
