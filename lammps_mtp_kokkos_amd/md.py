@@ -147,6 +147,13 @@ class DeviceNVE:
         return float(self.ev[0].item()) + 0.5 * MVV2E * float(m[1])
 
 
+def _torch_stream(dev):
+    import torch
+    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
+        capi.use_private_torch_stream(dev)
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
 def evaluate_cell(ctx, pos, cell, types=None, list_cutoff=7.0, vflag=1, grades=False, device=None):
     """One device-resident evaluation of a periodic cell of any shape and size (rows of `cell` = lattice vectors):
     ghost images (mtp_ghosts_build_cell), the full list (mtp_build_neighbors_device), the force call and the fold of the
@@ -156,9 +163,7 @@ def evaluate_cell(ctx, pos, cell, types=None, list_cutoff=7.0, vflag=1, grades=F
     neighbourhood mode), grades [n] and max_grade."""
     import torch
     dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _torch_stream(dev)
     pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
     cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
     n = len(pos)
@@ -293,9 +298,7 @@ def _cell_passes(ctx, configs, list_cutoff, vflag, grades, max_atoms_per_pass, d
     pass's candidate vectors"""
     import torch
     dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _torch_stream(dev)
     cut = float(list_cutoff)
     cfg_mode = bool(grades) and bool(ctx.pot.info.configuration_mode)
     C = int(ctx.pot.info.coeff_count)
@@ -435,8 +438,7 @@ def select_cells(ctx, configs, threshold=1.1, out_path=None, list_cutoff=7.0, ma
     or None where the original column was kept; swaps: the log [(pool row, slot, pivot)])."""
     import torch
     dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__: the pool is filled on this stream
-        capi.use_private_torch_stream(dev)
+    _torch_stream(dev)                                       # the pool is filled on this stream
     info = ctx.pot.info
     if not info.has_selection:
         raise capi.MtpError(-23, "select_cells: the potential was loaded without its selection state")
@@ -485,9 +487,7 @@ def _design_passes(ctx, configs, list_cutoff, virial, max_atoms_per_pass, device
     Returns the plan."""
     import torch
     dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _torch_stream(dev)
     cut = float(list_cutoff)
     info = ctx.pot.info
     cols = int(info.species_count + info.alpha_scalar_count)
@@ -682,13 +682,6 @@ def solve_linear(energy, force, virial, natoms, labels, theta0, weights=(1.0, 0.
 
 
 # ---- the same fit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -----------------------
-def _torch_stream(dev):
-    import torch
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def design_fingerprint(ctx, list_cutoff=7.0):
     """sha256 over everything the design matrix of a configuration depends on: the context's CURRENT radial coefficients,
     scaling, the cutoffs, the species count, the alpha tables and the list cutoff.  The linear coefficients do not enter:
@@ -919,9 +912,7 @@ def loss_cells(ctx, configs, labels, theta=None, weights=(1.0, 0.01, 0.001), gra
     if len(labels) != len(configs):
         raise ValueError("loss_cells: %d labels for %d configurations" % (len(labels), len(configs)))
     dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _torch_stream(dev)
     cut = float(list_cutoff)
     info = ctx.pot.info
     C = int(info.species_count ** 2 * info.radial_func_count * info.radial_basis_size + info.species_count + info.alpha_scalar_count)
@@ -1081,43 +1072,132 @@ def maxwell_boltzmann(items, mass_of_type, temperature, seed, keys):
     return out
 
 
+class _RunSetup:
+    """What sample_cells, relax_cells and relax_cells_vc (`who`) share around their passes.  The prologue: the grade steps (and
+    the refusal of thresholds without selection state) before anything touches the device, then the stream, the plan of the
+    passes, ghosts, buffers and masses.  The harness of one pass (each_pass).  And what the passes add up to: candidates,
+    records, final, dropped, steps_done, builds and the host trace [len(trace_names), steps + 1, ncfg]."""
+
+    def __init__(self, who, ctx, items, all_cells, natoms, mass_of_type, steps, grade_every, thresholds_named, select, brk,
+                 capture_gap, max_candidates, list_cutoff, every, check_every, max_atoms_per_pass, device, trace_names):
+        info = ctx.pot.info
+        self.grade_every = int(grade_every or 0)
+        if not info.has_selection:
+            if thresholds_named:
+                raise capi.MtpError(-23, who + ": thresholds need a potential loaded with its selection state")
+            self.grade_every = 0
+        import torch
+        self.torch, self.dev = torch, device or torch.device("cuda:0")
+        self.st = _torch_stream(self.dev)
+        self.who, self.ctx, self.items, self.all_cells, self.natoms = who, ctx, items, all_cells, natoms
+        self.steps, self.cut = int(steps), float(list_cutoff)
+        self.every, self.check_every = int(every), int(check_every or 0)
+        self.capture_args, self.max_candidates = (select, brk, int(capture_gap)), max_candidates
+        self.skin = self.cut - float(info.max_cutoff)
+        self.cfg_mode = bool(self.grade_every) and bool(info.configuration_mode)
+        self.plan, self.volume, self.max_rows = plan_cell_passes(all_cells, natoms, self.cut, max_atoms_per_pass)
+        self.ghosts = capi.Ghosts(self.dev.index or 0)
+        self.buf = _BatchBuffers(torch, self.dev)
+        self.mass_t, self.inv_mass_t = self.to(mass_of_type), self.to(1.0 / mass_of_type)
+        self.candidates, self.records, self.final = [], [], [None] * len(items)
+        self.dropped = self.steps_done = self.npass = self.builds = 0
+        self.trace_names = tuple(trace_names)
+        self.trace = np.zeros((len(self.trace_names), self.steps + 1, len(items))) if self.trace_names else None
+
+    def to(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def zeros(self, *shape):
+        return self.torch.zeros(shape, dtype=self.torch.float64, device=self.dev)
+
+    def graded(self, step):
+        return bool(self.grade_every) and step % self.grade_every == 0
+
+    def each_pass(self, body, empty_final, run_type, final_monitor=False):
+        """The passes, one complete run each.  A pass without an atom only fills final[k] = empty_final(k).  Any other gets a
+        run (`run_type`: the first ghost and list build; run.trace [len(trace_names), steps + 1, ncfg] on the device) and the
+        driver's body(run) -> (s: the last step made, final), then the final energies (and, for the kinetic energy, the monitor),
+        the synchronise that names the pass, x without the slot origins, final[k0:k1] = final(x, energies) -- one dict per
+        configuration, rows run.rows[j] of x --, the harvest of what was captured and the scatter of the trace."""
+        for k0, k1, lay in self.plan:
+            self.npass += 1
+            counts = self.natoms[k0:k1]
+            if int(counts.sum()) == 0:
+                for k in range(k0, k1):
+                    self.final[k] = empty_final(k)
+                continue
+            run = run_type(self, k0, k1, lay)
+            self.builds += 1
+            e_t = self.zeros(k1 - k0)
+            run.trace = self.zeros(len(self.trace_names), self.steps + 1, k1 - k0) if self.trace_names else None
+            s, final = body(run)
+            self.steps_done = max(self.steps_done, s)
+            run.energies(e_t)
+            if final_monitor:
+                run.monitor()
+            run.synchronize(self.npass, k0, k1)
+            xh = run.x[:run.n].cpu().numpy() - np.repeat(run.lay["origins"], counts, axis=0)
+            self.final[k0:k1] = final(xh, e_t.cpu().numpy())
+            self.dropped += run.harvest(k0, self.records, self.candidates)
+            if self.trace_names:
+                self.trace[:, : s + 1, k0:k1] = run.trace.cpu().numpy()[:, : s + 1]
+
+    def result(self, **more):
+        """the returned dict (`more`: the driver's own keys, after `dropped`)"""
+        out = dict(candidates=self.candidates, records=self.records, dropped=self.dropped, **more, final=self.final,
+                   steps_done=self.steps_done, builds=self.builds)
+        if self.trace_names:
+            out["trace"] = {name: self.trace[i, : self.steps_done + 1] for i, name in enumerate(self.trace_names)}
+        return out
+
+
 class _CellRun:
     """One pass of sample_cells / relax_cells -- a batch of cells that stays on the device for a whole run: the first ghost and
     list build, the per-configuration arrays every such run keeps (frozen, the capture state and its candidate buffer, the
     monitor block) and the launches around the integrator or minimiser: the force call with the ghost fold, the capture, the
-    monitor, the re-neighbouring in slot coordinates, the energies, and the harvest of what was captured."""
+    monitor and its one read, the re-neighbouring in slot coordinates, the energies, and the harvest of what was captured.
+    The driver sets `v`, the velocities the monitor looks at.  _DeformingCellRun is the same for cells that change."""
 
-    def __init__(self, ctx, ghosts, buf, items, cells, counts, lay, cut, max_rows, cfg_mode, room, st, vatom=False):
-        torch, dev = buf.torch, buf.dev
-        self.per_row = 10 if vatom else 4                     # (vatom: relax_cells_vc, the work layout of evaluate_cells)
-        self.ctx, self.ghosts, self.buf, self.items, self.cells, self.counts = ctx, ghosts, buf, items, cells, counts
-        self.lay, self.cut, self.cfg_mode, self.room, self.st = lay, cut, cfg_mode, room, st
-        self.C = C = int(ctx.pot.info.coeff_count)
-        self.ncfg = ncfg = len(counts)
-        self.cf = cf = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    vflag = 0                                                 # 4: per-atom virials (the work layout of evaluate_cells)
+
+    def __init__(self, setup, k0, k1, lay):
+        torch, dev, to = setup.torch, setup.dev, setup.to
+        self.per_row = 10 if self.vflag else 4
+        self.setup, self.k0, self.k1, self.lay = setup, k0, k1, lay
+        self.ctx, self.ghosts, self.buf = setup.ctx, setup.ghosts, setup.buf
+        self.cut, self.cfg_mode, self.st = setup.cut, setup.cfg_mode, setup.st
+        self.items, self.cells, self.counts = setup.items[k0:k1], setup.all_cells[k0:k1], setup.natoms[k0:k1]
+        self.room = max(setup.max_candidates - len(setup.records), 0)     # what earlier passes left of the candidate buffer
+        self.C = C = int(self.ctx.pot.info.coeff_count)
+        self.ncfg = ncfg = k1 - k0
+        self.nonempty = int((self.counts > 0).sum())
+        self.cf = cf = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)
         self.n = n = int(cf[-1])
-        self.stride = int(counts.max())
-        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self.rows = [(int(cf[j]), int(cf[j + 1])) for j in range(ncfg)]
+        self.stride = int(self.counts.max())
         self.cf_t, self.org_t = to(cf), to(lay["origins"])
         na = lambda rows: rows + (rows & 1)
         self.work_size = lambda rows: self.per_row * na(rows) + 10 + C + (C & 1)
-        nall = _pass_ghosts_and_list(ctx, ghosts, buf, items, cf, cells, lay, cut, n + max_rows,
-                                     lambda rows, first: buf.reserve(rows, ncfg, self.work_size(rows), 0), st)
+        buf = self.buf
+        nall = _pass_ghosts_and_list(self.ctx, self.ghosts, buf, self.items, cf, self.cells, lay, self.cut,
+                                     n + int(setup.max_rows[k0:k1].sum()),
+                                     lambda rows, first: buf.reserve(rows, ncfg, self.work_size(rows), 0), self.st)
         self.x = buf.xall
         self.row_cfg = torch.empty(n, dtype=torch.int32, device=dev)
-        capi.sample_row_map(self.cf_t, self.row_cfg, stream=st)
+        capi.sample_row_map(self.cf_t, self.row_cfg, stream=self.st)
         self.x_ref = self.x[:n].clone()
         self.frozen = torch.zeros(ncfg, dtype=torch.int32, device=dev)
         self.last_capture = torch.full((ncfg,), -2 ** 30, dtype=torch.int32, device=dev)
         self.slot = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
         self.counts_t = torch.zeros(3, dtype=torch.int32, device=dev)    # captured, dropped, frozen
         self.g_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
-        mon = torch.zeros((3 if vatom else 2) * ncfg + 4, dtype=torch.float64, device=dev)
+        mon = torch.zeros((3 if self.vflag else 2) * ncfg + 4, dtype=torch.float64, device=dev)
         self.mv2, self.d2, self.block = mon[:ncfg], mon[ncfg: 2 * ncfg], mon[2 * ncfg: 2 * ncfg + 4]
-        self.cellmove, self.monitor_read = mon[2 * ncfg + 4:], mon[ncfg:]     # (vatom: d2 | block | cellmove is ONE read)
-        self.cand_x = torch.zeros((max(room, 1), self.stride, 3), dtype=torch.float64, device=dev)
-        self.rec = torch.zeros((max(room, 1), 2), dtype=torch.int32, device=dev)
-        self.rec_grade = torch.zeros(max(room, 1), dtype=torch.float64, device=dev)
+        self.cellmove, self.monitor_read = mon[2 * ncfg + 4:], mon[ncfg:]     # (vflag: d2 | block | cellmove is ONE read)
+        self.cand_x = torch.zeros((max(self.room, 1), self.stride, 3), dtype=torch.float64, device=dev)
+        self.cand_cell = None                                 # (fixed cells: a candidate's cell is the one given)
+        self.rec = torch.zeros((max(self.room, 1), 2), dtype=torch.int32, device=dev)
+        self.rec_grade = torch.zeros(max(self.room, 1), dtype=torch.float64, device=dev)
         self.layout(nall)
 
     def layout(self, rows):
@@ -1129,31 +1209,50 @@ class _CellRun:
         self.maxg, self.coeff = w[p * m + 8: p * m + 9], w[p * m + 10: p * m + 10 + C]
 
     def forces(self, grade):
-        ctx, buf, st, n, cfg_mode = self.ctx, self.buf, self.st, self.n, self.cfg_mode
+        ctx, buf, st, n, vf = self.ctx, self.buf, self.st, self.n, self.vflag
+        nbh, cfg = grade and not self.cfg_mode, grade and self.cfg_mode
         self.ghosts.forward(self.x, stream=st)
         capi.zero_async(self.work, stream=st)
-        ctx.compute_device_rows(0, n, False, self.x, buf.tall, self.f, eflag=3, vflag=0, grade=grade, eatom_t=self.eatom, ev_t=self.ev,
-                                grades_t=buf.grades if grade and not cfg_mode else None, maxg_t=self.maxg if grade else None,
-                                coeff_t=self.coeff if grade and cfg_mode else None, stream=st)
-        self.ghosts.reverse_finish(ctx, self.f, self.ev, eflag=3, vflag=0, stream=st)
-        if grade and cfg_mode:
-            ctx.batch_cfg_grades(self.cf_t, n, self.g_t, stream=st)
-        elif grade:
+        ctx.compute_device_rows(0, n, False, self.x, buf.tall, self.f, eflag=3, vflag=vf, grade=grade, eatom_t=self.eatom,
+                                vatom_t=self.vatom if vf else None, ev_t=self.ev, grades_t=buf.grades if nbh else None,
+                                maxg_t=self.maxg if grade else None, coeff_t=self.coeff if cfg else None, stream=st)
+        self.ghosts.reverse_finish(ctx, self.f, self.ev, eflag=3, vflag=vf, stream=st)
+        if vf:                                                # the virial per configuration and, in the SAME launch, the grades
+            capi.batch_reduce(self.cf_t, vatom_t=self.vatom, grades_t=buf.grades if nbh else None, virial_t=self.virial,
+                              cfg_grade_t=self.g_t if nbh else None, stream=st)
+        elif nbh:
             capi.batch_reduce(self.cf_t, grades_t=buf.grades, cfg_grade_t=self.g_t, stream=st)
+        if cfg:
+            ctx.batch_cfg_grades(self.cf_t, n, self.g_t, stream=st)
 
-    def capture(self, step, select, brk, gap):
+    def capture(self, step):
+        select, brk, gap = self.setup.capture_args
         capi.sample_capture(self.cf_t, self.n, self.row_cfg, self.g_t, step, select, brk, gap, self.x, self.org_t, self.frozen,
                             self.last_capture, self.slot, self.room, self.stride, self.cand_x, self.rec, self.rec_grade,
                             self.counts_t, stream=self.st)
 
-    def monitor(self, v, mass_t, mv2_t=None):
-        capi.sample_monitor(self.cf_t, self.frozen, self.x, self.x_ref, v, self.buf.tall, mass_t, self.counts_t,
+    def moved(self):
+        """after the positions were moved (fixed cells: nothing follows)"""
+
+    def monitor(self, mv2_t=None):
+        capi.sample_monitor(self.cf_t, self.frozen, self.x, self.x_ref, self.v, self.buf.tall, self.setup.mass_t, self.counts_t,
                             self.mv2 if mv2_t is None else mv2_t, self.d2, self.block, stream=self.st)
+
+    def read(self):
+        """the monitor and the one host read between rebuilds: (nothing is running any more, the lists are stale: an atom of a
+        running configuration moved more than half the skin)"""
+        self.monitor()
+        b = self.block.cpu().numpy()
+        return b[1] >= self.nonempty, b[0] > (0.5 * self.setup.skin) ** 2
 
     def energies(self, out_t):
         capi.batch_reduce(self.cf_t, eatom_t=self.eatom, energy_t=out_t, stream=self.st)
 
     def reneighbor(self):
+        self.rebuild()
+        self.setup.builds += 1
+
+    def rebuild(self):
         x, n, lay, st = self.x, self.n, self.lay, self.st
         capi.sample_to_cell(n, self.row_cfg, self.org_t, x, stream=st)
         rows = self.ghosts.build_batch(x, self.cf, self.cells, lay["origins"], self.cut, stream=st)
@@ -1168,19 +1267,121 @@ class _CellRun:
         except capi.MtpError as e:
             raise capi.MtpError(e.code, "pass %d (configurations %d to %d): %s" % (npass, k0, k1 - 1, e)) from e
 
-    def harvest(self, k0, records, candidates, cand_cell=None):
-        """appends this pass's records (configuration numbers from k0) and candidates; returns the number dropped.  cand_cell
+    def harvest(self, k0, records, candidates):
+        """appends this pass's records (configuration numbers from k0) and candidates; returns the number dropped.  self.cand_cell
         [slots, 9]: the cell every candidate was captured in, where cells change during the run"""
         ch = self.counts_t.cpu().numpy()
         ncap = int(ch[0])
         rh, gh, snap = self.rec[:ncap].cpu().numpy(), self.rec_grade[:ncap].cpu().numpy(), self.cand_x[:ncap].cpu().numpy()
-        ch9 = None if cand_cell is None else cand_cell[:ncap].cpu().numpy().reshape(ncap, 3, 3)
+        ch9 = None if self.cand_cell is None else self.cand_cell[:ncap].cpu().numpy().reshape(ncap, 3, 3)
         for j in range(ncap):
             k = int(rh[j, 0])
             records.append((k0 + k, int(rh[j, 1]), float(gh[j])))
             cell = self.cells[k] if ch9 is None else ch9[j]
             candidates.append((snap[j, : int(self.counts[k])].copy(), cell.copy(), self.items[k][1].copy()))
         return int(ch[1])
+
+
+class _DeformingCellRun(_CellRun):
+    """_CellRun for cells that change during the run (relax_cells_vc; a batched NPT would sit on the same run): forces with
+    per-atom virials and the virial per configuration, the geometry h = h0 . D, x = origin + xt . D in the arrays `A`
+    (mtp_relax_cell_arrays; the driver adds its minimiser's state and sets v = A["vt"]), ghosts that follow the cell after a
+    move, the stale rule with the cell's own movement in it, candidates with the cell of their graded step, and a rebuild that
+    lays the pass out again for the cells as they are."""
+
+    vflag = 4
+
+    def __init__(self, setup, k0, k1, lay):
+        super().__init__(setup, k0, k1, lay)
+        to, zeros, ncfg, n = setup.to, setup.zeros, self.ncfg, self.n
+        self.eye = eye = setup.torch.eye(3, dtype=setup.torch.float64, device=setup.dev).reshape(1, 9).repeat(ncfg, 1)
+        h0_t = to(self.cells.reshape(ncfg, 9))
+        self.virial = zeros(ncfg, 6)
+        self.A = A = dict(cfg_first=self.cf_t, x=self.x, xt=zeros(n, 3), f=self.f, type=self.buf.tall, inv_mass=setup.inv_mass_t,
+                          virial=self.virial, h0=h0_t, origins=self.org_t, D=eye.clone(), Dbinv=eye.clone(), href=h0_t.clone(),
+                          nimg=to(_cell_images(self.cells, self.cut)), frozen=self.frozen, h=h0_t.clone(), T=eye.clone(),
+                          cellmove=self.cellmove, counts=self.counts_t)
+        capi.relax_cell_rebase(ncfg, self.row_cfg, self.org_t, self.x, A["D"], A["xt"], A["Dbinv"], stream=self.st)   # xt = x - origin
+        self.cand_cell = zeros(max(self.room, 1), 9)
+
+    def capture(self, step):
+        super().capture(step)
+        capi.relax_cell_capture_cells(self.slot, self.room, self.A["h"], self.cand_cell, stream=self.st)
+
+    def moved(self):
+        self.ghosts.deform(self.row_cfg, self.A["T"], stream=self.st)
+
+    def read(self):
+        self.monitor()
+        ncfg = self.ncfg
+        m = self.monitor_read.cpu().numpy()                   # d2 [ncfg] | block [4] | cellmove [ncfg]
+        return m[ncfg + 1] >= self.nonempty, cell_list_stale(m[:ncfg], m[ncfg + 4:], self.setup.skin)
+
+    def rebuild(self):
+        A, buf, ghosts, st, n, ncfg, cut, to = self.A, self.buf, self.ghosts, self.st, self.n, self.ncfg, self.cut, self.setup.to
+        hh = A["h"].cpu().numpy().reshape(ncfg, 3, 3)                 # the cells the atoms sit in now
+        with np.errstate(all="ignore"):
+            bad = ~(np.isfinite(hh).all((1, 2)) & (_det3(hh) > 0.0))
+        hh[bad] = self.cells[bad]                                     # (such a configuration fails at its next step)
+        capi.sample_to_cell(n, self.row_cfg, self.org_t, self.x, stream=st)     # with the OLD origins
+        try:
+            new = capi.batch_layout(hh, cut, cut)
+        except capi.MtpError as e:
+            if e.code != -24:
+                raise
+            raise capi.MtpError(-24, "%s: pass %d: configuration %d no longer fits the pass with its relaxed cell: %s"
+                                % (self.setup.who, self.setup.npass, self.k0 + int(getattr(e, "nfit", 0)), e)) from e
+        org_t = to(new["origins"])
+        try:
+            rows = ghosts.build_batch(self.x, self.cf, hh, new["origins"], cut, stream=st)
+        except capi.MtpError as e:                                    # (the capacity protocol: a shrinking cell has more images)
+            if e.code != -24 or ghosts.nall <= buf.cap or ghosts.nall >= 2 ** 31 - 1:
+                raise
+            keep_x, keep_t = self.x[:n].clone(), buf.tall[:n].clone()
+            buf.reserve(ghosts.nall, ncfg, self.work_size(ghosts.nall), 0)
+            buf.xall[:n], buf.tall[:n] = keep_x, keep_t
+            self.x = buf.xall
+            capi.sample_to_cell(n, self.row_cfg, org_t, self.x, stream=st)     # (the refused build wrapped and translated already)
+            rows = ghosts.build_batch(self.x, self.cf, hh, new["origins"], cut, stream=st)
+        ghosts.types(buf.tall, stream=st)
+        self.ctx.build_neighbors_device(self.x, n, rows, cut, new["lo"], new["hi"], stream=st)
+        buf.reserve(0, ncfg, self.work_size(rows), 0)                 # (rows may exceed what the work array was sized for)
+        self.layout(rows)
+        self.x_ref.copy_(self.x[:n])
+        self.cells, self.lay, self.org_t = hh, new, org_t
+        A.update(x=self.x, f=self.f, type=buf.tall, origins=org_t, href=to(hh.reshape(ncfg, 9)), nimg=to(_cell_images(hh, cut)))
+        A["T"].copy_(self.eye)
+        self.cellmove.zero_()
+        capi.relax_cell_rebase(ncfg, self.row_cfg, org_t, self.x, A["D"], A["xt"], A["Dbinv"], stream=st)
+
+
+def _minimise_pass(run, steps, graded, step, every, check_every):
+    """The step loop relax_cells and relax_cells_vc share, s = 0 ... steps: forces (graded on a grade step) -> on a grade step
+    the capture, BEFORE the minimiser -> step(s, last): the driver's one minimiser launch (and its trace) -> what follows a
+    move -> every `check_every` steps since the last rebuild, after step 0 and at a rebuild the one read: (nothing runs any
+    more, the lists are stale) -> the rebuild.  After step `steps` no move is made.  Returns the last step made."""
+    s, since = 0, 0
+    while True:
+        grade = graded(s)
+        run.forces(grade)
+        if grade:
+            run.capture(s)
+        step(s, s == steps)
+        if s == steps:
+            break
+        run.moved()
+        since += 1
+        need = since >= every
+        if s == 0 or need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
+            done, stale = run.read()
+            if done:                                          # nothing is running any more: this step moved nothing
+                break
+            need = need or stale
+        if need:
+            run.reneighbor()
+            since = 0
+        s += 1
+    return s
 
 
 def _run_arguments(who, items, masses, threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every,
@@ -1282,81 +1483,39 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
     (items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities,
      max_candidates) = _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break,
                                          capture_gap, max_candidates, velocities, grade_every, every, check_every)
-    info = ctx.pot.info
-    grade_every = int(grade_every or 0)
-    if not info.has_selection:
-        if threshold_select is not None or threshold_break is not None:
-            raise capi.MtpError(-23, "sample_cells: thresholds need a potential loaded with its selection state")
-        grade_every = 0
-    import torch
-    dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    steps, dt, cut, seed = int(steps), float(dt), float(list_cutoff), int(seed) & (2 ** 64 - 1)
-    every, check_every, capture_gap = int(every), int(check_every or 0), int(capture_gap)
+    setup = _RunSetup("sample_cells", ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
+                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
+                      list_cutoff, every, check_every, max_atoms_per_pass, device, ("energy", "kinetic") if trace else ())
+    to, st, buf, mass_t, inv_mass_t, graded = setup.to, setup.st, setup.buf, setup.mass_t, setup.inv_mass_t, setup.graded
+    steps, every, check_every = setup.steps, setup.every, setup.check_every
+    dt, seed = float(dt), int(seed) & (2 ** 64 - 1)
     t_damp = 0.0 if t_damp is None or not np.isfinite(float(t_damp)) or float(t_damp) <= 0.0 else float(t_damp)
     dtf = 0.5 * dt * FTM2V
-    half_skin2 = (0.5 * (cut - float(info.max_cutoff))) ** 2
-    cfg_mode = bool(grade_every) and bool(info.configuration_mode)
-    ncfg_all = len(items)
     if velocities is None:
         velocities = maxwell_boltzmann(items, mass_of_type, temperature, seed, keys)
-    passes, volume, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
-    ghosts = capi.Ghosts(dev.index or 0)
-    buf = _BatchBuffers(torch, dev)
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    mass_t, inv_mass_t = to(mass_of_type), to(1.0 / mass_of_type)
-    candidates, records, final = [], [], [None] * ncfg_all
-    frozen_all = np.zeros(ncfg_all, dtype=bool)
-    dropped, steps_done, npass, builds = 0, 0, 0, [0]
-    tr_e = np.zeros((steps + 1, ncfg_all)) if trace else None
-    tr_k = np.zeros((steps + 1, ncfg_all)) if trace else None
-    for k0, k1, lay in passes:
-        npass += 1
-        ncfg = k1 - k0
-        counts = natoms[k0:k1]
-        cf = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-        n = int(cf[-1])
-        if n == 0:
-            for k in range(k0, k1):
-                final[k] = dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0)
-            continue
-        nonempty = int((counts > 0).sum())
-        run = _CellRun(ctx, ghosts, buf, items[k0:k1], all_cells[k0:k1], counts, lay, cut, int(max_rows[k0:k1].sum()), cfg_mode,
-                       max(max_candidates - len(records), 0), st)
-        builds[0] += 1
-        cf_t, row_cfg, x, frozen, block, mv2 = run.cf_t, run.row_cfg, run.x, run.frozen, run.block, run.mv2
-        v = to(np.concatenate(velocities[k0:k1]))
+    frozen_all = np.zeros(len(items), dtype=bool)
+
+    def one_pass(run):
+        k0, k1, n, cf_t, row_cfg, x, frozen = run.k0, run.k1, run.n, run.cf_t, run.row_cfg, run.x, run.frozen
+        run.v = v = to(np.concatenate(velocities[k0:k1]))
         temp_t = to(temperature[k0:k1])
         key_t = to(keys[k0:k1].view(np.int64))
-        e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
-        tr_dev = torch.zeros((2, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
-        forces = run.forces
-        capture = lambda step: run.capture(step, select, brk, capture_gap)
-        monitor = lambda mv2_t=None: run.monitor(v, mass_t, mv2_t)
 
         def second_half(step, kick):
             capi.sample_final(n, row_cfg, cf_t, frozen, v, run.f, buf.tall, mass_t, inv_mass_t, temp_t, key_t, seed, step,
                               kick, dt, t_damp, stream=st)
 
         def record(step):
-            run.energies(tr_dev[0, step])
-            monitor(tr_dev[1, step])
+            run.energies(run.trace[0, step])
+            run.monitor(run.trace[1, step])
 
-        def reneighbor():
-            run.reneighbor()
-            builds[0] += 1
-
-        graded = lambda step: bool(grade_every) and step % grade_every == 0
-        forces(graded(0))
+        run.forces(graded(0))
         if t_damp > 0.0:
             second_half(0, 0.0)                               # (fix langevin's setup: the thermostat force of step 0, no kick)
         stop = False
         if graded(0):
-            capture(0)
-            monitor()
-            stop = float(block.cpu()[1]) >= nonempty
+            run.capture(0)
+            stop = run.read()[0]
         if trace:
             record(0)
         s, since = 0, 0
@@ -1366,41 +1525,36 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
             since += 1
             need = since >= every
             if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
-                monitor()
-                b = block.cpu().numpy()
-                if b[1] >= nonempty:                          # everything is frozen: this first half wrote nothing
+                done, stale = run.read()
+                if done:                                      # everything is frozen: this first half wrote nothing
                     s -= 1
                     break
-                need = need or b[0] > half_skin2
+                need = need or stale
             if need:
-                reneighbor()
+                run.reneighbor()
                 since = 0
-            forces(graded(s))
+            grade = graded(s)
+            run.forces(grade)
             second_half(s, dtf)
-            if graded(s):
-                capture(s)
+            if grade:
+                run.capture(s)
             if trace:
                 record(s)
-        steps_done = max(steps_done, s)
-        run.energies(e_t)
-        monitor()
-        run.synchronize(npass, k0, k1)
-        xh = x[:n].cpu().numpy() - np.repeat(lay["origins"], counts, axis=0)
-        vh, eh, mh, fh = v.cpu().numpy(), e_t.cpu().numpy(), mv2.cpu().numpy(), frozen.cpu().numpy()
-        frozen_all[k0:k1] = fh != 0
-        for j in range(ncfg):
-            a, b = int(cf[j]), int(cf[j + 1])
-            final[k0 + j] = dict(x=xh[a:b], v=vh[a:b], energy=float(eh[j]),
-                                 temperature=float(mh[j]) * MVV2E / (3.0 * (b - a) * KB) if b > a else 0.0)
-        dropped += run.harvest(k0, records, candidates)
-        if trace:
-            th = tr_dev.cpu().numpy()
-            tr_e[: s + 1, k0:k1] = th[0, : s + 1]
-            tr_k[: s + 1, k0:k1] = 0.5 * MVV2E * th[1, : s + 1]
-    out = dict(candidates=candidates, records=records, dropped=dropped, frozen=frozen_all, final=final, steps_done=steps_done,
-               builds=builds[0])
+
+        def final(xh, eh):                                    # (the harness ran the monitor once more: sum m v^2 at the end)
+            vh, mh = v.cpu().numpy(), run.mv2.cpu().numpy()
+            frozen_all[k0:k1] = frozen.cpu().numpy() != 0
+            return [dict(x=xh[a:b], v=vh[a:b], energy=float(eh[j]),
+                         temperature=float(mh[j]) * MVV2E / (3.0 * (b - a) * KB) if b > a else 0.0)
+                    for j, (a, b) in enumerate(run.rows)]
+
+        return s, final
+
+    setup.each_pass(one_pass, lambda k: dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0), _CellRun,
+                    final_monitor=True)
+    out = setup.result(frozen=frozen_all)
     if trace:
-        out["trace"] = dict(energy=tr_e[: steps_done + 1], kinetic=tr_k[: steps_done + 1])
+        out["trace"]["kinetic"] = 0.5 * MVV2E * out["trace"]["kinetic"]
     return out
 
 
@@ -1461,97 +1615,40 @@ def relax_cells(ctx, configs, steps, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, 
     (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, params,
      dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
                             threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every)
-    info = ctx.pot.info
-    grade_every = int(grade_every or 0)
-    if not info.has_selection:
-        if threshold_select is not None or threshold_break is not None:
-            raise capi.MtpError(-23, "relax_cells: thresholds need a potential loaded with its selection state")
-        grade_every = 0
-    import torch
-    dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    steps, cut = int(steps), float(list_cutoff)
-    every, check_every, capture_gap = int(every), int(check_every or 0), int(capture_gap)
-    half_skin2 = (0.5 * (cut - float(info.max_cutoff))) ** 2
-    cfg_mode = bool(grade_every) and bool(info.configuration_mode)
-    ncfg_all = len(items)
-    passes, volume, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
-    ghosts = capi.Ghosts(dev.index or 0)
-    buf = _BatchBuffers(torch, dev)
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    mass_t, inv_mass_t = to(mass_of_type), to(1.0 / mass_of_type)
-    candidates, records, final = [], [], [None] * ncfg_all
-    dropped, steps_done, npass, builds = 0, 0, 0, 0
-    tr_e = np.zeros((steps + 1, ncfg_all)) if trace else None
-    tr_f = np.zeros((steps + 1, ncfg_all)) if trace else None
-    graded = lambda step: bool(grade_every) and step % grade_every == 0
-    for k0, k1, lay in passes:
-        npass += 1
-        ncfg = k1 - k0
-        counts = natoms[k0:k1]
-        if int(counts.sum()) == 0:
-            for k in range(k0, k1):
-                final[k] = dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt)
-            continue
-        nonempty = int((counts > 0).sum())
-        run = _CellRun(ctx, ghosts, buf, items[k0:k1], all_cells[k0:k1], counts, lay, cut, int(max_rows[k0:k1].sum()), cfg_mode,
-                       max(max_candidates - len(records), 0), st)
-        builds += 1
-        n, cf = run.n, run.cf
-        v = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        state = torch.zeros((3, ncfg), dtype=torch.float64, device=dev)
+    setup = _RunSetup("relax_cells", ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
+                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
+                      list_cutoff, every, check_every, max_atoms_per_pass, device, ("energy", "fmax") if trace else ())
+    torch, dev, st, buf = setup.torch, setup.dev, setup.st, setup.buf
+
+    def one_pass(run):
+        ncfg = run.ncfg
+        run.v = v = setup.zeros(run.n, 3)
+        state = setup.zeros(3, ncfg)
         dt_t, alpha_t, fmax_t = state[0], state[1], state[2]
         dt_t.fill_(dt)
         alpha_t.fill_(params.alpha_start)
         npos_t = torch.zeros(ncfg, dtype=torch.int32, device=dev)
         done_t = torch.full((ncfg,), -1, dtype=torch.int32, device=dev)
-        e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
-        tr_dev = torch.zeros((2, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
-        s, since = 0, 0
-        while True:
-            run.forces(graded(s))
-            if graded(s):
-                run.capture(s, select, brk, capture_gap)
-            capi.relax_step(run.cf_t, params, s, run.x, v, run.f, buf.tall, inv_mass_t, dt_t, alpha_t, npos_t, run.frozen, done_t,
-                            fmax_t, run.counts_t, last=s == steps, stream=st)
+
+        def step(s, last):
+            capi.relax_step(run.cf_t, params, s, run.x, v, run.f, buf.tall, setup.inv_mass_t, dt_t, alpha_t, npos_t, run.frozen,
+                            done_t, fmax_t, run.counts_t, last=last, stream=st)
             if trace:
-                run.energies(tr_dev[0, s])
-                tr_dev[1, s].copy_(fmax_t)
-            if s == steps:
-                break
-            since += 1
-            need = since >= every
-            if s == 0 or need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
-                run.monitor(v, mass_t)
-                b = run.block.cpu().numpy()
-                if b[1] >= nonempty:                          # nothing is running any more: this step moved nothing
-                    break
-                need = need or b[0] > half_skin2
-            if need:
-                run.reneighbor()
-                builds += 1
-                since = 0
-            s += 1
-        steps_done = max(steps_done, s)
-        run.energies(e_t)
-        run.synchronize(npass, k0, k1)
-        xh = run.x[:n].cpu().numpy() - np.repeat(lay["origins"], counts, axis=0)
-        eh, sh, fh, dh = e_t.cpu().numpy(), state.cpu().numpy(), run.frozen.cpu().numpy(), done_t.cpu().numpy()
-        for j in range(ncfg):
-            a, b = int(cf[j]), int(cf[j + 1])
-            final[k0 + j] = dict(x=xh[a:b], energy=float(eh[j]), fmax=float(sh[2, j]), status=capi.RELAX_STATUS[int(fh[j])],
-                                 step=int(dh[j]), dt=float(sh[0, j]))
-        dropped += run.harvest(k0, records, candidates)
-        if trace:
-            th = tr_dev.cpu().numpy()
-            tr_e[: s + 1, k0:k1] = th[0, : s + 1]
-            tr_f[: s + 1, k0:k1] = th[1, : s + 1]
-    out = dict(candidates=candidates, records=records, dropped=dropped, final=final, steps_done=steps_done, builds=builds)
-    if trace:
-        out["trace"] = dict(energy=tr_e[: steps_done + 1], fmax=tr_f[: steps_done + 1])
-    return out
+                run.energies(run.trace[0, s])
+                run.trace[1, s].copy_(fmax_t)
+
+        s = _minimise_pass(run, setup.steps, setup.graded, step, setup.every, setup.check_every)
+
+        def final(xh, eh):
+            sh, fh, dh = state.cpu().numpy(), run.frozen.cpu().numpy(), done_t.cpu().numpy()
+            return [dict(x=xh[a:b], energy=float(eh[j]), fmax=float(sh[2, j]), status=capi.RELAX_STATUS[int(fh[j])],
+                         step=int(dh[j]), dt=float(sh[0, j])) for j, (a, b) in enumerate(run.rows)]
+
+        return s, final
+
+    setup.each_pass(one_pass, lambda k: dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt),
+                    _CellRun)
+    return setup.result()
 
 
 def cell_list_stale(d2, cellmove, skin):
@@ -1639,163 +1736,47 @@ def relax_cells_vc(ctx, configs, steps, pressure=0.0, stol=1e-4, cell_mask=(1, 1
     stol, pressure, cell_factor, cell_mass, mask, per_atom = _relax_vc_arguments(natoms, mass_of_type, pressure, stol, cell_mask,
                                                                                  isotropic, cell_factor, cell_mass)
     params = capi.relax_cell_params(fire, stol, pressure, cell_factor, cell_mass, mask, isotropic, per_atom)
-    info = ctx.pot.info
-    grade_every = int(grade_every or 0)
-    if not info.has_selection:
-        if threshold_select is not None or threshold_break is not None:
-            raise capi.MtpError(-23, who + ": thresholds need a potential loaded with its selection state")
-        grade_every = 0
-    import torch
-    dev = device or torch.device("cuda:0")
-    if torch.cuda.current_stream(dev).cuda_stream == 0:      # see DeviceNVE.__init__
-        capi.use_private_torch_stream(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    steps, cut = int(steps), float(list_cutoff)
-    every, check_every, capture_gap = int(every), int(check_every or 0), int(capture_gap)
-    skin = cut - float(info.max_cutoff)
-    cfg_mode = bool(grade_every) and bool(info.configuration_mode)
-    ncfg_all = len(items)
-    passes, volume0, max_rows = plan_cell_passes(all_cells, natoms, cut, max_atoms_per_pass)
-    ghosts = capi.Ghosts(dev.index or 0)
-    buf = _BatchBuffers(torch, dev)
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    mass_t, inv_mass_t = to(mass_of_type), to(1.0 / mass_of_type)
-    candidates, records, final = [], [], [None] * ncfg_all
-    dropped, steps_done, npass, builds = 0, 0, 0, 0
-    tr = np.zeros((4, steps + 1, ncfg_all)) if trace else None            # energy, fmax, smax, volume
-    graded = lambda step: bool(grade_every) and step % grade_every == 0
-    for k0, k1, lay in passes:
-        npass += 1
-        ncfg = k1 - k0
-        counts = natoms[k0:k1]
-        if int(counts.sum()) == 0:
-            for k in range(k0, k1):
-                final[k] = dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt,
-                                cell=all_cells[k].copy(), virial=np.zeros(6), volume=float(volume0[k]),
-                                enthalpy=pressure * float(volume0[k]), smax=0.0)
-            continue
-        nonempty = int((counts > 0).sum())
-        run = _CellRun(ctx, ghosts, buf, items[k0:k1], all_cells[k0:k1].copy(), counts, lay, cut, int(max_rows[k0:k1].sum()),
-                       cfg_mode, max(max_candidates - len(records), 0), st, vatom=True)
-        builds += 1
-        n, cf, cf_t, row_cfg = run.n, run.cf, run.cf_t, run.row_cfg
-        eye = torch.eye(3, dtype=torch.float64, device=dev).reshape(1, 9).repeat(ncfg, 1)
-        h0_t = to(all_cells[k0:k1].reshape(ncfg, 9))
-        A = dict(cfg_first=cf_t, x=run.x, xt=torch.zeros((n, 3), dtype=torch.float64, device=dev),
-                 vt=torch.zeros((n, 3), dtype=torch.float64, device=dev), f=run.f, type=buf.tall, inv_mass=inv_mass_t,
-                 virial=torch.zeros((ncfg, 6), dtype=torch.float64, device=dev), h0=h0_t, origins=run.org_t, D=eye.clone(),
-                 vq=torch.zeros((ncfg, 9), dtype=torch.float64, device=dev), Dbinv=eye.clone(), href=h0_t.clone(),
-                 nimg=to(_cell_images(run.cells, cut)),
-                 dt=torch.full((ncfg,), dt, dtype=torch.float64, device=dev),
+    setup = _RunSetup(who, ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
+                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
+                      list_cutoff, every, check_every, max_atoms_per_pass, device,
+                      ("energy", "fmax", "smax", "volume") if trace else ())
+    torch, dev, st, zeros = setup.torch, setup.dev, setup.st, setup.zeros
+
+    def one_pass(run):
+        ncfg, A = run.ncfg, run.A
+        A.update(vt=zeros(run.n, 3), vq=zeros(ncfg, 9), dt=torch.full((ncfg,), dt, dtype=torch.float64, device=dev),
                  alpha=torch.full((ncfg,), fire.alpha_start, dtype=torch.float64, device=dev),
-                 npos=torch.zeros(ncfg, dtype=torch.int32, device=dev), frozen=run.frozen,
-                 done_step=torch.full((ncfg,), -1, dtype=torch.int32, device=dev),
-                 fmax=torch.zeros(ncfg, dtype=torch.float64, device=dev), smax=torch.zeros(ncfg, dtype=torch.float64, device=dev),
-                 gcell=torch.zeros((ncfg, 9), dtype=torch.float64, device=dev), h=h0_t.clone(), T=eye.clone(),
-                 cellmove=run.cellmove, counts=run.counts_t)
-        capi.relax_cell_rebase(ncfg, row_cfg, run.org_t, run.x, A["D"], A["xt"], A["Dbinv"], stream=st)   # xt = x - origin
-        cand_cell = torch.zeros((max(run.room, 1), 9), dtype=torch.float64, device=dev)
-        e_t = torch.zeros(ncfg, dtype=torch.float64, device=dev)
-        tr_dev = torch.zeros((4, steps + 1, ncfg), dtype=torch.float64, device=dev) if trace else None
+                 npos=torch.zeros(ncfg, dtype=torch.int32, device=dev),
+                 done_step=torch.full((ncfg,), -1, dtype=torch.int32, device=dev), fmax=zeros(ncfg), smax=zeros(ncfg),
+                 gcell=zeros(ncfg, 9))
+        run.v = A["vt"]
 
-        def forces(grade):
-            ghosts.forward(run.x, stream=st)
-            capi.zero_async(run.work, stream=st)
-            ctx.compute_device_rows(0, n, False, run.x, buf.tall, run.f, eflag=3, vflag=4, grade=grade, eatom_t=run.eatom,
-                                    vatom_t=run.vatom, ev_t=run.ev, grades_t=buf.grades if grade and not cfg_mode else None,
-                                    maxg_t=run.maxg if grade else None, coeff_t=run.coeff if grade and cfg_mode else None, stream=st)
-            ghosts.reverse_finish(ctx, run.f, run.ev, eflag=3, vflag=4, stream=st)
-            nbh = grade and not cfg_mode
-            capi.batch_reduce(cf_t, vatom_t=run.vatom, grades_t=buf.grades if nbh else None, virial_t=A["virial"],
-                              cfg_grade_t=run.g_t if nbh else None, stream=st)
-            if grade and cfg_mode:
-                ctx.batch_cfg_grades(cf_t, n, run.g_t, stream=st)
+        def step(s, last):
+            if trace:
+                run.trace[3, s].copy_(_det3(A["h"].view(ncfg, 3, 3)))
+            capi.relax_cell_step(ncfg, params, s, A, last=last, stream=st)
+            if trace:
+                run.energies(run.trace[0, s])
+                run.trace[1, s].copy_(A["fmax"])
+                run.trace[2, s].copy_(A["smax"])
 
-        def reneighbor():
-            hh = A["h"].cpu().numpy().reshape(ncfg, 3, 3)             # the cells the atoms sit in now
+        s = _minimise_pass(run, setup.steps, setup.graded, step, setup.every, setup.check_every)
+
+        def final(xh, eh):
+            fh, dh = run.frozen.cpu().numpy(), A["done_step"].cpu().numpy()
+            hh, wh = A["h"].cpu().numpy().reshape(ncfg, 3, 3), A["virial"].cpu().numpy()
+            dth, fmh, smh = A["dt"].cpu().numpy(), A["fmax"].cpu().numpy(), A["smax"].cpu().numpy()
             with np.errstate(all="ignore"):
-                bad = ~(np.isfinite(hh).all((1, 2)) & (_det3(hh) > 0.0))
-            hh[bad] = run.cells[bad]                                  # (such a configuration fails at its next step)
-            capi.sample_to_cell(n, row_cfg, run.org_t, run.x, stream=st)     # with the OLD origins
-            try:
-                new = capi.batch_layout(hh, cut, cut)
-            except capi.MtpError as e:
-                if e.code != -24:
-                    raise
-                raise capi.MtpError(-24, "%s: pass %d: configuration %d no longer fits the pass with its relaxed cell: %s"
-                                    % (who, npass, k0 + int(getattr(e, "nfit", 0)), e)) from e
-            org_t = to(new["origins"])
-            try:
-                rows = ghosts.build_batch(run.x, cf, hh, new["origins"], cut, stream=st)
-            except capi.MtpError as e:                                # (the capacity protocol: a shrinking cell has more images)
-                if e.code != -24 or ghosts.nall <= buf.cap or ghosts.nall >= 2 ** 31 - 1:
-                    raise
-                keep_x, keep_t = run.x[:n].clone(), buf.tall[:n].clone()
-                buf.reserve(ghosts.nall, ncfg, run.work_size(ghosts.nall), 0)
-                buf.xall[:n], buf.tall[:n] = keep_x, keep_t
-                run.x = buf.xall
-                capi.sample_to_cell(n, row_cfg, org_t, run.x, stream=st)     # (the refused build wrapped and translated already)
-                rows = ghosts.build_batch(run.x, cf, hh, new["origins"], cut, stream=st)
-            ghosts.types(buf.tall, stream=st)
-            ctx.build_neighbors_device(run.x, n, rows, cut, new["lo"], new["hi"], stream=st)
-            buf.reserve(0, ncfg, run.work_size(rows), 0)              # (rows may exceed what the work array was sized for)
-            run.layout(rows)
-            run.x_ref.copy_(run.x[:n])
-            run.cells, run.lay, run.org_t = hh, new, org_t
-            A.update(x=run.x, f=run.f, type=buf.tall, origins=org_t, href=to(hh.reshape(ncfg, 9)),
-                     nimg=to(_cell_images(hh, cut)))
-            A["T"].copy_(eye)
-            run.cellmove.zero_()
-            capi.relax_cell_rebase(ncfg, row_cfg, org_t, run.x, A["D"], A["xt"], A["Dbinv"], stream=st)
+                vol = _det3(hh)
+            return [dict(x=xh[a:b], energy=float(eh[j]), fmax=float(fmh[j]), status=capi.RELAX_STATUS[int(fh[j])], step=int(dh[j]),
+                         dt=float(dth[j]), cell=hh[j].copy(), virial=wh[j].copy(), volume=float(vol[j]),
+                         enthalpy=float(eh[j]) + pressure * float(vol[j]), smax=float(smh[j])) for j, (a, b) in enumerate(run.rows)]
 
-        s, since = 0, 0
-        while True:
-            forces(graded(s))
-            if graded(s):
-                run.capture(s, select, brk, capture_gap)
-                capi.relax_cell_capture_cells(run.slot, run.room, A["h"], cand_cell, stream=st)
-            if trace:
-                tr_dev[3, s].copy_(_det3(A["h"].view(ncfg, 3, 3)))
-            capi.relax_cell_step(ncfg, params, s, A, last=s == steps, stream=st)
-            if trace:
-                run.energies(tr_dev[0, s])
-                tr_dev[1, s].copy_(A["fmax"])
-                tr_dev[2, s].copy_(A["smax"])
-            if s == steps:
-                break
-            ghosts.deform(row_cfg, A["T"], stream=st)
-            since += 1
-            need = since >= every
-            if s == 0 or need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
-                run.monitor(A["vt"], mass_t)
-                m = run.monitor_read.cpu().numpy()                # d2 [ncfg] | block [4] | cellmove [ncfg]
-                if m[ncfg + 1] >= nonempty:                       # nothing is running any more: this step moved nothing
-                    break
-                need = need or cell_list_stale(m[:ncfg], m[ncfg + 4:], skin)
-            if need:
-                reneighbor()
-                builds += 1
-                since = 0
-            s += 1
-        steps_done = max(steps_done, s)
-        run.energies(e_t)
-        run.synchronize(npass, k0, k1)
-        xh = run.x[:n].cpu().numpy() - np.repeat(run.lay["origins"], counts, axis=0)
-        eh, fh, dh = e_t.cpu().numpy(), run.frozen.cpu().numpy(), A["done_step"].cpu().numpy()
-        hh, wh = A["h"].cpu().numpy().reshape(ncfg, 3, 3), A["virial"].cpu().numpy()
-        dth, fmh, smh = A["dt"].cpu().numpy(), A["fmax"].cpu().numpy(), A["smax"].cpu().numpy()
-        with np.errstate(all="ignore"):
-            vol = _det3(hh)
-        for j in range(ncfg):
-            a, b = int(cf[j]), int(cf[j + 1])
-            final[k0 + j] = dict(x=xh[a:b], energy=float(eh[j]), fmax=float(fmh[j]), status=capi.RELAX_STATUS[int(fh[j])],
-                                 step=int(dh[j]), dt=float(dth[j]), cell=hh[j].copy(), virial=wh[j].copy(), volume=float(vol[j]),
-                                 enthalpy=float(eh[j]) + pressure * float(vol[j]), smax=float(smh[j]))
-        dropped += run.harvest(k0, records, candidates, cand_cell)
-        if trace:
-            tr[:, : s + 1, k0:k1] = tr_dev.cpu().numpy()[:, : s + 1]
-    out = dict(candidates=candidates, records=records, dropped=dropped, final=final, steps_done=steps_done, builds=builds)
-    if trace:
-        out["trace"] = dict(energy=tr[0, : steps_done + 1], fmax=tr[1, : steps_done + 1], smax=tr[2, : steps_done + 1],
-                            volume=tr[3, : steps_done + 1])
-    return out
+        return s, final
+
+    def empty_final(k):
+        return dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt, cell=all_cells[k].copy(),
+                    virial=np.zeros(6), volume=float(setup.volume[k]), enthalpy=pressure * float(setup.volume[k]), smax=0.0)
+
+    setup.each_pass(one_pass, empty_final, _DeformingCellRun)
+    return setup.result()

@@ -356,3 +356,38 @@ def test_capture_under_relaxation_follows_the_twin_and_feeds_select_cells(fname,
     sel = select_cells(ctx, got["candidates"], threshold=1.1, list_cutoff=LIST_CUTOFF, max_swaps=0)
     for gb, (_, _, g) in zip(sel["grade_before"], got["records"]):
         assert abs(gb - g) <= 1e-9 * max(1.0, g)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graded", [False, True], ids=["plain", "graded"])
+def test_a_batch_split_into_passes_has_the_run_of_the_whole_batch(graded):
+    """tests/_passes.py.  plain: the run of test_relax_cells_follows_the_host_driven_loop; graded: potential and thresholds of
+    the capture test, max_candidates at its default (nothing is dropped).  every=20 is beyond the run and 0.42 A of travel is
+    below half the skin, so every pass with an atom in it builds its lists once.  The one-atom configuration converges at
+    step 0: alone in its pass, it ends that pass there.  Slot translation costs bits: the bounds are the trajectory bounds."""
+    import _passes
+    from lammps_mtp_kokkos_amd.md import relax_cells
+    fname, species = GRADED[0] if graded else POTS[0]
+    batch = _batch.mixed_batch(species)
+    ctx = _ctx(fname, graded)
+    kw = dict(masses=MASSES[species], list_cutoff=LIST_CUTOFF, dmax=0.02)
+    if graded:
+        kw["grade_every"] = 4
+        natoms = [len(c[0]) for c in batch]
+        table = _relax.reference_loop(ctx, batch, 12, select=BIG, brk=BIG, **kw)["grades"]
+        select, brk = sorted([_midpoint_threshold(table, natoms), _midpoint_threshold(table, natoms, central=True)])
+        kw.update(threshold_select=select, threshold_break=brk)
+
+    def run(a, b, cap):
+        return relax_cells(ctx, batch[a:b], 12, every=20, max_atoms_per_pass=cap, trace=True, **kw)
+
+    def same_final(f, w, config):
+        assert sorted(f) == sorted(w) and f["x"].shape == w["x"].shape == config[0].shape
+        assert _sample.wrapped_diff(f["x"], w["x"], config[1]) < X_TOL and abs(f["energy"] - w["energy"]) < E_TOL
+        assert abs(f["fmax"] - w["fmax"]) < V_TOL and abs(f["dt"] - w["dt"]) <= 1e-12 * w["dt"]
+        assert f["status"] == w["status"] and f["step"] == w["step"]
+
+    whole, split = _passes.assert_split_runs_are_the_whole_run(run, batch, LIST_CUTOFF, same_final, dict(energy=E_TOL, fmax=V_TOL), X_TOL)
+    assert whole["steps_done"] == 12 and whole["builds"] == 1 and split[1]["builds"] == 5 and split[8]["builds"] == 3
+    assert graded == (len(whole["records"]) > 0)
+    assert not graded or "captured-frozen" in [f["status"] for f in whole["final"]]

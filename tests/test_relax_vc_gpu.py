@@ -581,3 +581,44 @@ def test_candidates_carry_the_cell_they_were_graded_in(fname, species):
     sel = select_cells(ctx, got["candidates"], threshold=1.1, list_cutoff=LIST_CUTOFF, max_swaps=0)
     for gb, (_, _, g) in zip(sel["grade_before"], got["records"]):
         assert abs(gb - g) <= 1e-9 * max(1.0, g)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graded", [False, True], ids=["plain", "graded"])
+def test_a_batch_split_into_passes_has_the_run_of_the_whole_batch(graded):
+    """tests/_passes.py.  plain: the run of test_relax_cells_vc_follows_the_host_driven_loop; graded: potential and thresholds
+    of the capture test, max_candidates at its default (nothing is dropped).  every=20 is beyond the run; whether the moving
+    cells make a pass rebuild is the pass's own affair, so the builds are those of the passes' configurations run alone.  A
+    candidate carries the cell of its graded step.  Slot translation costs bits: the bounds are those of the host-driven-loop
+    test."""
+    import _passes
+    from lammps_mtp_kokkos_amd.md import relax_cells_vc
+    fname, species = GRADED[0] if graded else POTS[0]
+    batch = _batch.mixed_batch(species)
+    ctx = _ctx(fname, graded)
+    kw = dict(masses=MASSES[species], dmax=0.02, pressure=1.0 * GPA)
+    if graded:
+        kw["grade_every"] = 4
+        natoms = [len(c[0]) for c in batch]
+        table = _relax_vc.reference_loop(_relax_vc.evaluate_with(ctx, LIST_CUTOFF), batch, 12, select=BIG, brk=BIG, **kw)["grades"]
+        select, brk = sorted([_midpoint_threshold(table, natoms), _midpoint_threshold(table, natoms, central=True)])
+        kw.update(threshold_select=select, threshold_break=brk)
+
+    def run(a, b, cap):
+        return relax_cells_vc(ctx, batch[a:b], 12, every=20, list_cutoff=LIST_CUTOFF, max_atoms_per_pass=cap, trace=True, **kw)
+
+    def same_final(f, w, config):
+        assert sorted(f) == sorted(w) and f["x"].shape == w["x"].shape == config[0].shape
+        assert _sample.wrapped_diff(f["x"], w["x"], w["cell"]) < X_TOL and _cell_diff(f["cell"], w["cell"]) < X_TOL
+        assert abs(f["energy"] - w["energy"]) < E_TOL and abs(f["fmax"] - w["fmax"]) < V_TOL and abs(f["smax"] - w["smax"]) < V_TOL
+        assert abs(f["dt"] - w["dt"]) <= 1e-12 * w["dt"] and f["status"] == w["status"] and f["step"] == w["step"]
+        assert np.abs(f["virial"] - w["virial"]).max() < E_TOL and abs(f["volume"] - w["volume"]) < 1e-8
+        assert abs(f["enthalpy"] - w["enthalpy"]) < E_TOL
+
+    def same_cell(got, want, given, step):
+        assert _cell_diff(got, want) < X_TOL and np.array_equal(got, given) == (step == 0)
+
+    whole, split = _passes.assert_split_runs_are_the_whole_run(run, batch, LIST_CUTOFF, same_final,
+                                                               dict(energy=E_TOL, fmax=V_TOL, smax=V_TOL, volume=E_TOL), X_TOL, same_cell)
+    assert whole["steps_done"] == 12 and graded == (len(whole["records"]) > 0)
+    assert not graded or any(s > 0 for _, s, _ in whole["records"])

@@ -487,3 +487,39 @@ def test_half_skin_displacement_triggers_a_rebuild():
     still = sample_cells(ctx, [(pos, cell, types)], 300.0, 40, 1e-3, t_damp=None, velocities=[v0], masses=183.84,
                          list_cutoff=LIST_CUTOFF, every=1000, check_every=0)
     assert still["builds"] == 1                                # (without the read nothing asks for one)
+
+
+# ---- 10. more than one pass ----------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graded", [False, True], ids=["plain", "graded"])
+def test_a_batch_split_into_passes_has_the_run_of_the_whole_batch(graded):
+    """tests/_passes.py.  plain: the Langevin run of the host-driven-loop test; graded: the cold run, potential and threshold of
+    the capture test, max_candidates at its default (nothing is dropped).  every=20 is beyond both runs and nothing travels
+    half the skin (1 A) in them, so every pass with an atom in it builds its lists once.  Slot translation costs bits: the
+    bounds are those of test_a_configuration_alone_has_the_trajectory_and_records_it_had_in_the_batch."""
+    import _passes
+    from lammps_mtp_kokkos_amd.md import sample_cells
+    fname, selection, species, T, dt, steps = ("W_L16_nbh.almtp", True, 1, COLD["T"], COLD["dt"], COLD["steps"]) if graded else \
+        ("W_L8.mtp", False, 1, 300.0, 1e-3, 10)
+    batch, keys, temps, vel = _setup(species, T)
+    kw = {}
+    if graded:
+        thr = _midpoint_threshold(_reference(fname, True, species, T, dt, steps, 4)["grades"], [len(c[0]) for c in batch])
+        kw = dict(grade_every=4, threshold_select=thr, threshold_break=BIG)
+
+    def run(a, b, cap):
+        return sample_cells(_ctx(fname, selection), batch[a:b], temps[a:b], steps, dt, t_damp=0.1, seed=5, keys=keys[a:b],
+                            masses=MASSES[species], velocities=vel[a:b], list_cutoff=LIST_CUTOFF, every=20, max_atoms_per_pass=cap,
+                            trace=True, **kw)
+
+    def same_final(f, w, config):
+        assert sorted(f) == sorted(w) and f["x"].shape == w["x"].shape == config[0].shape
+        assert _sample.wrapped_diff(f["x"], w["x"], config[1]) < X_TOL
+        assert np.abs(f["v"] - w["v"]).max(initial=0.0) < V_TOL and abs(f["energy"] - w["energy"]) < E_TOL
+        assert abs(f["temperature"] - w["temperature"]) <= 1e-9 * max(1.0, w["temperature"])
+
+    whole, split = _passes.assert_split_runs_are_the_whole_run(run, batch, LIST_CUTOFF, same_final, dict(energy=E_TOL, kinetic=E_TOL),
+                                                               X_TOL)
+    assert whole["steps_done"] == steps and whole["builds"] == 1 and split[1]["builds"] == 5 and split[8]["builds"] == 3
+    assert graded == (len(whole["records"]) > 0)
