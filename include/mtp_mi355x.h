@@ -655,6 +655,91 @@ int mtp_relax_cell_capture_cells(void *stream, int ncfg, const int *d_slot, int 
  * over the steps; mtp_ghosts_forward / reverse / reverse_finish / types work unchanged. */
 int mtp_ghosts_deform(mtp_ghosts *g, void *stream, const int *d_row_cfg, const double *d_T /*[ncfg][9]*/);
 
+/* ---- batched constant-pressure sampling: Langevin MD of a whole batch of cells at a target pressure (NPT) -------------
+ *
+ * The batched sampling with the cell moved by stochastic cell rescaling, a first-order stochastic barostat in the spirit of
+ * Bernetti & Bussi, J. Chem. Phys. 153, 114107 (2020).  Conventions of the variable-cell relaxation above: rows of h are the
+ * lattice vectors, x - origin = s . h, W [eV] is the configurational virial for x -> x (I + eps) (xx yy zz xy xz yz, what
+ * mtp_batch_reduce leaves from a force call with MTP_VIRIAL_ATOM), pressure in eV/A^3.  Per configuration k, V = det h and
+ * kT = kB T[k]:
+ *   Kt_ab = mvv2e sum_i m_i v_ia v_ib   the kinetic tensor [eV];   Wt = W + Kt
+ *   M     = compressibility / (3 tau_p V0),  V0 the volume of the cell AS GIVEN [1 / (eV ps)]: a constant of the run, so no
+ *           mobility-gradient term arises
+ * One barostat move over a time dt is the symmetric log-strain
+ *   A = M dt [(Wt - p V I + kT I) o mask] + sqrt(2 kT M dt) N o mask,     N_aa = xi_aa,  N_ab = N_ba = xi_ab / sqrt(2)
+ *   isotropic != 0:  A <- (tr A / 3) I  (the three diagonal mask entries must be 1)
+ *   every |A_ab| is capped at strain_max, keeping its sign; capped[k] counts the steps at which a component was
+ *   E = I + A + A^2/2 + A^3/6 + A^4/24,  Einv the same series in -A.  strain_max <= 0.05 is required; at the default 0.01 the
+ *       truncation is below |3 A|^5 / 120 < 3e-10, far under the step's own O(dt) error
+ *   x - origin <- (x - origin) . E,  v <- v . Einv,  h <- h . E,  T <- T . E
+ * Where the + kT I comes from.  At fixed scaled positions and scaled momenta the flow h -> h exp(t S), S symmetric, preserves
+ * the Haar measure dh / V^3 of the cells.  The target exp(-beta (K + U + p V)) V^-2 dh (isotropic: dV) has the density
+ * rho = exp(-beta (K + U + p V)) V against that measure, and the logarithmic derivative of rho along the generator S is
+ * beta (Wt - p V I) : S + tr S (the momenta scale with Einv, hence Kt beside W).  The move is one Euler-Maruyama step of the
+ * overdamped Langevin equation dA = M kT grad(log rho) dt + sqrt(2 M kT) dB in the Frobenius metric of the symmetric
+ * matrices, of which rho is the stationary density.  Flexible cells also rotate slowly (symmetric strains do not commute);
+ * energies, forces and virials are invariant under it and nothing removes it.
+ * Noise: xi = sqrt(12) (u - 0.5), u = (w + 0.5) 2^-32 from Philox4x32-10 as in mtp_sample_final -- uniform with zero mean, unit
+ * variance and zero third moment, all a weak first-order scheme needs (and what fix langevin does); no transcendental function.
+ * Key: `seed`; counter (step, 0x80000000 + j, low word of key[k], high word of key[k]): call j = 0 gives xx, yy, zz from the
+ * words 0, 1, 2, call j = 1 xy, xz, yz.  Atom indices stay below 2^31, so these counters never meet an atom's.
+ * A step s = 1, 2, ... is
+ *   mtp_sample_cell_step(s) -> mtp_ghosts_deform(T) -> force call with per-atom virial -> mtp_ghosts_reverse_finish
+ *   -> mtp_batch_reduce (W) -> mtp_sample_final -> on a grade step: mtp_sample_capture -> mtp_relax_cell_capture_cells
+ * so that the forces of a kick are always those of the positions and the cell they were computed in, while the W that drives
+ * the cell at step s is the one of the force call of step s - 1: a one-step lag, an O(dt) error of the same order as the
+ * Euler-Maruyama move itself.
+ */
+typedef struct mtp_sample_cell_params {
+  double dt;              /* > 0, finite [ps] */
+  double dtf;             /* finite: 0.5 dt ftm2v, as for mtp_sample_initial */
+  double tau_p;           /* [ps]; not finite or <= 0: the barostat is off */
+  double compressibility; /* > 0, finite [A^3/eV]: an estimate; it sets the time scale only */
+  double pressure;        /* finite [eV/A^3] */
+  double strain_max;      /* in (0, 0.05] */
+  int cell_mask[6];       /* 0 or 1 each (xx yy zz xy xz yz); all 0: the barostat is off */
+  int isotropic;          /* != 0: the cell changes its volume only */
+  unsigned long long seed;
+} mtp_sample_cell_params;
+/* The device arrays of mtp_sample_cell_step: per owned row, per atom type, per configuration.  All are the caller's. */
+typedef struct mtp_sample_cell_arrays {
+  const int *cfg_first;          /* [ncfg + 1] */
+  double *x, *v;                 /* [n][3] slot coordinates, velocities */
+  const double *f;               /* [n][3] folded forces (with the thermostat's, as mtp_sample_final left them) */
+  const int *type;               /* [n] */
+  const double *inv_mass, *mass; /* per type */
+  const double *virial;          /* [ncfg][6] W of the previous force call */
+  const double *temperature;     /* [ncfg] */
+  const unsigned long long *key; /* [ncfg] */
+  const double *origins;         /* [ncfg][3] */
+  const double *V0;              /* [ncfg] */
+  double *h;                     /* [ncfg][9] the current cell: start it at the cell given */
+  double *T;                     /* [ncfg][9] the deformation since the last rebuild: what mtp_ghosts_deform takes (start: I) */
+  const double *href;            /* [ncfg][9] the cell at the last rebuild */
+  const int *nimg;               /* [ncfg][3] as for mtp_relax_cell_step */
+  int *frozen, *done_step;       /* [ncfg] */
+  double *cellmove;              /* [ncfg] mtp_relax_cell_step's list-validity measure */
+  int *capped;                   /* [ncfg] */
+  double *press;                 /* [ncfg] tr Wt / (3 V) of the last step [eV/A^3] */
+  int *counts;                   /* [3] mtp_sample_capture's */
+} mtp_sample_cell_arrays;
+/* The first half step of every non-empty configuration with frozen[k] == 0, with its barostat move.  One launch; the work
+ * split, the segment rule (a wavefront up to 256 rows, the workgroup above) and the fixed-order reductions without
+ * floating-point atomics of mtp_relax_cell_step:
+ *   1. kick: v += dtf f / m  (mtp_sample_initial's expression);  the six components of Kt from the kicked velocities
+ *   2. a component of W or Kt, V or V0 not finite, V <= 0 or V0 <= 0:  frozen[k] = 3 (failed), done_step[k] = step,
+ *      ++counts[2]; none of its rows or cell state is written
+ *   3. press[k] = tr Wt / (3 V)
+ *   4. barostat off (tau_p, or an all-zero mask):  x += dt v -- rows come out bit for bit as mtp_sample_initial leaves them;
+ *      h, T, cellmove and capped are not written, nothing is drawn
+ *   5. otherwise A, E, Einv as above from V = det h and the W given;  x = origin + ((x - origin) + dt v) . E;  v = v . Einv;
+ *      h = h . E, T = T . E;  cellmove[k] as mtp_relax_cell_step (8.) defines it
+ * MTP_ERR_ARG, nothing launched: a NULL stream (no context), ncfg < 0, step < 0, a missing array, dt not positive or not
+ * finite, dtf / pressure / compressibility not finite, compressibility <= 0, strain_max outside (0, 0.05], a mask entry that
+ * is neither 0 nor 1, isotropic with a diagonal mask entry of 0. */
+int mtp_sample_cell_step(void *stream, int ncfg, const mtp_sample_cell_params *params, int step,
+                         const mtp_sample_cell_arrays *arrays);
+
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------
  *

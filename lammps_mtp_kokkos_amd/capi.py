@@ -48,6 +48,7 @@ EXPORTS = [
     "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
     "mtp_sample_to_cell", "mtp_relax_step",
     "mtp_relax_cell_step", "mtp_relax_cell_rebase", "mtp_relax_cell_capture_cells", "mtp_ghosts_deform",
+    "mtp_sample_cell_step",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -114,7 +115,7 @@ def kernel_source_hash():
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
-                      "mtp_relax_cell.hip", "mtp_relax_common.hpp")
+                      "mtp_relax_cell.hip", "mtp_relax_common.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1173,6 +1174,41 @@ def relax_cell_capture_cells(slot_t, max_candidates, h_t, cand_cell_t, stream=No
                                             _ptr(cand_cell_t))
     if rc:
         raise MtpError(rc, "mtp_relax_cell_capture_cells")
+
+
+# ---- batched constant-pressure sampling (include/mtp_mi355x.h)
+
+class SampleCellParams(C.Structure):
+    """mtp_sample_cell_params"""
+    _fields_ = [(n, C.c_double) for n in ("dt", "dtf", "tau_p", "compressibility", "pressure", "strain_max")] + \
+               [("cell_mask", C.c_int * 6), ("isotropic", C.c_int), ("seed", C.c_ulonglong)]
+
+
+SAMPLE_CELL_ARRAYS = ("cfg_first", "x", "v", "f", "type", "inv_mass", "mass", "virial", "temperature", "key", "origins", "V0", "h", "T",
+                      "href", "nimg", "frozen", "done_step", "cellmove", "capped", "press", "counts")
+
+
+class SampleCellArrays(C.Structure):
+    """mtp_sample_cell_arrays: device pointers, in the order of SAMPLE_CELL_ARRAYS"""
+    _fields_ = [(n, C.c_void_p) for n in SAMPLE_CELL_ARRAYS]
+
+
+def sample_cell_params(dt, dtf, tau_p, compressibility, pressure, strain_max=0.01, cell_mask=(1, 1, 1, 1, 1, 1), isotropic=False,
+                       seed=0):
+    """a SampleCellParams (no check: mtp_sample_cell_step makes them); tau_p None: the barostat is off"""
+    return SampleCellParams(float(dt), float(dtf), 0.0 if tau_p is None else float(tau_p), float(compressibility), float(pressure),
+                            float(strain_max), (C.c_int * 6)(*[int(m) for m in cell_mask]), int(bool(isotropic)),
+                            int(seed) & (2 ** 64 - 1))
+
+
+def sample_cell_step(ncfg, params, step, arrays, stream=None):
+    """the first half step of every running configuration with its barostat move, in one launch: mtp_sample_cell_step.  `params`
+    is a SampleCellParams, `arrays` a dict of device tensors with the keys SAMPLE_CELL_ARRAYS (float64; key int64; type, nimg,
+    frozen, done_step, capped, counts and cfg_first int32)."""
+    A = SampleCellArrays(*[_ptr(arrays.get(n)) for n in SAMPLE_CELL_ARRAYS])
+    rc = lib().mtp_sample_cell_step(_st(stream), int(ncfg), C.byref(params), int(step), C.byref(A))
+    if rc:
+        raise MtpError(rc, "mtp_sample_cell_step")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

@@ -9,20 +9,6 @@ namespace {
 
 using namespace relax_common;
 
-__device__ __forceinline__ double det3(const double *m)
-{
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-
-// c = a . b
-__device__ __forceinline__ void mul3(const double *a, const double *b, double *c)
-{
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-}
-
 // inv = m^-1 (cofactors over the determinant)
 __device__ __forceinline__ void inv3(const double *m, double det, double *inv)
 {
@@ -192,17 +178,10 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
     double hn[9], T[9];
     mul3(A.h0 + 9 * (size_t) k, Dn, hn);
     mul3(A.Dbinv + 9 * (size_t) k, Dn, T);
-    double move = 0.0;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const double d0 = hn[3 * r] - A.href[9 * (size_t) k + 3 * r], d1 = hn[3 * r + 1] - A.href[9 * (size_t) k + 3 * r + 1],
-                   d2 = hn[3 * r + 2] - A.href[9 * (size_t) k + 3 * r + 2];
-      move += (double) (A.nimg[3 * (size_t) k + r] + 1) * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-    }
     A.dt[k] = dt;
     A.alpha[k] = alpha;
     A.npos[k] = npos;
-    A.cellmove[k] = move;
+    A.cellmove[k] = cell_move(hn, A.href + 9 * (size_t) k, A.nimg + 3 * (size_t) k);
 #pragma unroll
     for (int q = 0; q < 9; q++) {
       A.D[9 * (size_t) k + q] = Dn[q];

@@ -46,6 +46,33 @@ __device__ __forceinline__ double relax_total(double val, double *part)
   return t;
 }
 
+// 3 x 3 matrices of a cell, row-major [3 a + b] (the two kernels that move cells: mtp_relax_cell.hip, mtp_sample_cell.hip)
+__device__ __forceinline__ double det3(const double *m)
+{
+  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+}
+
+// c = a . b
+__device__ __forceinline__ void mul3(const double *a, const double *b, double *c)
+{
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
+
+// sum_a (nimg_a + 1) |h_a - href_a| over the rows of a cell: the list-validity measure of a moving cell (mtp_relax_cell_step, 8.)
+__device__ __forceinline__ double cell_move(const double *h, const double *href, const int *nimg)
+{
+  double move = 0.0;
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const double d0 = h[3 * r] - href[3 * r], d1 = h[3 * r + 1] - href[3 * r + 1], d2 = h[3 * r + 2] - href[3 * r + 2];
+    move += (double) (nimg[r] + 1) * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+  }
+  return move;
+}
+
 inline bool in_range(const mtp_relax_params &p)
 {
   const double all[7] = {p.ftol, p.dt_max, p.dmax, p.f_inc, p.f_dec, p.alpha_start, p.f_alpha};

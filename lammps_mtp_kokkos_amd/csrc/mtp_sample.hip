@@ -11,6 +11,7 @@
 
 #include "../../include/mtp_mi355x.h"
 #include "mtp_device.hpp"
+#include "mtp_philox.hpp"
 
 namespace {
 
@@ -18,24 +19,6 @@ namespace {
 constexpr double SAMPLE_MVV2E = 1.0364269e-4;
 constexpr double SAMPLE_FTM2V = 1.0 / SAMPLE_MVV2E;
 constexpr double SAMPLE_KB = 8.617343e-5;
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of
-//   (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),  key += (W0, W1) between rounds
-__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
-{
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-    const unsigned lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 // row_cfg[i] = the configuration of owned row i: the last k < ncfg with cfg_first[k] <= i (empty configurations share
 // their start with the next one, which this skips).  The one binary search per row of a pass.

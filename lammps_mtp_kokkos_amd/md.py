@@ -15,7 +15,8 @@ cutoff: mtp_ghosts_build_cell, list bounds from mtp_ghosts_cell_bounds).  evalua
 without the integrator; evaluate_cells does many of them -- training or candidate configurations, each with its own
 cell -- in one device pass (include/mtp_mi355x.h, "batched configurations").  sample_cells is the integrator over that
 batch layout: Langevin (or NVE) MD of all the cells at once with the extrapolation grade watched, and the extrapolating
-configurations captured, on the device (include/mtp_mi355x.h, "batched sampling").
+configurations captured, on the device (include/mtp_mi355x.h, "batched sampling"); sample_cells_npt does the same at constant
+pressure, the cells moved by a stochastic barostat ("batched constant-pressure sampling").
 
 torch only allocates the arrays and provides the stream; the host sees the ghost count and the list size at a
 re-neighbouring (they size arrays) and nothing else.
@@ -1283,9 +1284,10 @@ class _CellRun:
 
 
 class _DeformingCellRun(_CellRun):
-    """_CellRun for cells that change during the run (relax_cells_vc; a batched NPT would sit on the same run): forces with
+    """_CellRun for cells that change during the run (relax_cells_vc, sample_cells_npt): forces with
     per-atom virials and the virial per configuration, the geometry h = h0 . D, x = origin + xt . D in the arrays `A`
-    (mtp_relax_cell_arrays; the driver adds its minimiser's state and sets v = A["vt"]), ghosts that follow the cell after a
+    (mtp_relax_cell_arrays; the driver adds its minimiser's state and sets v = A["vt"] -- sample_cells_npt moves h itself and
+    adds the arrays of mtp_sample_cell_arrays: D stays I and xt is not read), ghosts that follow the cell after a
     move, the stale rule with the cell's own movement in it, candidates with the cell of their graded step, and a rebuild that
     lays the pass out again for the cells as they are."""
 
@@ -1409,34 +1411,35 @@ def _run_arguments(who, items, masses, threshold_select, threshold_break, captur
 
 
 def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break, capture_gap,
-                      max_candidates, velocities, grade_every, every, check_every):
-    """the host-side checks of sample_cells (nothing here touches the device); returns the normalised arguments"""
+                      max_candidates, velocities, grade_every, every, check_every, who="sample_cells"):
+    """the host-side checks of sample_cells and sample_cells_npt (`who`; nothing here touches the device); returns the normalised
+    arguments"""
     items, all_cells, natoms = _batch_items(configs)
     ncfg = len(items)
     if not (float(dt) > 0.0 and np.isfinite(float(dt))):
-        raise ValueError("sample_cells: dt must be positive and finite, got %r" % (dt,))
+        raise ValueError(who + ": dt must be positive and finite, got %r" % (dt,))
     if int(steps) < 0 or int(steps) >= 2 ** 30:
-        raise ValueError("sample_cells: steps must be in [0, 2^30)")
-    select, brk, mass_of_type, max_candidates = _run_arguments("sample_cells", items, masses, threshold_select, threshold_break,
+        raise ValueError(who + ": steps must be in [0, 2^30)")
+    select, brk, mass_of_type, max_candidates = _run_arguments(who, items, masses, threshold_select, threshold_break,
                                                                capture_gap, max_candidates, grade_every, every, check_every)
     if keys is None:
         keys = np.arange(ncfg, dtype=np.uint64)
     else:
         if len(keys) != ncfg:
-            raise ValueError("sample_cells: %d keys for %d configurations" % (len(keys), ncfg))
+            raise ValueError(who + ": %d keys for %d configurations" % (len(keys), ncfg))
         keys = np.array([int(q) & (2 ** 64 - 1) for q in keys], dtype=np.uint64)
     temperature = np.asarray(temperature, dtype=np.float64)
     if temperature.ndim == 0:
         temperature = np.full(ncfg, float(temperature))
     if temperature.shape != (ncfg,) or not (np.isfinite(temperature).all() and (temperature >= 0.0).all()):
-        raise ValueError("sample_cells: temperature is a non-negative scalar or one per configuration (%d)" % ncfg)
+        raise ValueError(who + ": temperature is a non-negative scalar or one per configuration (%d)" % ncfg)
     if velocities is not None:
         if len(velocities) != ncfg:
-            raise ValueError("sample_cells: %d velocity arrays for %d configurations" % (len(velocities), ncfg))
+            raise ValueError(who + ": %d velocity arrays for %d configurations" % (len(velocities), ncfg))
         velocities = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]
         for k, v in enumerate(velocities):
             if len(v) != natoms[k]:
-                raise ValueError("sample_cells: velocities[%d] must be [%d, 3]" % (k, natoms[k]))
+                raise ValueError(who + ": velocities[%d] must be [%d, 3]" % (k, natoms[k]))
     return items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities, max_candidates
 
 
@@ -1676,14 +1679,19 @@ def _relax_vc_arguments(natoms, mass_of_type, pressure, stol, cell_mask, isotrop
     cell_mass = float(np.mean(mass_of_type)) if cell_mass is None else float(cell_mass)
     if not (np.isfinite(cell_mass) and cell_mass > 0.0):
         raise ValueError("relax_cells_vc: cell_mass must be positive and finite, got %r" % (cell_mass,))
+    return stol, pressure, cell_factor, cell_mass, _cell_mask("relax_cells_vc", cell_mask), per_atom
+
+
+def _cell_mask(who, cell_mask):
+    """cell_mask as a list of six 0 / 1, or ValueError"""
     try:
         mask = [int(m) for m in cell_mask]
         exact = all(float(m) == q for m, q in zip(cell_mask, mask))
     except (TypeError, ValueError):
         mask, exact = [], False
     if len(mask) != 6 or not exact or any(m not in (0, 1) for m in mask):
-        raise ValueError("relax_cells_vc: cell_mask is six entries 0 or 1 (xx yy zz xy xz yz), got %r" % (cell_mask,))
-    return stol, pressure, cell_factor, cell_mass, mask, per_atom
+        raise ValueError("%s: cell_mask is six entries 0 or 1 (xx yy zz xy xz yz), got %r" % (who, cell_mask))
+    return mask
 
 
 def _cell_images(cells, rghost):
@@ -1780,3 +1788,155 @@ def relax_cells_vc(ctx, configs, steps, pressure=0.0, stol=1e-4, cell_mask=(1, 1
 
     setup.each_pass(one_pass, empty_final, _DeformingCellRun)
     return setup.result()
+
+
+def _npt_arguments(pressure, compressibility, tau_p, t_damp, cell_mask, isotropic, strain_max):
+    """the host-side checks of sample_cells_npt's own arguments (nothing here touches the device); returns (pressure,
+    compressibility, tau_p or None: the barostat is off, t_damp, cell_mask [6], strain_max)"""
+    who = "sample_cells_npt"
+    pressure, compressibility, strain_max = float(pressure), float(compressibility), float(strain_max)
+    if not np.isfinite(pressure):
+        raise ValueError("%s: pressure must be finite, got %r" % (who, pressure))
+    if not (np.isfinite(compressibility) and compressibility > 0.0):
+        raise ValueError("%s: compressibility must be positive and finite, got %r" % (who, compressibility))
+    if t_damp is None or not (np.isfinite(float(t_damp)) and float(t_damp) > 0.0):
+        raise ValueError("%s: t_damp must be positive and finite (the barostat's noise is at the thermostat's temperature), got %r"
+                         % (who, t_damp))
+    if not 0.0 < strain_max <= 0.05:
+        raise ValueError("%s: strain_max must be in (0, 0.05], got %r" % (who, strain_max))
+    mask = _cell_mask(who, cell_mask)
+    if isotropic and mask[:3] != [1, 1, 1]:
+        raise ValueError("%s: isotropic needs the three diagonal entries of cell_mask to be 1, got %r" % (who, cell_mask))
+    if tau_p is not None:
+        tau_p = float(tau_p)
+        if not (np.isfinite(tau_p) and tau_p > 0.0):
+            tau_p = None
+    return pressure, compressibility, tau_p, float(t_damp), mask, strain_max
+
+
+def sample_cells_npt(ctx, configs, temperature, pressure, steps, dt, *, compressibility, tau_p=1.0, t_damp=0.1,
+                     cell_mask=(1, 1, 1, 1, 1, 1), isotropic=False, strain_max=0.01, seed=0, keys=None, masses=183.84, grade_every=10,
+                     threshold_select=None, threshold_break=None, capture_gap=0, max_candidates=None, velocities=None,
+                     list_cutoff=7.0, every=10, check_every=4, max_atoms_per_pass=None, device=None, trace=False):
+    """sample_cells at constant pressure: Langevin MD of a whole batch of independent periodic cells at the target `temperature`
+    [K] and `pressure` [eV/A^3; 1 GPa = capi.GPA], device-resident, the cell of every configuration moved by stochastic cell
+    rescaling -- a first-order stochastic barostat in the spirit of Bernetti & Bussi, J. Chem. Phys. 153, 114107 (2020), one
+    state machine per configuration run by mtp_sample_cell_step (include/mtp_mi355x.h, "batched constant-pressure sampling":
+    the move, its noise and where its terms come from).  Every argument of sample_cells has its meaning there; grade watching
+    and capture are sample_cells', and a candidate carries the cell of its graded step.
+
+    `compressibility` [A^3/eV] is an estimate of the isothermal compressibility and `tau_p` [ps] the barostat's time: together
+    they set how fast the cell answers (M = compressibility / (3 tau_p V0), V0 the volume given), not where it ends up.
+    tau_p None, not finite or not positive, or a `cell_mask` (xx yy zz xy xz yz; 0 or 1) of zeros: the cells stay as given, and
+    the trajectory is sample_cells'.  `isotropic`: the cell changes its volume only.  `strain_max` (at most 0.05) caps every
+    component of the log-strain of one step; final[k]["capped"] counts the steps at which it did.  A finite positive `t_damp`
+    is required: the barostat's noise is at the thermostat's temperature.  A flexible cell also rotates slowly (symmetric
+    strains do not commute); energies, forces and virials are invariant under it and nothing removes it.
+
+    Step 0 is sample_cells' step 0 with the virial tallied.  Step s = 1 ... steps: mtp_sample_cell_step(s) (kick, the kinetic
+    tensor, the barostat move from the virial of the PREVIOUS force call, drift) -> ghosts follow the cell (mtp_ghosts_deform)
+    -> ONE force call with per-atom virials -> ghost fold -> the virial per configuration -> mtp_sample_final -> on a grade
+    step mtp_sample_capture and the cells of the captured.  Lists are rebuilt as in relax_cells_vc: every `every` steps or when
+    cell_list_stale says so at the one read of the monitor (every `check_every` steps since the last rebuild); a rebuild lays
+    the pass out again for the cells as they are.  A configuration whose virial, kinetic tensor or volume is not finite (or
+    whose volume is not positive) fails: it is not written again.
+
+    Returns what sample_cells returns (frozen [ncfg]: True for every configuration that no longer moves); final[k] also has
+    cell [3, 3], volume, virial [6] (W at x and cell), pressure = tr (W + Kt) / (3 V) [eV/A^3], capped, status ("running",
+    "captured-frozen" or "failed") and step (of the failure, -1 otherwise); trace=True adds volume (of the cell the step's
+    forces were taken in) and pressure [steps_done + 1, ncfg]."""
+    who = "sample_cells_npt"
+    (items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities,
+     max_candidates) = _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break,
+                                         capture_gap, max_candidates, velocities, grade_every, every, check_every, who)
+    pressure, compressibility, tau_p, t_damp, mask, strain_max = _npt_arguments(pressure, compressibility, tau_p, t_damp, cell_mask,
+                                                                                isotropic, strain_max)
+    setup = _RunSetup(who, ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
+                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
+                      list_cutoff, every, check_every, max_atoms_per_pass, device,
+                      ("energy", "kinetic", "volume", "pressure") if trace else ())
+    torch, dev, to, st, zeros, graded = setup.torch, setup.dev, setup.to, setup.st, setup.zeros, setup.graded
+    steps, every, check_every = setup.steps, setup.every, setup.check_every
+    dt, seed = float(dt), int(seed) & (2 ** 64 - 1)
+    dtf = 0.5 * dt * FTM2V
+    barostat = tau_p is not None and any(mask)
+    params = capi.sample_cell_params(dt, dtf, tau_p, compressibility, pressure, strain_max, mask, isotropic, seed)
+    if velocities is None:
+        velocities = maxwell_boltzmann(items, mass_of_type, temperature, seed, keys)
+    frozen_all = np.zeros(len(items), dtype=bool)
+
+    def one_pass(run):
+        k0, k1, n, ncfg, A = run.k0, run.k1, run.n, run.ncfg, run.A
+        run.v = v = to(np.concatenate(velocities[k0:k1]))
+        A.update(v=v, mass=setup.mass_t, temperature=to(temperature[k0:k1]), key=to(keys[k0:k1].view(np.int64)),
+                 V0=to(setup.volume[k0:k1]), done_step=torch.full((ncfg,), -1, dtype=torch.int32, device=dev),
+                 capped=torch.zeros(ncfg, dtype=torch.int32, device=dev), press=zeros(ncfg))
+
+        def second_half(step, kick):
+            capi.sample_final(n, run.row_cfg, run.cf_t, run.frozen, v, run.f, run.buf.tall, setup.mass_t, setup.inv_mass_t,
+                              A["temperature"], A["key"], seed, step, kick, dt, t_damp, stream=st)
+
+        def record(step):                                     # (pressure: tr W + 2 K over 3 V, from the monitor's sum m v^2)
+            run.energies(run.trace[0, step])
+            run.monitor(run.trace[1, step])
+            vol = _det3(A["h"].view(ncfg, 3, 3))
+            run.trace[2, step].copy_(vol)
+            run.trace[3, step].copy_((run.virial[:, :3].sum(1) + MVV2E * run.trace[1, step]) / (3.0 * vol))
+
+        run.forces(graded(0))
+        second_half(0, 0.0)                                   # (fix langevin's setup: the thermostat force of step 0, no kick)
+        stop = False
+        if graded(0):
+            run.capture(0)
+            stop = run.read()[0]
+        if trace:
+            record(0)
+        s, since = 0, 0
+        while s < steps and not stop:
+            s += 1
+            capi.sample_cell_step(ncfg, params, s, A, stream=st)
+            if barostat:
+                run.moved()
+            since += 1
+            need = since >= every
+            if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
+                done, stale = run.read()
+                if done:                                      # nothing is running any more: this first half wrote nothing
+                    s -= 1
+                    break
+                need = need or stale
+            if need:
+                run.reneighbor()
+                since = 0
+            grade = graded(s)
+            run.forces(grade)
+            second_half(s, dtf)
+            if grade:
+                run.capture(s)
+            if trace:
+                record(s)
+
+        def final(xh, eh):                                    # (the harness ran the monitor once more: sum m v^2 at the end)
+            vh, mh, fh = v.cpu().numpy(), run.mv2.cpu().numpy(), run.frozen.cpu().numpy()
+            hh, wh = A["h"].cpu().numpy().reshape(ncfg, 3, 3), run.virial.cpu().numpy()
+            dh, ch = A["done_step"].cpu().numpy(), A["capped"].cpu().numpy()
+            frozen_all[k0:k1] = fh != 0
+            with np.errstate(all="ignore"):
+                vol = _det3(hh)
+                press = (wh[:, :3].sum(1) + MVV2E * mh) / (3.0 * vol)
+            return [dict(x=xh[a:b], v=vh[a:b], energy=float(eh[j]),
+                         temperature=float(mh[j]) * MVV2E / (3.0 * (b - a) * KB) if b > a else 0.0, cell=hh[j].copy(),
+                         volume=float(vol[j]), virial=wh[j].copy(), pressure=float(press[j]) if b > a else 0.0, capped=int(ch[j]),
+                         status=capi.RELAX_STATUS[int(fh[j])], step=int(dh[j])) for j, (a, b) in enumerate(run.rows)]
+
+        return s, final
+
+    def empty_final(k):
+        return dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0, cell=all_cells[k].copy(),
+                    volume=float(setup.volume[k]), virial=np.zeros(6), pressure=0.0, capped=0, status=capi.RELAX_STATUS[0], step=-1)
+
+    setup.each_pass(one_pass, empty_final, _DeformingCellRun, final_monitor=True)
+    out = setup.result(frozen=frozen_all)
+    if trace:
+        out["trace"]["kinetic"] = 0.5 * MVV2E * out["trace"]["kinetic"]
+    return out
