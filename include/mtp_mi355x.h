@@ -17,7 +17,7 @@
  *     context's own stream, resolved once per call -- every launch and RCCL group of that call runs on it;
  *   - entry points without a context (the other mtp_halo_*, mtp_ghosts_*, mtp_nve_* calls, mtp_zero_async,
  *     mtp_batch_reduce, mtp_ghosts_owner_device, mtp_batch_design_reduce, the mtp_sample_* calls, mtp_relax_step, the
- *     mtp_relax_cell_* calls,
+ *     mtp_relax_cell_* calls, mtp_neb_step,
  *     mtp_normal_clear, mtp_normal_accumulate, mtp_normal_get, mtp_normal_set): NULL is
  *     rejected with MTP_ERR_ARG -- there is no stream to map it to, and the legacy null stream is never used.
  * The context's stream is created NON-BLOCKING: it does not synchronise with the legacy default stream, so a caller
@@ -739,6 +739,91 @@ typedef struct mtp_sample_cell_arrays {
  * is neither 0 nor 1, isotropic with a diagonal mask entry of 0. */
 int mtp_sample_cell_step(void *stream, int ncfg, const mtp_sample_cell_params *params, int step,
                          const mtp_sample_cell_arrays *arrays);
+
+/* ---- batched nudged elastic band: minimum-energy paths of a whole batch of bands, decided on the device --------------
+ *
+ * What follows the minima: the path between two of them and its barrier.  A band is a run of M >= 3 CONSECUTIVE
+ * configurations (its images) of the batched layout with the same atom count, the same types and the same, fixed cell; band b
+ * is the configurations [band_first[b], band_first[b + 1]).  Its first and last image are never moved.  The bands of a batch
+ * are independent; the images of a band are not -- this is the one kernel of the batched family that couples configurations.
+ * The method is the climbing-image NEB with the improved tangent (Henkelman & Jonsson, J. Chem. Phys. 113, 9978; Henkelman,
+ * Uberuaga & Jonsson, ibid. 9901), minimised by the FIRE state machine of mtp_relax_step, ONE per band.  Layout, slot
+ * coordinates, force / grade call, capture and monitor block are those of the batched relaxation; a step s = 0, 1, ... is
+ *   mtp_ghosts_forward -> force call with MTP_ENERGY_ATOM -> mtp_ghosts_reverse[_finish]
+ *   -> on a grade step: the per-configuration grades -> mtp_sample_capture
+ *   -> mtp_neb_step(s)
+ * Re-neighbouring wraps every image into the cell on its own, so neighbouring images may differ by lattice vectors: all
+ * differences between images go through the minimum image mic(d) = d - rint(d . h^-1) . h (row vectors, rint to even), which
+ * is the true difference as long as no atom moves more than a quarter of the smallest cell height between two images.
+ */
+#define MTP_NEB_MAX_IMAGES 64 /* the image energies and the per-image totals of a band live in LDS */
+typedef struct mtp_neb_params {
+  mtp_relax_params fire; /* as for mtp_relax_step; ftol bounds the largest |F_neb| of a row */
+  double spring;         /* > 0, finite: the spring constant between neighbouring images [eV/A^2] */
+  int climb_step;        /* the first step with a climbing image; < 0: never */
+} mtp_neb_params;
+/* The device arrays of mtp_neb_step.  All are the caller's. */
+typedef struct mtp_neb_arrays {
+  const int *band_first;   /* [nband + 1] configuration indices: the device copy of the host table given to the call */
+  const int *cfg_first;    /* [ncfg + 1] */
+  double *x, *v;           /* [n][3] slot coordinates, velocities (start: 0) */
+  const double *f;         /* [n][3] folded forces */
+  const double *eatom;     /* [n] per-atom energies of the same force call */
+  const int *type;         /* [n] */
+  const double *inv_mass;  /* per type */
+  const double *origins;   /* [ncfg][3] */
+  const double *cell;      /* [nband][9] h, rows = lattice vectors */
+  const double *cell_inv;  /* [nband][9] h^-1 */
+  double *fneb;            /* [n][3] F_neb */
+  double *energy;          /* [ncfg] E_i */
+  double *dt, *alpha;      /* [nband] FIRE state, as for mtp_relax_step */
+  int *npos, *done_step;   /* [nband] */
+  double *fmax;            /* [nband] */
+  int *climber;            /* [nband] the climbing image of the last step looked at (its index within the band), -1: none */
+  int *band_status;        /* [nband] 0 running, 1 stopped by a capture, 2 converged, 3 failed */
+  int *frozen;             /* [ncfg] mtp_sample_capture's and mtp_sample_monitor's: every image of a stopped band is set */
+  int *counts;             /* [3] mtp_sample_capture's */
+} mtp_neb_arrays;
+/* One NEB step of every band with band_status[b] == 0.  One launch, one workgroup of 256 threads per band: an image is served
+ * by one wavefront (the four of the workgroup take the images in turn), the FIRE sweeps over the interior rows -- consecutive
+ * rows -- by the whole workgroup.  Every floating-point sum has a fixed order (the reductions of mtp_relax_step; per-image
+ * totals are added in image order) and there are no floating-point atomics: a band's result depends on its own rows only,
+ * whatever the batch around it.  The one atomic is the integer count counts[2].  Images are i = 0 ... M - 1, rows of image i
+ * are those of configuration band_first[b] + i; "interior" is 0 < i < M - 1.
+ *   1. capture check: if frozen[k] != 0 for an image of the band (mtp_sample_capture froze it), band_status[b] = 1,
+ *      done_step[b] = step, every image still at 0 gets frozen[k] = 1 and is added to counts[2]; NOTHING else is written
+ *   2. E_i = the sum of the image's rows of eatom;  energy[k] = E_i
+ *   3. tangents, for every interior image and each of its atoms j, on cell coordinates c = x - origins[k]:
+ *        D+ = mic(c_{i+1} - c_i),  D- = mic(c_i - c_{i-1})
+ *        E_{i+1} > E_i > E_{i-1}:  tau = D+;    E_{i+1} < E_i < E_{i-1}:  tau = D-;    otherwise, with
+ *        big / small = the larger / smaller of |E_{i+1} - E_i| and |E_{i-1} - E_i|:
+ *        tau = big D+ + small D- if E_{i+1} > E_{i-1}, else small D+ + big D-
+ *      |tau| = sqrt(sum over atoms and components of tau^2);  |tau| zero or not finite: the band fails (5.)
+ *   4. F.t = (sum F tau) / |tau|;  |D+|, |D-| the norms over the whole image;
+ *        F_neb = F + g tau,  g = (spring (|D+| - |D-|) - F.t) / |tau|      (= F - (F.t) t + spring (|D+| - |D-|) t)
+ *      from step >= climb_step >= 0 the interior image of the highest E_i (the lowest index on a tie) climbs instead:
+ *        g = -2 F.t / |tau|                                                  (= F - 2 (F.t) t)
+ *      climber[b] = its index, -1 before that step;  fneb = F_neb for the interior rows, 0 for the rows of both end images
+ *   5. FIRE, rules 1 to 4 of mtp_relax_step over the interior rows of the WHOLE band with F_neb in place of f:
+ *      P = sum F_neb.v, vv, ff, fmax2 = the largest |F_neb|^2 of a row;  fmax[b] = sqrt(fmax2)
+ *      ff not finite (or 3. failed; or an E_i that is not finite, after which nothing of 3. and 4. is written, fmax[b] = 0 and
+ *      climber[b] = -1; or images of different atom counts, for which nothing of 2. to 4. is written either):
+ *                           band_status[b] = 3, frozen[k] = 3 for ALL its images, done_step[b] = step, counts[2] += M
+ *      fmax2 <= ftol^2:     band_status[b] = 2, frozen[k] = 2 for all its images, done_step[b] = step, counts[2] += M;
+ *                           the interior rows of v are set to 0, x is not written
+ *      (with `last` != 0 the call ends here: it only decides, and has written fneb, energy, fmax and climber)
+ *      then a, b, npos, dt, alpha by rule 3 of mtp_relax_step from the band's dt[b], alpha[b], npos[b];  v' = a v + b F_neb;
+ *      vmax over the interior rows;  dtv = dt, or dmax / vmax if dt vmax > dmax;  x += dtv v';  v = v' + (dtv ftm2v / m) F_neb
+ *      No row of the two end images is written, ever.
+ *   6. MTP_ERR_ARG, nothing launched: a NULL stream (no context), nband < 0, ncfg < 0, step < 0, a missing array (nband > 0),
+ *      FIRE parameters outside the ranges of mtp_relax_params, spring not finite or <= 0, and a band table -- the HOST copy
+ *      band_first [nband + 1], the only thing the check can read without waiting for the device -- that starts below 0, ends
+ *      above ncfg or has a band of fewer than 3 or more than MTP_NEB_MAX_IMAGES images.  (A band for which the device copy
+ *      says so is skipped by the kernel.)  Equal atom counts and types within a band are the caller's to check on the host.
+ * nband == 0 launches nothing.  The caller starts dt, alpha, npos as for mtp_relax_step, done_step and climber at -1,
+ * band_status and v at 0. */
+int mtp_neb_step(void *stream, int nband, const int *band_first /* host */, int ncfg, const mtp_neb_params *params, int step,
+                 int last, const mtp_neb_arrays *arrays);
 
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------

@@ -48,7 +48,7 @@ EXPORTS = [
     "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
     "mtp_sample_to_cell", "mtp_relax_step",
     "mtp_relax_cell_step", "mtp_relax_cell_rebase", "mtp_relax_cell_capture_cells", "mtp_ghosts_deform",
-    "mtp_sample_cell_step",
+    "mtp_sample_cell_step", "mtp_neb_step",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -115,7 +115,7 @@ def kernel_source_hash():
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
-                      "mtp_relax_cell.hip", "mtp_relax_common.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp")
+                      "mtp_relax_cell.hip", "mtp_relax_common.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1209,6 +1209,39 @@ def sample_cell_step(ncfg, params, step, arrays, stream=None):
     rc = lib().mtp_sample_cell_step(_st(stream), int(ncfg), C.byref(params), int(step), C.byref(A))
     if rc:
         raise MtpError(rc, "mtp_sample_cell_step")
+
+
+# ---- batched nudged elastic band (include/mtp_mi355x.h)
+
+NEB_STATUS = ("running", "captured-frozen", "converged", "failed")         # band_status[b] = 0, 1, 2, 3
+NEB_MAX_IMAGES = 64
+
+
+class NebParams(C.Structure):
+    """mtp_neb_params: NebParams(RelaxParams, spring, climb_step); climb_step < 0: no image ever climbs"""
+    _fields_ = [("fire", RelaxParams), ("spring", C.c_double), ("climb_step", C.c_int)]
+
+
+NEB_ARRAYS = ("band_first", "cfg_first", "x", "v", "f", "eatom", "type", "inv_mass", "origins", "cell", "cell_inv", "fneb", "energy",
+              "dt", "alpha", "npos", "done_step", "fmax", "climber", "band_status", "frozen", "counts")
+
+
+class NebArrays(C.Structure):
+    """mtp_neb_arrays: device pointers, in the order of NEB_ARRAYS"""
+    _fields_ = [(n, C.c_void_p) for n in NEB_ARRAYS]
+
+
+def neb_step(band_first, ncfg, params, step, arrays, last=False, stream=None):
+    """one climbing-image NEB step of every running band, with the convergence decision, in one launch: mtp_neb_step.
+    `band_first` [nband + 1] is the HOST band table (int32 numpy; the argument check reads it), arrays["band_first"] its copy on
+    the device; `params` is a NebParams, `arrays` a dict of device tensors with the keys NEB_ARRAYS (float64; band_first,
+    cfg_first, type, npos, done_step, climber, band_status, frozen and counts int32).  last=True only decides."""
+    bf = np.ascontiguousarray(band_first, dtype=np.int32)
+    A = NebArrays(*[_ptr(arrays.get(n)) for n in NEB_ARRAYS])
+    rc = lib().mtp_neb_step(_st(stream), len(bf) - 1, _np(bf, C.c_int), int(ncfg), C.byref(params), int(step), int(bool(last)),
+                            C.byref(A))
+    if rc:
+        raise MtpError(rc, "mtp_neb_step")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

@@ -16,7 +16,9 @@ without the integrator; evaluate_cells does many of them -- training or candidat
 cell -- in one device pass (include/mtp_mi355x.h, "batched configurations").  sample_cells is the integrator over that
 batch layout: Langevin (or NVE) MD of all the cells at once with the extrapolation grade watched, and the extrapolating
 configurations captured, on the device (include/mtp_mi355x.h, "batched sampling"); sample_cells_npt does the same at constant
-pressure, the cells moved by a stochastic barostat ("batched constant-pressure sampling").
+pressure, the cells moved by a stochastic barostat ("batched constant-pressure sampling").  relax_cells and relax_cells_vc take
+the batch to its minima ("batched relaxation"), neb_cells connects minima by climbing-image nudged elastic bands ("batched
+nudged elastic band").
 
 torch only allocates the arrays and provides the stream; the host sees the ghost count and the list size at a
 re-neighbouring (they size arrays) and nothing else.
@@ -1939,4 +1941,190 @@ def sample_cells_npt(ctx, configs, temperature, pressure, steps, dt, *, compress
     out = setup.result(frozen=frozen_all)
     if trace:
         out["trace"]["kinetic"] = 0.5 * MVV2E * out["trace"]["kinetic"]
+    return out
+
+
+def _minimum_image(d, cell, cell_inv):
+    """d - rint(d . h^-1) . h, rows of `cell` the lattice vectors: what mtp_neb_step applies to every difference of two images"""
+    return d - np.rint(d @ cell_inv) @ cell
+
+
+def interpolate_band(pos_a, pos_b, cell, nimages):
+    """Host only: `nimages` >= 2 images from pos_a to pos_b [n, 3], linear in the minimum-image difference of the two under
+    `cell` (rows = lattice vectors) -- an atom that crosses a periodic boundary between the two takes the short way.  The first
+    image is pos_a, the last pos_a + mic(pos_b - pos_a): pos_b up to lattice vectors.  The images are continuous (not wrapped)."""
+    a = np.asarray(pos_a, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(pos_b, dtype=np.float64).reshape(-1, 3)
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    if a.shape != b.shape:
+        raise ValueError("interpolate_band: %d and %d atoms" % (len(a), len(b)))
+    if int(nimages) < 2:
+        raise ValueError("interpolate_band: at least 2 images")
+    d = _minimum_image(b - a, cell, np.linalg.inv(cell))
+    return [a + d * (i / (int(nimages) - 1.0)) for i in range(int(nimages))]
+
+
+def plan_band_passes(cells, natoms, band_first, list_cutoff, max_atoms_per_pass=None):
+    """Host arithmetic only: plan_cell_passes for a batch whose configurations [band_first[b], band_first[b + 1]) form bands
+    that must stay together.  A boundary of plan_cell_passes that falls inside a band moves to the band's start, and so does a
+    split the layout's limits ask for; a band that does not fit a pass alone raises MtpError(-24) and names the band.  The pass
+    that follows a moved boundary gains the images that were in front of it: it may hold more owned atoms than
+    `max_atoms_per_pass` (and more rows than plan_cell_passes' guard of 2^31 - 2^20), by less than one band's worth -- as a
+    single configuration above the cap does in plan_cell_passes; only the layout's limits are checked again.  Returns what
+    plan_cell_passes returns."""
+    band_first = np.asarray(band_first, dtype=np.int64)
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    cut = float(list_cutoff)
+    passes, volume, max_rows = plan_cell_passes(cells, natoms, cut, max_atoms_per_pass)
+    band_start = lambda k: int(band_first[np.searchsorted(band_first, k, side="right") - 1])
+    starts = sorted({band_start(k0) for k0, _, _ in passes})
+    queue = [(a, b) for a, b in zip(starts, starts[1:] + [len(cells)])]
+    queue.reverse()
+    out = []
+    while queue:
+        k0, k1 = queue.pop()
+        try:
+            out.append((k0, k1, capi.batch_layout(cells[k0:k1], cut, cut)))
+        except capi.MtpError as e:
+            if e.code != -24:
+                raise
+            mid = band_start(k0 + int(getattr(e, "nfit", 0)))
+            if mid <= k0:
+                raise capi.MtpError(-24, "neb_cells: band %d (configurations %d to %d) does not fit a pass on its own: %s"
+                                    % (int(np.searchsorted(band_first, k0, side="right")) - 1, k0,
+                                       int(band_first[np.searchsorted(band_first, k0, side="right")]) - 1, e)) from e
+            queue.append((mid, k1))
+            queue.append((k0, mid))
+    return out, volume, max_rows
+
+
+def _neb_arguments(bands, spring, climb_after):
+    """the host-side checks neb_cells adds to those of relax_cells (nothing here touches the device).  Returns the images of all
+    bands as configurations, the band table and the climb step."""
+    configs, band_first = [], [0]
+    if not (np.isfinite(float(spring)) and float(spring) > 0.0):
+        raise ValueError("neb_cells: spring must be positive and finite, got %r" % (spring,))
+    if climb_after is not None and int(climb_after) < 0:
+        raise ValueError("neb_cells: climb_after is a number of steps, or None for no climbing image")
+    for b, band in enumerate(bands):
+        images, cell = band[0], np.asarray(band[1], dtype=np.float64).reshape(3, 3)
+        types = band[2] if len(band) > 2 else None
+        images = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in images]
+        if not 3 <= len(images) <= capi.NEB_MAX_IMAGES:
+            raise ValueError("neb_cells: band %d has %d images: 3 to %d are possible" % (b, len(images), capi.NEB_MAX_IMAGES))
+        if len({len(p) for p in images}) != 1 or len(images[0]) == 0:
+            raise ValueError("neb_cells: band %d: every image needs the same, non-zero number of atoms, got %s"
+                             % (b, [len(p) for p in images]))
+        with np.errstate(all="ignore"):
+            cross = np.stack([np.cross(cell[1], cell[2]), np.cross(cell[2], cell[0]), np.cross(cell[0], cell[1])])
+            volume = float(cell[0] @ cross[0])
+            heights = volume / np.sqrt((cross * cross).sum(1))
+        if not (np.isfinite(cell).all() and volume > 0.0):
+            raise ValueError("neb_cells: band %d: the cell must be finite, right-handed and non-degenerate (det > 0)" % b)
+        inv = np.linalg.inv(cell)
+        for i in range(len(images) - 1):
+            d = _minimum_image(images[i + 1] - images[i], cell, inv)
+            far = float(np.sqrt((d * d).sum(1)).max())
+            if not far <= 0.25 * float(heights.min()):
+                raise ValueError("neb_cells: band %d: an atom moves %.3f A between images %d and %d, more than a quarter of the "
+                                 "smallest cell height (%.3f A): the minimum image is not exact, use more images or a larger cell"
+                                 % (b, far, i, i + 1, float(heights.min())))
+        configs += [(p, cell, types) for p in images]
+        band_first.append(len(configs))
+    return configs, np.array(band_first, dtype=np.int32), -1 if climb_after is None else int(climb_after)
+
+
+def neb_cells(ctx, bands, steps, spring=5.0, climb_after=None, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, n_min=5, f_inc=1.1,
+              f_dec=0.5, alpha_start=0.1, f_alpha=0.99, masses=183.84, grade_every=0, threshold_select=None, threshold_break=None,
+              capture_gap=0, max_candidates=None, list_cutoff=7.0, every=10, check_every=4, max_atoms_per_pass=None, device=None,
+              trace=False):
+    """What follows relax_cells in the active-learning loop: the minimum-energy paths between minima and their barriers, for a
+    whole batch of independent bands at once, device-resident -- the climbing-image nudged elastic band with the improved
+    tangent (Henkelman & Jonsson, JCP 113, 9978; Henkelman, Uberuaga & Jonsson, JCP 113, 9901), one FIRE state machine per band,
+    run by mtp_neb_step -- while the extrapolation grade is watched as in sample_cells: the transition state is where a
+    potential extrapolates most.  `bands` is a sequence of (images: [pos [n, 3], ...], cell, types): 3 to 64 images of the same
+    atoms in the same, fixed cell (interpolate_band makes a first guess).  The first and the last image are never moved.
+
+    The images of all bands are the configurations of one batch (passes, lists and capture arguments as relax_cells; a band is
+    never split between passes: plan_band_passes).  Step s = 0 ... steps is: ONE force call over all rows -> ghost fold -> on a
+    grade step mtp_sample_capture -> mtp_neb_step(s): image energies, tangents and spring forces under the minimum image (a
+    re-neighbouring wraps every image on its own), F_neb = F - (F.t) t + spring (|D+| - |D-|) t, from step `climb_after` on
+    (None: never) F - 2 (F.t) t for the interior image of highest energy, then FIRE over the interior rows of the band (the
+    FIRE arguments are those of relax_cells; `ftol` bounds the largest |F_neb| of an atom).  A band stops as "converged",
+    "failed" (a non-finite force or energy, or a vanishing tangent) or "captured-frozen" (one of its images went over threshold_break;
+    the band stops at the next mtp_neb_step); all its images are then frozen.  After step `steps` no move is made.
+
+    Refused on the host before anything touches the device (ValueError): fewer than 3 or more than 64 images, differing or zero
+    atom counts, a spring that is not positive, and a band in which an atom moves more than a quarter of the smallest cell
+    height between two neighbouring images, after minimum image -- up to there the minimum image is the true difference.
+
+    Returns dict(bands: per band dict(images: [M] positions [n, 3], made continuous along the band on the host -- the first as
+    wrapped at the last rebuild, each next one unwrapped against the one before; energies [M]; barrier_forward, barrier_backward:
+    the highest image energy minus that of the first and of the last image; highest: the index of that image; fmax: the largest
+    |F_neb| at the last step the band was looked at; status: "running", "captured-frozen", "converged" or "failed"; step: the
+    step at which it stopped, -1 otherwise; dt); candidates, records, dropped: as sample_cells, configuration numbers counting
+    the images of all bands in order; final: per image dict(x, energy); steps_done; builds) and, with trace=True (one more
+    launch and a copy a step), trace: dict(energy [steps_done + 1, number of images], fmax [steps_done + 1, number of bands])."""
+    configs, band_first, climb_step = _neb_arguments(bands, spring, climb_after)
+    (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, fire,
+     dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
+                            threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every,
+                            who="neb_cells")
+    params = capi.NebParams(fire, float(spring), climb_step)
+    setup = _RunSetup("neb_cells", ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
+                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
+                      list_cutoff, every, check_every, max_atoms_per_pass, device, ("energy", "fmax") if trace else ())
+    # _RunSetup planned the passes for configurations alone; each_pass reads the plan from this attribute, and the harness is
+    # shared with drivers that know no bands, so the plan that keeps bands together replaces it here
+    setup.plan, _, _ = plan_band_passes(all_cells, natoms, band_first, setup.cut, max_atoms_per_pass)
+    torch, dev, st = setup.torch, setup.dev, setup.st
+    results = [None] * len(bands)
+
+    def one_pass(run):
+        b0, b1 = int(np.searchsorted(band_first, run.k0)), int(np.searchsorted(band_first, run.k1))
+        nband, ncfg = b1 - b0, run.ncfg
+        bf = (band_first[b0: b1 + 1] - run.k0).astype(np.int32)
+        cells = run.cells[bf[:-1]]
+        run.v = v = setup.zeros(run.n, 3)
+        state = setup.zeros(3, nband)
+        state[0].fill_(dt)
+        state[1].fill_(fire.alpha_start)
+        ints = torch.zeros((4, nband), dtype=torch.int32, device=dev)      # npos, done_step, climber, band_status
+        ints[1:3].fill_(-1)
+        first_t = setup.to(bf[:-1].astype(np.int64))
+        A = dict(band_first=setup.to(bf), cfg_first=run.cf_t, v=v, type=run.buf.tall, inv_mass=setup.inv_mass_t, origins=run.org_t,
+                 cell=setup.to(cells.reshape(nband, 9)), cell_inv=setup.to(np.linalg.inv(cells).reshape(nband, 9)),
+                 fneb=setup.zeros(run.n, 3), energy=setup.zeros(ncfg), dt=state[0], alpha=state[1], fmax=state[2], npos=ints[0],
+                 done_step=ints[1], climber=ints[2], band_status=ints[3], frozen=run.frozen, counts=run.counts_t)
+
+        def step(s, last):
+            A.update(x=run.x, f=run.f, eatom=run.eatom)           # (a rebuild lays the work array out again)
+            capi.neb_step(bf, ncfg, params, s, A, last=last, stream=st)
+            if trace:
+                run.energies(run.trace[0, s])
+                run.trace[1, s].index_copy_(0, first_t, state[2])     # (a band's fmax sits at its first image)
+
+        s = _minimise_pass(run, setup.steps, setup.graded, step, setup.every, setup.check_every)
+
+        def final(xh, eh):
+            sh, ih = state.cpu().numpy(), ints.cpu().numpy()
+            for j in range(nband):
+                k0, k1 = int(bf[j]), int(bf[j + 1])
+                inv = np.linalg.inv(cells[j])
+                images = [xh[slice(*run.rows[k0])].copy()]
+                for k in range(k0 + 1, k1):
+                    images.append(images[-1] + _minimum_image(xh[slice(*run.rows[k])] - images[-1], cells[j], inv))
+                e = eh[k0:k1].copy()
+                top = int(np.argmax(e))
+                results[b0 + j] = dict(images=images, energies=e, barrier_forward=float(e[top] - e[0]),
+                                       barrier_backward=float(e[top] - e[-1]), highest=top, fmax=float(sh[2, j]),
+                                       status=capi.NEB_STATUS[int(ih[3, j])], step=int(ih[1, j]), dt=float(sh[0, j]))
+            return [dict(x=xh[a:b], energy=float(eh[j])) for j, (a, b) in enumerate(run.rows)]
+
+        return s, final
+
+    setup.each_pass(one_pass, lambda k: dict(x=np.zeros((0, 3)), energy=0.0), _CellRun)
+    out = setup.result(bands=results)
+    if trace:
+        out["trace"]["fmax"] = out["trace"]["fmax"][:, band_first[:-1].astype(np.int64)]
     return out
