@@ -115,7 +115,7 @@ def kernel_source_hash():
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
-                      "mtp_relax_cell.hip", "mtp_relax_common.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip")
+                      "mtp_relax_cell.hip", "mtp_batch_step.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())

@@ -4,12 +4,13 @@
 // and the ghost fold: the image energies, the tangents under the minimum image, the NEB force, ONE FIRE state machine per band
 // over its interior rows, the convergence decision and the move.  This is the one kernel of the batched family that couples
 // configurations: a workgroup owns a band.  No context, no handle: every array is the caller's, and the entry point takes the
-// stream and rejects NULL (the rule of mtp_relax_step).
-#include "mtp_relax_common.hpp"
+// stream and rejects NULL (the rule of mtp_relax_step).  The FIRE rule, its row sweeps and the fixed-order reductions are the
+// family's: mtp_batch_step.hpp.
+#include "mtp_batch_step.hpp"
 
 namespace {
 
-using namespace relax_common;   // the fixed-order reductions and the range check of the FIRE parameters
+using namespace batch_step;
 
 constexpr int NT = MTP_BATCH_BLOCK;
 
@@ -46,7 +47,7 @@ __device__ __forceinline__ void tangent_row(const double *x, size_t rm, size_t r
 __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_params p, int step, int last, mtp_neb_arrays A)
 {
   __shared__ double sE[MTP_NEB_MAX_IMAGES], sP[MTP_NEB_MAX_IMAGES], sVV[MTP_NEB_MAX_IMAGES], sFF[MTP_NEB_MAX_IMAGES],
-      sFM[MTP_NEB_MAX_IMAGES], part[RELAX_WAVES];
+      sFM[MTP_NEB_MAX_IMAGES], part[BATCH_WAVES];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int k0 = A.band_first[b], M = A.band_first[b + 1] - k0;
   if (M < 3 || M > MTP_NEB_MAX_IMAGES) return;   // (the host copy of the table was checked: the device copy must not overrun LDS)
@@ -76,11 +77,11 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_param
   }
   // 2. the energies of the images
   if (!broken)
-    for (int i = wave; i < M; i += RELAX_WAVES) {
+    for (int i = wave; i < M; i += BATCH_WAVES) {
       const double *ea = A.eatom + cfg_first[i];
       double e = 0.0;
       for (int j = lane; j < n; j += 64) e += ea[j];
-      e = relax_total<64, false>(e, part);
+      e = segment_total<64, false>(e, part);
       if (lane == 0) {
         sE[i] = e;
         A.energy[k0 + i] = e;
@@ -103,7 +104,7 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_param
     hi[a] = A.cell_inv[9 * (size_t) b + a];
   }
   if (!broken)
-    for (int i = wave; i < M; i += RELAX_WAVES) {
+    for (int i = wave; i < M; i += BATCH_WAVES) {
       const size_t r0 = (size_t) cfg_first[i];
       if (i == 0 || i == M - 1) {
         for (int j = lane; j < n; j += 64) {
@@ -138,10 +139,10 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_param
           ft += A.f[3 * (r0 + j) + a] * tau[a];
         }
       }
-      sp = relax_total<64, false>(sp, part);
-      sm = relax_total<64, false>(sm, part);
-      tt = relax_total<64, false>(tt, part);
-      ft = relax_total<64, false>(ft, part);
+      sp = segment_total<64, false>(sp, part);
+      sm = segment_total<64, false>(sm, part);
+      tt = segment_total<64, false>(tt, part);
+      ft = segment_total<64, false>(ft, part);
       const double norm = sqrt(tt), fpar = ft / norm;
       const bool bad = !(norm > 0.0 && isfinite(norm));
       const double g = (i == climber ? -2.0 * fpar : p.spring * (sqrt(sp) - sqrt(sm)) - fpar) / norm;
@@ -160,10 +161,10 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_param
         ff += f2;
         fm = fmax(fm, f2);
       }
-      P = relax_total<64, false>(P, part);
-      vv = relax_total<64, false>(vv, part);
-      ff = relax_total<64, false>(ff, part);
-      fm = relax_total<64, true>(fm, part);
+      P = segment_total<64, false>(P, part);
+      vv = segment_total<64, false>(vv, part);
+      ff = segment_total<64, false>(ff, part);
+      fm = segment_total<64, true>(fm, part);
       if (lane == 0) {
         sP[i] = P;
         sVV[i] = vv;
@@ -172,7 +173,7 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_param
       }
     }
   __syncthreads();   // the totals in LDS, and d_fneb of every image, are there for every thread
-  // 5. FIRE over the interior rows: the rules of mtp_relax_step with F_neb in place of f, ONE state machine for the band
+  // 5. FIRE over the interior rows: the rule of mtp_batch_step.hpp with F_neb in place of f, ONE state machine for the band
   double P = 0.0, vv = 0.0, ff = broken ? NAN : 0.0, fmax2 = 0.0;
   if (!broken)
     for (int i = 1; i < M - 1; i++) {
@@ -202,44 +203,16 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) neb_step_kernel(mtp_neb_param
     return;
   }
   if (last) return;
-  double dt = A.dt[b], alpha = A.alpha[b], ca, cb;
-  int npos = A.npos[b];
-  if (P > 0.0) {
-    ca = 1.0 - alpha;
-    cb = alpha * sqrt(vv / ff);
-    npos += 1;
-    if (npos > p.fire.n_min) {
-      dt = fmin(dt * p.fire.f_inc, p.fire.dt_max);
-      alpha *= p.fire.f_alpha;
-    }
-  } else {
-    ca = cb = 0.0;
-    npos = 0;
-    alpha = p.fire.alpha_start;
-    if (vv > 0.0) dt *= p.fire.f_dec;
-  }
-  double vmax = 0.0;
-  for (int r = r0 + t; r < r1; r += NT) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) vmax = fmax(vmax, fabs(ca * A.v[3 * (size_t) r + c] + cb * A.fneb[3 * (size_t) r + c]));
-  }
-  vmax = relax_total<NT, true>(vmax, part);   // (its barriers: every thread has read dt, alpha and npos before thread 0 writes them)
-  double dtv = dt;
-  if (dtv * vmax > p.fire.dmax) dtv = p.fire.dmax / vmax;
-  for (int r = r0 + t; r < r1; r += NT) {
-    const double kick = (dtv * RELAX_FTM2V) * A.inv_mass[A.type[r] - 1];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const double fc = A.fneb[3 * (size_t) r + c];
-      const double vm = ca * A.v[3 * (size_t) r + c] + cb * fc;
-      A.x[3 * (size_t) r + c] += dtv * vm;
-      A.v[3 * (size_t) r + c] = vm + kick * fc;
-    }
-  }
+  fire_state s = {A.dt[b], A.alpha[b], A.npos[b]};
+  double ca, cb;
+  fire_mix(P, vv, ff, p.fire, s, ca, cb);
+  // (the total's barriers: every thread has read dt, alpha and npos before thread 0 writes them)
+  const double vmax = segment_total<NT, true>(fire_rows_vmax<NT>(t, r0, r1, ca, cb, A.v, A.fneb), part);
+  fire_rows_move<NT>(t, r0, r1, ca, cb, fire_step(s.dt, vmax, p.fire), A.x, A.v, A.fneb, A.type, A.inv_mass);
   if (t == 0) {
-    A.dt[b] = dt;
-    A.alpha[b] = alpha;
-    A.npos[b] = npos;
+    A.dt[b] = s.dt;
+    A.alpha[b] = s.alpha;
+    A.npos[b] = s.npos;
   }
 }
 
@@ -256,9 +229,8 @@ int mtp_neb_step(void *stream, int nband, const int *band_first, int ncfg, const
   if (nband == 0) return MTP_OK;
   if (!band_first || !arrays) return MTP_ERR_ARG;
   const mtp_neb_arrays &A = *arrays;
-  if (!A.band_first || !A.cfg_first || !A.x || !A.v || !A.f || !A.eatom || !A.type || !A.inv_mass || !A.origins || !A.cell ||
-      !A.cell_inv || !A.fneb || !A.energy || !A.dt || !A.alpha || !A.npos || !A.done_step || !A.fmax || !A.climber ||
-      !A.band_status || !A.frozen || !A.counts)
+  if (any_null({A.band_first, A.cfg_first, A.x, A.v, A.f, A.eatom, A.type, A.inv_mass, A.origins, A.cell, A.cell_inv, A.fneb,
+                A.energy, A.dt, A.alpha, A.npos, A.done_step, A.fmax, A.climber, A.band_status, A.frozen, A.counts}))
     return MTP_ERR_ARG;
   if (band_first[0] < 0 || band_first[nband] > ncfg) return MTP_ERR_ARG;
   for (int b = 0; b < nband; b++) {
@@ -267,7 +239,7 @@ int mtp_neb_step(void *stream, int nband, const int *band_first, int ncfg, const
   }
   hipLaunchKernelGGL(neb_step_kernel, dim3(nband), dim3(MTP_BATCH_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), *params, step,
                      last ? 1 : 0, A);
-  return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE;
+  return launched();
 }
 
 }   // extern "C"

@@ -3,12 +3,13 @@
 // every per-atom array, positions in slot coordinates between re-neighbourings.  ONE launch a step, after the force call and
 // the ghost fold: the per-configuration reductions, the FIRE state machine, the convergence decision and the move, so that
 // nothing is read back between re-neighbourings.  No context, no handle: every array is the caller's, and the entry point
-// takes the stream and rejects NULL (the rule of mtp_sample_*).
-#include "mtp_relax_common.hpp"
+// takes the stream and rejects NULL (the rule of mtp_sample_*).  The FIRE rule, its row sweeps, the reductions and the split of a
+// workgroup over the configurations are the family's: mtp_batch_step.hpp.
+#include "mtp_batch_step.hpp"
 
 namespace {
 
-using namespace relax_common;   // the reductions and the parameter check, shared with mtp_relax_cell.hip
+using namespace batch_step;
 
 // One configuration, served by thread t of NT (all of them take every branch together: each decision is made from totals
 // that are the same in all).  Rows are read one per thread, consecutive threads consecutive rows; v' = a v + b f is computed
@@ -35,10 +36,10 @@ __device__ __forceinline__ void relax_configuration(int t, int k, int r0, int r1
     ff += f2;
     fmax2 = fmax(fmax2, f2);
   }
-  P = relax_total<NT, false>(P, part);
-  vv = relax_total<NT, false>(vv, part);
-  ff = relax_total<NT, false>(ff, part);
-  fmax2 = relax_total<NT, true>(fmax2, part);
+  P = segment_total<NT, false>(P, part);
+  vv = segment_total<NT, false>(vv, part);
+  ff = segment_total<NT, false>(ff, part);
+  fmax2 = segment_total<NT, true>(fmax2, part);
   if (t == 0) d_fmax[k] = sqrt(fmax2);
   const bool failed = !isfinite(ff);
   if (failed || fmax2 <= p.ftol * p.ftol) {
@@ -55,51 +56,19 @@ __device__ __forceinline__ void relax_configuration(int t, int k, int r0, int r1
     return;
   }
   if (last) return;
-  double dt = d_dt[k], alpha = d_alpha[k], a, b;
-  int npos = d_npos[k];
-  if (P > 0.0) {
-    a = 1.0 - alpha;
-    b = alpha * sqrt(vv / ff);
-    npos += 1;
-    if (npos > p.n_min) {
-      dt = fmin(dt * p.f_inc, p.dt_max);
-      alpha *= p.f_alpha;
-    }
-  } else {
-    a = b = 0.0;
-    npos = 0;
-    alpha = p.alpha_start;
-    if (vv > 0.0) dt *= p.f_dec;
-  }
-  double vmax = 0.0;
-  for (int r = r0 + t; r < r1; r += NT) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) vmax = fmax(vmax, fabs(a * v[3 * (size_t) r + c] + b * f[3 * (size_t) r + c]));
-  }
-  vmax = relax_total<NT, true>(vmax, part);
-  double dtv = dt;
-  if (dtv * vmax > p.dmax) dtv = p.dmax / vmax;
-  for (int r = r0 + t; r < r1; r += NT) {
-    const double kick = (dtv * RELAX_FTM2V) * inv_mass[type[r] - 1];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const double fc = f[3 * (size_t) r + c];
-      const double vm = a * v[3 * (size_t) r + c] + b * fc;
-      x[3 * (size_t) r + c] += dtv * vm;
-      v[3 * (size_t) r + c] = vm + kick * fc;
-    }
-  }
+  fire_state s = {d_dt[k], d_alpha[k], d_npos[k]};
+  double a, b;
+  fire_mix(P, vv, ff, p, s, a, b);
+  const double vmax = segment_total<NT, true>(fire_rows_vmax<NT>(t, r0, r1, a, b, v, f), part);
+  fire_rows_move<NT>(t, r0, r1, a, b, fire_step(s.dt, vmax, p), x, v, f, type, inv_mass);
   if (t == 0) {
-    d_dt[k] = dt;
-    d_alpha[k] = alpha;
-    d_npos[k] = npos;
+    d_dt[k] = s.dt;
+    d_alpha[k] = s.alpha;
+    d_npos[k] = s.npos;
   }
 }
 
-// The layout of sample_monitor_kernel / mtp_batch_reduce_kernel: a workgroup of four wavefronts owns four consecutive
-// configurations, one wavefront each for segments of up to MTP_BATCH_WAVE_ROWS rows, the whole workgroup, one after another,
-// for the longer ones.  Empty and frozen configurations are skipped: nothing of theirs is written.  The one atomic is the
-// integer count of frozen configurations; the order of every floating-point sum depends on the segment's length alone.
+// for_each_live_segment's split (mtp_batch_step.hpp).  The one atomic is the integer count of frozen configurations.
 __global__ void __launch_bounds__(MTP_BATCH_BLOCK) relax_step_kernel(int ncfg, const int *__restrict__ cfg_first,
                                                                     mtp_relax_params p, int step, int last,
                                                                     double *__restrict__ x, double *__restrict__ v,
@@ -110,24 +79,11 @@ __global__ void __launch_bounds__(MTP_BATCH_BLOCK) relax_step_kernel(int ncfg, c
                                                                     int *__restrict__ d_done_step, double *__restrict__ d_fmax,
                                                                     int *__restrict__ d_counts)
 {
-  __shared__ double part[RELAX_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k0 = blockIdx.x * RELAX_WAVES;
-  if (k0 + wave < ncfg) {   // (the whole wavefront)
-    const int k = k0 + wave, r0 = cfg_first[k], r1 = cfg_first[k + 1];
-    if (r1 > r0 && r1 - r0 <= MTP_BATCH_WAVE_ROWS && d_frozen[k] == 0)
-      relax_configuration<64>(lane, k, r0, r1, p, step, last, x, v, f, type, inv_mass, d_dt, d_alpha, d_npos, d_frozen,
-                              d_done_step, d_fmax, d_counts, part);
-  }
-  for (int w = 0; w < RELAX_WAVES && k0 + w < ncfg; w++) {   // (the whole workgroup)
-    const int k = k0 + w, r0 = cfg_first[k], r1 = cfg_first[k + 1];
-    if (r1 - r0 <= MTP_BATCH_WAVE_ROWS) continue;
-    const int fr = d_frozen[k];
-    __syncthreads();   // every thread has read the flag before thread 0 may set it
-    if (fr == 0)
-      relax_configuration<MTP_BATCH_BLOCK>(threadIdx.x, k, r0, r1, p, step, last, x, v, f, type, inv_mass, d_dt, d_alpha, d_npos,
-                                           d_frozen, d_done_step, d_fmax, d_counts, part);
-  }
+  __shared__ double part[BATCH_WAVES];
+  for_each_live_segment(ncfg, cfg_first, d_frozen, [&](auto nt, int t, int k, int r0, int r1) {
+    relax_configuration<decltype(nt)::value>(t, k, r0, r1, p, step, last, x, v, f, type, inv_mass, d_dt, d_alpha, d_npos, d_frozen,
+                                             d_done_step, d_fmax, d_counts, part);
+  });
 }
 
 }   // namespace
@@ -139,14 +95,14 @@ int mtp_relax_step(void *stream, int ncfg, const int *d_cfg_first, const mtp_rel
                    double *d_alpha, int *d_npos, int *d_frozen, int *d_done_step, double *d_fmax, int *d_counts)
 {
   if (!stream || ncfg < 0 || step < 0 || !params || !in_range(*params) ||
-      (ncfg > 0 && (!d_cfg_first || !d_x || !d_v || !d_f || !d_type || !d_inv_mass || !d_dt || !d_alpha || !d_npos ||
-                    !d_frozen || !d_done_step || !d_fmax || !d_counts)))
+      (ncfg > 0 && any_null({d_cfg_first, d_x, d_v, d_f, d_type, d_inv_mass, d_dt, d_alpha, d_npos, d_frozen, d_done_step, d_fmax,
+                             d_counts})))
     return MTP_ERR_ARG;
   if (ncfg == 0) return MTP_OK;
-  hipLaunchKernelGGL(relax_step_kernel, dim3((ncfg + RELAX_WAVES - 1) / RELAX_WAVES), dim3(MTP_BATCH_BLOCK), 0,
+  hipLaunchKernelGGL(relax_step_kernel, dim3((ncfg + BATCH_WAVES - 1) / BATCH_WAVES), dim3(MTP_BATCH_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), ncfg, d_cfg_first, *params, step, last ? 1 : 0, d_x, d_v, d_f, d_type,
                      d_inv_mass, d_dt, d_alpha, d_npos, d_frozen, d_done_step, d_fmax, d_counts);
-  return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE;
+  return launched();
 }
 
 }   // extern "C"

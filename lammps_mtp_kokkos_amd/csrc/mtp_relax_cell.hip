@@ -1,30 +1,17 @@
 // Batched variable-cell relaxation (include/mtp_mi355x.h, "batched variable-cell relaxation"): mtp_relax_step with the cell
-// among the degrees of freedom.  The layout, the wavefront / workgroup split and the fixed-order reductions are those of
-// relax_step_kernel (mtp_relax_common.hpp); the 3 x 3 quantities of a configuration -- D, h = h0 . D, W', G, the new D -- are
+// among the degrees of freedom.  The layout, the wavefront / workgroup split, the fixed-order reductions and the FIRE rule are
+// the family's (mtp_batch_step.hpp); the 3 x 3 quantities of a configuration -- D, h = h0 . D, W', G, the new D -- are
 // computed by every thread that serves it, from the same inputs in the same order, so that every branch is taken by all of
 // them together and nothing is staged.  Matrices are row-major [3 a + b]; vectors are rows (x = s . h).
-#include "mtp_relax_common.hpp"
+#include "mtp_batch_step.hpp"
 
 namespace {
 
-using namespace relax_common;
-
-// inv = m^-1 (cofactors over the determinant)
-__device__ __forceinline__ void inv3(const double *m, double det, double *inv)
-{
-  inv[0] = (m[4] * m[8] - m[5] * m[7]) / det;
-  inv[1] = (m[2] * m[7] - m[1] * m[8]) / det;
-  inv[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-  inv[3] = (m[5] * m[6] - m[3] * m[8]) / det;
-  inv[4] = (m[0] * m[8] - m[2] * m[6]) / det;
-  inv[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-  inv[6] = (m[3] * m[7] - m[4] * m[6]) / det;
-  inv[7] = (m[1] * m[6] - m[0] * m[7]) / det;
-  inv[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-}
+using namespace batch_step;
 
 // One configuration, served by thread t of NT.  Everything per configuration is read before the first reduction (in the
-// workgroup's case: before its first barrier), and thread 0 writes it back after the last one.
+// workgroup's case: before its first barrier), and thread 0 writes it back after the last one.  The row sweeps are this
+// kernel's own: the forces are transformed by D inside them.
 template <int NT>
 __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, int r1, const mtp_relax_cell_params &p, int step,
                                                          int last, const mtp_relax_cell_arrays &A, double *part)
@@ -75,10 +62,10 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
       ff += fa * fa;
     }
   }
-  P = relax_total<NT, false>(P, part);
-  vv = relax_total<NT, false>(vv, part);
-  ff = relax_total<NT, false>(ff, part);
-  fmax2 = relax_total<NT, true>(fmax2, part);
+  P = segment_total<NT, false>(P, part);
+  vv = segment_total<NT, false>(vv, part);
+  ff = segment_total<NT, false>(ff, part);
+  fmax2 = segment_total<NT, true>(fmax2, part);
   double smax = 0.0;
 #pragma unroll
   for (int q = 0; q < 9; q++) {   // the cell rows, after the atom total
@@ -119,22 +106,9 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
     return;
   }
   if (last) return;
-  double dt = A.dt[k], alpha = A.alpha[k], a, b;
-  int npos = A.npos[k];
-  if (P > 0.0) {
-    a = 1.0 - alpha;
-    b = alpha * sqrt(vv / ff);
-    npos += 1;
-    if (npos > fp.n_min) {
-      dt = fmin(dt * fp.f_inc, fp.dt_max);
-      alpha *= fp.f_alpha;
-    }
-  } else {
-    a = b = 0.0;
-    npos = 0;
-    alpha = fp.alpha_start;
-    if (vv > 0.0) dt *= fp.f_dec;
-  }
+  fire_state s = {A.dt[k], A.alpha[k], A.npos[k]};
+  double a, b;
+  fire_mix(P, vv, ff, fp, s, a, b);
   double vmax = 0.0;
   for (int r = r0 + t; r < r1; r += NT) {
     const double f0 = A.f[3 * (size_t) r], f1 = A.f[3 * (size_t) r + 1], f2 = A.f[3 * (size_t) r + 2];
@@ -144,14 +118,13 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
       vmax = fmax(vmax, fabs(a * A.vt[3 * (size_t) r + c] + b * fc));
     }
   }
-  vmax = relax_total<NT, true>(vmax, part);
+  vmax = segment_total<NT, true>(vmax, part);
 #pragma unroll
   for (int q = 0; q < 9; q++) vmax = fmax(vmax, fabs(a * vq[q] + b * G[q]));
-  double dtv = dt;
-  if (dtv * vmax > fp.dmax) dtv = fp.dmax / vmax;
+  const double dtv = fire_step(s.dt, vmax, fp);
   double Dn[9], vqn[9];
   {
-    const double kick = (dtv * RELAX_FTM2V) / p.cell_mass;
+    const double kick = (dtv * FTM2V) / p.cell_mass;
 #pragma unroll
     for (int q = 0; q < 9; q++) {
       const double vm = a * vq[q] + b * G[q];
@@ -160,7 +133,7 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
     }
   }
   for (int r = r0 + t; r < r1; r += NT) {
-    const double kick = (dtv * RELAX_FTM2V) * A.inv_mass[A.type[r] - 1];
+    const double kick = (dtv * FTM2V) * A.inv_mass[A.type[r] - 1];
     const double f0 = A.f[3 * (size_t) r], f1 = A.f[3 * (size_t) r + 1], f2 = A.f[3 * (size_t) r + 2];
     double xn[3];
 #pragma unroll
@@ -178,9 +151,9 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
     double hn[9], T[9];
     mul3(A.h0 + 9 * (size_t) k, Dn, hn);
     mul3(A.Dbinv + 9 * (size_t) k, Dn, T);
-    A.dt[k] = dt;
-    A.alpha[k] = alpha;
-    A.npos[k] = npos;
+    A.dt[k] = s.dt;
+    A.alpha[k] = s.alpha;
+    A.npos[k] = s.npos;
     A.cellmove[k] = cell_move(hn, A.href + 9 * (size_t) k, A.nimg + 3 * (size_t) k);
 #pragma unroll
     for (int q = 0; q < 9; q++) {
@@ -192,26 +165,14 @@ __device__ __forceinline__ void relax_cell_configuration(int t, int k, int r0, i
   }
 }
 
-// relax_step_kernel's split: a workgroup of four wavefronts owns four consecutive configurations, one wavefront each for
-// segments of up to MTP_BATCH_WAVE_ROWS rows, the whole workgroup, one after another, for the longer ones
+// for_each_live_segment's split (mtp_batch_step.hpp)
 __global__ void __launch_bounds__(MTP_BATCH_BLOCK) relax_cell_step_kernel(int ncfg, mtp_relax_cell_params p, int step, int last,
                                                                          mtp_relax_cell_arrays A)
 {
-  __shared__ double part[RELAX_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k0 = blockIdx.x * RELAX_WAVES;
-  if (k0 + wave < ncfg) {   // (the whole wavefront)
-    const int k = k0 + wave, r0 = A.cfg_first[k], r1 = A.cfg_first[k + 1];
-    if (r1 > r0 && r1 - r0 <= MTP_BATCH_WAVE_ROWS && A.frozen[k] == 0)
-      relax_cell_configuration<64>(lane, k, r0, r1, p, step, last, A, part);
-  }
-  for (int w = 0; w < RELAX_WAVES && k0 + w < ncfg; w++) {   // (the whole workgroup)
-    const int k = k0 + w, r0 = A.cfg_first[k], r1 = A.cfg_first[k + 1];
-    if (r1 - r0 <= MTP_BATCH_WAVE_ROWS) continue;
-    const int fr = A.frozen[k];
-    __syncthreads();   // every thread has read the flag before thread 0 may set it
-    if (fr == 0) relax_cell_configuration<MTP_BATCH_BLOCK>(threadIdx.x, k, r0, r1, p, step, last, A, part);
-  }
+  __shared__ double part[BATCH_WAVES];
+  for_each_live_segment(ncfg, A.cfg_first, A.frozen, [&](auto nt, int t, int k, int r0, int r1) {
+    relax_cell_configuration<decltype(nt)::value>(t, k, r0, r1, p, step, last, A, part);
+  });
 }
 
 // xt = (x - origin) . D^-1 per owned row (one lane a row); the first row of a configuration also leaves Dbinv = D^-1
@@ -269,16 +230,14 @@ int mtp_relax_cell_step(void *stream, int ncfg, const mtp_relax_cell_params *par
   if (ncfg > 0) {
     if (!arrays) return MTP_ERR_ARG;
     const mtp_relax_cell_arrays &A = *arrays;
-    const void *all[] = {A.cfg_first, A.x, A.xt, A.vt, A.f, A.type, A.inv_mass, A.virial, A.h0, A.origins, A.D, A.vq, A.Dbinv,
-                         A.href, A.nimg, A.dt, A.alpha, A.npos, A.frozen, A.done_step, A.fmax, A.smax, A.gcell, A.h, A.T,
-                         A.cellmove, A.counts};
-    for (const void *q : all)
-      if (!q) return MTP_ERR_ARG;
+    if (any_null({A.cfg_first, A.x, A.xt, A.vt, A.f, A.type, A.inv_mass, A.virial, A.h0, A.origins, A.D, A.vq, A.Dbinv, A.href,
+                  A.nimg, A.dt, A.alpha, A.npos, A.frozen, A.done_step, A.fmax, A.smax, A.gcell, A.h, A.T, A.cellmove, A.counts}))
+      return MTP_ERR_ARG;
   }
   if (ncfg == 0) return MTP_OK;
-  hipLaunchKernelGGL(relax_cell_step_kernel, dim3((ncfg + RELAX_WAVES - 1) / RELAX_WAVES), dim3(MTP_BATCH_BLOCK), 0,
+  hipLaunchKernelGGL(relax_cell_step_kernel, dim3((ncfg + BATCH_WAVES - 1) / BATCH_WAVES), dim3(MTP_BATCH_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), ncfg, *params, step, last ? 1 : 0, *arrays);
-  return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE;
+  return launched();
 }
 
 int mtp_relax_cell_rebase(void *stream, int ncfg, int nrows, const int *d_row_cfg, const double *d_origins, const double *d_x,
@@ -289,7 +248,7 @@ int mtp_relax_cell_rebase(void *stream, int ncfg, int nrows, const int *d_row_cf
   if (nrows == 0) return MTP_OK;
   hipLaunchKernelGGL(relax_cell_rebase_kernel, dim3((nrows + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), nrows,
                      d_row_cfg, d_origins, d_x, d_D, d_xt, d_Dbinv);
-  return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE;
+  return launched();
 }
 
 int mtp_relax_cell_capture_cells(void *stream, int ncfg, const int *d_slot, int max_candidates, const double *d_h,
@@ -300,7 +259,7 @@ int mtp_relax_cell_capture_cells(void *stream, int ncfg, const int *d_slot, int 
   if (ncfg == 0 || max_candidates == 0) return MTP_OK;
   hipLaunchKernelGGL(relax_cell_capture_cells_kernel, dim3((9 * ncfg + 255) / 256), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), ncfg, d_slot, max_candidates, d_h, d_cand_cell);
-  return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE;
+  return launched();
 }
 
 }   // extern "C"

@@ -4,21 +4,14 @@
 // between re-neighbourings.  Either side of the force call: the first half step, LAMMPS' fix langevin (uniform noise,
 // counter-based: Philox4x32-10) with the second half step in one launch, the per-configuration monitor, and the capture of
 // extrapolating configurations -- select / break decisions, slot hand-out and snapshot on the device.  No context, no
-// handle: every array is the caller's, every entry point takes the stream and rejects NULL (the rule of mtp_nve_*).
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-
-#include "../../include/mtp_mi355x.h"
-#include "mtp_device.hpp"
+// handle: every array is the caller's, every entry point takes the stream and rejects NULL (the rule of mtp_nve_*).  The unit
+// constants, the wavefront reductions and the launch epilogue are the family's: mtp_batch_step.hpp.
+#include "mtp_batch_step.hpp"
 #include "mtp_philox.hpp"
 
 namespace {
 
-// LAMMPS metal units (update.cpp): the constants of lammps_mtp_kokkos_amd/md.py
-constexpr double SAMPLE_MVV2E = 1.0364269e-4;
-constexpr double SAMPLE_FTM2V = 1.0 / SAMPLE_MVV2E;
-constexpr double SAMPLE_KB = 8.617343e-5;
+using namespace batch_step;
 
 // row_cfg[i] = the configuration of owned row i: the last k < ncfg with cfg_first[k] <= i (empty configurations share
 // their start with the next one, which this skips).  The one binary search per row of a pass.
@@ -74,8 +67,8 @@ __global__ void __launch_bounds__(256) sample_final_kernel(int nrows, const int 
   double fi[3] = {f[3 * (size_t) i], f[3 * (size_t) i + 1], f[3 * (size_t) i + 2]};
   if (THERMOSTAT) {
     const double m = mass[t];
-    const double gamma1 = -m / t_damp / SAMPLE_FTM2V;
-    const double gamma2 = sqrt(m) * sqrt(24.0 * SAMPLE_KB * temperature[k] / t_damp / dt / SAMPLE_MVV2E) / SAMPLE_FTM2V;
+    const double gamma1 = -m / t_damp / FTM2V;
+    const double gamma2 = sqrt(m) * sqrt(24.0 * KB * temperature[k] / t_damp / dt / MVV2E) / FTM2V;
     const unsigned long long kk = key[k];
     unsigned c[4] = {step, (unsigned) (i - cfg_first[k]), (unsigned) (kk & 0xffffffffull), (unsigned) (kk >> 32)};
     philox4x32_10(c, seed_lo, seed_hi);
@@ -88,19 +81,6 @@ __global__ void __launch_bounds__(256) sample_final_kernel(int nrows, const int 
   }
 #pragma unroll
   for (int a = 0; a < 3; a++) v[3 * (size_t) i + a] += dtf * im * fi[a];
-}
-
-__device__ __forceinline__ double wave_sum64(double v)   // xor butterfly: a fixed order, the same bits in every lane
-{
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max64(double v)
-{
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v = fmax(v, __shfl_xor(v, s, 64));
-  return v;
 }
 
 // what thread t of NT co-operating threads finds in rows [r0, r1): sum m v^2 and max |x - x_ref|^2
@@ -125,10 +105,11 @@ __device__ __forceinline__ void monitor_partials(int t, int r0, int r1, const do
   }
 }
 
-// The layout of mtp_batch_reduce_kernel: a workgroup of four wavefronts owns four consecutive configurations, one
-// wavefront each for segments of up to MTP_BATCH_WAVE_ROWS rows, the whole workgroup, one after another, for the longer
-// ones.  mv2[k] = sum m v^2, d2[k] = the largest squared displacement from x_ref (0 for a frozen configuration: it does
-// not move, and must not ask for a re-neighbouring).  No atomics; the order of every sum depends on the segment's length alone.
+// The split of for_each_live_segment (mtp_batch_step.hpp), written out: this kernel also serves empty and frozen
+// configurations, and combines its two values on thread 0 with one barrier pair for both, where the shared function's
+// segment_total would cost a pair for each.  mv2[k] = sum m v^2, d2[k] = the largest squared displacement from x_ref (0 for a
+// frozen configuration: it does not move, and must not ask for a re-neighbouring).  No atomics; the order of every sum
+// depends on the segment's length alone.
 __global__ void __launch_bounds__(MTP_BATCH_BLOCK) sample_monitor_kernel(int ncfg, const int *__restrict__ cfg_first,
                                                                         const int *__restrict__ frozen,
                                                                         const double *__restrict__ x,
@@ -299,8 +280,6 @@ __global__ void __launch_bounds__(256) sample_to_cell_kernel(int n3, const int *
   const int i = e / 3;
   x[e] -= origins[3 * (size_t) row_cfg[i] + (e - 3 * i)];
 }
-
-int launched() { return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE; }
 
 }   // namespace
 

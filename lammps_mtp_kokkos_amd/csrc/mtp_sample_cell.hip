@@ -1,18 +1,15 @@
 // Batched constant-pressure sampling (include/mtp_mi355x.h, "batched constant-pressure sampling"): mtp_sample_initial with the
-// cell moved by stochastic cell rescaling.  The layout, the wavefront / workgroup split and the fixed-order reductions are those
-// of relax_cell_step_kernel (mtp_relax_common.hpp); the 3 x 3 quantities of a configuration -- the kinetic tensor, the strain A,
-// E = exp(A), E^-1 -- are computed by every thread that serves it, from the same inputs in the same order, so that every branch
-// is taken by all of them together and nothing is staged.  Matrices are row-major [3 a + b]; vectors are rows (x = s . h).
+// cell moved by stochastic cell rescaling.  The layout, the wavefront / workgroup split and the fixed-order reductions are
+// the family's (mtp_batch_step.hpp, with the unit constants); the 3 x 3 quantities of a configuration -- the kinetic tensor, the
+// strain A, E = exp(A), E^-1 -- are computed by every thread that serves it, from the same inputs in the same order, so that every
+// branch is taken by all of them together and nothing is staged.  Matrices are row-major [3 a + b]; vectors are rows (x = s . h).
+#include "mtp_batch_step.hpp"
 #include "mtp_philox.hpp"
-#include "mtp_relax_common.hpp"
 
 namespace {
 
-using namespace relax_common;
+using namespace batch_step;
 
-// LAMMPS metal units (update.cpp), as mtp_sample.hip
-constexpr double NPT_MVV2E = 1.0364269e-4;
-constexpr double NPT_KB = 8.617343e-5;
 constexpr double NPT_SQRT12 = 3.4641016151377544;
 constexpr double NPT_SQRT1_2 = 0.70710678118654752;
 
@@ -58,7 +55,7 @@ __device__ __forceinline__ void sample_cell_configuration(int t, int k, int r0, 
 #pragma unroll
   for (int q = 0; q < 9; q++) h[q] = A.h[9 * (size_t) k + q];
   const double org[3] = {A.origins[3 * (size_t) k], A.origins[3 * (size_t) k + 1], A.origins[3 * (size_t) k + 2]};
-  const double V = det3(h), V0 = A.V0[k], kT = NPT_KB * A.temperature[k];
+  const double V = det3(h), V0 = A.V0[k], kT = KB * A.temperature[k];
   for (int r = r0 + t; r < r1; r += NT) {   // the kinetic tensor of the kicked velocities
     const double m = A.mass[A.type[r] - 1];
     double vk[3];
@@ -73,7 +70,7 @@ __device__ __forceinline__ void sample_cell_configuration(int t, int k, int r0, 
   bool failed = !isfinite(V) || !(V > 0.0) || !isfinite(V0) || !(V0 > 0.0);
 #pragma unroll
   for (int q = 0; q < 6; q++) {
-    kt[q] = NPT_MVV2E * relax_total<NT, false>(kt[q], part);
+    kt[q] = MVV2E * segment_total<NT, false>(kt[q], part);
     failed = failed || !isfinite(w6[q]) || !isfinite(kt[q]);
   }
   if (failed) {
@@ -168,29 +165,15 @@ __device__ __forceinline__ void sample_cell_configuration(int t, int k, int r0, 
   }
 }
 
-// relax_step_kernel's split: a workgroup of four wavefronts owns four consecutive configurations, one wavefront each for
-// segments of up to MTP_BATCH_WAVE_ROWS rows, the whole workgroup, one after another, for the longer ones
+// for_each_live_segment's split (mtp_batch_step.hpp); the two pointers it walks are taken from the argument block by value
 __global__ void __launch_bounds__(MTP_BATCH_BLOCK) sample_cell_step_kernel(sample_cell_args args)
 {
   (void) args;   // read through the kernarg segment pointer
   KP kp = (KP) __builtin_amdgcn_kernarg_segment_ptr();
-  const MTP_AS4 mtp_sample_cell_arrays &A = kp->A;
-  const int ncfg = kp->ncfg;
-  __shared__ double part[RELAX_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k0 = blockIdx.x * RELAX_WAVES;
-  if (k0 + wave < ncfg) {   // (the whole wavefront)
-    const int k = k0 + wave, r0 = A.cfg_first[k], r1 = A.cfg_first[k + 1];
-    if (r1 > r0 && r1 - r0 <= MTP_BATCH_WAVE_ROWS && A.frozen[k] == 0)
-      sample_cell_configuration<64>(lane, k, r0, r1, kp, part);
-  }
-  for (int w = 0; w < RELAX_WAVES && k0 + w < ncfg; w++) {   // (the whole workgroup)
-    const int k = k0 + w, r0 = A.cfg_first[k], r1 = A.cfg_first[k + 1];
-    if (r1 - r0 <= MTP_BATCH_WAVE_ROWS) continue;
-    const int fr = A.frozen[k];
-    __syncthreads();   // every thread has read the flag before thread 0 may set it
-    if (fr == 0) sample_cell_configuration<MTP_BATCH_BLOCK>(threadIdx.x, k, r0, r1, kp, part);
-  }
+  __shared__ double part[BATCH_WAVES];
+  for_each_live_segment(kp->ncfg, kp->A.cfg_first, kp->A.frozen, [&](auto nt, int t, int k, int r0, int r1) {
+    sample_cell_configuration<decltype(nt)::value>(t, k, r0, r1, kp, part);
+  });
 }
 
 // the ranges of the parameters; *barostat = whether the cell moves at all
@@ -220,15 +203,14 @@ int mtp_sample_cell_step(void *stream, int ncfg, const mtp_sample_cell_params *p
   if (ncfg > 0) {
     if (!arrays) return MTP_ERR_ARG;
     const mtp_sample_cell_arrays &A = *arrays;
-    const void *all[] = {A.cfg_first, A.x,    A.v,    A.f,      A.type,      A.inv_mass, A.mass,   A.virial, A.temperature, A.key, A.origins,
-                         A.V0,        A.h,    A.T,    A.href,   A.nimg,      A.frozen,   A.done_step, A.cellmove, A.capped, A.press, A.counts};
-    for (const void *q : all)
-      if (!q) return MTP_ERR_ARG;
+    if (any_null({A.cfg_first, A.x, A.v, A.f, A.type, A.inv_mass, A.mass, A.virial, A.temperature, A.key, A.origins, A.V0, A.h, A.T,
+                  A.href, A.nimg, A.frozen, A.done_step, A.cellmove, A.capped, A.press, A.counts}))
+      return MTP_ERR_ARG;
   }
   if (ncfg == 0) return MTP_OK;
-  hipLaunchKernelGGL(sample_cell_step_kernel, dim3((ncfg + RELAX_WAVES - 1) / RELAX_WAVES), dim3(MTP_BATCH_BLOCK), 0,
+  hipLaunchKernelGGL(sample_cell_step_kernel, dim3((ncfg + BATCH_WAVES - 1) / BATCH_WAVES), dim3(MTP_BATCH_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), sample_cell_args{ncfg, barostat, step, *params, *arrays});
-  return hipGetLastError() == hipSuccess ? MTP_OK : MTP_ERR_DEVICE;
+  return launched();
 }
 
 }   // extern "C"
