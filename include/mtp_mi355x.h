@@ -116,6 +116,12 @@ int mtp_potential_get_tables(const mtp_potential *pot, int32_t *alpha_index_basi
  * phase.  MTP_ERR_LIMIT (fwd_blocks still written) when no instantiation fits; any pointer may be NULL */
 int mtp_potential_kernel_shape(const mtp_potential *pot, int32_t *fwd_blocks, int32_t *block_lanes,
                                int32_t *blocks_per_lane, int32_t *max_degree);
+/* the blocks of the basic-moment pass as the kernels read them (host only), 8 ints a block: the 3 x 3 head x tail blocks
+ * of the generic kernels (five == 0) or the five-factor blocks of the fixed-shape kernels (five != 0).  Returns the
+ * number of blocks, or a negative error; `blocks` (may be NULL) must hold cap_blocks >= that many.  basic_pack (may be
+ * NULL) receives, for the basic at each LDS number, slot | a << 8 | b << 12 | c << 16 | mu << 20. */
+int mtp_potential_moment_blocks(const mtp_potential *pot, int five, int32_t *blocks /*[cap_blocks][8]*/, int cap_blocks,
+                                int32_t *basic_pack /*[B]*/);
 
 /* The device copies made in PairMTPKokkos::settings (KOKKOS/pair_mtp_kokkos.cpp:108-174).
  * Fails with MTP_ERR_DEVICE when no gfx950 device is usable: there is no CPU fallback. */

@@ -35,7 +35,7 @@ EXPORTS = [
     "mtp_ghosts_reverse", "mtp_ghosts_reverse_finish", "mtp_ghosts_types", "mtp_nve_initial", "mtp_nve_final", "mtp_nve_monitor",
     "mtp_context_set_deterministic", "mtp_zero_async", "mtp_potential_kernel_shape", "mtp_context_layout_mode",
     "mtp_ghosts_build_cell", "mtp_ghosts_cell_bounds",
-    "mtp_plan_fixed_fields", "mtp_plan_fixed_shape", "mtp_context_last_shape",
+    "mtp_plan_fixed_fields", "mtp_plan_fixed_shape", "mtp_context_last_shape", "mtp_potential_moment_blocks",
     "mtp_batch_layout", "mtp_ghosts_build_batch", "mtp_batch_reduce", "mtp_batch_cfg_grades",
     "mtp_potential_get_active_set", "mtp_potential_write_selection", "mtp_context_candidates_device",
     "mtp_batch_cfg_candidates", "mtp_maxvol_select",
@@ -306,6 +306,20 @@ class Potential:
         if rc:
             raise MtpError(rc, "%d head x tail blocks: no force kernel instantiation fits" % a.value)
         return dict(fwd_blocks=a.value, block_lanes=b.value, blocks_per_lane=c.value, max_degree=d.value)
+
+    def moment_blocks(self, five=False):
+        """the blocks of the basic-moment pass as the kernels read them (mtp_potential_moment_blocks): (blocks [n][8] int32,
+        pack [B] int32 = slot | a << 8 | b << 12 | c << 16 | mu << 20 of the basic at each LDS number).  five=False: the
+        3 x 3 head x tail blocks, five=True: the five-factor blocks of the fixed-shape kernels"""
+        n = lib().mtp_potential_moment_blocks(self.h, int(bool(five)), None, 0, None)
+        if n < 0:
+            raise MtpError(n, "moment_blocks")
+        blocks = np.zeros((n, 8), dtype=np.int32)
+        pack = np.zeros(self.sizes["B"], dtype=np.int32)
+        rc = lib().mtp_potential_moment_blocks(self.h, int(bool(five)), _np(blocks, C.c_int32), n, _np(pack, C.c_int32))
+        if rc != n:
+            raise MtpError(rc, "moment_blocks")
+        return blocks, pack
 
     def plan_fixed_fields(self, num_cus, inum, max_numneigh, variant=VARIANT_AUTO, grade=False):
         """the force kernel's template arguments and the fields of its argument block that the table structure and the

@@ -256,6 +256,20 @@ int mtp_potential_kernel_shape(const mtp_potential *p, int32_t *fwd_blocks, int3
   return MTP_OK;
 }
 
+int mtp_potential_moment_blocks(const mtp_potential *p, int five, int32_t *blocks, int cap_blocks, int32_t *basic_pack)
+{
+  if (!p || cap_blocks < 0) return MTP_ERR_ARG;
+  const std::vector<int32_t> &v = five ? p->fwd5_blocks : p->fwd_blocks;
+  const int n = five ? p->fwd5_block_count : p->fwd_block_count;
+  if (blocks) {
+    if (cap_blocks < n) return MTP_ERR_ARG;
+    if (n) std::memcpy(blocks, v.data(), (size_t) n * 8 * sizeof(int32_t));
+  }
+  if (basic_pack && !p->basic_pack_lds.empty())
+    std::memcpy(basic_pack, p->basic_pack_lds.data(), p->basic_pack_lds.size() * sizeof(int32_t));
+  return n;
+}
+
 int mtp_potential_get_tables(const mtp_potential *p, int32_t *aib, int32_t *ait, int32_t *map, double *rc,
                              double *sc, double *mc, double *inv)
 {

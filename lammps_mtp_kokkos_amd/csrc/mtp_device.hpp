@@ -78,6 +78,11 @@ struct MtpDevParams {
   // scalar map / linear coefficients / adjoint seeds: in the blob when small, else read from HBM/L2 once per atom
   // (at level 20 they are 11 KB, the difference between 3 and 4 wavefronts per CU)
   int scalars_in_lds;
+  // Five-factor blocks of the same pass (mtp_potential.hpp): nfb5 of them, int[nfb5][8] at byte off_fwd5 (below) of the
+  // blob, behind every prefix a launch copies into LDS -- read from HBM / L2, once per wavefront.  Shape fields: the
+  // fixed-shape kernels that take this table have both as constants, and the launcher matches them here.  (Both sit in
+  // padding ahead of pointers: no field moves, the block keeps its twelve lines.)
+  int nfb5;
   const int *g_map, *g_seed_idx;
   const double *g_lin, *g_seed_val;
   const MtpRow8 *rows;     // [T] by level, in HBM (always valid)
@@ -98,6 +103,7 @@ struct MtpDevParams {
   double *ev_slots;        // [8][MTP_EV_SLOTS], quantity-major
   double *cvec;            // [inum][cpad] candidate vectors dE_i/dtheta (grade calls only)
   int cpad;                // row stride of cvec and of the padded inverse active set (multiple of 16)
+  int off_fwd5;            // (see nfb5)
   double *dbasic;          // [inum][dpad] adjoints of the basics, zero padded (grade calls only)
   int dpad;                // = KL*KB of the lane grid
   int *err_flag;

@@ -31,6 +31,9 @@ template <class SH> bool selects(const MtpDevParams &p)
   if (mtp_pick_fwd_shape(p.nfb, &KL, &NB) != 0 || p.NT != 32) return false;
   const int deg = mtp_wave_kernel_deg(KL, p.P);
   const int wps = deg == mtp_wave_kernel_dlow(KL) && KL <= 32 && NB == 1 && p.wps == 3 ? 3 : 2;
+  // a shape that takes the five-factor blocks gives every block a lane of the grid (the count itself is matched below)
+  if constexpr (mtp_shape::has_nfb5<SH>::value)
+    if (p.nfb5 > KL * NB) return false;
   return KL == SH::kKL && NB == SH::kNB && MTP_PITCH == SH::kPITCH && (p.grade_flag != 0) == SH::kGRADE && deg == SH::kDEG &&
       wps == SH::kWPS && mtp_shape::matches<SH>(p);
 }

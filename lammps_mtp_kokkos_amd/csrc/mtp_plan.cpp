@@ -441,6 +441,10 @@ void build_blob(const mtp_potential &pot, const std::vector<MtpRow8> &rows8, con
   bb.off_leaf_cf = put(pot.leaf_cf.data(), pot.leaf_cf.size() * sizeof(double));
   bb.off_leaf_cb = pot.leaf_cb == pot.leaf_cf ? bb.off_leaf_cf : put(pot.leaf_cb.data(), pot.leaf_cb.size() * sizeof(double));
   bs.rows = end_prefix();
+  // behind every prefix, so in HBM / L2 only and no part of any LDS plan: the five-factor blocks of the basic-moment
+  // pass, which the kernels that take them read once per wavefront
+  bb.off_fwd5 = put(pot.fwd5_blocks.data(), pot.fwd5_blocks.size() * sizeof(int32_t));
+  bb.nfb5 = pot.fwd5_block_count;
   bb.blob_bytes = bs.norows;   // plan_launch decides per launch plan
   bb.rows_in_lds = 0;
 }
@@ -542,6 +546,7 @@ extern "C" int mtp_plan_fixed_fields(const mtp_potential *pot, int num_cus, int 
   };
 #define MTP_X(f) put(#f, p.f);
   MTP_SHAPE_INT_FIELDS(MTP_X)
+  MTP_SHAPE_EXT_FIELDS(MTP_X)
 #undef MTP_X
 #define MTP_X(f) put_all(#f, p.f, MTP_SHAPE_ARR_LEN);
   MTP_SHAPE_ARR_FIELDS(MTP_X)

@@ -605,6 +605,80 @@ int build_blocks(mtp_potential &p, std::string &err)
   return MTP_OK;
 }
 
+// Five-factor blocks of the basic-moment pass (layout: mtp_potential.hpp), beside the 3 x 3 ones: the same head x tail
+// grids, one per j = nu - a = b + c, cut into 3 heads x 2 tails or 2 heads x 3 tails, whichever takes fewer blocks for
+// the grid (the 3 x 2 cut at equal counts).  Heads and tails that no listed basic uses are left out of the grid first,
+// so a partly listed group is covered by the blocks its basics need, with -1 in the product slots that have no basic.
+// Basic indices in file numbering; relabel moves them to LDS numbering.
+int build_blocks5(mtp_potential &p, std::string &err)
+{
+  const int B = p.alpha_index_basic_count, P = p.max_alpha_index_basic, slot_count = p.slot_count;
+  std::vector<int> basic_of((size_t) slot_count * 16 * 16 * 16, -1);   // (slot, a, b, c) -> k
+  for (int i = 0; i < B; i++) {
+    const int32_t *q = &p.alpha_index_basic[4 * (size_t) i];
+    basic_of[(((size_t) (p.basic_pack[i] & 255) * 16 + q[1]) * 16 + q[2]) * 16 + q[3]] = i;
+  }
+  p.fwd5_blocks.clear();
+  p.fwd5_block_count = 0;
+  std::vector<int> covered((size_t) B, 0);
+  typedef std::pair<int, int> Pair;
+  for (int j = 0; j < P; j++) {
+    std::vector<Pair> heads, tails;   // (slot, a), (b, c)
+    auto basic = [&](const Pair &h, const Pair &t) {
+      return basic_of[(((size_t) h.first * 16 + h.second) * 16 + t.first) * 16 + t.second];
+    };
+    {
+      std::vector<Pair> all_heads, all_tails;
+      for (int nu = j; nu < P; nu++)   // (slots are numbered by nu)
+        for (int sidx = p.deg_first[nu]; sidx < p.deg_first[nu + 1]; sidx++) all_heads.push_back({sidx, nu - j});
+      for (int c = 0; c <= j; c++) all_tails.push_back({j - c, c});
+      for (const Pair &h : all_heads)
+        if (std::any_of(all_tails.begin(), all_tails.end(), [&](const Pair &t) { return basic(h, t) >= 0; })) heads.push_back(h);
+      for (const Pair &t : all_tails)
+        if (std::any_of(heads.begin(), heads.end(), [&](const Pair &h) { return basic(h, t) >= 0; })) tails.push_back(t);
+    }
+    // the blocks of the grid cut nh heads x nt tails (3 x 2 or 2 x 3), empty ones left out
+    auto cut = [&](int nh, int nt, std::vector<int32_t> *out) {
+      int count = 0;
+      for (size_t h0 = 0; h0 < heads.size(); h0 += nh)
+        for (size_t t0 = 0; t0 < tails.size(); t0 += nt) {
+          // factors 0, 1: heads; 3, 4: tails; 2: the third head (3 x 2) or the third tail (2 x 3)
+          const int hf[3] = {0, 1, 2}, tf[3] = {3, 4, 2};
+          int32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+          int16_t kk[6] = {-1, -1, -1, -1, -1, -1};
+          bool any = false;
+          for (int h = 0; h < nh && h0 + h < heads.size(); h++) w[hf[h]] |= heads[h0 + h].first | (heads[h0 + h].second << 16);
+          for (int t = 0; t < nt && t0 + t < tails.size(); t++) w[tf[t]] |= tails[t0 + t].first | (tails[t0 + t].second << 16);
+          if (nh == 3) w[2] |= (int32_t) 0x80000000u;   // shape bit: factor 2 is a head
+          for (int h = 0; h < nh && h0 + h < heads.size(); h++)
+            for (int t = 0; t < nt && t0 + t < tails.size(); t++) {
+              const int k = basic(heads[h0 + h], tails[t0 + t]);
+              if (k < 0) continue;
+              // products (0,3) (0,4) (1,3) (1,4), then (2,3) (2,4) of the 3 x 2 shape or (0,2) (1,2) of the 2 x 3 one
+              const int e = h < 2 && t < 2 ? 2 * h + t : nh == 3 ? 4 + t : 4 + h;
+              kk[e] = (int16_t) k;
+              if (out) covered[k]++;
+              any = true;
+            }
+          if (!any) continue;
+          count++;
+          if (out) {
+            std::memcpy(&w[5], kk, sizeof kk);
+            out->insert(out->end(), w, w + 8);
+          }
+        }
+      return count;
+    };
+    if (heads.empty()) continue;
+    const bool wide = cut(3, 2, nullptr) <= cut(2, 3, nullptr);
+    p.fwd5_block_count += wide ? cut(3, 2, &p.fwd5_blocks) : cut(2, 3, &p.fwd5_blocks);
+  }
+  for (int i = 0; i < B; i++)
+    if (covered[i] != 1)
+      return refuse(err, MTP_ERR_TABLE, "internal: basic moment not covered exactly once by the five-factor blocks");
+  return MTP_OK;
+}
+
 // leaf moments (mtp_potential.hpp): written by rows, never read by one, not a basic.  Their rows are deferred to the
 // end of the forward pass, which keeps the reference's in-order semantics only if no later row still adds to one of
 // the row's factors: a leaf with such a row stays an ordinary stored moment.
@@ -1030,6 +1104,13 @@ void relabel(mtp_potential &p, const std::vector<char> &leaf)
       if (k >= 0) k = (int16_t) perm[k];
     std::memcpy(&p.fwd_blocks[(size_t) 8 * blk + 3], kk, sizeof kk);
   }
+  for (int blk = 0; blk < p.fwd5_block_count; blk++) {   // and the six of each five-factor block
+    int16_t kk[6];
+    std::memcpy(kk, &p.fwd5_blocks[(size_t) 8 * blk + 5], sizeof kk);
+    for (int16_t &k : kk)
+      if (k >= 0) k = (int16_t) perm[k];
+    std::memcpy(&p.fwd5_blocks[(size_t) 8 * blk + 5], kk, sizeof kk);
+  }
 }
 
 // ---- gather programs of the product passes ---------------------------------------------------------------------
@@ -1356,6 +1437,7 @@ int mtp_potential::finalize(std::string &err)
   int rc = validate(*this, err);
   if (rc == MTP_OK) rc = build_slots(*this, err);
   if (rc == MTP_OK) rc = build_blocks(*this, err);
+  if (rc == MTP_OK) rc = build_blocks5(*this, err);
   if (rc != MTP_OK) return rc;
   const std::vector<char> leaf = find_leaves(*this, opt.leaves);
   build_levels(*this, leaf);

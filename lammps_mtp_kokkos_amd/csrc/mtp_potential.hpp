@@ -58,6 +58,15 @@ struct mtp_potential {
   // then nine int16 basic indices (head-major, -1 = no such basic) in 4.5 ints, padded}
   std::vector<int32_t> fwd_blocks;
   int fwd_block_count = 0;
+  // The same pass in five-factor blocks (the fixed-shape kernels of the narrow lane grids; the generic kernels keep the
+  // 3 x 3 blocks): a factor is a pair of table rows whose product is its value, a head {g row of slot s, x^a} or a tail
+  // {y^b, z^c}.  Factors 0, 1 are heads and 3, 4 tails; factor 2 is a third head (3 x 2 block, shape bit set) or a third
+  // tail (2 x 3 block).  Six products per block: (0,3) (0,4) (1,3) (1,4), then (2,3) (2,4) in a 3 x 2 block and (0,2)
+  // (1,2) in a 2 x 3 one.  8 ints per block: factor f in int f as {s | a<<16} or {b | c<<16}, the shape bit in bit 31
+  // of int 2, then six int16 basic indices in product order (-1 = no such basic).  A factor the block does not
+  // have reads rows 0.
+  std::vector<int32_t> fwd5_blocks;
+  int fwd5_block_count = 0;
   // per basic: slot | a<<8 | b<<12 | c<<16 | mu<<20 (what a lane needs per k)
   std::vector<int32_t> basic_pack;
   // adjoint seeds: D[idx] = val (last mapping entry wins, pair_mtp.cpp:217-218)

@@ -21,6 +21,10 @@
   X(off_seg_fwd) X(off_seg_bwd) X(rows_in_lds) X(tgt_in_lds) X(scalars_in_lds) X(dg_mode) X(fp_row) X(pow_row)        \
   X(dg_off) X(w_m) X(w_d) X(w_coef) X(w_nb) X(tab_rows) X(ov_doubles) X(m_doubles) X(d_doubles)                     \
   X(slot_mu_lo) X(slot_mu_hi)
+// int fields of tables that no launch copies into LDS (they sit behind every prefix of the blob): matched, read and
+// generated like the fields above; a list of its own because the list above is also the record of what the LDS plan
+// decides (tests/plan_dump.cpp)
+#define MTP_SHAPE_EXT_FIELDS(X) X(nfb5) X(off_fwd5)
 // int[MTP_PSTRIDE + 2] fields (a shape gives them as static constexpr int f(int k))
 #define MTP_SHAPE_ARR_FIELDS(X) X(deg_first) X(deg_coef) X(level_rows)
 #define MTP_SHAPE_ARR_LEN (MTP_PSTRIDE + 2)
@@ -39,6 +43,7 @@ namespace mtp_shape {
   template <class SH, class = void> struct has_##f : std::false_type {};            \
   template <class SH> struct has_##f<SH, std::void_t<decltype(&SH::f)>> : std::true_type {};
 MTP_SHAPE_INT_FIELDS(MTP_X)
+MTP_SHAPE_EXT_FIELDS(MTP_X)
 MTP_SHAPE_ARR_FIELDS(MTP_X)
 MTP_SHAPE_TAB_FIELDS(MTP_X)
 #undef MTP_X
@@ -50,6 +55,7 @@ template <class SH> bool matches(const MtpDevParams &p)
 #define MTP_X(f) \
   if constexpr (has_##f<SH>::value) ok = ok && p.f == SH::f;
   MTP_SHAPE_INT_FIELDS(MTP_X)
+  MTP_SHAPE_EXT_FIELDS(MTP_X)
 #undef MTP_X
 #define MTP_X(f)                    \
   if constexpr (has_##f<SH>::value) \

@@ -38,6 +38,7 @@ namespace shape_get {
     else return kp->f;                                                            \
   }
 MTP_SHAPE_INT_FIELDS(MTP_X)
+MTP_SHAPE_EXT_FIELDS(MTP_X)
 #undef MTP_X
 #define MTP_X(f)                                                                  \
   template <class SH> __device__ __forceinline__ int f(KP kp, int k)              \
@@ -126,6 +127,36 @@ template <class SH> constexpr bool block_regs_shape()
   else return false;
 }
 template <class SH> constexpr bool block_regs_ct = MTP_BLOCK_REGS && block_regs_shape<SH>();
+// Basic-moment pass in five-factor blocks (mtp_potential.hpp, fwd5_blocks) in the fixed shapes of the 3-per-SIMD build
+// that name the table (nfb5, off_fwd5) and keep a lane's block in registers (block_regs_ct: the force shape).  The 3 x 3 blocks of level 16 are half empty -- 130 basics in 26 blocks of
+// nine, because the head x tail grids are thin at both ends (16 x 1 ... 1 x 7) --, and a column costs a lane twelve
+// ds_read_b64.  Blocks of five factors and six products, cut 3 x 2 or 2 x 3 per grid, cover the same grids in 28: ten
+// reads a column, six accumulators, six reductions and six stores per atom, the indices from registers.  The table is
+// read from HBM / L2 once per wavefront: it is in no LDS prefix, so no launch plan changes.  The third factor's
+// partners differ between the two cuts: two selects per column, their mask one SGPR pair formed once per wavefront
+// (select_f64).  Every basic is the same sum over the same columns of (row x row) x (row x row), so the bits do not
+// change.  The generic kernels and the grade shape (no register to spare for the block) keep the 3 x 3 pass.
+#ifndef MTP_FWD5
+#define MTP_FWD5 1   // 0: the 3 x 3 blocks in the fixed shapes too, for A/B runs
+#endif
+template <class SH> constexpr bool fwd5_shape()
+{
+  if constexpr (mtp_shape::has_nfb5<SH>::value && mtp_shape::has_off_fwd5<SH>::value &&
+                mtp_shape::has_pow_row<SH>::value && mtp_shape::has_P<SH>::value && mtp_shape::has_tab_rows<SH>::value)
+    return SH::kWPS == 3 && SH::kNB == 1 && SH::nfb5 <= SH::kKL && SH::tab_rows * 8 * SH::kPITCH < 65536;
+  else return false;
+}
+template <class SH> constexpr bool fwd5_ct = MTP_FWD5 && fwd5_shape<SH>();
+// mask bit of the lane ? b : a, the lane mask in an SGPR pair (no VGPR holds the predicate)
+__device__ __forceinline__ double select_f64(unsigned long long mask, double a, double b)
+{
+  const unsigned alo = (unsigned) __double2loint(a), ahi = (unsigned) __double2hiint(a);
+  const unsigned blo = (unsigned) __double2loint(b), bhi = (unsigned) __double2hiint(b);
+  unsigned lo, hi;
+  asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(lo) : "v"(alo), "v"(blo), "s"(mask));
+  asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(hi) : "v"(ahi), "v"(bhi), "s"(mask));
+  return __hiloint2double((int) hi, (int) lo);
+}
 
 // Issue priority by phase (s_setprio), in the fixed FORCE shapes of the 3-per-SIMD build.  The phases of an atom want
 // opposite things of the SIMD: tile tables, basic moments, coefficient blocks and forces are VALU bursts; the loop head,

@@ -152,7 +152,45 @@
   // the 16-bit halves of bpk[h] and bpk[3 + h], decoded once per wavefront; block_offsets_to_addresses() per atom
   constexpr bool BLOCK_REGS = WPS == 3 && NB == 1 && block_regs_ct<SH>;
   unsigned bpk[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-  if constexpr (BLOCK_REGS) {
+  // fwd5_ct (mtp_wave_body.hpp): the pass in five-factor blocks, lane (q, kl) owns block kl.  The block's eight words are
+  // read from the blob in HBM / L2 once per wavefront (the table is in no LDS prefix) and stay in registers as
+  // block_regs_ct keeps the 3 x 3 offsets: bpk5[f] = row byte offsets of factor f as 16-bit halves, kk5[] = the six
+  // int16 basic indices in pairs, shape5 = the lanes whose factor 2 is a head (3 x 2 block), a lane mask in an SGPR
+  // pair.  fa[f] / fb[f]: LDS byte addresses of the two rows of factor f for this lane's neighbour column, per atom.
+  constexpr bool FWD5 = BLOCK_REGS && fwd5_ct<SH>;
+  constexpr int NACC = FWD5 ? 6 : 9;   // products of a block
+  unsigned fa[5], fb[5];
+  unsigned bpk5[5] = {0u, 0u, 0u, 0u, 0u}, kk5[3] = {0u, 0u, 0u};
+  unsigned long long shape5 = 0ull;
+  auto block5_addresses = [&]() {
+    bval[0] = kl < SHF(nfb5);
+    const unsigned tq = w.addr(w.tab + q);
+#pragma unroll
+    for (int f = 0; f < 5; f++) {
+      asm volatile("" : "+v"(bpk5[f]));   // opaque per atom: the adds stay inside the loop
+      fa[f] = tq + (bpk5[f] & 0xffffu);
+      fb[f] = tq + (bpk5[f] >> 16);
+      asm volatile("" : "+v"(fa[f]), "+v"(fb[f]));   // one finished address per register (block_addresses)
+    }
+  };
+  if constexpr (FWD5) {
+    const uint4 *bd = reinterpret_cast<const uint4 *>(kp->blob + SHF(off_fwd5)) + 2 * (kl < SHF(nfb5) ? kl : 0);
+    const uint4 lo = bd[0], hi = bd[1];
+    const unsigned wd[5] = {lo.x, lo.y, lo.z, lo.w, hi.x};
+    kk5[0] = hi.y;
+    kk5[1] = hi.z;
+    kk5[2] = hi.w;
+    const bool head2 = (wd[2] >> 31) != 0u;
+    shape5 = __ballot(head2);
+#pragma unroll
+    for (int f = 0; f < 5; f++) {   // a head {slot s, x^a} or a tail {y^b, z^c}: factor 2 by the block's shape
+      const int r0 = (int) (wd[f] & 0xffffu), r1 = (int) ((wd[f] >> 16) & 0x7fffu);
+      const bool head = f < 2 || (f == 2 && head2);
+      const unsigned o0 = (unsigned) mul24(head ? r0 : SHF(pow_row) + P + r0, 8 * PITCH);
+      const unsigned o1 = (unsigned) mul24(SHF(pow_row) + (head ? 0 : 2 * P) + r1, 8 * PITCH);
+      bpk5[f] = o0 | (o1 << 16);
+    }
+  } else if constexpr (BLOCK_REGS) {
     const int *bd = bt.fwd + 8 * (kl < SHF(nfb) ? kl : 0);
     const unsigned w0 = (unsigned) bd[0], w1 = (unsigned) bd[1], w2 = (unsigned) bd[2];
 #pragma unroll
@@ -327,12 +365,14 @@
     STAMP(1);   // compaction
     phase_prio<PHASE_PRIO, MTP_PRIO_BURST>();   // tile tables and basic moments: bursts
     // ---- 2+3. tiles: tables, then basic moments in registers ------------------------------
-    double acc[NB][9];
+    double acc[NB][NACC];
 #pragma unroll
     for (int t = 0; t < NB; t++)
 #pragma unroll
-      for (int e = 0; e < 9; e++) acc[t][e] = 0.0;
-    if constexpr (BLOCK_REGS) {
+      for (int e = 0; e < NACC; e++) acc[t][e] = 0.0;
+    if constexpr (FWD5) {
+      block5_addresses();
+    } else if constexpr (BLOCK_REGS) {
       block_offsets_to_addresses();
     } else if constexpr (WPS == 3) {
       int kl_o = kl;
@@ -351,6 +391,29 @@
         if (m * NG < ntp) {
           // the 12 reads of a block issue back to back (one LDS latency), then 6 products and 9 FMAs; the barriers
           // keep the scheduler from either splitting the burst or hoisting every column's reads (register blow-up)
+          if constexpr (FWD5) {
+            // five-factor block: ten reads, five factor values, the third factor's two partners by the block's shape,
+            // six FMAs.  A product is (row x row) x (row x row) with both inner products rounded first, as in the
+            // 3 x 3 pass (and fma(u, v, c) = fma(v, u, c)): the basics keep their bits
+            double Ra[5], Rb[5];
+#pragma unroll
+            for (int f = 0; f < 5; f++) {
+              Ra[f] = lds_ld(fa[f], m * NG);
+              Rb[f] = lds_ld(fb[f], m * NG);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            double F[5];
+#pragma unroll
+            for (int f = 0; f < 5; f++) F[f] = Ra[f] * Rb[f];
+            const double p4 = select_f64(shape5, F[0], F[3]), p5 = select_f64(shape5, F[1], F[4]);
+            acc[0][0] = fma(F[0], F[3], acc[0][0]);
+            acc[0][1] = fma(F[0], F[4], acc[0][1]);
+            acc[0][2] = fma(F[1], F[3], acc[0][2]);
+            acc[0][3] = fma(F[1], F[4], acc[0][3]);
+            acc[0][4] = fma(F[2], p4, acc[0][4]);
+            acc[0][5] = fma(F[2], p5, acc[0][5]);
+            __builtin_amdgcn_sched_barrier(0);
+          } else {
 #pragma unroll
           for (int t = 0; t < NB; t++) {
             double G[3], X[3], Y[3], Z[3];
@@ -374,6 +437,7 @@
               for (int u = 0; u < 3; u++) acc[t][3 * h + u] = fma(hd[h], tl[u], acc[t][3 * h + u]);
             __builtin_amdgcn_sched_barrier(0);
           }
+          }
         }
       }
       if (ntiles > 1) wave_fence();
@@ -384,7 +448,7 @@
 #pragma unroll
     for (int t = 0; t < NB; t++)
 #pragma unroll
-      for (int e = 0; e < 9; e++) {
+      for (int e = 0; e < NACC; e++) {
         if (NG >= 4) acc[t][e] = pair_sum16(acc[t][e]);   // KL = 16: groups differ in lane bits 4 and 5
         if (NG >= 2) acc[t][e] = pair_sum32(acc[t][e]);
       }
@@ -408,7 +472,17 @@
       }
     }
 #endif
-    if (q == 0) {
+    if constexpr (FWD5) {
+      if (q == 0 && bval[0]) {
+        // the block's six int16 basic indices in product order (-1: no such basic), from the registers
+#pragma unroll
+        for (int e = 0; e < 6; e++) {
+          asm volatile("" : "+v"(kk5[e >> 1]));   // (opaque per atom: the unpacked indices are not kept across the loop)
+          const int k = (int) (short) (kk5[e >> 1] >> (16 * (e & 1)));
+          if (k >= 0) w.M[k] = acc[0][e];
+        }
+      }
+    } else if (q == 0) {
 #pragma unroll
       for (int t = 0; t < NB; t++)
         if (bval[t]) {
