@@ -831,6 +831,60 @@ typedef struct mtp_neb_arrays {
 int mtp_neb_step(void *stream, int nband, const int *band_first /* host */, int ncfg, const mtp_neb_params *params, int step,
                  int last, const mtp_neb_arrays *arrays);
 
+/* ---- batched force constants: the Hessian of every configuration of a batch by central differences ----------------------
+ *
+ * What follows the stationary points: their second derivatives (is a minimum a minimum, has a saddle one unstable mode, the
+ * harmonic prefactor of a rate, Gamma-point phonons).  H = -dF/dx by central differences of the forces with a step h that is
+ * far inside the skin: ONE ghost build and ONE list serve all the force calls of a pass, and nothing is read back between
+ * them.  Layout, slot coordinates and force call are those of the batched relaxation.
+ *
+ * Selection: configuration j differentiates with respect to m_j <= n_j of its owned atoms, sel[sel_first[j] ...
+ * sel_first[j + 1]) -- ROW numbers of the batch, each within the configuration's own rows, none repeated.
+ * H_j is [3 m_j][3 m_j], row-major, at H + h_first[j], h_first[j] = sum_{i < j} (3 m_i)^2.  Row c = 3 a + d is the displaced
+ * coordinate (selected atom a, direction d), column r = 3 b + e the responding one (the force on selected atom b along e).
+ *
+ * A pass is K + 1 launches of mtp_hess_step, K = 6 sel_max with sel_max >= every m_j, around K + 1 force calls:
+ *   x0 = x;  for k = 0 ... K:  mtp_ghosts_forward -> force call with MTP_ENERGY_ATOM -> mtp_ghosts_reverse[_finish]
+ *                               -> mtp_hess_step(k)
+ *   mtp_hess_finish
+ * Displacement k < K moves the selected atom a = k / 6 of every configuration with m_j > a along d = (k % 6) / 2, by +h for
+ * even k and by -h for odd k.  Launch k, for a configuration with status[j] == 0 (any other is skipped: nothing of it is
+ * written) and at least one row:
+ *   1. k == 0: f0 = f on its owned rows, fmax[j] = sqrt(the largest |f0|^2 of a row), energy[j] = the sum of its rows of
+ *      eatom.  A component of f0 that is not finite -- or a selection that is longer than the configuration or sel_max or
+ *      names a row outside the configuration -- sets status[j] = MTP_HESS_FAILED; no displacement is made.
+ *   2. k >= 1, m_j > a' (a', d' of displacement k - 1, row c = 3 a' + d'): f holds the forces of that displacement.  After a
+ *      +h call the row is parked, H[c][r] = f[sel b][e]; after the -h call H[c][r] = (f[sel b][e] - H[c][r]) * inv2h with
+ *      inv2h = 1 / (2 h) computed once on the host in double -- this expression and no other.  If one of the 3 m_j components
+ *      is not finite, nothing of the row is written and status[j] = MTP_HESS_FAILED.
+ *   3. k >= 1, m_j > a': the moved coordinate is put back from the saved copy, x[row][d'] = x0[row][d'] (a failed
+ *      configuration too: after the pass x == x0 to the bit).
+ *   4. k < K, m_j > a, not failed: x[row][d] = x0[row][d] + h, or x0[row][d] - h.
+ * Segments of up to 256 rows are served by a wavefront, longer ones by the workgroup (the split of mtp_relax_step); every
+ * floating-point sum has a fixed order and every expression is evaluated as written (no fused multiply-add): a
+ * configuration's result depends on its own rows only, whatever the batch around it.
+ * MTP_ERR_ARG, nothing launched: a NULL stream, ncfg < 0, sel_max < 0 or above MTP_HESS_MAX_SELECTED, k outside
+ * [0, 6 sel_max], h not finite or <= 0, a missing array (ncfg > 0).  ncfg == 0 launches nothing.  The caller starts status,
+ * fmax and energy at 0. */
+#define MTP_HESS_FAILED 1
+#define MTP_HESS_MAX_SELECTED (1 << 28)
+int mtp_hess_step(void *stream, int ncfg, const int *d_cfg_first, const int *d_sel_first, const int *d_sel, int sel_max, int k,
+                  double h, double *d_x, const double *d_x0, const double *d_f, const double *d_eatom, const long long *d_h_first,
+                  double *d_H, double *d_f0, double *d_fmax, double *d_energy, int *d_status);
+/* The end of a pass, one launch, for every configuration with status[j] == 0 and m_j > 0 (a wavefront for up to 256 selected
+ * atoms, the workgroup for more):
+ *   1. diag[j][0] = asymmetry = max |H_cr - H_rc| of the matrix as harvested (an O(h^2) truncation quantity)
+ *   2. diag[j][1] = sum_rule = max_{c, e} |sum_b H[c][3 b + e]|, also of the matrix as harvested, the sum over b = 0 ...
+ *      m_j - 1 in that order: the total force that displacement c left on the selected atoms, over 2 h -- the
+ *      translation-invariance residual of the force call, of rounding size when m_j = n_j and meaningless otherwise.  (The
+ *      column sums, and with them the row sums of the symmetrised matrix, vanish only to O(h^2).)
+ *   3. H <- 0.5 (H + H^T): a pair is read once and both members are written by the same thread
+ *   4. mass_weight != 0: H[c][r] *= 1 / sqrt(M_a M_b), M = d_mass[d_type[row] - 1]
+ * MTP_ERR_ARG, nothing launched: a NULL stream, ncfg < 0, a missing array (ncfg > 0). */
+int mtp_hess_finish(void *stream, int ncfg, const int *d_sel_first, const int *d_sel, const int *d_type, const double *d_mass,
+                    int mass_weight, const long long *d_h_first, double *d_H, double *d_diag /* [ncfg][2] */,
+                    const int *d_status);
+
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------
  *

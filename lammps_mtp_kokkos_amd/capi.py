@@ -48,7 +48,7 @@ EXPORTS = [
     "mtp_sample_row_map", "mtp_sample_initial", "mtp_sample_final", "mtp_sample_monitor", "mtp_sample_capture",
     "mtp_sample_to_cell", "mtp_relax_step",
     "mtp_relax_cell_step", "mtp_relax_cell_rebase", "mtp_relax_cell_capture_cells", "mtp_ghosts_deform",
-    "mtp_sample_cell_step", "mtp_neb_step",
+    "mtp_sample_cell_step", "mtp_neb_step", "mtp_hess_step", "mtp_hess_finish",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -115,7 +115,8 @@ def kernel_source_hash():
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
-                      "mtp_relax_cell.hip", "mtp_batch_step.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip")
+                      "mtp_relax_cell.hip", "mtp_batch_step.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip",
+                      "mtp_hess.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1256,6 +1257,34 @@ def neb_step(band_first, ncfg, params, step, arrays, last=False, stream=None):
                             C.byref(A))
     if rc:
         raise MtpError(rc, "mtp_neb_step")
+
+
+# ---- batched force constants (include/mtp_mi355x.h)
+
+HESS_STATUS = ("ok", "failed")                                              # status_t[j] = 0, 1
+HESS_MAX_SELECTED = 2 ** 28
+
+
+def hess_step(cfg_first_t, sel_first_t, sel_t, sel_max, k, h, x_t, x0_t, f_t, eatom_t, h_first_t, H_t, f0_t, fmax_t, energy_t,
+              status_t, stream=None):
+    """launch k = 0 ... 6 sel_max of a pass of central differences: harvest displacement k - 1 into its row of H, put the moved
+    coordinate back from x0_t, make displacement k: mtp_hess_step.  sel_first_t [ncfg + 1], sel_t (row numbers) and status_t
+    [ncfg] are int32, h_first_t [ncfg] int64; H_t holds the [3 m][3 m] matrices one after another; f0_t [n, 3], fmax_t and
+    energy_t [ncfg] are written by launch 0."""
+    rc = lib().mtp_hess_step(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), _ptr(sel_first_t), _ptr(sel_t), int(sel_max),
+                             int(k), C.c_double(h), _ptr(x_t), _ptr(x0_t), _ptr(f_t), _ptr(eatom_t), _ptr(h_first_t), _ptr(H_t),
+                             _ptr(f0_t), _ptr(fmax_t), _ptr(energy_t), _ptr(status_t))
+    if rc:
+        raise MtpError(rc, "mtp_hess_step")
+
+
+def hess_finish(sel_first_t, sel_t, type_t, mass_t, mass_weight, h_first_t, H_t, diag_t, status_t, stream=None):
+    """the end of a pass: diag_t [ncfg, 2] = (asymmetry, sum_rule), H <- 0.5 (H + H^T), with mass_weight divided by
+    sqrt(M_a M_b) (mass_t per type): mtp_hess_finish"""
+    rc = lib().mtp_hess_finish(_st(stream), int(sel_first_t.numel()) - 1, _ptr(sel_first_t), _ptr(sel_t), _ptr(type_t), _ptr(mass_t),
+                               int(bool(mass_weight)), _ptr(h_first_t), _ptr(H_t), _ptr(diag_t), _ptr(status_t))
+    if rc:
+        raise MtpError(rc, "mtp_hess_finish")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

@@ -2128,3 +2128,205 @@ def neb_cells(ctx, bands, steps, spring=5.0, climb_after=None, ftol=1e-3, dt=1e-
     if trace:
         out["trace"]["fmax"] = out["trace"]["fmax"][:, band_first[:-1].astype(np.int64)]
     return out
+
+
+def _hessian_selections(atoms, natoms):
+    """the selected atoms of every configuration as int64 index arrays (None: all of them, in order); out of range or repeated
+    entries raise"""
+    if atoms is None:
+        atoms = [None] * len(natoms)
+    if len(atoms) != len(natoms):
+        raise ValueError("hessian_cells: atoms is None or one entry per configuration (%d), got %d" % (len(natoms), len(atoms)))
+    out = []
+    for k, a in enumerate(atoms):
+        n = int(natoms[k])
+        a = np.arange(n, dtype=np.int64) if a is None else np.asarray(a, dtype=np.int64).reshape(-1)
+        if len(a) and (a.min() < 0 or a.max() >= n):
+            raise ValueError("hessian_cells: configuration %d: atoms must be in [0, %d)" % (k, n))
+        if len(np.unique(a)) != len(a):
+            raise ValueError("hessian_cells: configuration %d: an atom is selected more than once" % k)
+        out.append(a)
+    return out
+
+
+def _hessian_sizes(nsel, max_hessian_bytes):
+    """the bytes of every configuration's Hessian, (3 m_j)^2 * 8; one above `max_hessian_bytes` on its own raises, named"""
+    size = 8 * (3 * np.asarray(nsel, dtype=np.int64)) ** 2
+    over = np.nonzero(size > int(max_hessian_bytes))[0]
+    if len(over):
+        raise ValueError("hessian_cells: configuration %d: its Hessian of %d selected atoms takes %d bytes, above max_hessian_bytes "
+                         "(%d)" % (int(over[0]), int(nsel[over[0]]), int(size[over[0]]), int(max_hessian_bytes)))
+    return size
+
+
+def cut_hessian_passes(plan, cells, nsel, list_cutoff, max_hessian_bytes=2 ** 31):
+    """Host arithmetic only: the passes `plan` of plan_cell_passes cut further so that the Hessians of a pass, sum (3 m_j)^2 * 8
+    bytes with m_j = nsel[j] selected atoms, stay within `max_hessian_bytes` (a configuration is never split; one that is above
+    the limit on its own raises, named).  A pass that is cut gets the layouts of its pieces."""
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    size, limit = _hessian_sizes(nsel, max_hessian_bytes), int(max_hessian_bytes)
+    cut, out = float(list_cutoff), []
+    for k0, k1, lay in plan:
+        pieces, begin, used = [], k0, 0
+        for k in range(k0, k1):
+            if k > begin and used + int(size[k]) > limit:
+                pieces.append((begin, k))
+                begin, used = k, 0
+            used += int(size[k])
+        pieces.append((begin, k1))
+        out += [(k0, k1, lay)] if len(pieces) == 1 else [(a, b, capi.batch_layout(cells[a:b], cut, cut)) for a, b in pieces]
+    return out
+
+
+def hessian_cells(ctx, configs, h=0.01, atoms=None, mass_weight=False, masses=183.84, list_cutoff=7.0, max_atoms_per_pass=None,
+                  max_hessian_bytes=2 ** 31, device=None):
+    """What follows relax_cells and neb_cells: the second derivatives at their stationary points, for a whole batch of
+    independent periodic cells at once, device-resident -- force constants by central differences of the forces with the step
+    `h` [A].  `configs` and the passes are those of evaluate_cells (`list_cutoff`, `max_atoms_per_pass`); a displacement of `h`
+    is far inside the skin (list_cutoff - the potential's cutoff; h >= half of it raises), so ONE ghost build and ONE list serve
+    all the force calls of a pass: 6 max_j m_j + 1 of them, each followed by ONE launch of mtp_hess_step, which harvests the
+    forces of the displacement just made into its row of H, restores the coordinate from the saved copy and makes the next
+    displacement.  Nothing is read back before the end of the pass, where mtp_hess_finish measures the asymmetry and the sum rule
+    and symmetrises.
+
+    `atoms`: None (every atom), or one entry per configuration: None, or the indices (into its `pos`) of the m atoms whose
+    coordinates are differentiated -- the others stay where they are, and H is the [3 m, 3 m] block of those atoms in the order
+    given.  Entries out of range or repeated raise.  mass_weight=True divides H[3a+d, 3b+e] by sqrt(M_a M_b) on the device
+    (`masses`: one, or one per atom type [g/mol]).  The passes are cut further so that the Hessians of one pass stay within
+    `max_hessian_bytes` (cut_hessian_passes; a single configuration above it raises, named).
+
+    Returns one dict per configuration: hessian [3 m, 3 m] (symmetrised; eV/A^2, or eV/(A^2 g/mol) when mass-weighted; row
+    3 a + d is the displaced coordinate, column 3 b + e the responding one), atoms [m], energy and f0 [n, 3] (in the order of
+    `pos`) at the undisplaced positions, fmax = the largest |f0_i|, asymmetry = max |H_cr - H_rc| before symmetrising (an
+    O(h^2) truncation quantity), sum_rule = max |sum_b H[c, 3 b + e]| (below), status: "ok" or "failed" (a force that was not
+    finite: the Hessian is then NaN; the other configurations are not affected).  An empty configuration, or an empty
+    selection, gives a (0, 0) Hessian.
+
+    sum_rule is taken from the matrix AS HARVESTED, before it is symmetrised, like the asymmetry -- not from the returned
+    `hessian`.  Row c of the harvested matrix holds the forces that displacement c left on the selected atoms, over 2 h; summed
+    over all atoms they vanish to rounding (Newton's third law in the force call), so for a full selection sum_rule is the
+    translation-invariance residual of the force path and stays within 3 n times the force parity bound over h.  The column
+    sums, and with them the row sums of the symmetrised `hessian`, vanish only to O(h^2) and have no such bound; that is why
+    modes() projects the translations out instead of relying on them."""
+    items, all_cells, natoms = _batch_items(configs)
+    h = float(h)
+    if not (h > 0.0 and np.isfinite(h)):
+        raise ValueError("hessian_cells: h must be positive and finite, got %r" % (h,))
+    select, brk, mass_of_type, _ = _run_arguments("hessian_cells", items, masses, None, None, 0, 0, 0, 1, 0)
+    selections = _hessian_selections(atoms, natoms)
+    nsel = np.array([len(a) for a in selections], dtype=np.int64)
+    skin = float(list_cutoff) - float(ctx.pot.info.max_cutoff)
+    if not h < 0.5 * skin:
+        raise ValueError("hessian_cells: h (%g A) must stay below half the skin (list_cutoff - cutoff = %g A): the list has to "
+                         "hold for every displaced copy" % (h, skin))
+    _hessian_sizes(nsel, max_hessian_bytes)                   # (a configuration too large raises before anything is set up)
+    setup = _RunSetup("hessian_cells", ctx, items, all_cells, natoms, mass_of_type, 0, 0, False, select, brk, 0, 0, list_cutoff, 1, 0,
+                      max_atoms_per_pass, device, ())
+    # _RunSetup planned the passes for the atoms alone; each_pass reads the plan from this attribute (as in neb_cells)
+    setup.plan = cut_hessian_passes(setup.plan, all_cells, nsel, setup.cut, max_hessian_bytes)
+    torch, dev, st, to = setup.torch, setup.dev, setup.st, setup.to
+
+    def empty(k):
+        return dict(hessian=np.zeros((0, 0)), atoms=selections[k], energy=0.0, f0=np.zeros((0, 3)), fmax=0.0, asymmetry=0.0,
+                    sum_rule=0.0, status=capi.HESS_STATUS[0])
+
+    def one_pass(run):
+        k0, ncfg, n = run.k0, run.ncfg, run.n
+        m = nsel[k0: run.k1]
+        sel = np.concatenate([run.rows[j][0] + selections[k0 + j] for j in range(ncfg)] + [np.zeros(1, dtype=np.int64)])
+        first = np.concatenate([[0], np.cumsum((3 * m) ** 2)])
+        sel_first_t, sel_t = to(np.concatenate([[0], np.cumsum(m)]).astype(np.int32)), to(sel.astype(np.int32))
+        h_first_t = to(first[:-1].astype(np.int64))
+        H = setup.zeros(max(int(first[-1]), 1))
+        x0 = run.x[:n].clone()
+        f0, state, diag = setup.zeros(n, 3), setup.zeros(2, ncfg), setup.zeros(ncfg, 2)
+        status = torch.zeros(ncfg, dtype=torch.int32, device=dev)
+        sel_max = int(m.max())
+        for k in range(6 * sel_max + 1):
+            run.forces(False)
+            capi.hess_step(run.cf_t, sel_first_t, sel_t, sel_max, k, h, run.x, x0, run.f, run.eatom, h_first_t, H, f0, state[0],
+                           state[1], status, stream=st)
+        capi.hess_finish(sel_first_t, sel_t, run.buf.tall, setup.mass_t, mass_weight, h_first_t, H, diag, status, stream=st)
+
+        def final(xh, eh):
+            Hh, fh, sh, dh, th = H.cpu().numpy(), f0.cpu().numpy(), state.cpu().numpy(), diag.cpu().numpy(), status.cpu().numpy()
+            out = []
+            for j, (a, b) in enumerate(run.rows):
+                if b == a:
+                    out.append(empty(k0 + j))
+                    continue
+                N = 3 * int(m[j])
+                Hj = Hh[int(first[j]): int(first[j]) + N * N].reshape(N, N).copy()
+                if th[j]:
+                    Hj[:] = np.nan
+                out.append(dict(hessian=Hj, atoms=selections[k0 + j], energy=float(sh[1, j]), f0=fh[a:b], fmax=float(sh[0, j]),
+                                asymmetry=float(dh[j, 0]), sum_rule=float(dh[j, 1]), status=capi.HESS_STATUS[int(th[j])]))
+            return out
+
+        return 0, final
+
+    setup.each_pass(one_pass, empty, _CellRun)
+    return setup.final
+
+
+def modes(hessian, masses_of_atoms, project_translations=True, zero_tol=1e-3):
+    """Host only: the normal modes of one Hessian of hessian_cells.  `hessian` [3 m, 3 m] in eV/A^2 with `masses_of_atoms` [m]
+    (or one mass) in g/mol -- it is mass-weighted here, D = H / sqrt(M_a M_b) --, or already mass-weighted with
+    masses_of_atoms=None (then the translations are taken as uniform).  With `project_translations` the three uniform
+    translations are projected out of D first (they come out as zero modes to rounding); this is meaningful for a FULL selection
+    only: pass False for the block of a partial one.  numpy's eigh, eigenvalues lambda ascending.
+
+    Returns dict(frequencies [3 m] in THz, nu = sign(lambda) sqrt(|lambda| FTM2V) / (2 pi): unstable modes come out NEGATIVE, the
+    convention of phonon codes; eigenvectors [3 m, 3 m], column i the mass-weighted mode of frequencies[i]; eigenvalues [3 m] in
+    eV/(A^2 g/mol); n_unstable: the modes with nu < -zero_tol; n_zero: those with |nu| <= zero_tol [THz])."""
+    H = np.array(hessian, dtype=np.float64)
+    if H.ndim != 2 or H.shape[0] != H.shape[1] or H.shape[0] % 3:
+        raise ValueError("modes: the Hessian must be [3 m, 3 m], got %r" % (H.shape,))
+    if not np.isfinite(H).all():
+        raise ValueError("modes: the Hessian is not finite (a failed configuration?)")
+    if not (float(zero_tol) >= 0.0):
+        raise ValueError("modes: zero_tol must not be negative")
+    m = H.shape[0] // 3
+    if masses_of_atoms is None:
+        root = np.ones(3 * m)
+    else:
+        M = np.asarray(masses_of_atoms, dtype=np.float64).reshape(-1)
+        M = np.full(m, M[0]) if len(M) == 1 else M
+        if len(M) != m or not ((M > 0.0).all() and np.isfinite(M).all()):
+            raise ValueError("modes: masses_of_atoms is one positive mass, or one per atom (%d)" % m)
+        root = np.repeat(np.sqrt(M), 3)
+        H = H / np.outer(root, root)
+    H = 0.5 * (H + H.T)
+    if project_translations and m:
+        T = np.zeros((3 * m, 3))
+        for d in range(3):
+            T[d::3, d] = root[d::3]
+        T /= np.linalg.norm(T, axis=0)
+        P = np.eye(3 * m) - T @ T.T
+        H = P @ H @ P
+        H = 0.5 * (H + H.T)
+    lam, vec = np.linalg.eigh(H) if m else (np.zeros(0), np.zeros((0, 0)))
+    nu = np.sign(lam) * np.sqrt(np.abs(lam) * FTM2V) / (2.0 * np.pi)
+    return dict(frequencies=nu, eigenvectors=vec, eigenvalues=lam, n_unstable=int((nu < -zero_tol).sum()),
+                n_zero=int((np.abs(nu) <= zero_tol).sum()))
+
+
+def vineyard_prefactor(freq_min, freq_saddle, zero_tol=1e-3):
+    """Host only: the harmonic transition-state prefactor of Vineyard (J. Phys. Chem. Solids 3, 121), nu* = prod nu_min /
+    prod' nu_saddle over the stable, non-zero modes (nu > zero_tol) of modes() at the minimum and at the saddle, in the unit of
+    the frequencies (THz); the rate is nu* exp(-barrier / kB T).  Evaluated through sums of logarithms.  Raises unless the
+    minimum has no unstable mode, the saddle exactly one (nu < -zero_tol), and the saddle one stable mode fewer than the
+    minimum."""
+    lo, hi = np.asarray(freq_min, dtype=np.float64).reshape(-1), np.asarray(freq_saddle, dtype=np.float64).reshape(-1)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("vineyard_prefactor: the frequencies must be finite")
+    if int((lo < -zero_tol).sum()):
+        raise ValueError("vineyard_prefactor: the minimum has %d unstable modes: it is no minimum" % int((lo < -zero_tol).sum()))
+    if int((hi < -zero_tol).sum()) != 1:
+        raise ValueError("vineyard_prefactor: the saddle has %d unstable modes, a first-order saddle has exactly one"
+                         % int((hi < -zero_tol).sum()))
+    stable_lo, stable_hi = lo[lo > zero_tol], hi[hi > zero_tol]
+    if len(stable_hi) != len(stable_lo) - 1:
+        raise ValueError("vineyard_prefactor: %d stable modes at the minimum, %d at the saddle: the saddle must have one fewer"
+                         % (len(stable_lo), len(stable_hi)))
+    return float(np.exp(np.log(stable_lo).sum() - np.log(stable_hi).sum()))
