@@ -391,8 +391,9 @@ int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x /*[capacity][3]*/,
  * Any number of images per direction, no lower limit on the cell size.  Ghost order, capacity protocol, the single
  * stream synchronisation and the NULL-stream rule as for mtp_ghosts_build; shift[k] = n . cell.  MTP_ERR_ARG for a
  * cell with det <= 0 or non-finite entries (nothing is launched); MTP_ERR_LIMIT, *nall_out = INT_MAX, when owned +
- * ghost atoms do not fit an int (never wrapped).  mtp_ghosts_forward / reverse / reverse_finish / types then work
- * on the handle unchanged. */
+ * ghost atoms do not fit an int (never wrapped).  nlocal == 0: MTP_OK, *nall_out = 0, nothing is launched and the
+ * stream is not synchronised (as in mtp_ghosts_build_batch).  mtp_ghosts_forward / reverse / reverse_finish / types
+ * then work on the handle unchanged. */
 int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x /*[capacity][3]*/, int nlocal, int capacity,
                           const double cell[9], double rghost, int *nall_out);
 /* Host arithmetic only: bounds of every position mtp_ghosts_build_cell can write for this cell and rghost (the lo / hi

@@ -83,10 +83,13 @@ __global__ void __launch_bounds__(256) ghosts_fill_kernel(Box3 b, const double *
       }
 }
 
-// ---- any periodic cell (mtp_ghosts_build_cell): rows of h are the lattice vectors, hinv its inverse, s = x . hinv the
-// fractional coordinates, m[a] = rghost / (spacing of the lattice planes normal to direction a).  The image of an atom
-// under the integer shift n is a ghost iff -m[a] <= s[a] + n[a] < 1 + m[a] in all three directions (the slab criterion of
-// LAMMPS' triclinic ghost cutoffs): separable, so the allowed n[a] form the closed range below and nothing is looped over.
+// ---- any periodic cell, one or many (mtp_ghosts_build_cell, mtp_ghosts_build_batch): rows of h are the lattice vectors,
+// hinv its inverse, s = x . hinv the fractional coordinates, m[a] = rghost / (spacing of the lattice planes normal to
+// direction a).  The image of an atom under the integer shift n is a ghost iff -m[a] <= s[a] + n[a] < 1 + m[a] in all three
+// directions (the slab criterion of LAMMPS' triclinic ghost cutoffs): separable, so the allowed n[a] form the closed range
+// below and nothing is looped over.  ONE criterion (wrap_and_count, shift_of) and TWO sources of the cell (OneCell,
+// SlotCells): the numpy twins in driver.py agree bit for bit with both builds because the arithmetic below is rounded one
+// operation at a time, in this order, in this one place.
 struct Cell9 {
   double h[9], hinv[9], m[3];
 };
@@ -95,41 +98,112 @@ struct Cell9 {
 // the wrapped Cartesian position ((s . h) . hinv may land one ulp on the other side of a bound, and the fill would then
 // write past its atom's slots)
 struct alignas(16) ShiftRange {
-  int lo[3], cnt[3], pad[2];   // n[a] in [lo[a], lo[a] + cnt[a]); 32 bytes, two 16-byte stores / loads
+  int lo[3], cnt[3], pad[2];   // n[a] in [lo[a], lo[a] + cnt[a]); pad[0] the configuration; 32 bytes, two 16-byte stores / loads
 };
 
-// wraps the owned atoms into s in [0, 1)^3 and counts their images.  SUM64 (only when the host cannot rule out a total
-// beyond int from the margins alone): count[i] saturates at INT_MAX and the exact total goes to *total64, one atomic per
-// block, so that such a total is seen on the host rather than wrapped by the scan
-template <bool SUM64>
-__global__ void __launch_bounds__(256) ghosts_cell_count_kernel(Cell9 c, double *__restrict__ x, int n, int *__restrict__ count,
+// wraps p into s in [0, 1)^3 of the cell -> w = s . h (+ org when there is one: a separate rounded add, and none at all
+// without, since + 0.0 would turn a -0.0 coordinate into +0.0), the shift ranges r.lo / r.cnt, and the number of images,
+// saturated at 2^32 - 1 (2^31 atoms of these still sum below 2^64)
+__device__ __forceinline__ unsigned long long wrap_and_count(const double *__restrict__ h, const double *__restrict__ hinv,
+                                                             const double *__restrict__ m, const double *__restrict__ org,
+                                                             const double p[3], double w[3], ShiftRange &r)
+{
+  double s[3];
+  unsigned long long prod = 1;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    // (products and sums rounded one by one, in this order: the numpy twin in driver.make_ghosts_cell does the same)
+    double v = __dadd_rn(__dadd_rn(__dmul_rn(p[0], hinv[a]), __dmul_rn(p[1], hinv[3 + a])), __dmul_rn(p[2], hinv[6 + a]));
+    v -= floor(v);
+    if (!(v < 1.0)) v = 0.0;   // floor() rounding at the upper edge (and a non-finite coordinate: counted from 0)
+    s[a] = v;
+    const double lo = ceil(-m[a] - v), hi = ceil(1.0 + m[a] - v) - 1.0;   // lo <= 0 <= hi
+    r.lo[a] = (int) fmax(lo, -1073741824.0);
+    r.cnt[a] = (int) fmin(hi - lo + 1.0, 1073741824.0);
+    prod = prod > 0xffffffffull ? prod : prod * (unsigned long long) r.cnt[a];   // stays below 2^63
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    w[a] = __dadd_rn(__dadd_rn(__dmul_rn(s[0], h[a]), __dmul_rn(s[1], h[3 + a])), __dmul_rn(s[2], h[6 + a]));
+    if (org) w[a] = __dadd_rn(w[a], org[a]);   // (the ghosts follow through owner + shift)
+  }
+  return prod - 1 > 0xffffffffull ? 0xffffffffull : prod - 1;
+}
+
+// image e of an atom (its box of shifts in lexicographic order, the zero shift left out) -> sh = n . h
+__device__ __forceinline__ void shift_of(const ShiftRange &r, int e, const double *__restrict__ h, double sh[3])
+{
+  const int zero = (-r.lo[0] * r.cnt[1] - r.lo[1]) * r.cnt[2] - r.lo[2];   // where the atom itself would stand
+  if (e >= zero) e++;
+  const int q = e / r.cnt[2];
+  const double n2 = r.lo[2] + (e - q * r.cnt[2]);
+  const int q1 = q / r.cnt[1];
+  const double n1 = r.lo[1] + (q - q1 * r.cnt[1]), n0 = r.lo[0] + q1;
+#pragma unroll
+  for (int a = 0; a < 3; a++) sh[a] = __dadd_rn(__dadd_rn(__dmul_rn(n0, h[a]), __dmul_rn(n1, h[3 + a])), __dmul_rn(n2, h[6 + a]));
+}
+
+// the last k < n with first[k] <= i (first[0] = 0 <= i): the owner of ghost i among the scanned offsets, the configuration
+// of owned row i among cfg_first (empty configurations share their start with the next one, which this skips).  (A 16-ary
+// search, 15 independent probes a round, measured slower on MI355X: 17 us against 7.5 us for 31 773 ghosts of 65 536 atoms.)
+__device__ __forceinline__ int last_at_or_below(const int *__restrict__ first, int n, int i)
+{
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (first[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// where the cell of a row comes from.  One cell for every row: a kernel argument by value, so h, hinv and m stay in scalar
+// registers; no origin.
+struct OneCell {
+  Cell9 c;
+  __device__ __forceinline__ int cfg_of_row(int) const { return 0; }
+  __device__ __forceinline__ const Cell9 &cell(int) const { return c; }
+  __device__ __forceinline__ const double *origin(int) const { return nullptr; }
+};
+
+// Many cells in one pass: owned atoms of configuration k are rows [cfg_first[k], cfg_first[k + 1]); slot[k] holds its cell
+// and the origin its images are translated by (mtp_batch_layout keeps the slots of two configurations at least the list
+// cutoff apart).
+struct CellSlot {
+  Cell9 c;
+  double org[3];
+};
+struct SlotCells {
+  const CellSlot *slot;
+  const int *cfg_first;
+  int ncfg;
+  __device__ __forceinline__ int cfg_of_row(int i) const { return last_at_or_below(cfg_first, ncfg, i); }
+  __device__ __forceinline__ const Cell9 &cell(int cfg) const { return slot[cfg].c; }
+  __device__ __forceinline__ const double *origin(int cfg) const { return slot[cfg].org; }
+};
+
+// wraps the owned atoms into their cells and counts their images; the shift ranges and the configuration go to range[] for
+// the fill pass.  SUM64 (only when the host cannot rule out a total beyond int from the margins alone): count[i] saturates
+// at INT_MAX and the exact total goes to *total64, one atomic per block, so that such a total is seen on the host rather
+// than wrapped by the scan
+template <class Cells, bool SUM64>
+__global__ void __launch_bounds__(256) ghosts_cell_count_kernel(Cells cells, double *__restrict__ x, int n, int *__restrict__ count,
                                                                ShiftRange *__restrict__ range,
                                                                unsigned long long *__restrict__ total64)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   unsigned long long mine = 0;
   if (i < n) {
+    const int cfg = cells.cfg_of_row(i);
+    const Cell9 &c = cells.cell(cfg);
     const double p[3] = {x[3 * (size_t) i], x[3 * (size_t) i + 1], x[3 * (size_t) i + 2]};
-    double s[3];
+    double w[3];
     ShiftRange r;
-    unsigned long long prod = 1;
+    mine = wrap_and_count(c.h, c.hinv, c.m, cells.origin(cfg), p, w, r);
+    r.pad[0] = cfg;
+    r.pad[1] = 0;
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-      // (products and sums rounded one by one, in this order: the numpy twin in driver.make_ghosts_cell does the same)
-      double v = __dadd_rn(__dadd_rn(__dmul_rn(p[0], c.hinv[a]), __dmul_rn(p[1], c.hinv[3 + a])), __dmul_rn(p[2], c.hinv[6 + a]));
-      v -= floor(v);
-      if (!(v < 1.0)) v = 0.0;   // floor() rounding at the upper edge (and a non-finite coordinate: counted from 0)
-      s[a] = v;
-      const double lo = ceil(-c.m[a] - v), hi = ceil(1.0 + c.m[a] - v) - 1.0;   // lo <= 0 <= hi
-      r.lo[a] = (int) fmax(lo, -1073741824.0);
-      r.cnt[a] = (int) fmin(hi - lo + 1.0, 1073741824.0);
-      prod = prod > 0xffffffffull ? prod : prod * (unsigned long long) r.cnt[a];   // stays below 2^63
-    }
-    r.pad[0] = r.pad[1] = 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-      x[3 * (size_t) i + a] = __dadd_rn(__dadd_rn(__dmul_rn(s[0], c.h[a]), __dmul_rn(s[1], c.h[3 + a])), __dmul_rn(s[2], c.h[6 + a]));
-    mine = prod - 1 > 0xffffffffull ? 0xffffffffull : prod - 1;   // 2^31 atoms of these still sum below 2^64
+    for (int a = 0; a < 3; a++) x[3 * (size_t) i + a] = w[a];
     count[i] = mine > 0x7fffffffull ? 0x7fffffff : (int) mine;
     range[i] = r;
   }
@@ -142,130 +216,22 @@ __global__ void __launch_bounds__(256) ghosts_cell_count_kernel(Cell9 c, double 
 }
 
 // one lane per GHOST (a 1-atom cell has hundreds of images of its one atom): the owner is the last atom whose scanned
-// offset is <= k, the shift triple comes from the position of k in that atom's box of shifts (lexicographic, the zero
-// shift left out) -> owner[k], shift[k] = n . h
-__global__ void __launch_bounds__(256) ghosts_cell_fill_kernel(Cell9 c, int n, int total, const int *__restrict__ first,
+// offset is <= k (first[n] = total > k), the shift triple comes from the position of k in that atom's box of shifts and
+// the cell of the owner's configuration -> owner[k], shift[k]
+template <class Cells>
+__global__ void __launch_bounds__(256) ghosts_cell_fill_kernel(Cells cells, int n, int total, const int *__restrict__ first,
                                                               const ShiftRange *__restrict__ range, int *__restrict__ owner,
                                                               double *__restrict__ shift, int capacity)
 {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= total || k >= capacity) return;
-  // bisection for the last atom with first[i] <= k (first[0] = 0 <= k, first[n] = total > k).  (A 16-ary search, 15
-  // independent probes a round, measured slower on MI355X: 17 us against 7.5 us for 31 773 ghosts of 65 536 atoms.)
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (first[mid] <= k) lo = mid;
-    else hi = mid - 1;
-  }
-  const ShiftRange r = range[lo];
-  int e = k - first[lo];
-  const int zero = (-r.lo[0] * r.cnt[1] - r.lo[1]) * r.cnt[2] - r.lo[2];   // where the atom itself would stand
-  if (e >= zero) e++;
-  const int q = e / r.cnt[2];
-  const double n2 = r.lo[2] + (e - q * r.cnt[2]);
-  const int q1 = q / r.cnt[1];
-  const double n1 = r.lo[1] + (q - q1 * r.cnt[1]), n0 = r.lo[0] + q1;
-  owner[k] = lo;
+  const int i = last_at_or_below(first, n, k);
+  const ShiftRange r = range[i];
+  double sh[3];
+  shift_of(r, k - first[i], cells.cell(r.pad[0]).h, sh);
+  owner[k] = i;
 #pragma unroll
-  for (int a = 0; a < 3; a++)
-    shift[3 * (size_t) k + a] = __dadd_rn(__dadd_rn(__dmul_rn(n0, c.h[a]), __dmul_rn(n1, c.h[3 + a])), __dmul_rn(n2, c.h[6 + a]));
-}
-
-// ---- many cells in one pass (mtp_ghosts_build_batch): the two kernels above with the cell looked up per atom.  Owned
-// atoms of configuration k are rows [cfg_first[k], cfg_first[k + 1]); slot[k] holds its cell and the origin its images
-// are translated by (mtp_batch_layout keeps the slots of two configurations at least the list cutoff apart).
-struct CellSlot {
-  Cell9 c;
-  double org[3];
-};
-
-// the configuration of owned row i: the last k < ncfg with cfg_first[k] <= i (empty configurations share their start
-// with the next one, which this skips)
-__device__ __forceinline__ int cfg_of_row(const int *__restrict__ cfg_first, int ncfg, int i)
-{
-  int lo = 0, hi = ncfg - 1;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (cfg_first[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// ghosts_cell_count_kernel per configuration: wraps atom i into ITS cell (same products, rounded one by one in the same
-// order), adds the slot origin, records the shift ranges and the configuration (range.pad[0]) for the fill pass
-template <bool SUM64>
-__global__ void __launch_bounds__(256) ghosts_batch_count_kernel(const CellSlot *__restrict__ slot, const int *__restrict__ cfg_first,
-                                                                int ncfg, double *__restrict__ x, int n, int *__restrict__ count,
-                                                                ShiftRange *__restrict__ range,
-                                                                unsigned long long *__restrict__ total64)
-{
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  unsigned long long mine = 0;
-  if (i < n) {
-    const int cfg = cfg_of_row(cfg_first, ncfg, i);
-    const double *__restrict__ h = slot[cfg].c.h, *__restrict__ hinv = slot[cfg].c.hinv, *__restrict__ m = slot[cfg].c.m;
-    const double p[3] = {x[3 * (size_t) i], x[3 * (size_t) i + 1], x[3 * (size_t) i + 2]};
-    double s[3];
-    ShiftRange r;
-    unsigned long long prod = 1;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      double v = __dadd_rn(__dadd_rn(__dmul_rn(p[0], hinv[a]), __dmul_rn(p[1], hinv[3 + a])), __dmul_rn(p[2], hinv[6 + a]));
-      v -= floor(v);
-      if (!(v < 1.0)) v = 0.0;   // floor() rounding at the upper edge (and a non-finite coordinate: counted from 0)
-      s[a] = v;
-      const double lo = ceil(-m[a] - v), hi = ceil(1.0 + m[a] - v) - 1.0;   // lo <= 0 <= hi
-      r.lo[a] = (int) fmax(lo, -1073741824.0);
-      r.cnt[a] = (int) fmin(hi - lo + 1.0, 1073741824.0);
-      prod = prod > 0xffffffffull ? prod : prod * (unsigned long long) r.cnt[a];   // stays below 2^63
-    }
-    r.pad[0] = cfg;
-    r.pad[1] = 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      const double w = __dadd_rn(__dadd_rn(__dmul_rn(s[0], h[a]), __dmul_rn(s[1], h[3 + a])), __dmul_rn(s[2], h[6 + a]));
-      x[3 * (size_t) i + a] = __dadd_rn(w, slot[cfg].org[a]);   // (the ghosts follow through owner + shift)
-    }
-    mine = prod - 1 > 0xffffffffull ? 0xffffffffull : prod - 1;
-    count[i] = mine > 0x7fffffffull ? 0x7fffffff : (int) mine;
-    range[i] = r;
-  }
-  if (SUM64) {
-    typedef hipcub::BlockReduce<unsigned long long, 256> Red;
-    __shared__ typename Red::TempStorage tmp;
-    const unsigned long long bsum = Red(tmp).Sum(mine);
-    if (threadIdx.x == 0 && bsum) atomicAdd(total64, bsum);
-  }
-}
-
-// ghosts_cell_fill_kernel with h taken from the owner's configuration
-__global__ void __launch_bounds__(256) ghosts_batch_fill_kernel(const CellSlot *__restrict__ slot, int n, int total,
-                                                               const int *__restrict__ first, const ShiftRange *__restrict__ range,
-                                                               int *__restrict__ owner, double *__restrict__ shift, int capacity)
-{
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= total || k >= capacity) return;
-  int lo = 0, hi = n - 1;   // the last atom with first[i] <= k
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (first[mid] <= k) lo = mid;
-    else hi = mid - 1;
-  }
-  const ShiftRange r = range[lo];
-  const double *__restrict__ h = slot[r.pad[0]].c.h;
-  int e = k - first[lo];
-  const int zero = (-r.lo[0] * r.cnt[1] - r.lo[1]) * r.cnt[2] - r.lo[2];   // where the atom itself would stand
-  if (e >= zero) e++;
-  const int q = e / r.cnt[2];
-  const double n2 = r.lo[2] + (e - q * r.cnt[2]);
-  const int q1 = q / r.cnt[1];
-  const double n1 = r.lo[1] + (q - q1 * r.cnt[1]), n0 = r.lo[0] + q1;
-  owner[k] = lo;
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    shift[3 * (size_t) k + a] = __dadd_rn(__dadd_rn(__dmul_rn(n0, h[a]), __dmul_rn(n1, h[3 + a])), __dmul_rn(n2, h[6 + a]));
+  for (int a = 0; a < 3; a++) shift[3 * (size_t) k + a] = sh[a];
 }
 
 // x[nlocal + k] = x[owner[k]] + shift[k]   (one lane per coordinate)
@@ -367,32 +333,54 @@ __global__ void __launch_bounds__(256) nve_monitor_kernel(const double *__restri
 
 }   // namespace
 
-struct mtp_ghosts {
-  int device = 0, nlocal = 0, nghost = 0;
-  int cap_local = 0, cap_ghost = 0;
-  int *d_count = nullptr, *d_first = nullptr, *d_owner = nullptr;
-  int *d_owner_all = nullptr;                // mtp_ghosts_owner_device only: [cap_owner_all] identity | d_owner
-  int cap_owner_all = 0;
-  double *d_shift = nullptr;
-  double *d_shift0 = nullptr;                // mtp_ghosts_deform only: [cap_shift0][3] the shifts as the last build left them
-  int cap_shift0 = 0;
-  bool shift0_valid = false;                 // d_shift0 holds the shifts of the last build
-  ShiftRange *d_range = nullptr;             // mtp_ghosts_build_cell only: [cap_range] + one 64-bit total behind them
-  int cap_range = 0;
-  CellSlot *d_slot = nullptr;                // mtp_ghosts_build_batch only: [cap_slot] cells + origins, and the
-  int *d_cfg_first = nullptr;                // [cap_slot + 1] first owned rows of the configurations
-  int cap_slot = 0;
-  std::vector<CellSlot> h_slot;              // host staging of d_slot
-  void *d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  std::string last_error;
-  ~mtp_ghosts()
+// grow-only device array of the handle.  reserve(n) makes room for n elements: what was there is released first (no build
+// carries contents over), and a failed allocation leaves the buffer empty.  It reports through hipError_t, as everything
+// in this file does (MD_HIP; no exceptions).
+template <class T>
+struct GrowBuf {
+  T *p = nullptr;
+  size_t cap = 0;   // elements
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf &) = delete;
+  GrowBuf &operator=(const GrowBuf &) = delete;
+  ~GrowBuf() { release(); }
+  void release()
   {
-    (void) hipSetDevice(device);
-    for (void *p : {(void *) d_count, (void *) d_first, (void *) d_owner, (void *) d_shift, (void *) d_range, (void *) d_slot,
-                    (void *) d_cfg_first, (void *) d_owner_all, (void *) d_shift0, d_tmp})
-      if (p) (void) hipFree(p);
+    if (p) (void) hipFree(p);
+    p = nullptr;
+    cap = 0;
   }
+  hipError_t reserve(size_t n)
+  {
+    if (n <= cap) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc((void **) &p, n * sizeof(T));
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
+};
+
+// Buffers that grow together (d_count / d_tmp / d_first, d_owner / d_shift, d_slot / d_cfg_first) are ALL released before the
+// first of them is allocated again, in the order they stand here: the last of a group has room only if every member has,
+// so its capacity is the one that is asked, and a build after a failed allocation allocates the whole group again.
+struct mtp_ghosts {
+  int device = 0, nlocal = 0, nghost = 0;    // nghost > 0 only while d_owner / d_shift hold the maps of a finished build
+  GrowBuf<int> d_count;                      // [nlocal + 1 + nlocal / 8] per-atom image counts,
+  GrowBuf<char> d_tmp;                       // the workspace of a scan over that many (bytes),
+  GrowBuf<int> d_first;                      // their scanned offsets
+  GrowBuf<ShiftRange> d_range;               // cell builds only: [d_first.cap] ranges + one 64-bit total in the last element
+  GrowBuf<int> d_owner;                      // [cap_ghost()]
+  GrowBuf<double> d_shift;                   // [cap_ghost()][3]
+  GrowBuf<double> d_shift0;                  // mtp_ghosts_deform only: [d_shift.cap] the shifts as the last build left them
+  bool shift0_valid = false;                 // d_shift0 holds the shifts of the last build
+  GrowBuf<int> d_owner_all;                  // mtp_ghosts_owner_device only: identity | d_owner
+  GrowBuf<CellSlot> d_slot;                  // mtp_ghosts_build_batch only: [ncfg + ncfg / 8] cells + origins, and the
+  GrowBuf<int> d_cfg_first;                  // [d_slot.cap + 1] first owned rows of the configurations
+  std::vector<CellSlot> h_slot;              // host staging of d_slot
+  std::string last_error;
+  int cap_ghost() const { return (int) (d_shift.cap / 3); }
+  unsigned long long *d_total64() const { return reinterpret_cast<unsigned long long *>(d_range.p + (d_range.cap - 1)); }
+  ~mtp_ghosts() { (void) hipSetDevice(device); }   // (runs before the members free themselves)
 };
 
 #define MD_HIP(call)                                                                        \
@@ -410,45 +398,92 @@ static int ghosts_null_stream(mtp_ghosts *g, const char *fn)
   return MTP_ERR_ARG;
 }
 
-// allocation growth shared by the two builds: per-atom counts / offsets (+ the scan's workspace), per-ghost maps
+// every build starts here once its arguments are accepted, BEFORE a buffer is grown or freed: whatever fails later, the
+// handle reports no ghosts rather than those of the build before over maps that are gone.  nghost becomes the new total
+// only after ghosts_reserve_ghosts has succeeded.
+static void ghosts_reset(mtp_ghosts *g, int nlocal)
+{
+  g->nlocal = nlocal;
+  g->nghost = 0;
+  g->shift0_valid = false;
+}
+
+// allocation growth shared by the builds: per-atom counts / offsets (+ the scan's workspace), per-ghost maps
 static hipError_t ghosts_reserve_local(mtp_ghosts *g, int nlocal, hipStream_t st)
 {
-  if (nlocal + 1 <= g->cap_local) return hipSuccess;
+  if ((size_t) nlocal + 1 <= g->d_first.cap) return hipSuccess;
   hipError_t e;
-  if (g->d_count) (void) hipFree(g->d_count);
-  if (g->d_first) (void) hipFree(g->d_first);
-  g->d_count = g->d_first = nullptr;
-  g->cap_local = 0;
   const size_t n = (size_t) nlocal + 1 + nlocal / 8;
-  if ((e = hipMalloc((void **) &g->d_count, n * sizeof(int))) != hipSuccess) return e;
-  if ((e = hipMalloc((void **) &g->d_first, n * sizeof(int))) != hipSuccess) return e;
-  g->cap_local = (int) n;
-  size_t need = 0;
-  (void) hipcub::DeviceScan::ExclusiveSum(nullptr, need, g->d_count, g->d_first, (int) n, st);
-  if (need > g->tmp_bytes) {
-    if (g->d_tmp) (void) hipFree(g->d_tmp);
-    g->d_tmp = nullptr;
-    g->tmp_bytes = 0;
-    if ((e = hipMalloc(&g->d_tmp, need)) != hipSuccess) return e;
-    g->tmp_bytes = need;
-  }
-  return hipSuccess;
+  size_t need = 0;   // (a size query: no pointer is read)
+  (void) hipcub::DeviceScan::ExclusiveSum(nullptr, need, g->d_count.p, g->d_first.p, (int) n, st);
+  g->d_count.release();
+  g->d_tmp.release();
+  g->d_first.release();
+  if ((e = g->d_count.reserve(n)) != hipSuccess) return e;
+  if ((e = g->d_tmp.reserve(need)) != hipSuccess) return e;
+  return g->d_first.reserve(n);
 }
 
 static hipError_t ghosts_reserve_ghosts(mtp_ghosts *g, int total)
 {
-  if (total <= g->cap_ghost) return hipSuccess;
-  hipError_t e;
-  if (g->d_owner) (void) hipFree(g->d_owner);
-  if (g->d_shift) (void) hipFree(g->d_shift);
-  g->d_owner = nullptr;
-  g->d_shift = nullptr;
-  g->cap_ghost = 0;
+  if (total <= g->cap_ghost()) return hipSuccess;
   const size_t n = std::min((size_t) total + total / 8 + 64, (size_t) 0x7fffffff);
-  if ((e = hipMalloc((void **) &g->d_owner, n * sizeof(int))) != hipSuccess) return e;
-  if ((e = hipMalloc((void **) &g->d_shift, 3 * n * sizeof(double))) != hipSuccess) return e;
-  g->cap_ghost = (int) n;
-  return hipSuccess;
+  g->d_owner.release();
+  g->d_shift.release();
+  const hipError_t e = g->d_owner.reserve(n);
+  return e != hipSuccess ? e : g->d_shift.reserve(3 * n);
+}
+
+// what mtp_ghosts_build_cell and mtp_ghosts_build_batch share once the entry point `fn` has checked its arguments, reset
+// the handle, set the device and has its cells where the kernels read them: count, scan, ONE read-back, fill.  `hint`
+// ends the refusal of a total beyond 32 bits; sum64 is the caller's own bound (an atom has at most floor(1 + 2 m_a) + 1
+// shifts per direction: when that bound over all atoms fits an int -- every cell a simulation meets -- the scanned int
+// total is exact and the 64-bit sum is not taken).  nlocal > 0.
+template <class Cells>
+static int ghosts_build_cells(mtp_ghosts *g, const char *fn, const char *hint, hipStream_t st, const Cells &cells,
+                              double *d_x, int nlocal, int capacity, bool sum64, int *nall_out)
+{
+  MD_HIP(ghosts_reserve_local(g, nlocal, st));
+  if ((size_t) nlocal + 2 > g->d_range.cap) MD_HIP(g->d_range.reserve(g->d_first.cap + 1));
+  MD_HIP(hipMemsetAsync(g->d_count.p, 0, ((size_t) nlocal + 1) * sizeof(int), st));
+  if (sum64) MD_HIP(hipMemsetAsync(g->d_total64(), 0, sizeof(unsigned long long), st));
+  const int nb = (nlocal + 255) / 256;
+  if (sum64)
+    hipLaunchKernelGGL((ghosts_cell_count_kernel<Cells, true>), dim3(nb), dim3(256), 0, st, cells, d_x, nlocal, g->d_count.p,
+                       g->d_range.p, g->d_total64());
+  else
+    hipLaunchKernelGGL((ghosts_cell_count_kernel<Cells, false>), dim3(nb), dim3(256), 0, st, cells, d_x, nlocal, g->d_count.p,
+                       g->d_range.p, g->d_total64());
+  size_t tb = g->d_tmp.cap;
+  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp.p, tb, g->d_count.p, g->d_first.p, nlocal + 1, st));
+  int total = 0;
+  unsigned long long total64 = 0;
+  if (sum64) MD_HIP(hipMemcpyAsync(&total64, g->d_total64(), sizeof(total64), hipMemcpyDeviceToHost, st));
+  else MD_HIP(hipMemcpyAsync(&total, g->d_first.p + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
+  MD_HIP(hipStreamSynchronize(st));
+  if (sum64) {
+    if (total64 > 0x7fffffffull - (unsigned long long) nlocal) {   // never wrapped: the scanned offsets are not used
+      *nall_out = 0x7fffffff;
+      g->last_error = std::string(fn) + ": owned + ghost atoms do not fit a 32-bit count " + hint;
+      return MTP_ERR_LIMIT;
+    }
+    total = (int) total64;   // == d_first[nlocal]: no per-atom count saturated
+  }
+  *nall_out = nlocal + total;
+  if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written or kept
+    g->last_error = std::string(fn) + ": capacity of the position array is smaller than owned + ghost atoms";
+    return MTP_ERR_LIMIT;
+  }
+  MD_HIP(ghosts_reserve_ghosts(g, total));
+  g->nghost = total;
+  if (total > 0) {
+    hipLaunchKernelGGL(ghosts_cell_fill_kernel<Cells>, dim3((total + 255) / 256), dim3(256), 0, st, cells, nlocal, total,
+                       g->d_first.p, g->d_range.p, g->d_owner.p, g->d_shift.p, g->cap_ghost());
+    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner.p,
+                       g->d_shift.p, 3 * total);
+  }
+  MD_HIP(hipGetLastError());
+  return MTP_OK;
 }
 
 // h^-1 (cofactors over the determinant), the margins m[a] = rghost / d_a with d_a = V / |h_b x h_c| the spacing of the
@@ -501,32 +536,31 @@ int mtp_ghosts_build(mtp_ghosts *g, void *stream, double *d_x, int nlocal, int c
       g->last_error = "mtp_ghosts_build: box edge shorter than the ghost cutoff";
       return MTP_ERR_LIMIT;
     }
+  ghosts_reset(g, nlocal);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   MD_HIP(hipSetDevice(g->device));
   MD_HIP(ghosts_reserve_local(g, nlocal, st));
   Box3 b{{box[0], box[1], box[2]}, rghost};
   const int nb = (nlocal + 255) / 256;
-  MD_HIP(hipMemsetAsync(g->d_count, 0, ((size_t) nlocal + 1) * sizeof(int), st));
-  if (nlocal > 0) hipLaunchKernelGGL(ghosts_count_kernel, dim3(nb), dim3(256), 0, st, b, d_x, nlocal, g->d_count);
-  size_t tb = g->tmp_bytes;
-  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp, tb, g->d_count, g->d_first, nlocal + 1, st));
+  MD_HIP(hipMemsetAsync(g->d_count.p, 0, ((size_t) nlocal + 1) * sizeof(int), st));
+  if (nlocal > 0) hipLaunchKernelGGL(ghosts_count_kernel, dim3(nb), dim3(256), 0, st, b, d_x, nlocal, g->d_count.p);
+  size_t tb = g->d_tmp.cap;
+  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp.p, tb, g->d_count.p, g->d_first.p, nlocal + 1, st));
   int total = 0;
-  MD_HIP(hipMemcpyAsync(&total, g->d_first + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
+  MD_HIP(hipMemcpyAsync(&total, g->d_first.p + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
   MD_HIP(hipStreamSynchronize(st));
   MD_HIP(ghosts_reserve_ghosts(g, total));
-  g->nlocal = nlocal;
   g->nghost = total;
-  g->shift0_valid = false;
   *nall_out = nlocal + total;
   if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written
     g->last_error = "mtp_ghosts_build: capacity of the position array is smaller than owned + ghost atoms";
     return MTP_ERR_LIMIT;
   }
   if (nlocal > 0 && total > 0) {
-    hipLaunchKernelGGL(ghosts_fill_kernel, dim3(nb), dim3(256), 0, st, b, d_x, nlocal, g->d_first, g->d_owner, g->d_shift,
-                       g->cap_ghost);
-    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
-                       g->d_shift, 3 * total);
+    hipLaunchKernelGGL(ghosts_fill_kernel, dim3(nb), dim3(256), 0, st, b, d_x, nlocal, g->d_first.p, g->d_owner.p, g->d_shift.p,
+                       g->cap_ghost());
+    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner.p,
+                       g->d_shift.p, 3 * total);
   }
   MD_HIP(hipGetLastError());
   return MTP_OK;
@@ -562,74 +596,23 @@ int mtp_ghosts_build_cell(mtp_ghosts *g, void *stream, double *d_x, int nlocal, 
   if (!g || !d_x || nlocal < 0 || capacity < nlocal || !cell || !(rghost > 0.0) || !std::isfinite(rghost) || !nall_out)
     return MTP_ERR_ARG;
   if (!stream) return ghosts_null_stream(g, "mtp_ghosts_build_cell");
-  Cell9 c;
-  for (int k = 0; k < 9; k++) c.h[k] = cell[k];
-  if (!(cell_setup(cell, rghost, c.hinv, c.m) > 0.0)) {
+  OneCell one;
+  for (int k = 0; k < 9; k++) one.c.h[k] = cell[k];
+  if (!(cell_setup(cell, rghost, one.c.hinv, one.c.m) > 0.0)) {
     g->last_error = "mtp_ghosts_build_cell: the cell must be finite, right-handed and non-degenerate (det > 0)";
     return MTP_ERR_ARG;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  MD_HIP(hipSetDevice(g->device));
-  MD_HIP(ghosts_reserve_local(g, nlocal, st));
-  if (nlocal + 1 > g->cap_range) {
-    if (g->d_range) (void) hipFree(g->d_range);
-    g->d_range = nullptr;
-    g->cap_range = 0;
-    MD_HIP(hipMalloc((void **) &g->d_range, ((size_t) g->cap_local + 1) * sizeof(ShiftRange)));
-    g->cap_range = g->cap_local;
+  ghosts_reset(g, nlocal);
+  if (nlocal == 0) {   // nothing to wrap, no images
+    *nall_out = 0;
+    return MTP_OK;
   }
-  // an atom has at most floor(1 + 2 m_a) + 1 shifts per direction: when that bound times nlocal fits an int (every cell
-  // a simulation meets), the scanned int total is exact and the 64-bit sum is not taken
   double bound = (double) nlocal;
-  for (int a = 0; a < 3; a++) bound *= std::floor(1.0 + 2.0 * c.m[a]) + 1.0;
+  for (int a = 0; a < 3; a++) bound *= std::floor(1.0 + 2.0 * one.c.m[a]) + 1.0;
   const bool sum64 = !(bound + (double) nlocal < 2147483647.0);
-  unsigned long long *d_total64 = reinterpret_cast<unsigned long long *>(g->d_range + g->cap_range);
-  const int nb = (nlocal + 255) / 256;
-  MD_HIP(hipMemsetAsync(g->d_count, 0, ((size_t) nlocal + 1) * sizeof(int), st));
-  if (sum64) MD_HIP(hipMemsetAsync(d_total64, 0, sizeof(unsigned long long), st));
-  if (nlocal > 0) {
-    if (sum64)
-      hipLaunchKernelGGL(ghosts_cell_count_kernel<true>, dim3(nb), dim3(256), 0, st, c, d_x, nlocal, g->d_count, g->d_range, d_total64);
-    else
-      hipLaunchKernelGGL(ghosts_cell_count_kernel<false>, dim3(nb), dim3(256), 0, st, c, d_x, nlocal, g->d_count, g->d_range, d_total64);
-  }
-  size_t tb = g->tmp_bytes;
-  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp, tb, g->d_count, g->d_first, nlocal + 1, st));
-  int total = 0;
-  unsigned long long total64 = 0;
-  if (sum64) MD_HIP(hipMemcpyAsync(&total64, d_total64, sizeof(total64), hipMemcpyDeviceToHost, st));
-  else MD_HIP(hipMemcpyAsync(&total, g->d_first + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
-  MD_HIP(hipStreamSynchronize(st));
-  if (sum64) {
-    if (total64 > 0x7fffffffull - (unsigned long long) nlocal) {   // never wrapped: the scanned offsets are not used
-      g->nlocal = nlocal;
-      g->nghost = 0;
-      g->shift0_valid = false;
-      *nall_out = 0x7fffffff;
-      g->last_error = "mtp_ghosts_build_cell: owned + ghost atoms do not fit a 32-bit count (cell far smaller than rghost?)";
-      return MTP_ERR_LIMIT;
-    }
-    total = (int) total64;   // == d_first[nlocal]: no per-atom count saturated
-  }
-  g->nlocal = nlocal;
-  g->nghost = 0;
-  g->shift0_valid = false;
-  *nall_out = nlocal + total;
-  if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written or kept
-    g->last_error = "mtp_ghosts_build_cell: capacity of the position array is smaller than owned + ghost atoms";
-    return MTP_ERR_LIMIT;
-  }
-  MD_HIP(ghosts_reserve_ghosts(g, total));
-  g->nghost = total;
-  g->shift0_valid = false;
-  if (total > 0) {
-    hipLaunchKernelGGL(ghosts_cell_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c, nlocal, total, g->d_first,
-                       g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
-    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
-                       g->d_shift, 3 * total);
-  }
-  MD_HIP(hipGetLastError());
-  return MTP_OK;
+  MD_HIP(hipSetDevice(g->device));
+  return ghosts_build_cells(g, "mtp_ghosts_build_cell", "(cell far smaller than rghost?)", reinterpret_cast<hipStream_t>(stream), one,
+                            d_x, nlocal, capacity, sum64, nall_out);
 }
 
 // ---- batched configurations ------------------------------------------------------------------------------------------
@@ -742,8 +725,7 @@ int mtp_ghosts_build_batch(mtp_ghosts *g, void *stream, double *d_x, int ncfg, c
     g->last_error = "mtp_ghosts_build_batch: capacity is smaller than the owned atoms";
     return MTP_ERR_ARG;
   }
-  // an atom of configuration k has at most floor(1 + 2 m_a) + 1 shifts per direction: when that bound, summed over the
-  // batch, fits an int, the scanned int total is exact and the 64-bit sum is not taken
+  // (the bound of ghosts_build_cells, summed over the batch)
   g->h_slot.resize((size_t) ncfg);
   double bound = (double) nlocal;
   for (int k = 0; k < ncfg; k++) {
@@ -765,77 +747,24 @@ int mtp_ghosts_build_batch(mtp_ghosts *g, void *stream, double *d_x, int ncfg, c
     }
     bound += per_atom * (double) (cfg_first[k + 1] - cfg_first[k]);
   }
-  g->nlocal = nlocal;
-  g->nghost = 0;
-  g->shift0_valid = false;
+  ghosts_reset(g, nlocal);
   *nall_out = nlocal;
   if (nlocal == 0) return MTP_OK;   // nothing to wrap, no images
   const bool sum64 = !(bound < 2147483647.0);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   MD_HIP(hipSetDevice(g->device));
-  MD_HIP(ghosts_reserve_local(g, nlocal, st));
-  if (nlocal + 1 > g->cap_range) {
-    if (g->d_range) (void) hipFree(g->d_range);
-    g->d_range = nullptr;
-    g->cap_range = 0;
-    MD_HIP(hipMalloc((void **) &g->d_range, ((size_t) g->cap_local + 1) * sizeof(ShiftRange)));
-    g->cap_range = g->cap_local;
-  }
-  if (ncfg > g->cap_slot) {
-    if (g->d_slot) (void) hipFree(g->d_slot);
-    if (g->d_cfg_first) (void) hipFree(g->d_cfg_first);
-    g->d_slot = nullptr;
-    g->d_cfg_first = nullptr;
-    g->cap_slot = 0;
+  if ((size_t) ncfg + 1 > g->d_cfg_first.cap) {
     const size_t n = (size_t) ncfg + ncfg / 8;
-    MD_HIP(hipMalloc((void **) &g->d_slot, n * sizeof(CellSlot)));
-    MD_HIP(hipMalloc((void **) &g->d_cfg_first, (n + 1) * sizeof(int)));
-    g->cap_slot = (int) n;
+    g->d_slot.release();
+    g->d_cfg_first.release();
+    MD_HIP(g->d_slot.reserve(n));
+    MD_HIP(g->d_cfg_first.reserve(n + 1));
   }
-  // (the stream is synchronised below, before this call returns: the host arrays outlive both copies)
-  MD_HIP(hipMemcpyAsync(g->d_slot, g->h_slot.data(), (size_t) ncfg * sizeof(CellSlot), hipMemcpyHostToDevice, st));
-  MD_HIP(hipMemcpyAsync(g->d_cfg_first, cfg_first, ((size_t) ncfg + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-  unsigned long long *d_total64 = reinterpret_cast<unsigned long long *>(g->d_range + g->cap_range);
-  MD_HIP(hipMemsetAsync(g->d_count, 0, ((size_t) nlocal + 1) * sizeof(int), st));
-  if (sum64) MD_HIP(hipMemsetAsync(d_total64, 0, sizeof(unsigned long long), st));
-  const int nb = (nlocal + 255) / 256;
-  if (sum64)
-    hipLaunchKernelGGL(ghosts_batch_count_kernel<true>, dim3(nb), dim3(256), 0, st, g->d_slot, g->d_cfg_first, ncfg, d_x, nlocal,
-                       g->d_count, g->d_range, d_total64);
-  else
-    hipLaunchKernelGGL(ghosts_batch_count_kernel<false>, dim3(nb), dim3(256), 0, st, g->d_slot, g->d_cfg_first, ncfg, d_x, nlocal,
-                       g->d_count, g->d_range, d_total64);
-  size_t tb = g->tmp_bytes;
-  MD_HIP(hipcub::DeviceScan::ExclusiveSum(g->d_tmp, tb, g->d_count, g->d_first, nlocal + 1, st));
-  int total = 0;
-  unsigned long long total64 = 0;
-  if (sum64) MD_HIP(hipMemcpyAsync(&total64, d_total64, sizeof(total64), hipMemcpyDeviceToHost, st));
-  else MD_HIP(hipMemcpyAsync(&total, g->d_first + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
-  MD_HIP(hipStreamSynchronize(st));
-  if (sum64) {
-    if (total64 > 0x7fffffffull - (unsigned long long) nlocal) {   // never wrapped: the scanned offsets are not used
-      *nall_out = 0x7fffffff;
-      g->last_error = "mtp_ghosts_build_batch: owned + ghost atoms do not fit a 32-bit count (split the batch)";
-      return MTP_ERR_LIMIT;
-    }
-    total = (int) total64;   // == d_first[nlocal]: no per-atom count saturated
-  }
-  *nall_out = nlocal + total;
-  if (nlocal + total > capacity) {   // the caller's arrays are too short: sizes are reported, nothing is written or kept
-    g->last_error = "mtp_ghosts_build_batch: capacity of the position array is smaller than owned + ghost atoms";
-    return MTP_ERR_LIMIT;
-  }
-  MD_HIP(ghosts_reserve_ghosts(g, total));
-  g->nghost = total;
-  g->shift0_valid = false;
-  if (total > 0) {
-    hipLaunchKernelGGL(ghosts_batch_fill_kernel, dim3((total + 255) / 256), dim3(256), 0, st, g->d_slot, nlocal, total, g->d_first,
-                       g->d_range, g->d_owner, g->d_shift, g->cap_ghost);
-    hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * total + 255) / 256), dim3(256), 0, st, d_x, nlocal, g->d_owner,
-                       g->d_shift, 3 * total);
-  }
-  MD_HIP(hipGetLastError());
-  return MTP_OK;
+  // (ghosts_build_cells synchronises the stream before this call returns: the host arrays outlive both copies)
+  MD_HIP(hipMemcpyAsync(g->d_slot.p, g->h_slot.data(), (size_t) ncfg * sizeof(CellSlot), hipMemcpyHostToDevice, st));
+  MD_HIP(hipMemcpyAsync(g->d_cfg_first.p, cfg_first, ((size_t) ncfg + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  return ghosts_build_cells(g, "mtp_ghosts_build_batch", "(split the batch)", st, SlotCells{g->d_slot.p, g->d_cfg_first.p, ncfg}, d_x,
+                            nlocal, capacity, sum64, nall_out);
 }
 
 int mtp_ghosts_forward(mtp_ghosts *g, void *stream, double *d_x)
@@ -844,7 +773,7 @@ int mtp_ghosts_forward(mtp_ghosts *g, void *stream, double *d_x)
   if (!stream) return ghosts_null_stream(g, "mtp_ghosts_forward");
   if (g->nghost > 0)
     hipLaunchKernelGGL(ghosts_forward_kernel, dim3((3 * g->nghost + 255) / 256), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), d_x, g->nlocal, g->d_owner, g->d_shift, 3 * g->nghost);
+                       reinterpret_cast<hipStream_t>(stream), d_x, g->nlocal, g->d_owner.p, g->d_shift.p, 3 * g->nghost);
   MD_HIP(hipGetLastError());
   return MTP_OK;
 }
@@ -855,7 +784,7 @@ int mtp_ghosts_reverse(mtp_ghosts *g, void *stream, double *d_f)
   if (!stream) return ghosts_null_stream(g, "mtp_ghosts_reverse");
   if (g->nghost > 0)
     hipLaunchKernelGGL(ghosts_reverse_kernel, dim3((3 * g->nghost + 255) / 256), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), d_f, g->nlocal, g->d_owner, 3 * g->nghost);
+                       reinterpret_cast<hipStream_t>(stream), d_f, g->nlocal, g->d_owner.p, 3 * g->nghost);
   MD_HIP(hipGetLastError());
   return MTP_OK;
 }
@@ -865,7 +794,7 @@ int mtp_ghosts_reverse_finish(mtp_ghosts *g, mtp_context *ctx, void *stream, int
   if (!g || !ctx || !d_f) return MTP_ERR_ARG;
   // the tally fold of a force call made with finish_tallies = 0 rides in the launch that folds the ghost forces
   // (a context is at hand: NULL -> the context's stream, as in mtp_compute_device)
-  return mtp_internal_finish_unpack(ctx, stream, eflag, vflag, d_ev, d_f, g->d_owner, d_f + 3 * (size_t) g->nlocal, 3 * g->nghost);
+  return mtp_internal_finish_unpack(ctx, stream, eflag, vflag, d_ev, d_f, g->d_owner.p, d_f + 3 * (size_t) g->nlocal, 3 * g->nghost);
 }
 
 int mtp_ghosts_types(mtp_ghosts *g, void *stream, int *d_type)
@@ -874,7 +803,7 @@ int mtp_ghosts_types(mtp_ghosts *g, void *stream, int *d_type)
   if (!stream) return ghosts_null_stream(g, "mtp_ghosts_types");
   if (g->nghost > 0)
     hipLaunchKernelGGL(ghosts_types_kernel, dim3((g->nghost + 255) / 256), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), d_type, g->nlocal, g->d_owner, g->nghost);
+                       reinterpret_cast<hipStream_t>(stream), d_type, g->nlocal, g->d_owner.p, g->nghost);
   MD_HIP(hipGetLastError());
   return MTP_OK;
 }
@@ -887,18 +816,12 @@ int mtp_ghosts_deform(mtp_ghosts *g, void *stream, const int *d_row_cfg, const d
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   MD_HIP(hipSetDevice(g->device));
   if (!g->shift0_valid) {   // the first call after a build keeps that build's shifts
-    if (g->nghost > g->cap_shift0) {
-      if (g->d_shift0) (void) hipFree(g->d_shift0);
-      g->d_shift0 = nullptr;
-      g->cap_shift0 = 0;
-      MD_HIP(hipMalloc((void **) &g->d_shift0, 3 * (size_t) g->cap_ghost * sizeof(double)));
-      g->cap_shift0 = g->cap_ghost;
-    }
-    MD_HIP(hipMemcpyAsync(g->d_shift0, g->d_shift, 3 * (size_t) g->nghost * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (3 * (size_t) g->nghost > g->d_shift0.cap) MD_HIP(g->d_shift0.reserve(g->d_shift.cap));
+    MD_HIP(hipMemcpyAsync(g->d_shift0.p, g->d_shift.p, 3 * (size_t) g->nghost * sizeof(double), hipMemcpyDeviceToDevice, st));
     g->shift0_valid = true;
   }
-  hipLaunchKernelGGL(ghosts_deform_kernel, dim3((3 * g->nghost + 255) / 256), dim3(256), 0, st, g->d_owner, d_row_cfg, d_T,
-                     g->d_shift0, g->d_shift, 3 * g->nghost);
+  hipLaunchKernelGGL(ghosts_deform_kernel, dim3((3 * g->nghost + 255) / 256), dim3(256), 0, st, g->d_owner.p, d_row_cfg, d_T,
+                     g->d_shift0.p, g->d_shift.p, 3 * g->nghost);
   MD_HIP(hipGetLastError());
   return MTP_OK;
 }
@@ -909,19 +832,12 @@ int mtp_ghosts_owner_device(mtp_ghosts *g, void *stream, const int **d_owner, in
   if (!stream) return ghosts_null_stream(g, "mtp_ghosts_owner_device");
   const int n = g->nlocal + g->nghost;
   MD_HIP(hipSetDevice(g->device));
-  if (n > g->cap_owner_all || !g->d_owner_all) {
-    if (g->d_owner_all) (void) hipFree(g->d_owner_all);
-    g->d_owner_all = nullptr;
-    g->cap_owner_all = 0;
-    const size_t cap = (size_t) n + n / 8 + 64;
-    MD_HIP(hipMalloc((void **) &g->d_owner_all, cap * sizeof(int)));
-    g->cap_owner_all = (int) std::min(cap, (size_t) 0x7fffffff);
-  }
+  if ((size_t) n > g->d_owner_all.cap || !g->d_owner_all.p) MD_HIP(g->d_owner_all.reserve((size_t) n + n / 8 + 64));
   if (n > 0)
     hipLaunchKernelGGL(ghosts_owner_all_kernel, dim3((n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       g->d_owner_all, g->nlocal, g->d_owner, n);
+                       g->d_owner_all.p, g->nlocal, g->d_owner.p, n);
   MD_HIP(hipGetLastError());
-  *d_owner = g->d_owner_all;
+  *d_owner = g->d_owner_all.p;
   *nall = n;
   return MTP_OK;
 }

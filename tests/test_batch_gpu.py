@@ -375,3 +375,126 @@ def test_an_atom_type_outside_the_potential_is_reported_at_the_synchronise_namin
     assert ei.value.code == -22
     good = evaluate_cells(ctx, _batch.mixed_batch()[:3], list_cutoff=LIST_CUTOFF)     # the context is still good
     _check_against(good[1], _mixed_reference("W_L8.mtp", 1)[1], 2, "after the refusal")
+
+
+# ---- the single-cell build and the batched build are one criterion with two sources of the cell; one handle serves both ------
+
+def _owners(g, n, nall, dev, st):
+    """the owner row of every row of the last build, read through the type fold"""
+    import torch
+    ty = torch.zeros(nall, dtype=torch.int32, device=dev)
+    ty[:n] = torch.arange(1, n + 1, dtype=torch.int32, device=dev)
+    g.types(ty, stream=st)
+    torch.cuda.synchronize()
+    return ty.cpu().numpy().astype(np.int64) - 1
+
+
+def _rows(pos, nall, dev):
+    import torch
+    xa = torch.zeros((nall, 3), dtype=torch.float64, device=dev)
+    xa[:len(pos)] = torch.from_numpy(np.ascontiguousarray(pos))
+    return xa
+
+
+def _one_cell_case(which):
+    if which == "primitive":                       # hundreds of images of its one atom: the zero-shift skip, the per-ghost decode
+        pos, cell, _ = _cells.primitive_cell()
+    elif which == "tilted5_far":
+        pos, cell, _ = _far(_batch.mixed_batch())[2]
+    else:
+        pos, cell, _ = _batch.sheared8_cell()
+    return pos, cell
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["primitive", "tilted5_far", "sheared8"])
+def test_a_batch_of_one_configuration_is_the_single_cell_build(which):
+    """build_batch with cfg_first = [0, n] and a zero origin against build_cell on another handle: the same count, owners and
+    ghost offsets from their owners (both form a ghost as owner + shift) bit for bit; the owned rows with ==, since the
+    origin add can only turn a -0.0 into +0.0.  The tilted cell again under a non-zero origin: rows minus the origin to
+    1e-12, the bound of the twin tests for a translated cell."""
+    pos, cell = _one_cell_case(which)
+    n = len(pos)
+    dev, st = _device_stream()
+    nall = len(make_ghosts_cell(pos, cell, LIST_CUTOFF)[0])
+    assert nall > n
+    cf = np.array([0, n], dtype=np.int32)
+    gc, xc = capi.Ghosts(0), _rows(pos, nall, dev)
+    assert gc.build_cell(xc, n, cell, LIST_CUTOFF, stream=st) == nall
+    owner_c, one = _owners(gc, n, nall, dev, st), xc.cpu().numpy()
+    origins = [np.zeros((1, 3))] + ([np.array([[11.5, -3.25, 0.75]])] if which == "tilted5_far" else [])
+    for org in origins:
+        gb, xb = capi.Ghosts(0), _rows(pos, nall, dev)
+        assert gb.build_batch(xb, cf, [cell], org, LIST_CUTOFF, stream=st) == nall
+        owner_b, many = _owners(gb, n, nall, dev, st), xb.cpu().numpy()
+        assert np.array_equal(owner_b, owner_c) and np.array_equal(owner_c[:n], np.arange(n))
+        if not org.any():
+            assert np.array_equal(many[n:] - many[owner_b[n:]], one[n:] - one[owner_c[n:]])
+            assert (many[:n] == one[:n]).all()
+        else:
+            err = float(np.abs((many - org) - one).max())
+            print("%s under origin %s: max |rows - origin - single-cell rows| %.3e" % (which, org[0], err))
+            assert err < 1e-12
+
+
+@pytest.mark.gpu
+def test_one_handle_across_every_build_growing_and_shrinking():
+    """orthogonal build, build_cell and build_batch in turn on ONE handle, sizes going 16 -> 1 -> 70 -> 300 -> 3 -> 1 owned
+    atoms (every buffer regrows at the 300, the range buffer with its 64-bit total behind it among them): after each, nall,
+    owners and positions are those a fresh handle gives for the same call -- the same code on the same input, compared
+    exactly.  After each of the last two builds owner(), then deform with identity matrices: forward reproduces that build's
+    ghost rows exactly -- the second time only if the build in between dropped the shifts the first deform had kept."""
+    import torch
+    from lammps_mtp_kokkos_amd import mtpgen
+    dev, st = _device_stream()
+
+    def cell_step(pos, cell):
+        nall = len(make_ghosts_cell(pos, cell, LIST_CUTOFF)[0])
+        return len(pos), (lambda: _rows(pos, nall, dev)), (lambda g, x: g.build_cell(x, len(pos), cell, LIST_CUTOFF, stream=st))
+
+    def batch_step(batch):
+        xa, twin, lay, cf, _, _ = _upload_batch(batch)
+        cells = [c for _, c, _ in batch]
+        return int(cf[-1]), xa.clone, (lambda g, x: g.build_batch(x, cf, cells, lay["origins"], LIST_CUTOFF, stream=st))
+
+    bpos, box = mtpgen.bcc_lattice(2, 2, 2)
+    assert (box >= 3.0).all()
+    ppos, pcell, _ = _cells.primitive_cell()
+    tpos, tcell, _ = _cells.replicate(*_cells.tilted5_cell(), (4, 3, 5))
+    assert len(tpos) == 300
+    steps = [("box", (len(bpos), (lambda: _rows(bpos, 27 * len(bpos), dev)),
+                      (lambda g, x: g.build(x, len(bpos), box, 3.0, stream=st)))),
+             ("primitive", cell_step(ppos, pcell)),
+             ("mixed batch", batch_step(_batch.mixed_batch())),
+             ("tilted 300", cell_step(tpos, tcell)),
+             ("first two of the batch", batch_step(_batch.mixed_batch()[:2])),
+             ("primitive again", cell_step(ppos, pcell))]
+    row_cfg_of = {"first two of the batch": [0, 1, 1], "primitive again": [0]}    # the configuration of every owned row
+    g = capi.Ghosts(0)
+    for what, (n, rows, build) in steps:
+        got, want = [], []
+        for handle, out in ((g, got), (capi.Ghosts(0), want)):
+            x = rows()
+            nall = build(handle, x)
+            out += [nall, _owners(handle, n, nall, dev, st), x.cpu().numpy()[:nall], x]
+        print("%s: %d owned, %d rows" % (what, n, got[0]))
+        assert got[0] == want[0] > n, what
+        assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2]), what
+        if what not in row_cfg_of:
+            continue
+        nall, owner, built, x = got
+        ptr, nown = g.owner(stream=st)                                               # identity | owners, in the handle's storage
+
+        class _Span:
+            pass
+        span = _Span()
+        span.__cuda_array_interface__ = dict(shape=(nown,), typestr="<i4", data=(int(ptr), False), version=2, strides=None)
+        torch.cuda.synchronize()
+        assert nown == nall and np.array_equal(torch.as_tensor(span, device=dev).cpu().numpy(), owner)
+        row_cfg = torch.tensor(row_cfg_of[what], dtype=torch.int32, device=dev)
+        eye = torch.eye(3, dtype=torch.float64, device=dev).reshape(1, 9).repeat(max(row_cfg_of[what]) + 1, 1).contiguous()
+        g.deform(row_cfg, eye, stream=st)
+        x[n:] = -5.0
+        g.forward(x, stream=st)
+        torch.cuda.synchronize()
+        assert np.array_equal(x.cpu().numpy()[:nall], built)
