@@ -221,6 +221,18 @@ static __device__ __forceinline__ double pair_sum32(double v)
       __longlong_as_double((long long) (((unsigned long long) c[1] << 32) | a[1]));
 }
 
+// pair_sum32 of two values for one exchange: v_permlane32_swap of a against b leaves {a of half 0 | b of half 0} in one
+// register and {a of half 1 | b of half 1} in the other, so their sum is the pair sum of a in the lanes of half 0 and
+// the pair sum of b in those of half 1, each the half-0 term plus the half-1 term as pair_sum32 adds them.
+static __device__ __forceinline__ double pair_sum32_t(double a, double b)
+{
+  const long long ba = __double_as_longlong(a), bb = __double_as_longlong(b);
+  const auto l = __builtin_amdgcn_permlane32_swap((unsigned) ba, (unsigned) bb, false, false);
+  const auto h = __builtin_amdgcn_permlane32_swap((unsigned) (ba >> 32), (unsigned) (bb >> 32), false, false);
+  return __longlong_as_double((long long) (((unsigned long long) h[0] << 32) | l[0])) +
+      __longlong_as_double((long long) (((unsigned long long) h[1] << 32) | l[1]));
+}
+
 static __device__ __forceinline__ double wave_sum(double v)   // same bits in every lane
 {
   v += partner_f64<1>(v);

@@ -157,6 +157,29 @@ __device__ __forceinline__ double select_f64(unsigned long long mask, double a, 
   asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(hi) : "v"(ahi), "v"(bhi), "s"(mask));
   return __hiloint2double((int) hi, (int) lo);
 }
+// Two trims of the five-factor force shape (fwd5_ct and no grade call); every output bit stays.
+// sum_t_ct: the six accumulators cross the two neighbour groups in pairs (pair_sum32_t, mtp_kernel_common.hpp): half 0
+// ends with the totals of products 0..2, half 1 with those of 3..5, and every lane of a block stores three moments --
+// three exchanges, adds and stores per atom instead of six.  The lane's three int16 indices (products 3 q + 0..2) are
+// packed into kk5[0..1] once per wavefront.
+#ifndef MTP_SUM_T
+#define MTP_SUM_T 1   // 0: six pair_sum32 and six stores from half 0, for A/B runs
+#endif
+template <class SH> constexpr bool force5_shape()
+{
+  if constexpr (fwd5_shape<SH>()) return !SH::kGRADE;
+  else return false;
+}
+template <class SH> constexpr bool sum_t_ct = MTP_SUM_T && MTP_FWD5 && force5_shape<SH>();
+// cnt_sgpr_ct: the neighbour count goes back into an SGPR behind the compaction.  The optimiser merges the branch that
+// clamps it to cj_cap with the lane test of the error flag inside and leaves the count in a VGPR, and every test behind
+// it -- the tile count, the padded tile width, the sixteen column tests of the basic-moment pass in both copies of the
+// tile loop -- is then a vector compare with an EXEC region around the column.  From an SGPR they are scalar compares
+// and branches.
+#ifndef MTP_CNT_SGPR
+#define MTP_CNT_SGPR 1   // 0: the count as the optimiser leaves it, for A/B runs
+#endif
+template <class SH> constexpr bool cnt_sgpr_ct = MTP_CNT_SGPR && MTP_FWD5 && force5_shape<SH>();
 
 // Issue priority by phase (s_setprio), in the fixed FORCE shapes of the 3-per-SIMD build.  The phases of an atom want
 // opposite things of the SIMD: tile tables, basic moments, coefficient blocks and forces are VALU bursts; the loop head,

@@ -159,6 +159,8 @@
   // pair.  fa[f] / fb[f]: LDS byte addresses of the two rows of factor f for this lane's neighbour column, per atom.
   constexpr bool FWD5 = BLOCK_REGS && fwd5_ct<SH>;
   constexpr int NACC = FWD5 ? 6 : 9;   // products of a block
+  // the trims of the five-factor force shape (mtp_wave_body.hpp: sum_t_ct, cnt_sgpr_ct)
+  constexpr bool SUM_T = FWD5 && NG == 2 && sum_t_ct<SH>, CNT_SGPR = FWD5 && cnt_sgpr_ct<SH>;
   unsigned fa[5], fb[5];
   unsigned bpk5[5] = {0u, 0u, 0u, 0u, 0u}, kk5[3] = {0u, 0u, 0u};
   unsigned long long shape5 = 0ull;
@@ -177,9 +179,14 @@
     const uint4 *bd = reinterpret_cast<const uint4 *>(kp->blob + SHF(off_fwd5)) + 2 * (kl < SHF(nfb5) ? kl : 0);
     const uint4 lo = bd[0], hi = bd[1];
     const unsigned wd[5] = {lo.x, lo.y, lo.z, lo.w, hi.x};
-    kk5[0] = hi.y;
-    kk5[1] = hi.z;
-    kk5[2] = hi.w;
+    if constexpr (SUM_T) {   // the indices of products 3 q + 0..2 in kk5[0..1]
+      kk5[0] = q ? (hi.z >> 16) | (hi.w << 16) : hi.y;
+      kk5[1] = q ? hi.w >> 16 : hi.z & 0xffffu;
+    } else {
+      kk5[0] = hi.y;
+      kk5[1] = hi.z;
+      kk5[2] = hi.w;
+    }
     const bool head2 = (wd[2] >> 31) != 0u;
     shape5 = __ballot(head2);
 #pragma unroll
@@ -348,6 +355,7 @@
       if (lane == 0) atomicExch(kp->err_flag, 2);
       cnt = kp->cj_cap;
     }
+    if constexpr (CNT_SGPR) cnt = __builtin_amdgcn_readfirstlane(cnt);   // (cnt_sgpr_ct: the merge above left it in a VGPR)
     {   // dummy neighbours pad tile 0 to a multiple of NG
       const int pos = cnt + lane;
       if (cnt < NT && lane < NG && pos < ((min(cnt, NT) + NG - 1) / NG) * NG) {
@@ -445,6 +453,10 @@
     STAMP(3);   // basic moments
     phase_prio<PHASE_PRIO, MTP_PRIO_CHAIN>();   // product passes, leaf sweep, energy: a few instructions between LDS round trips
     // sum over the neighbour groups, then moments + adjoints into LDS
+    if constexpr (SUM_T) {   // total e in half 0, total e + 3 in half 1
+#pragma unroll
+      for (int e = 0; e < 3; e++) acc[0][e] = pair_sum32_t(acc[0][e], acc[0][e + 3]);
+    } else {
 #pragma unroll
     for (int t = 0; t < NB; t++)
 #pragma unroll
@@ -452,6 +464,7 @@
         if (NG >= 4) acc[t][e] = pair_sum16(acc[t][e]);   // KL = 16: groups differ in lane bits 4 and 5
         if (NG >= 2) acc[t][e] = pair_sum32(acc[t][e]);
       }
+    }
     for (int m = SHF(B) + lane; m < SHF(Am); m += 64) w.M[m] = 0.0;
     for (int m = lane; m < SHF(Ad); m += 64) w.D[m] = 0.0;
 #if MTP_LEAF_SWEEP
@@ -472,7 +485,17 @@
       }
     }
 #endif
-    if constexpr (FWD5) {
+    if constexpr (SUM_T) {
+      if (bval[0]) {
+        // the lane's three int16 basic indices, products 3 q + 0..2 (-1: no such basic), from the registers
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+          asm volatile("" : "+v"(kk5[e >> 1]));   // (opaque per atom: the unpacked indices are not kept across the loop)
+          const int k = (int) (short) (kk5[e >> 1] >> (16 * (e & 1)));
+          if (k >= 0) w.M[k] = acc[0][e];
+        }
+      }
+    } else if constexpr (FWD5) {
       if (q == 0 && bval[0]) {
         // the block's six int16 basic indices in product order (-1: no such basic), from the registers
 #pragma unroll
