@@ -719,6 +719,9 @@ const char *mtp_kernel_build_flags()
 #if MTP_ROW_REGS != 1
       "MTP_ROW_REGS=" MTP_STR(MTP_ROW_REGS) " "
 #endif
+#if MTP_ROW_KEEP_L1 != 1
+      "MTP_ROW_KEEP_L1=" MTP_STR(MTP_ROW_KEEP_L1) " "
+#endif
 #if MTP_PHASE_PRIO != 1
       "MTP_PHASE_PRIO=" MTP_STR(MTP_PHASE_PRIO) " "
 #endif

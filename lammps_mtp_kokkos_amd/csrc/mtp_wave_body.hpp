@@ -273,6 +273,8 @@ template <class SH, int MI> constexpr int slot_delta()
     }
   return 0;
 }
+// the lane's index into the gathered ids: lane, spelled lane & 31 under row_keep_l1_ct (defined with it below)
+template <class SH> __device__ __forceinline__ int gather_lane(int lane);
 template <int PITCH, class SH>
 __device__ __forceinline__ void build_tile(KP kp, const BlockTables &bt, const WaveLds<PITCH> &w,
                                            int t0, int cnt, int ntp, bool gather, bool powers, bool with_dg, bool do_park,
@@ -282,7 +284,7 @@ __device__ __forceinline__ void build_tile(KP kp, const BlockTables &bt, const W
   if (gather) {
     if (lane < ntp) {
       const bool real = t0 + lane < cnt;
-      const int j = real ? w.cj[t0 + lane] : i;
+      const int j = real ? w.cj[t0 + gather_lane<SH>(lane)] : i;
       double dx = 0, dy = 0, dz = 0, r = kp->rmax, inv = kp->inv_rmax;
       if (real) {
         const double *xj = row3(kp->x, j);
@@ -683,28 +685,76 @@ template <int U, int NIT> __device__ __forceinline__ void backward_level_kept(co
     lds_add(&at8(D, kr[u].lo & 0xffffu), d3[u] * m1[u]);
   }
 }
-template <int U, class SH, int L, int NK>
-__device__ __forceinline__ void forward_levels_kept(const MtpRow8 *rows, const MtpRow8 (&kr)[NK], double *M, int lane)
+// row_keep_l1_ct (round 16): the first ROW_KEEP_L1 blocks of the first level, a long one, join the kept rows -- its first
+// two trips at MTP_PU = 2.  Each lane loads its row of them once per wavefront, from the blob, both passes take those
+// trips from registers and run the level's other blocks as before, in the same order.  Two registers a block: with
+// them the function stands at 168 VGPRs.
+#ifndef MTP_ROW_KEEP_L1
+#define MTP_ROW_KEEP_L1 1   // 0: the first level reads all its rows per atom, for A/B runs
+#endif
+constexpr int ROW_KEEP_L1 = 4;
+template <class SH> constexpr bool row_keep_l1_shape()
+{
+  if constexpr (row_regs_shape<SH>()) return level_blocks<SH>(0) >= ROW_KEEP_L1 && !level_kept<SH>(0);
+  else return false;
+}
+template <class SH> constexpr bool row_keep_l1_ct = MTP_ROW_KEEP_L1 && row_regs_ct<SH> && row_keep_l1_shape<SH>();
+template <class SH> constexpr int kept_l1_count() { return row_keep_l1_ct<SH> ? ROW_KEEP_L1 : 1; }   // (1: an array nobody reads)
+template <class SH, int N1> __device__ __forceinline__ void load_kept_l1_rows(const MtpRow8 *rows, MtpRow8 (&k1)[N1], int lane)
+{
+#pragma unroll
+  for (int b = 0; b < N1; b++) k1[b] = rows[SH::level_rows(0) + 64 * b + lane];
+}
+// At 168 VGPRs hipcc spilled one dword of that build: the LDS address of the gather's cj[] read (build_tile), base + 4
+// lane, which it keeps across the atom loop for the atoms of more than one tile.  The gather runs in the lanes below
+// ntp <= 32, where lane & 31 is lane; spelled so, the address can be formed from the lane & 31 registers that the
+// force phase keeps anyway, and nothing spills.  The other kernels keep the plain spelling and with it their code.
+template <class SH> __device__ __forceinline__ int gather_lane(int lane)
+{
+  if constexpr (row_keep_l1_ct<SH>) return lane & 31;
+  else return lane;
+}
+// K1: the first ROW_KEEP_L1 blocks of level 0 are k1[] (whole trips: ROW_KEEP_L1 is a multiple of U)
+template <int U, class SH, int L, bool K1, int NK, int N1>
+__device__ __forceinline__ void forward_levels_kept(const MtpRow8 *rows, const MtpRow8 (&kr)[NK], const MtpRow8 (&k1)[N1], double *M,
+                                                    int lane)
 {
   if constexpr (L < SH::nlevels) {
     constexpr int beg = SH::level_rows(L), nit = level_blocks<SH>(L);
-    if constexpr (level_kept<SH>(L)) forward_level_kept<U, nit>(&kr[kept_before<SH>(L)], M);
-    else forward_level<U>(rows + beg + lane, nit, M);
+    if constexpr (level_kept<SH>(L)) {
+      forward_level_kept<U, nit>(&kr[kept_before<SH>(L)], M);
+    } else if constexpr (K1 && L == 0) {
+      static_assert(N1 == ROW_KEEP_L1 && ROW_KEEP_L1 % U == 0 && nit >= ROW_KEEP_L1, "whole trips from registers");
+#pragma unroll
+      for (int b = 0; b < ROW_KEEP_L1; b += U) forward_level_kept<U, U>(&k1[b], M);
+      forward_level<U>(rows + (beg + 64 * ROW_KEEP_L1) + lane, nit - ROW_KEEP_L1, M);
+    } else {
+      forward_level<U>(rows + beg + lane, nit, M);
+    }
     wave_fence();
-    forward_levels_kept<U, SH, L + 1>(rows, kr, M, lane);
+    forward_levels_kept<U, SH, L + 1, K1>(rows, kr, k1, M, lane);
   }
 }
 // (K counts the levels done: level L = nlevels - 1 - K, so that the call site names no member of SH)
-template <int U, class SH, int K, int NK>
-__device__ __forceinline__ void backward_levels_kept(const MtpRow8 *rows, const MtpRow8 (&kr)[NK], const double *M, double *D, int lane)
+template <int U, class SH, int K, bool K1, int NK, int N1>
+__device__ __forceinline__ void backward_levels_kept(const MtpRow8 *rows, const MtpRow8 (&kr)[NK], const MtpRow8 (&k1)[N1],
+                                                     const double *M, double *D, int lane)
 {
   if constexpr (K < SH::nlevels) {
     constexpr int L = SH::nlevels - 1 - K;
     constexpr int beg = SH::level_rows(L), nit = level_blocks<SH>(L);
-    if constexpr (level_kept<SH>(L)) backward_level_kept<U, nit>(&kr[kept_before<SH>(L)], M, D);
-    else backward_level<U>(rows + beg + lane, nit, M, D);
+    if constexpr (level_kept<SH>(L)) {
+      backward_level_kept<U, nit>(&kr[kept_before<SH>(L)], M, D);
+    } else if constexpr (K1 && L == 0) {
+      static_assert(N1 == ROW_KEEP_L1 && ROW_KEEP_L1 % U == 0 && nit >= ROW_KEEP_L1, "whole trips from registers");
+#pragma unroll
+      for (int b = 0; b < ROW_KEEP_L1; b += U) backward_level_kept<U, U>(&k1[b], M, D);
+      backward_level<U>(rows + (beg + 64 * ROW_KEEP_L1) + lane, nit - ROW_KEEP_L1, M, D);
+    } else {
+      backward_level<U>(rows + beg + lane, nit, M, D);
+    }
     wave_fence();
-    backward_levels_kept<U, SH, K + 1>(rows, kr, M, D, lane);
+    backward_levels_kept<U, SH, K + 1, K1>(rows, kr, k1, M, D, lane);
   }
 }
 

@@ -95,6 +95,10 @@
   constexpr bool ROW_REGS = !GATHER && MTP_PU >= ROW_KEEP_LEVEL && row_regs_ct<SH>;   // (the gather passes have no rows per level)
   MtpRow8 krow[kept_count<SH>()];
   if constexpr (ROW_REGS) load_kept_rows<SH, 0>(bt.rows, krow, lane);
+  // row_keep_l1_ct: and its row of the first blocks of the first level (whole trips of the passes)
+  constexpr bool KEEP_L1 = ROW_REGS && ROW_KEEP_L1 % MTP_PU == 0 && row_keep_l1_ct<SH>;
+  MtpRow8 krow1[kept_l1_count<SH>()];
+  if constexpr (KEEP_L1) load_kept_l1_rows<SH>(bt.rows, krow1, lane);
   // (not in the KL = 16 grade build: there the SGPR pair costs a twelfth spilled VGPR dword)
   constexpr bool MU_PACKED = MTP_MU_BITS && WPS == 3 && !(GRADE && KL == 16);
   SlotMu<MU_PACKED> smu{bt.smu, 0ull};
@@ -524,7 +528,7 @@
     if constexpr (GATHER) {
       gather_pass(kp->prog_fwd, bt.seg_fwd, SHF(nlevels), w.M, w.M, w.M, lane);
     } else {
-      if constexpr (ROW_REGS) forward_levels_kept<MTP_PU, SH, 0>(bt.rows, krow, w.M, lane);
+      if constexpr (ROW_REGS) forward_levels_kept<MTP_PU, SH, 0, KEEP_L1>(bt.rows, krow, krow1, w.M, lane);
       else if (rows_lds) products_forward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, lane);
       else products_forward<MTP_PU, SH>(kp, kp->rows, bt.level, w.M, lane);
     }
@@ -575,7 +579,7 @@
     if constexpr (GATHER) {
       gather_pass(kp->prog_bwd, bt.seg_bwd, SHF(nlevels), w.D, w.M, w.D, lane);
     } else {
-      if constexpr (ROW_REGS) backward_levels_kept<MTP_PU, SH, 0>(bt.rows, krow, w.M, w.D, lane);
+      if constexpr (ROW_REGS) backward_levels_kept<MTP_PU, SH, 0, KEEP_L1>(bt.rows, krow, krow1, w.M, w.D, lane);
       else if (rows_lds) products_backward<MTP_PU, SH>(kp, bt.rows, bt.level, w.M, w.D, lane);
       else products_backward<MTP_PU, SH>(kp, kp->rows, bt.level, w.M, w.D, lane);
     }
