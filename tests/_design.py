@@ -12,6 +12,7 @@ import numpy as np
 
 import _cells
 import _stars
+import _tables
 import _train
 from lammps_mtp_kokkos_amd.driver import periodic_system_cell
 
@@ -136,10 +137,12 @@ SPECIAL_BITS = np.int32(-2 ** 31 + 2 ** 30)                      # the top two b
 
 @functools.lru_cache(maxsize=None)
 def handles(name):
-    """namespace(path, pot, tables, orc) of a file of potentials/ or of a key of test_train_gpu.GENERATED, which is written
-    once into a directory that lives as long as the process"""
+    """namespace(path, pot, tables, orc) of a file of potentials/, of a key of test_train_gpu.GENERATED or of a case of
+    tests/_tables.CENTRE_TABLES; the latter two are written once into a directory that lives as long as the process"""
     from lammps_mtp_kokkos_amd import capi, mtpgen
     from oracle.pyoracle import Oracle
+    if name in _tables.CENTRE_TABLES:
+        return _tables.centre_handles(name)
     path, keep = os.path.join(POT, name), None
     if not os.path.exists(path):
         from test_train_gpu import GENERATED
@@ -162,6 +165,8 @@ def star_cases():
             cases["%s-%s" % (fname, special)] = (fname, SMALL_KL, 72, special, "mixed")
         for which in sorted(GENERATED):
             cases["%s-%s" % (which, special)] = (which, GENERATED_KL, 73, special, "mixed")
+        for which in sorted(_tables.CENTRE_TABLES):          # hand-made tables: Mu up to 16, rank 11, sparse slots
+            cases["%s-%s" % (which, special)] = (which, _tables.CENTRE_KL, 74, special, "mixed")
     cases["ranges"] = ("W_L8.mtp", RANGE_KL, 91, None, "mixed")
     cases["bits"] = ("W_L8.mtp", BITS_KL, 93, None, "mixed")
     cases["second"] = ("W_L8.mtp", SECOND_KL, 94, None, "mixed")

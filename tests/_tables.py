@@ -1,6 +1,9 @@
 """Seeded MLIP-3 tables that do not come from the level generator (mtpgen.build_table): any set of radial slots
 (mu, nu), each with all of its monomials or a chosen subset (a sparse table: coefficient blocks with holes), any
-radial basis size, scaling and window.  Shared by tests/test_shapes_cpu.py and tests/test_gpu_shapes.py.
+radial basis size, scaling and window.  Shared by the force kernel's instantiation matrix (tests/test_shapes_cpu.py,
+tests/test_gpu_shapes.py, tests/test_gpu_geometry.py) and, through CENTRE_TABLES at the end of the file, by the tests of the
+two per-centre kernels: the design rows (tests/_design.py, tests/test_design_cpu.py, tests/test_design_gpu.py) and the
+training gradient (tests/test_train_cpu.py, tests/test_train_gpu.py).
 
 Scalars of a table:
   * every rank-0 basic on its own;
@@ -10,6 +13,11 @@ Scalars of a table:
   * a few three-factor chains: (contraction) x (rank-0 basic).
 Rows are written target by target, each target after its factors: topologically ordered.
 """
+import functools
+import os
+import tempfile
+from types import SimpleNamespace
+
 import numpy as np
 
 from lammps_mtp_kokkos_amd import mtpgen
@@ -214,3 +222,81 @@ def basic_limit_slots(extra):
         slots.append((8 + k, 1))
         subsets[(8 + k, 1)] = [(1, 0, 0)]
     return slots, subsets
+
+
+# ---- tables for the per-centre kernels (csrc/mtp_design.hip, csrc/mtp_train.hip, csrc/mtp_centre_common.hpp) -----------
+# The level generator stops at five radial functions, dense slots and rank 8.  Each case below is the smallest table that
+# reaches one more path of those kernels; `reaches` says which (NT = 32 columns per tile, eight threads -- parts -- per
+# column, 256 threads; tile_radial deals radial function mu to part 7 - mu % 8).
+_MU16 = [(mu, 0) for mu in range(16)] + [(0, 1), (7, 1), (8, 1), (15, 1), (15, 2), (8, 3), (0, 6)]
+_MU16_SUB = {(0, 6): [(6, 0, 0), (2, 2, 2), (0, 3, 3), (1, 0, 5), (4, 1, 1)]}
+CENTRE_TABLES = dict(
+    mu6=dict(slots=[(mu, 0) for mu in range(6)] + [(5, 1), (4, 2)], species=1,
+             reaches="parts 3 and 2 compute a radial function and write a power row"),
+    mu8=dict(slots=[(mu, 0) for mu in range(8)] + [(0, 1), (7, 1), (3, 2), (7, 2), (1, 3), (6, 3)], species=2,
+             reaches="every part computes a radial function: part 0 (nb, r^-nu) computes mu = 7"),
+    mu9=dict(slots=[(mu, 0) for mu in range(9)] + [(8, 1), (0, 2), (8, 2), (3, 3)], species=2, R=9, scaling=0.37,
+             reaches="second trip of the dealing loop in part 7 only, the thread that keeps Q and Q'; R != 8 behind 2 Mu"),
+    mu13_gaps=dict(slots=[(0, 0), (2, 0), (5, 0), (7, 0), (12, 0), (2, 1), (12, 1), (5, 2), (7, 3), (0, 4)],
+                   subsets={(0, 4): [(4, 0, 0), (2, 1, 1), (0, 2, 2), (1, 3, 0), (0, 0, 4), (1, 1, 2)]}, species=2,
+                   reaches="radial functions without basics (empty mufirst runs), 2 Mu > 24 scratch rows, blk = 208"),
+    mu16_sp3=dict(slots=_MU16, subsets=_MU16_SUB, species=3,
+                  reaches="Mu NT = 512 items and blk = 384: second trips of both vjp loops; 1152 radial columns"),
+    mu16_sp2_nbh=dict(slots=_MU16, subsets=_MU16_SUB, species=2, mvs="nbh",
+                      reaches="Sp Mu R = 256, the grade kernels' limit: the unfused candidate vectors at Mu = 16"),
+    rank11=dict(slots=[(0, 0), (1, 0), (0, 11), (1, 11)],
+                subsets={(0, 11): [(11, 0, 0), (4, 4, 3), (5, 3, 3), (0, 0, 11)],
+                         (1, 11): [(4, 4, 3), (0, 11, 0), (5, 3, 3), (1, 1, 9)]}, species=1,
+                reaches="P = 12, the loader's cap; multiplicity 11 550 in the packed rows; holes in coefficient blocks"),
+)
+# exact neighbour counts of the star sets these tables are run on: no, one and two neighbours, a full tile, one past it,
+# three tiles; row lengths K, K + 1 and past two compaction sweeps
+CENTRE_KL = [(K, L) for K in (0, 1, 2, 32, 33, 65) for L in (K, K + 1, 129)]
+
+
+def deal_wrongly(radial_coeffs, Sp, Mu, how):
+    """a copy of the radial block [Sp Sp, Mu, R] (flat) as a wrong tile_radial would use it.  "dropped": the second trip of
+    its loop never runs, every mu >= 8 gives zero; "modulo": the coefficient row is taken at mu % 8; "part0": the share of
+    part 0, radial function 7, is never computed.  For the tests that show that their rule rejects such a kernel."""
+    rc = np.array(radial_coeffs, dtype=np.float64).reshape(Sp * Sp, Mu, -1)
+    if how == "dropped":
+        rc[:, 8:] = 0.0
+    elif how == "modulo":
+        rc[:, 8:] = rc[:, :Mu - 8].copy()
+    else:
+        assert how == "part0" and Mu >= 8
+        rc[:, 7] = 0.0
+    assert not np.array_equal(rc.reshape(-1), np.asarray(radial_coeffs).reshape(-1))
+    return rc.reshape(-1)
+
+
+# (case, damage) pairs of the "judge rejects" tests: every case with a second trip, and part 0's share on mu8
+DEALT_WRONGLY = [(n, h) for n in ("mu9", "mu13_gaps", "mu16_sp3", "mu16_sp2_nbh") for h in ("dropped", "modulo")] + [("mu8", "part0")]
+
+
+def centre_table(name):
+    """(table, factors per scalar) of a case of CENTRE_TABLES"""
+    c = CENTRE_TABLES[name]
+    return make_table(c["slots"], c.get("subsets"))
+
+
+def write_centre(name, path, mvs=None):
+    """the case written to `path`; mvs: a selection state of that mode where the case itself has none"""
+    c = CENTRE_TABLES[name]
+    tab, nfac = centre_table(name)
+    return write(tab, nfac, path, mvs=mvs or c.get("mvs"), species=c["species"], R=c.get("R", 8), scaling=c.get("scaling", 1.0))
+
+
+@functools.lru_cache(maxsize=None)
+def centre_handles(name):
+    """namespace(path, pot, tables, orc, keep) of a case, as tests/_design.handles returns it (which hands these names on to
+    here): written once into a directory that lives as long as the process.  Every case must be one the training calls
+    accept."""
+    from lammps_mtp_kokkos_amd import capi
+    from oracle.pyoracle import Oracle
+    keep = tempfile.TemporaryDirectory()
+    path = write_centre(name, os.path.join(keep.name, name + (".almtp" if CENTRE_TABLES[name].get("mvs") else ".mtp")))
+    pot = capi.Potential(path)
+    t = pot.train_table()
+    assert t["supported"], (name, t["message"])
+    return SimpleNamespace(path=path, pot=pot, tables=pot.tables(), orc=Oracle(path), keep=keep)

@@ -252,6 +252,73 @@ def test_judge_rejects_1e8_relative_on_one_column_of_a_one_neighbour_star_beside
     assert _design.column_ratio(got["force"], want["f_all"]) <= 1.0
 
 
+# ---- hand-made tables for the per-centre kernels (tests/_tables.CENTRE_TABLES): Mu up to 16, rank 11, sparse slots ---------
+# Their star sets are registered in _design.star_cases(), so test_twin_alone_is_inside_the_bound_... above holds the twin to
+# the oracle's columns on each of them.  Here: every case has the property it is in the catalogue for, and the rule rejects a
+# twin whose radial functions are dealt the way a wrong tile_radial would deal them.
+# name -> Mu, blk = Sp Mu R, [radial functions without a basic], [P, largest multiplicity]
+CENTRE_PROPERTIES = dict(mu6=(6, 48, []), mu8=(8, 128, []), mu9=(9, 162, []), mu13_gaps=(13, 208, [1, 3, 4, 6, 8, 9, 10, 11]),
+                         mu16_sp3=(16, 384, []), mu16_sp2_nbh=(16, 256, []), rank11=(2, 16, [], 12, 11550))
+
+
+def test_the_catalogue_is_the_list_of_properties():
+    assert sorted(CENTRE_PROPERTIES) == sorted(_tables.CENTRE_TABLES)
+
+
+@pytest.mark.parametrize("name", sorted(CENTRE_PROPERTIES))
+def test_every_centre_table_is_supported_and_has_the_property_it_is_there_for(name):
+    Mu, blk, empty = CENTRE_PROPERTIES[name][:3]
+    case, h = _tables.CENTRE_TABLES[name], _design.handles(name)
+    s, t = h.pot.sizes, h.pot.train_table()
+    assert t["supported"] and t["message"] == "" and t["C"] == len(h.pot.theta())
+    assert (s["Mu"], s["Sp"] * s["Mu"] * s["R"], s["Sp"], s["R"]) == (Mu, blk, case["species"], case.get("R", 8))
+    assert h.tables["scaling"] == case.get("scaling", 1.0) and (b"#MVS" in open(h.path, "rb").read()) == bool(case.get("mvs"))
+    mf = t["mufirst"]
+    assert [mu for mu in range(Mu) if mf[mu] == mf[mu + 1]] == empty and mf[0] == 0 and mf[-1] == s["B"]
+    used = sorted(set(int(mu) for mu in h.tables["alpha_index_basic"][:, 0]))
+    assert used == [mu for mu in range(Mu) if mu not in empty]
+    # what the training kernel's loops do with it (NT = 32 columns, 256 threads, 24 scratch rows for value mode)
+    assert (Mu > 8) == (name in ("mu9", "mu13_gaps", "mu16_sp3", "mu16_sp2_nbh")), "second trip of the dealing and item loops"
+    assert (2 * Mu > 24) == (name in ("mu13_gaps", "mu16_sp3", "mu16_sp2_nbh")), "scratch rows sized by 2 Mu"
+    assert (blk > 256) == (name == "mu16_sp3"), "second trip of the loop over the radial block"
+    for slot, mons in case.get("subsets", {}).items():           # a sparse slot: some of its monomials, not all
+        have = [tuple(b[1:]) for b in h.tables["alpha_index_basic"] if b[0] == slot[0] and sum(b[1:]) == slot[1]]
+        assert sorted(have) == sorted(mons) and len(mons) < len(mtpgen.monomials(slot[1]))
+    if len(CENTRE_PROPERTIES[name]) > 3:
+        P, mult = CENTRE_PROPERTIES[name][3:]
+        assert s["P"] == P and int(h.tables["alpha_index_times"][:, 2].max()) == mult
+        for slot in case["subsets"]:
+            assert (4, 4, 3) in case["subsets"][slot]
+    print("%s: Mu %d, blk %d, B %d, A %d, S %d, C %d: %s" % (name, Mu, blk, s["B"], s["A"], s["S"], s["C"], case["reaches"]))
+
+
+def _deal_wrongly(tables, how):
+    """the tables with the radial block as a wrong tile_radial would use it (tests/_tables.deal_wrongly)"""
+    Mu = int(np.asarray(tables["alpha_index_basic"])[:, 0].max()) + 1
+    return dict(tables, radial_coeffs=_tables.deal_wrongly(tables["radial_coeffs"], len(tables["species_coeffs"]), Mu, how))
+
+
+@pytest.mark.parametrize("special", [None, "edge"])
+@pytest.mark.parametrize("name,how", _tables.DEALT_WRONGLY)
+def test_judge_rejects_radial_functions_dealt_wrongly_over_the_eight_parts(name, how, special):
+    """every star with a neighbour strictly inside the cutoff is rejected, in its basis row, its force rows and its virial
+    rows; a star without one (K = 0, or K = 1 with its one neighbour ON the cutoff, where every radial function and its
+    derivative vanish) sees nothing of the radial block and stays inside the bound"""
+    case = "%s-%s" % (name, special)
+    c = _design.star_case(case)
+    r = _ratios(case, _design.twin_rows(_deal_wrongly(c.h.tables, how), c.st))
+    seen = [s for s, (K, L) in enumerate(c.st.KL) if K > (1 if special == "edge" else 0)]
+    _only(r, seen, what="%s %s" % (case, how))
+    fold = np.minimum(np.minimum(r["basis"], r["force"]), r["virial"])
+    one = [s for s in seen if c.st.KL[s][0] <= 32]
+    many = [s for s in seen if c.st.KL[s][0] > 32]
+    print("%s %s: the damaged twin misses the bound %.1e-fold at least on one tile, %.1e-fold on several" % (
+        case, how, fold[one].min(), fold[many].min()))
+    assert len(one) and len(many) and (fold[one] > 1.0).all() and (fold[many] > 1.0).all()
+    if special is None:
+        assert any(c.st.KL[s][0] == 1 for s in seen) and any(c.st.KL[s][0] == 2 for s in seen)
+
+
 # ---- the tangent kernel's table ----------------------------------------------------------------------------------------
 def _replay(pot, rng):
     """the table's level-ordered rows over an image with every moment stored, values AND tangents, against the file-order

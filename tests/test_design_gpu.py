@@ -14,6 +14,7 @@ import _batch  # noqa: E402
 import _cells  # noqa: E402
 import _design  # noqa: E402
 import _stars  # noqa: E402
+import _tables  # noqa: E402
 import _train  # noqa: E402
 from lammps_mtp_kokkos_amd import capi, md  # noqa: E402
 
@@ -251,6 +252,26 @@ def test_generated_potentials_species_pairs_radial_size_scaling_and_cutoff(which
     small = [k for k, (K, L) in enumerate(st.KL) if 0 < K <= 6]
     if Sp >= 3:
         assert any(len(set(st.types[st.neigh[st.first[k]:st.first[k + 1]]])) < Sp for k in small), "a row that lacks a neighbour type"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("special", [None, "edge"])
+@pytest.mark.parametrize("name", sorted(_tables.CENTRE_TABLES))
+def test_hand_made_tables_six_to_sixteen_radial_functions_rank_eleven_and_sparse_slots(name, special):
+    """tests/_tables.CENTRE_TABLES, which the level generator cannot make: every part of a neighbour column computes a radial
+    function (Mu = 6, 8), the second trip of tile_radial's dealing loop (Mu = 9, 13, 16), radial functions without a basic,
+    three species at Mu = 16, P = 12 with a multiplicity of 11 550 in the packed rows, slots that list some of their
+    monomials.  K in {0, 1, 2, 32, 33, 65} x L in {K, K + 1, 129}, rows shuffled, one launch; plain and with an entry on the
+    cutoff.  tests/test_design_cpu.py shows that the rule rejects radial functions dealt wrongly on these very sets"""
+    c, want, got = _run_case("%s-%s" % (name, special))
+    case = _tables.CENTRE_TABLES[name]
+    assert c.st.KL == _tables.CENTRE_KL and _ctx(name).pot.sizes["Sp"] == case["species"]
+    assert set(c.st.types[c.st.ilist]) == set(range(1, case["species"] + 1)), "a centre of every species"
+    if special is None:                                      # no vacuous comparison: no scalar's force column is all zero
+        bounds = list(c.st.start) + [c.st.nall]
+        for s, (K, L) in enumerate(c.st.KL):
+            if K >= 2:
+                assert np.abs(want["f_all"][bounds[s]:bounds[s + 1], :, case["species"]:]).max((0, 1)).all(), (s, K, L)
 
 
 def _outer(st):

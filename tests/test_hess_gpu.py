@@ -395,8 +395,25 @@ def test_mass_weighting_on_the_device_is_the_division_by_the_root_masses():
         w = 1.0 / np.sqrt(np.outer(M, M))
         err = np.abs(got[j]["hessian"] - want[j]["hessian"] * w)
         assert (err <= _bound(want[j]["f0"], want[j]["hessian"]) * w).all(), j
-    ratio = np.abs(got[5]["hessian"]).max() / np.abs(want[5]["hessian"]).max()
-    assert 1.0 / MASSES[species].max() <= ratio <= 1.0 / MASSES[species].min()
+    # The largest entry of H / sqrt(m_c m_r) over the largest entry of H lies between 1 / m_max and 1 / m_min in exact
+    # arithmetic, and ON an end of that interval when both maxima sit in a block of two atoms of one species (here they do:
+    # the lighter species, the upper end).  So this is an equality test, and its two sides differ by
+    #   (a) roundings.  Device: p = fl(m_c m_r), q = fl(sqrt p), t = fl(1 / q), fl(s t), each correctly rounded: relative
+    #       errors u / 2 (the square root halves p's), u, u, u with u = 2^-53.  Host: the quotient of the two maxima and
+    #       1 / m, u each.  5.5 u in all, which is 2.75 eps: 3 eps.
+    #   (b) the two runs.  `got` and `want` come from two passes of force calls whose atomic sums need not run in the same
+    #       order, so their H differ in the last places -- enough to put the quotient on either side of 1 / m from one
+    #       run to the next (measured: 3 eps below in one run, equal in the next), which is how this assertion failed
+    #       on unchanged kernels and passed when run again.  No count of roundings bounds that; the project's force
+    #       parity bound does.  The loop above has just held every entry of got to want w within _bound w, hence
+    #       max |got| <= (max |H| + _bound) / m_min and max |got| >= (max |H| - _bound) / m_max.
+    hmax = np.abs(want[5]["hessian"]).max()
+    ratio = np.abs(got[5]["hessian"]).max() / hmax
+    slack = _bound(want[5]["f0"], want[5]["hessian"]) / hmax + 3.0 * np.finfo(np.float64).eps
+    lo, hi = 1.0 / MASSES[species].max(), 1.0 / MASSES[species].min()
+    print("mass weighting: max |H w| / max |H| = 1 / m_min x (1 %+.3e), = 1 / m_max x (1 %+.3e); eps %.3e, slack %.3e"
+          % (ratio / hi - 1.0, ratio / lo - 1.0, np.finfo(np.float64).eps, slack))
+    assert lo * (1.0 - slack) <= ratio <= hi * (1.0 + slack)
 
 
 @pytest.mark.gpu

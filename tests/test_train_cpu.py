@@ -22,6 +22,7 @@ import _cells  # noqa: E402
 import _design  # noqa: E402
 import _mutate  # noqa: E402
 import _stars  # noqa: E402
+import _tables  # noqa: E402
 import _train  # noqa: E402
 from lammps_mtp_kokkos_amd import capi, mtpgen  # noqa: E402
 from lammps_mtp_kokkos_amd.driver import design_twin, periodic_system_cell, train_twin  # noqa: E402
@@ -129,6 +130,11 @@ def _nine_radial(tmp):
 STAR_FD_KL = [(1, 1), (1, 2), (2, 3), (33, 40), (65, 129)]
 STAR_FD_CASES = [("W_L8 plain", _w8, None), ("W_L8 edge", _w8, "edge"), ("5 species level 6", _five_species, None),
                  ("3 species R = 9 edge", _nine_radial, "edge")]
+# the hand-made tables of tests/_tables.CENTRE_TABLES (Mu up to 16, rank 11, sparse slots), and one of them with an entry on
+# the cutoff.  Worst ratios measured: mu6 9.1e-12, mu8 1.1e-11, mu9 8.5e-12 (edge 1.7e-11), mu13_gaps 5.8e-12, mu16_sp3
+# 1.2e-11, mu16_sp2_nbh 5.8e-12, rank11 1.1e-11
+STAR_FD_CASES += [(name, lambda tmp, name=name: _design.handles(name).path, None) for name in sorted(_tables.CENTRE_TABLES)]
+STAR_FD_CASES += [("mu9 edge", lambda tmp: _design.handles("mu9").path, "edge")]
 
 
 @pytest.mark.parametrize("label,make,special", STAR_FD_CASES, ids=[c[0] for c in STAR_FD_CASES])
@@ -145,6 +151,11 @@ def test_twin_rows_of_stars_against_the_oracles_finite_difference_star_by_star(t
     ebar, fbar, vbar = _train.row_cotangents(st, 8)
     rows = train_twin(tables, s, theta, _train.padded_rows(st, ebar), fbar, _train.padded_rows(st, vbar))["rows"][:len(st.ilist)]
     cols = list(range(len(theta))) if len(theta) < 40 else _train.sample_columns(orc, 24)
+    if label.split()[0] in _tables.CENTRE_TABLES and len(theta) >= 40:
+        # the sample may miss what the table is there for: one column of EVERY radial function (pair 1-1) as well, those
+        # without a basic (their columns are zero) included
+        Mu, R = orc.m.radial_func_count, orc.m.radial_basis_size
+        cols = sorted(set(cols) | set(mu * R + mu % R for mu in range(Mu)))
     worst = 0.0
     try:
         _train.set_theta(orc, theta)
@@ -186,6 +197,66 @@ def test_twin_value_of_stars_is_the_oracle_at_a_perturbed_theta(special, order):
         w = int(np.argmax(v))
         print("twin value %s %s %s: worst error / tolerance %.3e at star %d (K, L) = %s" % (special, order, k, v[w], w, st.KL[w]))
         assert np.isfinite(v).all() and v[w] <= 1.0, (k, w, st.KL[w], v[w])
+
+
+@pytest.mark.parametrize("special", [None, "edge"])
+@pytest.mark.parametrize("name", sorted(_tables.CENTRE_TABLES))
+def test_twin_value_on_the_hand_made_tables_is_the_oracle_at_a_perturbed_theta(name, special):
+    """tests/_tables.CENTRE_TABLES on the stars of the GPU tests (tests/_tables.CENTRE_KL), per star, through
+    _train.oracle_value"""
+    h = _design.handles(name)
+    st = _train.star_set(h.tables, _tables.CENTRE_KL, 74, special)
+    s = _train.star_system(st)
+    theta0 = _train.get_theta(h.orc)
+    np.testing.assert_array_equal(theta0, h.pot.theta())
+    theta = theta0 * (1.0 + 0.05 * np.random.default_rng(2).normal(size=len(theta0)))
+    try:
+        _train.set_theta(h.orc, theta)
+        want = _train.oracle_value(h.orc, s)
+    finally:
+        _train.set_theta(h.orc, theta0)
+    tw = train_twin(h.tables, s, theta)
+    n = len(st.ilist)                                        # (the twin's eatom and vatom by list row, the oracle's by atom)
+    ratios = _stars.per_star_ratios(st, dict(f=tw["force"], eatom=_train.by_atom(st, tw["eatom"][:n]), vatom=_train.by_atom(st, tw["vatom"][:n])),
+                                    dict(f=want["force"], eatom=want["eatom"], vatom=want["vatom"]))
+    for k, v in ratios.items():
+        w = int(np.argmax(v))
+        print("twin value %s %s %s: worst error / tolerance %.3e at star %d (K, L) = %s" % (name, special, k, v[w], w, st.KL[w]))
+        assert np.isfinite(v).all() and v[w] <= 1.0, (k, w, st.KL[w], v[w])
+    assert np.abs(want["force"]).max() > 1e-3
+
+
+@pytest.mark.parametrize("name,how", _tables.DEALT_WRONGLY)
+def test_the_rule_of_the_gpu_rows_rejects_radial_functions_dealt_wrongly(name, how):
+    """the GPU tests hold the kernel's gradient rows to the twin's with _train.star_block_ratio.  Rows of a twin whose radial
+    functions are those a wrong tile_radial would compute ("dropped": no second trip, mu >= 8 gives zero; "modulo": the
+    coefficient row of mu % 8; "part0": radial function 7 never computed) are refused by that rule at every star with a
+    neighbour inside the cutoff, one tile or several, and pass at the K = 0 stars, whose rows hold ebar alone"""
+    h = _design.handles(name)
+    st = _train.star_set(h.tables, _tables.CENTRE_KL, 74)
+    s = _train.star_system(st)
+    n, Sp, nrad = len(st.ilist), len(h.tables["species_coeffs"]), len(h.tables["radial_coeffs"])
+    theta0 = h.pot.theta()
+    theta = theta0 * (1.0 + 0.05 * np.random.default_rng(2).normal(size=len(theta0)))
+    ebar, fbar, vbar = _train.row_cotangents(st, 174)
+    cots = (_train.padded_rows(st, ebar), fbar, _train.padded_rows(st, vbar))
+    good = train_twin(h.tables, s, theta, *cots)["rows"][:n]
+    wrong = np.concatenate([_tables.deal_wrongly(theta[:nrad], Sp, h.pot.sizes["Mu"], how), theta[nrad:]])
+    bad = train_twin(h.tables, s, wrong, *cots)["rows"][:n]
+    folds = {}
+    for k, (K, L) in enumerate(st.KL):
+        if K == 0:
+            assert _train.star_block_ratio(bad[k:k + 1], good[k:k + 1], nrad, Sp, st.KL[k:k + 1], "%s %s K = 0" % (name, how)) <= 1.0
+            continue
+        with pytest.raises(AssertionError, match="misses 1e-9") as ei:
+            _train.star_block_ratio(bad[k:k + 1], good[k:k + 1], nrad, Sp, st.KL[k:k + 1], "%s %s" % (name, how))
+        w = good[k]
+        folds[k] = float((np.abs(bad[k] - w) / (1e-9 + 1e-10 * np.abs(w).max())).max())
+    one = [f for k, f in folds.items() if st.KL[k][0] <= 32]
+    many = [f for k, f in folds.items() if st.KL[k][0] > 32]
+    print("%s %s: the damaged twin's rows miss the bound %.1e-fold at least on one tile, %.1e-fold on several" % (
+        name, how, min(one), min(many)))
+    assert len(one) == 9 and len(many) == 6 and min(one) > 1.0 and min(many) > 1.0
 
 
 def test_unit_energy_cotangent_rows_are_the_oracles_coeff_ders():

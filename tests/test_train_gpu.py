@@ -17,6 +17,7 @@ import _cells  # noqa: E402
 import _design  # noqa: E402
 import _mutate  # noqa: E402
 import _stars  # noqa: E402
+from _tables import CENTRE_KL, CENTRE_TABLES, write_centre  # noqa: E402
 import _train  # noqa: E402
 from lammps_mtp_kokkos_amd import capi, md, mtpgen  # noqa: E402
 from lammps_mtp_kokkos_amd.driver import periodic_system_cell, train_twin  # noqa: E402
@@ -32,7 +33,8 @@ def _device_stream():
 
 @functools.lru_cache(maxsize=None)
 def _pot(fname):
-    return capi.Potential(os.path.join(POT, fname))
+    """a file of potentials/ or a case of tests/_tables.CENTRE_TABLES"""
+    return _design.handles(fname).pot if fname in CENTRE_TABLES else capi.Potential(os.path.join(POT, fname))
 
 
 @functools.lru_cache(maxsize=None)
@@ -496,6 +498,119 @@ def test_generated_potentials_three_and_five_species_nine_radial_functions_and_a
     small = [k for k, (K, L) in enumerate(st.KL) if 0 < K <= 6]
     if Sp >= 3:
         assert any(len(set(st.types[st.neigh[st.first[k]:st.first[k + 1]]])) < Sp for k in small), "a row that lacks a neighbour type"
+
+
+# ---- hand-made tables (tests/_tables.CENTRE_TABLES): what the level generator cannot make -----------------------------------
+# Mu = 6 and 8: every part of a neighbour column computes a radial function; Mu = 9, 13, 16: the second trip of tile_radial's
+# dealing loop (made by the thread that keeps Q and Q'), of the vjp item loop (Mu NT > 256) and, with three species, of the
+# loop over the radial block (blk = 384); 2 Mu > 24 scratch rows; radial functions without a basic; P = 12 and a
+# multiplicity of 11 550; slots that list some of their monomials.  tests/test_train_cpu.py holds the twin to the oracle's
+# finite differences on these tables and shows that the rule used here rejects radial functions dealt wrongly.
+@functools.lru_cache(maxsize=None)
+def _centre_handles(name):
+    return _Handles(_design.handles(name).path)
+
+
+def _radial_columns_without_basics(name):
+    """indices into theta of the radial columns of every radial function that no basic uses, all species pairs"""
+    h = _design.handles(name)
+    s, mf = h.pot.sizes, h.pot.train_table()["mufirst"]
+    empty = [mu for mu in range(s["Mu"]) if mf[mu] == mf[mu + 1]]
+    return np.array([(pair * s["Mu"] + mu) * s["R"] + rho for pair in range(s["Sp"] ** 2) for mu in empty for rho in range(s["R"])],
+                    dtype=np.int64)
+
+
+def _assert_positive_zero(rows, cols, what):
+    """bit for bit +0.0: an empty sum that was never added to, not a small number inside the bound"""
+    assert len(cols) and rows[:, cols].size and not rows[:, cols].copy().view(np.int64).any(), what
+    rest = np.setdiff1d(np.arange(rows.shape[1]), cols)
+    assert np.abs(rows[:, rest]).max() > 1e-3, what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("special", [None, "edge"])
+@pytest.mark.parametrize("name", sorted(CENTRE_TABLES))
+def test_hand_made_tables_stars_value_and_gradient_rows(name, special):
+    """K in {0, 1, 2, 32, 33, 65} x L in {K, K + 1, 129} (tests/_tables.CENTRE_KL), at a theta perturbed by 5 %"""
+    h = _centre_handles(name)
+    case = CENTRE_TABLES[name]
+    assert h.Sp == case["species"] and h.nrad == h.Sp * h.Sp * h.pot.sizes["Mu"] * case.get("R", 8)
+    st = _train.star_set(h.tables, CENTRE_KL, 74, special)
+    theta = h.perturbed_theta()
+    cots = _train.row_cotangents(st, 174)
+    got = _star_call(h.ctx, st, theta, *cots)
+    _judge_stars(h, st, theta, cots, got, "%s stars %s" % (name, special))
+    assert set(st.types[st.ilist]) == set(range(1, h.Sp + 1)), "a centre of every species"
+    if name == "mu13_gaps":
+        _assert_positive_zero(got["rows"], _radial_columns_without_basics(name), "columns of radial functions without basics")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["mu9", "mu13_gaps", "mu16_sp3"])
+def test_hand_made_tables_periodic_cell_with_owner_map_and_ghosts(name):
+    """the 16-atom replica with the case's species: ghosts, an owner map that folds them, fbar by owner"""
+    Sp = CENTRE_TABLES[name]["species"]
+    pos, cell, types = _two_species(_design.replica16_cell(), 4)
+    if Sp == 3:
+        types = np.random.default_rng(4).integers(1, 4, len(pos)).astype(np.int32)
+    assert set(types) == set(range(1, Sp + 1))
+    s = periodic_system_cell(pos, cell, types, _cells.LIST_CUTOFF)
+    assert s.nall > s.nlocal and (np.asarray(s.owner)[s.nlocal:] < s.nlocal).all()
+    theta = _perturbed_theta(name)
+    cots = _train.cotangents(s.nlocal, 7)
+    tw = train_twin(_tables(name), s, theta, *cots)
+    got = _device_call(name, s, theta, *cots)
+    _batch.close(got["eatom"], tw["eatom"], "%s cell eatom" % name, atol=1e-10)
+    _batch.close(got["force"], tw["force"], "%s cell force" % name)
+    _batch.close(got["vatom"], tw["vatom"], "%s cell vatom" % name, atol=1e-8)
+    _check_rows(name, got["rows"], tw["rows"], "%s cell rows" % name)
+    if name == "mu13_gaps":
+        _assert_positive_zero(got["rows"], _radial_columns_without_basics(name), "columns of radial functions without basics")
+
+
+@pytest.mark.gpu
+def test_unfused_candidate_vectors_at_sixteen_radial_functions_entry_by_entry():
+    """mu16_sp2_nbh: Sp Mu R = 256, the grade kernels' limit, on a table outside the fused shape (Mu > 4), so the candidate
+    vectors come from csrc/mtp_cvec_kernel.hip: four passes over mu0, all four crad entries of every lane.  The grades of the
+    call against the oracle's under the rule of tests/test_gpu_shapes._check; then every entry of the candidate vectors
+    against the training kernel's ebar = 1 rows (which tests/test_train_cpu.py holds to the oracle through the twin)"""
+    from test_gpu_shapes import _check
+    name = "mu16_sp2_nbh"
+    path = _design.handles(name).path
+    s = _system("replica16_two")
+    pot, ctx, got, want = _check(path, s, grade=True)
+    sz = pot.sizes
+    assert sz["Mu"] == 16 > 4 and sz["Sp"] * sz["Mu"] * sz["R"] == 256 and not pot.info.configuration_mode, "unfused, at the limit"
+    g, w = got["grades"][s.ilist], want["grades"][s.ilist]
+    print("%s grades: worst error / bound %.3e, max grade %.6e" % (name, float((np.abs(g - w) / (1e-9 + 1e-9 * np.abs(w))).max()), want["max_grade"]))
+    cand = ctx.candidates()[:s.nlocal].cpu().numpy()
+    theta = pot.theta()
+    C = len(theta)
+    assert cand.shape[1] >= C and C == sz["C"]
+    rows = _device_call(name, s, theta, np.ones(s.nlocal), None, None, value=False)["rows"]
+    _check_rows(name, cand[:, :C], rows, "%s: candidate vectors against the ebar = 1 rows" % name)
+    _check_rows(name, rows, cand[:, :C], "%s: ebar = 1 rows against the candidate vectors" % name)
+    assert (np.abs(rows[:, :256 * sz["Sp"]]).reshape(len(rows), -1, 16, 8).max((0, 1, 3)) > 1e-6).all(), "every radial function"
+
+
+@pytest.mark.gpu
+def test_three_species_at_sixteen_radial_functions_grades_refused_training_goes_on(tmp_path):
+    """mu16_sp3 with a selection state: Sp Mu R = 384 is above the grade kernels' 256 and the grade call is refused with
+    MTP_ERR_LIMIT; a training call on the same context afterwards is judged like any other"""
+    path = write_centre("mu16_sp3", str(tmp_path / "mu16_sp3.almtp"), mvs="nbh")
+    h = _Handles.__new__(_Handles)
+    from oracle.pyoracle import Oracle
+    h.pot = capi.Potential(path, selection=True)
+    h.ctx, h.tables, h.orc = capi.Context(h.pot, 0), h.pot.tables(), Oracle(path)
+    h.Sp, h.nrad = len(h.tables["species_coeffs"]), len(h.tables["radial_coeffs"])
+    assert h.pot.info.has_selection and h.Sp * h.pot.sizes["Mu"] * h.pot.sizes["R"] == 384
+    st = _train.star_set(h.tables, [(1, 2), (2, 2), (33, 34), (0, 1), (65, 66)], 90)
+    h.ctx.set_neighbors(st.ilist, st.first, st.neigh, st.nall)
+    with pytest.raises(capi.MtpError, match="Sp\\*Mu\\*R above 256") as ei:
+        h.ctx.compute(st.x, st.types, grade=True)
+    assert ei.value.code == -24
+    theta, cots = h.perturbed_theta(), _train.row_cotangents(st, 91)
+    _judge_stars(h, st, theta, cots, _star_call(h.ctx, st, theta, *cots), "mu16_sp3 after the refused grade call")
 
 
 @pytest.mark.gpu
