@@ -675,6 +675,8 @@ hipError_t mtp_launch_ev_finish(double *ev_slots, double *ev, hipStream_t st)
   return hipGetLastError();
 }
 
+// Every compile-time switch of the force kernel that differs from its shipped value, in the order of the block of
+// defaults at the top of mtp_wave_body.hpp, then the grade GEMM's pair (defaults beside mtp_grade_kernel_os above).
 const char *mtp_kernel_build_flags()
 {
 #define MTP_STR2(x) #x
@@ -683,41 +685,14 @@ const char *mtp_kernel_build_flags()
 #if MTP_PU != 2
       "MTP_PU=" MTP_STR(MTP_PU) " "
 #endif
-#if MTP_LD != 1
-      "MTP_LD=" MTP_STR(MTP_LD) " "
+#if MTP_FWD5 != 1
+      "MTP_FWD5=" MTP_STR(MTP_FWD5) " "
 #endif
-#if MTP_POLY_CH != 8
-      "MTP_POLY_CH=" MTP_STR(MTP_POLY_CH) " "
+#if MTP_SUM_T != 1
+      "MTP_SUM_T=" MTP_STR(MTP_SUM_T) " "
 #endif
-#if MTP_POLY_ACC != 1
-      "MTP_POLY_ACC=" MTP_STR(MTP_POLY_ACC) " "
-#endif
-#if MTP_COEF_DPP != 1
-      "MTP_COEF_DPP=" MTP_STR(MTP_COEF_DPP) " "
-#endif
-#if MTP_LEAF_SWEEP != 1
-      "MTP_LEAF_SWEEP=" MTP_STR(MTP_LEAF_SWEEP) " "
-#endif
-#if MTP_E_HOIST != 1
-      "MTP_E_HOIST=" MTP_STR(MTP_E_HOIST) " "
-#endif
-#if MTP_MU_BITS != 1
-      "MTP_MU_BITS=" MTP_STR(MTP_MU_BITS) " "
-#endif
-#if MTP_LEVEL_ARGS != 1
-      "MTP_LEVEL_ARGS=" MTP_STR(MTP_LEVEL_ARGS) " "
-#endif
-#if MTP_SLOT_ARGS != 1
-      "MTP_SLOT_ARGS=" MTP_STR(MTP_SLOT_ARGS) " "
-#endif
-#if MTP_FP_REGS != 1
-      "MTP_FP_REGS=" MTP_STR(MTP_FP_REGS) " "
-#endif
-#if MTP_BLOCK_REGS != 1
-      "MTP_BLOCK_REGS=" MTP_STR(MTP_BLOCK_REGS) " "
-#endif
-#if MTP_ROW_REGS != 1
-      "MTP_ROW_REGS=" MTP_STR(MTP_ROW_REGS) " "
+#if MTP_CNT_SGPR != 1
+      "MTP_CNT_SGPR=" MTP_STR(MTP_CNT_SGPR) " "
 #endif
 #if MTP_ROW_KEEP_L1 != 1
       "MTP_ROW_KEEP_L1=" MTP_STR(MTP_ROW_KEEP_L1) " "
@@ -725,7 +700,6 @@ const char *mtp_kernel_build_flags()
 #if MTP_PHASE_PRIO != 1
       "MTP_PHASE_PRIO=" MTP_STR(MTP_PHASE_PRIO) " "
 #endif
-
 #if MTP_GRADE_TPB != 512 || MTP_GRADE_WPE != 2
       "MTP_GRADE_TPB=" MTP_STR(MTP_GRADE_TPB) " "
 #endif

@@ -14,10 +14,31 @@
 
 namespace {
 
+// ---- compile-time switches of the force kernel -----------------------------------------------------------------------
+// All of them, with their shipped values; `make variant EXTRA=-DMTP_...=` builds another.  mtp_kernel_build_flags()
+// (mtp_kernels.hip) names every one that differs from the value here, in this order, then MTP_GRADE_TPB / MTP_GRADE_WPE
+// of the grade GEMM, whose defaults stand beside that kernel; MTP_STAMPS (a diagnostic build, no value) is named by
+// mtp_build_flags() itself.  tests/test_row_reads_cpu.py checks that no default here lacks its entry there.  The switches
+// of decided comparisons are taken out of the sources with the arm that lost.
 #ifndef MTP_PU
 #define MTP_PU 2   // times rows in flight per lane in the row-per-lane product passes (4 until the leaf moments and the
                    // per-tile totals changed the balance: re-measured 1 / 2 / 3 / 4 / 5 / 6 rows: 0.473 / 0.473 / 0.477 / 0.482 /
                    // 0.486 / 0.496 ms at level 16)
+#endif
+#ifndef MTP_FWD5
+#define MTP_FWD5 1   // 0: the 3 x 3 blocks in the fixed shapes too, for A/B runs (fwd5_ct)
+#endif
+#ifndef MTP_SUM_T
+#define MTP_SUM_T 1   // 0: six pair_sum32 and six stores from half 0, for A/B runs (sum_t_ct)
+#endif
+#ifndef MTP_CNT_SGPR
+#define MTP_CNT_SGPR 1   // 0: the count as the optimiser leaves it, for A/B runs (cnt_sgpr_ct)
+#endif
+#ifndef MTP_ROW_KEEP_L1
+#define MTP_ROW_KEEP_L1 1   // 0: the first level reads all its rows per atom, for A/B runs (row_keep_l1_ct)
+#endif
+#ifndef MTP_PHASE_PRIO
+#define MTP_PHASE_PRIO 1   // 0: every phase at the launch's priority, for A/B runs (phase_prio_ct)
 #endif
 
 // The parameter block is read through the kernarg segment pointer (address space 4: scalar loads from the constant
@@ -64,20 +85,17 @@ template <class F, int... I> __device__ __forceinline__ void static_for(F &&f, s
 // structure, yet read from the LDS blob the tile build waits for three 16-byte reads of slot[] at the head of every
 // radial function before a store address exists, tests every row index (an EXEC region each) and multiplies it by
 // the pitch, and the kernel entry forms the slot -> mu word by two ballots.  slot_ct: the tile build takes the rows
-// from the shape (build_tile) and SlotMu::bits is the shape's constant.  The generic kernels keep the reads.
-#ifndef MTP_SLOT_ARGS
-#define MTP_SLOT_ARGS 1   // 0: the fixed shapes read slot[] and smu[] from the blob too, for A/B runs
-#endif
+// from the shape (build_tile) and SlotMu::bits is the shape's constant.  The generic kernels keep the reads
+// (profiles/r09_ab_slot_tables.txt has the timing).
 template <class SH>
-constexpr bool slot_rows_ct = MTP_SLOT_ARGS && mtp_shape::has_slot_row<SH>::value && mtp_shape::has_Mu<SH>::value &&
+constexpr bool slot_rows_ct = mtp_shape::has_slot_row<SH>::value && mtp_shape::has_Mu<SH>::value &&
     mtp_shape::has_P<SH>::value && mtp_shape::has_R<SH>::value;
 template <class SH>
-constexpr bool slot_mu_shape = mtp_shape::has_slot_mu_lo<SH>::value && mtp_shape::has_slot_mu_hi<SH>::value &&
+constexpr bool slot_mu_ct = mtp_shape::has_slot_mu_lo<SH>::value && mtp_shape::has_slot_mu_hi<SH>::value &&
     mtp_shape::has_nslot<SH>::value && mtp_shape::has_Mu<SH>::value;
-template <class SH> constexpr bool slot_mu_ct = MTP_SLOT_ARGS && slot_mu_shape<SH>;
 template <class SH> constexpr unsigned long long slot_mu_bits()
 {
-  if constexpr (slot_mu_shape<SH>) return ((unsigned long long) (unsigned) SH::slot_mu_hi << 32) | (unsigned) SH::slot_mu_lo;
+  if constexpr (slot_mu_ct<SH>) return ((unsigned long long) (unsigned) SH::slot_mu_hi << 32) | (unsigned) SH::slot_mu_lo;
   else return 0ull;   // (never used: a shape without the map)
 }
 template <class SH> __device__ __forceinline__ int slot_mu_of(int s) { return (int) (slot_mu_bits<SH>() >> (2 * s)) & 3; }
@@ -86,12 +104,9 @@ template <class SH> __device__ __forceinline__ int slot_mu_of(int s) { return (i
 // the halves (v_permlane32_swap with both operands equal leaves the low half's value in one register and the high
 // half's in the other, in every lane: pair_sum32) hands all four to both, and where the shape fixes the slot -> mu map
 // and the slots of every rank, each slot visit takes the register of its mu: no f' rows are written (fp_from_parked),
-// no fence, no read per slot visit.  Same bits as the stored and re-read value, same arithmetic after it.
-#ifndef MTP_FP_REGS
-#define MTP_FP_REGS 1   // 0: the f' rows go through LDS in the fixed shapes too, for A/B runs
-#endif
-template <class SH>
-constexpr bool fp_regs_ct = MTP_FP_REGS && slot_mu_shape<SH> && mtp_shape::has_deg_first<SH>::value;
+// no fence, no read per slot visit.  Same bits as the stored and re-read value, same arithmetic after it (timed against
+// the rows through LDS in the same log).
+template <class SH> constexpr bool fp_regs_ct = slot_mu_ct<SH> && mtp_shape::has_deg_first<SH>::value;
 #define MTP_FP_N 4   // f'_0 .. f'_3: Mu <= 4 in the nodg layouts
 __device__ __forceinline__ void fp_exchange(const double (&park)[2], double (&F)[MTP_FP_N])
 {
@@ -116,17 +131,14 @@ __device__ __forceinline__ double fp_pick(const double (&F)[MTP_FP_N], int mu)
 // not fit beside the rest of the loop.  Their row byte offsets (below 2^16: tab_rows x 8 PITCH) do, as 16-bit halves of
 // six registers, and an address per atom is then one add of the base and a 16-bit word.  The descriptors are table
 // contents and are still read from the blob, once per wavefront.  Not in the grade shape: that build has no register
-// to spare.
-#ifndef MTP_BLOCK_REGS
-#define MTP_BLOCK_REGS 1   // 0: the block addresses are decoded from the blob per atom, for A/B runs
-#endif
+// to spare.  (Against the decode per atom: profiles/r10_ab_force_regs.txt.)
 template <class SH> constexpr bool block_regs_shape()
 {
   if constexpr (mtp_shape::has_pow_row<SH>::value && mtp_shape::has_P<SH>::value && mtp_shape::has_tab_rows<SH>::value)
     return !SH::kGRADE && SH::kWPS == 3 && SH::kNB == 1 && SH::tab_rows * 8 * SH::kPITCH < 65536;
   else return false;
 }
-template <class SH> constexpr bool block_regs_ct = MTP_BLOCK_REGS && block_regs_shape<SH>();
+template <class SH> constexpr bool block_regs_ct = block_regs_shape<SH>();
 // Basic-moment pass in five-factor blocks (mtp_potential.hpp, fwd5_blocks) in the fixed shapes of the 3-per-SIMD build
 // that name the table (nfb5, off_fwd5) and keep a lane's block in registers (block_regs_ct: the force shape).  The 3 x 3 blocks of level 16 are half empty -- 130 basics in 26 blocks of
 // nine, because the head x tail grids are thin at both ends (16 x 1 ... 1 x 7) --, and a column costs a lane twelve
@@ -136,9 +148,6 @@ template <class SH> constexpr bool block_regs_ct = MTP_BLOCK_REGS && block_regs_
 // partners differ between the two cuts: two selects per column, their mask one SGPR pair formed once per wavefront
 // (select_f64).  Every basic is the same sum over the same columns of (row x row) x (row x row), so the bits do not
 // change.  The generic kernels and the grade shape (no register to spare for the block) keep the 3 x 3 pass.
-#ifndef MTP_FWD5
-#define MTP_FWD5 1   // 0: the 3 x 3 blocks in the fixed shapes too, for A/B runs
-#endif
 template <class SH> constexpr bool fwd5_shape()
 {
   if constexpr (mtp_shape::has_nfb5<SH>::value && mtp_shape::has_off_fwd5<SH>::value &&
@@ -162,9 +171,6 @@ __device__ __forceinline__ double select_f64(unsigned long long mask, double a, 
 // ends with the totals of products 0..2, half 1 with those of 3..5, and every lane of a block stores three moments --
 // three exchanges, adds and stores per atom instead of six.  The lane's three int16 indices (products 3 q + 0..2) are
 // packed into kk5[0..1] once per wavefront.
-#ifndef MTP_SUM_T
-#define MTP_SUM_T 1   // 0: six pair_sum32 and six stores from half 0, for A/B runs
-#endif
 template <class SH> constexpr bool force5_shape()
 {
   if constexpr (fwd5_shape<SH>()) return !SH::kGRADE;
@@ -176,9 +182,6 @@ template <class SH> constexpr bool sum_t_ct = MTP_SUM_T && MTP_FWD5 && force5_sh
 // it -- the tile count, the padded tile width, the sixteen column tests of the basic-moment pass in both copies of the
 // tile loop -- is then a vector compare with an EXEC region around the column.  From an SGPR they are scalar compares
 // and branches.
-#ifndef MTP_CNT_SGPR
-#define MTP_CNT_SGPR 1   // 0: the count as the optimiser leaves it, for A/B runs
-#endif
 template <class SH> constexpr bool cnt_sgpr_ct = MTP_CNT_SGPR && MTP_FWD5 && force5_shape<SH>();
 
 // Issue priority by phase (s_setprio), in the fixed FORCE shapes of the 3-per-SIMD build.  The phases of an atom want
@@ -190,9 +193,6 @@ template <class SH> constexpr bool cnt_sgpr_ct = MTP_CNT_SGPR && MTP_FWD5 && for
 // lowered in the bursts: four s_setprio per atom, -5.7 % per step on the headline launch.  The generic kernels and the
 // grade shape compile as they did.  (A start offset per SIMD slot, MTP_WAVE_STAGGER, was measured beside it, lost, and
 // is not in the sources: the same record.)
-#ifndef MTP_PHASE_PRIO
-#define MTP_PHASE_PRIO 1   // 0: every phase at the launch's priority, for A/B runs
-#endif
 template <class SH, class = void> struct has_kernel_args : std::false_type {};
 template <class SH> struct has_kernel_args<SH, std::void_t<decltype(&SH::kGRADE), decltype(&SH::kWPS)>> : std::true_type {};
 template <class SH> constexpr bool phase_prio_shape()
@@ -513,11 +513,7 @@ static __device__ __forceinline__ const double &at8(const double *base, unsigned
 // has the bounds, and with them the block count of every level, as constants (level_ct).  The generic kernels keep the
 // LDS reads: a scalar load of the field per bound costs their headline function ten more s_load than the round-6 guard
 // allows (tests/test_isa_params_cpu.py; profiles/r08_ab_table_reads.txt has the timing).
-#ifndef MTP_LEVEL_ARGS
-#define MTP_LEVEL_ARGS 1   // 0: the fixed shapes read the bounds from the blob's level table too, for A/B runs
-#endif
-template <class SH>
-constexpr bool level_ct = MTP_LEVEL_ARGS && mtp_shape::has_nlevels<SH>::value && mtp_shape::has_level_rows<SH>::value;
+template <class SH> constexpr bool level_ct = mtp_shape::has_nlevels<SH>::value && mtp_shape::has_level_rows<SH>::value;
 template <class SH> __device__ __forceinline__ int level_row(const int *level, int l)   // l wave-uniform
 {
   if constexpr (level_ct<SH>) return SH::level_rows(l);
@@ -620,10 +616,8 @@ __device__ __forceinline__ void products_backward(KP kp, const MtpRow8 *rows, co
 // the trip starts with a row read that its operand reads wait for: latency the level cannot hide.  The rows are the
 // same for every atom, so where the shape fixes the level table (level_ct: which levels are short is then a constant)
 // and keeps the rows in the LDS blob, each lane loads the rows of those blocks once per wavefront, from the blob (rows
-// are table contents, not shape), and both passes take them from registers: same rows, same lanes, same order.
-#ifndef MTP_ROW_REGS
-#define MTP_ROW_REGS 1   // 0: every level reads its rows per atom, for A/B runs
-#endif
+// are table contents, not shape), and both passes take them from registers: same rows, same lanes, same order
+// (profiles/r10_ab_force_regs.txt).
 constexpr int ROW_KEEP_LEVEL = 2;   // blocks of a level that is kept (one trip at MTP_PU = 2)
 constexpr int ROW_KEEP_MAX = 3;     // blocks kept in all: two registers each
 template <class SH> constexpr int level_blocks(int l) { return (SH::level_rows(l + 1) - SH::level_rows(l)) >> 6; }
@@ -643,7 +637,7 @@ template <class SH> constexpr bool row_regs_shape()
         kept_before<SH>(SH::nlevels) <= ROW_KEEP_MAX;
   else return false;
 }
-template <class SH> constexpr bool row_regs_ct = MTP_ROW_REGS && row_regs_shape<SH>();
+template <class SH> constexpr bool row_regs_ct = row_regs_shape<SH>();
 template <class SH> constexpr int kept_count()
 {
   if constexpr (row_regs_ct<SH>) return kept_before<SH>(SH::nlevels);
@@ -689,9 +683,6 @@ template <int U, int NIT> __device__ __forceinline__ void backward_level_kept(co
 // two trips at MTP_PU = 2.  Each lane loads its row of them once per wavefront, from the blob, both passes take those
 // trips from registers and run the level's other blocks as before, in the same order.  Two registers a block: with
 // them the function stands at 168 VGPRs.
-#ifndef MTP_ROW_KEEP_L1
-#define MTP_ROW_KEEP_L1 1   // 0: the first level reads all its rows per atom, for A/B runs
-#endif
 constexpr int ROW_KEEP_L1 = 4;
 template <class SH> constexpr bool row_keep_l1_shape()
 {
@@ -763,49 +754,44 @@ __device__ __forceinline__ void backward_levels_kept(const MtpRow8 *rows, const 
 // e += cf M[a0] M[a1] with cf = linear coefficient x mult (grade calls also keep M[a3] += mult M[a0] M[a1]: the
 // candidate vector lists the leaves' values).  Reverse: D[a0] += cb M[a1], D[a1] += cb M[a0] with the constant adjoint
 // cb = seed(a3) x mult -- no D[a3] read.  Row per lane as above; the constants are lane-contiguous like the rows.
+// The factors are final once the stored levels are done and cb is a constant, so the reverse terms issue in the same
+// sweep from the factors already in registers (D must hold the seeds by then).  Every D slot still receives its seed,
+// then the leaf terms in the same row and lane order, then the level terms: bitwise the same as a second pass over the
+// leaf rows behind the energy, which was measured slower (profiles/r05_ab_product_tail.txt).
 // FAR: rows and constants come from HBM / L2 (wide lane grids, whose rows do not fit in LDS): batches of U rows are
-// requested MTP_LD batches ahead of their use, as in the gather passes; otherwise both sit in the LDS blob.
-// REV (MTP_LEAF_SWEEP): the factors are final once the stored levels are done and cb is a constant, so the reverse terms
-// issue in the same sweep from the factors already in registers (D must hold the seeds by then).  Every D slot still
-// receives its seed, then the leaf terms in the same row and lane order, then the level terms: bitwise the same.
-#ifndef MTP_LD
-#define MTP_LD 1   // (2: equal, 4: 2 % slower at level 20)
-#endif
-#ifndef MTP_LEAF_SWEEP
-#define MTP_LEAF_SWEEP 1   // 0: a second pass over the leaf rows for the reverse terms (leaf_backward), for A/B runs
-#endif
-#ifndef MTP_E_HOIST
-#define MTP_E_HOIST 1   // 0: the energy table of the stored scalars is read after the product passes, for A/B runs
-#endif
-template <int U, bool STORE, bool FAR, bool REV = false>
-__device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double *cf, int beg, int nit, double *M, int lane,
-                                               const double *cb = nullptr, double *D_ = nullptr)
+// requested AHEAD batches ahead of their use, as in the gather passes (one; two: equal, four: 2 % slower at level 20);
+// otherwise both sit in the LDS blob.  (The ring is written for any AHEAD, and stays so: with the one-trip loops over
+// it folded by hand the optimiser takes another path through the generic kernels and every one of them changes by a
+// few instructions.)
+template <int U, bool STORE, bool FAR>
+__device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double *cf, const double *cb, int beg, int nit,
+                                               double *M, double *D, int lane)
 {
-  constexpr int D = FAR ? MTP_LD : 1;
-  constexpr int NC = REV ? 2 : 1;   // constants per row: cf (and cb)
+  constexpr int AHEAD = 1;   // batches in flight (FAR)
+  constexpr int NC = 2;      // constants per row: cf, cb
   double e = 0.0;
   const MtpRow8 *rp = rows + beg + lane;
-  const double *cp = cf + lane, *bp = REV ? cb + lane : cp;
+  const double *cp = cf + lane, *bp = cb + lane;
   const int nb = (nit + U - 1) / U;
-  MtpRow8 q[D][U];
-  double qc[D][NC][U];
+  MtpRow8 q[AHEAD][U];
+  double qc[AHEAD][NC][U];
   auto fetch = [&](int b, MtpRow8 (&r)[U], double (&c)[NC][U]) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int o = 64 * min(b * U + u, nit - 1);   // uniform clamp: the tail re-reads the last block
       r[u] = rp[o];
       c[0][u] = cp[o];
-      if constexpr (REV) c[NC - 1][u] = bp[o];
+      c[1][u] = bp[o];
     }
   };
   if (FAR) {
 #pragma unroll
-    for (int d = 0; d < D; d++)
+    for (int d = 0; d < AHEAD; d++)
       if (d < nb) fetch(d, q[d], qc[d]);   // uniform
   }
-  for (int b0 = 0; b0 < nb; b0 += D) {
+  for (int b0 = 0; b0 < nb; b0 += AHEAD) {
 #pragma unroll
-    for (int d = 0; d < D; d++) {
+    for (int d = 0; d < AHEAD; d++) {
       const int b = b0 + d;
       if (b < nb) {   // uniform
         MtpRow8 rw[U];
@@ -817,7 +803,7 @@ __device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double
 #pragma unroll
             for (int k = 0; k < NC; k++) c[k][u] = qc[d][k][u];
           }
-          if (b + D < nb) fetch(b + D, q[d], qc[d]);   // uniform
+          if (b + AHEAD < nb) fetch(b + AHEAD, q[d], qc[d]);   // uniform
         } else {
           fetch(b, rw, c);
         }
@@ -832,73 +818,14 @@ __device__ __forceinline__ double leaf_forward(const MtpRow8 *rows, const double
             const double v = m0[u] * m1[u];
             e = fma(c[0][u], v, e);
             if (STORE) lds_add(&at8(M, rw[u].hi & 0xffffu), (double) ((int) rw[u].hi >> 16) * v);
-            if constexpr (REV) {
-              lds_add(&at8(D_, rw[u].lo >> 16), c[NC - 1][u] * m0[u]);
-              lds_add(&at8(D_, rw[u].lo & 0xffffu), c[NC - 1][u] * m1[u]);
-            }
-          }
-      }
-    }
-  }
-  if (STORE || REV) wave_fence();
-  return e;
-}
-
-template <int U, bool FAR>
-__device__ __forceinline__ void leaf_backward(const MtpRow8 *rows, const double *cb, int beg, int nit, const double *M,
-                                              double *D_, int lane)
-{
-  constexpr int D = FAR ? MTP_LD : 1;
-  const MtpRow8 *rp = rows + beg + lane;
-  const double *cp = cb + lane;
-  const int nb = (nit + U - 1) / U;
-  MtpRow8 q[D][U];
-  double qc[D][U];
-  auto fetch = [&](int b, MtpRow8 (&r)[U], double (&c)[U]) {
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int o = 64 * min(b * U + u, nit - 1);
-      r[u] = rp[o];
-      c[u] = cp[o];
-    }
-  };
-  if (FAR) {
-#pragma unroll
-    for (int d = 0; d < D; d++)
-      if (d < nb) fetch(d, q[d], qc[d]);
-  }
-  for (int b0 = 0; b0 < nb; b0 += D) {
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-      const int b = b0 + d;
-      if (b < nb) {
-        MtpRow8 rw[U];
-        double c[U], m0[U], m1[U];
-        if (FAR) {
-#pragma unroll
-          for (int u = 0; u < U; u++) {
-            rw[u] = q[d][u];
-            c[u] = qc[d][u];
-          }
-          if (b + D < nb) fetch(b + D, q[d], qc[d]);
-        } else {
-          fetch(b, rw, c);
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-          m0[u] = at8(M, rw[u].lo & 0xffffu);
-          m1[u] = at8(M, rw[u].lo >> 16);
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++)
-          if (b * U + u < nit) {
-            lds_add(&at8(D_, rw[u].lo >> 16), c[u] * m0[u]);
-            lds_add(&at8(D_, rw[u].lo & 0xffffu), c[u] * m1[u]);
+            lds_add(&at8(D, rw[u].lo >> 16), c[1][u] * m0[u]);
+            lds_add(&at8(D, rw[u].lo & 0xffffu), c[1][u] * m1[u]);
           }
       }
     }
   }
   wave_fence();
+  return e;
 }
 
 // Phase 4, gather form (round 2).  A level of a pass is a list of chunks; lane l of a group of 64 lanes runs one chunk:
@@ -973,44 +900,22 @@ __device__ __forceinline__ void gather_pass(const MtpRow8 *prog, const int *seg,
 }
 
 // ---- phase 5 helpers ------------------------------------------------------------------------
-// sum_{i<C} coef[i] * m[i]; the coefficient address is the same in all lanes of a half (LDS broadcast)
-#ifndef MTP_POLY_ACC
-#define MTP_POLY_ACC 1   // independent accumulation chains of a derivative polynomial (1 | 2 | 4 measured at 65,536 atoms: 0.4367 | 0.4388 | 0.4406 ms; no difference at 2,048)
-#endif
+// sum_{i<C} coef[i] * m[i] in one accumulation chain from 0.0; the coefficient address is the same in all lanes of a
+// half (LDS broadcast: a ds_read_b64 per coefficient; two and four chains were measured 0.5 % and 0.9 % slower)
 template <int C> __device__ __forceinline__ double poly_eval(unsigned coef, const double *m)
 {
-  constexpr int NA = MTP_POLY_ACC;
-  double a[NA];
+  double a = 0.0;
 #pragma unroll
-  for (int k = 0; k < NA; k++) a[k] = 0.0;
-#ifndef MTP_POLY_CH
-#define MTP_POLY_CH 8
-#endif
-  constexpr int CH = MTP_POLY_CH;   // reads per burst
-#pragma unroll
-  for (int i0 = 0; i0 < C; i0 += CH) {
-    double c[CH];
-#pragma unroll
-    for (int u = 0; u < CH; u++)
-      if (i0 + u < C) c[u] = lds_ld(coef, i0 + u);
-#pragma unroll
-    for (int u = 0; u < CH; u++)
-      if (i0 + u < C) a[(i0 + u) % NA] = fma(c[u], m[i0 + u], a[(i0 + u) % NA]);
-  }
-  double r = a[0];
-#pragma unroll
-  for (int k = 1; k < NA; k++) r += a[k];
-  return r;
+  for (int i = 0; i < C; i++) a = fma(lds_ld(coef, i), m[i], a);
+  return a;
 }
 
 // The same sum with the coefficients broadcast by DPP instead of by LDS: the lanes of a row of 16 belong to one half
 // (rows 0-1: half 0, rows 2-3: half 1), so coef_l = the block of this lane's half + 8 (lane & 15) bytes reads 16
 // coefficients per ds_read_b64 (one LDS cycle per half-wavefront, 32 consecutive banks: conflict-free), and
 // v_fmac_f64_dpp row_newbcast:i hands coefficient i to its row.  Same FMAs in the same order as poly_eval (bitwise the
-// same G); lanes whose coefficient lies past the block read whatever follows it in the image and are never broadcast.
-#ifndef MTP_COEF_DPP
-#define MTP_COEF_DPP 1   // 0: every coefficient is a broadcast ds_read_b64 (poly_eval), for A/B runs
-#endif
+// same G; profiles/r04_ab_coef_dpp.txt has the timing of the two); lanes whose coefficient lies past the block read
+// whatever follows it in the image and are never broadcast.
 template <int C, int K0> __device__ __forceinline__ void dpp_chunks(double &a, const double *c, const double *m)
 {
   if constexpr (K0 < C) {
@@ -1030,7 +935,7 @@ template <int C> __device__ __forceinline__ double poly_eval_dpp(unsigned coef_l
 }
 // DPP for C >= 2 only: a single coefficient is one read either way, and the DPP form adds the zeroing of the sum.
 // coef: the block's address, + 8 (lane & 15) bytes where coef_dpp<C>.
-template <int C> constexpr bool coef_dpp = MTP_COEF_DPP && C >= 2;
+template <int C> constexpr bool coef_dpp = C >= 2;
 template <int C> __device__ __forceinline__ double poly_sum(unsigned coef, const double *m)
 {
   if constexpr (coef_dpp<C>) return poly_eval_dpp<C>(coef, m);
@@ -1051,10 +956,8 @@ template <int C> __device__ __forceinline__ double poly_sum(unsigned coef, const
 // dependent LDS round trips (mu, then f'_mu) instead of one.  The 3-per-SIMD build has Mu <= 4 and ranks <= 6, hence at
 // most 28 slots (the planner checks 32, mtp_context.hip): there the whole table is two bits per slot in one SGPR pair,
 // formed once per wavefront, and a lookup is a shift and a mask (scalar for a uniform slot, v_lshrrev_b64 per lane).
-// The 2-per-SIMD builds keep the reads (PACKED = false): two more SGPRs across the atom loop cost them spills.
-#ifndef MTP_MU_BITS
-#define MTP_MU_BITS 1   // 0: mu is read from smu[] at the point of use in every build, for A/B runs
-#endif
+// The 2-per-SIMD builds keep the reads (PACKED = false): two more SGPRs across the atom loop cost them spills
+// (profiles/r06_ab_param_loads.txt).
 template <bool PACKED> struct SlotMu {
   const int *smu;
   unsigned long long bits;   // PACKED: mu(s) = bits >> 2 s & 3

@@ -19,7 +19,7 @@
   // compiled out of it; the 2-per-SIMD build takes either (uniform flag).
   constexpr bool NODG_CT = WPS == 3;
   // f' of the force phase from registers: the dg-free build of a shape that fixes the slot -> mu map (mtp_wave_body.hpp)
-  constexpr bool FP_REGS = NODG_CT && MTP_MU_BITS && fp_regs_ct<SH>;
+  constexpr bool FP_REGS = NODG_CT && fp_regs_ct<SH>;
   constexpr bool PHASE_PRIO = phase_prio_ct<SH>;   // s_setprio by phase (mtp_wave_body.hpp)
   constexpr int NG = 64 / KL;            // neighbour groups in the wavefront
   constexpr int NPG = NT / NG;           // neighbours per group per tile
@@ -100,7 +100,7 @@
   MtpRow8 krow1[kept_l1_count<SH>()];
   if constexpr (KEEP_L1) load_kept_l1_rows<SH>(bt.rows, krow1, lane);
   // (not in the KL = 16 grade build: there the SGPR pair costs a twelfth spilled VGPR dword)
-  constexpr bool MU_PACKED = MTP_MU_BITS && WPS == 3 && !(GRADE && KL == 16);
+  constexpr bool MU_PACKED = WPS == 3 && !(GRADE && KL == 16);
   SlotMu<MU_PACKED> smu{bt.smu, 0ull};
   if constexpr (MU_PACKED && slot_mu_ct<SH>) {   // the shape's constant
     smu.bits = slot_mu_bits<SH>();
@@ -471,11 +471,8 @@
     }
     for (int m = SHF(B) + lane; m < SHF(Am); m += 64) w.M[m] = 0.0;
     for (int m = lane; m < SHF(Ad); m += 64) w.D[m] = 0.0;
-#if MTP_LEAF_SWEEP
     // adjoint seeds (atom-invariant) behind the zeros, in the same program order: the leaf sweep adds onto them
     store_seeds();
-#endif
-#if MTP_E_HOIST
     // the first 64 energy-table entries, requested ahead of the product passes: the energy then costs one LDS round trip
     int emap0 = 0;
     double elin0 = 0.0;
@@ -488,7 +485,6 @@
         elin0 = kp->g_lin[lane];
       }
     }
-#endif
     if constexpr (SUM_T) {
       if (bval[0]) {
         // the lane's three int16 basic indices, products 3 q + 0..2 (-1: no such basic), from the registers
@@ -538,8 +534,8 @@
     // (bounds from the blob's level table or the shape's constants: level_row, mtp_wave_body.hpp)
     const int leaf_beg = level_row<SH>(bt.level, SHF(nlevels));
     const int leaf_nit = (level_row<SH>(bt.level, SHF(nlevels) + 1) - leaf_beg) >> 6;
-    if (rows_lds) e = leaf_forward<MTP_PU, GRADE, false, MTP_LEAF_SWEEP>(bt.rows, bt.leaf_cf, leaf_beg, leaf_nit, w.M, lane, bt.leaf_cb, w.D);
-    else e = leaf_forward<MTP_PU, GRADE, true, MTP_LEAF_SWEEP>(kp->rows, kp->leaf_cf, leaf_beg, leaf_nit, w.M, lane, kp->leaf_cb, w.D);
+    if (rows_lds) e = leaf_forward<MTP_PU, GRADE, false>(bt.rows, bt.leaf_cf, bt.leaf_cb, leaf_beg, leaf_nit, w.M, w.D, lane);
+    else e = leaf_forward<MTP_PU, GRADE, true>(kp->rows, kp->leaf_cf, kp->leaf_cb, leaf_beg, leaf_nit, w.M, w.D, lane);
     STAMP(4);   // products forward
     // ---- candidate vector, species and linear blocks (pair_mtp_extrapolation.cpp:235-252) ----
     if (GRADE) {
@@ -547,16 +543,11 @@
       for (int k = lane; k < SHF(Sp); k += 64) crow[k] = k == itype ? 1.0 : 0.0;
       for (int k = lane; k < SHF(S); k += 64) crow[SHF(Sp) + k] = w.M[kp->g_map_all[k]];
     }
-#if MTP_E_HOIST
     if (lane < SHF(Se)) e += elin0 * w.M[emap0];
-    const int k_e = lane + 64;
-#else
-    const int k_e = lane;
-#endif
     if (SHF(scalars_in_lds))
-      for (int k = k_e; k < SHF(Se); k += 64) e += bt.lin[k] * w.M[bt.map[k]];
+      for (int k = lane + 64; k < SHF(Se); k += 64) e += bt.lin[k] * w.M[bt.map[k]];
     else
-      for (int k = k_e; k < SHF(Se); k += 64) e += kp->g_lin[k] * w.M[kp->g_map[k]];
+      for (int k = lane + 64; k < SHF(Se); k += 64) e += kp->g_lin[k] * w.M[kp->g_map[k]];
     if (e_per_atom) {
       e = wave_sum(e) + kp->species_coeffs[itype];
       if (lane == 9) {   // (lane 9 carries the energy tally; nothing of e stays live into the force phase)
@@ -567,15 +558,7 @@
       eacc += e + (lane == 0 ? kp->species_coeffs[itype] : 0.0);
     }
     // ---- 4b. adjoints (pair_mtp.cpp:217-233) ----------------------------------------------
-#if !MTP_LEAF_SWEEP
-    store_seeds();
-    wave_fence();
-    STAMP(5);   // energy + seeds
-    if (rows_lds) leaf_backward<MTP_PU, false>(bt.rows, bt.leaf_cb, leaf_beg, leaf_nit, w.M, w.D, lane);
-    else leaf_backward<MTP_PU, true>(kp->rows, kp->leaf_cb, leaf_beg, leaf_nit, w.M, w.D, lane);
-#else
     STAMP(5);   // energy
-#endif
     if constexpr (GATHER) {
       gather_pass(kp->prog_bwd, bt.seg_bwd, SHF(nlevels), w.D, w.M, w.D, lane);
     } else {
@@ -644,7 +627,6 @@
         {   // rank 0: P_s = D_k, no gradient; dg_s = f'_mu (nodg: its row fp_row + mu; else the slot's dg row)
           const unsigned cg0 = pcol + 8u * (unsigned) (nodg ? SHF(fp_row) * PITCH : SHF(dg_off));
           const int n0 = SHA(deg_first, 1);
-#if MTP_COEF_DPP
           // four slots per per-lane read: lane i of each row holds D_{s4 + i} (poly_eval_dpp)
           for (int s4 = 0; s4 < n0; s4 += 4) {
             const double c = lds_ld(pcoef_l + 8u * (unsigned) (SHA(deg_coef, 0) + s4), 0);
@@ -667,18 +649,6 @@
             term(std::integral_constant<int, 2>());
             term(std::integral_constant<int, 3>());
           }
-#else
-          for (int sidx = 0; sidx < n0; sidx++) {
-            const double dk = w.coef[SHA(deg_coef, 0) + sidx];
-            const int mu = nodg ? smu.template uniform<true, GRADE>(sidx) : smu.template uniform<false, GRADE>(sidx);
-            if constexpr (FP_REGS) S0 = fma(fp_pick(Fp, slot_mu_of<SH>(sidx)), dk, S0);
-            else S0 = fma(lds_ld(cg0 + 8u * (unsigned) ((nodg ? mu : sidx) * PITCH), 0), dk, S0);
-            if (GRADE) {
-#pragma unroll
-              for (int v = 0; v < 4; v++) Wm[v] += (mu == v && part == 0) ? dk : 0.0;
-            }
-          }
-#endif
         }
         double mono[DEG * (DEG + 1) / 2];
         mono[0] = 1.0;

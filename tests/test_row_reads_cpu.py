@@ -92,6 +92,53 @@ def test_switch_is_named_by_the_build_flags():
     assert '"MTP_ROW_KEEP_L1=" MTP_STR(MTP_ROW_KEEP_L1)' in flags
 
 
+KERNEL_UNITS = ("mtp_wave_body.hpp", "mtp_wave_kernel_body.hpp", "mtp_kernels.hip", "mtp_kernels_fixed.hip",
+                "mtp_kernel_common.hpp")
+# the twelve retired switches, without their MTP_ prefix (a search of the tree for a retired name then finds nothing)
+RETIRED = ["MTP_" + s for s in ("LD", "POLY_ACC", "POLY_CH", "COEF_DPP", "LEAF_SWEEP", "E_HOIST", "MU_BITS", "LEVEL_ARGS",
+                                "SLOT_ARGS", "FP_REGS", "BLOCK_REGS", "ROW_REGS")]
+
+
+def _switch_defaults(text):
+    """the MTP_ names given a default: every #define between an #ifndef MTP_... and its #endif"""
+    names, inside = [], False
+    for line in text.splitlines():
+        if re.match(r"#\s*ifndef\s+MTP_\w+", line):
+            inside = True
+        elif re.match(r"#\s*endif", line):
+            inside = False
+        elif inside:
+            names += re.findall(r"^#\s*define\s+(MTP_\w+)", line)
+    return names
+
+
+def test_every_switch_default_is_named_by_the_build_flags():
+    """A library built with any compile-time switch of the force or grade kernels off its default says so: every default
+    in the kernels' files has its entry in mtp_kernel_build_flags(), so that build_flags() == "" (tests/test_domain_cpu.py)
+    means the shipped values.  MTP_GRADE_WPE is set together with MTP_GRADE_TPB and reported under its entry."""
+    flags = open(os.path.join(CSRC, "mtp_kernels.hip")).read()
+    body = flags[flags.index("const char *mtp_kernel_build_flags()"):]
+    body = body[:body.index("\n}\n")]
+    found = []
+    for unit in KERNEL_UNITS:
+        found += _switch_defaults(open(os.path.join(CSRC, unit)).read())
+    assert {"MTP_PU", "MTP_FWD5", "MTP_SUM_T", "MTP_CNT_SGPR", "MTP_GRADE_TPB", "MTP_GRADE_WPE"} <= set(found), found
+    for name in found:
+        if name != "MTP_GRADE_WPE":
+            assert '"%s=" MTP_STR(%s)' % (name, name) in body, name
+    assert "MTP_GRADE_WPE" in body
+
+
+def test_retired_switches_are_gone_from_the_sources():
+    """the switches of decided comparisons left the sources with the arm that lost"""
+    pattern = re.compile(r"\b(%s)\b" % "|".join(RETIRED))
+    for name in sorted(os.listdir(CSRC)):
+        path = os.path.join(CSRC, name)
+        if os.path.isfile(path) and not name.endswith(".so"):
+            hits = pattern.findall(open(path, errors="replace").read())
+            assert not hits, (name, hits)
+
+
 @pytest.fixture(scope="module")
 def force_function(tmp_path_factory):
     """(resource notes, [(address, instruction text)]) of w16_force_3ps; every offload bundle of the library is read"""
