@@ -428,6 +428,7 @@ namespace {
 // head x tail blocks
 struct ScheduleOptions {
   bool leaves, renumber, debug_banks;   // MTP_NO_LEAF and MTP_NO_RENUMBER unset, MTP_DEBUG_BANKS set
+  bool search_v1;                       // MTP_BANK_SEARCH=v1: the greedy two-move search (search_banks)
   int bank_rounds = -1, bank_scale = -1, refine_programs = -1;   // MTP_BANK_ROUNDS, MTP_BANK_SCALE, MTP_REFINE_PROGRAMS
 };
 
@@ -437,6 +438,8 @@ ScheduleOptions read_options()
   o.leaves = !std::getenv("MTP_NO_LEAF");
   o.renumber = !std::getenv("MTP_NO_RENUMBER");
   o.debug_banks = std::getenv("MTP_DEBUG_BANKS") != nullptr;
+  const char *search = std::getenv("MTP_BANK_SEARCH");
+  o.search_v1 = search && std::strcmp(search, "v1") == 0;
   if (const char *e = std::getenv("MTP_BANK_ROUNDS")) o.bank_rounds = std::max(0, std::atoi(e));
   if (const char *e = std::getenv("MTP_BANK_SCALE")) o.bank_scale = std::max(1, std::atoi(e));
   if (const char *e = std::getenv("MTP_REFINE_PROGRAMS")) o.refine_programs = std::atoi(e) != 0;
@@ -881,10 +884,39 @@ struct BankModel {
   }
 };
 
+// The annealed search (search_banks, v2).  Shipped effort for row-per-lane potentials: 4 rounds x 16 times the proposals;
+// at level 16 that takes the model from 888 to about 210 extra cycles per atom in half the time v1 needed for 335
+// (profiles/bank_search_ab.txt).  Inverse temperatures by Anneal's scale: a round starts at ANNEAL_K0 plus up to
+// ANNEAL_K_STEP (the last round) and ends at ANNEAL_K1; hotter starts lose the greedy order for nothing.
+constexpr int BANK_ROUNDS_V2 = 4, BANK_SCALE_V2 = 16;
+constexpr int ANNEAL_K0 = 24, ANNEAL_K_STEP = 8, ANNEAL_K1 = 60;
+constexpr int ROW_TRIALS_V2 = 200;   // row proposals per row, round and unit of scale ...
+constexpr long long ROW_TRIALS_MIN = 200000;   // ... and at least so many a round: small tables cost next to nothing
+constexpr long long RENUMBER_TRIALS_MIN = 50000;   // (likewise for the renumbering proposals of a round)
+
+// Acceptance rule of the annealed search: a proposal that raises the model by d > 0 cycles passes with probability
+// 2^(-d k / 4); the inverse temperature k rises linearly from k0 to k1 over the proposals of a round.  Proposals that
+// keep the model pass.  Integer arithmetic and the caller's Lcg only, so the walk is the same on every host.
+struct Anneal {
+  int k0, k1, k = -1;
+  uint32_t thr[8] = {0};   // thr[d]: passes if the next 31-bit draw is below it
+  void at(long long t, long long trials)
+  {
+    const int kk = k0 + (int) ((long long) (k1 - k0) * t / std::max(trials, 1ll));
+    if (kk == k) return;
+    k = kk;
+    uint64_t qk = 1ull << 32, f = 1ull << 31;
+    for (int i = 0; i < k; i++) qk = (qk * 3611622603ull) >> 32;   // 2^(-1/4) in 32 fractional bits
+    for (int d = 1; d < 8; d++) thr[d] = (uint32_t) (f = (f * qk) >> 32);
+  }
+  bool pass(int d, Lcg &next) const { return d <= 0 || (d < 8 && next() < thr[d]); }
+};
+
 // Search round (a): renumber moments, rows fixed.  Numbers swap inside a class only (cls: basics, stored products,
-// leaves).
+// leaves).  Without `an` only proposals that lower the model pass; with it the round anneals and ends on the best
+// numbering it has seen.
 void renumber_round(mtp_potential &p, const BankModel &model, const std::vector<char> &leaf,
-                    const std::vector<int> cls_members[3], Lcg &next, int bank_scale)
+                    const std::vector<int> cls_members[3], Lcg &next, int bank_scale, Anneal *an = nullptr)
 {
   const int A = p.alpha_moment_count, B = p.alpha_index_basic_count;
   const std::vector<MtpRow> &rows = p.rows_by_level;
@@ -949,8 +981,12 @@ void renumber_round(mtp_potential &p, const BankModel &model, const std::vector<
       hist[(size_t) id * 32 + t] = (uint8_t) (hist[(size_t) id * 32 + t] + k - k2);
     }
   };
-  const long long trials = bank_scale * std::min<long long>(200ll * A, 300000ll);
+  long long trials = bank_scale * std::min<long long>(200ll * A, 300000ll);
+  if (an) trials = std::max(trials, RENUMBER_TRIALS_MIN);
+  long long cur = 0, best = 0;   // model relative to the start of the round
+  std::vector<int32_t> best_perm;
   for (long long t = 0; t < trials; t++) {
+    if (an) an->at(t, trials);
     // three proposals in four start from a moment some row uses (weighted by use: the often-used moments are the ones
     // that collide), the rest from any moment
     int m1 = (int) (next() % (uint32_t) A);
@@ -964,11 +1000,19 @@ void renumber_round(mtp_potential &p, const BankModel &model, const std::vector<
     const int m2 = cls[next() % (uint32_t) cls.size()];
     if (m1 == m2) continue;
     const int p1 = p.moment_perm[m1], p2 = p.moment_perm[m2];
-    if (move_delta(m1, p1, p2, m2) + move_delta(m2, p2, p1, m1) >= 0) continue;
+    const int delta = move_delta(m1, p1, p2, m2) + move_delta(m2, p2, p1, m1);
+    if (an ? !an->pass(delta, next) : delta >= 0) continue;
+    if (an && delta > 0 && cur == best && best_perm.empty()) best_perm = p.moment_perm;   // leaving the best numbering
     apply_move(m1, p1, p2, m2);
     apply_move(m2, p2, p1, m1);
     std::swap(p.moment_perm[m1], p.moment_perm[m2]);
+    cur += delta;
+    if (cur <= best) {   // (among equals the latest: the other round may find a way on from it)
+      best = cur;
+      best_perm.clear();
+    }
   }
+  if (!best_perm.empty()) p.moment_perm.swap(best_perm);
 }
 
 // Search round (b): swap rows inside a level (they commute), numbering fixed.
@@ -999,13 +1043,131 @@ void swap_rows_round(mtp_potential &p, const BankModel &model, Lcg &next, int ba
   }
 }
 
-// MTP_DEBUG_BANKS: the model before and after the search, the adds split by stream (a0, a1: reverse pass; a3:
-// forward) and into same-address / same-bank shares
-void report_banks(const mtp_potential &p, const BankModel &model, long long cost_before, int bank_rounds,
-                  int bank_scale)
+// Search round (b) of the annealed search: moves of rows, numbering fixed.  A row may exchange its two factors (the
+// product commutes, and the reverse pass adds d3 m0 to D[a1] and d3 m1 to D[a0] either way: the exchange only decides
+// which of the two add instructions, and which of the two reads, carries which moment), two rows of a level may swap
+// places, with or without an exchange in either, and three rows of a level may rotate over three add groups.  The
+// model is kept as bank histograms per access (the accesses of BankModel::group_cost), so a proposal costs a few
+// counter updates per row it touches.  Acceptance by `an`; the round ends on the best rows it has seen.
+struct RowAnnealer {
+  std::vector<MtpRow> &rows;
+  const std::vector<int32_t> &perm;
+  const int leaf_row0, A;
+  std::vector<uint8_t> hadd, hread, rcnt;   // [16-group][stream][16], [32-group][stream][32]: load per bank;
+                                            // [32-group][stream][moment]: rows that read the moment
+  std::vector<int> gcost;                   // add cycles of each 16-group: where the proposals start
+  RowAnnealer(mtp_potential &p, int leaf_row0_)
+      : rows(p.rows_by_level), perm(p.moment_perm), leaf_row0(leaf_row0_), A(p.alpha_moment_count)
+  {
+    hadd.assign(rows.size() / 16 * 3 * 16, 0);
+    hread.assign(rows.size() / 32 * 3 * 32, 0);
+    rcnt.assign(rows.size() / 32 * 3 * (size_t) A, 0);
+    gcost.assign(rows.size() / 16, 0);
+    for (int r = 0; r < (int) rows.size(); r++) (void) put(r, +1);
+  }
+  // row r enters (s = +1) or leaves (s = -1) the accesses of its groups; returns the change of the model
+  int put(int r, int s)
+  {
+    const MtpRow &row = rows[(size_t) r];
+    const int m3[3] = {row.a0, row.a1, row.a3};
+    int d = 0;
+    for (int st = 0; st < (r >= leaf_row0 ? 2 : 3); st++) {   // (leaf rows: no access to their target)
+      const int m = m3[st], num = perm[(size_t) m];
+      uint8_t &h = hadd[((size_t) (r / 16) * 3 + st) * 16 + num % 16];
+      const int da = kWAdd[st] * (pen(h + s) - pen(h));
+      h = (uint8_t) (h + s);
+      gcost[(size_t) (r / 16)] += da;
+      d += da;
+      uint8_t &c = rcnt[((size_t) (r / 32) * 3 + st) * A + m];   // reads of one address broadcast
+      if ((s > 0 ? c : c - 1) == 0) {
+        uint8_t &hr = hread[((size_t) (r / 32) * 3 + st) * 32 + num % 32];
+        d += kWRead[st] * (pen(hr + s) - pen(hr));
+        hr = (uint8_t) (hr + s);
+      }
+      c = (uint8_t) (c + s);
+    }
+    return d;
+  }
+  // rows at pos[0..n) take the contents now[0..n); returns the change of the model
+  int place(const int *pos, const MtpRow *now, int n)
+  {
+    int d = 0;
+    for (int i = 0; i < n; i++) d += put(pos[i], -1);
+    for (int i = 0; i < n; i++) rows[(size_t) pos[i]] = now[i];
+    for (int i = 0; i < n; i++) d += put(pos[i], +1);
+    return d;
+  }
+};
+
+void anneal_rows_round(mtp_potential &p, const BankModel &model, Lcg &next, long long trials, Anneal &an)
+{
+  RowAnnealer ra(p, model.leaf_row0);
+  std::vector<MtpRow> &rows = p.rows_by_level;
+  const int nlev2 = (int) p.level_offset.size() - 1;
+  auto exchanged = [](MtpRow r) {
+    std::swap(r.a0, r.a1);
+    return r;
+  };
+  long long cur = 0, best = 0;   // model relative to the start of the round
+  std::vector<MtpRow> best_rows;
+  for (long long t = 0; t < trials; t++) {
+    an.at(t, trials);
+    const int l = (int) (next() % (uint32_t) nlev2);
+    const int b = p.level_offset[l], n = p.level_offset[l + 1] - b;
+    if (n < 1) continue;
+    // the first row comes from a 16-row group that has a collision (four tries), its partners from anywhere in the level
+    int pos[3] = {b + (int) (next() % (uint32_t) n), 0, 0};
+    for (int tries = 0; tries < 4 && ra.gcost[(size_t) (pos[0] / 16)] == 0; tries++) pos[0] = b + (int) (next() % (uint32_t) n);
+    const uint32_t kind = next() % 8u;   // 0-1 exchange, 2-3 swap, 4-5 swap and exchange, 6-7 three-cycle
+    MtpRow was[3], now[3];
+    int np = 1;
+    if (kind < 2) {
+      if (rows[(size_t) pos[0]].a0 == rows[(size_t) pos[0]].a1) continue;   // a square: nothing changes
+    } else {
+      np = kind < 6 ? 2 : 3;
+      for (int i = 1; i < np; i++) pos[i] = b + (int) (next() % (uint32_t) n);
+      // rows of one add group (hence of one read group) trade places for nothing
+      if (pos[0] / 16 == pos[1] / 16 || (np == 3 && (pos[2] / 16 == pos[0] / 16 || pos[2] / 16 == pos[1] / 16))) continue;
+    }
+    for (int i = 0; i < np; i++) was[i] = rows[(size_t) pos[i]];
+    if (kind < 2) {
+      now[0] = exchanged(was[0]);
+    } else if (kind < 6) {
+      now[0] = was[1];
+      now[1] = was[0];
+      if (kind >= 4) {
+        const uint32_t which = 1u + next() % 3u;   // the row that arrives at pos[0], at pos[1], or both
+        if (which & 1u) now[0] = exchanged(now[0]);
+        if (which & 2u) now[1] = exchanged(now[1]);
+      }
+    } else {
+      now[0] = was[2];
+      now[1] = was[0];
+      now[2] = was[1];
+    }
+    const int delta = ra.place(pos, now, np);
+    if (!an.pass(delta, next)) {
+      (void) ra.place(pos, was, np);
+      continue;
+    }
+    if (delta > 0 && cur == best && best_rows.empty()) {   // leaving the best rows: keep them
+      best_rows = rows;
+      for (int i = 0; i < np; i++) best_rows[(size_t) pos[i]] = was[i];
+    }
+    cur += delta;
+    if (cur <= best) {
+      best = cur;
+      best_rows.clear();
+    }
+  }
+  if (!best_rows.empty()) rows.swap(best_rows);
+}
+
+// MTP_DEBUG_BANKS: one line of the model, the adds split by stream (a0, a1: reverse pass; a3: forward) and into
+// same-address / same-bank shares
+void report_split(const mtp_potential &p, const BankModel &model, const char *when)
 {
   const std::vector<MtpRow> &rows = p.rows_by_level;
-  const long long cr = model.total(32), ca = model.total(16);
   long long same_addr[3] = {0, 0, 0}, same_bank[3] = {0, 0, 0};
   for (size_t r0 = 0; r0 < rows.size(); r0 += 16)
     for (int st = 0; st < ((int) r0 >= model.leaf_row0 ? 2 : 3); st++) {
@@ -1023,16 +1185,57 @@ void report_banks(const mtp_potential &p, const BankModel &model, long long cost
         same_bank[st] += pen(h[b]) - (h[b] - nid[b]);
       }
     }
-  std::fprintf(stderr, "mtp: LDS bank model of the product passes: %lld -> %lld extra cycles per atom (reads %lld, adds %lld); "
-                       "%d head x tail blocks, %d rounds x %d\n", cost_before, cr + ca, cr, ca, p.fwd_block_count, bank_rounds, bank_scale);
-  std::fprintf(stderr, "mtp:   adds, same address / other address on the bank: D[a0] %lld / %lld, D[a1] %lld / %lld, M[a3] %lld / %lld\n",
-               same_addr[0], same_bank[0], same_addr[1], same_bank[1], same_addr[2], same_bank[2]);
+  std::fprintf(stderr, "mtp:   %s: reads %lld, adds %lld; adds, same address / other address on the bank: D[a0] %lld / %lld, D[a1] %lld / %lld, M[a3] %lld / %lld\n",
+               when, model.total(32), model.total(16), same_addr[0], same_bank[0], same_addr[1], same_bank[1], same_addr[2],
+               same_bank[2]);
 }
 
-// LDS numbering of the moments.  The row order is fixed by now: renumber the moments -- basics among [0, B), products
-// among [B, A), so the zero-fill and the k < B loops of the kernel keep working -- by pairwise swaps that lower the
-// modelled extra cycles (BankModel), alternating with swaps of rows inside a level.  Deterministic (fixed-seed LCG).
-// moment_perm[file index] = LDS index; relabel writes every device table in LDS numbering.
+// MTP_DEBUG_BANKS: the model before and after the search, and the same-address adds that no search can avoid.  A moment
+// used u times in a level of G add groups has to share a group u - G times; a factor may sit in either D stream (factor
+// exchange), so the two streams count as one of 2 G places.  Neutral padding rows count like any row.
+void report_banks(const mtp_potential &p, const BankModel &model, long long cost_before, int bank_rounds,
+                  int bank_scale, bool v1)
+{
+  const std::vector<MtpRow> &rows = p.rows_by_level;
+  const long long cr = model.total(32), ca = model.total(16);
+  std::fprintf(stderr, "mtp: LDS bank model of the product passes: %lld -> %lld extra cycles per atom (reads %lld, adds %lld); "
+                       "%d head x tail blocks, %d rounds x %d, search %s\n", cost_before, cr + ca, cr, ca, p.fwd_block_count,
+               bank_rounds, bank_scale, v1 ? "v1" : "v2");
+  report_split(p, model, "after");
+  long long forced_d = 0, forced_m = 0;
+  std::vector<int> uf((size_t) p.alpha_moment_count), ut((size_t) p.alpha_moment_count);
+  for (size_t l = 0; l + 1 < p.level_offset.size(); l++) {
+    const int b = p.level_offset[l], e = p.level_offset[l + 1], groups = (e - b) / 16;
+    std::fill(uf.begin(), uf.end(), 0);
+    std::fill(ut.begin(), ut.end(), 0);
+    for (int r = b; r < e; r++) {
+      uf[(size_t) rows[(size_t) r].a0]++;
+      uf[(size_t) rows[(size_t) r].a1]++;
+      if (r < model.leaf_row0) ut[(size_t) rows[(size_t) r].a3]++;
+    }
+    long long fd = 0, fm = 0;
+    for (int m = 0; m < p.alpha_moment_count; m++) {
+      fd += std::max(0, uf[(size_t) m] - 2 * groups);
+      fm += std::max(0, ut[(size_t) m] - groups);
+    }
+    std::fprintf(stderr, "mtp:   forced same-address adds, %s %d (%d add groups): D[a0] + D[a1] %lld, M[a3] %lld\n",
+                 b >= model.leaf_row0 ? "leaf block" : "level", (int) l + 1, groups, fd, fm);
+    forced_d += fd;
+    forced_m += fm;
+  }
+  std::fprintf(stderr, "mtp:   forced same-address adds in all: D[a0] + D[a1] %lld, M[a3] %lld\n", forced_d, forced_m);
+}
+
+// LDS numbering of the moments and order of the rows inside their levels, by a deterministic local search (fixed-seed
+// LCG) on the modelled extra cycles (BankModel).  The moments are renumbered -- basics among [0, B), products among
+// [B, A), so the zero-fill and the k < B loops of the kernel keep working -- by pairwise swaps, in rounds that alternate
+// with moves of rows inside a level.  moment_perm[file index] = LDS index; relabel writes every device table in LDS
+// numbering.
+//   v2 (the default for row-per-lane potentials): both rounds anneal (Anneal) and end on the best state they saw; the
+//       row round exchanges the factors of a row, swaps rows with or without an exchange and rotates three rows, on
+//       incremental bank histograms (RowAnnealer).
+//   v1 (MTP_BANK_SEARCH=v1, and the gather-form potentials): only proposals that lower the model pass, the row round
+//       swaps two rows and recounts their groups.
 void search_banks(mtp_potential &p, const std::vector<char> &leaf, const ScheduleOptions &opt)
 {
   std::vector<int> cls_members[3];   // 0 basics, 1 stored products, 2 leaves (file indices)
@@ -1040,21 +1243,34 @@ void search_banks(mtp_potential &p, const std::vector<char> &leaf, const Schedul
     cls_members[m < p.alpha_index_basic_count ? 0 : (leaf[m] ? 2 : 1)].push_back(m);
   const BankModel model{p, p.level_offset[(size_t) p.normal_levels]};
   const long long cost_before = model.total(32) + model.total(16);
+  if (opt.debug_banks) report_split(p, model, "before");
   // Search effort.  Potentials whose product passes run row per lane (the narrow lane grids: up to level 16) pay every
-  // modelled collision in ds_add_f64 cycles, the busiest pipe of their kernel: eight rounds of four times the proposals
-  // (about 10 s at level 16, once per potential load) take the model from 403 to 335 extra cycles per atom and the force
-  // call from 0.4322 to 0.4272 ms (same box, alternating runs).  The wide grids run the gather programs, which have
-  // their own refinement (refine_program): two rounds.  MTP_BANK_ROUNDS / MTP_BANK_SCALE override (tests use two
-  // rounds).  (row per lane <=> at most 32 head x tail blocks in the basic-moment pass, mtp_pick_fwd_shape)
+  // modelled collision in ds_add_f64 cycles, the busiest pipe of their kernel.  v1 ran eight rounds of four times the
+  // proposals for them (16 s at level 16 on the development host, once per potential load; model 888 -> 335 extra cycles
+  // per atom).  v2 runs BANK_ROUNDS_V2 x BANK_SCALE_V2 (see there).  The wide grids run the gather programs, which have
+  // their own refinement (refine_program): two rounds of v1, whose model the kernel does not follow for them.
+  // MTP_BANK_ROUNDS / MTP_BANK_SCALE override (tests use two rounds).  (row per lane <=> at most 32 head x tail blocks
+  // in the basic-moment pass, mtp_pick_fwd_shape)
   const bool row_per_lane = p.fwd_block_count <= 32;
-  const int bank_rounds = opt.bank_rounds >= 0 ? opt.bank_rounds : (row_per_lane ? 8 : 2);
-  const int bank_scale = opt.bank_scale >= 1 ? opt.bank_scale : (row_per_lane ? 4 : 1);
+  const bool v1 = opt.search_v1 || !row_per_lane;
+  const int bank_rounds = opt.bank_rounds >= 0 ? opt.bank_rounds : (!row_per_lane ? 2 : (v1 ? 8 : BANK_ROUNDS_V2));
+  const int bank_scale = opt.bank_scale >= 1 ? opt.bank_scale : (!row_per_lane ? 1 : (v1 ? 4 : BANK_SCALE_V2));
   Lcg next{0x9E3779B97F4A7C15ull};
   for (int round = 0; round < bank_rounds; round++) {
-    renumber_round(p, model, leaf, cls_members, next, bank_scale);
-    swap_rows_round(p, model, next, bank_scale);
+    if (v1) {
+      renumber_round(p, model, leaf, cls_members, next, bank_scale);
+      swap_rows_round(p, model, next, bank_scale);
+    } else {
+      // every round reheats, later rounds less: the first one leaves the greedy order of order_rows behind, the last
+      // ones only polish
+      Anneal an{ANNEAL_K0 + ANNEAL_K_STEP * round / std::max(bank_rounds - 1, 1), ANNEAL_K1};
+      renumber_round(p, model, leaf, cls_members, next, bank_scale, &an);
+      an.k = -1;
+      const long long row_trials = bank_scale * ROW_TRIALS_V2 * (long long) p.rows_by_level.size();
+      anneal_rows_round(p, model, next, std::max(row_trials, ROW_TRIALS_MIN), an);
+    }
   }
-  if (opt.debug_banks) report_banks(p, model, cost_before, bank_rounds, bank_scale);
+  if (opt.debug_banks) report_banks(p, model, cost_before, bank_rounds, bank_scale, v1);
 }
 
 // Everything the kernels index by moment, in LDS numbering (moment_perm): the rows, the adjoint seeds, the leaf and
