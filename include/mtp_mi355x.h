@@ -886,6 +886,85 @@ int mtp_hess_finish(void *stream, int ncfg, const int *d_sel_first, const int *d
                     int mass_weight, const long long *d_h_first, double *d_H, double *d_diag /* [ncfg][2] */,
                     const int *d_status);
 
+/* ---- batched elastic constants: the second derivatives of every configuration of a batch with respect to its cell ------
+ *
+ * What the force constants leave out: the Hessian of the cell degrees of freedom.  Stress-strain coefficients by central
+ * differences of the stress, and the force-strain coupling by central differences of the forces, over the twelve homogeneous
+ * strains x -> x (I +- h E_w), h far inside the skin over the list cutoff: ONE ghost build and ONE list serve the thirteen
+ * force calls of a pass, and nothing is read back between them.  Layout, slot coordinates and the force call with per-atom
+ * virials are those of the batched variable-cell relaxation: the cell h0 has the lattice vectors as rows, W = -dE/d(eps) for
+ * x -> x (I + eps) is what mtp_batch_reduce leaves per configuration, components xx yy zz xy xz yz everywhere.
+ *
+ * Definitions, per configuration j of n_j atoms, N = 3 n_j:
+ *   strain k = 0 ... 11: component w = k / 2, amplitude s = +h (k even) or -h (k odd), D = I + s E_w; E_w has a 1 on the
+ *     diagonal for w < 3 and 0.5 on BOTH off-diagonal entries otherwise (engineering shear).  The atoms move at fixed scaled
+ *     coordinates, x[r][b] = origin[b] + ((xt[r][0] D[0][b] + xt[r][1] D[1][b]) + xt[r][2] D[2][b]), and the ghosts follow
+ *     through mtp_ghosts_deform with T = D.
+ *   stress: sigma_v = -(W_v / V), V = det(h0) * det(D) (both by cofactors along the first row), the Cauchy stress [eV/A^3]
+ *   Bt [6][6]:       Bt[w][v] = (sigma_v(+h E_w) - sigma_v(-h E_w)) * inv2h, inv2h = 1 / (2 h) computed once on the host
+ *   coupling [6][N]: Lambda[w][3 i + d] = (f_id(+h E_w) - f_id(-h E_w)) * inv2h, at c_first[j] = 18 * cfg_first[j]
+ * A pass is thirteen launches of mtp_elastic_step around thirteen force calls:
+ *   x0 = x;  for k = 0 ... 12:  mtp_ghosts_forward -> force call with MTP_ENERGY_ATOM and MTP_VIRIAL_ATOM ->
+ *                                mtp_ghosts_reverse_finish -> mtp_batch_reduce (W) -> mtp_elastic_step(k) -> mtp_ghosts_deform(T)
+ *   mtp_elastic_finish [-> the pass of mtp_hess_step at D = I -> mtp_hess_finish -> mtp_elastic_relax]
+ * Launch k, for a configuration with status[j] == 0 (any other is skipped: nothing of it is written) and at least one row:
+ *   1. k == 0: f0 = f on its rows, fmax[j] = sqrt(the largest |f0|^2 of a row), energy[j] = the sum of its rows of eatom,
+ *      stress0[j][v] = -(W_v / V0), V0 = det(h0).  A component of f0 or of W that is not finite, or V0 that is not a positive
+ *      finite number, sets status[j] = MTP_ELASTIC_FAILED.
+ *   2. k >= 1 harvests strain k - 1 (w', its sign): after the +h call the six stresses and the N forces are parked in row w'
+ *      of Bt and of the coupling; after the -h call out = (parked - now) * inv2h -- this expression and no other.  If one of
+ *      the 6 + N numbers is not finite, nothing of the two rows is written and status[j] = MTP_ELASTIC_FAILED.
+ *   3. the geometry of strain k: k < 12: T[j] = D_k and x as above; k == 12: x = x0 from the saved copy, to the bit, and
+ *      T[j] = I.  A configuration that failed in 1. or 2. is returned to x0 and T[j] = I by the launch that failed it.
+ * Segments of up to 256 rows are served by a wavefront, longer ones by the workgroup (the split of mtp_relax_step); every
+ * floating-point sum has a fixed order and every expression is evaluated as written (no fused multiply-add): a
+ * configuration's result depends on its own rows only, whatever the batch around it.
+ * MTP_ERR_ARG, nothing launched: a NULL stream, ncfg < 0, k outside [0, 12], h not finite or <= 0, a missing array
+ * (ncfg > 0).  ncfg == 0 launches nothing.  The caller starts status, fmax and energy at 0. */
+#define MTP_ELASTIC_FAILED 1
+#define MTP_ELASTIC_UNSTABLE 2
+int mtp_elastic_step(void *stream, int ncfg, const int *d_cfg_first, int k, double h, double *d_x, const double *d_x0,
+                     const double *d_xt, const double *d_origins, const double *d_h0 /* [ncfg][9] */, const double *d_f,
+                     const double *d_eatom, const double *d_virial /* [ncfg][6] */, double *d_T /* [ncfg][9] */,
+                     double *d_Bt /* [ncfg][36] */, double *d_coupling, const long long *d_c_first, double *d_f0, double *d_fmax,
+                     double *d_energy, double *d_stress0 /* [ncfg][6] */, int *d_status);
+/* The end of a pass, one launch, one wavefront for every configuration with status[j] == 0 and at least one row:
+ *   1. K[v][w] = 0.5 * ((((d_ik s_jl + d_jk s_il) + d_il s_jk) + d_jl s_ik) - 2 d_kl s_ij) with v = (i, j), w = (k, l),
+ *      s = stress0 and d the Kronecker delta as 0.0 / 1.0: Wallace's relation between the stress-strain coefficients under a
+ *      residual stress and the second derivatives of the energy with respect to Lagrangian strain
+ *   2. B[v][w] = Bt[w][v]: stress component v, strain component w.  NOT symmetric under stress:
+ *      B - B^T = d s^T - s d^T + O(h^2), d = (1, 1, 1, 0, 0, 0)
+ *   3. M = B - K; diag[j][0] = asymmetry = max_{v < w} |M[v][w] - M[w][v]| (an O(h^2) truncation quantity);
+ *      C[v][w] = C[w][v] = 0.5 * (M[v][w] + M[w][v]): a pair is read once and both members are written by one lane
+ *   4. diag[j][1] = sum_rule = max_{w, d} |sum_i Lambda[w][3 i + d]|, the sum over the atoms i = 0 ... n_j - 1 in that order:
+ *      the translation-invariance residual of the force call, of rounding size
+ * MTP_ERR_ARG, nothing launched: a NULL stream, ncfg < 0, a missing array (ncfg > 0). */
+int mtp_elastic_finish(void *stream, int ncfg, const int *d_cfg_first, const long long *d_c_first, const double *d_coupling,
+                       const double *d_stress0, const double *d_Bt, double *d_B /* [ncfg][36] */, double *d_C /* [ncfg][36] */,
+                       double *d_diag /* [ncfg][2] */, const int *d_status);
+/* Relaxed ions, one launch per LDS tier, one workgroup for every configuration with status[j] == 0 and 0 < N <=
+ * MTP_ELASTIC_RELAX_MAX_N (a larger one is left as it is: the caller solves it on the host).  H_j [N][N] at H + h_first[j]
+ * is the symmetrised, NOT mass-weighted Hessian of a full selection in the order of the rows (mtp_hess_finish).
+ *   1. A = H + tau sum_d t_d t_d^T with the three normalised translations t_d: A[r][c] = H[r][c] + (tau / n) where
+ *      r % 3 == c % 3, tau = trace(H) / N.  Lambda^T is orthogonal to the t_d (the sum rule), so A^-1 Lambda^T is the
+ *      pseudo-inverse H^+ Lambda^T where H is positive semi-definite with the translations as its only null vectors.
+ *   2. A = L L^T in LDS, fp64, packed lower triangle, column by column; a pivot that is <= 0 or not finite sets status[j] =
+ *      MTP_ELASTIC_UNSTABLE, and U, B_rel and C_rel of the configuration become NaN (B and C stay)
+ *   3. U [6][N] at U + c_first[j]: A U[w] = Lambda'[w], the internal-strain displacements per unit strain, with
+ *      Lambda'[w][3 i + d] = Lambda[w][3 i + d] - (sum_i Lambda[w][3 i + d]) / n: what rounding left of a translation is taken out
+ *   4. R[v][w] = sum_c Lambda'[v][c] U[w][c] over c = 0 ... N - 1 in that order;
+ *      B_rel[v][w] = B[v][w] - R[v][w] / V0,  C_rel[v][w] = C[v][w] - (0.5 * (R[v][w] + R[w][v])) / V0,  V0 = vol[j]
+ * A configuration of one atom has the translations as its only degrees of freedom: U = 0, B_rel = B, C_rel = C.
+ * This is exact where the forces vanish; d sigma_v / d u_c = -Lambda[v][c] / V has a correction of size |f0| / V otherwise.
+ * The tiers: N <= 48, <= 96 and <= 192 take 12, 42 and 154 KiB of LDS a workgroup.
+ * MTP_ERR_ARG, nothing launched: a NULL stream, ncfg < 0, a missing array (ncfg > 0). */
+#define MTP_ELASTIC_TIER_SMALL 48
+#define MTP_ELASTIC_TIER_MIDDLE 96
+#define MTP_ELASTIC_RELAX_MAX_N 192
+int mtp_elastic_relax(void *stream, int ncfg, const int *d_cfg_first, const long long *d_h_first, const double *d_H,
+                      const long long *d_c_first, const double *d_coupling, const double *d_vol, const double *d_B,
+                      const double *d_C, double *d_U, double *d_B_rel, double *d_C_rel, int *d_status);
+
 
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------
  *

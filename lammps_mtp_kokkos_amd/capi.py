@@ -49,6 +49,7 @@ EXPORTS = [
     "mtp_sample_to_cell", "mtp_relax_step",
     "mtp_relax_cell_step", "mtp_relax_cell_rebase", "mtp_relax_cell_capture_cells", "mtp_ghosts_deform",
     "mtp_sample_cell_step", "mtp_neb_step", "mtp_hess_step", "mtp_hess_finish",
+    "mtp_elastic_step", "mtp_elastic_finish", "mtp_elastic_relax",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -116,7 +117,7 @@ def kernel_source_hash():
     src = os.path.join(_HERE, "csrc")
     other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
                       "mtp_relax_cell.hip", "mtp_batch_step.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip",
-                      "mtp_hess.hip")
+                      "mtp_hess.hip", "mtp_elastic.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1285,6 +1286,48 @@ def hess_finish(sel_first_t, sel_t, type_t, mass_t, mass_weight, h_first_t, H_t,
                                int(bool(mass_weight)), _ptr(h_first_t), _ptr(H_t), _ptr(diag_t), _ptr(status_t))
     if rc:
         raise MtpError(rc, "mtp_hess_finish")
+
+
+# ---- batched elastic constants (include/mtp_mi355x.h)
+
+ELASTIC_STATUS = ("ok", "failed", "unstable")                               # status_t[j] = 0, 1, 2
+ELASTIC_TIERS = (48, 96, 192)                                               # the LDS tiers of mtp_elastic_relax: N = 3 n up to ...
+ELASTIC_RELAX_MAX_N = ELASTIC_TIERS[-1]
+
+
+def elastic_step(cfg_first_t, k, h, x_t, x0_t, xt_t, origins_t, h0_t, f_t, eatom_t, virial_t, T_t, Bt_t, coupling_t, c_first_t,
+                 f0_t, fmax_t, energy_t, stress0_t, status_t, stream=None):
+    """launch k = 0 ... 12 of a pass of central differences over the strains x -> x (I +- h E_w): harvest strain k - 1 into row
+    (k - 1) / 2 of Bt_t [ncfg, 6, 6] and of coupling_t (the [6][3 n] blocks one after another, c_first_t [ncfg] int64 = 18
+    cfg_first), then lay x_t and T_t [ncfg, 9] out for strain k (k = 12: back to x0_t): mtp_elastic_step.  f0_t [n, 3], fmax_t,
+    energy_t [ncfg] and stress0_t [ncfg, 6] are written by launch 0; status_t [ncfg] int32."""
+    rc = lib().mtp_elastic_step(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), int(k), C.c_double(h), _ptr(x_t),
+                                _ptr(x0_t), _ptr(xt_t), _ptr(origins_t), _ptr(h0_t), _ptr(f_t), _ptr(eatom_t), _ptr(virial_t),
+                                _ptr(T_t), _ptr(Bt_t), _ptr(coupling_t), _ptr(c_first_t), _ptr(f0_t), _ptr(fmax_t), _ptr(energy_t),
+                                _ptr(stress0_t), _ptr(status_t))
+    if rc:
+        raise MtpError(rc, "mtp_elastic_step")
+
+
+def elastic_finish(cfg_first_t, c_first_t, coupling_t, stress0_t, Bt_t, B_t, C_t, diag_t, status_t, stream=None):
+    """the end of a pass: B_t [ncfg, 6, 6] = Bt^T, C_t = sym(B - K(stress0)), diag_t [ncfg, 2] = (asymmetry, sum_rule):
+    mtp_elastic_finish"""
+    rc = lib().mtp_elastic_finish(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), _ptr(c_first_t), _ptr(coupling_t),
+                                  _ptr(stress0_t), _ptr(Bt_t), _ptr(B_t), _ptr(C_t), _ptr(diag_t), _ptr(status_t))
+    if rc:
+        raise MtpError(rc, "mtp_elastic_finish")
+
+
+def elastic_relax(cfg_first_t, h_first_t, H_t, c_first_t, coupling_t, vol_t, B_t, C_t, U_t, B_rel_t, C_rel_t, status_t, stream=None):
+    """relaxed ions for the configurations of up to ELASTIC_RELAX_MAX_N coordinates: U_t (laid out like coupling_t) =
+    (H + tau sum t t^T)^-1 Lambda^T by Cholesky in LDS, B_rel_t = B - R / V, C_rel_t = C - sym(R) / V with R = Lambda U^T;
+    status_t[j] = 2 ("unstable") where a pivot is not positive: mtp_elastic_relax.  H_t: the symmetrised full Hessians of
+    hess_finish without mass weights."""
+    rc = lib().mtp_elastic_relax(_st(stream), int(cfg_first_t.numel()) - 1, _ptr(cfg_first_t), _ptr(h_first_t), _ptr(H_t),
+                                 _ptr(c_first_t), _ptr(coupling_t), _ptr(vol_t), _ptr(B_t), _ptr(C_t), _ptr(U_t), _ptr(B_rel_t),
+                                 _ptr(C_rel_t), _ptr(status_t))
+    if rc:
+        raise MtpError(rc, "mtp_elastic_relax")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

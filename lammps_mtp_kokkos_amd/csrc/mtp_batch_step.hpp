@@ -1,5 +1,5 @@
 // What every one-launch-a-step kernel over the batched layout shares (mtp_relax.hip, mtp_relax_cell.hip, mtp_sample.hip,
-// mtp_sample_cell.hip, mtp_neb.hip, mtp_hess.hip): the unit constants, the fixed-order reductions over a wavefront or a workgroup of
+// mtp_sample_cell.hip, mtp_neb.hip, mtp_hess.hip, mtp_elastic.hip): the unit constants, the fixed-order reductions over a wavefront or a workgroup of
 // MTP_BATCH_BLOCK threads, the split of a workgroup over the configurations that still run, the FIRE rule with the row sweeps
 // of its fixed-cell users, the 3 x 3 helpers of the kernels that move cells, and the host side of an entry point: the range
 // check of the FIRE parameters, the pointer check and the launch epilogue.  Each of these is defined here and nowhere else.

@@ -2330,3 +2330,242 @@ def vineyard_prefactor(freq_min, freq_saddle, zero_tol=1e-3):
         raise ValueError("vineyard_prefactor: %d stable modes at the minimum, %d at the saddle: the saddle must have one fewer"
                          % (len(stable_lo), len(stable_hi)))
     return float(np.exp(np.log(stable_lo).sum() - np.log(stable_hi).sum()))
+
+
+# ---- elastic constants: the second derivatives with respect to the cell -------------------------------------------------------
+
+VOIGT = (0, 1, 2, 5, 4, 3)    # Voigt's 11 22 33 23 13 12 in the project's order xx yy zz xy xz yz
+_PAIRS = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))
+_COMPONENT = {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (1, 0): 3, (0, 2): 4, (2, 0): 4, (1, 2): 5, (2, 1): 5}
+
+
+def to_voigt(M):
+    """Host only: a [6] vector or [6, 6] matrix in the project's component order xx yy zz xy xz yz, reordered to Voigt's
+    11 22 33 23 13 12 (a permutation; the engineering-shear convention is the same in both)"""
+    M = np.asarray(M, dtype=np.float64)
+    if M.shape == (6,):
+        return M[list(VOIGT)].copy()
+    if M.shape != (6, 6):
+        raise ValueError("to_voigt: a [6] vector or a [6, 6] matrix, got %r" % (M.shape,))
+    return M[np.ix_(VOIGT, VOIGT)].copy()
+
+
+def stress_correction(stress):
+    """Host only: K [6, 6] of Wallace's relation for the Cauchy stress `stress` [6] (xx yy zz xy xz yz),
+    K_ijkl = (d_ik s_jl + d_jk s_il + d_il s_jk + d_jl s_ik - 2 d_kl s_ij) / 2 with row (i, j) and column (k, l): the
+    stress-strain coefficients B of a stressed state and the second derivatives C of its energy with respect to Lagrangian strain,
+    per volume, differ by it, C = B - K.  K - K^T = d s^T - s d^T with d = (1, 1, 1, 0, 0, 0)."""
+    s = np.asarray(stress, dtype=np.float64)
+    if s.shape != (6,):
+        raise ValueError("stress_correction: the stress is [6] (xx yy zz xy xz yz), got %r" % (s.shape,))
+    sg = lambda a, b: s[_COMPONENT[(a, b)]]
+    dl = lambda a, b: 1.0 if a == b else 0.0
+    K = np.zeros((6, 6))
+    for v, (i, j) in enumerate(_PAIRS):
+        for w, (k, l) in enumerate(_PAIRS):
+            K[v, w] = 0.5 * ((((dl(i, k) * sg(j, l) + dl(j, k) * sg(i, l)) + dl(i, l) * sg(j, k)) + dl(j, l) * sg(i, k))
+                             - 2.0 * dl(k, l) * sg(i, j))
+    return K
+
+
+def moduli(C):
+    """Host only: the polycrystalline moduli of one matrix of elastic constants `C` [6, 6] (eV/A^3, engineering shears; the
+    project's order or Voigt's: every quantity here is the same for both).  Returns dict(bulk_voigt, bulk_reuss, bulk_hill,
+    shear_voigt, shear_reuss, shear_hill [eV/A^3]; compressibility = 1 / bulk_reuss [A^3/eV], what sample_cells_npt takes;
+    born_stable: the smallest eigenvalue of sym(C) is positive; min_eigenvalue).  A matrix that is not [6, 6], not finite or
+    singular raises."""
+    C = np.asarray(C, dtype=np.float64)
+    if C.shape != (6, 6):
+        raise ValueError("moduli: the elastic constants are [6, 6], got %r" % (C.shape,))
+    if not np.isfinite(C).all():
+        raise ValueError("moduli: the elastic constants are not finite (a failed configuration?)")
+    C = 0.5 * (C + C.T)
+    lam = np.linalg.eigvalsh(C)
+    if not np.abs(lam).min() > 0.0:
+        raise ValueError("moduli: the matrix of elastic constants is singular")
+    S = np.linalg.inv(C)
+    n3, s3 = slice(0, 3), slice(3, 6)
+    dia = lambda M: float(np.trace(M[n3, n3]))
+    off = lambda M: float(M[0, 1] + M[0, 2] + M[1, 2])
+    shr = lambda M: float(np.trace(M[s3, s3]))
+    kv, gv = (dia(C) + 2.0 * off(C)) / 9.0, (dia(C) - off(C) + 3.0 * shr(C)) / 15.0
+    kr, gr = 1.0 / (dia(S) + 2.0 * off(S)), 15.0 / (4.0 * dia(S) - 4.0 * off(S) + 3.0 * shr(S))
+    return dict(bulk_voigt=kv, bulk_reuss=kr, bulk_hill=0.5 * (kv + kr), shear_voigt=gv, shear_reuss=gr, shear_hill=0.5 * (gv + gr),
+                compressibility=1.0 / kr, born_stable=bool(lam[0] > 0.0), min_eigenvalue=float(lam[0]))
+
+
+def relax_ions(B, C, coupling, hessian, volume, internal_strain=None):
+    """Host only: the ionic term of the elastic constants, by the algorithm of mtp_elastic_relax in numpy (elastic_cells uses it
+    for the configurations above capi.ELASTIC_RELAX_MAX_N coordinates).  `B`, `C` [6, 6]: the clamped birch and elastic of
+    elastic_cells; `coupling` [6, 3 n] = Lambda; `hessian` [3 n, 3 n] of hessian_cells for ALL atoms, not mass-weighted (it is
+    symmetrised here); `volume` V0.  A = H + tau sum_d t_d t_d^T with the three normalised translations t_d and tau =
+    trace(H) / 3 n, factorised by Cholesky; U = A^-1 Lambda^T (Lambda^T, with the mean over the atoms taken out of every row, is
+    orthogonal to the translations, so this is H^+ Lambda^T at a minimum), R = Lambda U^T.  With `internal_strain` [6, 3 n] given, that U is used and nothing is solved.
+    Returns dict(internal_strain=U [6, 3 n], birch_relaxed = B - R / V0, elastic_relaxed = C - sym(R) / V0, status "ok" or
+    "unstable": A is not positive definite -- the configuration is no minimum -- and the three are NaN)."""
+    B, C = np.asarray(B, dtype=np.float64), np.asarray(C, dtype=np.float64)
+    Lam, H = np.asarray(coupling, dtype=np.float64), np.asarray(hessian, dtype=np.float64)
+    N = Lam.shape[1] if Lam.ndim == 2 else -1
+    if B.shape != (6, 6) or C.shape != (6, 6) or Lam.ndim != 2 or Lam.shape[0] != 6 or N % 3 or H.shape != (N, N):
+        raise ValueError("relax_ions: B and C are [6, 6], coupling [6, 3 n] and hessian [3 n, 3 n], got %r, %r, %r, %r"
+                         % (B.shape, C.shape, Lam.shape, H.shape))
+    V0 = float(volume)
+    if not (V0 > 0.0 and np.isfinite(V0)):
+        raise ValueError("relax_ions: the volume must be positive and finite, got %r" % (volume,))
+    status = capi.ELASTIC_STATUS[0]
+    if N:                                                     # what rounding left of a translation in Lambda is taken out
+        Lam = (Lam.reshape(6, N // 3, 3) - Lam.reshape(6, N // 3, 3).mean(1, keepdims=True)).reshape(6, N)
+    if internal_strain is not None:
+        U = np.asarray(internal_strain, dtype=np.float64)
+        if U.shape != Lam.shape:
+            raise ValueError("relax_ions: internal_strain is [6, 3 n] like the coupling, got %r" % (U.shape,))
+    elif N <= 3:                                              # one atom: only the translations, nothing relaxes
+        U = np.zeros((6, N))
+    else:
+        A = 0.5 * (H + H.T)
+        tau = float(np.trace(A)) / N
+        for d in range(3):
+            A[d::3, d::3] += tau / (N // 3)
+        try:
+            if not np.isfinite(A).all():
+                raise np.linalg.LinAlgError("not finite")
+            L = np.linalg.cholesky(A)
+            U = np.linalg.solve(L.T, np.linalg.solve(L, Lam.T)).T
+        except np.linalg.LinAlgError:
+            nan = np.full((6, 6), np.nan)
+            return dict(internal_strain=np.full((6, N), np.nan), birch_relaxed=nan, elastic_relaxed=nan.copy(),
+                        status=capi.ELASTIC_STATUS[2])
+    R = Lam @ U.T
+    return dict(internal_strain=U, birch_relaxed=B - R / V0, elastic_relaxed=C - 0.5 * (R + R.T) / V0, status=status)
+
+
+def elastic_cells(ctx, configs, h=0.005, relax_ions=False, h_atoms=0.01, list_cutoff=7.0, max_atoms_per_pass=None,
+                  max_hessian_bytes=2 ** 31, device=None):
+    """What hessian_cells leaves out: the second derivatives with respect to the CELL -- elastic constants -- for a whole batch of
+    independent periodic cells at once, device-resident.  `configs` and the passes are those of evaluate_cells.  A pass makes ONE
+    ghost build and ONE list and runs 13 force calls with per-atom virials on them, at zero strain and at x -> x (I +- h E_w) for
+    the six components w (order xx yy zz xy xz yz; a shear E_w has 1/2 on both off-diagonal entries: engineering shear), the
+    atoms at fixed scaled coordinates and the ghosts following through mtp_ghosts_deform; mtp_elastic_step harvests between the
+    calls and mtp_elastic_finish ends the pass (include/mtp_mi355x.h, "batched elastic constants").  Nothing is read back before
+    the end of the pass.  `h` must stay below half the skin over the list cutoff: a pair inside the cutoff after the strain was
+    inside the list before it.
+
+    Returns one dict per configuration (eV, A; to_voigt reorders to 11 22 33 23 13 12):
+      stress [6]       the Cauchy stress sigma = -W / V at zero strain [eV/A^3]
+      birch [6, 6]     B[v][w] = d sigma_v / d eps_w by central differences, as harvested.  NOT symmetric under residual stress:
+                       B - B^T = d sigma^T - sigma d^T + O(h^2), d = (1, 1, 1, 0, 0, 0)
+      elastic [6, 6]   C = sym(B - K(sigma)), K = stress_correction(stress) (Wallace): the second derivatives of the energy with
+                       respect to Lagrangian strain, per volume; moduli(C) gives bulk and shear moduli and the compressibility
+      asymmetry        max |(B - K) - (B - K)^T| before symmetrising, an O(h^2) truncation quantity
+      coupling [6, 3n] Lambda[w][3 i + d] = d f_id / d eps_w at fixed scaled coordinates;  sum_rule = max |sum_i Lambda[w][3 i + d]|,
+                       the translation-invariance residual, of rounding size
+      energy, f0 [n, 3], fmax, volume, status: "ok", "failed" (a force or virial that was not finite: the matrices are NaN; the
+      other configurations are not affected) or "unstable" (below)
+    All of these are for CLAMPED ions.  relax_ions=True goes on, in the same pass, with the force constants of all atoms
+    (hessian_cells' loop, displacement `h_atoms` [A], 6 n + 1 more force calls; the passes are then cut by cut_hessian_passes to
+    `max_hessian_bytes`) and mtp_elastic_relax, and adds
+      hessian [3n, 3n], internal_strain [6, 3n] = U = H^+ Lambda^T (the displacements per unit strain),
+      birch_relaxed = B - Lambda U^T / V, elastic_relaxed = C - sym(Lambda U^T) / V
+    "unstable": the Hessian has a negative mode, the relaxed matrices are NaN, the clamped ones stay.  The ionic term is exact
+    only where the forces vanish -- d sigma_v / d u_c = -Lambda[v][c] / V has a correction of size |f0| / V otherwise -- so relax
+    with relax_cells or relax_cells_vc first and look at the `fmax` returned here.  An empty configuration gives zeros of the
+    right shapes."""
+    who = "elastic_cells"
+    items, all_cells, natoms = _batch_items(configs)
+    h, h_atoms = float(h), float(h_atoms)
+    if not (h > 0.0 and np.isfinite(h)):
+        raise ValueError("elastic_cells: h must be positive and finite, got %r" % (h,))
+    if not (h_atoms > 0.0 and np.isfinite(h_atoms)):
+        raise ValueError("elastic_cells: h_atoms must be positive and finite, got %r" % (h_atoms,))
+    skin = float(list_cutoff) - float(ctx.pot.info.max_cutoff)
+    if not h < 0.5 * skin / float(list_cutoff):
+        raise ValueError("elastic_cells: h (%g) must stay below half the skin over the list cutoff (%g / %g / 2 = %g): the list has to "
+                         "hold for every strained copy" % (h, skin, float(list_cutoff), 0.5 * skin / float(list_cutoff)))
+    if not h_atoms < 0.5 * skin:
+        raise ValueError("elastic_cells: h_atoms (%g A) must stay below half the skin (list_cutoff - cutoff = %g A): the list has to "
+                         "hold for every displaced copy" % (h_atoms, skin))
+    ionic = bool(relax_ions)
+    if ionic:
+        _hessian_sizes(natoms, max_hessian_bytes)
+    select, brk, mass_of_type, _ = _run_arguments(who, items, 1.0, None, None, 0, 0, 0, 1, 0)
+    setup = _RunSetup(who, ctx, items, all_cells, natoms, mass_of_type, 0, 0, False, select, brk, 0, 0, list_cutoff, 1, 0,
+                      max_atoms_per_pass, device, ())
+    if ionic:
+        setup.plan = cut_hessian_passes(setup.plan, all_cells, natoms, setup.cut, max_hessian_bytes)
+    torch, dev, st, to, zeros = setup.torch, setup.dev, setup.st, setup.to, setup.zeros
+    solve_on_host = globals()["relax_ions"]
+
+    def empty(k):
+        z = lambda *s: np.zeros(s)
+        out = dict(stress=z(6), birch=z(6, 6), elastic=z(6, 6), coupling=z(6, 0), asymmetry=0.0, sum_rule=0.0, energy=0.0,
+                   f0=z(0, 3), fmax=0.0, volume=float(setup.volume[k]), status=capi.ELASTIC_STATUS[0])
+        if ionic:
+            out.update(hessian=z(0, 0), internal_strain=z(6, 0), birch_relaxed=z(6, 6), elastic_relaxed=z(6, 6))
+        return out
+
+    def one_pass(run):
+        k0, ncfg, n, A = run.k0, run.ncfg, run.n, run.A
+        cf = run.cf.astype(np.int64)
+        c_first_t = to(18 * cf[:-1])
+        x0 = run.x[:n].clone()
+        f0, state, diag = zeros(n, 3), zeros(2, ncfg), zeros(ncfg, 2)
+        stress0, Bt, B, Cm, coupling = zeros(ncfg, 6), zeros(ncfg, 36), zeros(ncfg, 36), zeros(ncfg, 36), zeros(max(18 * n, 1))
+        status = torch.zeros(ncfg, dtype=torch.int32, device=dev)
+        for k in range(13):
+            run.forces(False)
+            capi.elastic_step(run.cf_t, k, h, run.x, x0, A["xt"], run.org_t, A["h0"], run.f, run.eatom, run.virial, A["T"], Bt,
+                              coupling, c_first_t, f0, state[0], state[1], stress0, status, stream=st)
+            run.moved()
+        capi.elastic_finish(run.cf_t, c_first_t, coupling, stress0, Bt, B, Cm, diag, status, stream=st)
+        if ionic:
+            first = np.concatenate([[0], np.cumsum((3 * np.diff(cf)) ** 2)])
+            h_first_t, sel_t = to(first[:-1].astype(np.int64)), to(np.arange(n + 1, dtype=np.int32))
+            H, U, B_rel, C_rel = zeros(max(int(first[-1]), 1)), zeros(max(18 * n, 1)), zeros(ncfg, 36), zeros(ncfg, 36)
+            hdiag, hstate, hf0 = zeros(ncfg, 2), zeros(2, ncfg), zeros(n, 3)
+            sel_max = int(run.counts.max())
+            for k in range(6 * sel_max + 1):
+                run.forces(False)
+                capi.hess_step(run.cf_t, run.cf_t, sel_t, sel_max, k, h_atoms, run.x, x0, run.f, run.eatom, h_first_t, H, hf0, hstate[0],
+                               hstate[1], status, stream=st)
+            capi.hess_finish(run.cf_t, sel_t, run.buf.tall, setup.mass_t, False, h_first_t, H, hdiag, status, stream=st)
+            capi.elastic_relax(run.cf_t, h_first_t, H, c_first_t, coupling, to(setup.volume[k0: run.k1]), B, Cm, U, B_rel, C_rel,
+                               status, stream=st)
+
+        def final(xh, eh):
+            fh, sh, dh, th = f0.cpu().numpy(), state.cpu().numpy(), diag.cpu().numpy(), status.cpu().numpy()
+            s0, Bh, Ch, Lh = stress0.cpu().numpy(), B.cpu().numpy(), Cm.cpu().numpy(), coupling.cpu().numpy()
+            if ionic:
+                Hh, Uh, Brh, Crh = H.cpu().numpy(), U.cpu().numpy(), B_rel.cpu().numpy(), C_rel.cpu().numpy()
+            out = []
+            for j, (a, b) in enumerate(run.rows):
+                if b == a:
+                    out.append(empty(k0 + j))
+                    continue
+                N, code = 3 * (b - a), int(th[j])
+                r = dict(stress=s0[j].copy(), birch=Bh[j].reshape(6, 6).copy(), elastic=Ch[j].reshape(6, 6).copy(),
+                         coupling=Lh[18 * a: 18 * b].reshape(6, N).copy(), asymmetry=float(dh[j, 0]), sum_rule=float(dh[j, 1]),
+                         energy=float(sh[1, j]), f0=fh[a:b], fmax=float(sh[0, j]), volume=float(setup.volume[k0 + j]))
+                if code == 1:
+                    for key in ("birch", "elastic", "coupling"):
+                        r[key][:] = np.nan
+                if ionic:
+                    r["hessian"] = Hh[int(first[j]): int(first[j]) + N * N].reshape(N, N).copy()
+                    if code == 1:
+                        r["hessian"][:] = np.nan
+                        r.update(internal_strain=np.full((6, N), np.nan), birch_relaxed=np.full((6, 6), np.nan),
+                                 elastic_relaxed=np.full((6, 6), np.nan))
+                    elif N > capi.ELASTIC_RELAX_MAX_N:                # above the largest LDS tier: the same algorithm on the host
+                        more = solve_on_host(r["birch"], r["elastic"], r["coupling"], r["hessian"], r["volume"])
+                        code = capi.ELASTIC_STATUS.index(more.pop("status"))
+                        r.update(more)
+                    else:
+                        r.update(internal_strain=Uh[18 * a: 18 * b].reshape(6, N).copy(), birch_relaxed=Brh[j].reshape(6, 6).copy(),
+                                 elastic_relaxed=Crh[j].reshape(6, 6).copy())
+                r["status"] = capi.ELASTIC_STATUS[code]
+                out.append(r)
+            return out
+
+        return 0, final
+
+    setup.each_pass(one_pass, empty, _DeformingCellRun)
+    return setup.final
