@@ -25,6 +25,8 @@ re-neighbouring (they size arrays) and nothing else.
 """
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 
 from . import capi
@@ -1075,30 +1077,34 @@ def maxwell_boltzmann(items, mass_of_type, temperature, seed, keys):
     return out
 
 
-class _RunSetup:
-    """What sample_cells, relax_cells and relax_cells_vc (`who`) share around their passes.  The prologue: the grade steps (and
-    the refusal of thresholds without selection state) before anything touches the device, then the stream, the plan of the
-    passes, ghosts, buffers and masses.  The harness of one pass (each_pass).  And what the passes add up to: candidates,
-    records, final, dropped, steps_done, builds and the host trace [len(trace_names), steps + 1, ncfg]."""
+_Capture = collections.namedtuple("_Capture", "select brk gap max_candidates grade_every thresholds_named")
 
-    def __init__(self, who, ctx, items, all_cells, natoms, mass_of_type, steps, grade_every, thresholds_named, select, brk,
-                 capture_gap, max_candidates, list_cutoff, every, check_every, max_atoms_per_pass, device, trace_names):
-        info = ctx.pot.info
-        self.grade_every = int(grade_every or 0)
+
+class _RunSetup:
+    """What the batched drivers (`who`) share around their passes.  The prologue: the grade steps (and the refusal of thresholds
+    without selection state) before anything touches the device, then the stream, the plan of the passes, ghosts, buffers and
+    masses.  The harness of one pass (each_pass).  And what the passes add up to: candidates, records, final, dropped,
+    steps_done, builds and the host trace [len(trace_names), steps + 1, ncfg].  `batch`: _batch_items' triple; `capture`: the
+    _Capture of _run_arguments, None without grade steps; `replan(plan)`: the passes a driver wants in place of the plan's."""
+
+    def __init__(self, who, ctx, batch, mass_of_type, *, list_cutoff, max_atoms_per_pass, device, capture=None, steps=0, every=1,
+                 check_every=0, trace_names=(), replan=None):
+        info, (items, all_cells, natoms) = ctx.pot.info, batch
+        self.capture = capture = capture or _Capture(2.0, 10.0, 0, 0, 0, False)     # (None: nothing is ever graded or captured)
+        self.grade_every = int(capture.grade_every or 0)
         if not info.has_selection:
-            if thresholds_named:
+            if capture.thresholds_named:
                 raise capi.MtpError(-23, who + ": thresholds need a potential loaded with its selection state")
             self.grade_every = 0
         import torch
         self.torch, self.dev = torch, device or torch.device("cuda:0")
         self.st = _torch_stream(self.dev)
         self.who, self.ctx, self.items, self.all_cells, self.natoms = who, ctx, items, all_cells, natoms
-        self.steps, self.cut = int(steps), float(list_cutoff)
-        self.every, self.check_every = int(every), int(check_every or 0)
-        self.capture_args, self.max_candidates = (select, brk, int(capture_gap)), max_candidates
+        self.steps, self.every, self.check_every, self.cut = int(steps), int(every), int(check_every or 0), float(list_cutoff)
         self.skin = self.cut - float(info.max_cutoff)
         self.cfg_mode = bool(self.grade_every) and bool(info.configuration_mode)
-        self.plan, self.volume, self.max_rows = plan_cell_passes(all_cells, natoms, self.cut, max_atoms_per_pass)
+        plan, self.volume, self.max_rows = plan_cell_passes(all_cells, natoms, self.cut, max_atoms_per_pass)
+        self.plan = plan if replan is None else replan(plan)
         self.ghosts = capi.Ghosts(self.dev.index or 0)
         self.buf = _BatchBuffers(torch, self.dev)
         self.mass_t, self.inv_mass_t = self.to(mass_of_type), self.to(1.0 / mass_of_type)
@@ -1170,7 +1176,7 @@ class _CellRun:
         self.ctx, self.ghosts, self.buf = setup.ctx, setup.ghosts, setup.buf
         self.cut, self.cfg_mode, self.st = setup.cut, setup.cfg_mode, setup.st
         self.items, self.cells, self.counts = setup.items[k0:k1], setup.all_cells[k0:k1], setup.natoms[k0:k1]
-        self.room = max(setup.max_candidates - len(setup.records), 0)     # what earlier passes left of the candidate buffer
+        self.room = max(setup.capture.max_candidates - len(setup.records), 0)     # what earlier passes left of the candidate buffer
         self.C = C = int(self.ctx.pot.info.coeff_count)
         self.ncfg = ncfg = k1 - k0
         self.nonempty = int((self.counts > 0).sum())
@@ -1229,8 +1235,8 @@ class _CellRun:
             ctx.batch_cfg_grades(self.cf_t, n, self.g_t, stream=st)
 
     def capture(self, step):
-        select, brk, gap = self.setup.capture_args
-        capi.sample_capture(self.cf_t, self.n, self.row_cfg, self.g_t, step, select, brk, gap, self.x, self.org_t, self.frozen,
+        c = self.setup.capture
+        capi.sample_capture(self.cf_t, self.n, self.row_cfg, self.g_t, step, c.select, c.brk, c.gap, self.x, self.org_t, self.frozen,
                             self.last_capture, self.slot, self.room, self.stride, self.cand_x, self.rec, self.rec_grade,
                             self.counts_t, stream=self.st)
 
@@ -1388,14 +1394,48 @@ def _minimise_pass(run, steps, graded, step, every, check_every):
     return s
 
 
-def _run_arguments(who, items, masses, threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every,
-                   check_every):
-    """the host-side checks sample_cells and relax_cells (`who`) share: thresholds, atom types and masses, the capture and
-    list arguments.  Returns (select, brk, mass_of_type, max_candidates)."""
-    select = 2.0 if threshold_select is None else float(threshold_select)
-    brk = 10.0 if threshold_break is None else float(threshold_break)
-    if select > brk:
-        raise ValueError("%s: threshold_select (%g) is above threshold_break (%g)" % (who, select, brk))
+def _sample_pass(run, steps, graded, every, check_every, first_half, second_half, record=None, thermostat=True):
+    """The step loop sample_cells and sample_cells_npt share.  Step 0: forces (graded on a grade step) -> with `thermostat`
+    second_half(0, False), fix langevin's setup: the thermostat force, no kick -> on a grade step the capture and one read.
+    Step s = 1 ... steps: first_half(s), the driver's launch and what follows its move -> the reads and rebuilds of
+    _minimise_pass, without the read after step 0 -> forces -> second_half(s, True) -> on a grade step the capture.  record(s)
+    (or None) follows every step made, step 0 included.  Returns the last step made: a first half wrote nothing if the read
+    after it finds nothing running, and is not counted."""
+    record = record or (lambda step: None)
+    run.forces(graded(0))
+    if thermostat:
+        second_half(0, False)
+    stop = False
+    if graded(0):
+        run.capture(0)
+        stop = run.read()[0]
+    record(0)
+    s, since = 0, 0
+    while s < steps and not stop:
+        s += 1
+        first_half(s)
+        since += 1
+        need = since >= every
+        if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
+            done, stale = run.read()
+            if done:                                          # nothing is running any more: this first half wrote nothing
+                s -= 1
+                break
+            need = need or stale
+        if need:
+            run.reneighbor()
+            since = 0
+        grade = graded(s)
+        run.forces(grade)
+        second_half(s, True)
+        if grade:
+            run.capture(s)
+        record(s)
+    return s
+
+
+def _mass_of_type(who, items, masses):
+    """the masses per atom type; ValueError unless the types count from 1 and `masses` is one positive mass or one per type"""
     ntypes = max([int(t.max()) for _, t in items if len(t)], default=1)
     if min([int(t.min()) for _, t in items if len(t)], default=1) < 1:
         raise ValueError("%s: atom types count from 1" % who)
@@ -1404,12 +1444,25 @@ def _run_arguments(who, items, masses, threshold_select, threshold_break, captur
         mass_of_type = np.full(ntypes, float(mass_of_type[0]))
     if len(mass_of_type) < ntypes or not (mass_of_type > 0.0).all():
         raise ValueError("%s: masses is one positive mass, or one per atom type (%d)" % (who, ntypes))
+    return mass_of_type
+
+
+def _run_arguments(who, items, masses, threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every,
+                   check_every):
+    """the host-side checks sample_cells and relax_cells (`who`) share: thresholds, atom types and masses, the capture and
+    list arguments.  Returns (mass_of_type, the _Capture that _RunSetup takes)."""
+    select = 2.0 if threshold_select is None else float(threshold_select)
+    brk = 10.0 if threshold_break is None else float(threshold_break)
+    if select > brk:
+        raise ValueError("%s: threshold_select (%g) is above threshold_break (%g)" % (who, select, brk))
+    mass_of_type = _mass_of_type(who, items, masses)
     if int(capture_gap) < 0 or int(grade_every or 0) < 0 or int(every) < 1 or int(check_every or 0) < 0:
         raise ValueError("%s: capture_gap, grade_every and check_every must not be negative, every at least 1" % who)
     max_candidates = 4 * len(items) if max_candidates is None else int(max_candidates)
     if max_candidates < 0:
         raise ValueError("%s: max_candidates must not be negative" % who)
-    return select, brk, mass_of_type, max_candidates
+    return mass_of_type, _Capture(select, brk, int(capture_gap), max_candidates, grade_every,
+                                  threshold_select is not None or threshold_break is not None)
 
 
 def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break, capture_gap,
@@ -1422,8 +1475,8 @@ def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_s
         raise ValueError(who + ": dt must be positive and finite, got %r" % (dt,))
     if int(steps) < 0 or int(steps) >= 2 ** 30:
         raise ValueError(who + ": steps must be in [0, 2^30)")
-    select, brk, mass_of_type, max_candidates = _run_arguments(who, items, masses, threshold_select, threshold_break,
-                                                               capture_gap, max_candidates, grade_every, every, check_every)
+    mass_of_type, capture = _run_arguments(who, items, masses, threshold_select, threshold_break, capture_gap, max_candidates,
+                                           grade_every, every, check_every)
     if keys is None:
         keys = np.arange(ncfg, dtype=np.uint64)
     else:
@@ -1442,7 +1495,7 @@ def _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_s
         for k, v in enumerate(velocities):
             if len(v) != natoms[k]:
                 raise ValueError(who + ": velocities[%d] must be [%d, 3]" % (k, natoms[k]))
-    return items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities, max_candidates
+    return (items, all_cells, natoms), capture, keys, temperature, mass_of_type, velocities
 
 
 def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=None, masses=183.84, grade_every=10,
@@ -1485,20 +1538,19 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
     steps_done: the steps made (the largest over the passes); builds: the list builds of all passes) and, with the diagnostic trace=True
     (two more launches a step), trace: dict(energy, kinetic [steps_done
     + 1, ncfg]) -- potential and kinetic energy per configuration after every step, step 0 first."""
-    (items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities,
-     max_candidates) = _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break,
-                                         capture_gap, max_candidates, velocities, grade_every, every, check_every)
-    setup = _RunSetup("sample_cells", ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
-                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
-                      list_cutoff, every, check_every, max_atoms_per_pass, device, ("energy", "kinetic") if trace else ())
-    to, st, buf, mass_t, inv_mass_t, graded = setup.to, setup.st, setup.buf, setup.mass_t, setup.inv_mass_t, setup.graded
-    steps, every, check_every = setup.steps, setup.every, setup.check_every
+    batch, capture, keys, temperature, mass_of_type, velocities = _sample_arguments(
+        configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break, capture_gap, max_candidates, velocities,
+        grade_every, every, check_every)
+    setup = _RunSetup("sample_cells", ctx, batch, mass_of_type, capture=capture, steps=steps, every=every, check_every=check_every,
+                      trace_names=("energy", "kinetic") if trace else (), list_cutoff=list_cutoff,
+                      max_atoms_per_pass=max_atoms_per_pass, device=device)
+    to, st, buf, mass_t, inv_mass_t = setup.to, setup.st, setup.buf, setup.mass_t, setup.inv_mass_t
     dt, seed = float(dt), int(seed) & (2 ** 64 - 1)
     t_damp = 0.0 if t_damp is None or not np.isfinite(float(t_damp)) or float(t_damp) <= 0.0 else float(t_damp)
     dtf = 0.5 * dt * FTM2V
     if velocities is None:
-        velocities = maxwell_boltzmann(items, mass_of_type, temperature, seed, keys)
-    frozen_all = np.zeros(len(items), dtype=bool)
+        velocities = maxwell_boltzmann(setup.items, mass_of_type, temperature, seed, keys)
+    frozen_all = np.zeros(len(setup.items), dtype=bool)
 
     def one_pass(run):
         k0, k1, n, cf_t, row_cfg, x, frozen = run.k0, run.k1, run.n, run.cf_t, run.row_cfg, run.x, run.frozen
@@ -1508,43 +1560,15 @@ def sample_cells(ctx, configs, temperature, steps, dt, t_damp=0.1, seed=0, keys=
 
         def second_half(step, kick):
             capi.sample_final(n, row_cfg, cf_t, frozen, v, run.f, buf.tall, mass_t, inv_mass_t, temp_t, key_t, seed, step,
-                              kick, dt, t_damp, stream=st)
+                              dtf if kick else 0.0, dt, t_damp, stream=st)
 
         def record(step):
             run.energies(run.trace[0, step])
             run.monitor(run.trace[1, step])
 
-        run.forces(graded(0))
-        if t_damp > 0.0:
-            second_half(0, 0.0)                               # (fix langevin's setup: the thermostat force of step 0, no kick)
-        stop = False
-        if graded(0):
-            run.capture(0)
-            stop = run.read()[0]
-        if trace:
-            record(0)
-        s, since = 0, 0
-        while s < steps and not stop:
-            s += 1
-            capi.sample_initial(n, row_cfg, frozen, x, v, run.f, buf.tall, inv_mass_t, dtf, dt, stream=st)
-            since += 1
-            need = since >= every
-            if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
-                done, stale = run.read()
-                if done:                                      # everything is frozen: this first half wrote nothing
-                    s -= 1
-                    break
-                need = need or stale
-            if need:
-                run.reneighbor()
-                since = 0
-            grade = graded(s)
-            run.forces(grade)
-            second_half(s, dtf)
-            if grade:
-                run.capture(s)
-            if trace:
-                record(s)
+        s = _sample_pass(run, setup.steps, setup.graded, setup.every, setup.check_every,
+                         lambda step: capi.sample_initial(n, row_cfg, frozen, x, v, run.f, buf.tall, inv_mass_t, dtf, dt, stream=st),
+                         second_half, record if trace else None, thermostat=t_damp > 0.0)
 
         def final(xh, eh):                                    # (the harness ran the monitor once more: sum m v^2 at the end)
             vh, mh = v.cpu().numpy(), run.mv2.cpu().numpy()
@@ -1581,11 +1605,11 @@ def _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec
         raise ValueError(who + ": f_inc >= 1, f_dec in (0, 1), alpha_start in [0, 1] and f_alpha in (0, 1] are required")
     if int(n_min) < 0:
         raise ValueError(who + ": n_min must not be negative")
-    select, brk, mass_of_type, max_candidates = _run_arguments(who, items, masses, threshold_select, threshold_break,
-                                                               capture_gap, max_candidates, grade_every, every, check_every)
+    mass_of_type, capture = _run_arguments(who, items, masses, threshold_select, threshold_break, capture_gap, max_candidates,
+                                           grade_every, every, check_every)
     params = capi.RelaxParams(num["ftol"], num["dt_max"], num["dmax"], num["f_inc"], num["f_dec"], num["alpha_start"], num["f_alpha"],
                               int(n_min))
-    return items, all_cells, natoms, select, brk, mass_of_type, max_candidates, params, num["dt"]
+    return (items, all_cells, natoms), capture, mass_of_type, params, num["dt"]
 
 
 def relax_cells(ctx, configs, steps, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1,
@@ -1617,12 +1641,12 @@ def relax_cells(ctx, configs, steps, ftol=1e-3, dt=1e-3, dt_max=1e-2, dmax=0.1, 
     candidates, records, dropped: as sample_cells; steps_done: the last step whose forces were computed (the largest over the
     passes); builds) and, with trace=True (one more launch and a copy a step), trace: dict(energy, fmax [steps_done + 1, ncfg]) --
     per configuration and step, step 0 first, fmax as in `final`."""
-    (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, params,
-     dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
-                            threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every)
-    setup = _RunSetup("relax_cells", ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
-                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
-                      list_cutoff, every, check_every, max_atoms_per_pass, device, ("energy", "fmax") if trace else ())
+    batch, capture, mass_of_type, params, dt = _relax_arguments(
+        configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses, threshold_select, threshold_break,
+        capture_gap, max_candidates, grade_every, every, check_every)
+    setup = _RunSetup("relax_cells", ctx, batch, mass_of_type, capture=capture, steps=steps, every=every, check_every=check_every,
+                      trace_names=("energy", "fmax") if trace else (), list_cutoff=list_cutoff,
+                      max_atoms_per_pass=max_atoms_per_pass, device=device)
     torch, dev, st, buf = setup.torch, setup.dev, setup.st, setup.buf
 
     def one_pass(run):
@@ -1740,16 +1764,15 @@ def relax_cells_vc(ctx, configs, steps, pressure=0.0, stol=1e-4, cell_mask=(1, 1
     pressure * volume and smax (as fmax: at the last step the minimiser looked at it), and trace=True adds smax and volume
     [steps_done + 1, ncfg] (volume: of the cell the step's forces were taken in)."""
     who = "relax_cells_vc"
-    (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, fire,
-     dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
-                            threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every, who)
-    stol, pressure, cell_factor, cell_mass, mask, per_atom = _relax_vc_arguments(natoms, mass_of_type, pressure, stol, cell_mask,
+    batch, capture, mass_of_type, fire, dt = _relax_arguments(
+        configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses, threshold_select, threshold_break,
+        capture_gap, max_candidates, grade_every, every, check_every, who)
+    stol, pressure, cell_factor, cell_mass, mask, per_atom = _relax_vc_arguments(batch[2], mass_of_type, pressure, stol, cell_mask,
                                                                                  isotropic, cell_factor, cell_mass)
     params = capi.relax_cell_params(fire, stol, pressure, cell_factor, cell_mass, mask, isotropic, per_atom)
-    setup = _RunSetup(who, ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
-                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
-                      list_cutoff, every, check_every, max_atoms_per_pass, device,
-                      ("energy", "fmax", "smax", "volume") if trace else ())
+    setup = _RunSetup(who, ctx, batch, mass_of_type, capture=capture, steps=steps, every=every, check_every=check_every,
+                      trace_names=("energy", "fmax", "smax", "volume") if trace else (), list_cutoff=list_cutoff,
+                      max_atoms_per_pass=max_atoms_per_pass, device=device)
     torch, dev, st, zeros = setup.torch, setup.dev, setup.st, setup.zeros
 
     def one_pass(run):
@@ -1785,8 +1808,9 @@ def relax_cells_vc(ctx, configs, steps, pressure=0.0, stol=1e-4, cell_mask=(1, 1
         return s, final
 
     def empty_final(k):
-        return dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt, cell=all_cells[k].copy(),
-                    virial=np.zeros(6), volume=float(setup.volume[k]), enthalpy=pressure * float(setup.volume[k]), smax=0.0)
+        return dict(x=np.zeros((0, 3)), energy=0.0, fmax=0.0, status=capi.RELAX_STATUS[0], step=-1, dt=dt,
+                    cell=setup.all_cells[k].copy(), virial=np.zeros(6), volume=float(setup.volume[k]),
+                    enthalpy=pressure * float(setup.volume[k]), smax=0.0)
 
     setup.each_pass(one_pass, empty_final, _DeformingCellRun)
     return setup.result()
@@ -1848,24 +1872,22 @@ def sample_cells_npt(ctx, configs, temperature, pressure, steps, dt, *, compress
     "captured-frozen" or "failed") and step (of the failure, -1 otherwise); trace=True adds volume (of the cell the step's
     forces were taken in) and pressure [steps_done + 1, ncfg]."""
     who = "sample_cells_npt"
-    (items, all_cells, natoms, select, brk, keys, temperature, mass_of_type, velocities,
-     max_candidates) = _sample_arguments(configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break,
-                                         capture_gap, max_candidates, velocities, grade_every, every, check_every, who)
+    batch, capture, keys, temperature, mass_of_type, velocities = _sample_arguments(
+        configs, temperature, steps, dt, keys, masses, threshold_select, threshold_break, capture_gap, max_candidates, velocities,
+        grade_every, every, check_every, who)
     pressure, compressibility, tau_p, t_damp, mask, strain_max = _npt_arguments(pressure, compressibility, tau_p, t_damp, cell_mask,
                                                                                 isotropic, strain_max)
-    setup = _RunSetup(who, ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
-                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
-                      list_cutoff, every, check_every, max_atoms_per_pass, device,
-                      ("energy", "kinetic", "volume", "pressure") if trace else ())
-    torch, dev, to, st, zeros, graded = setup.torch, setup.dev, setup.to, setup.st, setup.zeros, setup.graded
-    steps, every, check_every = setup.steps, setup.every, setup.check_every
+    setup = _RunSetup(who, ctx, batch, mass_of_type, capture=capture, steps=steps, every=every, check_every=check_every,
+                      trace_names=("energy", "kinetic", "volume", "pressure") if trace else (), list_cutoff=list_cutoff,
+                      max_atoms_per_pass=max_atoms_per_pass, device=device)
+    torch, dev, to, st, zeros = setup.torch, setup.dev, setup.to, setup.st, setup.zeros
     dt, seed = float(dt), int(seed) & (2 ** 64 - 1)
     dtf = 0.5 * dt * FTM2V
     barostat = tau_p is not None and any(mask)
     params = capi.sample_cell_params(dt, dtf, tau_p, compressibility, pressure, strain_max, mask, isotropic, seed)
     if velocities is None:
-        velocities = maxwell_boltzmann(items, mass_of_type, temperature, seed, keys)
-    frozen_all = np.zeros(len(items), dtype=bool)
+        velocities = maxwell_boltzmann(setup.items, mass_of_type, temperature, seed, keys)
+    frozen_all = np.zeros(len(setup.items), dtype=bool)
 
     def one_pass(run):
         k0, k1, n, ncfg, A = run.k0, run.k1, run.n, run.ncfg, run.A
@@ -1874,9 +1896,14 @@ def sample_cells_npt(ctx, configs, temperature, pressure, steps, dt, *, compress
                  V0=to(setup.volume[k0:k1]), done_step=torch.full((ncfg,), -1, dtype=torch.int32, device=dev),
                  capped=torch.zeros(ncfg, dtype=torch.int32, device=dev), press=zeros(ncfg))
 
+        def first_half(step):
+            capi.sample_cell_step(ncfg, params, step, A, stream=st)
+            if barostat:
+                run.moved()
+
         def second_half(step, kick):
             capi.sample_final(n, run.row_cfg, run.cf_t, run.frozen, v, run.f, run.buf.tall, setup.mass_t, setup.inv_mass_t,
-                              A["temperature"], A["key"], seed, step, kick, dt, t_damp, stream=st)
+                              A["temperature"], A["key"], seed, step, dtf if kick else 0.0, dt, t_damp, stream=st)
 
         def record(step):                                     # (pressure: tr W + 2 K over 3 V, from the monitor's sum m v^2)
             run.energies(run.trace[0, step])
@@ -1885,38 +1912,8 @@ def sample_cells_npt(ctx, configs, temperature, pressure, steps, dt, *, compress
             run.trace[2, step].copy_(vol)
             run.trace[3, step].copy_((run.virial[:, :3].sum(1) + MVV2E * run.trace[1, step]) / (3.0 * vol))
 
-        run.forces(graded(0))
-        second_half(0, 0.0)                                   # (fix langevin's setup: the thermostat force of step 0, no kick)
-        stop = False
-        if graded(0):
-            run.capture(0)
-            stop = run.read()[0]
-        if trace:
-            record(0)
-        s, since = 0, 0
-        while s < steps and not stop:
-            s += 1
-            capi.sample_cell_step(ncfg, params, s, A, stream=st)
-            if barostat:
-                run.moved()
-            since += 1
-            need = since >= every
-            if need or (check_every and since % check_every == 0):   # the one read between rebuilds, and one at a rebuild
-                done, stale = run.read()
-                if done:                                      # nothing is running any more: this first half wrote nothing
-                    s -= 1
-                    break
-                need = need or stale
-            if need:
-                run.reneighbor()
-                since = 0
-            grade = graded(s)
-            run.forces(grade)
-            second_half(s, dtf)
-            if grade:
-                run.capture(s)
-            if trace:
-                record(s)
+        s = _sample_pass(run, setup.steps, setup.graded, setup.every, setup.check_every, first_half, second_half,
+                         record if trace else None)
 
         def final(xh, eh):                                    # (the harness ran the monitor once more: sum m v^2 at the end)
             vh, mh, fh = v.cpu().numpy(), run.mv2.cpu().numpy(), run.frozen.cpu().numpy()
@@ -1934,7 +1931,7 @@ def sample_cells_npt(ctx, configs, temperature, pressure, steps, dt, *, compress
         return s, final
 
     def empty_final(k):
-        return dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0, cell=all_cells[k].copy(),
+        return dict(x=np.zeros((0, 3)), v=np.zeros((0, 3)), energy=0.0, temperature=0.0, cell=setup.all_cells[k].copy(),
                     volume=float(setup.volume[k]), virial=np.zeros(6), pressure=0.0, capped=0, status=capi.RELAX_STATUS[0], step=-1)
 
     setup.each_pass(one_pass, empty_final, _DeformingCellRun, final_monitor=True)
@@ -2066,17 +2063,13 @@ def neb_cells(ctx, bands, steps, spring=5.0, climb_after=None, ftol=1e-3, dt=1e-
     the images of all bands in order; final: per image dict(x, energy); steps_done; builds) and, with trace=True (one more
     launch and a copy a step), trace: dict(energy [steps_done + 1, number of images], fmax [steps_done + 1, number of bands])."""
     configs, band_first, climb_step = _neb_arguments(bands, spring, climb_after)
-    (items, all_cells, natoms, select, brk, mass_of_type, max_candidates, fire,
-     dt) = _relax_arguments(configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses,
-                            threshold_select, threshold_break, capture_gap, max_candidates, grade_every, every, check_every,
-                            who="neb_cells")
+    batch, capture, mass_of_type, fire, dt = _relax_arguments(
+        configs, steps, ftol, dt, dt_max, dmax, n_min, f_inc, f_dec, alpha_start, f_alpha, masses, threshold_select, threshold_break,
+        capture_gap, max_candidates, grade_every, every, check_every, who="neb_cells")
     params = capi.NebParams(fire, float(spring), climb_step)
-    setup = _RunSetup("neb_cells", ctx, items, all_cells, natoms, mass_of_type, steps, grade_every,
-                      threshold_select is not None or threshold_break is not None, select, brk, capture_gap, max_candidates,
-                      list_cutoff, every, check_every, max_atoms_per_pass, device, ("energy", "fmax") if trace else ())
-    # _RunSetup planned the passes for configurations alone; each_pass reads the plan from this attribute, and the harness is
-    # shared with drivers that know no bands, so the plan that keeps bands together replaces it here
-    setup.plan, _, _ = plan_band_passes(all_cells, natoms, band_first, setup.cut, max_atoms_per_pass)
+    setup = _RunSetup("neb_cells", ctx, batch, mass_of_type, capture=capture, steps=steps, every=every, check_every=check_every,
+                      trace_names=("energy", "fmax") if trace else (), list_cutoff=list_cutoff, max_atoms_per_pass=max_atoms_per_pass,
+                      device=device, replan=lambda plan: plan_band_passes(batch[1], batch[2], band_first, list_cutoff, max_atoms_per_pass)[0])
     torch, dev, st = setup.torch, setup.dev, setup.st
     results = [None] * len(bands)
 
@@ -2178,6 +2171,51 @@ def cut_hessian_passes(plan, cells, nsel, list_cutoff, max_hessian_bytes=2 ** 31
     return out
 
 
+def _positive_step(who, name, value):
+    """the difference step `name` of driver `who` as a float, or ValueError"""
+    if not (float(value) > 0.0 and np.isfinite(float(value))):
+        raise ValueError("%s: %s must be positive and finite, got %r" % (who, name, float(value)))
+    return float(value)
+
+
+def _displacement_in_skin(who, name, value, ctx, list_cutoff):
+    """an atom displaced by `value` [A] keeps its list: ValueError unless it is below half the skin"""
+    skin = float(list_cutoff) - float(ctx.pot.info.max_cutoff)
+    if not value < 0.5 * skin:
+        raise ValueError("%s: %s (%g A) must stay below half the skin (list_cutoff - cutoff = %g A): the list has to "
+                         "hold for every displaced copy" % (who, name, value, skin))
+
+
+def _hessian_pass(run, setup, selections, h, mass_weight, status):
+    """The difference loop of hessian_cells and of the ionic arm of elastic_cells.  `selections`: per configuration of the pass
+    the indices, into the configuration, of its differentiated atoms (None: all); `status` [ncfg] int32 on the device: a configuration that
+    has failed is skipped, one that fails here is marked.  Saves x and runs 6 max_j m_j + 1 times "forces, mtp_hess_step", then
+    mtp_hess_finish.  Returns dict(H: the blocks [3 m_j, 3 m_j], from h_first[j]; f0 [n, 3]; state [2, ncfg]: fmax, energy; diag
+    [ncfg, 2]: asymmetry, sum rule; blocks(): after the synchronise, the blocks on the host, NaN where status says failed).
+    The last element of `sel` only keeps the table from being empty: no kernel reads it, whatever it holds."""
+    to, zeros, ncfg, n = setup.to, setup.zeros, run.ncfg, run.n
+    m = run.counts.astype(np.int64) if selections is None else np.array([len(a) for a in selections], dtype=np.int64)
+    rows = [np.arange(n)] if selections is None else [run.rows[j][0] + selections[j] for j in range(ncfg)]
+    sel = np.concatenate(rows + [np.zeros(1, dtype=np.int64)])
+    first = np.concatenate([[0], np.cumsum((3 * m) ** 2)])
+    sel_first_t, sel_t = to(np.concatenate([[0], np.cumsum(m)]).astype(np.int32)), to(sel.astype(np.int32))
+    h_first_t = to(first[:-1].astype(np.int64))
+    H, x0, sel_max = zeros(max(int(first[-1]), 1)), run.x[:n].clone(), int(m.max())
+    f0, state, diag = zeros(n, 3), zeros(2, ncfg), zeros(ncfg, 2)
+    for k in range(6 * sel_max + 1):
+        run.forces(False)
+        capi.hess_step(run.cf_t, sel_first_t, sel_t, sel_max, k, h, run.x, x0, run.f, run.eatom, h_first_t, H, f0, state[0], state[1],
+                       status, stream=run.st)
+    capi.hess_finish(sel_first_t, sel_t, run.buf.tall, setup.mass_t, mass_weight, h_first_t, H, diag, status, stream=run.st)
+
+    def blocks():
+        Hh, failed = H.cpu().numpy(), status.cpu().numpy() == 1
+        return [np.full((N, N), np.nan) if bad else Hh[at: at + N * N].reshape(N, N).copy()
+                for N, at, bad in zip(3 * m, first, failed)]
+
+    return dict(H=H, h_first=h_first_t, f0=f0, state=state, diag=diag, blocks=blocks)
+
+
 def hessian_cells(ctx, configs, h=0.01, atoms=None, mass_weight=False, masses=183.84, list_cutoff=7.0, max_atoms_per_pass=None,
                   max_hessian_bytes=2 ** 31, device=None):
     """What follows relax_cells and neb_cells: the second derivatives at their stationary points, for a whole batch of
@@ -2208,59 +2246,35 @@ def hessian_cells(ctx, configs, h=0.01, atoms=None, mass_weight=False, masses=18
     translation-invariance residual of the force path and stays within 3 n times the force parity bound over h.  The column
     sums, and with them the row sums of the symmetrised `hessian`, vanish only to O(h^2) and have no such bound; that is why
     modes() projects the translations out instead of relying on them."""
-    items, all_cells, natoms = _batch_items(configs)
-    h = float(h)
-    if not (h > 0.0 and np.isfinite(h)):
-        raise ValueError("hessian_cells: h must be positive and finite, got %r" % (h,))
-    select, brk, mass_of_type, _ = _run_arguments("hessian_cells", items, masses, None, None, 0, 0, 0, 1, 0)
+    batch = items, all_cells, natoms = _batch_items(configs)
+    h = _positive_step("hessian_cells", "h", h)
+    mass_of_type = _mass_of_type("hessian_cells", items, masses)
     selections = _hessian_selections(atoms, natoms)
     nsel = np.array([len(a) for a in selections], dtype=np.int64)
-    skin = float(list_cutoff) - float(ctx.pot.info.max_cutoff)
-    if not h < 0.5 * skin:
-        raise ValueError("hessian_cells: h (%g A) must stay below half the skin (list_cutoff - cutoff = %g A): the list has to "
-                         "hold for every displaced copy" % (h, skin))
+    _displacement_in_skin("hessian_cells", "h", h, ctx, list_cutoff)
     _hessian_sizes(nsel, max_hessian_bytes)                   # (a configuration too large raises before anything is set up)
-    setup = _RunSetup("hessian_cells", ctx, items, all_cells, natoms, mass_of_type, 0, 0, False, select, brk, 0, 0, list_cutoff, 1, 0,
-                      max_atoms_per_pass, device, ())
-    # _RunSetup planned the passes for the atoms alone; each_pass reads the plan from this attribute (as in neb_cells)
-    setup.plan = cut_hessian_passes(setup.plan, all_cells, nsel, setup.cut, max_hessian_bytes)
-    torch, dev, st, to = setup.torch, setup.dev, setup.st, setup.to
+    setup = _RunSetup("hessian_cells", ctx, batch, mass_of_type, list_cutoff=list_cutoff, max_atoms_per_pass=max_atoms_per_pass,
+                      device=device, replan=lambda plan: cut_hessian_passes(plan, all_cells, nsel, list_cutoff, max_hessian_bytes))
 
     def empty(k):
         return dict(hessian=np.zeros((0, 0)), atoms=selections[k], energy=0.0, f0=np.zeros((0, 3)), fmax=0.0, asymmetry=0.0,
                     sum_rule=0.0, status=capi.HESS_STATUS[0])
 
     def one_pass(run):
-        k0, ncfg, n = run.k0, run.ncfg, run.n
-        m = nsel[k0: run.k1]
-        sel = np.concatenate([run.rows[j][0] + selections[k0 + j] for j in range(ncfg)] + [np.zeros(1, dtype=np.int64)])
-        first = np.concatenate([[0], np.cumsum((3 * m) ** 2)])
-        sel_first_t, sel_t = to(np.concatenate([[0], np.cumsum(m)]).astype(np.int32)), to(sel.astype(np.int32))
-        h_first_t = to(first[:-1].astype(np.int64))
-        H = setup.zeros(max(int(first[-1]), 1))
-        x0 = run.x[:n].clone()
-        f0, state, diag = setup.zeros(n, 3), setup.zeros(2, ncfg), setup.zeros(ncfg, 2)
-        status = torch.zeros(ncfg, dtype=torch.int32, device=dev)
-        sel_max = int(m.max())
-        for k in range(6 * sel_max + 1):
-            run.forces(False)
-            capi.hess_step(run.cf_t, sel_first_t, sel_t, sel_max, k, h, run.x, x0, run.f, run.eatom, h_first_t, H, f0, state[0],
-                           state[1], status, stream=st)
-        capi.hess_finish(sel_first_t, sel_t, run.buf.tall, setup.mass_t, mass_weight, h_first_t, H, diag, status, stream=st)
+        k0 = run.k0
+        status = setup.torch.zeros(run.ncfg, dtype=setup.torch.int32, device=setup.dev)
+        hp = _hessian_pass(run, setup, selections[k0: run.k1], h, mass_weight, status)
 
         def final(xh, eh):
-            Hh, fh, sh, dh, th = H.cpu().numpy(), f0.cpu().numpy(), state.cpu().numpy(), diag.cpu().numpy(), status.cpu().numpy()
-            out = []
+            fh, sh, dh, th = hp["f0"].cpu().numpy(), hp["state"].cpu().numpy(), hp["diag"].cpu().numpy(), status.cpu().numpy()
+            Hh, out = hp["blocks"](), []
             for j, (a, b) in enumerate(run.rows):
                 if b == a:
                     out.append(empty(k0 + j))
                     continue
-                N = 3 * int(m[j])
-                Hj = Hh[int(first[j]): int(first[j]) + N * N].reshape(N, N).copy()
-                if th[j]:
-                    Hj[:] = np.nan
-                out.append(dict(hessian=Hj, atoms=selections[k0 + j], energy=float(sh[1, j]), f0=fh[a:b], fmax=float(sh[0, j]),
-                                asymmetry=float(dh[j, 0]), sum_rule=float(dh[j, 1]), status=capi.HESS_STATUS[int(th[j])]))
+                out.append(dict(hessian=Hh[j], atoms=selections[k0 + j], energy=float(sh[1, j]), f0=fh[a:b],
+                                fmax=float(sh[0, j]), asymmetry=float(dh[j, 0]), sum_rule=float(dh[j, 1]),
+                                status=capi.HESS_STATUS[int(th[j])]))
             return out
 
         return 0, final
@@ -2439,6 +2453,9 @@ def relax_ions(B, C, coupling, hessian, volume, internal_strain=None):
     return dict(internal_strain=U, birch_relaxed=B - R / V0, elastic_relaxed=C - 0.5 * (R + R.T) / V0, status=status)
 
 
+_relax_ions_on_host = relax_ions                              # (elastic_cells has a parameter of the public name)
+
+
 def elastic_cells(ctx, configs, h=0.005, relax_ions=False, h_atoms=0.01, list_cutoff=7.0, max_atoms_per_pass=None,
                   max_hessian_bytes=2 ** 31, device=None):
     """What hessian_cells leaves out: the second derivatives with respect to the CELL -- elastic constants -- for a whole batch of
@@ -2471,29 +2488,20 @@ def elastic_cells(ctx, configs, h=0.005, relax_ions=False, h_atoms=0.01, list_cu
     with relax_cells or relax_cells_vc first and look at the `fmax` returned here.  An empty configuration gives zeros of the
     right shapes."""
     who = "elastic_cells"
-    items, all_cells, natoms = _batch_items(configs)
-    h, h_atoms = float(h), float(h_atoms)
-    if not (h > 0.0 and np.isfinite(h)):
-        raise ValueError("elastic_cells: h must be positive and finite, got %r" % (h,))
-    if not (h_atoms > 0.0 and np.isfinite(h_atoms)):
-        raise ValueError("elastic_cells: h_atoms must be positive and finite, got %r" % (h_atoms,))
+    batch = items, all_cells, natoms = _batch_items(configs)
+    h, h_atoms = _positive_step(who, "h", h), _positive_step(who, "h_atoms", h_atoms)
     skin = float(list_cutoff) - float(ctx.pot.info.max_cutoff)
     if not h < 0.5 * skin / float(list_cutoff):
         raise ValueError("elastic_cells: h (%g) must stay below half the skin over the list cutoff (%g / %g / 2 = %g): the list has to "
                          "hold for every strained copy" % (h, skin, float(list_cutoff), 0.5 * skin / float(list_cutoff)))
-    if not h_atoms < 0.5 * skin:
-        raise ValueError("elastic_cells: h_atoms (%g A) must stay below half the skin (list_cutoff - cutoff = %g A): the list has to "
-                         "hold for every displaced copy" % (h_atoms, skin))
+    _displacement_in_skin(who, "h_atoms", h_atoms, ctx, list_cutoff)
     ionic = bool(relax_ions)
     if ionic:
         _hessian_sizes(natoms, max_hessian_bytes)
-    select, brk, mass_of_type, _ = _run_arguments(who, items, 1.0, None, None, 0, 0, 0, 1, 0)
-    setup = _RunSetup(who, ctx, items, all_cells, natoms, mass_of_type, 0, 0, False, select, brk, 0, 0, list_cutoff, 1, 0,
-                      max_atoms_per_pass, device, ())
-    if ionic:
-        setup.plan = cut_hessian_passes(setup.plan, all_cells, natoms, setup.cut, max_hessian_bytes)
+    setup = _RunSetup(who, ctx, batch, _mass_of_type(who, items, 1.0), list_cutoff=list_cutoff, max_atoms_per_pass=max_atoms_per_pass,
+                      device=device,
+                      replan=(lambda plan: cut_hessian_passes(plan, all_cells, natoms, list_cutoff, max_hessian_bytes)) if ionic else None)
     torch, dev, st, to, zeros = setup.torch, setup.dev, setup.st, setup.to, setup.zeros
-    solve_on_host = globals()["relax_ions"]
 
     def empty(k):
         z = lambda *s: np.zeros(s)
@@ -2517,25 +2525,17 @@ def elastic_cells(ctx, configs, h=0.005, relax_ions=False, h_atoms=0.01, list_cu
                               coupling, c_first_t, f0, state[0], state[1], stress0, status, stream=st)
             run.moved()
         capi.elastic_finish(run.cf_t, c_first_t, coupling, stress0, Bt, B, Cm, diag, status, stream=st)
-        if ionic:
-            first = np.concatenate([[0], np.cumsum((3 * np.diff(cf)) ** 2)])
-            h_first_t, sel_t = to(first[:-1].astype(np.int64)), to(np.arange(n + 1, dtype=np.int32))
-            H, U, B_rel, C_rel = zeros(max(int(first[-1]), 1)), zeros(max(18 * n, 1)), zeros(ncfg, 36), zeros(ncfg, 36)
-            hdiag, hstate, hf0 = zeros(ncfg, 2), zeros(2, ncfg), zeros(n, 3)
-            sel_max = int(run.counts.max())
-            for k in range(6 * sel_max + 1):
-                run.forces(False)
-                capi.hess_step(run.cf_t, run.cf_t, sel_t, sel_max, k, h_atoms, run.x, x0, run.f, run.eatom, h_first_t, H, hf0, hstate[0],
-                               hstate[1], status, stream=st)
-            capi.hess_finish(run.cf_t, sel_t, run.buf.tall, setup.mass_t, False, h_first_t, H, hdiag, status, stream=st)
-            capi.elastic_relax(run.cf_t, h_first_t, H, c_first_t, coupling, to(setup.volume[k0: run.k1]), B, Cm, U, B_rel, C_rel,
-                               status, stream=st)
+        if ionic:                                             # (the strain loop left x = x0, and its failures in `status`)
+            U, B_rel, C_rel = zeros(max(18 * n, 1)), zeros(ncfg, 36), zeros(ncfg, 36)
+            hp = _hessian_pass(run, setup, None, h_atoms, False, status)
+            capi.elastic_relax(run.cf_t, hp["h_first"], hp["H"], c_first_t, coupling, to(setup.volume[k0: run.k1]), B, Cm, U, B_rel,
+                               C_rel, status, stream=st)
 
         def final(xh, eh):
             fh, sh, dh, th = f0.cpu().numpy(), state.cpu().numpy(), diag.cpu().numpy(), status.cpu().numpy()
             s0, Bh, Ch, Lh = stress0.cpu().numpy(), B.cpu().numpy(), Cm.cpu().numpy(), coupling.cpu().numpy()
             if ionic:
-                Hh, Uh, Brh, Crh = H.cpu().numpy(), U.cpu().numpy(), B_rel.cpu().numpy(), C_rel.cpu().numpy()
+                Hh, Uh, Brh, Crh = hp["blocks"](), U.cpu().numpy(), B_rel.cpu().numpy(), C_rel.cpu().numpy()
             out = []
             for j, (a, b) in enumerate(run.rows):
                 if b == a:
@@ -2549,13 +2549,12 @@ def elastic_cells(ctx, configs, h=0.005, relax_ions=False, h_atoms=0.01, list_cu
                     for key in ("birch", "elastic", "coupling"):
                         r[key][:] = np.nan
                 if ionic:
-                    r["hessian"] = Hh[int(first[j]): int(first[j]) + N * N].reshape(N, N).copy()
+                    r["hessian"] = Hh[j]
                     if code == 1:
-                        r["hessian"][:] = np.nan
                         r.update(internal_strain=np.full((6, N), np.nan), birch_relaxed=np.full((6, 6), np.nan),
                                  elastic_relaxed=np.full((6, 6), np.nan))
                     elif N > capi.ELASTIC_RELAX_MAX_N:                # above the largest LDS tier: the same algorithm on the host
-                        more = solve_on_host(r["birch"], r["elastic"], r["coupling"], r["hessian"], r["volume"])
+                        more = _relax_ions_on_host(r["birch"], r["elastic"], r["coupling"], r["hessian"], r["volume"])
                         code = capi.ELASTIC_STATUS.index(more.pop("status"))
                         r.update(more)
                     else:

@@ -10,6 +10,7 @@ from lammps_mtp_kokkos_amd import capi
 
 import _batch
 import _relax
+from _stub_run import StubRun
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -103,34 +104,6 @@ def test_relax_cells_checks_its_arguments_before_the_device(monkeypatch):
         assert ei.value.code == -23
 
 
-class _StubRun:
-    """a run that only writes down what the minimiser loop asks of it: F forces, C capture, M the monitor read, B rebuild;
-    `answers` are the (nothing runs any more, lists are stale) replies of the reads, in order, (False, False) once they run out"""
-
-    def __init__(self, answers=()):
-        self.log, self.answers, self.moves = [], list(answers), 0
-
-    def forces(self, grade):
-        self.log.append("F")
-        self.graded_forces = getattr(self, "graded_forces", []) + [bool(grade)]
-
-    def capture(self, step):
-        self.log.append("C%d" % step)
-
-    def step(self, s, last):
-        self.log.append("S%d%s" % (s, "last" if last else ""))
-
-    def moved(self):
-        self.moves += 1
-
-    def read(self):
-        self.log.append("M")
-        return self.answers.pop(0) if self.answers else (False, False)
-
-    def reneighbor(self):
-        self.log.append("B")
-
-
 @pytest.mark.parametrize("kw,answers,want,s_want", [
     (dict(steps=5, every=3, check_every=2), (), "F S0 M | F S1 M | F S2 M B | F S3 | F S4 M | F S5last", 5),
     (dict(steps=5, every=3, check_every=0), (), "F S0 M | F S1 | F S2 M B | F S3 | F S4 | F S5last", 5),
@@ -147,7 +120,7 @@ def test_the_minimiser_loop_asks_the_run_in_the_order_of_relax_cells(kw, answers
     due or stale (since = 0).  Case "stale": the rebuild of step 1 restarts the count, so the next reads are those of steps 3
     (since = 2) and 4 (since = 3 = every)."""
     from lammps_mtp_kokkos_amd import md
-    run = _StubRun(answers)
+    run = StubRun(answers)
     ge = kw.get("grade_every", 0)
     s = md._minimise_pass(run, kw["steps"], lambda step: bool(ge) and step % ge == 0, run.step, kw["every"], kw["check_every"])
     assert " ".join(run.log) == want.replace(" |", "")

@@ -128,3 +128,44 @@ def test_maxwell_boltzmann_is_per_configuration_and_has_no_net_momentum():
         assert np.abs((m[:, None] * v[k]).sum(0)).max() < 1e-9
         T = MVV2E * (m[:, None] * v[k] ** 2).sum() / (3 * len(m) * KB)
         assert abs(T - (300.0, 0, 0, 600.0)[k]) < 0.12 * (300.0, 0, 0, 600.0)[k]
+
+
+@pytest.mark.parametrize("kw,answers,want,s_want", [
+    (dict(steps=5, every=3, check_every=2), (), "F H0 | I1 F H1 | I2 M F H2 | I3 M B F H3 | I4 F H4 | I5 M F H5", 5),
+    (dict(steps=5, every=3, check_every=2), [(True, False)], "F H0 | I1 F H1 | I2 M", 1),
+    (dict(steps=5, every=3, check_every=2, grade_every=2), [(True, False)], "F H0 C0 M", 0),
+    (dict(steps=1, every=3, check_every=2, thermostat=False), (), "F | I1 F H1", 1),
+    (dict(steps=3, every=3, check_every=1), [(False, True)], "F H0 | I1 M B F H1 | I2 M F H2 | I3 M F H3", 3),
+    (dict(steps=2, every=3, check_every=0, grade_every=2), (), "F H0 C0 M | I1 F H1 | I2 F H2 C2", 2),
+], ids=["cadence", "all-frozen-at-a-read", "frozen-at-graded-step-0", "nve", "stale", "graded"])
+@pytest.mark.parametrize("recording", [False, True], ids=["", "record"])
+def test_the_sampler_loop_asks_the_run_in_the_order_of_sample_cells(kw, answers, want, s_want, recording):
+    """md._sample_pass, the step loop of sample_cells and sample_cells_npt, with a run that has no device behind it (the twin of
+    the test of md._minimise_pass in tests/test_relax_cpu.py).  F forces, H<s> second half, I<s> first half, C<s> capture, M read,
+    B rebuild; the sequences are read off the loop sample_cells had of its own:
+
+      case                     steps every check_every grade_every thermostat reads              sequence                          returns
+      cadence                  5     3     2           0           on         (False, False)...  F H0 | I1 F H1 | I2 M F H2 |      5
+                                                                                                 I3 M B F H3 | I4 F H4 | I5 M F H5
+      all frozen at a read     5     3     2           0           on         first (True, -)    F H0 | I1 F H1 | I2 M             1
+      frozen at graded step 0  5     3     2           2           on         first (True, -)    F H0 C0 M                         0
+      NVE                      1     3     2           0           off        (False, False)...  F | I1 F H1                       1
+      stale                    3     3     1           0           on         first (-, True)    F H0 | I1 M B F H1 | I2 M F H2 |  3
+                                                                                                 I3 M F H3
+      graded                   2     3     0           2           on         (False, False)...  F H0 C0 M | I1 F H1 | I2 F H2 C2  2
+
+    Step 0 is forces, the thermostat's setup call (no kick) and, graded, the capture and one read.  Then per step: the first
+    half, since += 1, the read at since >= every and at since % check_every == 0, the all-frozen break -- the step whose first
+    half wrote nothing is not counted --, the rebuild when due or stale (since = 0), forces, the second half, the capture.  The
+    forces are graded exactly on the grade steps, and record follows every completed step, step 0 included."""
+    from lammps_mtp_kokkos_amd import md
+    from _stub_run import StubRun
+    run = StubRun(answers)
+    ge = kw.get("grade_every", 0)
+    s = md._sample_pass(run, kw["steps"], lambda step: bool(ge) and step % ge == 0, kw["every"], kw["check_every"], run.first_half,
+                        run.second_half, run.record if recording else None, thermostat=kw.get("thermostat", True))
+    assert " ".join(run.log) == want.replace(" |", "")
+    assert s == s_want and run.log.count("B") == want.count("B")
+    assert run.graded_forces == [bool(ge) and q % ge == 0 for q in range(s + 1)]
+    assert run.recorded == (list(range(s + 1)) if recording else [])
+    assert run.moves == 0                                                            # (what follows a move is the first half's)
