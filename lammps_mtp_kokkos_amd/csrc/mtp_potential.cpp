@@ -5,6 +5,7 @@
 // (mtp_radial_basis.cpp:59-102) and PairMTPExtrapolation::read_file
 // (pair_mtp_extrapolation.cpp:528-612); SURVEY.md App. A is the condensed grammar.
 #include "mtp_potential.hpp"
+#include "mtp_bank_search.hpp"
 
 #include "../../include/mtp_mi355x.h"
 
@@ -446,11 +447,6 @@ ScheduleOptions read_options()
   return o;
 }
 
-struct Lcg {   // fixed-seed LCG of the local searches: the schedule is deterministic
-  uint64_t state;
-  uint32_t operator()() { return (uint32_t) ((state = state * 6364136223846793005ull + 1442695040888963407ull) >> 33); }
-};
-
 int refuse(std::string &err, int code, const char *msg)
 {
   err = msg;
@@ -841,436 +837,14 @@ void number_moments(mtp_potential &p, const std::vector<char> &leaf)
   for (int m = 0; m < A; m++) p.moment_perm[m] = m < B ? m : (leaf[m] ? next_leaf++ : next_stored++);
 }
 
-// LDS bank model of the product passes.  They read M[a0], M[a1], D[a3] (ds_read_b64: the two 32-lane halves of a wave
-// instruction are banked separately over 32 eight-byte banks) and add into M[a3], D[a0], D[a1] (ds_add_f64, banked like
-// ds_write_b64: four 16-lane groups over 16 eight-byte banks); distinct moments of one group on one bank serialise
-// (MI355X_MICROARCH.md, LDS table).
-const int kWRead[3] = {2, 2, 1}, kWAdd[3] = {1, 1, 1};   // a0, a1 are read in both passes, D[a3] in the reverse one
-int pen(int n) { return n > 1 ? n - 1 : 0; }
-
-struct BankModel {
-  const mtp_potential &p;
-  int leaf_row0;   // first (padded) row of the leaf block
-  // extra cycles of one group of rows [r0, r0 + grp) under the current numbering: grp = 32 the reads, 16 the adds
-  // reads of one address broadcast (count distinct moments); adds to one address serialise (count rows)
-  int group_cost(int r0, int grp) const
-  {
-    const int nbk = grp, *w3 = grp == 32 ? kWRead : kWAdd;
-    const bool distinct = grp == 32;
-    int c = 0;
-    for (int st = 0; st < (r0 >= leaf_row0 ? 2 : 3); st++) {   // (leaf rows: no access to their target)
-      int seen[32], ns = 0;
-      uint8_t h[32] = {0};
-      for (int r = r0; r < r0 + grp; r++) {
-        const MtpRow &row = p.rows_by_level[(size_t) r];
-        const int m = p.moment_perm[st == 0 ? row.a0 : (st == 1 ? row.a1 : row.a3)];
-        bool dup = false;
-        if (distinct)
-          for (int q = 0; q < ns; q++) dup |= seen[q] == m;
-        if (!dup) {
-          seen[ns++] = m;
-          h[m % nbk]++;
-        }
-      }
-      for (int b = 0; b < nbk; b++) c += w3[st] * pen(h[b]);
-    }
-    return c;
-  }
-  long long total(int grp) const
-  {
-    long long c = 0;
-    for (size_t r0 = 0; r0 < p.rows_by_level.size(); r0 += grp) c += group_cost((int) r0, grp);
-    return c;
-  }
-};
-
-// The annealed search (search_banks, v2).  Shipped effort for row-per-lane potentials: 4 rounds x 16 times the proposals;
-// at level 16 that takes the model from 888 to about 210 extra cycles per atom in half the time v1 needed for 335
-// (profiles/bank_search_ab.txt).  Inverse temperatures by Anneal's scale: a round starts at ANNEAL_K0 plus up to
-// ANNEAL_K_STEP (the last round) and ends at ANNEAL_K1; hotter starts lose the greedy order for nothing.
-constexpr int BANK_ROUNDS_V2 = 4, BANK_SCALE_V2 = 16;
-constexpr int ANNEAL_K0 = 24, ANNEAL_K_STEP = 8, ANNEAL_K1 = 60;
-constexpr int ROW_TRIALS_V2 = 200;   // row proposals per row, round and unit of scale ...
-constexpr long long ROW_TRIALS_MIN = 200000;   // ... and at least so many a round: small tables cost next to nothing
-constexpr long long RENUMBER_TRIALS_MIN = 50000;   // (likewise for the renumbering proposals of a round)
-
-// Acceptance rule of the annealed search: a proposal that raises the model by d > 0 cycles passes with probability
-// 2^(-d k / 4); the inverse temperature k rises linearly from k0 to k1 over the proposals of a round.  Proposals that
-// keep the model pass.  Integer arithmetic and the caller's Lcg only, so the walk is the same on every host.
-struct Anneal {
-  int k0, k1, k = -1;
-  uint32_t thr[8] = {0};   // thr[d]: passes if the next 31-bit draw is below it
-  void at(long long t, long long trials)
-  {
-    const int kk = k0 + (int) ((long long) (k1 - k0) * t / std::max(trials, 1ll));
-    if (kk == k) return;
-    k = kk;
-    uint64_t qk = 1ull << 32, f = 1ull << 31;
-    for (int i = 0; i < k; i++) qk = (qk * 3611622603ull) >> 32;   // 2^(-1/4) in 32 fractional bits
-    for (int d = 1; d < 8; d++) thr[d] = (uint32_t) (f = (f * qk) >> 32);
-  }
-  bool pass(int d, Lcg &next) const { return d <= 0 || (d < 8 && next() < thr[d]); }
-};
-
-// Search round (a): renumber moments, rows fixed.  Numbers swap inside a class only (cls: basics, stored products,
-// leaves).  Without `an` only proposals that lower the model pass; with it the round anneals and ends on the best
-// numbering it has seen.
-void renumber_round(mtp_potential &p, const BankModel &model, const std::vector<char> &leaf,
-                    const std::vector<int> cls_members[3], Lcg &next, int bank_scale, Anneal *an = nullptr)
-{
-  const int A = p.alpha_moment_count, B = p.alpha_index_basic_count;
-  const std::vector<MtpRow> &rows = p.rows_by_level;
-  struct Access {
-    int nbk, w;
-  };
-  std::vector<Access> acc;
-  // moment (file index) -> (access, weight of the moment in it: 1 for reads, its row count for adds), ascending
-  std::vector<std::vector<std::pair<int, int>>> occ((size_t) A);
-  std::vector<uint8_t> hist;                       // [access][32]: load per bank
-  auto add_accesses = [&](int grp) {   // (as in BankModel::group_cost)
-    const int nbk = grp, *w3 = grp == 32 ? kWRead : kWAdd;
-    const bool distinct = grp == 32;
-    const int ngroups = (int) rows.size() / grp;
-    for (int g = 0; g < ngroups; g++)
-      for (int st = 0; st < (grp * g >= model.leaf_row0 ? 2 : 3); st++) {
-        const int id = (int) acc.size();
-        acc.push_back({nbk, w3[st]});
-        hist.resize(hist.size() + 32, 0);
-        for (int r = grp * g; r < grp * g + grp; r++) {
-          const MtpRow &row = rows[(size_t) r];
-          const int m = st == 0 ? row.a0 : (st == 1 ? row.a1 : row.a3);
-          auto &o = occ[(size_t) m];
-          if (!o.empty() && o.back().first == id) {
-            if (distinct) continue;
-            o.back().second++;
-          } else {
-            o.push_back({id, 1});
-          }
-          hist[(size_t) id * 32 + (p.moment_perm[m] % nbk)]++;
-        }
-      }
-  };
-  add_accesses(32);
-  add_accesses(16);
-  auto mult_in = [&](int m, int id) {   // rows (adds) / 1 (reads) of moment m in access id, 0 if absent
-    const auto &o = occ[(size_t) m];
-    auto it = std::lower_bound(o.begin(), o.end(), std::make_pair(id, 0));
-    return it != o.end() && it->first == id ? it->second : 0;
-  };
-  // cost change of swapping the numbers of m (at `from`) and other (at `to`), counted over m's accesses; accesses
-  // holding both are counted once, from the smaller moment
-  auto move_delta = [&](int m, int from, int to, int other) {
-    int d = 0;
-    for (const auto &e : occ[(size_t) m]) {
-      const int id = e.first, k = e.second, k2 = mult_in(other, id);
-      if (k2 > 0 && m > other) continue;
-      const int f = from % acc[(size_t) id].nbk, t = to % acc[(size_t) id].nbk;
-      if (f == t) continue;
-      const uint8_t *h = &hist[(size_t) id * 32];
-      d += acc[(size_t) id].w * (pen(h[f] - k + k2) + pen(h[t] + k - k2) - pen(h[f]) - pen(h[t]));
-    }
-    return d;
-  };
-  auto apply_move = [&](int m, int from, int to, int other) {
-    for (const auto &e : occ[(size_t) m]) {
-      const int id = e.first, k = e.second, k2 = mult_in(other, id);
-      if (k2 > 0 && m > other) continue;
-      const int f = from % acc[(size_t) id].nbk, t = to % acc[(size_t) id].nbk;
-      if (f == t) continue;
-      hist[(size_t) id * 32 + f] = (uint8_t) (hist[(size_t) id * 32 + f] - k + k2);
-      hist[(size_t) id * 32 + t] = (uint8_t) (hist[(size_t) id * 32 + t] + k - k2);
-    }
-  };
-  long long trials = bank_scale * std::min<long long>(200ll * A, 300000ll);
-  if (an) trials = std::max(trials, RENUMBER_TRIALS_MIN);
-  long long cur = 0, best = 0;   // model relative to the start of the round
-  std::vector<int32_t> best_perm;
-  for (long long t = 0; t < trials; t++) {
-    if (an) an->at(t, trials);
-    // three proposals in four start from a moment some row uses (weighted by use: the often-used moments are the ones
-    // that collide), the rest from any moment
-    int m1 = (int) (next() % (uint32_t) A);
-    if ((next() & 3) != 0) {
-      const MtpRow &pr = rows[next() % (uint32_t) rows.size()];
-      const uint32_t st = next() % 3u;
-      m1 = st == 0 ? pr.a0 : (st == 1 ? pr.a1 : pr.a3);
-    }
-    const std::vector<int> &cls = cls_members[m1 < B ? 0 : (leaf[m1] ? 2 : 1)];
-    if (cls.size() < 2) continue;
-    const int m2 = cls[next() % (uint32_t) cls.size()];
-    if (m1 == m2) continue;
-    const int p1 = p.moment_perm[m1], p2 = p.moment_perm[m2];
-    const int delta = move_delta(m1, p1, p2, m2) + move_delta(m2, p2, p1, m1);
-    if (an ? !an->pass(delta, next) : delta >= 0) continue;
-    if (an && delta > 0 && cur == best && best_perm.empty()) best_perm = p.moment_perm;   // leaving the best numbering
-    apply_move(m1, p1, p2, m2);
-    apply_move(m2, p2, p1, m1);
-    std::swap(p.moment_perm[m1], p.moment_perm[m2]);
-    cur += delta;
-    if (cur <= best) {   // (among equals the latest: the other round may find a way on from it)
-      best = cur;
-      best_perm.clear();
-    }
-  }
-  if (!best_perm.empty()) p.moment_perm.swap(best_perm);
-}
-
-// Search round (b): swap rows inside a level (they commute), numbering fixed.
-void swap_rows_round(mtp_potential &p, const BankModel &model, Lcg &next, int bank_scale)
-{
-  std::vector<MtpRow> &rows = p.rows_by_level;
-  const int nlev2 = (int) p.level_offset.size() - 1;
-  const long long rtrials = bank_scale * std::min<long long>(100ll * (long long) rows.size(), 250000ll);
-  for (long long t = 0; t < rtrials; t++) {
-    const int l = (int) (next() % (uint32_t) nlev2);
-    const int b = p.level_offset[l], n = p.level_offset[l + 1] - b;
-    if (n < 2) continue;
-    // the first row comes from a 16-row group that has a collision (four tries), its partner from anywhere in the level
-    int r1 = b + (int) (next() % (uint32_t) n);
-    for (int tries = 0; tries < 4 && model.group_cost(r1 / 16 * 16, 16) == 0; tries++)
-      r1 = b + (int) (next() % (uint32_t) n);
-    const int r2 = b + (int) (next() % (uint32_t) n);
-    if (r1 / 16 == r2 / 16) continue;   // same add group (hence same read group): nothing changes
-    auto local = [&]() {
-      int c = model.group_cost(r1 / 16 * 16, 16) + model.group_cost(r2 / 16 * 16, 16);
-      c += model.group_cost(r1 / 32 * 32, 32);
-      if (r1 / 32 != r2 / 32) c += model.group_cost(r2 / 32 * 32, 32);
-      return c;
-    };
-    const int c0 = local();
-    std::swap(rows[(size_t) r1], rows[(size_t) r2]);
-    if (local() >= c0) std::swap(rows[(size_t) r1], rows[(size_t) r2]);
-  }
-}
-
-// Search round (b) of the annealed search: moves of rows, numbering fixed.  A row may exchange its two factors (the
-// product commutes, and the reverse pass adds d3 m0 to D[a1] and d3 m1 to D[a0] either way: the exchange only decides
-// which of the two add instructions, and which of the two reads, carries which moment), two rows of a level may swap
-// places, with or without an exchange in either, and three rows of a level may rotate over three add groups.  The
-// model is kept as bank histograms per access (the accesses of BankModel::group_cost), so a proposal costs a few
-// counter updates per row it touches.  Acceptance by `an`; the round ends on the best rows it has seen.
-struct RowAnnealer {
-  std::vector<MtpRow> &rows;
-  const std::vector<int32_t> &perm;
-  const int leaf_row0, A;
-  std::vector<uint8_t> hadd, hread, rcnt;   // [16-group][stream][16], [32-group][stream][32]: load per bank;
-                                            // [32-group][stream][moment]: rows that read the moment
-  std::vector<int> gcost;                   // add cycles of each 16-group: where the proposals start
-  RowAnnealer(mtp_potential &p, int leaf_row0_)
-      : rows(p.rows_by_level), perm(p.moment_perm), leaf_row0(leaf_row0_), A(p.alpha_moment_count)
-  {
-    hadd.assign(rows.size() / 16 * 3 * 16, 0);
-    hread.assign(rows.size() / 32 * 3 * 32, 0);
-    rcnt.assign(rows.size() / 32 * 3 * (size_t) A, 0);
-    gcost.assign(rows.size() / 16, 0);
-    for (int r = 0; r < (int) rows.size(); r++) (void) put(r, +1);
-  }
-  // row r enters (s = +1) or leaves (s = -1) the accesses of its groups; returns the change of the model
-  int put(int r, int s)
-  {
-    const MtpRow &row = rows[(size_t) r];
-    const int m3[3] = {row.a0, row.a1, row.a3};
-    int d = 0;
-    for (int st = 0; st < (r >= leaf_row0 ? 2 : 3); st++) {   // (leaf rows: no access to their target)
-      const int m = m3[st], num = perm[(size_t) m];
-      uint8_t &h = hadd[((size_t) (r / 16) * 3 + st) * 16 + num % 16];
-      const int da = kWAdd[st] * (pen(h + s) - pen(h));
-      h = (uint8_t) (h + s);
-      gcost[(size_t) (r / 16)] += da;
-      d += da;
-      uint8_t &c = rcnt[((size_t) (r / 32) * 3 + st) * A + m];   // reads of one address broadcast
-      if ((s > 0 ? c : c - 1) == 0) {
-        uint8_t &hr = hread[((size_t) (r / 32) * 3 + st) * 32 + num % 32];
-        d += kWRead[st] * (pen(hr + s) - pen(hr));
-        hr = (uint8_t) (hr + s);
-      }
-      c = (uint8_t) (c + s);
-    }
-    return d;
-  }
-  // rows at pos[0..n) take the contents now[0..n); returns the change of the model
-  int place(const int *pos, const MtpRow *now, int n)
-  {
-    int d = 0;
-    for (int i = 0; i < n; i++) d += put(pos[i], -1);
-    for (int i = 0; i < n; i++) rows[(size_t) pos[i]] = now[i];
-    for (int i = 0; i < n; i++) d += put(pos[i], +1);
-    return d;
-  }
-};
-
-void anneal_rows_round(mtp_potential &p, const BankModel &model, Lcg &next, long long trials, Anneal &an)
-{
-  RowAnnealer ra(p, model.leaf_row0);
-  std::vector<MtpRow> &rows = p.rows_by_level;
-  const int nlev2 = (int) p.level_offset.size() - 1;
-  auto exchanged = [](MtpRow r) {
-    std::swap(r.a0, r.a1);
-    return r;
-  };
-  long long cur = 0, best = 0;   // model relative to the start of the round
-  std::vector<MtpRow> best_rows;
-  for (long long t = 0; t < trials; t++) {
-    an.at(t, trials);
-    const int l = (int) (next() % (uint32_t) nlev2);
-    const int b = p.level_offset[l], n = p.level_offset[l + 1] - b;
-    if (n < 1) continue;
-    // the first row comes from a 16-row group that has a collision (four tries), its partners from anywhere in the level
-    int pos[3] = {b + (int) (next() % (uint32_t) n), 0, 0};
-    for (int tries = 0; tries < 4 && ra.gcost[(size_t) (pos[0] / 16)] == 0; tries++) pos[0] = b + (int) (next() % (uint32_t) n);
-    const uint32_t kind = next() % 8u;   // 0-1 exchange, 2-3 swap, 4-5 swap and exchange, 6-7 three-cycle
-    MtpRow was[3], now[3];
-    int np = 1;
-    if (kind < 2) {
-      if (rows[(size_t) pos[0]].a0 == rows[(size_t) pos[0]].a1) continue;   // a square: nothing changes
-    } else {
-      np = kind < 6 ? 2 : 3;
-      for (int i = 1; i < np; i++) pos[i] = b + (int) (next() % (uint32_t) n);
-      // rows of one add group (hence of one read group) trade places for nothing
-      if (pos[0] / 16 == pos[1] / 16 || (np == 3 && (pos[2] / 16 == pos[0] / 16 || pos[2] / 16 == pos[1] / 16))) continue;
-    }
-    for (int i = 0; i < np; i++) was[i] = rows[(size_t) pos[i]];
-    if (kind < 2) {
-      now[0] = exchanged(was[0]);
-    } else if (kind < 6) {
-      now[0] = was[1];
-      now[1] = was[0];
-      if (kind >= 4) {
-        const uint32_t which = 1u + next() % 3u;   // the row that arrives at pos[0], at pos[1], or both
-        if (which & 1u) now[0] = exchanged(now[0]);
-        if (which & 2u) now[1] = exchanged(now[1]);
-      }
-    } else {
-      now[0] = was[2];
-      now[1] = was[0];
-      now[2] = was[1];
-    }
-    const int delta = ra.place(pos, now, np);
-    if (!an.pass(delta, next)) {
-      (void) ra.place(pos, was, np);
-      continue;
-    }
-    if (delta > 0 && cur == best && best_rows.empty()) {   // leaving the best rows: keep them
-      best_rows = rows;
-      for (int i = 0; i < np; i++) best_rows[(size_t) pos[i]] = was[i];
-    }
-    cur += delta;
-    if (cur <= best) {
-      best = cur;
-      best_rows.clear();
-    }
-  }
-  if (!best_rows.empty()) rows.swap(best_rows);
-}
-
-// MTP_DEBUG_BANKS: one line of the model, the adds split by stream (a0, a1: reverse pass; a3: forward) and into
-// same-address / same-bank shares
-void report_split(const mtp_potential &p, const BankModel &model, const char *when)
-{
-  const std::vector<MtpRow> &rows = p.rows_by_level;
-  long long same_addr[3] = {0, 0, 0}, same_bank[3] = {0, 0, 0};
-  for (size_t r0 = 0; r0 < rows.size(); r0 += 16)
-    for (int st = 0; st < ((int) r0 >= model.leaf_row0 ? 2 : 3); st++) {
-      int ids[16][16], nid[16] = {0}, h[16] = {0};   // per bank: distinct moments, rows
-      for (size_t r = r0; r < r0 + 16; r++) {
-        const MtpRow &row = rows[r];
-        const int m = p.moment_perm[st == 0 ? row.a0 : (st == 1 ? row.a1 : row.a3)], b = m % 16;
-        h[b]++;
-        int q = 0;
-        while (q < nid[b] && ids[b][q] != m) q++;
-        if (q == nid[b]) ids[b][nid[b]++] = m;
-      }
-      for (int b = 0; b < 16; b++) {
-        same_addr[st] += h[b] - nid[b];
-        same_bank[st] += pen(h[b]) - (h[b] - nid[b]);
-      }
-    }
-  std::fprintf(stderr, "mtp:   %s: reads %lld, adds %lld; adds, same address / other address on the bank: D[a0] %lld / %lld, D[a1] %lld / %lld, M[a3] %lld / %lld\n",
-               when, model.total(32), model.total(16), same_addr[0], same_bank[0], same_addr[1], same_bank[1], same_addr[2],
-               same_bank[2]);
-}
-
-// MTP_DEBUG_BANKS: the model before and after the search, and the same-address adds that no search can avoid.  A moment
-// used u times in a level of G add groups has to share a group u - G times; a factor may sit in either D stream (factor
-// exchange), so the two streams count as one of 2 G places.  Neutral padding rows count like any row.
-void report_banks(const mtp_potential &p, const BankModel &model, long long cost_before, int bank_rounds,
-                  int bank_scale, bool v1)
-{
-  const std::vector<MtpRow> &rows = p.rows_by_level;
-  const long long cr = model.total(32), ca = model.total(16);
-  std::fprintf(stderr, "mtp: LDS bank model of the product passes: %lld -> %lld extra cycles per atom (reads %lld, adds %lld); "
-                       "%d head x tail blocks, %d rounds x %d, search %s\n", cost_before, cr + ca, cr, ca, p.fwd_block_count,
-               bank_rounds, bank_scale, v1 ? "v1" : "v2");
-  report_split(p, model, "after");
-  long long forced_d = 0, forced_m = 0;
-  std::vector<int> uf((size_t) p.alpha_moment_count), ut((size_t) p.alpha_moment_count);
-  for (size_t l = 0; l + 1 < p.level_offset.size(); l++) {
-    const int b = p.level_offset[l], e = p.level_offset[l + 1], groups = (e - b) / 16;
-    std::fill(uf.begin(), uf.end(), 0);
-    std::fill(ut.begin(), ut.end(), 0);
-    for (int r = b; r < e; r++) {
-      uf[(size_t) rows[(size_t) r].a0]++;
-      uf[(size_t) rows[(size_t) r].a1]++;
-      if (r < model.leaf_row0) ut[(size_t) rows[(size_t) r].a3]++;
-    }
-    long long fd = 0, fm = 0;
-    for (int m = 0; m < p.alpha_moment_count; m++) {
-      fd += std::max(0, uf[(size_t) m] - 2 * groups);
-      fm += std::max(0, ut[(size_t) m] - groups);
-    }
-    std::fprintf(stderr, "mtp:   forced same-address adds, %s %d (%d add groups): D[a0] + D[a1] %lld, M[a3] %lld\n",
-                 b >= model.leaf_row0 ? "leaf block" : "level", (int) l + 1, groups, fd, fm);
-    forced_d += fd;
-    forced_m += fm;
-  }
-  std::fprintf(stderr, "mtp:   forced same-address adds in all: D[a0] + D[a1] %lld, M[a3] %lld\n", forced_d, forced_m);
-}
-
-// LDS numbering of the moments and order of the rows inside their levels, by a deterministic local search (fixed-seed
-// LCG) on the modelled extra cycles (BankModel).  The moments are renumbered -- basics among [0, B), products among
-// [B, A), so the zero-fill and the k < B loops of the kernel keep working -- by pairwise swaps, in rounds that alternate
-// with moves of rows inside a level.  moment_perm[file index] = LDS index; relabel writes every device table in LDS
-// numbering.
-//   v2 (the default for row-per-lane potentials): both rounds anneal (Anneal) and end on the best state they saw; the
-//       row round exchanges the factors of a row, swaps rows with or without an exchange and rotates three rows, on
-//       incremental bank histograms (RowAnnealer).
-//   v1 (MTP_BANK_SEARCH=v1, and the gather-form potentials): only proposals that lower the model pass, the row round
-//       swaps two rows and recounts their groups.
+// LDS numbering of the moments and order of the rows inside their levels, by the bank search (mtp_bank_search.hpp) on
+// the rows, the numbering and the level bounds alone.  moment_perm[file index] = LDS index; relabel writes every device
+// table in LDS numbering.
 void search_banks(mtp_potential &p, const std::vector<char> &leaf, const ScheduleOptions &opt)
 {
-  std::vector<int> cls_members[3];   // 0 basics, 1 stored products, 2 leaves (file indices)
-  for (int m = 0; m < p.alpha_moment_count; m++)
-    cls_members[m < p.alpha_index_basic_count ? 0 : (leaf[m] ? 2 : 1)].push_back(m);
-  const BankModel model{p, p.level_offset[(size_t) p.normal_levels]};
-  const long long cost_before = model.total(32) + model.total(16);
-  if (opt.debug_banks) report_split(p, model, "before");
-  // Search effort.  Potentials whose product passes run row per lane (the narrow lane grids: up to level 16) pay every
-  // modelled collision in ds_add_f64 cycles, the busiest pipe of their kernel.  v1 ran eight rounds of four times the
-  // proposals for them (16 s at level 16 on the development host, once per potential load; model 888 -> 335 extra cycles
-  // per atom).  v2 runs BANK_ROUNDS_V2 x BANK_SCALE_V2 (see there).  The wide grids run the gather programs, which have
-  // their own refinement (refine_program): two rounds of v1, whose model the kernel does not follow for them.
-  // MTP_BANK_ROUNDS / MTP_BANK_SCALE override (tests use two rounds).  (row per lane <=> at most 32 head x tail blocks
-  // in the basic-moment pass, mtp_pick_fwd_shape)
-  const bool row_per_lane = p.fwd_block_count <= 32;
-  const bool v1 = opt.search_v1 || !row_per_lane;
-  const int bank_rounds = opt.bank_rounds >= 0 ? opt.bank_rounds : (!row_per_lane ? 2 : (v1 ? 8 : BANK_ROUNDS_V2));
-  const int bank_scale = opt.bank_scale >= 1 ? opt.bank_scale : (!row_per_lane ? 1 : (v1 ? 4 : BANK_SCALE_V2));
-  Lcg next{0x9E3779B97F4A7C15ull};
-  for (int round = 0; round < bank_rounds; round++) {
-    if (v1) {
-      renumber_round(p, model, leaf, cls_members, next, bank_scale);
-      swap_rows_round(p, model, next, bank_scale);
-    } else {
-      // every round reheats, later rounds less: the first one leaves the greedy order of order_rows behind, the last
-      // ones only polish
-      Anneal an{ANNEAL_K0 + ANNEAL_K_STEP * round / std::max(bank_rounds - 1, 1), ANNEAL_K1};
-      renumber_round(p, model, leaf, cls_members, next, bank_scale, &an);
-      an.k = -1;
-      const long long row_trials = bank_scale * ROW_TRIALS_V2 * (long long) p.rows_by_level.size();
-      anneal_rows_round(p, model, next, std::max(row_trials, ROW_TRIALS_MIN), an);
-    }
-  }
-  if (opt.debug_banks) report_banks(p, model, cost_before, bank_rounds, bank_scale, v1);
+  mtp_bank_search::Table table{p.rows_by_level, p.moment_perm, p.level_offset, p.level_offset[(size_t) p.normal_levels],
+                               p.alpha_index_basic_count, leaf};
+  mtp_bank_search::search(table, {opt.search_v1, opt.bank_rounds, opt.bank_scale, opt.debug_banks, p.fwd_block_count});
 }
 
 // Everything the kernels index by moment, in LDS numbering (moment_perm): the rows, the adjoint seeds, the leaf and
@@ -1403,7 +977,7 @@ void refine_program(const ProgramLevel &lv)
       for (int hw = 0; hw < 4; hw++) rc[((size_t) g * cs + u) * 4 + hw] = read_cost(g, u, hw >> 1, hw & 1);
     for (int q = 0; q < 4; q++) ac[(size_t) g * 4 + q] = add_cost(g, q);
   }
-  Lcg next{0xD1B54A32D192ED03ull};
+  mtp_bank_search::Lcg next{0xD1B54A32D192ED03ull};
   const long long trials = std::min<long long>(300ll * G * 64, 300000ll);
   for (long long t = 0; t < trials; t++) {
     // start from a read (or, one time in four, an add) that has a conflict: a lane on its most loaded bank moves

@@ -1,4 +1,4 @@
-// What the bank search of the schedule builder (csrc/mtp_potential.cpp, search_banks) leaves behind, printed without a
+// What the bank search of the schedule builder (csrc/mtp_bank_search.hpp, search) leaves behind, printed without a
 // device: tests/test_bank_search_cpu.py builds this from mtp_potential.cpp + mtp_plan.cpp alone (once more with
 // -fsanitize=address,undefined) and reads the lines.  The search itself is steered by the environment (MTP_BANK_SEARCH,
 // MTP_BANK_ROUNDS, MTP_BANK_SCALE, MTP_DEBUG_BANKS), as in the library.

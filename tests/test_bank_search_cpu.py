@@ -1,10 +1,12 @@
-"""The LDS-bank search of the schedule builder (csrc/mtp_potential.cpp: search_banks), host only.
+"""The LDS-bank search of the schedule builder (csrc/mtp_bank_search.hpp: search, which mtp_potential::finalize runs
+through search_banks), host only.
 
 tests/cpp/bank_search_dump.cpp is built from mtp_potential.cpp + mtp_plan.cpp alone (as `make plan_dump` builds its
 program) and prints the rows, the numbering and a hash of both after a load; MTP_DEBUG_BANKS=1 makes the library print
 its model on stderr.  Two searches: v1 (MTP_BANK_SEARCH=v1: greedy, two move kinds; the table of the commit before the
 annealed search, whose hashes are in tests/golden/bank_search_v1.json) and v2 (the default for row-per-lane potentials:
-annealed, with factor exchange, compound row moves and incremental bank histograms).
+annealed, with factor exchange and compound row moves).  Both run the same rounds on one incremental state of the model
+(State); they differ in the moves the row round proposes and in the acceptance rule.
 
 Checked for every committed potential at effort 2 x 1 (what the suites run), and for W_L16.mtp at the shipped default:
   same rows      the rows after the search are the file's rows as a multiset of {unordered (a0, a1), mult, a3} in file
@@ -13,12 +15,17 @@ Checked for every committed potential at effort 2 x 1 (what the suites run), and
                  classes basics / stored products / leaves;
   determinism    two loads print the same bytes;
   v1             reproduces the recorded hash;
+  tables         every load gives the hash and the model (before, after, reads, adds) that the last commit with the search
+                 inside mtp_potential.cpp gave (tests/golden/bank_search_tables.json): both searches at 2 x 1, W_L16.mtp
+                 at v1 8 x 4, v1 4 x 16, v2 4 x 16 and v2 0 x 1, W_L8.mtp and WRe_L20.mtp with nothing set;
   improvement    the model of v2 is below that of v1 at the same effort, and the printed floor of forced same-address
                  adds is at or below the count reached.  W_L8.mtp has 14 stored moments for add groups of 16 lanes: two
                  same-address adds per group and stream are forced, v1 already sits on that floor (64 = 64), and there
                  v2 has to reach the floor as well -- nothing is below it.
-A hand-made level of 32 rows whose hot factor is a0 in every row must end with that factor in both streams, and the
-program built with -fsanitize=address,undefined must run W_L16.mtp at 2 x 1 clean."""
+A hand-made level of 32 rows whose hot factor is a0 in every row must end with that factor in both streams, the
+program built with -fsanitize=address,undefined must run W_L16.mtp at 2 x 1 clean, and tests/cpp/bank_state_check.cpp
+(built the same way, from the header alone) holds the incremental state against the from-scratch count of the model
+over 20 000 random mutations of a hand-made table."""
 import collections
 import json
 import os
@@ -38,6 +45,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POT = os.path.join(ROOT, "potentials")
 CSRC = os.path.join(ROOT, "lammps_mtp_kokkos_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "bank_search_v1.json")
+TABLES = os.path.join(ROOT, "tests", "golden", "bank_search_tables.json")
+DEFAULTS = ("W_L8.mtp", "WRe_L20.mtp")   # also loaded with nothing set
 POTENTIALS = ["W_L8.mtp", "W_L16.mtp", "WRe_L20.mtp", "WRe_L10_cfg.almtp", "W_L16_nbh.almtp"]
 SUITE = (2, 1)            # the effort of the suites (tests/conftest.py)
 SHIPPED_V1 = (8, 4)       # what v1 shipped for row-per-lane potentials
@@ -51,9 +60,12 @@ def _compiler():
     return cxx
 
 
-def _build(out, extra=()):
-    src = [os.path.join(ROOT, "tests", "cpp", "bank_search_dump.cpp"), os.path.join(CSRC, "mtp_plan.cpp"),
-           os.path.join(CSRC, "mtp_potential.cpp")]
+DUMP_SRC = [os.path.join(ROOT, "tests", "cpp", "bank_search_dump.cpp"), os.path.join(CSRC, "mtp_plan.cpp"),
+            os.path.join(CSRC, "mtp_potential.cpp")]
+SANITIZE = ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+
+
+def _build(out, extra=(), src=DUMP_SRC):
     cmd = [_compiler(), "-std=c++17", "-O2", "-Wall", "-Wextra", "-Wno-unused-parameter", "-D__HIP_PLATFORM_AMD__",
            "-I/opt/rocm/include", *extra, "-o", out, *src]
     subprocess.run(cmd, check=True)
@@ -168,12 +180,27 @@ def golden():
     return json.load(open(GOLDEN))
 
 
+@pytest.fixture(scope="module")
+def tables():
+    return json.load(open(TABLES))
+
+
+def _check_table(r, want):
+    assert {"hash": r["hash"], "before": r["before"], "after": r["model"], "reads": r["reads"], "adds": r["adds"]} == want
+
+
 @pytest.mark.parametrize("name", POTENTIALS)
-def test_suite_effort_same_rows_determinism_v1_and_improvement(program, golden, name):
+def test_suite_effort_same_rows_determinism_v1_and_improvement(program, golden, tables, name):
     path = os.path.join(POT, name)
     procs = [_start(program, path, s, SUITE) for s in ("v1", "v2", "v2")]
-    old, new, again = [_finish(p) for p in procs]
+    if name in DEFAULTS:
+        procs.append(_start(program, path, None, None))
+    old, new, again = [_finish(p) for p in procs[:3]]
     assert old["search"] == "v1" and old["hash"] == golden["%s@%dx%d" % ((name,) + SUITE)]
+    _check_table(old, tables["%s@v1@%dx%d" % ((name,) + SUITE)])
+    _check_table(new, tables["%s@v2@%dx%d" % ((name,) + SUITE)])
+    if name in DEFAULTS:
+        _check_table(_finish(procs[3]), tables["%s@default" % name])
     assert new["stdout"] == again["stdout"] and new["stderr"] == again["stderr"]
     _check_same_rows(path, new, old)
     row_per_lane = int(re.search(r"(\d+) head x tail blocks", new["stderr"])[1]) <= 32
@@ -184,13 +211,16 @@ def test_suite_effort_same_rows_determinism_v1_and_improvement(program, golden, 
     _check_improvement(new, old)
 
 
-def test_shipped_effort_level16(program, golden):
+def test_shipped_effort_level16(program, golden, tables):
     path = os.path.join(POT, "W_L16.mtp")
     procs = [_start(program, path, "v1", None), _start(program, path, "v1", SHIPPED_V2), _start(program, path, "v2", None),
              _start(program, path, "v2", None)]
     parent, old, new, again = [_finish(p) for p in procs]
     assert "%d rounds x %d, search v1" % SHIPPED_V1 in parent["stderr"] and "%d rounds x %d, search v2" % SHIPPED_V2 in new["stderr"]
     assert parent["hash"] == golden["W_L16.mtp@%dx%d" % SHIPPED_V1]
+    _check_table(parent, tables["W_L16.mtp@v1@%dx%d" % SHIPPED_V1])
+    _check_table(old, tables["W_L16.mtp@v1@%dx%d" % SHIPPED_V2])
+    _check_table(new, tables["W_L16.mtp@v2@%dx%d" % SHIPPED_V2])
     assert new["stdout"] == again["stdout"] and new["stderr"] == again["stderr"]
     _check_same_rows(path, new, old)
     _check_improvement(new, old)      # v1 at v2's effort
@@ -237,15 +267,25 @@ def test_hot_factor_ends_in_both_streams(program, tmp_path):
     assert new["model"] < old["model"]
 
 
-def test_zero_rounds_is_no_search(program):
+def test_zero_rounds_is_no_search(program, tables):
     path = os.path.join(POT, "W_L16.mtp")
     a, b = _load(program, path, "v1", (0, 1)), _load(program, path, "v2", (0, 1))
+    _check_table(b, tables["W_L16.mtp@v2@0x1"])
     assert a["hash"] == b["hash"] and a["model"] == a["before"] == b["model"]
     assert np.array_equal(a["perm"][:a["B"]], np.arange(a["B"]))
 
 
 def test_sanitized_program_runs_clean(tmp_path):
     """a stand-alone program with its own main, built with -fsanitize=address,undefined: nothing is loaded into Python"""
-    exe = _build(str(tmp_path / "bank_search_dump_san"), extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    exe = _build(str(tmp_path / "bank_search_dump_san"), extra=SANITIZE)
     r = _load(exe, os.path.join(POT, "W_L16.mtp"), "v2", SUITE)
     assert r["search"] == "v2" and "runtime error" not in r["stderr"] and "AddressSanitizer" not in r["stderr"]
+
+
+def test_state_against_recount(tmp_path):
+    """tests/cpp/bank_state_check.cpp: a stand-alone program with its own main on csrc/mtp_bank_search.hpp alone, built
+    with -fsanitize=address,undefined; it exits non-zero at the first mismatch of State and recount"""
+    exe = _build(str(tmp_path / "bank_state_check"), extra=SANITIZE, src=[os.path.join(ROOT, "tests", "cpp", "bank_state_check.cpp")])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("bank_state_check: ok, 20000 mutations") and r.stderr == ""

@@ -1,4 +1,4 @@
-"""The table of the annealed bank search (csrc/mtp_potential.cpp: search_banks, v2) under the force kernels, on the GPU.
+"""The table of the annealed bank search (csrc/mtp_bank_search.hpp: search, v2) under the force kernels, on the GPU.
 
 v2 exchanges the two factors of product rows, moves rows inside their levels and numbers the moments differently; the
 kernels read all of that from the blob, so with its table the fixed force shape of level 16 is still bitwise the generic
