@@ -966,6 +966,53 @@ int mtp_elastic_relax(void *stream, int ncfg, const int *d_cfg_first, const long
                       const double *d_C, double *d_U, double *d_B_rel, double *d_C_rel, int *d_status);
 
 
+/* ---- batched symmetric eigen-solver: eigenvalues and eigenvectors of every matrix of a ragged batch, in LDS -----------------
+ *
+ * What follows mtp_hess_finish: the normal modes of a whole batch of force-constant matrices without a copy to the host.  One
+ * launch per LDS tier, one workgroup of MTP_BATCH_BLOCK threads per matrix; cyclic two-sided Jacobi in fp64.  Matrix j is
+ * [N_j][N_j], row-major, at A + a_first[j] (the blocks of mtp_hess_finish: h_first can be handed over as it is) and is only
+ * read; its eigenvalues go ascending to W + w_first[j], its eigenvectors, if d_V is given, to V + a_first[j], row-major, column
+ * i belonging to W[i]; info[j] = (sweeps made, off-diagonal Frobenius norm at the end).  A matrix with status[j] != 0 on entry
+ * is skipped, nothing of it is written (the status of a Hessian pass can be passed straight in); N_j == 0 writes nothing.
+ * Every sum runs in index order or through the fixed-order workgroup total, and no expression is contracted: the results do
+ * not depend on the batch a matrix is in.  Per matrix, in this order:
+ *   1. a_rc = 0.5 * (x + y) with x = A_rc / (root_r * root_c), y = A_cr / (root_c * root_r), root = d_root + w_first[j] (the
+ *      square roots of the masses, one per coordinate), or x = A_rc, y = A_cr without d_root
+ *   2. with project (N a multiple of 3): A <- P A P, P = I - sum_d t_d t_d^T, t_d[i] = root_i (or 1) where i % 3 == d,
+ *      normalised: tau_i = root_i / sqrt(sum_{k % 3 == i % 3} root_k^2), u[r][d] = sum_{i % 3 == d} a_ri tau_i,
+ *      g[d][e] = sum_{i % 3 == d} tau_i u[i][e] (all sums over ascending i), and for r >= c
+ *      a_rc <- ((a_rc - tau_r u[c][r % 3]) - u[r][c % 3] tau_c) + (tau_r g[r % 3][c % 3]) tau_c
+ *   3. norm = |A|_F: thread t adds a_rc^2 for r N + c = t, t + MTP_BATCH_BLOCK, ..., then the workgroup total.  A norm or a root
+ *      that is not finite, or project with N % 3 != 0, fails the matrix: W, V and info become NaN, status[j] = MTP_EIGH_FAILED.
+ *      thr = (norm * 2^-53) / N
+ *   4. sweeps in the parallel round-robin order: with Ne = N rounded up to even and M = Ne - 1, step s = 0 ... M - 1 rotates
+ *      the pairs (M, s) and ((s + i) mod M, (s - i) mod M), i = 1 ... Ne / 2 - 1, each taken as (p, q), p < q; a pair with the
+ *      padding index of an odd N is idle.  A pair rotates iff |a_pq| > thr: zeta = (a_qq - a_pp) / (2 a_pq),
+ *      t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (t = 1 at zeta = 0), c = 1 / sqrt(1 + t^2), s = t c; a_pp <- a_pp - t a_pq,
+ *      a_qq <- a_qq + t a_pq, a_pq <- 0 exactly.  All rotations of a step are computed from the diagonal 2 x 2 blocks first and
+ *      parked in LDS; after a barrier the 2 x 2 block B where pairs k1 > k2 of the step meet becomes J1^T B J2 (the rows first:
+ *      x_p. = c1 b_p. - s1 b_q., x_q. = s1 b_p. + c1 b_q.; then the columns: b_.p = c2 x_.p - s2 x_.q, b_.q = s2 x_.p + c2 x_.q)
+ *      and the columns of V: v_rp <- c v_rp - s v_rq, v_rq <- s v_rp + c v_rq.  A block whose two pairs have s = 0 and the
+ *      columns of a pair with s = 0 are left as they are.  Every element is written once per step, from old values.
+ *      The solve ends after the first sweep without a rotation, or after max_sweeps sweeps: then status[j] =
+ *      MTP_EIGH_NOT_CONVERGED and the state reached is still sorted and written.
+ *   5. the diagonal ascending by rank, ties by index: W, the permuted columns of V, info.
+ * The tiers: N <= 48 and <= 96 hold A (a packed lower triangle) and V in LDS, 30 and 113 KiB a workgroup (12 and 41 KiB
+ * without d_V); N <= 192 holds A alone (153 KiB) and serves d_V == NULL only.  A matrix above its limit -- MTP_EIGH_MAX_N_VECTORS
+ * with d_V, MTP_EIGH_MAX_N without -- gets status[j] = MTP_EIGH_TOO_LARGE and nothing else of it is written: the caller solves
+ * it on the host.
+ * MTP_ERR_ARG, nothing launched: a NULL stream, nmat < 0, max_sweeps < 1, a missing array (nmat > 0; d_root and d_V may be NULL). */
+#define MTP_EIGH_FAILED 1          /* a non-finite entry, mass root or norm; or project != 0 with N % 3 != 0 */
+#define MTP_EIGH_NOT_CONVERGED 2   /* max_sweeps sweeps and the last one still rotated */
+#define MTP_EIGH_TOO_LARGE 3       /* N above the tier that can serve it; nothing else of it is written */
+#define MTP_EIGH_TIER_SMALL 48
+#define MTP_EIGH_MAX_N_VECTORS 96
+#define MTP_EIGH_MAX_N 192
+int mtp_eigh_batched(void *stream, int nmat, const int *d_n, const long long *d_a_first, const double *d_A,
+                     const long long *d_w_first, const double *d_root /* [sum N_j] or NULL */, int project, int max_sweeps,
+                     double *d_W, double *d_V /* or NULL */, double *d_info /* [nmat][2] */, int *d_status);
+
+
 /* ---- MaxVol selection: which candidate vectors enter the active set ------------------------------------------------
  *
  * The step of the active-learning loop that consumes the grades (MLIP's select-add; the reference only grades,

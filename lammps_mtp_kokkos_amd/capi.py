@@ -49,7 +49,7 @@ EXPORTS = [
     "mtp_sample_to_cell", "mtp_relax_step",
     "mtp_relax_cell_step", "mtp_relax_cell_rebase", "mtp_relax_cell_capture_cells", "mtp_ghosts_deform",
     "mtp_sample_cell_step", "mtp_neb_step", "mtp_hess_step", "mtp_hess_finish",
-    "mtp_elastic_step", "mtp_elastic_finish", "mtp_elastic_relax",
+    "mtp_elastic_step", "mtp_elastic_finish", "mtp_elastic_relax", "mtp_eigh_batched",
     "mtp_normal_sizes", "mtp_normal_create", "mtp_normal_destroy", "mtp_normal_last_error", "mtp_normal_info",
     "mtp_normal_set_round_slices", "mtp_normal_clear", "mtp_normal_accumulate", "mtp_normal_get", "mtp_normal_set",
     "mtp_normal_factor", "mtp_normal_quadratic",
@@ -117,7 +117,7 @@ def kernel_source_hash():
     src = os.path.join(_HERE, "csrc")
     other_launches = ("mtp_neighbor_kernels.hip", "mtp_halo.hip", "mtp_md.hip", "mtp_sample.hip", "mtp_relax.hip",
                       "mtp_relax_cell.hip", "mtp_batch_step.hpp", "mtp_sample_cell.hip", "mtp_philox.hpp", "mtp_neb.hip",
-                      "mtp_hess.hip", "mtp_elastic.hip")
+                      "mtp_hess.hip", "mtp_elastic.hip", "mtp_eigh.hip")
     for n in sorted(os.listdir(src)):
         if n.endswith((".hip", ".hpp", ".cpp")) and n not in other_launches:
             h.update(n.encode())
@@ -1328,6 +1328,24 @@ def elastic_relax(cfg_first_t, h_first_t, H_t, c_first_t, coupling_t, vol_t, B_t
                                  _ptr(C_rel_t), _ptr(status_t))
     if rc:
         raise MtpError(rc, "mtp_elastic_relax")
+
+
+# ---- batched symmetric eigen-solver (include/mtp_mi355x.h)
+
+EIGH_STATUS = ("ok", "failed", "not converged", "too large")                # status_t[j] = 0, 1, 2, 3
+EIGH_MAX_N, EIGH_MAX_N_VECTORS = 192, 96                                    # the largest N without and with eigenvectors
+
+
+def eigh_batched(n_t, a_first_t, A_t, w_first_t, root_t, project, max_sweeps, W_t, V_t, info_t, status_t, stream=None):
+    """eigenvalues (and, with V_t, eigenvectors) of the matrices [N_j, N_j] at A_t + a_first_t[j] by Jacobi sweeps in LDS:
+    mtp_eigh_batched.  n_t and status_t [nmat] are int32, a_first_t and w_first_t [nmat] int64; root_t (one per coordinate, laid
+    out like W_t) divides A_rc by root_r root_c, or None; project takes the three translations out (N a multiple of 3); W_t holds
+    the eigenvalues ascending from w_first_t[j], V_t (or None) the eigenvectors like A_t, column i to W[i]; info_t [nmat, 2] =
+    (sweeps, off-diagonal norm).  status_t[j] != 0 on entry skips the matrix; 1, 2, 3 on return: EIGH_STATUS."""
+    rc = lib().mtp_eigh_batched(_st(stream), int(n_t.numel()), _ptr(n_t), _ptr(a_first_t), _ptr(A_t), _ptr(w_first_t), _ptr(root_t),
+                                int(bool(project)), int(max_sweeps), _ptr(W_t), _ptr(V_t), _ptr(info_t), _ptr(status_t))
+    if rc:
+        raise MtpError(rc, "mtp_eigh_batched")
 
 
 # ---- linear refit without the design matrix: double-double normal equations (include/mtp_mi355x.h) -------------------------

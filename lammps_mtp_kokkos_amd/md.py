@@ -2217,7 +2217,7 @@ def _hessian_pass(run, setup, selections, h, mass_weight, status):
 
 
 def hessian_cells(ctx, configs, h=0.01, atoms=None, mass_weight=False, masses=183.84, list_cutoff=7.0, max_atoms_per_pass=None,
-                  max_hessian_bytes=2 ** 31, device=None):
+                  max_hessian_bytes=2 ** 31, device=None, modes=False, project_translations=None, zero_tol=1e-3, vectors=False):
     """What follows relax_cells and neb_cells: the second derivatives at their stationary points, for a whole batch of
     independent periodic cells at once, device-resident -- force constants by central differences of the forces with the step
     `h` [A].  `configs` and the passes are those of evaluate_cells (`list_cutoff`, `max_atoms_per_pass`); a displacement of `h`
@@ -2245,29 +2245,50 @@ def hessian_cells(ctx, configs, h=0.01, atoms=None, mass_weight=False, masses=18
     over all atoms they vanish to rounding (Newton's third law in the force call), so for a full selection sum_rule is the
     translation-invariance residual of the force path and stays within 3 n times the force parity bound over h.  The column
     sums, and with them the row sums of the symmetrised `hessian`, vanish only to O(h^2) and have no such bound; that is why
-    modes() projects the translations out instead of relying on them."""
+    modes() projects the translations out instead of relying on them.
+
+    modes=True: the normal modes of every Hessian of a pass are solved on the device (mtp_eigh_batched) from the blocks
+    mtp_hess_finish left, before anything is copied back; the masses of the selected atoms weight a Hessian that is not yet
+    mass-weighted.  The dicts gain the keys of modes() -- frequencies, eigenvalues, eigenvectors (None unless `vectors`),
+    n_unstable, n_zero (`zero_tol`) -- and modes_status (capi.EIGH_STATUS; "failed" with NaN frequencies where the Hessian failed)
+    and solver: "device", or "host" for a matrix above the solver's size (capi.EIGH_MAX_N coordinates, capi.EIGH_MAX_N_VECTORS
+    with `vectors`), which goes through modes().  project_translations: None projects the translations out of the full selections
+    only; True or False decides for all.  `hessian` is returned as without modes."""
     batch = items, all_cells, natoms = _batch_items(configs)
     h = _positive_step("hessian_cells", "h", h)
     mass_of_type = _mass_of_type("hessian_cells", items, masses)
     selections = _hessian_selections(atoms, natoms)
     nsel = np.array([len(a) for a in selections], dtype=np.int64)
+    if modes and not (float(zero_tol) >= 0.0):
+        raise ValueError("hessian_cells: zero_tol must not be negative")
+    project = (nsel == natoms) if project_translations is None else np.full(len(nsel), bool(project_translations))
     _displacement_in_skin("hessian_cells", "h", h, ctx, list_cutoff)
     _hessian_sizes(nsel, max_hessian_bytes)                   # (a configuration too large raises before anything is set up)
     setup = _RunSetup("hessian_cells", ctx, batch, mass_of_type, list_cutoff=list_cutoff, max_atoms_per_pass=max_atoms_per_pass,
                       device=device, replan=lambda plan: cut_hessian_passes(plan, all_cells, nsel, list_cutoff, max_hessian_bytes))
 
     def empty(k):
-        return dict(hessian=np.zeros((0, 0)), atoms=selections[k], energy=0.0, f0=np.zeros((0, 3)), fmax=0.0, asymmetry=0.0,
-                    sum_rule=0.0, status=capi.HESS_STATUS[0])
+        out = dict(hessian=np.zeros((0, 0)), atoms=selections[k], energy=0.0, f0=np.zeros((0, 3)), fmax=0.0, asymmetry=0.0,
+                   sum_rule=0.0, status=capi.HESS_STATUS[0])
+        if modes:
+            out.update(_hessian_modes_keys(_modes_dict(np.zeros(0), np.zeros((0, 0)) if vectors else None, zero_tol, 0, 0, "device")))
+        return out
 
     def one_pass(run):
         k0 = run.k0
         status = setup.torch.zeros(run.ncfg, dtype=setup.torch.int32, device=setup.dev)
         hp = _hessian_pass(run, setup, selections[k0: run.k1], h, mass_weight, status)
+        if modes:     # solved from the blocks on the device; a Hessian that failed is skipped and stays "failed"
+            sel, root = selections[k0: run.k1], None
+            if not mass_weight:
+                root = [np.repeat(np.sqrt(mass_of_type[items[k0 + j][1][a] - 1]), 3) for j, a in enumerate(sel)]
+            solve = _eigh_device(setup.torch, setup.dev, run.st, 3 * nsel[k0: run.k1], hp["h_first"], hp["H"], root, project[k0: run.k1],
+                                 30, vectors, status)
 
         def final(xh, eh):
             fh, sh, dh, th = hp["f0"].cpu().numpy(), hp["state"].cpu().numpy(), hp["diag"].cpu().numpy(), status.cpu().numpy()
             Hh, out = hp["blocks"](), []
+            found = solve(zero_tol) if modes else None
             for j, (a, b) in enumerate(run.rows):
                 if b == a:
                     out.append(empty(k0 + j))
@@ -2275,6 +2296,11 @@ def hessian_cells(ctx, configs, h=0.01, atoms=None, mass_weight=False, masses=18
                 out.append(dict(hessian=Hh[j], atoms=selections[k0 + j], energy=float(sh[1, j]), f0=fh[a:b],
                                 fmax=float(sh[0, j]), asymmetry=float(dh[j, 0]), sum_rule=float(dh[j, 1]),
                                 status=capi.HESS_STATUS[int(th[j])]))
+                if modes:
+                    if found[j] is None:     # above the solver's size: the host routine, on the Hessian as returned
+                        M = None if mass_weight else mass_of_type[items[k0 + j][1][selections[k0 + j]] - 1]
+                        found[j] = _host_modes(Hh[j], M, bool(project[k0 + j]), zero_tol, vectors)
+                    out[-1].update(_hessian_modes_keys(found[j]))
             return out
 
         return 0, final
@@ -2323,6 +2349,124 @@ def modes(hessian, masses_of_atoms, project_translations=True, zero_tol=1e-3):
     nu = np.sign(lam) * np.sqrt(np.abs(lam) * FTM2V) / (2.0 * np.pi)
     return dict(frequencies=nu, eigenvectors=vec, eigenvalues=lam, n_unstable=int((nu < -zero_tol).sum()),
                 n_zero=int((np.abs(nu) <= zero_tol).sum()))
+
+
+def _modes_dict(lam, vec, zero_tol, status, sweeps, solver):
+    """the dict of modes() from eigenvalues (the same expression of lambda for the frequencies), with status, sweeps and solver"""
+    nu = np.sign(lam) * np.sqrt(np.abs(lam) * FTM2V) / (2.0 * np.pi)
+    return dict(frequencies=nu, eigenvectors=vec, eigenvalues=lam, n_unstable=int((nu < -zero_tol).sum()),
+                n_zero=int((np.abs(nu) <= zero_tol).sum()), status=capi.EIGH_STATUS[int(status)], sweeps=int(sweeps), solver=solver)
+
+
+def _host_modes(hessian, masses_of_atoms, project, zero_tol, vectors):
+    """a matrix the device does not take: modes(), in the dict of the device path"""
+    out = modes(hessian, masses_of_atoms, project, zero_tol)
+    out.update(eigenvectors=out["eigenvectors"] if vectors else None, status=capi.EIGH_STATUS[0], sweeps=0, solver="host")
+    return out
+
+
+def _hessian_modes_keys(found):
+    """what hessian_cells takes over from a dict of the solver: its status becomes modes_status"""
+    out = {k: found[k] for k in ("frequencies", "eigenvalues", "eigenvectors", "n_unstable", "n_zero", "solver")}
+    out["modes_status"] = found["status"]
+    return out
+
+
+def _eigh_device(torch, dev, st, sizes, first_t, A_t, roots, project, max_sweeps, vectors, status_t):
+    """What modes_cells and hessian_cells(modes=True) share: mtp_eigh_batched over the matrices [N_j, N_j] that lie on the device
+    at A_t + first_t[j] (sizes [nmat]), with `roots` (None, or per matrix the square roots of the masses, one per coordinate)
+    and per matrix `project`; a matrix with status_t[j] != 0 is skipped (status_t itself is not written).  The kernel takes one
+    projection flag a launch, so a batch that mixes both is solved in two, each skipping the other's matrices.  Nothing is
+    copied back here: the returned function read(zero_tol) does that (the copies wait for the stream) and gives, per matrix, the
+    dict of _modes_dict, or None where the device did not take the matrix (status "too large")."""
+    sizes, project = np.asarray(sizes, dtype=np.int64), np.asarray(project, dtype=bool)
+    nmat, w_first = len(sizes), np.concatenate([[0], np.cumsum(sizes)])
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    full = lambda count: torch.full((max(int(count), 1),), float("nan"), dtype=torch.float64, device=dev)
+    n_t, w_first_t = to(sizes.astype(np.int32)), to(w_first[:-1].astype(np.int64))
+    root_t = None if roots is None else to(np.concatenate(list(roots) + [np.ones(1)]).astype(np.float64))
+    W, V, info = full(w_first[-1]), (full((sizes ** 2).sum()) if vectors else None), full(2 * nmat).view(-1, 2)
+    done = status_t.clone()
+    for flag in (False, True):
+        pick = project == flag
+        if not pick.any():
+            continue
+        if pick.all():
+            capi.eigh_batched(n_t, first_t, A_t, w_first_t, root_t, flag, max_sweeps, W, V, info, done, stream=st)
+            continue
+        pick_t = to(pick)
+        mine = torch.where(pick_t, done, torch.full_like(done, -1))
+        capi.eigh_batched(n_t, first_t, A_t, w_first_t, root_t, flag, max_sweeps, W, V, info, mine, stream=st)
+        done = torch.where(pick_t, mine, done)
+
+    def read(zero_tol):
+        Wh, ih, sh = W.cpu().numpy(), info.cpu().numpy(), done.cpu().numpy()
+        Vh, at = (V.cpu().numpy(), first_t.cpu().numpy()) if vectors else (None, None)
+        out = []
+        for j, N in enumerate(sizes):
+            if sh[j] == 3:
+                out.append(None)
+                continue
+            lam = Wh[w_first[j]: w_first[j + 1]].copy()
+            vec = Vh[at[j]: at[j] + N * N].reshape(N, N).copy() if vectors else None
+            out.append(_modes_dict(lam, vec, zero_tol, sh[j], 0 if np.isnan(ih[j, 0]) else ih[j, 0], "device"))
+        return out
+
+    return read
+
+
+def modes_cells(hessians, masses_of_atoms=None, project_translations=True, zero_tol=1e-3, vectors=False, max_sweeps=30, device=None):
+    """modes() for a whole list of Hessians [3 m_j, 3 m_j] at once, solved on the device: mtp_eigh_batched, cyclic Jacobi in
+    LDS, one workgroup a matrix.  `masses_of_atoms`: None (the Hessians are mass-weighted already), one number, or one entry per
+    matrix with the meaning it has in modes() (None, one mass, or one per atom).  `project_translations`, `zero_tol`: as in
+    modes().  Wrong shapes and masses, and a Hessian that is not finite, raise before the device is touched.
+
+    Returns one dict per matrix with the keys of modes() -- frequencies from the same expression of the eigenvalues, eigenvectors
+    None unless `vectors` -- and status (capi.EIGH_STATUS: "not converged" after `max_sweeps` sweeps that all rotated, with the
+    state reached), sweeps, and solver: "device", or "host" for a matrix of more than capi.EIGH_MAX_N coordinates
+    (capi.EIGH_MAX_N_VECTORS with `vectors`), which goes through modes()."""
+    if not (float(zero_tol) >= 0.0):
+        raise ValueError("modes_cells: zero_tol must not be negative")
+    if int(max_sweeps) < 1:
+        raise ValueError("modes_cells: max_sweeps must be at least 1")
+    mats = [np.array(H, dtype=np.float64) for H in hessians]
+    if masses_of_atoms is None or np.isscalar(masses_of_atoms):
+        per = [masses_of_atoms] * len(mats)
+    elif len(masses_of_atoms) == len(mats):
+        per = list(masses_of_atoms)
+    else:
+        raise ValueError("modes_cells: masses_of_atoms is None, one number, or one entry per matrix (%d), got %d"
+                         % (len(mats), len(masses_of_atoms)))
+    roots = []
+    for j, (H, M) in enumerate(zip(mats, per)):
+        if H.ndim != 2 or H.shape[0] != H.shape[1] or H.shape[0] % 3:
+            raise ValueError("modes_cells: matrix %d: the Hessian must be [3 m, 3 m], got %r" % (j, H.shape))
+        if not np.isfinite(H).all():
+            raise ValueError("modes_cells: matrix %d: the Hessian is not finite (a failed configuration?)" % j)
+        m = H.shape[0] // 3
+        if M is None:
+            roots.append(np.ones(3 * m))
+            continue
+        M = np.asarray(M, dtype=np.float64).reshape(-1)
+        M = np.full(m, M[0]) if len(M) == 1 else M
+        if len(M) != m or not ((M > 0.0).all() and np.isfinite(M).all()):
+            raise ValueError("modes_cells: matrix %d: masses_of_atoms is one positive mass, or one per atom (%d)" % (j, m))
+        roots.append(np.repeat(np.sqrt(M), 3))
+    if not mats:
+        return []
+    import torch
+    dev = device or torch.device("cuda:0")
+    st = _torch_stream(dev)
+    sizes = np.array([len(H) for H in mats], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(sizes ** 2)])
+    A_t = torch.from_numpy(np.concatenate([H.reshape(-1) for H in mats] + [np.zeros(1)])).to(dev)
+    first_t = torch.from_numpy(first[:-1].astype(np.int64)).to(dev)
+    status_t = torch.zeros(len(mats), dtype=torch.int32, device=dev)
+    weighted = any(M is not None for M in per)
+    found = _eigh_device(torch, dev, st, sizes, first_t, A_t, roots if weighted else None, np.full(len(mats), bool(project_translations)),
+                         int(max_sweeps), bool(vectors), status_t)(zero_tol)
+    return [_host_modes(mats[j], per[j], bool(project_translations), zero_tol, vectors) if f is None else f
+            for j, f in enumerate(found)]
 
 
 def vineyard_prefactor(freq_min, freq_saddle, zero_tol=1e-3):

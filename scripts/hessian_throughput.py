@@ -2,14 +2,16 @@
 """Hessians per second of md.hessian_cells against what a user could do without it -- one md.evaluate_cells call per
 displacement over explicitly displaced copies of all configurations, with the difference quotients and the symmetrisation (the
 assembly of tests/_hess.py, vectorised over equal configurations) in numpy -- and the time md.modes then takes on the host
-for the same Hessians, so that a device eigen-solver can be decided on a number.
+for the same Hessians, beside what the device eigen-solver takes for them: md.hessian_cells(modes=True), which solves inside the
+pass, and md.modes_cells on the Hessians handed back (the copy to the device included).
 
 Workload: jitters (0.05 A) of the 16-atom bcc cell (2 x 2 x 2 cubic) of scripts/relax_throughput.py, W_L16.mtp (level 16),
 h = 0.01 A, all atoms: 6 x 16 + 1 = 97 force calls a pass.  Each leg runs in a fresh child process under its own `timeout`,
 warms up with a run of the same shapes, then times `--windows` windows with a host clock around work that ends in a device
 synchronise (the modes leg is host work alone, on Hessians it computes first); a leg that fails ends the run and nothing is
 tried again.  The hessian leg also checks itself at the timed size against the per-call loop, within the force parity bound
-over the step.  The parent writes the rates (median window) to profiles/hessian_throughput.json.
+over the step; the modes_device leg checks both its paths at the timed size against md.modes on the same Hessians, every
+eigenvalue within 8 N eps |D|_F.  The parent writes the rates (median window) to profiles/hessian_throughput.json.
 
     python scripts/hessian_throughput.py                  # all legs, writes the profile
     python scripts/hessian_throughput.py --leg hessian    # one leg in this process, prints its JSON line
@@ -62,12 +64,12 @@ def host_loop(ctx, configs):
 def run_leg(args):
     import torch
     from lammps_mtp_kokkos_amd import capi
-    from lammps_mtp_kokkos_amd.md import hessian_cells, modes
+    from lammps_mtp_kokkos_amd.md import hessian_cells, modes, modes_cells
     assert torch.cuda.is_available(), "this measurement needs the MI355X"
     ctx = capi.Context(capi.Potential(os.path.join(ROOT, "potentials", POTENTIAL)), 0)
     configs = workload(args.configs)
     kw = dict(h=H_STEP, masses=MASS, list_cutoff=7.0)
-    checks = {}
+    checks, more = {}, {}
 
     def device():
         res = hessian_cells(ctx, configs, **kw)
@@ -86,6 +88,34 @@ def run_leg(args):
         once = lambda: float(sum(r["hessian"].trace() for r in device()))
     elif args.leg == "percall":
         once = lambda: float(np.trace(host_loop(ctx, configs)[0], axis1=1, axis2=2).sum())
+    elif args.leg == "modes_device":
+        masses = np.full(ATOMS, MASS)
+        inside = lambda: hessian_cells(ctx, configs, modes=True, **kw)
+        got = inside()
+        handed = [r["hessian"] for r in got]
+        after = lambda: modes_cells(handed, [masses] * len(handed))
+        want = [modes(H, masses) for H in handed]
+        worst = 0.0
+        for found in (got, after()):
+            for r, w in zip(found, want):
+                assert r["solver"] == "device" and r.get("modes_status", r["status"]) == "ok", r["solver"]
+                bound = 8.0 * len(w["eigenvalues"]) * 2.0 ** -53 * float(np.sqrt((w["eigenvalues"] ** 2).sum()))
+                worst = max(worst, float(np.abs(r["eigenvalues"] - w["eigenvalues"]).max()) / bound)
+                assert r["n_unstable"] == w["n_unstable"] and r["n_zero"] == w["n_zero"]
+        assert worst <= 1.0, worst
+        checks = dict(worst_eigenvalue_difference_over_bound=worst, unstable_modes=int(sum(r["n_unstable"] for r in got)),
+                      zero_modes=int(sum(r["n_zero"] for r in got)))
+        once = lambda: float(sum(r["frequencies"].sum() for r in inside()))
+        alone = lambda: float(sum(r["frequencies"].sum() for r in after()))
+        alone()
+        windows = []
+        for _ in range(args.windows):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            alone()
+            torch.cuda.synchronize()
+            windows.append(time.perf_counter() - t0)
+        more = dict(seconds_per_window_modes_cells=windows)
     else:
         got = device()
         masses = np.full(ATOMS, MASS)
@@ -107,12 +137,12 @@ def run_leg(args):
     print(json.dumps(dict(leg=args.leg, configs=args.configs, atoms=ATOMS, force_calls_per_pass=CALLS, potential=POTENTIAL,
                           seconds_per_window=windows, hessians_per_second=args.configs / t,
                           configuration_evaluations_per_second=None if args.leg == "modes" else args.configs * CALLS / t,
-                          checksum=check, **checks)))
+                          checksum=check, **checks, **more)))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=["percall", "hessian", "modes"], default=None)
+    ap.add_argument("--leg", choices=["percall", "hessian", "modes", "modes_device"], default=None)
     ap.add_argument("--configs", type=int, default=1024)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=240, help="seconds, per leg")
@@ -121,7 +151,7 @@ def main():
     if args.leg:
         return run_leg(args)
     legs = {}
-    for leg in ("percall", "hessian", "modes"):
+    for leg in ("percall", "hessian", "modes", "modes_device"):
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--leg", leg,
                "--configs", str(args.configs), "--windows", str(args.windows)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
@@ -138,7 +168,13 @@ def main():
                   ratio_to_evaluate_cells_per_displacement=t["percall"] / t["hessian"],
                   modes_on_the_host_hessians_per_second=legs["modes"]["hessians_per_second"],
                   seconds_hessian_cells=t["hessian"], seconds_modes_on_the_host=t["modes"],
-                  modes_share_of_hessian_plus_modes=t["modes"] / (t["hessian"] + t["modes"]), legs=legs)
+                  modes_share_of_hessian_plus_modes=t["modes"] / (t["hessian"] + t["modes"]),
+                  seconds_hessian_cells_with_modes=t["modes_device"],
+                  seconds_modes_on_the_device=max(t["modes_device"] - t["hessian"], 0.0),
+                  seconds_modes_cells=float(np.median(legs["modes_device"]["seconds_per_window_modes_cells"])),
+                  device_modes_share_of_hessian_plus_modes=max(t["modes_device"] - t["hessian"], 0.0) / t["modes_device"],
+                  modes_host_over_modes_cells=t["modes"] / float(np.median(legs["modes_device"]["seconds_per_window_modes_cells"])),
+                  legs=legs)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
